@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of the IndustrialEnv.step() hot path on MI355X.
 
-Contract (driver):  python bench.py --gpus N --steps K --warmup W
+Contract (driver):  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  A plain run times the headline only: set-up, --settle seconds of load on the workload's twin, W warm-up and K timed
+  launches, the tally exchange, the outputs (--dump-outputs) and the result line.  --full adds every secondary record
+  and check listed below.  --dump-outputs DIR writes what the last timed launch returned (dump_outputs): the twin (a
+  second env handle over the same ring and output buffers) carries the settle load, so the timed handle starts from its
+  initial state and the same arguments give the same files.
   N > 1: one rank per GPU (RANK/LOCAL_RANK/WORLD_SIZE from torch.distributed.run).  Started WITHOUT a launcher,
   `bench.py --gpus N` starts its own N ranks (a child `python -m torch.distributed.run ... bench.py <same args>`,
   before this process has imported torch or touched the GPU), relays rank 0's JSON line, checks that the line
@@ -28,12 +33,13 @@ Modes (same arithmetic, bit-identical results -- tests/test_gpu_parity.py):
   graph / eager      step API: one step-kernel launch per env.step (state round-trips HBM),
                      --plan-steps of them replayed from one hipGraph / launched one by one.
 
-One JSON line on rank 0: metric/value/... + "roofline" + "cpu_baseline" (+ "parity", "step_api",
+One JSON line on rank 0: metric/value/... + "roofline" (+ with --full: "cpu_baseline", "parity", "step_api",
 "powergrid" = BASELINE configs[2] per GPU, i.e. configs[4] when N = 8, "robotassembly" = the third reference env at the
-same batch, "mixed" = configs[3], "single_env" = configs[0]); every timed record carries `rank_times.clock` (the shader clock
+same batch, "mixed" = configs[3], "single_env" = configs[0], the roofline's brackets); every timed record carries `rank_times.clock` (the shader clock
 held over the timed launches, in-kernel counters) and `rank_times.dpm` (sclk / mclk / power while its settle launches ran).
 """
 import argparse
+import copy
 import json
 import os
 import sys
@@ -91,7 +97,7 @@ class Workload:
 
     def __init__(self, ni, torch, key, B, device, rank, mode, P, ring_len, outputs, traj_layout, seed=0x5EED, ring_layout="rows"):
         self.ni, self.torch, self.key, self.B, self.mode, self.P = ni, torch, key, B, mode, P
-        self.outputs = outputs
+        self.outputs, self.seed, self.rank = outputs, seed, rank
         # "aos": the action ring as [R, B, A] (row-major slots: a policy's batched output; nig_rollout's ld_act == 0) -- rollout mode only
         self.ring_aos = ring_layout == "aos" and mode == "rollout"
         env = ni.make_batched(ENVS[key], B, device=device, seed=seed, env_index0=rank * B, autoreset=True, tally=True)
@@ -116,6 +122,21 @@ class Workload:
                              else torch.empty(rows, self.S, env.ld, dtype=torch.float32, device=device).expand(P, self.S, env.ld))
         self.plan = env.make_plan(P, self.ring, env.reward, env.flags) if mode == "graph" else None
         self.rings, self._turn = [self.ring], 0
+
+    def twin(self):
+        """A second env handle, in its initial state, over THIS workload's action ring(s) and output buffers (only the
+        handle's own workspace -- state, counters, tallies -- is new).  It carries the settle load of timed(): the ring
+        and output buffers the timed launches use are warmed exactly as by settling on this workload itself, while this
+        workload's handle still enters its W + K launches in the state it was created in (--dump-outputs: the same
+        outputs every run).  Every launch writes all P output rows of every lane, so nothing of the twin's remains
+        in the outputs after this workload's first launch."""
+        t = copy.copy(self)
+        t.env = self.ni.make_batched(ENVS[self.key], self.B, device=self.env.device, seed=self.seed, env_index0=self.rank * self.B,
+                                     autoreset=True, tally=True)
+        t.env.reset()
+        t.plan = t.env.make_plan(self.P, self.ring, t.env.reward, t.env.flags) if self.mode == "graph" else None
+        t.rings, t._turn = list(self.rings), 0
+        return t
 
     def use_big_ring(self, min_bytes):
         """Action rings whose union exceeds `min_bytes`: a launch reads slots 0..P-1 of ITS ring only (step k reads slot
@@ -271,9 +292,11 @@ def settle(torch, wl, seconds, stats=None):
     return n
 
 
-def timed(torch, dist, world, comm_dev, wl, K, W, settle_s=0.0, stats=None):
+def timed(torch, dist, world, comm_dev, wl, K, W, settle_s=0.0, stats=None, settle_wl=None):
     """[settle_s of untimed load,] W untimed + exactly K timed launches, bracketed by barrier + synchronize on both
     sides; HIP events on the launch stream around the same region.  Returns (wall s, device ms): max over ranks.
+    `settle_wl` (optional): wl.twin(), which carries the settle load instead (over wl's own ring and output buffers), so that
+    wl's handle enters its W + K launches in the state it was created in, whatever number of launches the settle took.
 
     The timed interval is THE SAME SET OF OPERATIONS at every world size: K launches + the stream synchronisation
     behind them.  The clock stops after the synchronisation and BEFORE the closing barrier (the barrier still brackets
@@ -283,11 +306,11 @@ def timed(torch, dist, world, comm_dev, wl, K, W, settle_s=0.0, stats=None):
     rank's own wall / device time: wall_min / wall_median / wall_max (s), launch_us per rank (HIP events)."""
     gpu = torch.cuda.is_available()          # False only in the CPU control-flow rehearsal (NIG_BENCH_REHEARSE=cpu)
     sync = torch.cuda.synchronize if gpu else (lambda: None)
-    n_settle = settle(torch, wl, settle_s, stats) if gpu else 0
+    n_settle = settle(torch, settle_wl or wl, settle_s, stats) if gpu else 0
     for _ in range(W):
         wl.launch()
     sync()
-    if stats is not None:      # launches of this workload so far, in order: profiles/phase_stats.py splits a kernel trace by them
+    if stats is not None:      # launches of this workload's kernel so far, in order (the settle ones on settle_wl when given): profiles/phase_stats.py splits a kernel trace by them
         stats["phases"] = [{"name": "settle", "launches": n_settle}, {"name": "warmup", "launches": W}, {"name": "timed", "launches": K}]
     ev0 = ev1 = None
     probe = _PROBE if (gpu and stats is not None) else None
@@ -505,6 +528,48 @@ def gathered_partial(world, comm_dev, ni, partial):
     return total, {"ranks": int(parts.shape[0]), "episodes_per_rank": per_rank_eps, "ok": True}
 
 
+DUMP_BYTES = 60 * 10**6       # --dump-outputs: the written lanes' outputs (under 64 MB with the tally and the .npy headers)
+DUMP_SEED = 0x5EED
+
+
+def dump_lanes(B, bytes_per_lane, budget=DUMP_BYTES):
+    """Lanes --dump-outputs writes: all of them when their outputs fit the budget, else a fixed, seeded sample (sorted)."""
+    import numpy as np
+    n = min(B, budget // bytes_per_lane)
+    if n < 1:
+        raise SystemExit(f"--dump-outputs: one lane's outputs take {bytes_per_lane} bytes, more than {budget}: use fewer --plan-steps")
+    return np.arange(B) if n == B else np.sort(np.random.default_rng(DUMP_SEED).choice(B, n, replace=False))
+
+
+def dump_outputs(wl, total, out_dir):
+    """--dump-outputs: what the timed path returned in its last bench step, for comparing two builds output for output.
+    Rollout mode: reward [P, n], flags [P, n] (the int32 flag word, exact in float64), obs [P, n, S] (outputs full) of
+    the last launch; graph / eager: reward [1, n] and flags [1, n] of its last env.step.  Always the state after it,
+    state [n, S], and the episode tally over every rank, tally [T_ROWS] (float64).  n lanes: dump_lanes."""
+    import numpy as np
+    torch, B, S, env = wl.torch, wl.B, wl.S, wl.env
+    if wl.mode == "rollout":
+        rew, fl = (None, None) if wl.rew is None else (wl.rew[:, :B], wl.fl[:, :B])
+        obs = wl.traj
+        if obs is not None and obs.shape[1:] != (B, S):                 # [P, S, ld] rows -> [P, B, S]
+            obs = obs[:, :, :B].permute(0, 2, 1)
+    else:
+        rew, fl, obs = env.reward[None], env.flags[None], None
+    rows = 0 if rew is None else rew.shape[0]
+    lanes = dump_lanes(B, rows * (4 + 8 + (4 * S if obs is not None else 0)) + 4 * S)
+    idx = torch.as_tensor(lanes, device=env.device)
+    arrays = {"state": env.obs.index_select(0, idx).to(torch.float32), "tally": torch.as_tensor(np.asarray(total, dtype=np.float64))}
+    if rew is not None:
+        arrays["reward"] = rew.index_select(1, idx).to(torch.float32)
+        arrays["flags"] = fl.index_select(1, idx).to(torch.float64)
+    if obs is not None:
+        arrays["obs"] = obs.index_select(1, idx).to(torch.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+    print(f"bench.py: wrote {', '.join(sorted(arrays))} of {lanes.size} of {B} lanes to {out_dir}", file=sys.stderr)
+
+
 def parity_probe_gpu(ni, torch, key, B, device, seed=0x5EED, Tp=256):
     """The workload's first Tp steps on the device; compared with the CPU oracle, bit for bit, by parity_probe_cpu."""
     L0 = ni._lib
@@ -693,7 +758,7 @@ def pin_rank(local_rank, local_world):
             share = len(allowed) // local_world
             mine = allowed[local_rank * share:(local_rank + 1) * share]
         os.sched_setaffinity(0, mine)
-        return {"pinned": True, "how": how, "cpus": len(mine), "first_cpu": mine[0], "last_cpu": mine[-1]}
+        return {"pinned": True, "how": how, "cpus": len(mine), "first_cpu": mine[0], "last_cpu": mine[-1], "cpu_set": list(mine)}
     except Exception as e:                                   # affinity is an optimisation, never a reason to fail
         return {"pinned": False, "reason": repr(e)}
 
@@ -881,6 +946,13 @@ def parse_args(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=4.0, help="wall budget of the all-core CPU baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement and check (parity probe, single env, step API, PowerGrid, "
+                         "RobotAssembly, mixed batch, the headline's brackets, fast-mode statistics, CPU baseline; per-env "
+                         "rates of --env mixed); the --no-* options above skip single ones of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step to DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all: a fixed, seeded sample of lanes when larger)")
     return ap.parse_args(argv)
 
 
@@ -888,6 +960,10 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs and (args.env == "mixed" or os.environ.get("NIG_BENCH_REHEARSE") == "cpu"):
+        raise SystemExit("--dump-outputs: only for the single-env device workload (not --env mixed, not NIG_BENCH_REHEARSE=cpu)")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher: this process becomes the launcher (nothing below runs here; no torch, no HIP call so far)
         return spawn_ranks(args.gpus, sys.argv[1:])
@@ -953,24 +1029,25 @@ def main():
         return bench_mixed(args, ni, torch, dist, device, comm_dev, world, rank)
     key = args.env
     B = args.batch or BASELINE_BATCH[key]
-    P, K, W = max(1, args.plan_steps), max(1, args.steps), max(0, args.warmup)
+    P, K, W = max(1, args.plan_steps), args.steps, max(0, args.warmup)
 
-    # Order of the GPU work: the secondary measurements run FIRST and the headline LAST, right behind them, so the
+    # Order of the GPU work (--full): the secondary measurements run FIRST and the headline LAST, right behind them, so the
     # headline's W warm-up launches start on a chip that is already at its sustained clocks (a cold start costs the
     # first ~10 ms of launches ~15 %; with the driver's --steps 20 the whole timed region is 5 ms).  The CPU halves
-    # of the parity probe and the CPU baseline run after all GPU timing.
+    # of the parity probe and the CPU baseline run after all GPU timing.  Without --full only the headline runs.
+    full = args.full
     parity_gpu = None
-    if rank == 0 and not args.no_parity:
+    if full and rank == 0 and not args.no_parity:
         parity_gpu = parity_probe_gpu(ni, torch, key, B, device)
 
     # ---- BASELINE configs[0]: one env, 1000 steps, reset on done (the plumbing configuration; ~50 ms)
     single_env = None
-    if rank == 0 and key == "cr" and not args.no_single_env:
+    if full and rank == 0 and key == "cr" and not args.no_single_env:
         single_env = measure_single_env(ni)
 
     # ---- secondary: the step API (one kernel launch per env.step, hipGraph replay of P of them)
     step_api = None
-    if args.mode == "rollout" and not args.no_step_api:
+    if full and args.mode == "rollout" and not args.no_step_api:
         w2 = Workload(ni, torch, key, B, device, rank, "graph", P, min(args.ring, 64), args.outputs, args.traj)     # (a 64-slot ring: the step API's working set stays what it was)
         K2 = max(2, min(K, 8))
         sw, sd = timed(torch, dist, world, comm_dev, w2, K2, 1)
@@ -985,7 +1062,7 @@ def main():
 
     # ---- secondary: PowerGrid-v0, 262144 lanes per GPU (BASELINE configs[2]; configs[4] = this at N = 8)
     powergrid = None
-    if key == "cr" and args.mode == "rollout" and not args.no_powergrid:
+    if full and key == "cr" and args.mode == "rollout" and not args.no_powergrid:
         Bp = BASELINE_BATCH["pg"]
         # action ring of 34 slots = 285 MB: larger than the 256 MB Infinity Cache, so every action read of this record comes
         # from HBM and all 168 B per env-step are HBM-side bytes (roofline_of; a 16-slot ring sat inside the cache)
@@ -1021,7 +1098,7 @@ def main():
     # ---- secondary: RobotAssembly-v0, 262144 lanes per GPU: the third reference env (robot_assembly.py:139-188, SURVEY rows
     # a15-a19) has no BASELINE config of its own; timed at PowerGrid's batch so the line carries all three (VERDICT r04 next #6b)
     robotassembly = None
-    if key == "cr" and args.mode == "rollout" and not args.no_robotassembly:
+    if full and key == "cr" and args.mode == "rollout" and not args.no_robotassembly:
         Br = BASELINE_BATCH["ra"]
         # 40 ring slots = 294 MB: larger than the Infinity Cache, every action read is an HBM read (as for PowerGrid above)
         w4 = Workload(ni, torch, "ra", Br, device, rank, "rollout", P, 40, args.outputs, args.traj)
@@ -1048,17 +1125,25 @@ def main():
 
     # ---- secondary: all 7 envs mixed-batch, 1 048 576 lanes per GPU (BASELINE configs[3]), ONE fused launch
     mixed = None
-    if key == "cr" and args.mode == "rollout" and not args.no_mixed:
+    if full and key == "cr" and args.mode == "rollout" and not args.no_mixed:
         mixed = measure_mixed(args, ni, torch, dist, device, comm_dev, world, rank, 1048576, max(2, min(K, 8)), 2,
                               args.settle, per_env_rates=False)
 
-    # ---- headline: workload resident in HBM before the timed region
+    # ---- headline: workload resident in HBM before the timed region; the settle load runs on its twin (Workload.twin: a
+    # second handle over the same buffers), so the W + K launches start from the workload's initial state and a run
+    # computes the same outputs every time (--dump-outputs)
     wl = Workload(ni, torch, key, B, device, rank, args.mode, P, args.ring, args.outputs, args.traj, ring_layout=args.ring_layout)
+    twin = wl.twin() if args.settle > 0 else None
     rank_times = {}
-    wall, dev_ms = timed(torch, dist, world, comm_dev, wl, K, W, args.settle, stats=rank_times)
+    wall, dev_ms = timed(torch, dist, world, comm_dev, wl, K, W, args.settle, stats=rank_times, settle_wl=twin)
+    if twin is not None:
+        twin.close()
+        del twin
     roof = roofline_of(wl, K, dev_ms)
     total, tally_check = gathered_tally(torch, dist, world, comm_dev, wl)
-    if args.mode == "rollout" and not args.no_brackets:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl, total, args.dump_outputs)
+    if full and args.mode == "rollout" and not args.no_brackets:
         roof.update(honest_brackets(torch, wl, K, roof, args.settle, phases=rank_times.get("phases")))
 
     if args.calibrate:   # known-size dword-per-lane copies for the PMC byte calibration (profiles/)
@@ -1071,7 +1156,7 @@ def main():
     del wl
     parity = parity_probe_cpu(parity_gpu, key, B) if parity_gpu is not None else None
     fast_stats = None
-    if rank == 0 and key in ENVS and args.mode == "rollout":     # untimed, after every timed region: a few launches with fresh actions
+    if full and rank == 0 and key in ENVS and args.mode == "rollout":     # untimed, after every timed region: a few launches with fresh actions
         fast_stats = fast_mode_statistics(ni, key, total, B, 0 if args.no_parity else (2 if key == "cr" else 1), device)
 
     if rank == 0:
@@ -1109,9 +1194,9 @@ def main():
             out["robotassembly"] = robotassembly
         if mixed is not None:
             out["mixed"] = mixed
-        if parity is not None or key in ENVS:
+        if full and (parity is not None or key in ENVS):
             out["parity"] = dict(parity or {}, fast_mode_statistics=fast_stats)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(key, B, args.cpu_seconds)
         print(json.dumps(out))
     if grouped(dist):
@@ -1121,7 +1206,7 @@ def main():
 def rehearse_cpu(args, ni, torch, dist, comm_dev, world, rank, affinity):
     """Control flow of an N-rank run on a box without a GPU (tests/test_host_logic.py).  No measurement: value null."""
     wl = RehearsalWorkload(ni, torch, rank)
-    K, W = max(1, args.steps), max(0, args.warmup)
+    K, W = args.steps, max(0, args.warmup)
     rank_times = {}
     wall, _ = timed(torch, dist, world, comm_dev, wl, K, W, stats=rank_times)
     total, check = gathered_tally(torch, dist, world, comm_dev, wl)
@@ -1241,8 +1326,8 @@ def measure_mixed(args, ni, torch, dist, device, comm_dev, world, rank, B, K, W,
 def bench_mixed(args, ni, torch, dist, device, comm_dev, world, rank):
     """--env mixed: BASELINE config 4 as the headline of its own line."""
     B = args.batch or 1048576
-    K, W = max(1, args.steps), max(0, args.warmup)
-    rec = measure_mixed(args, ni, torch, dist, device, comm_dev, world, rank, B, K, W, args.settle)
+    K, W = args.steps, max(0, args.warmup)
+    rec = measure_mixed(args, ni, torch, dist, device, comm_dev, world, rank, B, K, W, args.settle, per_env_rates=args.full)
     if args.calibrate:   # known-size dword-per-lane copies for the PMC byte calibration (profiles/pmc_to_traffic.py): 20 x 12 rows x 65 536 lanes
         cenv = ni.make_batched("ChemicalReactor-v0", 65536, device=device)
         cal = torch.empty(12, cenv.ld, dtype=torch.float32, device=device)

@@ -19,6 +19,7 @@ Fixture families:
   cr_info.npz   ChemicalReactor's reset / step info dicts (_get_safety_info margins) along a seeded run          [arg: info]
   reference_stats.npz  per-episode outcomes of the reference's own measurement loop (performance_benchmark.py:106-133)
                 under uniform float32 actions and the reference's own np.random draws, thousands of episodes per env  [arg: stats]
+  live_reference.npz  reset / step tuples of the reference under random actions, some beyond the clip bounds         [arg: live]
 Reference semantics pinned: NumPy 2.2.6; float32 actions (G1-G4) and float64 actions (G5, G6, datasets).
 """
 import json
@@ -603,7 +604,7 @@ def main():
         json.dump(meta, f, indent=1, sort_keys=True)
 
 
-if __name__ == "__main__" and not (len(sys.argv) > 1 and sys.argv[1] in ("datasets", "g5", "g6", "agents", "laws", "info", "stats")):
+if __name__ == "__main__" and not (len(sys.argv) > 1 and sys.argv[1] in ("datasets", "g5", "g6", "agents", "laws", "info", "stats", "live")):
     main()
 
 
@@ -936,3 +937,44 @@ def gen_stats():
 
 if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "stats":
     gen_stats()
+
+
+def gen_live():
+    """Three short episodes per env (at most 60 steps each) of the reference under float32 actions drawn uniformly from
+    [-1.2, 1.2] (default_rng(7)), its noise drawn through NoiseTap(11): per reset the draws and the observation, per step
+    the pre-step state, action, draws, observation, reward, terminated / truncated and the violation count.  The draws
+    of reset r are reset_noise[reset_off[r]:reset_off[r + 1]], those of step i step_noise[step_off[i]:step_off[i + 1]]."""
+    rng = np.random.default_rng(7)
+    utils = load_reference()
+    out = {}
+    for key, name in ENVS.items():
+        env = utils.make(name)
+        rows = {k: [] for k in ("reset_obs", "reset_noise", "pre", "action", "step_noise", "obs", "reward", "te", "tr",
+                                "viol", "t")}
+        with NoiseTap(11) as tap:
+            for ep in range(3):
+                obs, _ = env.reset()
+                rows["reset_noise"].append(tap.take()); rows["reset_obs"].append(obs.copy())
+                done, t = False, 0
+                while not done and t < 60:
+                    a = rng.uniform(-1.2, 1.2, env.action_dim).astype(f32)
+                    pre = env.state.copy()
+                    obs, r, te, tr, info = env.step(a)
+                    for k, v in (("pre", pre), ("action", a), ("step_noise", tap.take()), ("obs", obs.copy()), ("reward", float(r)),
+                                 ("te", bool(te)), ("tr", bool(tr)), ("viol", info["safety_metrics"].violation_count), ("t", t)):
+                        rows[k].append(v)
+                    done = te or tr; t += 1
+        off = lambda parts: np.cumsum([0] + [p.size for p in parts]).astype(np.int64)
+        out.update({f"{key}_reset_obs": np.asarray(rows["reset_obs"], dtype=f32),
+                    f"{key}_reset_noise": np.concatenate(rows["reset_noise"]), f"{key}_reset_off": off(rows["reset_noise"]),
+                    f"{key}_pre": np.asarray(rows["pre"], dtype=f32), f"{key}_action": np.asarray(rows["action"], dtype=f32),
+                    f"{key}_step_noise": np.concatenate(rows["step_noise"]), f"{key}_step_off": off(rows["step_noise"]),
+                    f"{key}_obs": np.asarray(rows["obs"], dtype=f32), f"{key}_reward": np.asarray(rows["reward"], dtype=np.float64),
+                    f"{key}_te": np.asarray(rows["te"], dtype=np.uint8), f"{key}_tr": np.asarray(rows["tr"], dtype=np.uint8),
+                    f"{key}_viol": np.asarray(rows["viol"], dtype=np.int32), f"{key}_t": np.asarray(rows["t"], dtype=np.int32)})
+        print(key, "resets", len(rows["reset_obs"]), "steps", len(rows["t"]))
+    np.savez_compressed(os.path.join(OUT, "live_reference.npz"), **out)
+
+
+if __name__ == "__main__" and len(sys.argv) > 1 and sys.argv[1] == "live":
+    gen_live()

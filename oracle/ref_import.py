@@ -2,8 +2,7 @@
 
 This container only: /root/reference does not exist on the GPU box, so nothing in
 `tests -m gpu`, `__graft_entry__.smoke()` or `bench.py` may import this module.
-It is used by `oracle/gen_golden.py` (fixture generation) and by the not-gpu test
-that cross-checks the C restatement against the live reference when it is present.
+It is used by `oracle/gen_golden.py` (fixture generation) only; no test imports it.
 
 The reference package's root `__init__` pulls jax/flax/optax (absent here), but its
 env hot path is NumPy-only (SURVEY.md finding 1).  We therefore

@@ -23,7 +23,7 @@ from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
-BENCH_ARGS = ["--gpus", "1", "--steps", "40", "--warmup", "8", "--no-step-api", "--no-cpu-baseline", "--no-parity",
+BENCH_ARGS = ["--gpus", "1", "--steps", "40", "--warmup", "8", "--full", "--no-step-api", "--no-cpu-baseline", "--no-parity",
               "--no-mixed", "--no-robotassembly", "--no-brackets", "--no-single-env"]
 
 

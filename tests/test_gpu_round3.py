@@ -32,7 +32,7 @@ def test_bench_two_ranks_on_one_gpu():
         env.pop(k, None)
     env["NIG_BENCH_REHEARSE"] = "1"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "8192", "--steps", "2",
-                        "--warmup", "1", "--plan-steps", "250", "--settle", "0", "--no-step-api", "--no-cpu-baseline",
+                        "--warmup", "1", "--plan-steps", "250", "--settle", "0", "--full", "--no-step-api", "--no-cpu-baseline",
                         "--no-parity", "--no-mixed", "--no-robotassembly", "--no-brackets"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     rec = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])

@@ -377,8 +377,8 @@ def test_bench_launches_and_verifies_its_own_ranks():
     assert rec["ms_per_step"] == pytest.approx(rt["wall_max_s"] * 1e3 / 3)         # the line's time IS the slowest rank's interval
     aff = rec["scale"]["rank_affinity"]
     assert len(aff) == 2 and all("pinned" in a for a in aff)
-    if all(a["pinned"] for a in aff):                                               # disjoint CPU shares
-        assert aff[0]["last_cpu"] < aff[1]["first_cpu"] or aff[1]["last_cpu"] < aff[0]["first_cpu"]
+    if all(a["pinned"] for a in aff):          # disjoint CPU shares (a NUMA node's CPU list need not be one range: 0-63,128-191)
+        assert not set(aff[0]["cpu_set"]) & set(aff[1]["cpu_set"]) and all(len(a["cpu_set"]) == a["cpus"] for a in aff)
     # N = 1 and N = 2 time the same set of operations: K launches + the stream synchronisation, no collective inside
     p1, rec1 = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1"], {"NIG_BENCH_REHEARSE": "cpu"})
     assert p1.returncode == 0, p1.stderr[-2000:]
@@ -518,6 +518,25 @@ def test_bench_refuses_a_world_that_differs_from_gpus():
     assert p.returncode != 0 and rec is None
 
 
+def test_bench_plain_run_options_and_output_sample():
+    """A plain run is the headline only (--full off by default); --steps below 1 and --dump-outputs without a device
+    workload are refused, not bent into something else; the dumped lanes are all of them when they fit, else the same
+    seeded, sorted sample every time, within the byte budget."""
+    import bench
+    args = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert args.full is False and args.dump_outputs is None and args.steps == 7
+    assert bench.parse_args(["--full", "--dump-outputs", "out"]).full and bench.parse_args(["--dump-outputs", "out"]).dump_outputs == "out"
+    assert np.array_equal(bench.dump_lanes(2048, 15048), np.arange(2048))
+    a, b = bench.dump_lanes(65536, 15048), bench.dump_lanes(65536, 15048)
+    assert np.array_equal(a, b) and np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < 65536
+    assert a.size * 15048 <= bench.DUMP_BYTES < a.size * 15048 + 15048
+    with pytest.raises(SystemExit):
+        bench.dump_lanes(8, bench.DUMP_BYTES + 1)
+    for argv in (["--steps", "0"], ["--dump-outputs", "out"]):
+        p, rec = _run_bench(["--gpus", "1"] + argv, {"NIG_BENCH_REHEARSE": "cpu"})
+        assert p.returncode != 0 and rec is None, argv
+
+
 def test_oracle_under_sanitizers():
     """SURVEY section 5 / VERDICT r02: the oracle's C restatement built with -fsanitize=address,undefined and the
     golden-vector tests (every entry point: step, step64, reset, rollouts, policies, the MLP actor, the generator) run
@@ -527,7 +546,8 @@ def test_oracle_under_sanitizers():
     asan = subprocess.run(["gcc", "-print-file-name=libasan.so"], capture_output=True, text=True).stdout.strip()
     if not os.path.isabs(asan) or not os.path.exists(asan):
         pytest.skip("no libasan in this toolchain")
-    env = dict(os.environ, NIG_ORACLE_SANITIZE="1", LD_PRELOAD=asan,
+    preload = ":".join(p for p in (asan, os.environ.get("LD_PRELOAD", "")) if p)     # the runtime first; keep what is preloaded already
+    env = dict(os.environ, NIG_ORACLE_SANITIZE="1", LD_PRELOAD=preload,
                ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1", OMP_NUM_THREADS="2")
     p = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "not gpu", "-p", "no:cacheprovider",
                         os.path.join(ROOT, "tests", "test_oracle_golden.py"), os.path.join(ROOT, "tests", "test_advanced_envs.py"),
