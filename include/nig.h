@@ -68,6 +68,7 @@ extern "C" {
 #define NIG_FLAG_INACTIVE 0x800u        /* lane was already done (no auto-reset): untouched  */
 #define NIG_FLAG_VIOL3 0x1000u          /* 4th safety condition violated (Advanced envs)     */
 #define NIG_FLAG_NVIOL_HI 0x2000u       /* adds 4 to the violation count field (Advanced envs) */
+#define NIG_FLAG_SHIELDED 0x4000u       /* nig_rollout_mlp_safe: the safety critic halved the action */
 #define NIG_FLAG_STEP_SHIFT 16          /* bits 16-31: current_step after this call          */
 
 /* per-lane counter word kept by the library */
@@ -437,6 +438,30 @@ int nig_set_mlp_policy(nig_handle *h, int32_t hidden, const float *W1, const flo
 int nig_rollout_mlp(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out,
                     int64_t out_stride, float *obs_out, int64_t obs_step_stride,
                     float *act_out, int64_t ld_act, int64_t act_step_stride, void *stream);
+
+/*
+ * Safety-critic shield of the reference agents' predict_with_safety (agents/cql.py, iql.py, td3bc.py):
+ * a = actor(s); p = sigmoid(critic([s, a])); the env receives a if p < threshold, a * 0.5 otherwise.
+ * The critic is a (S + A) -> 256 -> 256 -> 1 ReLU MLP (agents/networks.py SafetyCritic), evaluated after
+ * the actor in the same kernel by the same f32-MFMA scheme (its weights streamed through the same
+ * double-buffered LDS image; the one-row head on v_mfma_f32_4x4x1).
+ * Safety critic for the shielded MLP loop: C1 [S+A][hidden], c1 [hidden], C2 [hidden][hidden], c2,
+ * C3 [hidden][1], c3 [1]; row-major [in][out] (Flax Dense kernels); hidden must be 256.  The library
+ * keeps its own device copy; installing a new actor (nig_set_mlp_policy) keeps the critic.
+ */
+int nig_set_mlp_safety(nig_handle *h, int32_t hidden, const float *C1, const float *c1, const float *C2,
+                       const float *c2, const float *C3, const float *c3, float threshold, void *stream);
+
+/*
+ * As nig_rollout_mlp, with the shield: prob_out (optional) float [n_steps][>=B]: p of the UNshielded
+ * action, row k at prob_out + k*out_stride (live lanes only, like obs/act); act_out holds the action
+ * the env received; flags carry NIG_FLAG_SHIELDED on live steps whose action was halved.  The raw
+ * action is bit-identical to nig_rollout_mlp's.  NIG_ERR_INVALID without an actor or a critic,
+ * NIG_ERR_UNSUPPORTED for an env shape without the MFMA actor.
+ */
+int nig_rollout_mlp_safe(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out,
+                         int64_t out_stride, float *obs_out, int64_t obs_step_stride, float *act_out,
+                         int64_t ld_act, int64_t act_step_stride, float *prob_out, void *stream);
 
 /*
  * Host-buffer forms for SMALL batches -- the single-env drop-in classes (env.reset() / env.step()

@@ -401,9 +401,28 @@ class BatchedIndustrialEnv:
         (same outputs as rollout_policy)."""
         self.rollout_policy(n_steps, reward_out, flags_out, obs_out, act_out, _fn=self._L.nig_rollout_mlp)
 
+    def set_mlp_safety(self, weights, threshold: float):
+        """Install the reference agents' safety critic ((S+A)->256->256->1, ReLU, sigmoid) for rollout_mlp_safe():
+        weights = [(C1 [S+A,256], c1), (C2 [256,256], c2), (C3 [256,1], c3)], host arrays, [in, out].  The action
+        is halved unless p < threshold (the threshold is used as given).  Replacing the actor keeps the critic."""
+        W = [np.ascontiguousarray(np.asarray(x), dtype=np.float32) for pair in weights for x in pair]
+        D, Hd = self.state_dim + self.action_dim, 256
+        W[4] = W[4].reshape(-1, 1) if W[4].ndim == 1 else W[4]
+        assert [w.shape for w in W] == [(D, Hd), (Hd,), (Hd, Hd), (Hd,), (Hd, 1), (1,)], [w.shape for w in W]
+        with torch.cuda.device(self._dev_index):
+            _lib.check(self._L.nig_set_mlp_safety(self._h, Hd, *[w.ctypes.data_as(C.c_void_p) for w in W],
+                                                  float(threshold), self._stream()))
+
+    def rollout_mlp_safe(self, n_steps: int, reward_out=None, flags_out=None, obs_out=None, act_out=None, prob_out=None):
+        """rollout_mlp() with the safety-critic shield (predict_with_safety on the device): act_out holds the action the
+        env received; prob_out float32 [n_steps, >=B] the critic's p of the unshielded action (same row stride as
+        reward_out / flags_out); flags carry FLAG_SHIELDED where the action was halved."""
+        self.rollout_policy(n_steps, reward_out, flags_out, obs_out, act_out, _fn=self._L.nig_rollout_mlp_safe,
+                            _prob=prob_out)
+
     def rollout_policy(self, n_steps: int, reward_out: Optional[torch.Tensor] = None,
                        flags_out: Optional[torch.Tensor] = None, obs_out: Optional[torch.Tensor] = None,
-                       act_out: Optional[torch.Tensor] = None, _fn=None):
+                       act_out: Optional[torch.Tensor] = None, _fn=None, _prob=None):
         """n_steps closed-loop steps (action = installed policy(observation)) in ONE launch.
         obs_out: float32 contiguous [n_steps, B, S] (observation the policy acted on);
         act_out: float32 [n_steps, A, >=B]; reward_out / flags_out: [n_steps, >=B] or [B]."""
@@ -430,6 +449,11 @@ class BatchedIndustrialEnv:
             assert act_out.shape[0] >= n_steps and act_out.shape[1] == self.action_dim and act_out.shape[2] >= self.batch
             ap, lda, sa = C.c_void_p(act_out.data_ptr()), act_out.stride(1), act_out.stride(0)
         with torch.cuda.device(self._dev_index):
+            if _fn is self._L.nig_rollout_mlp_safe:
+                pp, ps = out(_prob, torch.float32)
+                assert pp is None or (rp is None and fp is None) or ps == (rs or fs), "prob_out shares the reward/flags row stride"
+                _lib.check(_fn(self._h, int(n_steps), rp, fp, rs or fs or ps, op, so, ap, lda, sa, pp, self._stream()))
+                return
             _lib.check((_fn or self._L.nig_rollout_policy)(self._h, int(n_steps), rp, fp, rs or fs, op, so, ap, lda, sa,
                                                            self._stream()))
 

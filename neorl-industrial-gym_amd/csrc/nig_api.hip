@@ -174,6 +174,8 @@ struct nig_handle {
     nig_policy pol_host;   // staging copy (must outlive the async H2D copy)
     bool has_policy;
     float *mlp_stream;     // device copy of the MFMA operand stream of the MLP actor (owned)
+    float *mlp_cstream;    // device copy of the MFMA operand stream of the safety critic (owned)
+    float mlp_threshold;   // shield threshold of nig_rollout_mlp_safe
     float *act32;          // nig_step64 on an env that takes float32 actions: the narrowed rows [A][ld] (owned, lazy)
     float *pid_mem;        // PID policies: per-lane integral / previous error, float [2*A][ld] (owned, lazy)
     bool may_hold_done;    // some lane may carry NIG_CTR_DONE although the handle auto-resets (see HF_MAY_HOLD_DONE)
@@ -354,7 +356,9 @@ extern "C" {
 // with at most four actions (ChemicalReactor, WaterTreatment) sums the head in the order of its v_mfma_f32_4x4x1 form (last-bit
 // differences in the action against 0.4.0; the oracle restates the new order).  New entry point: nig_clock_stamp.  A caller
 // workspace is refused only when positively identified as host / managed / foreign-device memory.
-const char *nig_version(void) { return "nig 0.5.0 (gfx950; generator nig-philox-v3)"; }
+// 0.6.0: nig_set_mlp_safety / nig_rollout_mlp_safe (the MFMA actor with the safety-critic shield) and NIG_FLAG_SHIELDED.  No
+// existing entry point's results changed.
+const char *nig_version(void) { return "nig 0.6.0 (gfx950; generator nig-philox-v3)"; }
 const char *nig_last_error(void) { return g_err; }
 
 int nig_tune(int32_t key, int64_t value)
@@ -498,7 +502,7 @@ int nig_create(int env, int64_t batch, int device, uint64_t seed, uint64_t env_i
     h->pol_dev = (nig_policy *)(h->ws + h->lay.bytes - POLICY_BYTES);
     h->t_dev = (uint32_t *)(h->ws + h->lay.bytes - POLICY_BYTES - 256);
     h->scratch = (double *)(h->ws + h->lay.bytes - POLICY_BYTES - 256 - align_up((int64_t)REDUCE_BLOCKS * NIG_T_ROWS * 8, 256));
-    h->has_policy = false; h->mlp_stream = nullptr; h->act32 = nullptr; h->pid_mem = nullptr; h->may_hold_done = true; h->hst_pinned = nullptr; h->hst_dev = nullptr; h->hst_bytes = 0; h->mirror = nullptr; h->ld_mirror = 0; h->act_soa = nullptr; h->act_soa_floats = 0;
+    h->has_policy = false; h->mlp_stream = nullptr; h->mlp_cstream = nullptr; h->mlp_threshold = 0.0f; h->act32 = nullptr; h->pid_mem = nullptr; h->may_hold_done = true; h->hst_pinned = nullptr; h->hst_dev = nullptr; h->hst_bytes = 0; h->mirror = nullptr; h->ld_mirror = 0; h->act_soa = nullptr; h->act_soa_floats = 0;
     h->state = (float *)(h->ws + h->lay.off_state); h->ld_state = h->lay.ld;
     const nig_layout &L = h->lay;
     hipLaunchKernelGGL(init_ws_kernel, dim3(grid_for(L.ld)), dim3(BLOCK), 0, (hipStream_t)0,
@@ -522,6 +526,7 @@ int nig_destroy(nig_handle *h)
 {
     if (!h) return NIG_OK;
     if (h->mlp_stream) (void)hipFree(h->mlp_stream);
+    if (h->mlp_cstream) (void)hipFree(h->mlp_cstream);
     if (h->pid_mem) (void)hipFree(h->pid_mem);
     if (h->act32) (void)hipFree(h->act32);
     if (h->act_soa) (void)hipFree(h->act_soa);
@@ -869,21 +874,19 @@ int nig_set_mlp_policy(nig_handle *h, int32_t hidden, const float *W1, const flo
     return NIG_OK;
 }
 
-int nig_rollout_mlp(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
-                    float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
-                    void *stream)
+// argument checks and kernel arguments shared by nig_rollout_mlp and nig_rollout_mlp_safe
+static int mlp_args(nig_handle *h, const char *fn, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                    float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride, MlpArgs &q)
 {
-    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp: bad argument%s");
-    if (!h->mlp_stream || !launch_of(h->env)->mlp) return fail(NIG_ERR_INVALID, "nig_rollout_mlp: no actor installed (nig_set_mlp_policy)%s");
-    if (out_stride != 0 && (out_stride < h->B || out_stride > NIG_MAX_PITCH))
-        return fail(NIG_ERR_INVALID, "nig_rollout_mlp: out_stride outside {0} U [batch, 2^26]%s");
-    if ((int64_t)n_steps * out_stride > 0xffffffffLL) return fail(NIG_ERR_INVALID, "nig_rollout_mlp: n_steps*out_stride >= 2^32%s");
+    char msg[160];
+    auto bad = [&](const char *what) { snprintf(msg, sizeof msg, "%s: %s", fn, what); return fail(NIG_ERR_INVALID, "%s", msg); };
+    if (out_stride != 0 && (out_stride < h->B || out_stride > NIG_MAX_PITCH)) return bad("out_stride outside {0} U [batch, 2^26]");
+    if ((int64_t)n_steps * out_stride > 0xffffffffLL) return bad("n_steps*out_stride >= 2^32");
     if (obs_out && (obs_step_stride < (int64_t)SPECS[h->env].state_dim * h->B || (obs_step_stride & 3) || ((uintptr_t)obs_out & 15)))
-        return fail(NIG_ERR_INVALID, "nig_rollout_mlp: obs_out needs 16-byte alignment and obs_step_stride >= S*batch (multiple of 4)%s");
+        return bad("obs_out needs 16-byte alignment and obs_step_stride >= S*batch (multiple of 4)");
     if (act_out && (ld_act < h->B || ld_act > NIG_MAX_PITCH || act_step_stride < (int64_t)SPECS[h->env].action_dim * ld_act))
-        return fail(NIG_ERR_INVALID, "nig_rollout_mlp: bad action trajectory pitch%s");
-    if ((int64_t)h->t + n_steps > 0xffffffffLL) return fail(NIG_ERR_INVALID, "nig_rollout_mlp: launch counter would wrap%s");
-    MlpArgs q;
+        return bad("bad action trajectory pitch");
+    if ((int64_t)h->t + n_steps > 0xffffffffLL) return bad("launch counter would wrap");
     memset(&q, 0, sizeof q);
     q.s = base_step_args(h);
     q.s.reward = reward_out; q.s.flags = flags_out;
@@ -891,9 +894,91 @@ int nig_rollout_mlp(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t 
     q.wstream = h->mlp_stream; q.n_steps = n_steps; q.out_stride = (uint32_t)out_stride;
     q.obs_out = obs_out; q.obs_step_stride = (uint64_t)obs_step_stride;
     q.act_out = act_out; q.ld_act_out = (uint32_t)ld_act; q.act_step_stride = (uint64_t)act_step_stride;
+    return NIG_OK;
+}
+
+int nig_rollout_mlp(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                    float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
+                    void *stream)
+{
+    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp: bad argument%s");
+    if (!h->mlp_stream || !launch_of(h->env)->mlp) return fail(NIG_ERR_INVALID, "nig_rollout_mlp: no actor installed (nig_set_mlp_policy)%s");
+    MlpArgs q;
+    const int rc = mlp_args(h, "nig_rollout_mlp", n_steps, reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act,
+                            act_step_stride, q);
+    if (rc != NIG_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)((h->B + BLOCK / 2 - 1) / (BLOCK / 2));     // 32 envs per wave, 128 per block
     launch_of(h->env)->mlp(q, grid, st);
+    HIP_TRY(hipGetLastError());
+    h->t += (uint32_t)n_steps;
+    return NIG_OK;
+}
+
+int nig_set_mlp_safety(nig_handle *h, int32_t hidden, const float *C1, const float *c1, const float *C2, const float *c2,
+                       const float *C3, const float *c3, float threshold, void *stream)
+{
+    if (!h || !C1 || !c1 || !C2 || !c2 || !C3 || !c3) return fail(NIG_ERR_INVALID, "nig_set_mlp_safety: NULL argument%s");
+    if (hidden != MLP_H) return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_safety: hidden must be 256 (agents/networks.py default)%s");
+    const int S = SPECS[h->env].state_dim, A = SPECS[h->env].action_dim, H = MLP_H;
+    if (S % 2 != 0 || A > 16 || !launch_of(h->env)->mlp_shield)
+        return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_safety: env shape not supported (even state dim, at most 16 actions)%s");
+    float *host = (float *)calloc((size_t)MLP_CSTREAM_FLOATS, sizeof(float));
+    if (!host) return fail(NIG_ERR_INVALID, "nig_set_mlp_safety: out of host memory%s");
+    // The critic's stream in the order rollout_mlp_shield_kernel consumes it (nig_kernels.hpp, MLP_CDIM / MLP_CR1 / MLP_CL1):
+    // layer 1 on x = [s, a, 0-pad] in one chunk, or two chunks of four tiles when eight tiles do not fit a chunk slot; then one
+    // chunk per hidden tile of layer 2 (128 records + bias + 16 head records of the one-row 4 x 4 x 1 head), c3 after the last.
+    const int D = S + A, DP = (D + 1) & ~1, CR1 = DP / 2 + 1, CL1 = MLP_MT * CR1 <= MLP_CHREC ? 1 : 2, TPC = MLP_MT / CL1;
+    auto rec = [&](int chunk, int r) { return host + ((size_t)chunk * MLP_CHREC + r) * 64; };
+    for (int m = 0; m < MLP_MT; ++m) {                      // layer 1, natural k order: k = 2*ks + hf (k >= S + A: zero pad)
+        const int ch = m / TPC, base = (m % TPC) * CR1;
+        for (int ks = 0; ks < DP / 2; ++ks)
+            for (int l = 0; l < 64; ++l) {
+                const int k = 2 * ks + (l >> 5);
+                if (k < D) rec(ch, base + ks)[l] = C1[(size_t)k * H + 32 * m + (l & 31)];
+            }
+        for (int l = 0; l < 32; ++l) rec(ch, base + DP / 2)[l] = c1[32 * m + l];
+    }
+    for (int m2 = 0; m2 < MLP_MT; ++m2) {                   // chunk CL1 + m2: as the actor's, with a one-row head
+        int r = 0;
+        for (int kt = 0; kt < MLP_MT; ++kt)
+            for (int t = 0; t < 16; ++t, ++r)
+                for (int l = 0; l < 64; ++l)
+                    rec(CL1 + m2, r)[l] = C2[(size_t)(32 * kt + mfma_row(t, l >> 5)) * H + 32 * m2 + (l & 31)];
+        for (int l = 0; l < 32; ++l) rec(CL1 + m2, r)[l] = c2[32 * m2 + l];
+        ++r;
+        for (int t = 0; t < 16; ++t, ++r)                     // 4 x 4 x 1 head, row 0 only: lane 4 b holds C3 of its half's hidden row
+            for (int l = 0; l < 64; l += 4) rec(CL1 + m2, r)[l] = C3[32 * m2 + mfma_row(t, l >> 5)];
+        if (r != MLP_PER) { free(host); return fail(NIG_ERR_INVALID, "nig_set_mlp_safety: internal record count mismatch%s"); }
+    }
+    for (int l = 0; l < 64; l += 4) rec(CL1 + MLP_MT - 1, MLP_PER)[l] = c3[0];
+    hipError_t e = hipSuccess;
+    if (!h->mlp_cstream) e = hipMalloc((void **)&h->mlp_cstream, (size_t)MLP_CSTREAM_FLOATS * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpyAsync(h->mlp_cstream, host, (size_t)MLP_CSTREAM_FLOATS * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    free(host);
+    if (e != hipSuccess) return fail(NIG_ERR_HIP, "nig_set_mlp_safety: %s", hipGetErrorString(e));
+    h->mlp_threshold = threshold;
+    return NIG_OK;
+}
+
+int nig_rollout_mlp_safe(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                         float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
+                         float *prob_out, void *stream)
+{
+    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_safe: bad argument%s");
+    if (!launch_of(h->env)->mlp_shield) return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_mlp_safe: env shape has no MFMA actor%s");
+    if (!h->mlp_stream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_safe: no actor installed (nig_set_mlp_policy)%s");
+    if (!h->mlp_cstream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_safe: no safety critic installed (nig_set_mlp_safety)%s");
+    MlpShieldArgs q;
+    memset(&q, 0, sizeof q);
+    const int rc = mlp_args(h, "nig_rollout_mlp_safe", n_steps, reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out,
+                            ld_act, act_step_stride, q.m);
+    if (rc != NIG_OK) return rc;
+    q.cstream = h->mlp_cstream; q.prob_out = prob_out; q.threshold = h->mlp_threshold;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned grid = (unsigned)((h->B + BLOCK / 2 - 1) / (BLOCK / 2));     // 32 envs per wave, 128 per block
+    launch_of(h->env)->mlp_shield(q, grid, st);
     HIP_TRY(hipGetLastError());
     h->t += (uint32_t)n_steps;
     return NIG_OK;

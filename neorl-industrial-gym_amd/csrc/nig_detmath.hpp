@@ -151,6 +151,12 @@ __device__ __forceinline__ float det_tanhf(float x)
     return (x < 0.0f) ? -t : t;
 }
 
+// logistic sigmoid 1 / (1 + e^-x): the safety critic's output, jax.nn.sigmoid (agents/cql.py predict_with_safety)
+__device__ __forceinline__ float det_sigmoidf(float x)
+{
+    return 1.0f / (1.0f + det_expf(-x));
+}
+
 // float32 sine, |x| up to a few hundred: Cody-Waite by pi/2 (3 constants), degree-7/8 kernels.
 // jnp.sin of a bus-angle difference, advanced_power_grid.py:402
 __device__ __forceinline__ float det_sinf(float x)

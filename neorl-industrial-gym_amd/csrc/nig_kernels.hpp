@@ -1658,8 +1658,28 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 template <class Env> constexpr bool mlp_two_blocks = true;       // (PowerGrid's 23 + 31 table reads per step / reset from L2 as well: they are noise beside 1 217 MFMAs)
 
-template <class Env>
-__global__ void __launch_bounds__(BLOCK, mlp_two_blocks<Env> ? 2 : 1) rollout_mlp_kernel(const MlpArgs q)
+// Safety-critic shield (rollout_mlp_shield_kernel, agents/cql.py predict_with_safety): after the actor, a second pass of the
+// same scheme evaluates p = sigmoid(critic([s, a])), critic = (S + A) -> 256 -> 256 -> 1 ReLU MLP, and the env receives a * 0.5
+// unless p < threshold.  The critic's operand stream (nig_set_mlp_safety) is laid out like the actor's: layer 1 on the input
+// x = [s (S), a (A), 0-pad to even] in MLP_CL1<Env> chunks (one, or two of four tiles each when eight tiles of MLP_CR1 records
+// exceed a chunk slot: PowerGrid, AdvancedPowerGrid, SupplyChain), then one chunk per hidden tile of layer 2 with its slice of
+// a ONE-row head on v_mfma_f32_4x4x1 (the actor's mlp_head4 form with A = 1; the head's bias in record MLP_PER of the last).
+// Its chunks are consumed through the same double-buffered LDS image, so the fill of the next chunk stays in flight across
+// actor -> critic and critic -> next step's actor.
+template <class Env> constexpr int MLP_CDIM = (Env::S + Env::A + 1) & ~1;                    // critic input, padded to even
+template <class Env> constexpr int MLP_CR1 = MLP_CDIM<Env> / 2 + 1;                          // records per critic layer-1 tile
+template <class Env> constexpr int MLP_CL1 = MLP_MT * MLP_CR1<Env> <= MLP_CHREC ? 1 : 2;     // chunks of critic layer 1
+constexpr int MLP_CSTREAM_FLOATS = (2 + MLP_MT) * MLP_CHREC * 64;                          // room for either layer-1 form
+
+struct MlpShieldArgs {
+    MlpArgs m;
+    const float *cstream;       // critic operand stream built by nig_set_mlp_safety
+    float *prob_out;            // [n_steps][>= B] p of the unshielded action (row k at prob_out + k * m.out_stride), may be NULL
+    float threshold;            // shield when !(p < threshold)
+};
+
+template <class Env, bool SHIELD>
+__device__ __attribute__((always_inline)) inline void rollout_mlp_body(const MlpArgs &q, const float *cstream, float *prob_out, float threshold)
 {
     constexpr int S = Env::S, A = Env::A, KS = Env::KS, KR = Env::KR;
     constexpr int KSN = KS > 0 ? KS : 1;
@@ -1702,9 +1722,17 @@ __global__ void __launch_bounds__(BLOCK, mlp_two_blocks<Env> ? 2 : 1) rollout_ml
         for (int pc = (int)wave; pc < pieces; pc += BLOCK / 64)
             __builtin_amdgcn_global_load_lds((nig_glb_void *)(src + pc * 256), (nig_lds_void *)(&s_w[buf][pc * 256]), 16, 0, 0);
     };
+    [[maybe_unused]] auto cfill = [&](int c, int buf, int pieces) __attribute__((always_inline)) {   // the same from the critic's stream
+        const float *src = cstream + (size_t)c * (MLP_CHREC * 64) + lane * 4u;
+        for (int pc = (int)wave; pc < pieces; pc += BLOCK / 64)
+            __builtin_amdgcn_global_load_lds((nig_glb_void *)(src + pc * 256), (nig_lds_void *)(&s_w[buf][pc * 256]), 16, 0, 0);
+    };
     constexpr int R1 = S / 2 + 1;                            // records per layer-1 tile
     constexpr int PIECES0 = (MLP_MT * R1 + 3) / 4;           // pieces of chunk 0
     static_assert(MLP_MT * R1 <= MLP_CHREC, "layer 1 must fit one chunk");
+    constexpr int CL1 = MLP_CL1<Env>, CR1 = MLP_CR1<Env>, CTPC = MLP_MT / CL1;   // critic: layer-1 chunks, records per tile, tiles per chunk
+    constexpr int CPIECES0 = (CTPC * CR1 + 3) / 4;           // pieces of a critic layer-1 chunk
+    static_assert(CTPC * CR1 <= MLP_CHREC, "a critic layer-1 chunk must fit one chunk slot");
     fill(0, 0, PIECES0);
     int gbuf = 0;                                            // buffer that holds (or receives) the chunk consumed next
     for (int it = 0; it < q.n_steps; ++it) {
@@ -1743,6 +1771,7 @@ __global__ void __launch_bounds__(BLOCK, mlp_two_blocks<Env> ? 2 : 1) rollout_ml
             if (it == 0) {
 #endif
             if (m2 + 1 < MLP_MT) fill(2 + m2, gbuf ^ 1, MLP_PIECES);
+            else if constexpr (SHIELD) cfill(0, gbuf ^ 1, CPIECES0);  // the critic's layer 1 follows the actor
             else if (it + 1 < q.n_steps) fill(0, gbuf ^ 1, PIECES0);   // layer 1 of the NEXT step (the weights do not change)
 #if defined(NIG_DIAG_MLP_SKIP) && (NIG_DIAG_MLP_SKIP & 2)
             }
@@ -1791,6 +1820,63 @@ __global__ void __launch_bounds__(BLOCK, mlp_two_blocks<Env> ? 2 : 1) rollout_ml
                 a[r] = det_tanhf(beta ? v1 : v0);
             }
         }
+        [[maybe_unused]] bool shield = false;
+        [[maybe_unused]] float prob = 0.0f;
+        if constexpr (SHIELD) {
+            // ---------------- safety critic on x = [s, a, 0]: the same three-layer scheme, one-row head ----------------
+            auto x = [&](int k) __attribute__((always_inline)) { return k < S ? s[k] : (k < S + A ? a[k - S] : 0.0f); };
+            f32x16 g1[MLP_MT];
+#pragma unroll
+            for (int c1 = 0; c1 < CL1; ++c1) {
+                __syncthreads();                            // critic layer-1 chunk c1 is in s_w[gbuf]
+                if (c1 + 1 < CL1) cfill(c1 + 1, gbuf ^ 1, CPIECES0);
+                else cfill(CL1, gbuf ^ 1, MLP_PIECES);
+                const float *wb = &s_w[gbuf][lane];
+#pragma unroll
+                for (int mm = 0; mm < CTPC; ++mm) {
+                    f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+                    for (int ks = 0; ks < CR1 - 1; ++ks)
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[(mm * CR1 + ks) * 64], half ? x(2 * ks + 1) : x(2 * ks), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[(mm * CR1 + CR1 - 1) * 64], half ? 0.0f : 1.0f, acc, 0, 0, 0);   // + c1
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[r] = fmaxf(acc[r], 0.0f);
+                    g1[c1 * CTPC + mm] = acc;
+                }
+                gbuf ^= 1;
+            }
+            f32x4 z4 = {0, 0, 0, 0};
+            constexpr int RING = 8;
+            for (int m2 = 0; m2 < MLP_MT; ++m2) {
+                __syncthreads();                            // critic chunk CL1 + m2 is in s_w[gbuf]
+                if (m2 + 1 < MLP_MT) cfill(CL1 + 1 + m2, gbuf ^ 1, MLP_PIECES);
+                else if (it + 1 < q.n_steps) fill(0, gbuf ^ 1, PIECES0);   // the actor's layer 1 of the NEXT step
+                const float *wb = &s_w[gbuf][lane];
+                f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                float ring[RING];
+#pragma unroll
+                for (int j = 0; j < RING; ++j) ring[j] = wb[j * 64];
+#pragma unroll
+                for (int i = 0; i < MLP_PER; ++i) {
+                    const float aop = ring[i % RING];
+                    if (i + RING < MLP_PER + 1) ring[i % RING] = wb[(i + RING) * 64];
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (i < MLP_MT * 16)
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aop, g1[i / 16][i % 16], acc, 0, 0, 0);
+                    else if (i == MLP_MT * 16)
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aop, half ? 0.0f : 1.0f, acc, 0, 0, 0);      // + c2
+                    else
+                        z4 = __builtin_amdgcn_mfma_f32_4x4x1f32(aop, fmaxf(acc[i - MLP_MT * 16 - 1], 0.0f), z4, 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if (m2 + 1 == MLP_MT) z4 = __builtin_amdgcn_mfma_f32_4x4x1f32(ring[MLP_PER % RING], half ? 0.0f : 1.0f, z4, 0, 0, 0);   // + c3
+                gbuf ^= 1;
+            }
+            prob = det_sigmoidf(z4[0] + __shfl_xor(z4[0], 32));
+            shield = !(prob < threshold);
+#pragma unroll
+            for (int r = 0; r < A; ++r) a[r] = shield ? a[r] * 0.5f : a[r];
+        }
 
 #if defined(NIG_DIAG_MLP_SKIP) && (NIG_DIAG_MLP_SKIP & 1)     // (diagnostic builds only, WRONG results: the actor without the env step)
 #pragma unroll
@@ -1816,6 +1902,9 @@ __global__ void __launch_bounds__(BLOCK, mlp_two_blocks<Env> ? 2 : 1) rollout_ml
 #pragma unroll
                 for (int j = 0; j < A; ++j) (ao + j * q.ld_act_out)[li] = a[j];
             }
+            if constexpr (SHIELD) {
+                if (prob_out) (prob_out + (uint32_t)it * q.out_stride)[li] = prob;
+            }
         }
         const RngKey key = make_key(gi, t_base + (uint32_t)it + 1u, p.seed_lo, p.seed_hi, s_probit);
         if constexpr (KS > 0) Env::draw_step(key, nz); else nz[0] = 0;
@@ -1826,6 +1915,7 @@ __global__ void __launch_bounds__(BLOCK, mlp_two_blocks<Env> ? 2 : 1) rollout_ml
         const uint32_t viol_ep = (ctr >> NIG_CTR_VIOL_SHIFT) + (uint32_t)res.nviol;
         const bool done = (res.terminated || res.truncated) && !frozen;
         uint32_t fl = pack_flags<Env>(res, step) | ((done && autoreset) ? NIG_FLAG_DID_RESET : 0u);
+        if constexpr (SHIELD) fl |= shield ? NIG_FLAG_SHIELDED : 0u;
         float rew = (float)res.reward;
         if (frozen) {
             fl = NIG_FLAG_INACTIVE | ((ctr & NIG_CTR_STEP_MASK) << NIG_FLAG_STEP_SHIFT);
@@ -1867,6 +1957,18 @@ __global__ void __launch_bounds__(BLOCK, mlp_two_blocks<Env> ? 2 : 1) rollout_ml
         p.ep_ret[li] = ret;
         if (lt.episodes > 0) lt.merge(p.tally + li, p.ld, p.n_en);
     }
+}
+
+template <class Env>
+__global__ void __launch_bounds__(BLOCK, mlp_two_blocks<Env> ? 2 : 1) rollout_mlp_kernel(const MlpArgs q)
+{
+    rollout_mlp_body<Env, false>(q, nullptr, nullptr, 0.0f);
+}
+
+template <class Env>
+__global__ void __launch_bounds__(BLOCK, mlp_two_blocks<Env> ? 2 : 1) rollout_mlp_shield_kernel(const MlpShieldArgs q)
+{
+    rollout_mlp_body<Env, true>(q.m, q.cstream, q.prob_out, q.threshold);
 }
 
 struct ResetArgs {
@@ -1931,6 +2033,7 @@ struct EnvLaunch {
     void (*rollout)(int out_mode, const RolloutArgs &, uint32_t t0, unsigned grid, hipStream_t);
     void (*policy)(const PolicyArgs &, unsigned grid, hipStream_t);
     void (*mlp)(const MlpArgs &, unsigned grid, hipStream_t);      // nullptr: env shape not supported by the MFMA actor
+    void (*mlp_shield)(const MlpShieldArgs &, unsigned grid, hipStream_t);   // the same with the safety-critic shield
     void (*reset)(const ResetArgs &, bool parity, unsigned grid, hipStream_t);
     void (*fill)(float *act, int64_t ld_act, int64_t B, uint64_t env0, uint32_t seed_lo, uint32_t seed_hi, uint32_t t,
                  unsigned grid, hipStream_t);
@@ -1950,6 +2053,12 @@ template <class Env>
 static void launch_mlp(const MlpArgs &q, unsigned grid, hipStream_t st)
 {
     if constexpr (Env::S % 2 == 0 && Env::A <= 16) hipLaunchKernelGGL((rollout_mlp_kernel<Env>), dim3(grid), dim3(BLOCK), 0, st, q);
+}
+
+template <class Env>
+static void launch_mlp_shield(const MlpShieldArgs &q, unsigned grid, hipStream_t st)
+{
+    if constexpr (Env::S % 2 == 0 && Env::A <= 16) hipLaunchKernelGGL((rollout_mlp_shield_kernel<Env>), dim3(grid), dim3(BLOCK), 0, st, q);
 }
 
 template <class Env>
@@ -2207,6 +2316,7 @@ static const EnvLaunch *env_launch_table()
 {
     static const EnvLaunch T = {launch_step<Env>, Env::HAS_ACT64 ? launch_step64<Env> : nullptr, launch_rollout_env<Env>, launch_policy<Env>,
                                 (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp<Env> : nullptr,
+                                (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp_shield<Env> : nullptr,
                                 launch_reset<Env>, launch_fill<Env>, rollout_rows_native<Env>};
     return &T;
 }

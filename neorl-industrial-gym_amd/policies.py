@@ -204,10 +204,15 @@ class MLPPolicy:
     `weights` = [(W1 [S,H], b1 [H]), (W2 [H,H], b2 [H]), (W3 [H,A], b3 [A])] as exported from the
     agent (Flax Dense kernels are [in, out]).  evaluate_with_safety() calls `predict_device`, so
     observations and actions never leave the device; `predict` is the host form of the same net
-    (agent.predict contract, agents/base.py:106-141)."""
+    (agent.predict contract, agents/base.py:106-141).
+
+    `safety_weights` (optional) = the agents' SafetyCritic, [(C1 [S+A,H], c1), (C2 [H,H], c2), (C3 [H,1], c3)]
+    (networks.py:147-169), with `constraint_threshold` (base.py: 0.1): predict_with_safety() follows
+    cql.py:354-394, and shielded() is the policy that acts with it (fused into the env kernel by
+    evaluate_with_safety when both nets have the reference shape)."""
     is_trained = True
 
-    def __init__(self, weights, device="cuda:0"):
+    def __init__(self, weights, device="cuda:0", safety_weights=None, constraint_threshold: float = 0.1):
         import torch
         self.device = torch.device(device)
         self.layers = [(torch.as_tensor(np.asarray(W), dtype=torch.float32, device=self.device).contiguous(),
@@ -219,6 +224,30 @@ class MLPPolicy:
         # the fused MFMA kernel covers the reference actor shape; anything else goes through torch GEMMs
         self.fusable = (len(self.weights) == 3 and self.weights[0][0].shape[1] == 256
                         and self.weights[1][0].shape == (256, 256))
+        self.constraint_threshold = float(constraint_threshold)
+        self.safety_weights = None
+        self.safety_layers = None
+        if safety_weights is not None:
+            self.safety_weights = [(np.asarray(W, dtype=f32).reshape(np.shape(W)[0], -1), np.asarray(b, dtype=f32).reshape(-1))
+                                   for W, b in safety_weights]
+            if self.safety_weights[0][0].shape[0] != self.state_dim + self.action_dim or self.safety_weights[-1][0].shape[1] != 1:
+                raise ValueError(f"safety critic must map S+A={self.state_dim + self.action_dim} inputs to 1 output, got "
+                                 f"{[w.shape for w, _ in self.safety_weights]}")
+            self.safety_layers = [(torch.as_tensor(W, device=self.device).contiguous(), torch.as_tensor(b, device=self.device).contiguous())
+                                  for W, b in self.safety_weights]
+
+    @classmethod
+    def from_agent(cls, agent, device="cuda:0"):
+        """The actor (and, when the agent has one, the safety critic with the agent's constraint_threshold) of a
+        reference agent: agent.state["actor"].params / agent.state["safety"].params, Flax trees
+        {"params": {"MLP_0": {"Dense_0|1|2": {"kernel", "bias"}}}} (any nested mapping of array-likes).  LayerNorm
+        networks are refused (ValueError); Dropout has no parameters and is inert at training=False."""
+        state = agent.state
+        actor = _dense_layers(state["actor"].params, "actor")
+        safety = state.get("safety") if hasattr(state, "get") else None
+        critic = None if safety is None or getattr(safety, "params", None) is None else _dense_layers(safety.params, "safety")
+        return cls(actor, device=device, safety_weights=critic,
+                   constraint_threshold=getattr(agent, "constraint_threshold", 0.1))
 
     def predict_device(self, obs):
         import torch
@@ -234,3 +263,83 @@ class MLPPolicy:
         single = o.dim() == 1
         out = self.predict_device(o.reshape(-1, self.state_dim)).cpu().numpy()
         return out[0] if single else out
+
+    def _threshold(self, safety_threshold):
+        return safety_threshold or self.constraint_threshold           # cql.py:384 (0.0 / None fall back)
+
+    def safety_probs_device(self, obs, actions):
+        """p = sigmoid(critic([obs, actions])), [n] (networks.py:147-169)."""
+        import torch
+        if self.safety_layers is None:
+            raise RuntimeError("Safety critic must be trained")
+        x = torch.cat([obs, actions], dim=1)
+        for i, (W, b) in enumerate(self.safety_layers):
+            x = torch.addmm(b, x, W)
+            if i + 1 < len(self.safety_layers):
+                x = torch.relu(x)
+        return torch.sigmoid(x[:, 0])
+
+    def predict_with_safety_device(self, obs, safety_threshold=None):
+        """predict_with_safety on device tensors: (actions [n, A], probs [n])."""
+        import torch
+        a = self.predict_device(obs)
+        p = self.safety_probs_device(obs, a)
+        return torch.where((p < self._threshold(safety_threshold))[:, None], a, a * 0.5), p
+
+    def predict_with_safety(self, observations, safety_threshold=None):
+        """cql.py:354-394: actions of the deterministic actor, halved where the safety critic's p is not below
+        `safety_threshold or constraint_threshold`; returns (actions, safety_probs) as NumPy arrays."""
+        import torch
+        if self.safety_layers is None:
+            raise RuntimeError("Safety critic must be trained")
+        o = torch.as_tensor(np.asarray(observations, dtype=f32), device=self.device)
+        single = o.dim() == 1
+        a, p = self.predict_with_safety_device(o.reshape(-1, self.state_dim), safety_threshold)
+        a, p = a.cpu().numpy(), p.cpu().numpy()
+        return (a[0], p[0]) if single else (a, p)
+
+    def shielded(self, safety_threshold=None):
+        """The policy that acts with predict_with_safety's actions (for evaluate_with_safety)."""
+        if self.safety_layers is None:
+            raise RuntimeError("Safety critic must be trained")
+        return ShieldedMLPPolicy(self, self._threshold(safety_threshold))
+
+
+class ShieldedMLPPolicy:
+    """MLPPolicy.shielded(): predict / predict_device give predict_with_safety's actions.  When actor and critic
+    have the reference shape (hidden 256), evaluate_with_safety runs it fused into the env kernel
+    (BatchedIndustrialEnv.rollout_mlp_safe); otherwise through torch GEMMs."""
+    is_trained = True
+
+    def __init__(self, base: MLPPolicy, threshold: float):
+        self.base = base
+        self.threshold = float(threshold)
+        self.state_dim, self.action_dim = base.state_dim, base.action_dim
+        self.weights, self.safety_weights = base.weights, base.safety_weights
+        sw = base.safety_weights
+        self.fusable = base.fusable and len(sw) == 3 and sw[0][0].shape[1] == 256 and sw[1][0].shape == (256, 256)
+
+    def predict_device(self, obs):
+        return self.base.predict_with_safety_device(obs, self.threshold)[0]
+
+    def predict(self, observations, deterministic: bool = True):
+        return self.base.predict_with_safety(observations, self.threshold)[0]
+
+
+def _dense_layers(tree, what):
+    """[(kernel, bias), ...] of Dense_0, Dense_1, ... of a Flax parameter tree (any nested mapping)."""
+    def walk(t, path):
+        for k, v in t.items():
+            if str(k).startswith("LayerNorm"):
+                raise ValueError(f"{what}: LayerNorm networks are not supported ({'/'.join(path + [str(k)])})")
+            if hasattr(v, "items"):
+                walk(v, path + [str(k)])
+    walk(tree, [])
+    t = tree
+    while hasattr(t, "items") and not any(str(k).startswith("Dense_") for k in t.keys()):
+        subs = [v for v in t.values() if hasattr(v, "items")]
+        if len(subs) != 1:
+            raise ValueError(f"{what}: cannot find the Dense layers of the parameter tree (keys {list(t.keys())})")
+        t = subs[0]
+    dense = sorted((k for k in t.keys() if str(k).startswith("Dense_")), key=lambda k: int(str(k)[6:]))
+    return [(np.asarray(t[k]["kernel"], dtype=f32), np.asarray(t[k]["bias"], dtype=f32)) for k in dense]

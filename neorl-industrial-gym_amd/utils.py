@@ -128,10 +128,13 @@ def _evaluate_batched(agent, env: BatchedIndustrialEnv, n_episodes: int, step_no
     remaining, rnd = int(n_episodes), 0
     device_policy = hasattr(agent, "to_struct") and step_noise_fn is None and reset_noise_fn is None
     fused_mlp = getattr(agent, "fusable", False) and step_noise_fn is None and reset_noise_fn is None
+    shielded = fused_mlp and getattr(agent, "safety_weights", None) is not None and hasattr(agent, "threshold")
     if device_policy:
         env.set_policy(agent)
     elif fused_mlp:
         env.set_mlp_policy(agent.weights)
+        if shielded:        # MLPPolicy.shielded(): actor + safety critic + shield in the same kernel
+            env.set_mlp_safety(agent.safety_weights, agent.threshold)
         device_policy = True
     while remaining > 0 and device_policy:
         # the agent runs ON the device: one fused launch plays every episode of the round to its end
@@ -143,7 +146,7 @@ def _evaluate_batched(agent, env: BatchedIndustrialEnv, n_episodes: int, step_no
         # the Advanced envs truncate on the step AFTER the cap (advanced_chemical_reactor.py:351 and
         # advanced_power_grid.py:331 test episode_step before its increment): one step more for them
         extra = 1 if env.env_id.startswith("Advanced") else 0
-        (env.rollout_mlp if fused_mlp else env.rollout_policy)(env.max_episode_steps + extra)
+        (env.rollout_mlp_safe if shielded else env.rollout_mlp if fused_mlp else env.rollout_policy)(env.max_episode_steps + extra)
         remaining -= k
     while remaining > 0:
         k = min(B, remaining)

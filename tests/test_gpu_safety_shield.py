@@ -1,0 +1,222 @@
+"""-m gpu: the fused safety-critic shield (nig_rollout_mlp_safe, BatchedIndustrialEnv.rollout_mlp_safe) -- the
+reference agents' predict_with_safety (agents/cql.py:354-394) in the MFMA actor kernel -- against the CPU oracle's
+actor and env step and a float64 host critic, and evaluate_with_safety's fused shielded path against its host form."""
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+ENVS = [("cr", "ChemicalReactor-v0"), ("pg", "PowerGrid-v0"), ("ra", "RobotAssembly-v0"),
+        ("acr", "AdvancedChemicalReactor-v0"), ("hvac", "HVACControl-v0"), ("steel", "SteelAnnealing-v0"),
+        ("supply", "SupplyChain-v0")]
+B, T, MAXS, SEED = 3000, 14, 9, 0x5EED        # B not a multiple of 128: a partial last block
+
+
+@pytest.fixture(scope="module")
+def ni():
+    import neorl_industrial_gym_amd as ni
+    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+    return ni
+
+
+def _random_actor(S, A, seed):       # the style of test_gpu_parity.py's MFMA-actor test
+    rng = np.random.default_rng(seed)
+    return [(rng.normal(0, 1.0 / np.sqrt(S), (S, 256)).astype(np.float32) * np.float32(0.05), rng.normal(0, 0.05, 256).astype(np.float32)),
+            (rng.normal(0, 1.0 / 16, (256, 256)).astype(np.float32), rng.normal(0, 0.05, 256).astype(np.float32)),
+            (rng.normal(0, 1.0 / 8, (256, A)).astype(np.float32), rng.normal(0, 0.1, A).astype(np.float32))]
+
+
+def _random_critic(S, A, seed):
+    rng = np.random.default_rng(seed)
+    D = S + A
+    return [(rng.normal(0, 1.0 / np.sqrt(D), (D, 256)).astype(np.float32) * np.float32(0.05), rng.normal(0, 0.05, 256).astype(np.float32)),
+            (rng.normal(0, 1.0 / 16, (256, 256)).astype(np.float32), rng.normal(0, 0.05, 256).astype(np.float32)),
+            (rng.normal(0, 1.0 / 2, (256, 1)).astype(np.float32), rng.normal(0, 0.1, 1).astype(np.float32))]
+
+
+def _critic64(cw, obs, act):
+    z = np.concatenate([obs.astype(np.float64), act.astype(np.float64)], axis=-1)
+    for i, (W, b) in enumerate(cw):
+        z = z @ W.astype(np.float64) + b.astype(np.float64)
+        if i < 2:
+            z = np.maximum(z, 0)
+    return 1.0 / (1.0 + np.exp(-z[..., 0]))
+
+
+def _run(ni, name, autoreset, ws, cw, thr):
+    env = ni.make_batched(name, B, autoreset=autoreset, tally=True, max_episode_steps=MAXS)
+    env.set_mlp_policy(ws)
+    env.set_mlp_safety(cw, thr)
+    dev = env.device
+    act = torch.zeros(T, env.action_dim, env.ld, dtype=torch.float32, device=dev)
+    obs = torch.zeros(T, B, env.state_dim, dtype=torch.float32, device=dev)
+    fl = torch.zeros(T, env.ld, dtype=torch.int32, device=dev)
+    rw = torch.zeros(T, env.ld, dtype=torch.float32, device=dev)
+    pr = torch.zeros(T, env.ld, dtype=torch.float32, device=dev)
+    env.reset()
+    env.rollout_mlp_safe(T, rw, fl, obs, act, pr)
+    torch.cuda.synchronize()
+    out = dict(act=act[:, :, :B].permute(0, 2, 1).cpu().numpy(), obs=obs.cpu().numpy(), flags=fl[:, :B].cpu().numpy(),
+               prob=pr[:, :B].cpu().numpy())
+    out["live"] = (out["flags"] & ni._lib.FLAG_INACTIVE) == 0
+    out["shielded"] = (out["flags"] & ni._lib.FLAG_SHIELDED) != 0
+    return env, out
+
+
+@pytest.mark.parametrize("key,name", ENVS)
+@pytest.mark.parametrize("autoreset", [False, True])
+def test_never_shield_is_the_plain_actor(ni, oracle, key, name, autoreset):
+    """Threshold 2.0 (p < 2 always): every action, the final state, step, done and tallies bit for bit the oracle's
+    MFMA-actor rollout; p within 1e-5 of a float64 critic on the recorded (obs, act); no shield flag."""
+    probe = ni.make_batched(name, 1)
+    S, A = probe.state_dim, probe.action_dim
+    probe.close()
+    ws, cw = _random_actor(S, A, 11), _random_critic(S, A, 12)
+    env, o = _run(ni, name, autoreset, ws, cw, 2.0)
+    r = oracle.rollout_mlp(key, B, T, ws, max_steps=MAXS, autoreset=autoreset, nthreads=8, trajectories=True)
+    live = o["live"]
+    assert np.array_equal(o["act"].view(np.uint32)[live], r["act"].view(np.uint32)[live])
+    assert np.array_equal(env.get_state().cpu().numpy().view(np.uint32), r["state"].view(np.uint32))
+    assert np.array_equal(env.current_step.cpu().numpy(), r["step"]) and np.array_equal(env.done.cpu().numpy(), r["done"] != 0)
+    assert np.array_equal(env.tally[ni._lib.T_EPISODES].cpu().numpy(), [t.episodes for t in r["tallies"]])
+    assert np.array_equal(env.total_violations.cpu().numpy(), [t.violations for t in r["tallies"]])
+    p64 = _critic64(cw, o["obs"], o["act"])
+    assert np.allclose(o["prob"][live], p64[live], atol=1e-5, rtol=0)
+    assert not o["shielded"].any()
+    env.close()
+
+
+@pytest.mark.parametrize("key,name", ENVS)
+@pytest.mark.parametrize("autoreset", [False, True])
+def test_always_shield_halves_and_steps_with_the_halved_action(ni, oracle, key, name, autoreset):
+    """Threshold 0.0 (p is never below 0): every live action is 0.5 x the oracle's actor on the recorded observation,
+    bit for bit, with the flag set; the next observation is the oracle's env step on that halved action."""
+    probe = ni.make_batched(name, 1)
+    S, A = probe.state_dim, probe.action_dim
+    probe.close()
+    ws, cw = _random_actor(S, A, 21), _random_critic(S, A, 22)
+    env, o = _run(ni, name, autoreset, ws, cw, 0.0)
+    live, L = o["live"], ni._lib
+    assert np.array_equal(o["shielded"], live)
+    for k in range(T):
+        raw = oracle.mlp_actions(key, ws, o["obs"][k])
+        want = (raw * np.float32(0.5)).astype(np.float32)
+        assert np.array_equal(o["act"][k].view(np.uint32)[live[k]], want.view(np.uint32)[live[k]]), k
+    # teacher-forced env step on the first lanes: obs[k+1] = step(obs[k], act[k]) where the lane neither finished nor reset
+    n, checked = 400, 0
+    for k in range(T - 1):
+        fl = o["flags"][k, :n]
+        step_after = (fl.astype(np.uint32) >> L.FLAG_STEP_SHIFT).astype(np.int32)
+        nz = np.stack([oracle.gen_step_noise(key, SEED, i, k + 1) for i in range(n)]) if oracle.spec(key).k_step else None
+        r = oracle.step(key, o["obs"][k, :n], o["act"][k, :n], nz, step_after - 1, max_steps=MAXS, flavor=oracle.MATH_POLY)
+        cont = live[k, :n] & live[k + 1, :n] & ((fl & (L.FLAG_TERMINATED | L.FLAG_TRUNCATED | L.FLAG_DID_RESET)) == 0)
+        checked += int(cont.sum())
+        assert np.array_equal(o["obs"][k + 1, :n][cont].view(np.uint32), r["state_next"][cont].view(np.uint32)), k
+    assert checked > n
+    env.close()
+
+
+@pytest.mark.parametrize("key,name", ENVS)
+@pytest.mark.parametrize("autoreset", [False, True])
+def test_mixed_shield_decisions(ni, oracle, key, name, autoreset):
+    """A threshold inside the range of p: every live action is exactly raw or 0.5 raw (raw = the oracle's actor), the
+    choice agrees with the flag, with p < thr on the kernel's own p, and with a float64 critic away from the threshold."""
+    probe = ni.make_batched(name, 1)
+    S, A = probe.state_dim, probe.action_dim
+    probe.close()
+    ws, cw = _random_actor(S, A, 31), _random_critic(S, A, 32)
+    env0, o0 = _run(ni, name, autoreset, ws, cw, 2.0)
+    env0.close()
+    # state columns of the order of 100 (ChemicalReactor's temperatures) saturate the critic (p == 1.0 everywhere): scale
+    # its state inputs by the observed magnitudes so that p spreads, then put the threshold at the median of p
+    sc = (1.0 / (1.0 + np.abs(o0["obs"][o0["live"]]).mean(axis=0))).astype(np.float32)
+    cw = [(np.concatenate([cw[0][0][:S] * np.float32(20.0) * sc[:, None], cw[0][0][S:]]).astype(np.float32), cw[0][1]), cw[1], cw[2]]
+    env0, o0 = _run(ni, name, autoreset, ws, cw, 2.0)
+    env0.close()
+    thr = float(np.median(o0["prob"][o0["live"]]))
+    env, o = _run(ni, name, autoreset, ws, cw, thr)
+    live = o["live"]
+    kept = np.zeros_like(live)
+    halved = np.zeros_like(live)
+    for k in range(T):
+        raw = oracle.mlp_actions(key, ws, o["obs"][k])
+        kept[k] = (o["act"][k].view(np.uint32) == raw.view(np.uint32)).all(axis=1)
+        halved[k] = (o["act"][k].view(np.uint32) == (raw * np.float32(0.5)).view(np.uint32)).all(axis=1)
+        p64 = _critic64(cw, o["obs"][k], raw)
+        far = live[k] & (np.abs(p64 - thr) > 1e-4)
+        assert np.array_equal(o["shielded"][k][far], (p64 >= thr)[far]), k
+    sh = o["shielded"]
+    assert ((kept | halved) | ~live).all()
+    assert halved[live & sh].all() and kept[live & ~sh].all()
+    assert np.array_equal(sh[live], ~(o["prob"][live] < np.float32(thr)))
+    assert not sh[~live].any()
+    frac = sh[live].mean()
+    assert 0.1 <= frac <= 0.9, frac
+    env.close()
+
+
+@pytest.mark.parametrize("thr", [2.0, 1e-6])
+def test_evaluate_with_safety_runs_the_fused_shield(ni, monkeypatch, thr):
+    """evaluate_with_safety(MLPPolicy.from_agent(agent).shielded(thr), batched env) takes the fused kernel and gives the
+    dict of the host loop around predict_with_safety (same nets, different float32 summation order)."""
+    import types
+    S, A = 12, 3
+    ws, cw = _random_actor(S, A, 41), _random_critic(S, A, 42)
+    flax = lambda layers: {"params": {"MLP_0": {f"Dense_{i}": {"kernel": W, "bias": b} for i, (W, b) in enumerate(layers)}}}
+    agent = types.SimpleNamespace(state={"actor": types.SimpleNamespace(params=flax(ws)),
+                                         "safety": types.SimpleNamespace(params=flax(cw))},
+                                  constraint_threshold=0.1, is_trained=True)
+    pol = ni.MLPPolicy.from_agent(agent).shielded(thr)
+    assert pol.fusable
+    a = ni.make_batched("ChemicalReactor-v0", 256, autoreset=False, tally=True, max_episode_steps=48)
+    b = ni.make_batched("ChemicalReactor-v0", 256, autoreset=False, tally=True, max_episode_steps=48)
+
+    class HostOnly:
+        is_trained = True
+
+        def predict(self, obs, deterministic=True):
+            return pol.predict(obs)
+    want = ni.evaluate_with_safety(HostOnly(), b, n_episodes=256)
+
+    def boom(*_a, **_k):
+        raise AssertionError("the fused shielded path must not step or predict on the host")
+    monkeypatch.setattr(a, "step", boom)
+    monkeypatch.setattr(pol, "predict", boom)
+    monkeypatch.setattr(pol, "predict_device", boom)
+    calls = []
+    real = a.rollout_mlp_safe
+    monkeypatch.setattr(a, "rollout_mlp_safe", lambda *x, **k: (calls.append(x), real(*x, **k)))
+    got = ni.evaluate_with_safety(pol, a, n_episodes=256)
+    assert calls
+    assert len(got) == 13 and set(got) == set(want)
+    for k in want:
+        assert got[k] == pytest.approx(want[k], rel=2e-3, abs=1e-6), k
+    a.close(); b.close()
+
+
+def test_shield_errors(ni):
+    S, A = 12, 3
+    ws, cw = _random_actor(S, A, 51), _random_critic(S, A, 52)
+    env = ni.make_batched("ChemicalReactor-v0", 256)
+    env.reset()
+    with pytest.raises(ni._lib.NigError):          # no actor, no critic
+        env.rollout_mlp_safe(2)
+    env.set_mlp_safety(cw, 0.5)
+    with pytest.raises(ni._lib.NigError):          # critic but no actor
+        env.rollout_mlp_safe(2)
+    env.close()
+    env = ni.make_batched("ChemicalReactor-v0", 256)
+    env.reset()
+    env.set_mlp_policy(ws)
+    with pytest.raises(ni._lib.NigError):          # actor but no critic
+        env.rollout_mlp_safe(2)
+    with pytest.raises(AssertionError):            # critic on S inputs instead of S + A
+        env.set_mlp_safety([(cw[0][0][:S], cw[0][1]), cw[1], cw[2]], 0.5)
+    with pytest.raises(AssertionError):            # two outputs
+        env.set_mlp_safety([cw[0], cw[1], (np.zeros((256, 2), np.float32), np.zeros(2, np.float32))], 0.5)
+    env.set_mlp_safety(cw, 0.5)
+    env.set_mlp_policy(ws)                          # replacing the actor keeps the critic
+    env.rollout_mlp_safe(2)
+    torch.cuda.synchronize()
+    env.close()
