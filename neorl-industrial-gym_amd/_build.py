@@ -154,6 +154,32 @@ def build_variant(name, verbose=False):
     return out
 
 
+# Test-only device probe of the math library (tests/detmath_probe.hip, tests/test_gpu_detmath.py): a shared library of its
+# own, never part of libnig.so, compiled with HIPCC_FLAGS -- the library's bits are a property of these flags.
+PROBE_SRC = os.path.join(os.path.dirname(_HERE), "tests", "detmath_probe.hip")
+PROBE = os.path.join(_HERE, "libnig_detmath_probe.so")
+
+
+def build_probe(verbose=False):
+    stamp = PROBE + ".srchash"
+    want = _digest([PROBE_SRC] + headers(), " ".join(HIPCC_FLAGS))
+    if os.path.exists(PROBE) and os.path.exists(stamp) and open(stamp).read().strip() == want:
+        return PROBE
+    hipcc = find_hipcc()
+    if hipcc is None:
+        raise RuntimeError("hipcc not found: cannot build the math-library probe")
+    os.makedirs(OBJ, exist_ok=True)
+    tmp = f"{PROBE}.tmp.{os.getpid()}"
+    cmd = [hipcc] + HIPCC_FLAGS + ["-shared", "-o", tmp, PROBE_SRC]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    os.replace(tmp, PROBE)
+    with open(stamp, "w") as f:
+        f.write(want)
+    return PROBE
+
+
 def ensure(verbose=False):
     """What importing the package calls.  Never compiles inside a profiled or GPU-initialised
     process: with NIG_NO_AUTOBUILD set, or under a rocprofiler preload, a stale library is an error

@@ -358,7 +358,13 @@ extern "C" {
 // workspace is refused only when positively identified as host / managed / foreign-device memory.
 // 0.6.0: nig_set_mlp_safety / nig_rollout_mlp_safe (the MFMA actor with the safety-critic shield) and NIG_FLAG_SHIELDED.  No
 // existing entry point's results changed.
-const char *nig_version(void) { return "nig 0.6.0 (gfx950; generator nig-philox-v3)"; }
+// 0.7.0: det_tanhf takes Cephes' odd polynomial below |x| = 0.625 (the quotient form lost all relative accuracy towards 0):
+// the actions of nig_rollout_mlp / nig_rollout_mlp_safe and AdvancedChemicalReactor's step (the mixing term, rpm < 625)
+// change wherever a tanh argument lies below the cut-off.  fdiv_c by a divisor below one returns IEEE's inf where the
+// quotient overflows (most likely NaN before, not measured on the device; AdvancedChemicalReactor / AdvancedPowerGrid only),
+// det_sinf's quadrant is defined for every float (results change only from |x| ~ 6.59e6 on, where |fk| >= 2^22, outside its
+// stated domain |x| <= 1e4).  Generator and every other env unchanged.
+const char *nig_version(void) { return "nig 0.7.0 (gfx950; generator nig-philox-v3)"; }
 const char *nig_last_error(void) { return g_err; }
 
 int nig_tune(int32_t key, int64_t value)

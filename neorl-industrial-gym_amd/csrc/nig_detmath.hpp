@@ -19,9 +19,25 @@ namespace nig {
 // 2^23 significands (tests/constdiv_check.c); v_div_fixup restores the IEEE special cases (signed
 // zero, inf, NaN).  Valid while neither x*RN(1/c) nor the residual leaves the normal range
 // (2^-100 < |x| < 2^100 is ample); every call site divides a physical quantity far inside that.
+// Over ALL floats: equal to IEEE x / c except on a fixed set of inputs with |x| < 2^-100, where x * RN(1/c) or
+// the residual is subnormal.  tests/test_gpu_detmath.py checks, at every divisor used here, IEEE equality for all other
+// floats and, for |x| < 2^-100, equality with the oracle's restatement of the sequence bit for bit, so the device's set is
+// exactly the restatement's; tests/test_detmath.py pins its size for 100, 418 000 and 0.1.
+// A divisor below one makes x * RN(1/c) overflow before x / c does: there the three steps give NaN where IEEE gives
+// inf (and by the ISA's description v_div_fixup passes a NaN quotient on).  So for c < 1 an |x| >= 2^64 is divided as
+// x 2^-64 and the quotient scaled back (both exact; rounding commutes with the scaling up to and including the overflow
+// to inf).  c < 1 folds away at every call site: divisors >= 1 keep the 4-VALU form.
 __device__ __forceinline__ float fdiv_c(float x, const float c)
 {
     const float rc = 1.0f / c;                    // folded at compile time (c is a literal at every call site)
+    if (c < 1.0f) {
+        const bool big = __builtin_fabsf(x) >= 0x1p64f;
+        const float xs = big ? x * 0x1p-64f : x;
+        const float q0 = xs * rc;
+        const float r = __builtin_fmaf(-c, q0, xs);
+        const float q = __builtin_fmaf(r, rc, q0);
+        return __builtin_amdgcn_div_fixupf(big ? q * 0x1p64f : q, c, x);
+    }
     const float q0 = x * rc;
     const float r = __builtin_fmaf(-c, q0, x);
     const float q = __builtin_fmaf(r, rc, q0);
@@ -135,30 +151,47 @@ __device__ __forceinline__ float det_logf(float x)
 
 // x^y for x >= 0 (x == 0 -> 0): exp(y * ln x) with the polynomials above.  Stands in for jnp's
 // float32 power in the two Advanced envs (advanced_chemical_reactor.py:301 Re**0.8,
-// advanced_power_grid.py:317 V**alpha); a few ulp, like XLA's own expansion.
+// advanced_power_grid.py:317 V**alpha).  NOT a few ulp: the error of y ln x is amplified by |y ln x|.  Measured over every
+// float of the envs' domains (tests/detmath_check.c): x^0.8 <= 24 ulp for x in [1, 2^29) (Re = 1e5 rpm) and <= 128 ulp
+// below 1; V^alpha, alpha in {1.2, 1.3, 1.5, 1.8}, <= 2.5 ulp for V in [0.5, 2).
 __device__ __forceinline__ float det_powf(float x, float y)
 {
     const float r = det_expf(y * det_logf(x));
     return (x > 0.0f) ? r : 0.0f;
 }
 
-// tanh(x) = (1 - e^-2x) / (1 + e^-2x) for x >= 0 (odd extension).  jnp.tanh, advanced_chemical_reactor.py:299
+// tanh: for |x| < 0.625 Cephes tanhf's odd degree-9 polynomial x + x^3 P(x^2), above it (1 - e^-2|x|) / (1 + e^-2|x|);
+// the sign of x copied onto the result.  <= 2 ulp over all floats, exactly odd, |t| <= 1 (tests/detmath_check.c).
+// (The quotient alone loses all relative accuracy towards 0: 10 % at 1e-7, and 0 below 3.7e-9.)  jnp.tanh,
+// advanced_chemical_reactor.py:299; the MLP actor's last layer (agents/networks.py:144).
 __device__ __forceinline__ float det_tanhf(float x)
 {
-    const float ax = fabsf(x);
+    const float ax = __builtin_fabsf(x);
     const float e = det_expf(-2.0f * ax);
-    const float t = (1.0f - e) / (1.0f + e);
-    return (x < 0.0f) ? -t : t;
+    const float tq = (1.0f - e) / (1.0f + e);
+    const float z = ax * ax;
+    float p = -5.70498872745e-3f;
+    p = __builtin_fmaf(p, z, 2.06390887954e-2f);
+    p = __builtin_fmaf(p, z, -5.37397155531e-2f);
+    p = __builtin_fmaf(p, z, 1.33314422036e-1f);
+    p = __builtin_fmaf(p, z, -3.33332819422e-1f);
+    const float tp = __builtin_fmaf(p * z, ax, ax);
+    return __builtin_copysignf(ax < 0.625f ? tp : tq, x);
 }
 
-// logistic sigmoid 1 / (1 + e^-x): the safety critic's output, jax.nn.sigmoid (agents/cql.py predict_with_safety)
+// logistic sigmoid 1 / (1 + e^-x): the safety critic's output, jax.nn.sigmoid (agents/cql.py predict_with_safety).
+// <= 3 ulp where the result is a normal float, monotone non-decreasing over all floats (the shield's p < threshold
+// relies on that); +0 for x < -88.72283, where det_expf(-x) overflows and the true value is a subnormal below 2^-126.
 __device__ __forceinline__ float det_sigmoidf(float x)
 {
     return 1.0f / (1.0f + det_expf(-x));
 }
 
-// float32 sine, |x| up to a few hundred: Cody-Waite by pi/2 (3 constants), degree-7/8 kernels.
-// jnp.sin of a bus-angle difference, advanced_power_grid.py:402
+// float32 sine: Cody-Waite by pi/2 (3 constants), degree-7/8 kernels.  Stated domain |x| <= 1e4, absolute error
+// <= 8e-8 there (tests/detmath_check.c).  Beyond it the reduction loses accuracy (from |x| ~ 3e7 on the result leaves
+// [-1, 1]) but stays one defined function of x: the quadrant is read from the low mantissa bits of fk + 1.5 * 2^23
+// (fk mod 4 for |fk| < 2^22, the same as the former (int)fk & 3 there), not from a float -> int conversion, which
+// saturates on the device and is undefined in C.  jnp.sin of a bus-angle difference, advanced_power_grid.py:402
 __device__ __forceinline__ float det_sinf(float x)
 {
     const float fk = floorf(x * 0.636619772367581343f + 0.5f);
@@ -176,9 +209,9 @@ __device__ __forceinline__ float det_sinf(float x)
     cp = cp * z * z;
     cp = cp + -0.5f * z;
     cp = cp + 1.0f;
-    const int q = (int)fk & 3;
-    float v = (q & 1) ? cp : sp;
-    v = (q & 2) ? -v : v;
+    const uint32_t q = __float_as_uint(fk + 12582912.0f);
+    float v = (q & 1u) ? cp : sp;
+    v = (q & 2u) ? -v : v;
     return v;
 }
 

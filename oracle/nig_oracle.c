@@ -133,13 +133,24 @@ static void det_sincos(double x, double *s, double *c)
 }
 
 static float det_powf(float x, float y) { return (x > 0.0f) ? det_expf(y * det_logf(x)) : 0.0f; }
+/* tanh: Cephes tanhf's odd degree-9 polynomial below |x| = 0.625, (1 - e^-2|x|) / (1 + e^-2|x|) above, sign of x copied */
 static float det_tanhf(float x)
 {
     float ax = fabsf(x);
-    float e = det_expf(-2.0f * ax);
-    float t = (1.0f - e) / (1.0f + e);
-    return (x < 0.0f) ? -t : t;
+    if (!(ax < 0.625f)) {
+        float e = det_expf(-2.0f * ax);
+        return copysignf((1.0f - e) / (1.0f + e), x);
+    }
+    float z = ax * ax;
+    float p = -5.70498872745e-3f;
+    p = fmaf(p, z, 2.06390887954e-2f);
+    p = fmaf(p, z, -5.37397155531e-2f);
+    p = fmaf(p, z, 1.33314422036e-1f);
+    p = fmaf(p, z, -3.33332819422e-1f);
+    return copysignf(fmaf(p * z, ax, ax), x);
 }
+/* logistic sigmoid, the safety critic's output (agents/cql.py predict_with_safety) */
+static float det_sigmoidf(float x) { return 1.0f / (1.0f + det_expf(-x)); }
 static float det_sinf(float x)
 {
     float fk = floorf(x * 0.636619772367581343f + 0.5f);
@@ -157,9 +168,12 @@ static float det_sinf(float x)
     cp = cp * z * z;
     cp = cp + -0.5f * z;
     cp = cp + 1.0f;
-    int q = (int)fk & 3;
-    float v = (q & 1) ? cp : sp;
-    return (q & 2) ? -v : v;
+    /* quadrant from the low mantissa bits of fk + 1.5 * 2^23 (fk mod 4 for |fk| < 2^22; defined for every float,
+     * unlike a float -> int conversion): the statement the device uses */
+    union { float f; uint32_t u; } km; km.f = fk + 12582912.0f;
+    uint32_t q = km.u;
+    float v = (q & 1u) ? cp : sp;
+    return (q & 2u) ? -v : v;
 }
 static float o_powf(float x, float y, int flavor) { return flavor == MATH_POLY ? det_powf(x, y) : powf(x, y); }
 static float o_tanhf(float x, int flavor) { return flavor == MATH_POLY ? det_tanhf(x) : tanhf(x); }
@@ -1466,16 +1480,17 @@ void oracle_rollout_policy(int env, int64_t n, uint64_t env0, uint64_t seed, uin
 #define MLP_H 256
 static int mlp_rho(int t) { return (t & 3) + 8 * (t >> 2); }
 
-static void mlp_actor(int S, int A, const float *W1, const float *b1, const float *W2, const float *b2,
-                      const float *W3, const float *b3, const float *obs, int flavor, float *act)
+/* the network up to its head's pre-activations pre[0..A): D inputs x (an odd D is padded with one zero input, as the
+ * device's operand stream pads it: MLP_CDIM), layers 1 / 2 / head in the device's summation order */
+static void mlp_pre(int D, int A, const float *W1, const float *b1, const float *W2, const float *b2,
+                    const float *W3, const float *b3, const float *x, float *pre)
 {
     float h1[MLP_H], h2[MLP_H];
-    (void)flavor;
     for (int u = 0; u < MLP_H; u++) {
         float acc = 0.0f;
-        for (int ks = 0; ks < S / 2; ks++) {
-            acc = fmaf(W1[(size_t)(2 * ks) * MLP_H + u], obs[2 * ks], acc);
-            acc = fmaf(W1[(size_t)(2 * ks + 1) * MLP_H + u], obs[2 * ks + 1], acc);
+        for (int ks = 0; 2 * ks < D; ks++) {
+            acc = fmaf(W1[(size_t)(2 * ks) * MLP_H + u], x[2 * ks], acc);
+            acc = (2 * ks + 1 < D) ? fmaf(W1[(size_t)(2 * ks + 1) * MLP_H + u], x[2 * ks + 1], acc) : fmaf(0.0f, 0.0f, acc);
         }
         acc = fmaf(b1[u], 1.0f, acc); acc = fmaf(0.0f, 0.0f, acc);
         h1[u] = fmaxf(acc, 0.0f);
@@ -1504,8 +1519,17 @@ static void mlp_actor(int S, int A, const float *W1, const float *b1, const floa
                 acc1 = fmaf(W3[(size_t)k1 * A + j], h2[k1], acc1);
             }
         acc0 = fmaf(b3[j], 1.0f, acc0); acc1 = fmaf(b3[j], 0.0f, acc1);
-        act[j] = det_tanhf(acc0 + acc1);
+        pre[j] = acc0 + acc1;
     }
+}
+
+static void mlp_actor(int S, int A, const float *W1, const float *b1, const float *W2, const float *b2,
+                      const float *W3, const float *b3, const float *obs, int flavor, float *act)
+{
+    float pre[16];
+    (void)flavor;
+    mlp_pre(S, A, W1, b1, W2, b2, W3, b3, obs, pre);
+    for (int j = 0; j < A; j++) act[j] = det_tanhf(pre[j]);
 }
 
 void oracle_mlp_actions(int env, int64_t n, const float *W1, const float *b1, const float *W2, const float *b2,
@@ -1513,6 +1537,35 @@ void oracle_mlp_actions(int env, int64_t n, const float *W1, const float *b1, co
 {
     const int S = SPECS[env].state_dim, A = SPECS[env].action_dim;
     for (int64_t i = 0; i < n; i++) mlp_actor(S, A, W1, b1, W2, b2, W3, b3, obs + (size_t)i * S, MATH_POLY, act + (size_t)i * A);
+}
+
+/* the actor's head pre-activations (the argument of its tanh), bit for bit what the device's head forms */
+void oracle_mlp_preact(int env, int64_t n, const float *W1, const float *b1, const float *W2, const float *b2,
+                       const float *W3, const float *b3, const float *obs, float *pre)
+{
+    const int S = SPECS[env].state_dim, A = SPECS[env].action_dim;
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) mlp_pre(S, A, W1, b1, W2, b2, W3, b3, obs + (size_t)i * S, pre + (size_t)i * A);
+}
+
+/* the safety critic of nig_rollout_mlp_safe: p = sigmoid(critic([s, a, 0-pad])), critic (S + A) -> 256 -> 256 -> 1 in
+ * the device's order -- layer 1 on x = [s, a] in natural k order, layer 2 as the actor's, the one-row head as two lane-half
+ * fma chains joined by one add (the actor's K = 1 head with A = 1; nig_api.hip nig_set_mlp_safety) */
+#define MLP_CRITIC_MAXIN 50      /* the device's limit on the critic's input: an even S <= 34 (its MFMA layer 1) + A <= 16 */
+int oracle_mlp_critic(int env, int64_t n, const float *C1, const float *c1, const float *C2, const float *c2,
+                      const float *C3, const float *c3, const float *obs, const float *act, float *prob)
+{
+    const int S = SPECS[env].state_dim, A = SPECS[env].action_dim;
+    if (S + A > MLP_CRITIC_MAXIN) return -1;
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) {
+        float x[MLP_CRITIC_MAXIN], z;
+        memcpy(x, obs + (size_t)i * S, S * sizeof(float));
+        memcpy(x + S, act + (size_t)i * A, A * sizeof(float));
+        mlp_pre(S + A, 1, C1, c1, C2, c2, C3, c3, x, &z);
+        prob[i] = det_sigmoidf(z);
+    }
+    return 0;
 }
 
 /* closed loop with the MLP actor (same conventions as oracle_rollout_policy) */
@@ -1580,4 +1633,143 @@ void oracle_philox(const uint32_t *ctr, const uint32_t *key, uint32_t *out)
 void oracle_gen_normals(uint64_t seed, uint64_t env_index, uint32_t t, uint32_t stream, int n, float *z)
 {
     gen_normals(seed, env_index, t, stream, n, z);
+}
+
+/* ------------------------------------------------------------------------------
+ * Batch exports of the math layer for the device-vs-oracle tests (tests/test_gpu_detmath.py) and the accuracy
+ * sweeps (tests/detmath_check.c): OpenMP-parallel, as many threads as OMP_NUM_THREADS asks for.
+ * ---------------------------------------------------------------------------- */
+/* the device's constant division (csrc/nig_detmath.hpp fdiv_c) restated: the three rounded steps (x 2^-64 and the
+ * quotient scaled back for |x| >= 2^64 when c < 1) and v_div_fixup's result for a finite divisor c > 0 whose exponent
+ * is within 150 of every float's: NaN stays NaN, x = +-inf gives +-inf, x = +-0 gives +-0, otherwise |q| with x's sign */
+static float fdiv_c_seq(float x, float c)
+{
+    volatile float rcv = 1.0f / c;
+    const float rc = rcv;
+    if (x != x) return x;
+    if (isinf(x) || x == 0.0f) return x;
+    const int big = c < 1.0f && fabsf(x) >= 0x1p64f;
+    const float xs = big ? x * 0x1p-64f : x;
+    const float q0 = xs * rc;
+    const float r = fmaf(-c, q0, xs);
+    float q = fmaf(r, rc, q0);
+    q = big ? q * 0x1p64f : q;
+    return copysignf(fabsf(q), x);
+}
+
+enum { DM_EXPF, DM_LOGF, DM_TANHF, DM_SIGMOIDF, DM_SINF };
+static float dm_unary(int fn, float x)
+{
+    switch (fn) {
+    case DM_EXPF: return det_expf(x);
+    case DM_LOGF: return det_logf(x);
+    case DM_TANHF: return det_tanhf(x);
+    case DM_SIGMOIDF: return det_sigmoidf(x);
+    default: return det_sinf(x);
+    }
+}
+static int same_f32(float a, float b)
+{
+    uint32_t ua, ub;
+    memcpy(&ua, &a, 4); memcpy(&ub, &b, 4);
+    return ua == ub || (a != a && b != b);       /* NaNs compare as "both NaN": x86 and gfx950 make different default NaNs */
+}
+
+void oracle_det_expf_batch(const float *x, float *y, int64_t n)
+{
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) y[i] = det_expf(x[i]);
+}
+void oracle_det_logf_batch(const float *x, float *y, int64_t n)
+{
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) y[i] = det_logf(x[i]);
+}
+void oracle_det_tanhf_batch(const float *x, float *y, int64_t n)
+{
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) y[i] = det_tanhf(x[i]);
+}
+void oracle_det_sigmoidf_batch(const float *x, float *y, int64_t n)
+{
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) y[i] = det_sigmoidf(x[i]);
+}
+void oracle_det_sinf_batch(const float *x, float *y, int64_t n)
+{
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) y[i] = det_sinf(x[i]);
+}
+void oracle_det_powf_batch(const float *x, const float *y, float *z, int64_t n)
+{
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) z[i] = det_powf(x[i], y[i]);
+}
+void oracle_fdiv_c_batch(float c, const float *x, float *y, int64_t n)
+{
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) y[i] = fdiv_c_seq(x[i], c);
+}
+void oracle_det_exp_batch(const double *x, double *y, int64_t n)
+{
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) y[i] = det_exp64(x[i]);
+}
+void oracle_det_sincos_batch(const double *x, double *s, double *c, int64_t n)
+{
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) det_sincos(x[i], s + i, c + i);
+}
+/* csrc/nig_detmath.hpp ddiv_y without v_div_fixup (the caller's operands are finite and nonzero) */
+void oracle_ddiv_y_batch(const double *a, const double *b, const double *y, double *q, int64_t n)
+{
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) {
+        const double q0 = a[i] * y[i];
+        const double q1 = fma(fma(-q0, b[i], a[i]), y[i], q0);
+        q[i] = fma(fma(-q1, b[i], a[i]), y[i], q1);
+    }
+}
+void oracle_probit_normal_batch(const uint32_t *w, float *z, int64_t n)
+{
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++) z[i] = probit_normal(w[i]);
+}
+void oracle_philox_batch(const uint32_t *ctr, const uint32_t *key, uint32_t *out, int64_t n)   /* [n][4], [n][2], [n][4] */
+{
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < n; i++)
+        philox4x32_r(PHILOX_ROUNDS, ctr[4 * i], ctr[4 * i + 1], ctr[4 * i + 2], ctr[4 * i + 3], key[2 * i], key[2 * i + 1], out + 4 * i);
+}
+
+/* device output got[i] of unary function fn at x = the float with bits base + i, against the oracle: the number of
+ * words that differ (NaN == NaN), the first such i in *first (-1 if none) */
+int64_t oracle_cmp_unary_f32(int fn, uint32_t base, int64_t n, const float *got, int64_t *first)
+{
+    int64_t bad = 0, lo = INT64_MAX;
+#pragma omp parallel for schedule(static) reduction(+:bad) reduction(min:lo)
+    for (int64_t i = 0; i < n; i++) {
+        const uint32_t b = base + (uint32_t)i;
+        float x;
+        memcpy(&x, &b, 4);
+        if (!same_f32(dm_unary(fn, x), got[i])) { bad++; if (i < lo) lo = i; }
+    }
+    *first = bad ? lo : -1;
+    return bad;
+}
+
+/* device outputs got[i] of fdiv_c(x, c) at x = bits base + i against the restated sequence (fdiv_c_seq): the number of
+ * words that differ (NaN == NaN), the first such i in *first (-1 if none) */
+int64_t oracle_cmp_fdiv_c(float c, uint32_t base, int64_t n, const float *got, int64_t *first)
+{
+    int64_t bad = 0, lo = INT64_MAX;
+#pragma omp parallel for schedule(static) reduction(+:bad) reduction(min:lo)
+    for (int64_t i = 0; i < n; i++) {
+        const uint32_t b = base + (uint32_t)i;
+        float x;
+        memcpy(&x, &b, 4);
+        if (!same_f32(fdiv_c_seq(x, c), got[i])) { bad++; if (i < lo) lo = i; }
+    }
+    *first = bad ? lo : -1;
+    return bad;
 }

@@ -8,8 +8,13 @@ import torch
 pytestmark = pytest.mark.gpu
 
 ENVS = [("cr", "ChemicalReactor-v0"), ("pg", "PowerGrid-v0"), ("ra", "RobotAssembly-v0"),
-        ("acr", "AdvancedChemicalReactor-v0"), ("hvac", "HVACControl-v0"), ("steel", "SteelAnnealing-v0"),
-        ("supply", "SupplyChain-v0")]
+        ("acr", "AdvancedChemicalReactor-v0"), ("apg", "AdvancedPowerGrid-v0"), ("hvac", "HVACControl-v0"),
+        ("steel", "SteelAnnealing-v0"), ("supply", "SupplyChain-v0")]
+# AdvancedPowerGrid resets every lane to the same state, draws no noise, and ends an episode whenever a voltage set-point
+# action (a[4], a[5]) lies below 0.95 -- which a halved tanh output always does.  So its lanes never spread p and never
+# continue an always-halved episode: the two tests that need that take the envs below, and
+# test_always_shield_ends_advanced_power_grid_episodes_like_the_oracle covers its always-shield case.
+ENVS_SPREAD = [e for e in ENVS if e[0] != "apg"]
 B, T, MAXS, SEED = 3000, 14, 9, 0x5EED        # B not a multiple of 128: a partial last block
 
 
@@ -44,7 +49,7 @@ def _critic64(cw, obs, act):
     return 1.0 / (1.0 + np.exp(-z[..., 0]))
 
 
-def _run(ni, name, autoreset, ws, cw, thr):
+def _run(ni, name, autoreset, ws, cw, thr, B=B):
     env = ni.make_batched(name, B, autoreset=autoreset, tally=True, max_episode_steps=MAXS)
     env.set_mlp_policy(ws)
     env.set_mlp_safety(cw, thr)
@@ -83,11 +88,14 @@ def test_never_shield_is_the_plain_actor(ni, oracle, key, name, autoreset):
     assert np.array_equal(env.total_violations.cpu().numpy(), [t.violations for t in r["tallies"]])
     p64 = _critic64(cw, o["obs"], o["act"])
     assert np.allclose(o["prob"][live], p64[live], atol=1e-5, rtol=0)
+    for k in range(T):                  # and bit for bit the oracle's restatement of the critic in the device's order
+        pk = oracle.mlp_critic(key, cw, o["obs"][k], o["act"][k])
+        assert np.array_equal(o["prob"][k].view(np.uint32)[live[k]], pk.view(np.uint32)[live[k]]), k
     assert not o["shielded"].any()
     env.close()
 
 
-@pytest.mark.parametrize("key,name", ENVS)
+@pytest.mark.parametrize("key,name", ENVS_SPREAD)
 @pytest.mark.parametrize("autoreset", [False, True])
 def test_always_shield_halves_and_steps_with_the_halved_action(ni, oracle, key, name, autoreset):
     """Threshold 0.0 (p is never below 0): every live action is 0.5 x the oracle's actor on the recorded observation,
@@ -117,7 +125,29 @@ def test_always_shield_halves_and_steps_with_the_halved_action(ni, oracle, key, 
     env.close()
 
 
-@pytest.mark.parametrize("key,name", ENVS)
+def test_always_shield_ends_advanced_power_grid_episodes_like_the_oracle(ni, oracle):
+    """AdvancedPowerGrid at threshold 0.0, no auto-reset: every action of step 0 is 0.5 x the oracle's actor bit for bit
+    and flagged; the halved step ends every episode exactly where the oracle's step does, and the state each lane keeps
+    is that step's next state, bit for bit."""
+    key, name = "apg", "AdvancedPowerGrid-v0"
+    probe = ni.make_batched(name, 1)
+    S, A = probe.state_dim, probe.action_dim
+    probe.close()
+    ws, cw = _random_actor(S, A, 21), _random_critic(S, A, 22)
+    env, o = _run(ni, name, False, ws, cw, 0.0)
+    live, L = o["live"], ni._lib
+    assert np.array_equal(o["shielded"], live) and live[0].all()
+    raw = oracle.mlp_actions(key, ws, o["obs"][0])
+    assert np.array_equal(o["act"][0].view(np.uint32), (raw * np.float32(0.5)).astype(np.float32).view(np.uint32))
+    r = oracle.step(key, o["obs"][0], o["act"][0], None, np.zeros(B, dtype=np.int32), max_steps=MAXS, flavor=oracle.MATH_POLY)
+    ended = (o["flags"][0] & L.FLAG_TERMINATED) != 0
+    assert np.array_equal(ended, r["terminated"] != 0) and ended.all()
+    assert not live[1:].any()
+    assert np.array_equal(env.get_state().cpu().numpy().view(np.uint32), r["state_next"].view(np.uint32))
+    env.close()
+
+
+@pytest.mark.parametrize("key,name", ENVS_SPREAD)
 @pytest.mark.parametrize("autoreset", [False, True])
 def test_mixed_shield_decisions(ni, oracle, key, name, autoreset):
     """A threshold inside the range of p: every live action is exactly raw or 0.5 raw (raw = the oracle's actor), the
@@ -144,6 +174,8 @@ def test_mixed_shield_decisions(ni, oracle, key, name, autoreset):
         kept[k] = (o["act"][k].view(np.uint32) == raw.view(np.uint32)).all(axis=1)
         halved[k] = (o["act"][k].view(np.uint32) == (raw * np.float32(0.5)).view(np.uint32)).all(axis=1)
         p64 = _critic64(cw, o["obs"][k], raw)
+        pk = oracle.mlp_critic(key, cw, o["obs"][k], raw)
+        assert np.array_equal(o["prob"][k].view(np.uint32)[live[k]], pk.view(np.uint32)[live[k]]), k
         far = live[k] & (np.abs(p64 - thr) > 1e-4)
         assert np.array_equal(o["shielded"][k][far], (p64 >= thr)[far]), k
     sh = o["shielded"]
@@ -153,6 +185,98 @@ def test_mixed_shield_decisions(ni, oracle, key, name, autoreset):
     assert not sh[~live].any()
     frac = sh[live].mean()
     assert 0.1 <= frac <= 0.9, frac
+    env.close()
+
+
+def _spread_critic(ni, name, autoreset, ws, cw, S):
+    """The critic with its state inputs scaled by the observed magnitudes, so that p spreads (test_mixed_shield_decisions)."""
+    env0, o0 = _run(ni, name, autoreset, ws, cw, 2.0)
+    env0.close()
+    sc = (1.0 / (1.0 + np.abs(o0["obs"][o0["live"]]).mean(axis=0))).astype(np.float32)
+    return [(np.concatenate([cw[0][0][:S] * np.float32(20.0) * sc[:, None], cw[0][0][S:]]).astype(np.float32), cw[0][1]), cw[1], cw[2]]
+
+
+@pytest.mark.parametrize("key,name", ENVS)
+def test_threshold_equal_to_an_occurring_p_is_shielded(ni, oracle, key, name):
+    """The threshold is a p that occurs at step 0 of the shielded run itself (step 0 acts on the reset states, so its p is
+    that of the never-shield run bit for bit): the lanes with p == threshold must be shielded (the shield is !(p < thr),
+    not p > thr), those below it must not, and p is the oracle critic's bit for bit."""
+    probe = ni.make_batched(name, 1)
+    S, A = probe.state_dim, probe.action_dim
+    probe.close()
+    ws, cw = _random_actor(S, A, 61), _random_critic(S, A, 62)
+    cw = _spread_critic(ni, name, True, ws, cw, S)
+    env0, o0 = _run(ni, name, True, ws, cw, 2.0)
+    env0.close()
+    p0 = np.sort(o0["prob"][0][o0["live"][0]])
+    thr = p0[len(p0) // 2]                                  # a float32 p of step 0, not a mean of two
+    env, o = _run(ni, name, True, ws, cw, float(thr))
+    live = o["live"]
+    assert np.array_equal(o["prob"][0].view(np.uint32), o0["prob"][0].view(np.uint32))
+    at = live[0] & (o["prob"][0] == thr)
+    assert at.any()
+    assert o["shielded"][0][at].all()
+    assert not o["shielded"][0][live[0] & (o["prob"][0] < thr)].any()
+    assert np.array_equal(o["shielded"][live], ~(o["prob"][live] < thr))
+    for k in range(T):
+        raw = oracle.mlp_actions(key, ws, o["obs"][k])
+        pk = oracle.mlp_critic(key, cw, o["obs"][k], raw)
+        assert np.array_equal(o["prob"][k].view(np.uint32)[live[k]], pk.view(np.uint32)[live[k]]), k
+    env.close()
+
+
+@pytest.mark.parametrize("key,name", [("cr", "ChemicalReactor-v0"), ("pg", "PowerGrid-v0"), ("apg", "AdvancedPowerGrid-v0")])
+@pytest.mark.parametrize("b", [1, 33, 129])
+def test_small_batches(ni, oracle, key, name, b):
+    """Batches of one lane, of part of a wave and of one block plus one lane: actions, p and the final state against the
+    oracle (threshold 2.0: the plain actor) and, at a threshold inside the range of p, the shield decision."""
+    probe = ni.make_batched(name, 1)
+    S, A = probe.state_dim, probe.action_dim
+    probe.close()
+    ws, cw = _random_actor(S, A, 71), _random_critic(S, A, 72)
+    env, o = _run(ni, name, True, ws, cw, 2.0, B=b)
+    r = oracle.rollout_mlp(key, b, T, ws, max_steps=MAXS, autoreset=True, nthreads=8, trajectories=True)
+    live = o["live"]
+    assert np.array_equal(o["act"].view(np.uint32)[live], r["act"].view(np.uint32)[live])
+    assert np.array_equal(env.get_state().cpu().numpy().view(np.uint32), r["state"].view(np.uint32))
+    for k in range(T):
+        pk = oracle.mlp_critic(key, cw, o["obs"][k], o["act"][k])
+        assert np.array_equal(o["prob"][k].view(np.uint32)[live[k]], pk.view(np.uint32)[live[k]]), k
+    env.close()
+    thr = float(o["prob"][0][0])
+    env, o = _run(ni, name, True, ws, cw, thr, B=b)
+    assert o["shielded"][0][0]
+    assert np.array_equal(o["shielded"][o["live"]], ~(o["prob"][o["live"]] < np.float32(thr)))
+    env.close()
+
+
+@pytest.mark.parametrize("key,name", [("cr", "ChemicalReactor-v0"), ("apg", "AdvancedPowerGrid-v0")])
+def test_two_launches_continue_one_rollout(ni, oracle, key, name):
+    """A shielded rollout in two launches from launch counter t0 (threshold 2.0) is the oracle's single rollout from t0:
+    the second launch takes up the counter, the states and the episode steps where the first left them."""
+    probe = ni.make_batched(name, 1)
+    S, A = probe.state_dim, probe.action_dim
+    probe.close()
+    ws, cw = _random_actor(S, A, 81), _random_critic(S, A, 82)
+    b, t0, T1, T2 = 700, 37, 5, 8
+    env = ni.make_batched(name, b, autoreset=True, tally=True, max_episode_steps=MAXS)
+    env.set_mlp_policy(ws)
+    env.set_mlp_safety(cw, 2.0)
+    env.counter = t0
+    env.reset()
+    acts = []
+    for n in (T1, T2):
+        act = torch.zeros(n, env.action_dim, env.ld, dtype=torch.float32, device=env.device)
+        fl = torch.zeros(n, env.ld, dtype=torch.int32, device=env.device)
+        rw = torch.zeros(n, env.ld, dtype=torch.float32, device=env.device)
+        env.rollout_mlp_safe(n, rw, fl, None, act, None)
+        torch.cuda.synchronize()
+        acts.append(act[:, :, :b].permute(0, 2, 1).cpu().numpy())
+    assert env.counter == t0 + T1 + T2
+    r = oracle.rollout_mlp(key, b, T1 + T2, ws, t0=t0, max_steps=MAXS, autoreset=True, nthreads=8, trajectories=True)
+    assert np.array_equal(np.concatenate(acts).view(np.uint32), r["act"].view(np.uint32))
+    assert np.array_equal(env.get_state().cpu().numpy().view(np.uint32), r["state"].view(np.uint32))
+    assert np.array_equal(env.current_step.cpu().numpy(), r["step"])
     env.close()
 
 
