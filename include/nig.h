@@ -19,6 +19,19 @@
  *   - every launch goes to the caller-supplied hipStream_t (passed as void*), no
  *     hidden synchronisation; a handle is not thread-safe, distinct handles are;
  *   - there is no CPU fallback: without a HIP device nig_create fails.
+ *
+ * Memory footprint (pinned by tests/test_gpu_footprint.py for every entry point and kernel form)
+ *   - a call writes only the documented words of the documented rows of its output arguments: columns [0, batch) of a
+ *     row, rows [0, n_steps) of a per-step output (one row / one block where a stride of 0 means "overwrite": it ends
+ *     holding the last step's values).  It never writes the pad columns [batch, pitch) of a row, the gap between the end
+ *     of a row set and the next step's (any stride above the stated minimum is legal, odd ones included), or anything
+ *     before or behind a buffer; in the workspace it never writes the pad columns [batch, ld) of the library-owned arrays;
+ *   - input arguments are never written, and the pad columns and stride gaps of an input (action rings, noise rows) never
+ *     influence a result: they may hold anything, NaN and infinities included;
+ *   - a pitch or stride below its stated minimum is NIG_ERR_INVALID and nothing is written;
+ *   - no alignment beyond the element size (4 bytes for float / uint32 / int32, 8 for double) is required of a caller
+ *     buffer unless the argument's text says so (the workspace: 256 bytes; row-major observation trajectories: 16 bytes),
+ *     and results do not depend on the alignment or pitch chosen.
  */
 #ifndef NIG_H
 #define NIG_H
@@ -259,7 +272,7 @@ int nig_reset(nig_handle *h, const uint8_t *mask, const double *init_noise, int6
  *   reward64_out double [B]  the reference's fp64 Python-float reward      may be NULL
  *   flags_out    uint32 [B]  NIG_FLAG_* word                               may be NULL
  *   final_obs    float [S][ld_obs] terminal observation of lanes that finished in this
- *                call (other lanes untouched)                              may be NULL
+ *                call (other lanes' columns untouched)                     may be NULL
  * The new state/observation is the library-owned state array (nig_layout.off_state);
  * with NIG_F_AUTORESET a finished lane already holds the first observation of its next
  * episode.  Without it a finished lane is frozen until nig_reset (the reference raises
@@ -292,7 +305,8 @@ int nig_step64(nig_handle *h, const double *actions, int64_t ld_act,
  * and replayed with one call (the per-step launch is otherwise host-bound at small batch).
  * Step k (0-based) of every replay reads its actions from ring slot k % ring_len:
  *   action_ring  float, slot s at action_ring + s*slot_stride, each slot [A][ld_act]
- *   reward_out / flags_out  optional; slot s at base + s*out_stride (out_stride 0 = every
+ *   reward_out / flags_out  optional; rings like the actions: step k writes slot s = k % ring_len at
+ *                base + s*out_stride (min(n_steps, ring_len) slots are written; out_stride 0 = every
  *                step overwrites the same [B] array)
  * Semantics per step are exactly nig_step's (same kernel); the launch counter advances by
  * n_steps per replay.  This is the shape of the reference's own measurement loop
@@ -330,6 +344,9 @@ int nig_plan_destroy(nig_plan *p);
  *                dense trajectory: each wave's 64 rows leave as whole-line 16-byte streaming stores).
  *                obs_step_stride == 0: every step overwrites the same block (as out_stride == 0 does for the
  *                reward / flag rows) -- the caller keeps the observations the last step returned
+ * A frozen lane (finished on a handle without NIG_F_AUTORESET, or done before the call) still gets its rows written in every
+ * step: flags_out = NIG_FLAG_INACTIVE | its step count, reward_out = 0.0f, and obs_out = the state the lane holds (the
+ * closed-loop entry points below leave a frozen lane's observation / action rows untouched instead).
  * Stands in for the step loops of the reference's harnesses: benchmark_environment_steps
  * (performance_benchmark.py:106-133) and the get_dataset episode loops
  * (chemical_reactor.py:364-405, power_grid.py:209-237, robot_assembly.py:259-296).
@@ -407,11 +424,14 @@ int nig_set_policy(nig_handle *h, const nig_policy *policy /* host */, void *str
  * n_steps closed-loop steps per lane in one launch: action = policy(observation), then
  * IndustrialEnv.step, state in registers.  Optional per-step outputs (any subset):
  *   obs_out   float row-major [n_steps][B][S]: the observation the policy acted on (D4RL
- *             'observations'), step k at obs_out + k*obs_step_stride
+ *             'observations'), step k at obs_out + k*obs_step_stride; obs_out 16-byte aligned,
+ *             obs_step_stride >= S*B and a multiple of 4 floats (NIG_ERR_INVALID otherwise; there
+ *             is no "overwrite" form: 0 is refused)
  *   act_out   float [n_steps][A][ld_act]: the policy's action (after its own clip, before the
- *             env's), step k at act_out + k*act_step_stride
+ *             env's), step k at act_out + k*act_step_stride (ld_act >= B, act_step_stride >= A*ld_act)
  *   reward_out / flags_out   row of step k at base + k*out_stride (0 = overwrite)
- * Frozen lanes (finished, no auto-reset) write NIG_FLAG_INACTIVE and leave obs/act rows untouched.
+ * Frozen lanes (finished, no auto-reset) write NIG_FLAG_INACTIVE | their step count and reward 0.0f and leave
+ * their obs/act rows untouched in that step (nig_rollout_mlp_safe: their prob_out words too).
  * This is the loop of utils.evaluate_with_safety (utils.py:80-112) and of the get_dataset
  * generators, with the agent on the device.
  */
@@ -434,7 +454,7 @@ int nig_rollout_policy(nig_handle *h, int32_t n_steps, float *reward_out, uint32
 int nig_set_mlp_policy(nig_handle *h, int32_t hidden, const float *W1, const float *b1, const float *W2,
                        const float *b2, const float *W3, const float *b3, void *stream);
 
-/* As nig_rollout_policy, with the MLP actor installed by nig_set_mlp_policy. */
+/* As nig_rollout_policy (arguments, minima, obs_out alignment, frozen lanes), with the MLP actor installed by nig_set_mlp_policy. */
 int nig_rollout_mlp(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out,
                     int64_t out_stride, float *obs_out, int64_t obs_step_stride,
                     float *act_out, int64_t ld_act, int64_t act_step_stride, void *stream);

@@ -99,6 +99,8 @@ class BatchedIndustrialEnv:
       env_index0       global index of lane 0 (sharding-invariant RNG streams)
       autoreset        finished lanes start their next episode inside the step kernel
       tally            keep per-lane episode tallies for evaluate_with_safety
+      workspace        optional caller-owned uint8 tensor on `device` that holds the handle's arrays (nig_create's
+                       `workspace`: at least nig_layout.bytes, 256-byte aligned); default: the env allocates its own
     Layouts: `state` / `obs` is the library-owned SoA array viewed as [B, S] with strides
     (1, ld) -- a zero-copy view a policy network can consume directly; actions are
     accepted as [A, B] (native SoA, no copy) or [B, A] (transposed on the way in).
@@ -106,7 +108,8 @@ class BatchedIndustrialEnv:
 
     def __init__(self, env_id: str, batch: int, device="cuda:0", seed: int = 0x5EED, env_index0: int = 0,
                  max_episode_steps: Optional[int] = None, dt: Optional[float] = None, autoreset: bool = True,
-                 tally: bool = False, bind_state: Optional[torch.Tensor] = None):
+                 tally: bool = False, bind_state: Optional[torch.Tensor] = None,
+                 workspace: Optional[torch.Tensor] = None):
         if env_id not in ENV_IDS:
             available = ", ".join(ENV_IDS.keys())
             raise ValueError(f"Unknown environment '{env_id}'. Available: {available}")
@@ -130,8 +133,14 @@ class BatchedIndustrialEnv:
         self.ld = int(lay.ld)
         dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         with torch.cuda.device(dev_index):
-            self._ws = torch.empty(int(lay.bytes), dtype=torch.uint8, device=self.device)
-            assert self._ws.data_ptr() % 256 == 0
+            if workspace is None:
+                self._ws = torch.empty(int(lay.bytes), dtype=torch.uint8, device=self.device)
+            else:
+                assert workspace.dtype == torch.uint8 and workspace.is_contiguous()
+                assert workspace.device.type == "cuda" and workspace.device.index == dev_index, "workspace on another device"
+                assert workspace.numel() >= int(lay.bytes), "workspace smaller than nig_layout.bytes"
+                self._ws = workspace[:int(lay.bytes)]
+            assert self._ws.data_ptr() % 256 == 0, "workspace must be 256-byte aligned"
             h = C.c_void_p()
             _lib.check(self._L.nig_create(self._eid, self.batch, dev_index, C.c_uint64(seed), C.c_uint64(env_index0),
                                           self.max_episode_steps if max_episode_steps else 0,

@@ -634,6 +634,16 @@ int nig_step64(nig_handle *h, const double *actions, int64_t ld_act, const doubl
 {
     if (!h) return fail(NIG_ERR_INVALID, "nig_step64: NULL handle%s");
     if (!actions || ld_act < h->B || ld_act > NIG_MAX_PITCH) return fail(NIG_ERR_INVALID, "nig_step64: actions NULL or ld_act outside [batch, 2^26]%s");
+    // every argument is checked before anything is launched: a refused call enqueues nothing (the narrowing copy below included)
+    const nig_env_spec &sp = SPECS[h->env];
+    const bool autoreset = (h->flags & NIG_F_AUTORESET) != 0;
+    const bool parity = (step_noise != nullptr) || (reset_noise != nullptr);
+    if (parity) {
+        if (sp.k_step > 0 && !step_noise) return fail(NIG_ERR_INVALID, "nig_step64: parity mode needs step_noise%s");
+        if (autoreset && !reset_noise) return fail(NIG_ERR_INVALID, "nig_step64: parity mode with auto-reset needs reset_noise%s");
+        if (ld_noise < h->B || ld_noise > NIG_MAX_PITCH) return fail(NIG_ERR_INVALID, "nig_step64: ld_noise outside [batch, 2^26]%s");
+    }
+    if (final_obs && (ld_obs < h->B || ld_obs > NIG_MAX_PITCH)) return fail(NIG_ERR_INVALID, "nig_step64: ld_obs outside [batch, 2^26]%s");
     const EnvLaunch *L = launch_of(h->env);
     if (!L->step64) {                             // this env's own arithmetic takes the action as float32
         const int A = SPECS[h->env].action_dim;
@@ -644,15 +654,6 @@ int nig_step64(nig_handle *h, const double *actions, int64_t ld_act, const doubl
         return nig_step(h, h->act32, h->lay.ld, step_noise, reset_noise, ld_noise, reward_out, reward64_out, flags_out,
                         final_obs, ld_obs, stream);
     }
-    const nig_env_spec &sp = SPECS[h->env];
-    const bool autoreset = (h->flags & NIG_F_AUTORESET) != 0;
-    const bool parity = (step_noise != nullptr) || (reset_noise != nullptr);
-    if (parity) {
-        if (sp.k_step > 0 && !step_noise) return fail(NIG_ERR_INVALID, "nig_step64: parity mode needs step_noise%s");
-        if (autoreset && !reset_noise) return fail(NIG_ERR_INVALID, "nig_step64: parity mode with auto-reset needs reset_noise%s");
-        if (ld_noise < h->B || ld_noise > NIG_MAX_PITCH) return fail(NIG_ERR_INVALID, "nig_step64: ld_noise outside [batch, 2^26]%s");
-    }
-    if (final_obs && (ld_obs < h->B || ld_obs > NIG_MAX_PITCH)) return fail(NIG_ERR_INVALID, "nig_step64: ld_obs outside [batch, 2^26]%s");
     h->t += 1;
     StepArgs a = base_step_args(h);
     a.actions64 = actions; a.ld_act = (uint32_t)ld_act;
