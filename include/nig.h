@@ -357,6 +357,28 @@ int nig_rollout(nig_handle *h, int32_t n_steps, const float *action_ring, int64_
                 void *stream);
 
 /*
+ * nig_rollout WITHOUT an action ring: every step draws its own uniform action in the kernel -- the reference's measurement
+ * loop as it is written (performance_benchmark.py:106-133: a fresh action_space.sample() on every step, step, reset on done).
+ * The step with launch counter t takes, for lane i, exactly the action nig_fill_actions(h, t, ...) writes for that lane:
+ * uniforms of the generator's action stream at key (env_index0 + i, t, seed), mapped into the env's action Box.  A call is
+ * therefore bit-identical -- outputs, state, counters, tallies -- to nig_rollout on a ring of n_steps slots filled with
+ * nig_fill_actions(t0 + 1 + s) (tests/test_gpu_rollout_sampled.py), with no ring in memory, no fill launches and no action
+ * reads: a finite ring repeats a lane's actions, one slot per step costs memory and traffic.
+ * Everything else is nig_rollout's: the output modes and their arguments, the rows of a frozen lane, auto-reset, tallies,
+ * the launch-counter advance (n_steps), the argument checks and their error texts (a refused call launches nothing), and the
+ * kernel form -- the same rule, thresholds, nig_tune knobs and launch shapes for the same handle, batch and output mode;
+ * the kernels are twins of the ring-fed ones under names of their own (rollout_sampled_kernel, rollout_sampled_wide_kernel,
+ * split_sampled_kernel, pg_pair_sampled_kernel).
+ * There is deliberately no act_out: the action of (lane, t) is a pure function of (seed, env index, t), so a caller who
+ * needs the actions of a call regenerates them with nig_fill_actions(t) for t = counter before the call + 1 ... + n_steps.
+ * Ring-fed only, as before: nig_rollout_noise (recorded draws come with recorded actions), nig_plan_create and the mixed
+ * launches (nig_rollout_mixed*, nig_mixed_rollout*).
+ */
+int nig_rollout_sampled(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out,
+                        int64_t out_stride, float *obs_out, int64_t ld_obs, int64_t obs_step_stride,
+                        void *stream);
+
+/*
  * nig_rollout with the reference's RECORDED random draws in place of the generator's -- parity mode of the fused
  * kernels: the same kernel forms nig_rollout selects for the handle and batch (three-wave, LDS-resident wide / paired,
  * one-wave; same thresholds, same launch shapes) run base.py:157-213 end to end on the values np.random returned

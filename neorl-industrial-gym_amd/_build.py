@@ -1,6 +1,7 @@
 """Build libnig.so (HIP kernels + C ABI) for gfx950 with hipcc, in-tree.
 
-One translation unit per environment (csrc/env_*.hip) plus the C ABI (csrc/nig_api.hip), compiled
+One translation unit per environment (csrc/env_*.hip; its nig_rollout_sampled kernels in csrc/sampled_*.hip) plus the C ABI
+(csrc/nig_api.hip), compiled
 in parallel and linked into ONE shared library.  Staleness is decided by a content hash of the
 sources (mtimes do not survive a snapshot copy to another machine), stored next to the library.
 """
@@ -111,7 +112,7 @@ def build(force=False, verbose=False, jobs=None):
 # Test-only library variants (loaded through NIG_LIB_PATH, never as libnig.so): name -> (translation units recompiled, flags)
 VARIANTS = {
     # bounded ring waits + error reporting (csrc/nig_ring.hpp; tests/test_gpu_ring_limit.py)
-    "ringlimit": (["env_cr", "env_pg", "env_ra", "nig_api"], ["-DNIG_RING_SPIN_LIMIT=4000000"]),
+    "ringlimit": (["env_cr", "env_pg", "env_ra", "sampled_cr", "sampled_pg", "sampled_ra", "nig_api"], ["-DNIG_RING_SPIN_LIMIT=4000000"]),
 }
 
 

@@ -326,7 +326,14 @@ class BatchedIndustrialEnv:
             assert action_ring.shape[1:] == (self.batch, self.action_dim) and action_ring.stride(1) == self.action_dim, \
                 "action_ring is [R, A, ld >= batch] or contiguous [R, batch, A]"
             A, ld = self.action_dim, 0                                                   # row-major [R, B, A]
+        rp, fp, os_, op, ldo, so = self._rollout_outputs(n_steps, reward_out, flags_out, obs_out)
+        with torch.cuda.device(self._dev_index):
+            _lib.check(self._L.nig_rollout(self._h, int(n_steps), C.c_void_p(action_ring.data_ptr()), ld,
+                                           action_ring.stride(0), R, rp, fp, os_, op, ldo, so, self._stream()))
 
+    def _rollout_outputs(self, n_steps, reward_out, flags_out, obs_out):
+        """The output arguments of nig_rollout / nig_rollout_sampled from the optional tensors, validated:
+        (reward ptr, flags ptr, out_stride, obs ptr, ld_obs, obs_step_stride)."""
         def out(t, dtype):
             if t is None:
                 return None, 0
@@ -351,9 +358,17 @@ class BatchedIndustrialEnv:
             else:
                 assert obs_out.shape[1] == self.state_dim and obs_out.shape[2] >= self.batch
                 op, ldo, so = C.c_void_p(obs_out.data_ptr()), obs_out.stride(1), obs_out.stride(0)
+        return rp, fp, rs or fs, op, ldo, so
+
+    def rollout_sampled(self, n_steps: int, reward_out: Optional[torch.Tensor] = None,
+                        flags_out: Optional[torch.Tensor] = None, obs_out: Optional[torch.Tensor] = None):
+        """rollout() without an action ring (nig_rollout_sampled): every step draws its own uniform action of the env's
+        action Box in the kernel -- the reference's measurement loop (performance_benchmark.py:106-133).  The step with launch
+        counter t takes the action fill_actions(t) writes, so the call is bit-identical to rollout() on a ring of n_steps slots
+        filled that way; to record the actions, regenerate them with fill_actions.  Outputs as rollout()."""
+        rp, fp, os_, op, ldo, so = self._rollout_outputs(n_steps, reward_out, flags_out, obs_out)
         with torch.cuda.device(self._dev_index):
-            _lib.check(self._L.nig_rollout(self._h, int(n_steps), C.c_void_p(action_ring.data_ptr()), ld,
-                                           action_ring.stride(0), R, rp, fp, rs or fs, op, ldo, so, self._stream()))
+            _lib.check(self._L.nig_rollout_sampled(self._h, int(n_steps), rp, fp, os_, op, ldo, so, self._stream()))
 
     def rollout_noise(self, n_steps: int, action_ring: torch.Tensor, step_noise: Optional[torch.Tensor],
                       reset_noise: Optional[torch.Tensor], reward_out: torch.Tensor, flags_out: torch.Tensor,

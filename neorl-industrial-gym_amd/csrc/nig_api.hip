@@ -364,7 +364,9 @@ extern "C" {
 // quotient overflows (most likely NaN before, not measured on the device; AdvancedChemicalReactor / AdvancedPowerGrid only),
 // det_sinf's quadrant is defined for every float (results change only from |x| ~ 6.59e6 on, where |fk| >= 2^22, outside its
 // stated domain |x| <= 1e4).  Generator and every other env unchanged.
-const char *nig_version(void) { return "nig 0.7.0 (gfx950; generator nig-philox-v3)"; }
+// 0.8.0: nig_rollout_sampled (the fused rollout draws its uniform actions in the kernel).  Additive: generator and every existing
+// entry point's results unchanged.
+const char *nig_version(void) { return "nig 0.8.0 (gfx950; generator nig-philox-v3)"; }
 const char *nig_last_error(void) { return g_err; }
 
 int nig_tune(int32_t key, int64_t value)
@@ -668,13 +670,16 @@ int nig_step64(nig_handle *h, const double *actions, int64_t ld_act, const doubl
 static int rollout_impl(nig_handle *h, int32_t n_steps, const float *action_ring, int64_t ld_act, int64_t slot_stride,
                         int32_t ring_len, const double *step_noise, int64_t step_noise_stride, const double *reset_noise,
                         int64_t reset_noise_stride, int64_t ld_noise, float *reward_out, uint32_t *flags_out, int64_t out_stride,
-                        float *obs_out, int64_t ld_obs, int64_t obs_step_stride, void *stream)
+                        float *obs_out, int64_t ld_obs, int64_t obs_step_stride, void *stream, bool sampled = false)
 {
-    if (!h || !action_ring || n_steps <= 0 || ring_len <= 0) return fail(NIG_ERR_INVALID, "nig_rollout: bad argument%s");
+    // sampled (nig_rollout_sampled): no ring -- the four ring arguments are not looked at, every other check is this function's
+    if (!h || n_steps <= 0 || (!sampled && (!action_ring || ring_len <= 0))) return fail(NIG_ERR_INVALID, "nig_rollout: bad argument%s");
+    if (sampled) { action_ring = nullptr; ld_act = h->lay.ld; slot_stride = 0; ring_len = 1; }
     // ld_act == 0: the ring is ROW-MAJOR, slot s = [B][A] at action_ring + s * slot_stride (what an agent's batched output looks like)
-    const bool act_aos = ld_act == 0;
+    const bool act_aos = !sampled && ld_act == 0;
     const int A_ = SPECS[h->env].action_dim;
-    if (act_aos) {
+    if (sampled) {
+    } else if (act_aos) {
         if (step_noise || reset_noise) return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_noise: the recorded-draw launches take [A][ld_act] action rows%s");
         if (slot_stride < (int64_t)A_ * h->B || slot_stride > 0xffffffffLL)
             return fail(NIG_ERR_INVALID, "nig_rollout: row-major action ring: slot_stride smaller than one [batch][A] slot (or >= 2^32)%s");
@@ -747,7 +752,8 @@ static int rollout_impl(nig_handle *h, int32_t n_steps, const float *action_ring
         q.s.ld_noise = (uint32_t)ld_noise;
         q.nz_step_stride = (uint64_t)step_noise_stride; q.nz_reset_stride = (uint64_t)reset_noise_stride;
     }
-    launch_of(h->env)->rollout(out_mode, q, h->t + 1u, grid_for(h->B), st);
+    if (sampled) launch_of(h->env)->rollout_sampled(out_mode, q, h->t + 1u, grid_for(h->B), st);
+    else launch_of(h->env)->rollout(out_mode, q, h->t + 1u, grid_for(h->B), st);
     HIP_TRY(hipGetLastError());
     h->t += (uint32_t)n_steps;
     return ring_check(h, st, "nig_rollout");
@@ -759,6 +765,13 @@ int nig_rollout(nig_handle *h, int32_t n_steps, const float *action_ring, int64_
 {
     return rollout_impl(h, n_steps, action_ring, ld_act, slot_stride, ring_len, nullptr, 0, nullptr, 0, 0, reward_out, flags_out,
                         out_stride, obs_out, ld_obs, obs_step_stride, stream);
+}
+
+int nig_rollout_sampled(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                        float *obs_out, int64_t ld_obs, int64_t obs_step_stride, void *stream)
+{
+    return rollout_impl(h, n_steps, nullptr, 0, 0, 0, nullptr, 0, nullptr, 0, 0, reward_out, flags_out,
+                        out_stride, obs_out, ld_obs, obs_step_stride, stream, true);
 }
 
 int nig_rollout_noise(nig_handle *h, int32_t n_steps, const float *action_ring, int64_t ld_act, int64_t slot_stride,

@@ -190,6 +190,38 @@ __device__ __forceinline__ RngKey make_key(uint64_t gi, uint32_t t, uint32_t see
     return k;
 }
 
+// One uniform action of the env's Box from one generator word (nig_rollout_sampled: the fused rollout draws what
+// nig_fill_actions writes).  fill_actions_kernel's definition is (float)(low + (high - low) * u) in float64 with u = m * 2^-24,
+// m the word's top 24 bits; the forms below give the same float32 for every m (tests/test_rollout_sampled_host.py runs all 2^24
+// for every Box of nig_envs.hpp) without float64, whose every operation is in the slow issue class:
+//   [-1, 1):  -1 + m * 2^-23 is a multiple of 2^-23 below 1 in magnitude, i.e. a float32: one fused multiply-add of the
+//             (exact) conversion of m rounds nothing;
+//   [0, high): high * (m * 2^-24) in float32 -- m * 2^-24 is exact, so float32 and float64 both round the one product high * u
+//             (the float64 product of two 24-bit significands is exact, its narrowing is the float32 product's rounding);
+//   any other Box (AdvancedChemicalReactor's 273.15 .. 473.15, AdvancedPowerGrid's dispatch and tap ranges): the float64 form
+//             itself -- the float32 sum rounds twice and differs on up to 14 % of the words.
+__device__ __forceinline__ float action_from_word(uint32_t word, float low, float high)
+{
+    const float mf = (float)(word >> 8);
+    if (low == -1.0f && high == 1.0f) return __builtin_fmaf(mf, 1.0f / 8388608.0f, -1.0f);
+    if (low == 0.0f) return high * (mf * (1.0f / 16777216.0f));
+    return (float)((double)low + ((double)high - (double)low) * u01(word));
+}
+
+// The action nig_fill_actions(t) writes for the key's lane: blocks STREAM_ACTION + j of the key's counter, words in order.
+template <class Env>
+__device__ __forceinline__ void sample_action(const RngKey &k, float (&a)[Env::A])
+{
+#pragma unroll
+    for (int j = 0; 4 * j < Env::A; ++j) {
+        const u32x4 x = k.block(STREAM_ACTION + (uint32_t)j);
+        const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (4 * j + c < Env::A) a[4 * j + c] = action_from_word(w[c], Env::act_low(4 * j + c), Env::act_high(4 * j + c));
+    }
+}
+
 // Env hooks that only some envs have, callable from generic lambdas (where a discarded
 // `if constexpr` branch is still name-checked because Env is not the lambda's own parameter).
 template <class Env>
@@ -707,12 +739,18 @@ struct RolloutLds {
 // normals, two slots, counters at ring_sync) instead of this wave's own generator; the caller has staged the generator's table
 // and passed the block barrier.  State, counters and tallies stay in REGISTERS: at the two waves per SIMD of that form the
 // register file has room for them, and the step is then one dependent chain of arithmetic instead of a chain of LDS round trips.
-template <class Env, int OUT, bool PAIRED, bool FULL, bool NOFREEZE = false, int BLK = 256, bool NOISE = false, bool RING = false>
+// SAMPLED (nig_rollout_sampled): there is no action ring -- the action of the step with launch counter t is drawn here, blocks
+// STREAM_ACTION + j of the lane's key at t (sample_action: what nig_fill_actions(t) writes for the lane), at the point of the step
+// where the ring-fed form issues the refill load of the same register set, DEPTH steps ahead of its use: the rounds of those one
+// or two generator blocks run in the shadow of the step's stores, and the loop holds no global load at all.
+template <class Env, int OUT, bool PAIRED, bool FULL, bool NOFREEZE = false, int BLK = 256, bool NOISE = false, bool RING = false,
+          bool SAMPLED = false>
 __device__ __forceinline__ void rollout_body(const RolloutArgs &q, const uint32_t base, unsigned char *smem,
                                              const v4f *ring_slots = nullptr, lds_u32_t *ring_sync = nullptr)
 {
     static_assert(!NOFREEZE || FULL, "NOFREEZE is a property of whole-block launches");
     static_assert(!NOISE || !PAIRED, "injected draws: nothing to share between the steps of a pair");
+    static_assert(!SAMPLED || !NOISE, "recorded draws come with recorded actions");
     static_assert(!RING || (!NOISE && !PAIRED && FULL && NOFREEZE && Env::KS > 4 && std::is_same<typename Env::fast_noise_t, float>::value),
                   "ring-fed form: whole blocks of an env with float32 step noise");
     static_assert(BLK == 256 || (Env::COOP_RESET && !Env::COMPACT_RESET), "wide blocks: no block barrier inside the loop");
@@ -786,7 +824,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs &q, const uint32_
     // path.
     constexpr bool SHARE = PAIRED;
     static_assert(!PAIRED || (Env::SHARED_STEP_BLOCK && KS > 0 && KS <= 2), "a shared step block holds two steps");
-    const float *ring = p.actions + base;
+    [[maybe_unused]] const float *ring = p.actions + base;
     // DEPTH = steps of slack between an action load and its use = ring of register sets = loop unroll.
     // The wait for a prefetched action is in-order with the stores issued before it; at the headline
     // size a step is ~1.2 us and a streaming store takes longer than two of them to be acknowledged.
@@ -889,7 +927,9 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs &q, const uint32_
         // registers of `a` are dead by now (the load lands in place, no rotation of register sets),
         // and the in-order vmcnt wait at the top of step it+DEPTH then only needs the stores of step
         // it-1 and older to have been acknowledged -- DEPTH full steps of slack.
-        {
+        if constexpr (SAMPLED) {
+            sample_action<Env>(make_key(gi, t_base + (uint32_t)(it + DEPTH) + 1u, p.seed_lo, p.seed_hi), abuf);
+        } else {
 #pragma unroll
             for (int k = 0; k < A; ++k) abuf[k] = in_range ? (act_next + k * p.ld_act)[tid] : 0.0f;
             slot = (slot + 1 == q.ring_len) ? 0 : slot + 1;
@@ -1013,12 +1053,16 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs &q, const uint32_
     };
 
     int it = q.it0;
-    slot = it % q.ring_len;
+    if constexpr (!SAMPLED) slot = it % q.ring_len;
     if constexpr (SHARE) {
         const u32x4 x = pair_block<Env>(make_key(gi, t_base + (uint32_t)it + 1u, p.seed_lo, p.seed_hi, s_probit));
         pair_noise<Env>(x.x, x.y, s_probit, nzA);
         kept0 = x.z; kept1 = x.w;
     }
+    if constexpr (SAMPLED) {
+#pragma unroll
+        for (int j = 0; j < DEPTH; ++j) sample_action<Env>(make_key(gi, t_base + (uint32_t)(it + j) + 1u, p.seed_lo, p.seed_hi), buf[j]);
+    } else {
 #pragma unroll
     for (int j = 0; j < DEPTH; ++j) {                                  // steps it .. it + DEPTH - 1
         const float *nx = ring + (size_t)slot * q.slot_stride;
@@ -1027,6 +1071,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs &q, const uint32_
         slot = (slot + 1 == q.ring_len) ? 0 : slot + 1;
     }
     act_next = ring + (size_t)slot * q.slot_stride;                   // step it + DEPTH: the first refill
+    }
     // Drain the prologue loads HERE (vmcnt(0); expcnt/lgkmcnt untouched).  Otherwise hipcc's waitcnt
     // pass merges "prologue loads still in flight" into the loop header and every iteration inherits
     // waits sized for the first one.
@@ -1066,6 +1111,13 @@ __global__ void __launch_bounds__(BLOCK, Env::ROLLOUT_WAVES) rollout_kernel(cons
 {
     __shared__ __attribute__((aligned(16))) unsigned char smem[RolloutLds<Env, OUT>::BYTES];
     rollout_body<Env, OUT, PAIRED, FULL, false, 256, NOISE>(q, (blockIdx.x + q.block0) * BLOCK, smem);
+}
+// nig_rollout_sampled's twin (a kernel name of its own: tools that pick kernels by name never confuse the two)
+template <class Env, int OUT, bool PAIRED, bool FULL>
+__global__ void __launch_bounds__(BLOCK, Env::ROLLOUT_WAVES) rollout_sampled_kernel(const RolloutArgs q)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char smem[RolloutLds<Env, OUT>::BYTES];
+    rollout_body<Env, OUT, PAIRED, FULL, false, 256, false, false, true>(q, (blockIdx.x + q.block0) * BLOCK, smem);
 }
 
 // The wide form (envs that declare WIDE_ROLLOUT_BLOCK): whole blocks of BLK lanes of a handle on which no lane can be
@@ -1154,20 +1206,20 @@ __device__ __forceinline__ void policy_stage_dense(const nig_policy *gpol, float
 }  // namespace nig
 #include "nig_pg_lds.hpp"
 namespace nig {
-template <class Env, int OUT, int BLK, bool NOISE = false>
+template <class Env, int OUT, int BLK, bool NOISE = false, bool SAMPLED = false>
 struct wide_body {                                // default: the register-resident body without freeze handling
     static constexpr int LDS_BYTES = RolloutLds<Env, OUT, BLK>::BYTES;
     __device__ static __forceinline__ void run(const RolloutArgs &q, uint32_t base, unsigned char *smem)
     {
-        rollout_body<Env, OUT, false, true, true, BLK, NOISE>(q, base, smem);
+        rollout_body<Env, OUT, false, true, true, BLK, NOISE, false, SAMPLED>(q, base, smem);
     }
 };
-template <int OUT, int BLK, bool NOISE>
-struct wide_body<PowerGrid, OUT, BLK, NOISE> {    // PowerGrid: state staged in LDS (nig_pg_lds.hpp)
+template <int OUT, int BLK, bool NOISE, bool SAMPLED>
+struct wide_body<PowerGrid, OUT, BLK, NOISE, SAMPLED> {    // PowerGrid: state staged in LDS (nig_pg_lds.hpp)
     static constexpr int LDS_BYTES = PgLds<BLK>::BYTES;
     __device__ static __forceinline__ void run(const RolloutArgs &q, uint32_t base, unsigned char *smem)
     {
-        pg_lds_rollout_body<OUT, BLK, false, NOISE>(q, base, smem);
+        pg_lds_rollout_body<OUT, BLK, false, NOISE, false, RolloutArgs, SAMPLED>(q, base, smem);
     }
 };
 
@@ -1176,6 +1228,12 @@ __global__ void __launch_bounds__(BLK, (BLK / 256) * Env::WIDE_ROLLOUT_WAVES) ro
 {
     __shared__ __attribute__((aligned(16))) unsigned char smem[wide_body<Env, OUT, BLK, NOISE>::LDS_BYTES];
     wide_body<Env, OUT, BLK, NOISE>::run(q, q.block0 * 256u + blockIdx.x * BLK, smem);
+}
+template <class Env, int OUT, int BLK>            // nig_rollout_sampled's twin
+__global__ void __launch_bounds__(BLK, (BLK / 256) * Env::WIDE_ROLLOUT_WAVES) rollout_sampled_wide_kernel(const RolloutArgs q)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char smem[wide_body<Env, OUT, BLK, false, true>::LDS_BYTES];
+    wide_body<Env, OUT, BLK, false, true>::run(q, q.block0 * 256u + blockIdx.x * BLK, smem);
 }
 
 }  // namespace nig
@@ -2039,6 +2097,7 @@ struct EnvLaunch {
                  unsigned grid, hipStream_t);
     // does `rollout` read a ROW-MAJOR action ring ([B][A] slots, RolloutArgs.s.ld_act == 0) natively for this request?
     bool (*rows_native)(int out_mode, const RolloutArgs &);
+    void (*rollout_sampled)(int out_mode, const RolloutArgs &, uint32_t t0, unsigned grid, hipStream_t);   // nig_rollout_sampled
 };
 
 template <class Env>
@@ -2091,11 +2150,23 @@ static void launch_step64(const StepArgs &a, bool parity, unsigned grid, hipStre
 
 // NOISE (here and below): the injected-draw variants of nig_rollout_noise, instantiated for the row-major full-output
 // mode only (out_mode 3, what the headline configuration runs) -- same form selection, same launch shapes.
-template <class Env, bool PAIRED, bool FULL, bool NOISE = false>
+// SAMPLED (here and below): nig_rollout_sampled -- the twin kernels that draw their actions (rollout_sampled_kernel,
+// rollout_sampled_wide_kernel, split_sampled_kernel, pg_pair_sampled_kernel), picked by the SAME rule, thresholds and launch
+// shapes: one copy of the selection code, the kernel name is the only thing the flag changes.
+template <class Env, bool PAIRED, bool FULL, bool NOISE = false, bool SAMPLED = false>
 static void launch_rollout_blocks(int out_mode, const RolloutArgs &q, unsigned grid, hipStream_t st)
 {
     if constexpr (NOISE) {
         hipLaunchKernelGGL((rollout_kernel<Env, 3, false, FULL, true>), dim3(grid), dim3(BLOCK), 0, st, q);
+        return;
+    }
+    if constexpr (SAMPLED) {
+        switch (out_mode) {
+        case 0: hipLaunchKernelGGL((rollout_sampled_kernel<Env, 0, PAIRED, FULL>), dim3(grid), dim3(BLOCK), 0, st, q); break;
+        case 1: hipLaunchKernelGGL((rollout_sampled_kernel<Env, 1, PAIRED, FULL>), dim3(grid), dim3(BLOCK), 0, st, q); break;
+        case 2: hipLaunchKernelGGL((rollout_sampled_kernel<Env, 2, PAIRED, FULL>), dim3(grid), dim3(BLOCK), 0, st, q); break;
+        default: hipLaunchKernelGGL((rollout_sampled_kernel<Env, 3, PAIRED, FULL>), dim3(grid), dim3(BLOCK), 0, st, q); break;
+        }
         return;
     }
     switch (out_mode) {
@@ -2107,7 +2178,7 @@ static void launch_rollout_blocks(int out_mode, const RolloutArgs &q, unsigned g
 }
 
 // the batch's whole 256-lane blocks in one launch without lane predication, a ragged last block in its own
-template <class Env, bool PAIRED, bool NOISE = false>
+template <class Env, bool PAIRED, bool NOISE = false, bool SAMPLED = false>
 static void launch_rollout_form(int out_mode, const RolloutArgs &q, unsigned /*grid*/, hipStream_t st)
 {
     const unsigned n_full = q.s.B / BLOCK;
@@ -2132,8 +2203,8 @@ static void launch_rollout_form(int out_mode, const RolloutArgs &q, unsigned /*g
                                                      (last_round == 0 || 4u * last_round >= 3u * per_round)));
         if (plain && n_full > 0 && even_rounds) {
             r.block0 = 0;
-            launch_split_blocks<Env, BLOCK / 64, NOISE>(out_mode, r, n_full, st);
-            if (q.s.B % BLOCK) { r.block0 = n_full; launch_rollout_blocks<Env, PAIRED, false, NOISE>(out_mode, r, 1u, st); }
+            launch_split_blocks<Env, BLOCK / 64, NOISE, SAMPLED>(out_mode, r, n_full, st);
+            if (q.s.B % BLOCK) { r.block0 = n_full; launch_rollout_blocks<Env, PAIRED, false, NOISE, SAMPLED>(out_mode, r, 1u, st); }
             return;
         }
     }
@@ -2157,6 +2228,13 @@ static void launch_rollout_form(int out_mode, const RolloutArgs &q, unsigned /*g
             if (n_wide > 0 && n_wide >= q.s.wide_min_blocks) {
                 r.block0 = 0;
                 if constexpr (NOISE) hipLaunchKernelGGL((rollout_wide_kernel<Env, 3, WB, true>), dim3(n_wide), dim3(WB), 0, st, r);
+                else if constexpr (SAMPLED)
+                switch (out_mode) {
+                case 0: hipLaunchKernelGGL((rollout_sampled_wide_kernel<Env, 0, WB>), dim3(n_wide), dim3(WB), 0, st, r); break;
+                case 1: hipLaunchKernelGGL((rollout_sampled_wide_kernel<Env, 1, WB>), dim3(n_wide), dim3(WB), 0, st, r); break;
+                case 2: hipLaunchKernelGGL((rollout_sampled_wide_kernel<Env, 2, WB>), dim3(n_wide), dim3(WB), 0, st, r); break;
+                default: hipLaunchKernelGGL((rollout_sampled_wide_kernel<Env, 3, WB>), dim3(n_wide), dim3(WB), 0, st, r); break;
+                }
                 else
                 switch (out_mode) {
                 case 0: hipLaunchKernelGGL((rollout_wide_kernel<Env, 0, WB>), dim3(n_wide), dim3(WB), 0, st, r); break;
@@ -2171,15 +2249,22 @@ static void launch_rollout_form(int out_mode, const RolloutArgs &q, unsigned /*g
                 // default one per compute unit): the paired form -- a producer wave draws the step's normals beside every
                 // stepping wave (rollout_pg_pair_kernel, nig_pg_lds.hpp)
                 if (first == 0 && n_full > 0 && q.s.split_blocks != 0 && n_full <= q.s.split_blocks) {
-                    r.block0 = 0;
-                    if constexpr (NOISE) hipLaunchKernelGGL((rollout_pg_pair_kernel<3, true>), dim3(n_full), dim3(512), 0, st, r);
-                    else
-                    switch (out_mode) {
 #ifdef NIG_DIAG_PG_PAIR_LDS            // (diagnostic builds only: round 3's LDS-resident stepping waves, for same-box A/Bs)
 #define NIG_PG_PAIR_REG false
 #else
 #define NIG_PG_PAIR_REG true
 #endif
+                    r.block0 = 0;
+                    if constexpr (NOISE) hipLaunchKernelGGL((rollout_pg_pair_kernel<3, true>), dim3(n_full), dim3(512), 0, st, r);
+                    else if constexpr (SAMPLED)
+                    switch (out_mode) {        // (the same stepper per output mode as below)
+                    case 0: hipLaunchKernelGGL((pg_pair_sampled_kernel<0, NIG_PG_PAIR_REG>), dim3(n_full), dim3(512), 0, st, r); break;
+                    case 1: hipLaunchKernelGGL((pg_pair_sampled_kernel<1, NIG_PG_PAIR_REG>), dim3(n_full), dim3(512), 0, st, r); break;
+                    case 2: hipLaunchKernelGGL((pg_pair_sampled_kernel<2, false>), dim3(n_full), dim3(512), 0, st, r); break;
+                    default: hipLaunchKernelGGL((pg_pair_sampled_kernel<3, false>), dim3(n_full), dim3(512), 0, st, r); break;
+                    }
+                    else
+                    switch (out_mode) {
                     case 0: hipLaunchKernelGGL((rollout_pg_pair_kernel<0, false, NIG_PG_PAIR_REG>), dim3(n_full), dim3(512), 0, st, r); break;
                     case 1: hipLaunchKernelGGL((rollout_pg_pair_kernel<1, false, NIG_PG_PAIR_REG>), dim3(n_full), dim3(512), 0, st, r); break;
                     // (with an observation trajectory the LDS-resident stepping body stays: its state image IS the transposing
@@ -2196,6 +2281,13 @@ static void launch_rollout_form(int out_mode, const RolloutArgs &q, unsigned /*g
                 r.block0 = first;
                 const unsigned nb = n_full - first;
                 if constexpr (NOISE) hipLaunchKernelGGL((rollout_wide_kernel<Env, 3, BLOCK, true>), dim3(nb), dim3(BLOCK), 0, st, r);
+                else if constexpr (SAMPLED)
+                switch (out_mode) {
+                case 0: hipLaunchKernelGGL((rollout_sampled_wide_kernel<Env, 0, BLOCK>), dim3(nb), dim3(BLOCK), 0, st, r); break;
+                case 1: hipLaunchKernelGGL((rollout_sampled_wide_kernel<Env, 1, BLOCK>), dim3(nb), dim3(BLOCK), 0, st, r); break;
+                case 2: hipLaunchKernelGGL((rollout_sampled_wide_kernel<Env, 2, BLOCK>), dim3(nb), dim3(BLOCK), 0, st, r); break;
+                default: hipLaunchKernelGGL((rollout_sampled_wide_kernel<Env, 3, BLOCK>), dim3(nb), dim3(BLOCK), 0, st, r); break;
+                }
                 else
                 switch (out_mode) {
                 case 0: hipLaunchKernelGGL((rollout_wide_kernel<Env, 0, BLOCK>), dim3(nb), dim3(BLOCK), 0, st, r); break;
@@ -2207,8 +2299,8 @@ static void launch_rollout_form(int out_mode, const RolloutArgs &q, unsigned /*g
             }
         }
     }
-    if (n_full > first) { r.block0 = first; launch_rollout_blocks<Env, PAIRED, true, NOISE>(out_mode, r, n_full - first, st); }
-    if (q.s.B % BLOCK) { r.block0 = n_full; launch_rollout_blocks<Env, PAIRED, false, NOISE>(out_mode, r, 1u, st); }
+    if (n_full > first) { r.block0 = first; launch_rollout_blocks<Env, PAIRED, true, NOISE, SAMPLED>(out_mode, r, n_full - first, st); }
+    if (q.s.B % BLOCK) { r.block0 = n_full; launch_rollout_blocks<Env, PAIRED, false, NOISE, SAMPLED>(out_mode, r, 1u, st); }
 }
 
 // nig_rollout's row-major action ring (ld_act == 0): true when EVERY kernel launch_rollout_form<Env, false> starts for this
@@ -2238,6 +2330,23 @@ static bool rollout_rows_native(int out_mode, const RolloutArgs &q)
 // the envs the reference can record draws for (ChemicalReactor, PowerGrid, RobotAssembly): nig_rollout_noise
 template <class Env> struct noise_rollout : std::bool_constant<(Env::ID <= 2)> {};
 
+template <class Env, bool SAMPLED>
+static void launch_rollout_paired(int out_mode, const RolloutArgs &q, uint32_t t0, unsigned grid, hipStream_t st)
+{
+    if constexpr (Env::SHARED_STEP_BLOCK) {
+        RolloutArgs r = q;
+        if ((t0 & 1u) == 0u) {                    // starts on the second step of a pair: peel it
+            r.n_steps = 1;
+            launch_rollout_form<Env, false, false, SAMPLED>(out_mode, r, grid, st);
+            if (q.n_steps == 1) return;
+            r.n_steps = q.n_steps; r.it0 = 1;
+        }
+        launch_rollout_form<Env, true, false, SAMPLED>(out_mode, r, grid, st);
+    } else {
+        launch_rollout_form<Env, false, false, SAMPLED>(out_mode, q, grid, st);
+    }
+}
+
 template <class Env>
 static void launch_rollout_env(int out_mode, const RolloutArgs &q, uint32_t t0, unsigned grid, hipStream_t st)
 {
@@ -2245,19 +2354,22 @@ static void launch_rollout_env(int out_mode, const RolloutArgs &q, uint32_t t0, 
         if constexpr (noise_rollout<Env>::value) launch_rollout_form<Env, false, true>(3, q, grid, st);
         return;
     }
-    if constexpr (Env::SHARED_STEP_BLOCK) {
-        RolloutArgs r = q;
-        if ((t0 & 1u) == 0u) {                    // starts on the second step of a pair: peel it
-            r.n_steps = 1;
-            launch_rollout_form<Env, false>(out_mode, r, grid, st);
-            if (q.n_steps == 1) return;
-            r.n_steps = q.n_steps; r.it0 = 1;
-        }
-        launch_rollout_form<Env, true>(out_mode, r, grid, st);
-    } else {
-        launch_rollout_form<Env, false>(out_mode, q, grid, st);
-    }
+    launch_rollout_paired<Env, false>(out_mode, q, t0, grid, st);
 }
+
+// nig_rollout_sampled: the same selection on the twin kernels.  Declared everywhere, DEFINED (and with it every sampled kernel
+// instantiated) only in the env's sampled_*.hip translation unit (NIG_DEFINE_ENV_SAMPLED): the env_*.hip units hold exactly the
+// instantiations they held before the twins existed -- their code objects do not move by an instruction (profiles/isa_diff.py) --
+// and the twins compile beside them in parallel.
+template <class Env>
+void launch_rollout_sampled_env(int out_mode, const RolloutArgs &q, uint32_t t0, unsigned grid, hipStream_t st)
+#ifdef NIG_SAMPLED_TU
+{
+    launch_rollout_paired<Env, true>(out_mode, q, t0, grid, st);
+}
+#else
+;
+#endif
 
 template <class Env>
 static void launch_policy(const PolicyArgs &q, unsigned grid, hipStream_t st)
@@ -2317,7 +2429,7 @@ static const EnvLaunch *env_launch_table()
     static const EnvLaunch T = {launch_step<Env>, Env::HAS_ACT64 ? launch_step64<Env> : nullptr, launch_rollout_env<Env>, launch_policy<Env>,
                                 (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp<Env> : nullptr,
                                 (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp_shield<Env> : nullptr,
-                                launch_reset<Env>, launch_fill<Env>, rollout_rows_native<Env>};
+                                launch_reset<Env>, launch_fill<Env>, rollout_rows_native<Env>, launch_rollout_sampled_env<Env>};
     return &T;
 }
 
@@ -2328,3 +2440,6 @@ void nig_launch_mixed_rollout(int out_mode, const nig::MixedArgs &m, unsigned gr
 
 #define NIG_DEFINE_ENV_LAUNCH(EnvType, fn_name) \
     const nig::EnvLaunch *fn_name() { return nig::env_launch_table<nig::EnvType>(); }
+// sampled_*.hip (compiled with NIG_SAMPLED_TU defined before this header): the env's nig_rollout_sampled launcher and kernels
+#define NIG_DEFINE_ENV_SAMPLED(EnvType) \
+    template void nig::launch_rollout_sampled_env<nig::EnvType>(int, const nig::RolloutArgs &, uint32_t, unsigned, hipStream_t);

@@ -170,9 +170,15 @@ __device__ __forceinline__ void pg_pair_producer(const QA &q, const uint32_t bas
 // the policy's own draws come from the producer's slot: policy_finish), the optional outputs are those of
 // rollout_policy_kernel (the observation acted on, row-major through the image's transposed reads; the policy's action
 // rows; reward + flag rows), run-time switches as there.  Bit-identical to rollout_policy_kernel (tests/test_gpu_split.py).
-template <int OUT, int BLK, bool PROD = false, bool NOISE = false, bool POLICY = false, class QA = RolloutArgs>
+// SAMPLED (nig_rollout_sampled): no action ring -- the one action register set is refilled, at the point of the step where the
+// ring-fed form issues its load, with the NEXT step's draw (sample_action: blocks STREAM_ACTION + 0, 1 of the lane's key at
+// counter t + 1).  That point is the quietest of the step for the generator: the action, the generation sums and the reward's
+// early terms have just died, no table read is in flight (an action needs none: rounds, a conversion and a fused multiply-add
+// per word), and the voltages' own blocks follow, so the sixteen extra rounds queue in front of the eight the step runs anyway.
+template <int OUT, int BLK, bool PROD = false, bool NOISE = false, bool POLICY = false, class QA = RolloutArgs, bool SAMPLED = false>
 __device__ __forceinline__ void pg_lds_rollout_body(const QA &q, const uint32_t base, unsigned char *smem)
 {
+    static_assert(!SAMPLED || (!NOISE && !POLICY), "sampled actions: the open loop on the generator's own draws");
     using Env = PowerGrid;
     constexpr int S = Env::S, A = Env::A;
     using Lds = PgLds<BLK>;
@@ -239,7 +245,7 @@ __device__ __forceinline__ void pg_lds_rollout_body(const QA &q, const uint32_t 
     constexpr int DEPTH = 1;
     float buf[DEPTH][A];
     [[maybe_unused]] int slot = 0;
-    if constexpr (!POLICY) slot = q.it0 % q.ring_len;
+    if constexpr (!POLICY && !SAMPLED) slot = q.it0 % q.ring_len;
     [[maybe_unused]] const float *act_next = nullptr;
     const int it0 = arg_it0(q);
     float *rew_row = p.reward ? p.reward + base + (size_t)it0 * q.out_stride : nullptr;
@@ -363,7 +369,9 @@ __device__ __forceinline__ void pg_lds_rollout_body(const QA &q, const uint32_t 
             }
             ngen7 = ngen[7];
             // refill this action register set (step it + DEPTH), issued before the step's stores: see rollout_body
-            if constexpr (!POLICY) {
+            if constexpr (SAMPLED) {
+                sample_action<Env>(make_key(gi, t_base + (uint32_t)it + 2u, p.seed_lo, p.seed_hi), abuf);
+            } else if constexpr (!POLICY) {
 #ifdef NIG_DIAG_PG_NOACTLOAD           // (diagnostic builds only, profiles/r05: no global load in the loop -- the action is a cheap hash of lane
             // and step instead; what do the action reads cost?)
 #pragma unroll
@@ -604,7 +612,9 @@ __device__ __forceinline__ void pg_lds_rollout_body(const QA &q, const uint32_t 
         }
     };
 
-    if constexpr (!POLICY) {
+    if constexpr (SAMPLED) {
+        sample_action<Env>(make_key(gi, t_base + (uint32_t)it0 + 1u, p.seed_lo, p.seed_hi), buf[0]);
+    } else if constexpr (!POLICY) {
 #pragma unroll
     for (int j = 0; j < DEPTH; ++j) {
         load_action(ring + (size_t)slot * q.slot_stride, buf[j]);
@@ -662,6 +672,28 @@ __global__ void __launch_bounds__(512, 2) rollout_pg_pair_kernel(const RolloutAr
             (lds_u32_t *)(smem + PL::OFF_SYNC) + wave * 4);
         NIG_RING_REPORT(q.s.ring_err, (lds_u32_t *)(smem + PL::OFF_SYNC) + wave * 4, threadIdx.x & 63u);
     } else pg_lds_rollout_body<OUT, 256, true, NOISE>(q, base, smem);
+}
+// nig_rollout_sampled's twin: the same roles, the same stepper per output mode.  The draw of the action stays in the STEPPING
+// wave (both steppers refill their action set where they used to load it): the producer's two-slot ring carries normals only,
+// and a slot layout of its own for actions would be a second protocol to keep for two generator blocks a step.
+template <int OUT, bool REG>
+__global__ void __launch_bounds__(512, 2) pg_pair_sampled_kernel(const RolloutArgs q)
+{
+    using PL = std::conditional_t<REG, PgPairRegLds<OUT>, PgPairLdsT<false>>;
+    __shared__ __attribute__((aligned(16))) unsigned char smem[PL::BYTES];
+    float4 *const s_probit = reinterpret_cast<float4 *>(smem + PgLds<256>::OFF_PROBIT);
+    for (int i_ = (int)threadIdx.x; i_ < 768; i_ += 512) s_probit[i_] = NIG_PROBIT[i_];
+    if (threadIdx.x < 16u) reinterpret_cast<uint32_t *>(smem + PL::OFF_SYNC)[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint32_t base = (blockIdx.x + q.block0) * 256u;
+    const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (wave >= 4u) pg_pair_producer<false, false, RolloutArgs, PL>(q, base, smem, wave - 4u, threadIdx.x & 63u);
+    else if constexpr (REG) {
+        rollout_body<PowerGrid, OUT, false, true, true, 256, false, true, true>(
+            q, base, smem, reinterpret_cast<const v4f *>(smem + PL::OFF_NZ) + wave * (PL::K * PL::SLOT_V4),
+            (lds_u32_t *)(smem + PL::OFF_SYNC) + wave * 4);
+        NIG_RING_REPORT(q.s.ring_err, (lds_u32_t *)(smem + PL::OFF_SYNC) + wave * 4, threadIdx.x & 63u);
+    } else pg_lds_rollout_body<OUT, 256, true, false, false, RolloutArgs, true>(q, base, smem);
 }
 
 // The closed loop's stepping wave with its state in REGISTERS (paired form, calls WITHOUT the observation stream): the loop of

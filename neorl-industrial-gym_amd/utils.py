@@ -172,7 +172,7 @@ def _evaluate_batched(agent, env: BatchedIndustrialEnv, n_episodes: int, step_no
 
 
 def uniform_action_statistics(env_id: str, batch: int, episodes_per_lane: int, device="cuda:0", seed: int = 0xBEEF,
-                              plan_steps: int = 250, outputs: str = "min") -> Dict[str, Any]:
+                              plan_steps: int = 250, outputs: str = "min", action_source: str = "ring") -> Dict[str, Any]:
     """Episode statistics of the reference's measurement loop (performance_benchmark.py:106-133: a uniform random action per
     step, reset on done) in FAST MODE -- fused rollout launches, in-kernel generator, auto-reset -- over the first
     `episodes_per_lane` episodes of every lane.  A fixed episode count per lane is an unbiased sample ("episodes finished
@@ -181,12 +181,18 @@ def uniform_action_statistics(env_id: str, batch: int, episodes_per_lane: int, d
     Returns sums over the counted episodes: episodes, steps, viol (base.py:179-183 violation counts), crit, c0..c2 (steps on
     which built-in constraint k failed), term / trunc / shut (how the episodes ended), ret (sum of rewards), hist (episode
     lengths, index = length), launches.  outputs: "min" = reward + flag rows; "full" also writes the observation
-    trajectory (the kernel instantiation bench.py's headline times)."""
+    trajectory (the kernel instantiation bench.py's headline times).
+    action_source: "ring" (the default) fills the ring with `plan_steps` fill_actions launches before every rollout launch;
+    "generated" allocates no ring and runs no fill launches -- rollout_sampled draws every step's action in the kernel, from the
+    same action stream (at the launch's own counters t instead of 7000 + t: the same distribution)."""
+    if action_source not in ("ring", "generated"):
+        raise ValueError(f"action_source is 'ring' or 'generated', not {action_source!r}")
+    generated = action_source == "generated"
     L = _lib
     env = make_batched(env_id, batch, device=device, seed=seed, autoreset=True)
     dev, B, K, P = env.device, env.batch, int(episodes_per_lane), int(plan_steps)
     env.reset()
-    ring = torch.empty(P, env.action_dim, env.ld, dtype=torch.float32, device=dev)
+    ring = None if generated else torch.empty(P, env.action_dim, env.ld, dtype=torch.float32, device=dev)
     rew = torch.empty(P, env.ld, dtype=torch.float32, device=dev)
     fl = torch.empty(P, env.ld, dtype=torch.int32, device=dev)
     traj = torch.empty(P, B, env.state_dim, dtype=torch.float32, device=dev) if outputs == "full" else None
@@ -197,10 +203,13 @@ def uniform_action_statistics(env_id: str, batch: int, episodes_per_lane: int, d
     hist = torch.zeros(env.max_episode_steps + 1, dtype=torch.int64, device=dev)
     launches = t = 0
     while True:
-        for s in range(P):
-            t += 1
-            env.fill_actions(7000 + t, ring[s])
-        env.rollout(P, ring, rew, fl, traj)
+        if generated:
+            env.rollout_sampled(P, rew, fl, traj)
+        else:
+            for s in range(P):
+                t += 1
+                env.fill_actions(7000 + t, ring[s])
+            env.rollout(P, ring, rew, fl, traj)
         f = fl[:, :B]
         done = (f & (L.FLAG_TERMINATED | L.FLAG_TRUNCATED)) != 0
         cum = done.cumsum(0, dtype=torch.int32)
