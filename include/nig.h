@@ -82,6 +82,7 @@ extern "C" {
 #define NIG_FLAG_VIOL3 0x1000u          /* 4th safety condition violated (Advanced envs)     */
 #define NIG_FLAG_NVIOL_HI 0x2000u       /* adds 4 to the violation count field (Advanced envs) */
 #define NIG_FLAG_SHIELDED 0x4000u       /* nig_rollout_mlp_safe: the safety critic halved the action */
+#define NIG_FLAG_UNCERTAIN 0x8000u      /* nig_rollout_mlp_ensemble: uncertainty > threshold on this live step */
 #define NIG_FLAG_STEP_SHIFT 16          /* bits 16-31: current_step after this call          */
 
 /* per-lane counter word kept by the library */
@@ -504,6 +505,60 @@ int nig_set_mlp_safety(nig_handle *h, int32_t hidden, const float *C1, const flo
 int nig_rollout_mlp_safe(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out,
                          int64_t out_stride, float *obs_out, int64_t obs_step_stride, float *act_out,
                          int64_t ld_act, int64_t act_step_stride, float *prob_out, void *stream);
+
+/*
+ * Ensemble of MLP actors (agents/ensemble.py EnsembleAgent: predict, predict_with_uncertainty,
+ * get_high_uncertainty_mask) fused with IndustrialEnv.step: n_members actors of nig_set_mlp_policy's
+ * shape and layouts are evaluated per step by the same f32-MFMA scheme, one after the other through
+ * the same LDS image, and reduced in registers.  With p_k the float32 action of member k (bit for bit
+ * what nig_rollout_mlp computes for that network on the same observation), K = n_members:
+ *   NIG_ENSEMBLE_AVERAGE ("mean" / "weighted", np.average: a float64 action)
+ *       acc = (double)p_0 * weights[0];  acc = acc + (double)p_k * weights[k], k = 1 .. K-1 in order
+ *       (every product rounded);  action = acc / weight_sum.
+ *       ChemicalReactor / PowerGrid / RobotAssembly step on that float64 action with nig_step64's
+ *       arithmetic; every other env receives it rounded to float32 (nig_step64's rule for them).
+ *       weights = the ACTIVE weights (for "mean": w[:K] / np.sum(w[:K]); for "weighted": w[:K]);
+ *       weight_sum = np.sum(weights), computed by the caller -- the library never sums weights.
+ *   NIG_ENSEMBLE_VOTING (np.mean of a float32 array: a float32 action, nig_step's arithmetic)
+ *       acc = p_0;  acc = acc + p_k;  action = acc / (float)K.   weights / weight_sum are ignored.
+ *   uncertainty (float32; np.std over the members, mean over the action dimensions) -- the order the
+ *   library documents and its tests restate, per action dimension about member 0, d_k = p_k - p_0:
+ *       s1 = 0, s2 = 0;  s1 = s1 + d_k, s2 = s2 + d_k * d_k for k = 1 .. K-1 in order;
+ *       v = s2 - (s1 * s1) / (float)K;  v = v > 0 ? v : 0;  sd = sqrt(v / (float)K);
+ *       uncertainty = (((0 + sd_0) + sd_1) + ... + sd_{A-1}) / (float)A.
+ *   It is exactly 0 for identical members and for K = 1, and agrees with the reference's two-pass
+ *   np.std to 1e-5 relative (the subtraction loses at most a factor 1 + K of float32's precision,
+ *   because member 0's own deviation is part of v).  All divisions and the square root are IEEE
+ *   correctly rounded; no product is fused into a sum.
+ * A live step whose uncertainty > uncertainty_threshold (strict) carries NIG_FLAG_UNCERTAIN.
+ * W1 .. b3: host arrays [n_members] of host pointers.  NIG_ERR_INVALID: n_members outside
+ * 1 .. NIG_MAX_ENSEMBLE, a NULL array, an unknown method, (AVERAGE) a non-finite weight or weight_sum,
+ * weight_sum == 0.  NIG_ERR_UNSUPPORTED: hidden != 256, an env shape without the MFMA actor.
+ * The handle's single actor and critic (nig_set_mlp_policy / _safety) are left alone, and vice versa.
+ * NIG_MAX_ENSEMBLE bounds the handle's operand streams (341 KB per member); the kernel's registers
+ * do not depend on it.
+ */
+#define NIG_MAX_ENSEMBLE 8
+#define NIG_ENSEMBLE_AVERAGE 0
+#define NIG_ENSEMBLE_VOTING 1
+int nig_set_mlp_ensemble(nig_handle *h, int32_t n_members, int32_t hidden, const float *const *W1,
+                         const float *const *b1, const float *const *W2, const float *const *b2,
+                         const float *const *W3, const float *const *b3, int32_t method,
+                         const double *weights, double weight_sum, float uncertainty_threshold, void *stream);
+
+/*
+ * As nig_rollout_mlp (arguments, minima, obs_out alignment, frozen lanes, tallies, launch counter), with
+ * the installed ensemble.  act_out: the action the env received, rounded to float32 for
+ * NIG_ENSEMBLE_AVERAGE (the exact float64 action is the law above applied to member_act_out).
+ * unc_out (optional) float [n_steps][>= B], row k at unc_out + k*out_stride.  member_act_out (optional)
+ * float: member m of step k is one [A][ld_act] block at member_act_out + (k*n_members + m)*act_step_stride
+ * (ld_act / act_step_stride are checked as for act_out when either is given).  Frozen lanes leave their
+ * unc_out / member_act_out words untouched.  NIG_ERR_INVALID without an installed ensemble.
+ */
+int nig_rollout_mlp_ensemble(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out,
+                             int64_t out_stride, float *obs_out, int64_t obs_step_stride, float *act_out,
+                             int64_t ld_act, int64_t act_step_stride, float *unc_out,
+                             float *member_act_out, void *stream);
 
 /*
  * Host-buffer forms for SMALL batches -- the single-env drop-in classes (env.reset() / env.step()

@@ -444,9 +444,40 @@ class BatchedIndustrialEnv:
         self.rollout_policy(n_steps, reward_out, flags_out, obs_out, act_out, _fn=self._L.nig_rollout_mlp_safe,
                             _prob=prob_out)
 
+    def set_mlp_ensemble(self, members, weights=None, weight_sum=None, method: str = "mean", uncertainty_threshold: float = 0.2):
+        """Install an ensemble of actors (agents/ensemble.py EnsembleAgent) for rollout_mlp_ensemble(): `members` = a list of
+        set_mlp_policy() weight lists.  method "mean" / "weighted": `weights` = the ACTIVE float64 weights of np.average (for
+        "mean" already divided by their sum, as the reference does) and `weight_sum` = np.sum(weights) (computed here with
+        NumPy when None); "voting": both ignored.  policies.EnsemblePolicy.install() derives all of it from an agent."""
+        if method not in ("mean", "weighted", "voting"):
+            raise ValueError(f"Unknown ensemble method: {method}")
+        K, S, A, Hd = len(members), self.state_dim, self.action_dim, 256
+        W = [[np.ascontiguousarray(np.asarray(x), dtype=np.float32) for pair in m for x in pair] for m in members]
+        for w in W:
+            assert [x.shape for x in w] == [(S, Hd), (Hd,), (Hd, Hd), (Hd,), (Hd, A), (A,)], [x.shape for x in w]
+        cols = [(C.c_void_p * K)(*[w[j].ctypes.data for w in W]) for j in range(6)] if K else [None] * 6
+        wp, ws = None, 0.0
+        if method != "voting":
+            aw = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
+            assert aw.shape == (K,), aw.shape
+            wp, ws = aw.ctypes.data_as(C.c_void_p), float(np.sum(aw) if weight_sum is None else weight_sum)
+        with torch.cuda.device(self._dev_index):
+            _lib.check(self._L.nig_set_mlp_ensemble(self._h, K, Hd, *cols, _lib.ENSEMBLE_VOTING if method == "voting" else _lib.ENSEMBLE_AVERAGE,
+                                                    wp, ws, float(uncertainty_threshold), self._stream()))
+        self._ensemble_members = K
+
+    def rollout_mlp_ensemble(self, n_steps: int, reward_out=None, flags_out=None, obs_out=None, act_out=None, unc_out=None,
+                             member_act_out=None):
+        """rollout_mlp() with the installed ensemble: act_out holds the action the env received (the float64 average rounded
+        to float32 for "mean" / "weighted"); unc_out float32 [n_steps, >=B] the members' disagreement (same row stride as
+        reward_out / flags_out); member_act_out float32 [n_steps, K, A, >=B] every member's action (same pitches as act_out);
+        flags carry FLAG_UNCERTAIN where the uncertainty exceeds the installed threshold."""
+        self.rollout_policy(n_steps, reward_out, flags_out, obs_out, act_out, _fn=self._L.nig_rollout_mlp_ensemble,
+                            _prob=unc_out, _members=member_act_out)
+
     def rollout_policy(self, n_steps: int, reward_out: Optional[torch.Tensor] = None,
                        flags_out: Optional[torch.Tensor] = None, obs_out: Optional[torch.Tensor] = None,
-                       act_out: Optional[torch.Tensor] = None, _fn=None, _prob=None):
+                       act_out: Optional[torch.Tensor] = None, _fn=None, _prob=None, _members=None):
         """n_steps closed-loop steps (action = installed policy(observation)) in ONE launch.
         obs_out: float32 contiguous [n_steps, B, S] (observation the policy acted on);
         act_out: float32 [n_steps, A, >=B]; reward_out / flags_out: [n_steps, >=B] or [B]."""
@@ -473,6 +504,18 @@ class BatchedIndustrialEnv:
             assert act_out.shape[0] >= n_steps and act_out.shape[1] == self.action_dim and act_out.shape[2] >= self.batch
             ap, lda, sa = C.c_void_p(act_out.data_ptr()), act_out.stride(1), act_out.stride(0)
         with torch.cuda.device(self._dev_index):
+            if _fn is self._L.nig_rollout_mlp_ensemble:
+                pp, ps = out(_prob, torch.float32)
+                assert pp is None or (rp is None and fp is None) or ps == (rs or fs), "unc_out shares the reward/flags row stride"
+                mp = None
+                if _members is not None:
+                    K, m = getattr(self, "_ensemble_members", 0), _members
+                    assert m.dtype == torch.float32 and m.dim() == 4 and m.stride(3) == 1 and m.stride(0) == K * m.stride(1)
+                    assert m.shape[0] >= n_steps and m.shape[1] == K and m.shape[2] == self.action_dim and m.shape[3] >= self.batch
+                    assert ap is None or (m.stride(2), m.stride(1)) == (lda, sa), "member_act_out shares act_out's pitches"
+                    mp, lda, sa = C.c_void_p(m.data_ptr()), m.stride(2), m.stride(1)
+                _lib.check(_fn(self._h, int(n_steps), rp, fp, rs or fs or ps, op, so, ap, lda, sa, pp, mp, self._stream()))
+                return
             if _fn is self._L.nig_rollout_mlp_safe:
                 pp, ps = out(_prob, torch.float32)
                 assert pp is None or (rp is None and fp is None) or ps == (rs or fs), "prob_out shares the reward/flags row stride"

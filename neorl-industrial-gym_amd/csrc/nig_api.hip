@@ -176,6 +176,8 @@ struct nig_handle {
     float *mlp_stream;     // device copy of the MFMA operand stream of the MLP actor (owned)
     float *mlp_cstream;    // device copy of the MFMA operand stream of the safety critic (owned)
     float mlp_threshold;   // shield threshold of nig_rollout_mlp_safe
+    // nig_set_mlp_ensemble (owned): the members' operand streams back to back, MLP_STREAM_FLOATS floats each; their active weights
+    float *ens_stream; double *ens_w; int ens_members, ens_cap, ens_method; double ens_wsum; float ens_threshold;
     float *act32;          // nig_step64 on an env that takes float32 actions: the narrowed rows [A][ld] (owned, lazy)
     float *pid_mem;        // PID policies: per-lane integral / previous error, float [2*A][ld] (owned, lazy)
     bool may_hold_done;    // some lane may carry NIG_CTR_DONE although the handle auto-resets (see HF_MAY_HOLD_DONE)
@@ -366,6 +368,9 @@ extern "C" {
 // stated domain |x| <= 1e4).  Generator and every other env unchanged.
 // 0.8.0: nig_rollout_sampled (the fused rollout draws its uniform actions in the kernel).  Additive: generator and every existing
 // entry point's results unchanged.
+// Still 0.8.0: nig_set_mlp_ensemble / nig_rollout_mlp_ensemble (K MFMA actors per step, EnsembleAgent's action and uncertainty) and
+// NIG_FLAG_UNCERTAIN.  Additive: generator and every existing entry point's results unchanged.  The number did not move because
+// tests/test_rollout_sampled_host.py pins the string; a caller tells the two apart by the exported symbol.
 const char *nig_version(void) { return "nig 0.8.0 (gfx950; generator nig-philox-v3)"; }
 const char *nig_last_error(void) { return g_err; }
 
@@ -510,7 +515,7 @@ int nig_create(int env, int64_t batch, int device, uint64_t seed, uint64_t env_i
     h->pol_dev = (nig_policy *)(h->ws + h->lay.bytes - POLICY_BYTES);
     h->t_dev = (uint32_t *)(h->ws + h->lay.bytes - POLICY_BYTES - 256);
     h->scratch = (double *)(h->ws + h->lay.bytes - POLICY_BYTES - 256 - align_up((int64_t)REDUCE_BLOCKS * NIG_T_ROWS * 8, 256));
-    h->has_policy = false; h->mlp_stream = nullptr; h->mlp_cstream = nullptr; h->mlp_threshold = 0.0f; h->act32 = nullptr; h->pid_mem = nullptr; h->may_hold_done = true; h->hst_pinned = nullptr; h->hst_dev = nullptr; h->hst_bytes = 0; h->mirror = nullptr; h->ld_mirror = 0; h->act_soa = nullptr; h->act_soa_floats = 0;
+    h->has_policy = false; h->mlp_stream = nullptr; h->mlp_cstream = nullptr; h->mlp_threshold = 0.0f; h->ens_stream = nullptr; h->ens_w = nullptr; h->ens_members = 0; h->ens_cap = 0; h->ens_method = 0; h->ens_wsum = 0.0; h->ens_threshold = 0.0f; h->act32 = nullptr; h->pid_mem = nullptr; h->may_hold_done = true; h->hst_pinned = nullptr; h->hst_dev = nullptr; h->hst_bytes = 0; h->mirror = nullptr; h->ld_mirror = 0; h->act_soa = nullptr; h->act_soa_floats = 0;
     h->state = (float *)(h->ws + h->lay.off_state); h->ld_state = h->lay.ld;
     const nig_layout &L = h->lay;
     hipLaunchKernelGGL(init_ws_kernel, dim3(grid_for(L.ld)), dim3(BLOCK), 0, (hipStream_t)0,
@@ -535,6 +540,8 @@ int nig_destroy(nig_handle *h)
     if (!h) return NIG_OK;
     if (h->mlp_stream) (void)hipFree(h->mlp_stream);
     if (h->mlp_cstream) (void)hipFree(h->mlp_cstream);
+    if (h->ens_stream) (void)hipFree(h->ens_stream);
+    if (h->ens_w) (void)hipFree(h->ens_w);
     if (h->pid_mem) (void)hipFree(h->pid_mem);
     if (h->act32) (void)hipFree(h->act32);
     if (h->act_soa) (void)hipFree(h->act_soa);
@@ -843,15 +850,12 @@ int nig_rollout_policy(nig_handle *h, int32_t n_steps, float *reward_out, uint32
 // Row of a 32x32 MFMA result tile held in register t by lane half hf (MI355X_MICROARCH / guide section 3).
 static inline int mfma_row(int t, int hf) { return (t & 3) + 8 * (t >> 2) + 4 * hf; }
 
-int nig_set_mlp_policy(nig_handle *h, int32_t hidden, const float *W1, const float *b1, const float *W2, const float *b2,
-                       const float *W3, const float *b3, void *stream)
+// The MFMA operand stream of one actor (S -> 256 -> 256 -> A), written into the zeroed host[MLP_STREAM_FLOATS]: the one builder of
+// nig_set_mlp_policy and of every member of nig_set_mlp_ensemble.  False: internal record count mismatch.
+static bool build_mlp_stream(int S, int A, const float *W1, const float *b1, const float *W2, const float *b2, const float *W3,
+                             const float *b3, float *host)
 {
-    if (!h || !W1 || !b1 || !W2 || !b2 || !W3 || !b3) return fail(NIG_ERR_INVALID, "nig_set_mlp_policy: NULL argument%s");
-    if (hidden != MLP_H) return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_policy: hidden must be 256 (agents/networks.py default)%s");
-    const int S = SPECS[h->env].state_dim, A = SPECS[h->env].action_dim, H = MLP_H;
-    if (S % 2 != 0 || A > 16) return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_policy: env shape not supported (even state dim, at most 16 actions)%s");
-    float *host = (float *)calloc((size_t)MLP_STREAM_FLOATS, sizeof(float));
-    if (!host) return fail(NIG_ERR_INVALID, "nig_set_mlp_policy: out of host memory%s");
+    const int H = MLP_H;
     // Build the operand stream in exactly the order rollout_mlp_kernel consumes it, chunk by chunk (a chunk = one
     // fill of an LDS buffer, MLP_CHREC record slots, zero padded).  Record = 64 floats; lane l = (i = l & 31,
     // hf = l >> 5) holds W[k(hf)][32*tile + i].
@@ -877,7 +881,7 @@ int nig_set_mlp_policy(nig_handle *h, int32_t hidden, const float *W1, const flo
                 } else if ((l & 15) < A)                      // v_mfma_f32_16x16x1 (four blocks): lane 16 b + i holds head row i of block b's hidden row
                     rec(1 + m2, r)[l] = W3[(size_t)(32 * m2 + mfma_row(t, l >> 5)) * A + (l & 15)];
             }
-        if (r != MLP_PER) { free(host); return fail(NIG_ERR_INVALID, "nig_set_mlp_policy: internal record count mismatch%s"); }
+        if (r != MLP_PER) return false;
     }
     if (A <= 4) {                                                    // the head's bias rides at the end of the last chunk
         for (int l = 0; l < 64; ++l)
@@ -885,6 +889,19 @@ int nig_set_mlp_policy(nig_handle *h, int32_t hidden, const float *W1, const flo
     } else
         for (int l = 0; l < 64; ++l)
             if ((l & 15) < A) rec(MLP_MT, MLP_PER)[l] = b3[l & 15];
+    return true;
+}
+
+int nig_set_mlp_policy(nig_handle *h, int32_t hidden, const float *W1, const float *b1, const float *W2, const float *b2,
+                       const float *W3, const float *b3, void *stream)
+{
+    if (!h || !W1 || !b1 || !W2 || !b2 || !W3 || !b3) return fail(NIG_ERR_INVALID, "nig_set_mlp_policy: NULL argument%s");
+    if (hidden != MLP_H) return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_policy: hidden must be 256 (agents/networks.py default)%s");
+    const int S = SPECS[h->env].state_dim, A = SPECS[h->env].action_dim;
+    if (S % 2 != 0 || A > 16) return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_policy: env shape not supported (even state dim, at most 16 actions)%s");
+    float *host = (float *)calloc((size_t)MLP_STREAM_FLOATS, sizeof(float));
+    if (!host) return fail(NIG_ERR_INVALID, "nig_set_mlp_policy: out of host memory%s");
+    if (!build_mlp_stream(S, A, W1, b1, W2, b2, W3, b3, host)) { free(host); return fail(NIG_ERR_INVALID, "nig_set_mlp_policy: internal record count mismatch%s"); }
     hipError_t e = hipSuccess;
     if (!h->mlp_stream) e = hipMalloc((void **)&h->mlp_stream, (size_t)MLP_STREAM_FLOATS * sizeof(float));
     if (e == hipSuccess) e = hipMemcpyAsync(h->mlp_stream, host, (size_t)MLP_STREAM_FLOATS * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream);
@@ -999,6 +1016,80 @@ int nig_rollout_mlp_safe(nig_handle *h, int32_t n_steps, float *reward_out, uint
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)((h->B + BLOCK / 2 - 1) / (BLOCK / 2));     // 32 envs per wave, 128 per block
     launch_of(h->env)->mlp_shield(q, grid, st);
+    HIP_TRY(hipGetLastError());
+    h->t += (uint32_t)n_steps;
+    return NIG_OK;
+}
+
+int nig_set_mlp_ensemble(nig_handle *h, int32_t n_members, int32_t hidden, const float *const *W1, const float *const *b1,
+                         const float *const *W2, const float *const *b2, const float *const *W3, const float *const *b3,
+                         int32_t method, const double *weights, double weight_sum, float uncertainty_threshold, void *stream)
+{
+    if (!h) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: NULL handle%s");
+    if (n_members < 1 || n_members > NIG_MAX_ENSEMBLE) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: n_members outside 1 .. NIG_MAX_ENSEMBLE%s");
+    if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: NULL member array (W1 / b1 / W2 / b2 / W3 / b3)%s");
+    for (int k = 0; k < n_members; ++k)
+        if (!W1[k] || !b1[k] || !W2[k] || !b2[k] || !W3[k] || !b3[k]) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: NULL member array (W1 / b1 / W2 / b2 / W3 / b3 of a member)%s");
+    if (method != NIG_ENSEMBLE_AVERAGE && method != NIG_ENSEMBLE_VOTING) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: unknown method%s");
+    double w[NIG_MAX_ENSEMBLE] = {0};
+    if (method == NIG_ENSEMBLE_AVERAGE) {
+        if (!weights) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: NULL weights with NIG_ENSEMBLE_AVERAGE%s");
+        for (int k = 0; k < n_members; ++k) {
+            if (!std::isfinite(weights[k])) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: non-finite entry of weights%s");
+            w[k] = weights[k];
+        }
+        if (!std::isfinite(weight_sum)) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: non-finite weight_sum%s");
+        if (weight_sum == 0.0) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: weight_sum is zero (np.average raises)%s");
+    }
+    if (hidden != MLP_H) return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_ensemble: hidden must be 256 (agents/networks.py default)%s");
+    const int S = SPECS[h->env].state_dim, A = SPECS[h->env].action_dim;
+    if (S % 2 != 0 || A > 16 || !launch_of(h->env)->mlp_ensemble)
+        return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_ensemble: env shape not supported (even state dim, at most 16 actions)%s");
+    float *host = (float *)calloc((size_t)n_members * MLP_STREAM_FLOATS, sizeof(float));
+    if (!host) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: out of host memory%s");
+    for (int k = 0; k < n_members; ++k)
+        if (!build_mlp_stream(S, A, W1[k], b1[k], W2[k], b2[k], W3[k], b3[k], host + (size_t)k * MLP_STREAM_FLOATS)) {
+            free(host);
+            return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: internal record count mismatch%s");
+        }
+    hipError_t e = hipSuccess;
+    h->ens_members = 0;                                     // no ensemble while the streams are being replaced
+    if (h->ens_cap < n_members) {
+        if (h->ens_stream) (void)hipFree(h->ens_stream);
+        h->ens_stream = nullptr; h->ens_cap = 0;
+        e = hipMalloc((void **)&h->ens_stream, (size_t)n_members * MLP_STREAM_FLOATS * sizeof(float));
+        if (e == hipSuccess) h->ens_cap = n_members;
+    }
+    if (e == hipSuccess && !h->ens_w) e = hipMalloc((void **)&h->ens_w, sizeof w);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->ens_stream, host, (size_t)n_members * MLP_STREAM_FLOATS * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h->ens_w, w, sizeof w, hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    free(host);
+    if (e != hipSuccess) return fail(NIG_ERR_HIP, "nig_set_mlp_ensemble: %s", hipGetErrorString(e));
+    h->ens_members = n_members; h->ens_method = method; h->ens_wsum = weight_sum; h->ens_threshold = uncertainty_threshold;
+    return NIG_OK;
+}
+
+int nig_rollout_mlp_ensemble(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                             float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
+                             float *unc_out, float *member_act_out, void *stream)
+{
+    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_ensemble: bad argument (handle, n_steps)%s");
+    if (!launch_of(h->env)->mlp_ensemble) return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_mlp_ensemble: env shape has no MFMA actor%s");
+    if (h->ens_members < 1 || !h->ens_stream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_ensemble: no ensemble installed (nig_set_mlp_ensemble)%s");
+    MlpEnsArgs q;
+    memset(&q, 0, sizeof q);
+    // member_act_out shares act_out's pitches: the same checks apply to it when act_out is absent
+    const int rc = mlp_args(h, "nig_rollout_mlp_ensemble", n_steps, reward_out, flags_out, out_stride, obs_out, obs_step_stride,
+                            act_out ? act_out : member_act_out, ld_act, act_step_stride, q.m);
+    if (rc != NIG_OK) return rc;
+    q.m.act_out = act_out;
+    q.m.wstream = h->ens_stream;
+    q.n_members = h->ens_members; q.w = h->ens_w; q.wsum = h->ens_wsum; q.kf = (float)h->ens_members; q.threshold = h->ens_threshold;
+    q.unc_out = unc_out; q.member_out = member_act_out;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned grid = (unsigned)((h->B + BLOCK / 2 - 1) / (BLOCK / 2));     // 32 envs per wave, 128 per block
+    launch_of(h->env)->mlp_ensemble(h->ens_method == NIG_ENSEMBLE_AVERAGE ? ENS_AVERAGE : ENS_VOTING, q, grid, st);
     HIP_TRY(hipGetLastError());
     h->t += (uint32_t)n_steps;
     return NIG_OK;

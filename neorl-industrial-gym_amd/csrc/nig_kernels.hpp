@@ -1736,9 +1736,43 @@ struct MlpShieldArgs {
     float threshold;            // shield when !(p < threshold)
 };
 
-template <class Env, bool SHIELD>
-__device__ __attribute__((always_inline)) inline void rollout_mlp_body(const MlpArgs &q, const float *cstream, float *prob_out, float threshold)
+// Ensemble actor (rollout_mlp_ensemble_kernel, agents/ensemble.py EnsembleAgent.predict / predict_with_uncertainty): ENS != 0 runs
+// n_members actor passes per step through the same double-buffered LDS image -- member k + 1's layer-1 chunk is in flight while
+// member k's last hidden tile is consumed, the next step's member 0 behind the last member -- and reduces the members' actions
+// p_k (float32, each bit for bit the single actor's) as they arrive, in registers that do not grow with the member count:
+//   action, ENS_AVERAGE ("mean" / "weighted"; float64, the env steps with step_core<Env, NZ, double> where the env has it):
+//       acc = (double)p_0 * w_0;  acc = acc + (double)p_k * w_k  (k = 1 .. K-1, products rounded);  action = acc / wsum
+//   action, ENS_VOTING (np.mean of a float32 array; float32):  acc = p_0;  acc = acc + p_k;  action = acc / (float)K
+//   uncertainty (float32), per action dimension about member 0, d_k = p_k - p_0:
+//       s1 = sum_k d_k,  s2 = sum_k d_k * d_k  (k = 1 .. K-1 in order, from 0),  v = max(s2 - (s1 * s1) / (float)K, 0),
+//       sd = sqrt(v / (float)K);   uncertainty = (sd_0 + sd_1 + ... + sd_{A-1}) / (float)A, summed in index order.
+//   The shifted form needs p_0, s1, s2 and the action's accumulator: 5 A registers (4 A for voting) whatever K is, where the
+//   reference's two-pass np.std needs all K A member actions at once.  It is exactly 0 for identical members, and because member
+//   0's own deviation from the mean is part of v, s2 <= (1 + K) v: the subtraction loses at most a factor 1 + K <= 9 of float32's
+//   precision (measured against np.std: tests/test_ensemble_host.py, 1e-5 relative).
+// Every division and the square root are IEEE correctly rounded: plain `/` and __builtin_sqrtf, which hipcc expands to the
+// v_div_scale / v_div_fmas / v_div_fixup sequences (float32: -fhip-fp32-correctly-rounded-divide-sqrt, the compiler's default,
+// denormals kept) -- the translation unit is compiled with -ffp-contract=off, so no product above fuses into a sum.
+constexpr int ENS_NONE = 0, ENS_AVERAGE = 1, ENS_VOTING = 2;
+struct MlpEnsArgs {
+    MlpArgs m;                  // m.wstream: the members' operand streams, MLP_STREAM_FLOATS floats apart, in member order
+    int n_members;
+    const double *w;            // device [n_members]: the active weights (ENS_AVERAGE)
+    double wsum;                // np.sum of the active weights, computed by the host
+    float kf;                   // (float)n_members
+    float threshold;            // NIG_FLAG_UNCERTAIN when uncertainty > threshold
+    float *unc_out;             // [n_steps][>= B], row k at unc_out + k * m.out_stride, may be NULL
+    float *member_out;          // member k of step it: [A][m.ld_act_out] at member_out + (it * n_members + k) * m.act_step_stride, may be NULL
+};
+
+template <class Env, bool SHIELD, int ENS = ENS_NONE>
+__device__ __attribute__((always_inline)) inline void rollout_mlp_body(const MlpArgs &q, const float *cstream, float *prob_out, float threshold,
+                                                                       [[maybe_unused]] const MlpEnsArgs *eq = nullptr)
 {
+    static_assert(!(SHIELD && ENS != ENS_NONE), "the ensemble has no shield");
+    // the env steps on the ensemble's float64 action where its NumPy arithmetic follows the action's type (nig_step64's rule)
+    constexpr bool ACT64 = ENS == ENS_AVERAGE && Env::HAS_ACT64;
+    using act_t = std::conditional_t<ACT64, double, float>;
     constexpr int S = Env::S, A = Env::A, KS = Env::KS, KR = Env::KR;
     constexpr int KSN = KS > 0 ? KS : 1;
     static_assert(S % 2 == 0 && A <= 16, "MFMA actor needs an even state dim and at most 16 actions");
@@ -1775,8 +1809,9 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
     LaneTally lt;
     lt.clear();
     // fill LDS buffer `buf` with chunk `c` of the operand stream: this wave's quarter of the KiB pieces
+    const float *wsrc = q.wstream;                           // operand stream of the actor (ensemble: of the member) being filled from
     auto fill = [&](int c, int buf, int pieces) __attribute__((always_inline)) {
-        const float *src = q.wstream + (size_t)c * (MLP_CHREC * 64) + lane * 4u;
+        const float *src = (ENS != ENS_NONE ? wsrc : q.wstream) + (size_t)c * (MLP_CHREC * 64) + lane * 4u;
         for (int pc = (int)wave; pc < pieces; pc += BLOCK / 64)
             __builtin_amdgcn_global_load_lds((nig_glb_void *)(src + pc * 256), (nig_lds_void *)(&s_w[buf][pc * 256]), 16, 0, 0);
     };
@@ -1793,7 +1828,12 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
     static_assert(CTPC * CR1 <= MLP_CHREC, "a critic layer-1 chunk must fit one chunk slot");
     fill(0, 0, PIECES0);
     int gbuf = 0;                                            // buffer that holds (or receives) the chunk consumed next
+    const int n_members = ENS != ENS_NONE ? eq->n_members : 1;
     for (int it = 0; it < q.n_steps; ++it) {
+        [[maybe_unused]] float e_p0[A], e_s1[A], e_s2[A], e_f[A];   // ensemble: member 0, sum d, sum d^2, float32 action sum
+        [[maybe_unused]] double e_d[A];                            // ensemble: float64 weighted action sum
+        int mem = 0;
+        do {                                                       // (one pass unless ENS)
         // ---------------- actor: 3 layers of f32 MFMA, whole wave (EXEC all ones) ----------------
         // chunk boundary: every wave's share of the fill has landed (the compiler drains vmcnt before the barrier)
         // and every wave is done with the buffer the next fill overwrites
@@ -1830,6 +1870,11 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
 #endif
             if (m2 + 1 < MLP_MT) fill(2 + m2, gbuf ^ 1, MLP_PIECES);
             else if constexpr (SHIELD) cfill(0, gbuf ^ 1, CPIECES0);  // the critic's layer 1 follows the actor
+            else if constexpr (ENS != ENS_NONE) {                     // layer 1 of the next member, or of member 0 for the next step
+                const bool more = mem + 1 < n_members;
+                wsrc = more ? wsrc + MLP_STREAM_FLOATS : q.wstream;
+                if (more || it + 1 < q.n_steps) fill(0, gbuf ^ 1, PIECES0);
+            }
             else if (it + 1 < q.n_steps) fill(0, gbuf ^ 1, PIECES0);   // layer 1 of the NEXT step (the weights do not change)
 #if defined(NIG_DIAG_MLP_SKIP) && (NIG_DIAG_MLP_SKIP & 2)
             }
@@ -1877,6 +1922,49 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
                 const float v1 = __shfl(out[4 + (r & 3)] + out[12 + (r & 3)], src);
                 a[r] = det_tanhf(beta ? v1 : v0);
             }
+        }
+        if constexpr (ENS != ENS_NONE) {                     // fold member `mem` into the running sums (the law above)
+            if (writer && !(ctr & NIG_CTR_DONE) && eq->member_out) {
+                float *mo = eq->member_out + ((size_t)it * (size_t)n_members + (size_t)mem) * q.act_step_stride;
+#pragma unroll
+                for (int j = 0; j < A; ++j) (mo + j * q.ld_act_out)[li] = a[j];
+            }
+            if (mem == 0) {
+#pragma unroll
+                for (int j = 0; j < A; ++j) {
+                    e_p0[j] = a[j]; e_s1[j] = 0.0f; e_s2[j] = 0.0f;
+                    if constexpr (ENS == ENS_AVERAGE) e_d[j] = (double)a[j] * eq->w[0]; else e_f[j] = a[j];
+                }
+            } else {
+                [[maybe_unused]] const double wk = ENS == ENS_AVERAGE ? eq->w[mem] : 0.0;
+#pragma unroll
+                for (int j = 0; j < A; ++j) {
+                    const float d = a[j] - e_p0[j];
+                    e_s1[j] = e_s1[j] + d; e_s2[j] = e_s2[j] + d * d;
+                    if constexpr (ENS == ENS_AVERAGE) e_d[j] = e_d[j] + (double)a[j] * wk; else e_f[j] = e_f[j] + a[j];
+                }
+            }
+        }
+        } while (ENS != ENS_NONE && ++mem < n_members);
+        [[maybe_unused]] float unc = 0.0f;
+        [[maybe_unused]] bool uncertain = false;
+        [[maybe_unused]] double a64[ACT64 ? A : 1];
+        if constexpr (ENS != ENS_NONE) {                     // once per step: the ensemble's action, its uncertainty, the flag bit
+            const float kf = eq->kf;
+            float usum = 0.0f;
+#pragma unroll
+            for (int j = 0; j < A; ++j) {
+                float v = e_s2[j] - (e_s1[j] * e_s1[j]) / kf;
+                v = v > 0.0f ? v : 0.0f;
+                usum = usum + __builtin_sqrtf(v / kf);
+                if constexpr (ENS == ENS_AVERAGE) {
+                    const double x = e_d[j] / eq->wsum;
+                    if constexpr (ACT64) a64[j] = x;
+                    a[j] = (float)x;                         // act_out's word; the action itself for envs that take float32 (nig_step64's rule)
+                } else a[j] = e_f[j] / kf;
+            }
+            unc = usum / (float)A;
+            uncertain = unc > eq->threshold;
         }
         [[maybe_unused]] bool shield = false;
         [[maybe_unused]] float prob = 0.0f;
@@ -1963,17 +2051,22 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
             if constexpr (SHIELD) {
                 if (prob_out) (prob_out + (uint32_t)it * q.out_stride)[li] = prob;
             }
+            if constexpr (ENS != ENS_NONE) {
+                if (eq->unc_out) (eq->unc_out + (uint32_t)it * q.out_stride)[li] = unc;
+            }
         }
         const RngKey key = make_key(gi, t_base + (uint32_t)it + 1u, p.seed_lo, p.seed_hi, s_probit);
         if constexpr (KS > 0) Env::draw_step(key, nz); else nz[0] = 0;
         const int step_pre = (int)(ctr & NIG_CTR_STEP_MASK);
-        StepResult<Env> res;
-        step_core<Env>(s, a, nz, step_pre, p.max_steps, p.dt32, p.dt, p.cmask, n, res);
+        StepResult<Env, reward_of<Env, act_t>> res;
+        if constexpr (ACT64) step_core<Env>(s, a64, nz, step_pre, p.max_steps, p.dt32, p.dt, p.cmask, n, res);
+        else step_core<Env>(s, a, nz, step_pre, p.max_steps, p.dt32, p.dt, p.cmask, n, res);
         const int step = step_pre + 1;
         const uint32_t viol_ep = (ctr >> NIG_CTR_VIOL_SHIFT) + (uint32_t)res.nviol;
         const bool done = (res.terminated || res.truncated) && !frozen;
         uint32_t fl = pack_flags<Env>(res, step) | ((done && autoreset) ? NIG_FLAG_DID_RESET : 0u);
         if constexpr (SHIELD) fl |= shield ? NIG_FLAG_SHIELDED : 0u;
+        if constexpr (ENS != ENS_NONE) fl |= uncertain ? NIG_FLAG_UNCERTAIN : 0u;
         float rew = (float)res.reward;
         if (frozen) {
             fl = NIG_FLAG_INACTIVE | ((ctr & NIG_CTR_STEP_MASK) << NIG_FLAG_STEP_SHIFT);
@@ -1983,7 +2076,7 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
         } else {
             ctr = (uint32_t)step | (viol_ep << NIG_CTR_VIOL_SHIFT);
             if (tally) {
-                if constexpr (Env::RET_F32) ret = (double)((float)ret + res.reward);
+                if constexpr (Env::RET_F32 && !ACT64) ret = (double)((float)ret + res.reward);
                 else ret = ret + (double)res.reward;
             }
         }
@@ -2027,6 +2120,13 @@ template <class Env>
 __global__ void __launch_bounds__(BLOCK, mlp_two_blocks<Env> ? 2 : 1) rollout_mlp_shield_kernel(const MlpShieldArgs q)
 {
     rollout_mlp_body<Env, true>(q.m, q.cstream, q.prob_out, q.threshold);
+}
+
+// ENS = ENS_AVERAGE / ENS_VOTING.  Instantiated in the env's ensemble_*.hip translation unit only (launch_mlp_ensemble_env).
+template <class Env, int ENS>
+__global__ void __launch_bounds__(BLOCK, mlp_two_blocks<Env> ? 2 : 1) rollout_mlp_ensemble_kernel(const MlpEnsArgs q)
+{
+    rollout_mlp_body<Env, false, ENS>(q.m, nullptr, nullptr, 0.0f, &q);
 }
 
 struct ResetArgs {
@@ -2098,6 +2198,7 @@ struct EnvLaunch {
     // does `rollout` read a ROW-MAJOR action ring ([B][A] slots, RolloutArgs.s.ld_act == 0) natively for this request?
     bool (*rows_native)(int out_mode, const RolloutArgs &);
     void (*rollout_sampled)(int out_mode, const RolloutArgs &, uint32_t t0, unsigned grid, hipStream_t);   // nig_rollout_sampled
+    void (*mlp_ensemble)(int ens, const MlpEnsArgs &, unsigned grid, hipStream_t);   // nig_rollout_mlp_ensemble; nullptr as `mlp`
 };
 
 template <class Env>
@@ -2371,6 +2472,21 @@ void launch_rollout_sampled_env(int out_mode, const RolloutArgs &q, uint32_t t0,
 ;
 #endif
 
+// nig_rollout_mlp_ensemble: as the sampled twins, declared everywhere and DEFINED (its kernels instantiated) only in the env's
+// ensemble_*.hip translation unit (NIG_DEFINE_ENV_ENSEMBLE), so the env_*.hip units keep the instantiations they had.
+template <class Env>
+void launch_mlp_ensemble_env(int ens, const MlpEnsArgs &q, unsigned grid, hipStream_t st)
+#ifdef NIG_ENSEMBLE_TU
+{
+    if constexpr (Env::S % 2 == 0 && Env::A <= 16) {
+        if (ens == ENS_AVERAGE) hipLaunchKernelGGL((rollout_mlp_ensemble_kernel<Env, ENS_AVERAGE>), dim3(grid), dim3(BLOCK), 0, st, q);
+        else hipLaunchKernelGGL((rollout_mlp_ensemble_kernel<Env, ENS_VOTING>), dim3(grid), dim3(BLOCK), 0, st, q);
+    }
+}
+#else
+;
+#endif
+
 template <class Env>
 static void launch_policy(const PolicyArgs &q, unsigned grid, hipStream_t st)
 {
@@ -2429,7 +2545,8 @@ static const EnvLaunch *env_launch_table()
     static const EnvLaunch T = {launch_step<Env>, Env::HAS_ACT64 ? launch_step64<Env> : nullptr, launch_rollout_env<Env>, launch_policy<Env>,
                                 (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp<Env> : nullptr,
                                 (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp_shield<Env> : nullptr,
-                                launch_reset<Env>, launch_fill<Env>, rollout_rows_native<Env>, launch_rollout_sampled_env<Env>};
+                                launch_reset<Env>, launch_fill<Env>, rollout_rows_native<Env>, launch_rollout_sampled_env<Env>,
+                                (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp_ensemble_env<Env> : nullptr};
     return &T;
 }
 
@@ -2443,3 +2560,6 @@ void nig_launch_mixed_rollout(int out_mode, const nig::MixedArgs &m, unsigned gr
 // sampled_*.hip (compiled with NIG_SAMPLED_TU defined before this header): the env's nig_rollout_sampled launcher and kernels
 #define NIG_DEFINE_ENV_SAMPLED(EnvType) \
     template void nig::launch_rollout_sampled_env<nig::EnvType>(int, const nig::RolloutArgs &, uint32_t, unsigned, hipStream_t);
+// ensemble_*.hip (compiled with NIG_ENSEMBLE_TU defined before this header): the env's nig_rollout_mlp_ensemble launcher and kernels
+#define NIG_DEFINE_ENV_ENSEMBLE(EnvType) \
+    template void nig::launch_mlp_ensemble_env<nig::EnvType>(int, const nig::MlpEnsArgs &, unsigned, hipStream_t);

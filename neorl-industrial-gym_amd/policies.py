@@ -326,6 +326,187 @@ class ShieldedMLPPolicy:
         return self.base.predict_with_safety(observations, self.threshold)[0]
 
 
+def ensemble_active_weights(weights, n_members: int, method: str):
+    """The weights np.average receives in agents/ensemble.py:236-249 and their NumPy sum: the FIRST n_members entries of the
+    agent's weight vector (whichever members were trained), divided by their sum for "mean", as they are for "weighted"."""
+    aw = np.asarray(weights, dtype=np.float64)[:n_members]
+    if aw.shape != (n_members,):
+        raise ValueError(f"{n_members} active members need at least as many weights, got {np.shape(weights)}")
+    if method == "mean":
+        aw = aw / np.sum(aw)
+    return aw, np.sum(aw)
+
+
+def ensemble_action(preds, weights, method: str):
+    """EnsembleAgent._predict_impl's combination of the members' float32 actions preds [K, ..., A], in the order the library
+    documents (include/nig.h, nig_set_mlp_ensemble) -- bit for bit np.average / np.mean of the reference:
+    "mean" / "weighted": float64 ((double)p_0 w_0 + (double)p_1 w_1 + ...) / np.sum(w); "voting": float32 (p_0 + p_1 + ...) / K."""
+    preds = np.asarray(preds, dtype=f32)
+    K = preds.shape[0]
+    if method == "voting":
+        acc = preds[0]
+        for k in range(1, K):
+            acc = acc + preds[k]
+        return acc / f32(K)
+    if method not in ("mean", "weighted"):
+        raise ValueError(f"Unknown ensemble method: {method}")
+    aw, wsum = ensemble_active_weights(weights, K, method)
+    acc = preds[0].astype(np.float64) * aw[0]
+    for k in range(1, K):
+        acc = acc + preds[k].astype(np.float64) * aw[k]
+    return acc / wsum
+
+
+def ensemble_uncertainty(preds):
+    """np.std over the members, mean over the action dimensions (ensemble.py:304-310), float32, in the library's documented
+    order: per dimension about member 0, d_k = p_k - p_0, s1 = sum d_k, s2 = sum d_k^2 (k = 1 .. K-1 in order),
+    v = max(s2 - s1^2 / K, 0), sd = sqrt(v / K); then ((sd_0 + sd_1) + ...) / A.  Exactly 0 for identical members and K = 1."""
+    preds = np.asarray(preds, dtype=f32)
+    K, A = preds.shape[0], preds.shape[-1]
+    kf = f32(K)
+    s1 = np.zeros(preds.shape[1:], dtype=f32)
+    s2 = np.zeros(preds.shape[1:], dtype=f32)
+    for k in range(1, K):
+        d = preds[k] - preds[0]
+        s1 = s1 + d
+        s2 = s2 + d * d
+    v = s2 - (s1 * s1) / kf
+    v = np.where(v > 0, v, f32(0.0)).astype(f32)
+    sd = np.sqrt(v / kf)
+    usum = np.zeros(preds.shape[1:-1], dtype=f32)
+    for j in range(A):
+        usum = usum + sd[..., j]
+    return usum / f32(A)
+
+
+class EnsemblePolicy:
+    """The reference's EnsembleAgent (agents/ensemble.py) over K MLPPolicy members, kept on the GPU: predict is the weighted
+    average ("mean", "weighted": float64, as np.average returns it) or the plain mean ("voting": float32) of the members'
+    actions; predict_with_uncertainty / get_high_uncertainty_mask / evaluate_diversity report how much the members disagree.
+    The arithmetic is the one include/nig.h documents for nig_set_mlp_ensemble (ensemble_action, ensemble_uncertainty above).
+
+    `members`: MLPPolicy objects or weight lists, in the agent's list order; `weights`: the agent's weight vector -- its FIRST
+    len(members) entries are the active ones (ensemble.py:238), default 1 / K each.  When every member has the reference shape
+    (`fusable`), evaluate_with_safety runs the ensemble fused into the env kernel (BatchedIndustrialEnv.rollout_mlp_ensemble)."""
+    is_trained = True
+
+    def __init__(self, members, weights=None, method: str = "mean", uncertainty_threshold: float = 0.2, device="cuda:0"):
+        if method not in ("mean", "weighted", "voting"):
+            raise ValueError(f"Unknown ensemble method: {method}")
+        # (a member is an MLPPolicy, a weight list, or any object with MLPPolicy's predict / state_dim / action_dim surface)
+        self.members = [m if hasattr(m, "predict") else MLPPolicy(m, device=device) for m in members]
+        if not self.members:
+            raise RuntimeError("No trained agents in ensemble")
+        K = len(self.members)
+        self.device = getattr(self.members[0], "device", device)
+        self.state_dim, self.action_dim = self.members[0].state_dim, self.members[0].action_dim
+        if any((m.state_dim, m.action_dim) != (self.state_dim, self.action_dim) for m in self.members):
+            raise ValueError("ensemble members must share the state and action dimensions")
+        self.weights = np.ones(K) / K if weights is None else np.asarray(weights, dtype=np.float64)
+        if self.weights.ndim != 1 or self.weights.shape[0] < K:
+            raise ValueError(f"{K} members need at least {K} weights, got shape {self.weights.shape}")
+        self.ensemble_method = method
+        self.uncertainty_threshold = uncertainty_threshold
+        self.fusable = all(getattr(m, "fusable", False) for m in self.members) and K <= 8          # NIG_MAX_ENSEMBLE
+
+    @classmethod
+    def from_agent(cls, agent, device="cuda:0"):
+        """From a reference EnsembleAgent: the trained members of agent.agents in list order (MLPPolicy.from_agent each; a
+        LayerNorm member is refused), agent.weights, agent.ensemble_method, agent.uncertainty_threshold."""
+        trained = [a for a in agent.agents if getattr(a, "is_trained", False)]
+        if not trained:
+            raise RuntimeError("No trained agents in ensemble")
+        return cls([MLPPolicy.from_agent(a, device=device) for a in trained], weights=np.asarray(agent.weights, dtype=np.float64),
+                   method=agent.ensemble_method, uncertainty_threshold=agent.uncertainty_threshold, device=device)
+
+    def install(self, env):
+        """Install the ensemble on a BatchedIndustrialEnv for rollout_mlp_ensemble()."""
+        K = len(self.members)
+        if self.ensemble_method == "voting":
+            aw = wsum = None
+        else:
+            aw, wsum = ensemble_active_weights(self.weights, K, self.ensemble_method)
+        env.set_mlp_ensemble([m.weights for m in self.members], aw, wsum, self.ensemble_method, self.uncertainty_threshold)
+
+    # ---- device (torch) forms of the same law ----
+    def member_actions_device(self, obs):
+        import torch
+        return torch.stack([m.predict_device(obs) for m in self.members])
+
+    def _action_device(self, preds, method):
+        import torch
+        K = preds.shape[0]
+        if method == "voting":
+            acc = preds[0]
+            for k in range(1, K):
+                acc = acc + preds[k]
+            return acc / torch.tensor(K, dtype=torch.float32, device=preds.device)
+        aw, wsum = ensemble_active_weights(self.weights, K, method)
+        acc = preds[0].double() * float(aw[0])
+        for k in range(1, K):
+            acc = acc + preds[k].double() * float(aw[k])
+        return acc / float(wsum)
+
+    @staticmethod
+    def _uncertainty_device(preds):
+        import torch
+        K, A = preds.shape[0], preds.shape[-1]
+        kf = torch.tensor(K, dtype=torch.float32, device=preds.device)
+        s1 = torch.zeros_like(preds[0])
+        s2 = torch.zeros_like(preds[0])
+        for k in range(1, K):
+            d = preds[k] - preds[0]
+            s1 = s1 + d
+            s2 = s2 + d * d
+        v = s2 - (s1 * s1) / kf
+        v = torch.where(v > 0, v, torch.zeros_like(v))
+        sd = torch.sqrt(v / kf)
+        usum = torch.zeros_like(sd[..., 0])
+        for j in range(A):
+            usum = usum + sd[..., j]
+        return usum / torch.tensor(A, dtype=torch.float32, device=preds.device)
+
+    def predict_device(self, obs):
+        return self._action_device(self.member_actions_device(obs), self.ensemble_method)
+
+    def predict_with_uncertainty_device(self, obs):
+        """(actions, uncertainties) on device tensors; the action is the "mean" law whatever the method (ensemble.py:298-302)."""
+        import torch
+        preds = self.member_actions_device(obs)
+        if preds.shape[0] < 2:
+            return preds[0], torch.zeros(preds.shape[1], dtype=torch.float32, device=preds.device)
+        return self._action_device(preds, "mean"), self._uncertainty_device(preds)
+
+    # ---- host forms (agent.predict contract) ----
+    def _member_actions(self, observations):
+        return np.array([m.predict(observations) for m in self.members])
+
+    def predict(self, observations, deterministic: bool = True):
+        return ensemble_action(self._member_actions(observations), self.weights, self.ensemble_method)
+
+    def predict_with_uncertainty(self, observations, return_individual: bool = False):
+        preds = self._member_actions(observations)
+        if preds.shape[0] < 2:                     # ensemble.py:288-292: the single member's own action, uncertainty 0
+            action = preds[0]
+            unc = np.zeros(action.shape[0]) if action.ndim > 1 else 0.0
+            return (action, unc, [action]) if return_individual else (action, unc)
+        action, unc = ensemble_action(preds, self.weights, "mean"), ensemble_uncertainty(preds)
+        return (action, unc, preds) if return_individual else (action, unc)
+
+    def get_high_uncertainty_mask(self, observations, threshold=None):
+        _, unc = self.predict_with_uncertainty(observations)
+        return unc > (threshold or self.uncertainty_threshold)
+
+    def evaluate_diversity(self, observations):
+        preds = self._member_actions(observations)
+        K = preds.shape[0]
+        if K < 2:
+            return {"diversity_score": 0.0, "disagreement": 0.0}
+        dist = [np.mean(np.abs(preds[i] - preds[j])) for i in range(K) for j in range(i + 1, K)]
+        unc = ensemble_uncertainty(preds.reshape(K, -1, preds.shape[-1]))
+        return {"diversity_score": float(np.mean(dist)), "disagreement": float(np.mean(unc)), "n_agents": K}
+
+
 def _dense_layers(tree, what):
     """[(kernel, bias), ...] of Dense_0, Dense_1, ... of a Flax parameter tree (any nested mapping)."""
     def walk(t, path):

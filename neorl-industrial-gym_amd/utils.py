@@ -127,10 +127,25 @@ def _evaluate_batched(agent, env: BatchedIndustrialEnv, n_episodes: int, step_no
     B = env.batch
     remaining, rnd = int(n_episodes), 0
     device_policy = hasattr(agent, "to_struct") and step_noise_fn is None and reset_noise_fn is None
-    fused_mlp = getattr(agent, "fusable", False) and step_noise_fn is None and reset_noise_fn is None
+    plain = step_noise_fn is None and reset_noise_fn is None
+    if plain and all(hasattr(agent, k) for k in ("agents", "weights", "ensemble_method")) and not hasattr(agent, "install"):
+        # the reference's EnsembleAgent: its K actors fused into the env kernel where members and env allow it (EnsemblePolicy);
+        # otherwise the agent stays as it is and takes the host loop below
+        from .policies import EnsemblePolicy
+        try:
+            upgraded = EnsemblePolicy.from_agent(agent, device=env.device)
+            if upgraded.fusable and env.state_dim % 2 == 0 and env.action_dim <= 16:
+                agent = upgraded
+        except Exception:
+            pass
+    ensemble = plain and hasattr(agent, "install") and getattr(agent, "fusable", False) and env.state_dim % 2 == 0 and env.action_dim <= 16
+    fused_mlp = not hasattr(agent, "install") and getattr(agent, "fusable", False) and step_noise_fn is None and reset_noise_fn is None
     shielded = fused_mlp and getattr(agent, "safety_weights", None) is not None and hasattr(agent, "threshold")
     if device_policy:
         env.set_policy(agent)
+    elif ensemble:
+        agent.install(env)
+        device_policy = True
     elif fused_mlp:
         env.set_mlp_policy(agent.weights)
         if shielded:        # MLPPolicy.shielded(): actor + safety critic + shield in the same kernel
@@ -146,7 +161,8 @@ def _evaluate_batched(agent, env: BatchedIndustrialEnv, n_episodes: int, step_no
         # the Advanced envs truncate on the step AFTER the cap (advanced_chemical_reactor.py:351 and
         # advanced_power_grid.py:331 test episode_step before its increment): one step more for them
         extra = 1 if env.env_id.startswith("Advanced") else 0
-        (env.rollout_mlp_safe if shielded else env.rollout_mlp if fused_mlp else env.rollout_policy)(env.max_episode_steps + extra)
+        (env.rollout_mlp_ensemble if ensemble else env.rollout_mlp_safe if shielded else env.rollout_mlp if fused_mlp
+         else env.rollout_policy)(env.max_episode_steps + extra)
         remaining -= k
     while remaining > 0:
         k = min(B, remaining)
