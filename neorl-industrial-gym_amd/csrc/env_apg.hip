@@ -1,3 +1,3 @@
 // kernels of AdvancedPowerGrid (nig_envs.hpp) -- one translation unit per environment
-#include "nig_kernels.hpp"
+#include "nig_launch.hpp"
 NIG_DEFINE_ENV_LAUNCH(AdvancedPowerGrid, nig_launch_apg)

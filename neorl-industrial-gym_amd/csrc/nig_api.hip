@@ -4,7 +4,7 @@
 
 #include <atomic>
 
-#include "nig_kernels.hpp"
+#include "nig_launch.hpp"
 
 namespace nig {
 

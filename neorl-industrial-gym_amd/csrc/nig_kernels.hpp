@@ -8,6 +8,7 @@
 // shutdown -> (optional) episode tally flush and in-kernel auto-reset.  No MFMA: these are
 // elementwise ODE updates (HBM-bound, DESIGN.md "Roofline").
 //
+// Device code only: the host side that launches these kernels is nig_launch.hpp (what the .hip units include).
 // Translation units: every environment's kernels are instantiated in a file of their own
 // (env_*.hip: `NIG_DEFINE_ENV_LAUNCH(Env, name)`), the C ABI and the env-independent kernels
 // live in nig_api.hip; _build.py compiles them in parallel and links libnig.so.
@@ -2178,388 +2179,3 @@ __global__ void __launch_bounds__(BLOCK) fill_actions_kernel(float *act, int64_t
 
 
 }  // namespace nig
-
-// =====================================================================================
-// host side: per-environment launch table.  Each env_*.hip instantiates its kernels through
-// NIG_DEFINE_ENV_LAUNCH; nig_api.hip reaches them through these function pointers only.
-// =====================================================================================
-namespace nig {
-
-struct EnvLaunch {
-    void (*step)(const StepArgs &, bool parity, unsigned grid, hipStream_t);
-    void (*step64)(const StepArgs &, bool parity, unsigned grid, hipStream_t);   // float64 action rows; nullptr: the env takes float32
-    void (*rollout)(int out_mode, const RolloutArgs &, uint32_t t0, unsigned grid, hipStream_t);
-    void (*policy)(const PolicyArgs &, unsigned grid, hipStream_t);
-    void (*mlp)(const MlpArgs &, unsigned grid, hipStream_t);      // nullptr: env shape not supported by the MFMA actor
-    void (*mlp_shield)(const MlpShieldArgs &, unsigned grid, hipStream_t);   // the same with the safety-critic shield
-    void (*reset)(const ResetArgs &, bool parity, unsigned grid, hipStream_t);
-    void (*fill)(float *act, int64_t ld_act, int64_t B, uint64_t env0, uint32_t seed_lo, uint32_t seed_hi, uint32_t t,
-                 unsigned grid, hipStream_t);
-    // does `rollout` read a ROW-MAJOR action ring ([B][A] slots, RolloutArgs.s.ld_act == 0) natively for this request?
-    bool (*rows_native)(int out_mode, const RolloutArgs &);
-    void (*rollout_sampled)(int out_mode, const RolloutArgs &, uint32_t t0, unsigned grid, hipStream_t);   // nig_rollout_sampled
-    void (*mlp_ensemble)(int ens, const MlpEnsArgs &, unsigned grid, hipStream_t);   // nig_rollout_mlp_ensemble; nullptr as `mlp`
-};
-
-template <class Env>
-static void launch_reset(const ResetArgs &a, bool parity, unsigned grid, hipStream_t st)
-{
-    if (parity) hipLaunchKernelGGL((reset_kernel<Env, true>), dim3(grid), dim3(BLOCK), 0, st, a);
-    else hipLaunchKernelGGL((reset_kernel<Env, false>), dim3(grid), dim3(BLOCK), 0, st, a);
-}
-
-// the MFMA actor exists for even state dims and at most 16 actions (nig_set_mlp_policy refuses the others)
-template <class Env>
-static void launch_mlp(const MlpArgs &q, unsigned grid, hipStream_t st)
-{
-    if constexpr (Env::S % 2 == 0 && Env::A <= 16) hipLaunchKernelGGL((rollout_mlp_kernel<Env>), dim3(grid), dim3(BLOCK), 0, st, q);
-}
-
-template <class Env>
-static void launch_mlp_shield(const MlpShieldArgs &q, unsigned grid, hipStream_t st)
-{
-    if constexpr (Env::S % 2 == 0 && Env::A <= 16) hipLaunchKernelGGL((rollout_mlp_shield_kernel<Env>), dim3(grid), dim3(BLOCK), 0, st, q);
-}
-
-template <class Env>
-static void launch_step(const StepArgs &a, bool parity, unsigned grid, hipStream_t st)
-{
-    constexpr int FB = Env::STEP_BLOCK;
-    if (parity) { hipLaunchKernelGGL((step_kernel<Env, true>), dim3(grid), dim3(BLOCK), 0, st, a); return; }
-    if constexpr (Env::COOP_RESET) {
-        // auto-reset handles whose batch leaves one wave per SIMD (up to nig_tune(NIG_TUNE_SPLIT_BLOCKS) 256-lane blocks, default
-        // one per compute unit -- the knob of the three-wave rollout, the same regime): a helper wave per lane wave prepares
-        // the restart states beside the step (step_kernel, HELP)
-        if ((a.hflags & NIG_F_AUTORESET) != 0 && a.split_blocks != 0 && grid <= a.split_blocks) {
-            hipLaunchKernelGGL((step_kernel<Env, false, false, BLOCK, true>), dim3(grid), dim3(2 * BLOCK), 0, st, a);
-            return;
-        }
-    }
-    if (FB != BLOCK && a.B > 768u * BLOCK)            // more 256-thread blocks than are resident at once (3 per CU)
-        hipLaunchKernelGGL((step_kernel<Env, false, false, FB>), dim3((a.B + FB - 1) / FB), dim3(FB), 0, st, a);
-    else hipLaunchKernelGGL((step_kernel<Env, false>), dim3(grid), dim3(BLOCK), 0, st, a);
-}
-
-template <class Env>
-static void launch_step64(const StepArgs &a, bool parity, unsigned grid, hipStream_t st)
-{
-    if constexpr (Env::HAS_ACT64) {
-        if (parity) hipLaunchKernelGGL((step_kernel<Env, true, true>), dim3(grid), dim3(BLOCK), 0, st, a);
-        else hipLaunchKernelGGL((step_kernel<Env, false, true>), dim3(grid), dim3(BLOCK), 0, st, a);
-    }
-}
-
-// NOISE (here and below): the injected-draw variants of nig_rollout_noise, instantiated for the row-major full-output
-// mode only (out_mode 3, what the headline configuration runs) -- same form selection, same launch shapes.
-// SAMPLED (here and below): nig_rollout_sampled -- the twin kernels that draw their actions (rollout_sampled_kernel,
-// rollout_sampled_wide_kernel, split_sampled_kernel, pg_pair_sampled_kernel), picked by the SAME rule, thresholds and launch
-// shapes: one copy of the selection code, the kernel name is the only thing the flag changes.
-template <class Env, bool PAIRED, bool FULL, bool NOISE = false, bool SAMPLED = false>
-static void launch_rollout_blocks(int out_mode, const RolloutArgs &q, unsigned grid, hipStream_t st)
-{
-    if constexpr (NOISE) {
-        hipLaunchKernelGGL((rollout_kernel<Env, 3, false, FULL, true>), dim3(grid), dim3(BLOCK), 0, st, q);
-        return;
-    }
-    if constexpr (SAMPLED) {
-        switch (out_mode) {
-        case 0: hipLaunchKernelGGL((rollout_sampled_kernel<Env, 0, PAIRED, FULL>), dim3(grid), dim3(BLOCK), 0, st, q); break;
-        case 1: hipLaunchKernelGGL((rollout_sampled_kernel<Env, 1, PAIRED, FULL>), dim3(grid), dim3(BLOCK), 0, st, q); break;
-        case 2: hipLaunchKernelGGL((rollout_sampled_kernel<Env, 2, PAIRED, FULL>), dim3(grid), dim3(BLOCK), 0, st, q); break;
-        default: hipLaunchKernelGGL((rollout_sampled_kernel<Env, 3, PAIRED, FULL>), dim3(grid), dim3(BLOCK), 0, st, q); break;
-        }
-        return;
-    }
-    switch (out_mode) {
-    case 0: hipLaunchKernelGGL((rollout_kernel<Env, 0, PAIRED, FULL>), dim3(grid), dim3(BLOCK), 0, st, q); break;
-    case 1: hipLaunchKernelGGL((rollout_kernel<Env, 1, PAIRED, FULL>), dim3(grid), dim3(BLOCK), 0, st, q); break;
-    case 2: hipLaunchKernelGGL((rollout_kernel<Env, 2, PAIRED, FULL>), dim3(grid), dim3(BLOCK), 0, st, q); break;
-    default: hipLaunchKernelGGL((rollout_kernel<Env, 3, PAIRED, FULL>), dim3(grid), dim3(BLOCK), 0, st, q); break;
-    }
-}
-
-// the batch's whole 256-lane blocks in one launch without lane predication, a ragged last block in its own
-template <class Env, bool PAIRED, bool NOISE = false, bool SAMPLED = false>
-static void launch_rollout_form(int out_mode, const RolloutArgs &q, unsigned /*grid*/, hipStream_t st)
-{
-    const unsigned n_full = q.s.B / BLOCK;
-    RolloutArgs r = q;
-    if constexpr ((PAIRED || Env::KS == 0 || NOISE) && split_rollout<Env>::value) {
-        // Up to one 256-lane block per CU the batch leaves a single wave on every SIMD: producer / integrator /
-        // recorder wave per 64 lanes instead (nig_split.hpp; one block per CU is resident).  Larger batches run that
-        // form in ROUNDS of one block per CU, which beats the one-wave form (lanes filling the SIMDs) by 4-12 % when
-        // the rounds come out even -- measured at 2, 3, 4, 8 and 16 rounds, profiles/r02/rounds_probe.txt -- and loses
-        // when the last round is mostly empty (1.5 rounds: -8 %): used when the last round is at least 3/4 full.
-        // Round 5: ... and only for launches that write an observation trajectory (out_mode >= 2).  A round takes the three-wave
-        // pipeline's ~142 us per 250 steps whatever it writes, so with reward + flags or no outputs the rounds LOSE to lanes
-        // filling the SIMDs -- 131 072 lanes 280 vs 214-231 us, 262 144 lanes 555 vs 384-409 us, 1 048 576 lanes 2.20 vs
-        // 1.31-1.46 ms -- while with the trajectory (HBM-bound either way) they win by 6-15 % (335 vs 378 us, 680 vs 726 us,
-        // 3.30 vs 3.72 ms; profiles/r05/cr_rounds_by_output_mode.txt).  Found by the mixed-launch floor table, whose
-        // stand-alone ChemicalReactor column was slower than the same body inside the mixed kernel.
-        const bool plain = (q.s.hflags & NIG_F_AUTORESET) != 0 && (q.s.hflags & HF_MAY_HOLD_DONE) == 0;
-        const unsigned per_round = q.s.split_blocks;       // nig_tune(NIG_TUNE_SPLIT_BLOCKS), default: the device's compute units
-        const unsigned last_round = per_round ? n_full % per_round : 0u;
-        const bool even_rounds = per_round != 0 && (n_full <= per_round ||
-                                                    (split_rounds<Env>::value && (out_mode >= 2 || NOISE) &&
-                                                     (last_round == 0 || 4u * last_round >= 3u * per_round)));
-        if (plain && n_full > 0 && even_rounds) {
-            r.block0 = 0;
-            launch_split_blocks<Env, BLOCK / 64, NOISE, SAMPLED>(out_mode, r, n_full, st);
-            if (q.s.B % BLOCK) { r.block0 = n_full; launch_rollout_blocks<Env, PAIRED, false, NOISE, SAMPLED>(out_mode, r, 1u, st); }
-            return;
-        }
-    }
-    // (Round 5 tried the three-wave form for the LAST, partial residency round of a RobotAssembly batch -- 262 144 lanes = 768 blocks
-    // one-wave + 256 three-wave, two launches -- on the idea that those blocks run one to a compute unit anyway: slower, full outputs
-    // 1 857-1 877 vs 1 842-1 863 us, reward + flags 1 590 vs 1 464, none 1 559 vs 1 427 (profiles/r05/ra_tail_round_three_wave_ab.txt):
-    // one launch lets the tail's blocks start as compute units free up, two launches drain the chip in between.  Not kept.)
-    unsigned first = 0;                            // first 256-lane block the forms below still have to run
-    if constexpr (!PAIRED && wide_rollout<Env>::value != 0) {
-        // Envs with an LDS-resident rollout body (PowerGrid, nig_pg_lds.hpp), handles on which no lane can be frozen:
-        // from nig_tune(NIG_TUNE_WIDE_MIN_BLOCKS) wide blocks up, the batch's whole 512-lane blocks in the wide form
-        // (four waves per SIMD); a remaining whole 256-lane block, and every whole block of a smaller batch, in the same
-        // body with 256-thread blocks (three blocks per CU by LDS: 262 144 lanes would need 1.33 rounds, which is why
-        // big batches take the wide form; small ones spread over more CUs this way and still run ~7 % fewer instructions
-        // than the register-resident kernel, without its spills: 65 536 lanes 927 -> 858 us, 98 304 lanes 1.29 -> 1.08 ms
-        // per 250 steps, profiles/r03/pg_small.txt).  A knob value of 2^30 or more keeps everything on rollout_kernel.
-        constexpr int WB = wide_rollout<Env>::value;
-        const bool plain = (q.s.hflags & NIG_F_AUTORESET) != 0 && (q.s.hflags & HF_MAY_HOLD_DONE) == 0;
-        if (plain && q.s.wide_min_blocks < (1u << 30)) {
-            const unsigned n_wide = q.s.B / WB;
-            if (n_wide > 0 && n_wide >= q.s.wide_min_blocks) {
-                r.block0 = 0;
-                if constexpr (NOISE) hipLaunchKernelGGL((rollout_wide_kernel<Env, 3, WB, true>), dim3(n_wide), dim3(WB), 0, st, r);
-                else if constexpr (SAMPLED)
-                switch (out_mode) {
-                case 0: hipLaunchKernelGGL((rollout_sampled_wide_kernel<Env, 0, WB>), dim3(n_wide), dim3(WB), 0, st, r); break;
-                case 1: hipLaunchKernelGGL((rollout_sampled_wide_kernel<Env, 1, WB>), dim3(n_wide), dim3(WB), 0, st, r); break;
-                case 2: hipLaunchKernelGGL((rollout_sampled_wide_kernel<Env, 2, WB>), dim3(n_wide), dim3(WB), 0, st, r); break;
-                default: hipLaunchKernelGGL((rollout_sampled_wide_kernel<Env, 3, WB>), dim3(n_wide), dim3(WB), 0, st, r); break;
-                }
-                else
-                switch (out_mode) {
-                case 0: hipLaunchKernelGGL((rollout_wide_kernel<Env, 0, WB>), dim3(n_wide), dim3(WB), 0, st, r); break;
-                case 1: hipLaunchKernelGGL((rollout_wide_kernel<Env, 1, WB>), dim3(n_wide), dim3(WB), 0, st, r); break;
-                case 2: hipLaunchKernelGGL((rollout_wide_kernel<Env, 2, WB>), dim3(n_wide), dim3(WB), 0, st, r); break;
-                default: hipLaunchKernelGGL((rollout_wide_kernel<Env, 3, WB>), dim3(n_wide), dim3(WB), 0, st, r); break;
-                }
-                first = n_wide * (WB / BLOCK);
-            }
-            if constexpr (pair_rollout<Env>::value) {
-                // a batch that would leave one wave on every SIMD (at most nig_tune(NIG_TUNE_SPLIT_BLOCKS) 256-lane blocks,
-                // default one per compute unit): the paired form -- a producer wave draws the step's normals beside every
-                // stepping wave (rollout_pg_pair_kernel, nig_pg_lds.hpp)
-                if (first == 0 && n_full > 0 && q.s.split_blocks != 0 && n_full <= q.s.split_blocks) {
-#ifdef NIG_DIAG_PG_PAIR_LDS            // (diagnostic builds only: round 3's LDS-resident stepping waves, for same-box A/Bs)
-#define NIG_PG_PAIR_REG false
-#else
-#define NIG_PG_PAIR_REG true
-#endif
-                    r.block0 = 0;
-                    if constexpr (NOISE) hipLaunchKernelGGL((rollout_pg_pair_kernel<3, true>), dim3(n_full), dim3(512), 0, st, r);
-                    else if constexpr (SAMPLED)
-                    switch (out_mode) {        // (the same stepper per output mode as below)
-                    case 0: hipLaunchKernelGGL((pg_pair_sampled_kernel<0, NIG_PG_PAIR_REG>), dim3(n_full), dim3(512), 0, st, r); break;
-                    case 1: hipLaunchKernelGGL((pg_pair_sampled_kernel<1, NIG_PG_PAIR_REG>), dim3(n_full), dim3(512), 0, st, r); break;
-                    case 2: hipLaunchKernelGGL((pg_pair_sampled_kernel<2, false>), dim3(n_full), dim3(512), 0, st, r); break;
-                    default: hipLaunchKernelGGL((pg_pair_sampled_kernel<3, false>), dim3(n_full), dim3(512), 0, st, r); break;
-                    }
-                    else
-                    switch (out_mode) {
-                    case 0: hipLaunchKernelGGL((rollout_pg_pair_kernel<0, false, NIG_PG_PAIR_REG>), dim3(n_full), dim3(512), 0, st, r); break;
-                    case 1: hipLaunchKernelGGL((rollout_pg_pair_kernel<1, false, NIG_PG_PAIR_REG>), dim3(n_full), dim3(512), 0, st, r); break;
-                    // (with an observation trajectory the LDS-resident stepping body stays: its state image IS the transposing
-                    // image of the row-major rows; the register body pays an extra LDS round trip for them -- same box, 65 536
-                    // lanes x 250 steps: reward + flags 665 -> 582 us, no outputs 643 -> 557 us with registers, but full outputs
-                    // 687 -> 774 us: profiles/r04/pg_pair_reg_ab.txt)
-                    case 2: hipLaunchKernelGGL((rollout_pg_pair_kernel<2, false, false>), dim3(n_full), dim3(512), 0, st, r); break;
-                    default: hipLaunchKernelGGL((rollout_pg_pair_kernel<3, false, false>), dim3(n_full), dim3(512), 0, st, r); break;
-                    }
-                    first = n_full;
-                }
-            }
-            if (n_full > first) {
-                r.block0 = first;
-                const unsigned nb = n_full - first;
-                if constexpr (NOISE) hipLaunchKernelGGL((rollout_wide_kernel<Env, 3, BLOCK, true>), dim3(nb), dim3(BLOCK), 0, st, r);
-                else if constexpr (SAMPLED)
-                switch (out_mode) {
-                case 0: hipLaunchKernelGGL((rollout_sampled_wide_kernel<Env, 0, BLOCK>), dim3(nb), dim3(BLOCK), 0, st, r); break;
-                case 1: hipLaunchKernelGGL((rollout_sampled_wide_kernel<Env, 1, BLOCK>), dim3(nb), dim3(BLOCK), 0, st, r); break;
-                case 2: hipLaunchKernelGGL((rollout_sampled_wide_kernel<Env, 2, BLOCK>), dim3(nb), dim3(BLOCK), 0, st, r); break;
-                default: hipLaunchKernelGGL((rollout_sampled_wide_kernel<Env, 3, BLOCK>), dim3(nb), dim3(BLOCK), 0, st, r); break;
-                }
-                else
-                switch (out_mode) {
-                case 0: hipLaunchKernelGGL((rollout_wide_kernel<Env, 0, BLOCK>), dim3(nb), dim3(BLOCK), 0, st, r); break;
-                case 1: hipLaunchKernelGGL((rollout_wide_kernel<Env, 1, BLOCK>), dim3(nb), dim3(BLOCK), 0, st, r); break;
-                case 2: hipLaunchKernelGGL((rollout_wide_kernel<Env, 2, BLOCK>), dim3(nb), dim3(BLOCK), 0, st, r); break;
-                default: hipLaunchKernelGGL((rollout_wide_kernel<Env, 3, BLOCK>), dim3(nb), dim3(BLOCK), 0, st, r); break;
-                }
-                first = n_full;
-            }
-        }
-    }
-    if (n_full > first) { r.block0 = first; launch_rollout_blocks<Env, PAIRED, true, NOISE, SAMPLED>(out_mode, r, n_full - first, st); }
-    if (q.s.B % BLOCK) { r.block0 = n_full; launch_rollout_blocks<Env, PAIRED, false, NOISE, SAMPLED>(out_mode, r, 1u, st); }
-}
-
-// nig_rollout's row-major action ring (ld_act == 0): true when EVERY kernel launch_rollout_form<Env, false> starts for this
-// request reads a lane's actions as contiguous bytes -- the LDS-resident PowerGrid body (nig_pg_lds.hpp: wide 512 / 256 and the
-// paired form's LDS stepper).  Mirrors the form selection above, predicate by predicate: whole 256-lane blocks only (a ragged
-// block runs rollout_kernel), an auto-reset handle without held lanes, the wide knob on, and not the paired regime's
-// register-resident stepper (out_mode 0 / 1 below NIG_TUNE_SPLIT_BLOCKS blocks: rollout_body reads rows).
-template <class Env>
-static bool rollout_rows_native(int out_mode, const RolloutArgs &q)
-{
-    if constexpr (wide_rollout<Env>::value == 0 || Env::A != 8) return false;
-    else {
-        constexpr unsigned WB = (unsigned)wide_rollout<Env>::value;
-        const bool plain = (q.s.hflags & NIG_F_AUTORESET) != 0 && (q.s.hflags & HF_MAY_HOLD_DONE) == 0;
-        if (!plain || q.s.wide_min_blocks >= (1u << 30) || q.s.B % BLOCK != 0u || q.s.B == 0u) return false;
-        const unsigned n_full = q.s.B / BLOCK, n_wide = q.s.B / WB;
-        const bool wide = n_wide > 0 && n_wide >= q.s.wide_min_blocks;
-        if constexpr (pair_rollout<Env>::value) {
-            const bool paired = !wide && q.s.split_blocks != 0 && n_full <= q.s.split_blocks;
-            if (paired && out_mode <= 1 && NIG_PG_PAIR_REG) return false;
-        }
-        return true;
-    }
-}
-
-// t0 = launch counter of the call's first step (host-known: rollouts are never graph-captured)
-// the envs the reference can record draws for (ChemicalReactor, PowerGrid, RobotAssembly): nig_rollout_noise
-template <class Env> struct noise_rollout : std::bool_constant<(Env::ID <= 2)> {};
-
-template <class Env, bool SAMPLED>
-static void launch_rollout_paired(int out_mode, const RolloutArgs &q, uint32_t t0, unsigned grid, hipStream_t st)
-{
-    if constexpr (Env::SHARED_STEP_BLOCK) {
-        RolloutArgs r = q;
-        if ((t0 & 1u) == 0u) {                    // starts on the second step of a pair: peel it
-            r.n_steps = 1;
-            launch_rollout_form<Env, false, false, SAMPLED>(out_mode, r, grid, st);
-            if (q.n_steps == 1) return;
-            r.n_steps = q.n_steps; r.it0 = 1;
-        }
-        launch_rollout_form<Env, true, false, SAMPLED>(out_mode, r, grid, st);
-    } else {
-        launch_rollout_form<Env, false, false, SAMPLED>(out_mode, q, grid, st);
-    }
-}
-
-template <class Env>
-static void launch_rollout_env(int out_mode, const RolloutArgs &q, uint32_t t0, unsigned grid, hipStream_t st)
-{
-    if (q.s.step_noise != nullptr || q.s.reset_noise != nullptr) {       // injected draws (nig_rollout_noise has validated the request)
-        if constexpr (noise_rollout<Env>::value) launch_rollout_form<Env, false, true>(3, q, grid, st);
-        return;
-    }
-    launch_rollout_paired<Env, false>(out_mode, q, t0, grid, st);
-}
-
-// nig_rollout_sampled: the same selection on the twin kernels.  Declared everywhere, DEFINED (and with it every sampled kernel
-// instantiated) only in the env's sampled_*.hip translation unit (NIG_DEFINE_ENV_SAMPLED): the env_*.hip units hold exactly the
-// instantiations they held before the twins existed -- their code objects do not move by an instruction (profiles/isa_diff.py) --
-// and the twins compile beside them in parallel.
-template <class Env>
-void launch_rollout_sampled_env(int out_mode, const RolloutArgs &q, uint32_t t0, unsigned grid, hipStream_t st)
-#ifdef NIG_SAMPLED_TU
-{
-    launch_rollout_paired<Env, true>(out_mode, q, t0, grid, st);
-}
-#else
-;
-#endif
-
-// nig_rollout_mlp_ensemble: as the sampled twins, declared everywhere and DEFINED (its kernels instantiated) only in the env's
-// ensemble_*.hip translation unit (NIG_DEFINE_ENV_ENSEMBLE), so the env_*.hip units keep the instantiations they had.
-template <class Env>
-void launch_mlp_ensemble_env(int ens, const MlpEnsArgs &q, unsigned grid, hipStream_t st)
-#ifdef NIG_ENSEMBLE_TU
-{
-    if constexpr (Env::S % 2 == 0 && Env::A <= 16) {
-        if (ens == ENS_AVERAGE) hipLaunchKernelGGL((rollout_mlp_ensemble_kernel<Env, ENS_AVERAGE>), dim3(grid), dim3(BLOCK), 0, st, q);
-        else hipLaunchKernelGGL((rollout_mlp_ensemble_kernel<Env, ENS_VOTING>), dim3(grid), dim3(BLOCK), 0, st, q);
-    }
-}
-#else
-;
-#endif
-
-template <class Env>
-static void launch_policy(const PolicyArgs &q, unsigned grid, hipStream_t st)
-{
-    if constexpr (split_rollout<Env>::value && (Env::SHARED_STEP_BLOCK || Env::KS == 0)) {
-        // Producer / integrator / recorder wave per 64 lanes (nig_split_policy.hpp) for the batch's whole 256-lane blocks --
-        // up to one block per CU, and (ChemicalReactor) larger batches in rounds under the rule of the open-loop rollout (the last
-        // round at least 3/4 full) -- and the one-wave kernel for a ragged last block.  RobotAssembly (round 4: S = 24, the
-        // form's BIG layout): a single round only, as in the open loop; the observations of the transition stream ride in its
-        // P -> I slots since round 5.
-        const bool plain = (q.s.hflags & NIG_F_AUTORESET) != 0 && (q.s.hflags & HF_MAY_HOLD_DONE) == 0;
-        const unsigned n_full = q.s.B / BLOCK, per_round = q.s.split_blocks;
-        const unsigned last_round = per_round ? n_full % per_round : 0u;
-        constexpr bool big = SplitPolicyLds<Env, BLOCK / 64>::BIG;
-        // (beyond one round only for calls that write the observation stream, as in the open loop, and only up to TWO rounds:
-        // a closed-loop round takes ~1 us per step whatever it writes, lanes filling the SIMDs take 1.75 / 2.5 us per step at
-        // 131 072 / 262 144 lanes without the stream and 1.97 / 3.25 with it -- two rounds 1.84, four rounds 3.72:
-        // profiles/r05/policy_rounds_cr.txt)
-        const bool even_rounds = per_round != 0 && (n_full <= per_round ||
-                                                    (!big && split_rounds<Env>::value && q.obs_out != nullptr && n_full <= 2u * per_round &&
-                                                     (last_round == 0 || 4u * last_round >= 3u * per_round)));
-        if (plain && n_full > 0 && even_rounds) {
-            PolicyArgs r = q;
-            r.block0 = 0;
-            hipLaunchKernelGGL((split_policy_kernel<Env, BLOCK / 64>), dim3(n_full), dim3(192 * (BLOCK / 64)), 0, st, r);
-            if (q.s.B % BLOCK) { r.block0 = n_full; hipLaunchKernelGGL((rollout_policy_kernel<Env>), dim3(1), dim3(BLOCK), 0, st, r); }
-            return;
-        }
-    }
-    if constexpr (pair_rollout<Env>::value) {
-        // PowerGrid, affine policies, batches of at most one 256-lane block per compute unit (the open loop's paired-form
-        // regime, nig_tune(NIG_TUNE_SPLIT_BLOCKS)): stepping + producer wave per 64 lanes (rollout_pg_pair_policy_kernel);
-        // a ragged last block on the one-wave kernel.  PID policies keep their memory in registers: one-wave kernel.
-        const bool plain = (q.s.hflags & NIG_F_AUTORESET) != 0 && (q.s.hflags & HF_MAY_HOLD_DONE) == 0;
-        const unsigned n_full = q.s.B / BLOCK;
-        if (plain && q.pol_kind == NIG_POLICY_AFFINE && n_full > 0 && q.s.split_blocks != 0 && n_full <= q.s.split_blocks) {
-            PolicyArgs r = q;
-            r.block0 = 0;
-            hipLaunchKernelGGL((rollout_pg_pair_policy_kernel<PolicyArgs>), dim3(n_full), dim3(512), 0, st, r);
-            if (q.s.B % BLOCK) { r.block0 = n_full; hipLaunchKernelGGL((rollout_policy_kernel<Env>), dim3(1), dim3(BLOCK), 0, st, r); }
-            return;
-        }
-    }
-    hipLaunchKernelGGL((rollout_policy_kernel<Env>), dim3(grid), dim3(BLOCK), 0, st, q);
-}
-
-template <class Env>
-static void launch_fill(float *act, int64_t ld_act, int64_t B, uint64_t env0, uint32_t seed_lo, uint32_t seed_hi, uint32_t t,
-                        unsigned grid, hipStream_t st)
-{
-    hipLaunchKernelGGL((fill_actions_kernel<Env>), dim3(grid), dim3(BLOCK), 0, st, act, ld_act, B, env0, seed_lo, seed_hi, t);
-}
-
-template <class Env>
-static const EnvLaunch *env_launch_table()
-{
-    static const EnvLaunch T = {launch_step<Env>, Env::HAS_ACT64 ? launch_step64<Env> : nullptr, launch_rollout_env<Env>, launch_policy<Env>,
-                                (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp<Env> : nullptr,
-                                (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp_shield<Env> : nullptr,
-                                launch_reset<Env>, launch_fill<Env>, rollout_rows_native<Env>, launch_rollout_sampled_env<Env>,
-                                (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp_ensemble_env<Env> : nullptr};
-    return &T;
-}
-
-}  // namespace nig
-
-// nig_mixed.hip
-void nig_launch_mixed_rollout(int out_mode, const nig::MixedArgs &m, unsigned grid, hipStream_t st);
-
-#define NIG_DEFINE_ENV_LAUNCH(EnvType, fn_name) \
-    const nig::EnvLaunch *fn_name() { return nig::env_launch_table<nig::EnvType>(); }
-// sampled_*.hip (compiled with NIG_SAMPLED_TU defined before this header): the env's nig_rollout_sampled launcher and kernels
-#define NIG_DEFINE_ENV_SAMPLED(EnvType) \
-    template void nig::launch_rollout_sampled_env<nig::EnvType>(int, const nig::RolloutArgs &, uint32_t, unsigned, hipStream_t);
-// ensemble_*.hip (compiled with NIG_ENSEMBLE_TU defined before this header): the env's nig_rollout_mlp_ensemble launcher and kernels
-#define NIG_DEFINE_ENV_ENSEMBLE(EnvType) \
-    template void nig::launch_mlp_ensemble_env<nig::EnvType>(int, const nig::MlpEnsArgs &, unsigned, hipStream_t);

@@ -1,0 +1,270 @@
+// nig_launch.hpp -- the host side of libnig.so's kernels: the per-environment launch table.  Each env_*.hip instantiates
+// its kernels through NIG_DEFINE_ENV_LAUNCH; nig_api.hip reaches them through these function pointers only.  Which kernel
+// form a rollout launch takes is decided in nig_launch_plan.hpp; the functions here run its plans.
+#pragma once
+#include "nig_kernels.hpp"
+#include "nig_launch_plan.hpp"
+
+namespace nig {
+
+struct EnvLaunch {
+    void (*step)(const StepArgs &, bool parity, unsigned grid, hipStream_t);
+    void (*step64)(const StepArgs &, bool parity, unsigned grid, hipStream_t);   // float64 action rows; nullptr: the env takes float32
+    void (*rollout)(int out_mode, const RolloutArgs &, uint32_t t0, unsigned grid, hipStream_t);
+    void (*policy)(const PolicyArgs &, unsigned grid, hipStream_t);
+    void (*mlp)(const MlpArgs &, unsigned grid, hipStream_t);      // nullptr: env shape not supported by the MFMA actor
+    void (*mlp_shield)(const MlpShieldArgs &, unsigned grid, hipStream_t);   // the same with the safety-critic shield
+    void (*reset)(const ResetArgs &, bool parity, unsigned grid, hipStream_t);
+    void (*fill)(float *act, int64_t ld_act, int64_t B, uint64_t env0, uint32_t seed_lo, uint32_t seed_hi, uint32_t t,
+                 unsigned grid, hipStream_t);
+    // does `rollout` read a ROW-MAJOR action ring ([B][A] slots, RolloutArgs.s.ld_act == 0) natively for this request?
+    bool (*rows_native)(int out_mode, const RolloutArgs &);
+    void (*rollout_sampled)(int out_mode, const RolloutArgs &, uint32_t t0, unsigned grid, hipStream_t);   // nig_rollout_sampled
+    void (*mlp_ensemble)(int ens, const MlpEnsArgs &, unsigned grid, hipStream_t);   // nig_rollout_mlp_ensemble; nullptr as `mlp`
+};
+
+template <class Env>
+static void launch_reset(const ResetArgs &a, bool parity, unsigned grid, hipStream_t st)
+{
+    if (parity) hipLaunchKernelGGL((reset_kernel<Env, true>), dim3(grid), dim3(BLOCK), 0, st, a);
+    else hipLaunchKernelGGL((reset_kernel<Env, false>), dim3(grid), dim3(BLOCK), 0, st, a);
+}
+
+// the MFMA actor exists for even state dims and at most 16 actions (nig_set_mlp_policy refuses the others)
+template <class Env>
+static void launch_mlp(const MlpArgs &q, unsigned grid, hipStream_t st)
+{
+    if constexpr (Env::S % 2 == 0 && Env::A <= 16) hipLaunchKernelGGL((rollout_mlp_kernel<Env>), dim3(grid), dim3(BLOCK), 0, st, q);
+}
+
+template <class Env>
+static void launch_mlp_shield(const MlpShieldArgs &q, unsigned grid, hipStream_t st)
+{
+    if constexpr (Env::S % 2 == 0 && Env::A <= 16) hipLaunchKernelGGL((rollout_mlp_shield_kernel<Env>), dim3(grid), dim3(BLOCK), 0, st, q);
+}
+
+template <class Env>
+static void launch_step(const StepArgs &a, bool parity, unsigned grid, hipStream_t st)
+{
+    constexpr int FB = Env::STEP_BLOCK;
+    if (parity) { hipLaunchKernelGGL((step_kernel<Env, true>), dim3(grid), dim3(BLOCK), 0, st, a); return; }
+    if constexpr (Env::COOP_RESET) {
+        // auto-reset handles whose batch leaves one wave per SIMD (up to nig_tune(NIG_TUNE_SPLIT_BLOCKS) 256-lane blocks, default
+        // one per compute unit -- the knob of the three-wave rollout, the same regime): a helper wave per lane wave prepares
+        // the restart states beside the step (step_kernel, HELP)
+        if ((a.hflags & NIG_F_AUTORESET) != 0 && a.split_blocks != 0 && grid <= a.split_blocks) {
+            hipLaunchKernelGGL((step_kernel<Env, false, false, BLOCK, true>), dim3(grid), dim3(2 * BLOCK), 0, st, a);
+            return;
+        }
+    }
+    if (FB != BLOCK && a.B > 768u * BLOCK)            // more 256-thread blocks than are resident at once (3 per CU)
+        hipLaunchKernelGGL((step_kernel<Env, false, false, FB>), dim3((a.B + FB - 1) / FB), dim3(FB), 0, st, a);
+    else hipLaunchKernelGGL((step_kernel<Env, false>), dim3(grid), dim3(BLOCK), 0, st, a);
+}
+
+template <class Env>
+static void launch_step64(const StepArgs &a, bool parity, unsigned grid, hipStream_t st)
+{
+    if constexpr (Env::HAS_ACT64) {
+        if (parity) hipLaunchKernelGGL((step_kernel<Env, true, true>), dim3(grid), dim3(BLOCK), 0, st, a);
+        else hipLaunchKernelGGL((step_kernel<Env, false, true>), dim3(grid), dim3(BLOCK), 0, st, a);
+    }
+}
+
+// The output mode as a template argument: the ONE place a run-time out_mode is switched on.  f is a generic callable taking
+// std::integral_constant<int, 0..3>.
+template <class F>
+static void with_out_mode(int out_mode, F &&f)
+{
+    switch (out_mode) {
+    case 0: f(std::integral_constant<int, 0>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    default: f(std::integral_constant<int, 3>{}); break;
+    }
+}
+
+// (nig_launch_plan.hpp restates these three constants to stay free of HIP headers)
+static_assert(PLAN_BLOCK == BLOCK && PLAN_F_AUTORESET == NIG_F_AUTORESET && PLAN_HF_MAY_HOLD_DONE == HF_MAY_HOLD_DONE);
+
+template <class Env>
+struct PlanTraits {
+    static constexpr bool split_rollout = nig::split_rollout<Env>::value, split_rounds = nig::split_rounds<Env>::value;
+    static constexpr bool pair_rollout = nig::pair_rollout<Env>::value, ks0 = Env::KS == 0, shared_step_block = Env::SHARED_STEP_BLOCK;
+    static constexpr int wide_rollout = nig::wide_rollout<Env>::value;
+    // (read by plan_policy for the three-wave envs only, for which the closed loop's LDS layout exists and fits)
+    static constexpr bool split_policy_big = SplitPolicyLds<Env, BLOCK / 64>::BIG;
+};
+
+// One segment of a rollout plan.  Every form's kernels stay behind the trait that declares them: no env gains a kernel.
+// NOISE: the injected-draw variants of nig_rollout_noise, instantiated for the row-major full-output mode only (OUT 3, what the
+// headline configuration runs).  SAMPLED: nig_rollout_sampled -- the twin kernels that draw their actions (rollout_sampled_kernel,
+// rollout_sampled_wide_kernel, split_sampled_kernel, pg_pair_sampled_kernel): the same plan, the kernel name is the only thing
+// either flag changes.
+template <class Env, bool PAIRED, bool NOISE, bool SAMPLED, int OUT>
+static void launch_rollout_segment(const Segment &s, const RolloutArgs &r, hipStream_t st)
+{
+    const dim3 grid(s.grid);
+    // (One-wave and three-wave: no `else` after the sampled launch, so a sampled_*.hip unit instantiates the ring-fed kernel
+    // beside its twin, unreachable there -- its code object has always held those copies and is required not to move by a
+    // symbol: profiles/isa_diff.py.)
+    auto one_wave = [&](auto FULL) {
+        if constexpr (SAMPLED) { hipLaunchKernelGGL((rollout_sampled_kernel<Env, OUT, PAIRED, FULL()>), grid, dim3(BLOCK), 0, st, r); return; }
+        hipLaunchKernelGGL((rollout_kernel<Env, OUT, PAIRED, FULL(), NOISE>), grid, dim3(BLOCK), 0, st, r);
+    };
+    auto wide = [&](auto BLK) {
+        if constexpr (SAMPLED) hipLaunchKernelGGL((rollout_sampled_wide_kernel<Env, OUT, BLK()>), grid, dim3(BLK()), 0, st, r);
+        else hipLaunchKernelGGL((rollout_wide_kernel<Env, OUT, BLK(), NOISE>), grid, dim3(BLK()), 0, st, r);
+    };
+    constexpr bool WIDE = !PAIRED && wide_rollout<Env>::value != 0;
+    switch (s.form) {
+    case Form::OneWaveFull: one_wave(std::true_type{}); break;
+    case Form::OneWaveRagged: one_wave(std::false_type{}); break;
+    case Form::ThreeWave:
+        if constexpr ((PAIRED || Env::KS == 0 || NOISE) && split_rollout<Env>::value)
+            launch_split_blocks<Env, BLOCK / 64, OUT, NOISE, SAMPLED>(r, s.grid, st);
+        break;
+    case Form::Wide: if constexpr (WIDE) wide(std::integral_constant<int, wide_rollout<Env>::value>{}); break;
+    case Form::Wide256: if constexpr (WIDE) wide(std::integral_constant<int, BLOCK>{}); break;
+    case Form::PairedReg:
+    case Form::PairedLds:
+        if constexpr (WIDE && pair_rollout<Env>::value) {
+            constexpr bool REG = paired_stepper_reg(OUT);      // (what the plan's form says: the same function of the same constant)
+            if constexpr (SAMPLED) hipLaunchKernelGGL((pg_pair_sampled_kernel<OUT, REG>), grid, dim3(512), 0, st, r);
+            else hipLaunchKernelGGL((rollout_pg_pair_kernel<OUT, NOISE, REG>), grid, dim3(512), 0, st, r);
+        }
+        break;
+    }
+}
+
+template <class Env, bool PAIRED, bool NOISE = false, bool SAMPLED = false>
+static void launch_rollout_form(int out_mode, const RolloutArgs &q, unsigned /*grid*/, hipStream_t st)
+{
+    const LaunchPlan plan = plan_rollout<PlanTraits<Env>>(PAIRED, NOISE, out_mode, q.s.B, q.s.hflags, q.s.split_blocks, q.s.wide_min_blocks);
+    with_out_mode(out_mode, [&](auto MODE) {
+        constexpr int OUT = NOISE ? 3 : MODE();    // (nig_rollout_noise accepts out_mode 3 only)
+        RolloutArgs r = q;
+        for (const Segment &s : plan) { r.block0 = s.block0; launch_rollout_segment<Env, PAIRED, NOISE, SAMPLED, OUT>(s, r, st); }
+    });
+}
+
+// nig_rollout's row-major action ring (ld_act == 0): true when EVERY kernel launch_rollout_form<Env, false> starts for this
+// request reads a lane's actions as contiguous bytes -- asked of the plan itself.  (A == 8: two 16-byte loads per lane.)
+template <class Env>
+static bool rollout_rows_native(int out_mode, const RolloutArgs &q)
+{
+    const LaunchPlan plan = plan_rollout<PlanTraits<Env>>(false, false, out_mode, q.s.B, q.s.hflags, q.s.split_blocks, q.s.wide_min_blocks);
+    bool native = Env::A == 8 && plan.n > 0;
+    for (const Segment &s : plan) native = native && reads_lane_bytes(s.form);
+    return native;
+}
+
+// the envs the reference can record draws for (ChemicalReactor, PowerGrid, RobotAssembly): nig_rollout_noise
+template <class Env> struct noise_rollout : std::bool_constant<(Env::ID <= 2)> {};
+
+// t0 = launch counter of the call's first step (host-known: rollouts are never graph-captured)
+template <class Env, bool SAMPLED>
+static void launch_rollout_paired(int out_mode, const RolloutArgs &q, uint32_t t0, unsigned grid, hipStream_t st)
+{
+    if constexpr (Env::SHARED_STEP_BLOCK) {
+        RolloutArgs r = q;
+        if ((t0 & 1u) == 0u) {                    // starts on the second step of a pair: peel it
+            r.n_steps = 1;
+            launch_rollout_form<Env, false, false, SAMPLED>(out_mode, r, grid, st);
+            if (q.n_steps == 1) return;
+            r.n_steps = q.n_steps; r.it0 = 1;
+        }
+        launch_rollout_form<Env, true, false, SAMPLED>(out_mode, r, grid, st);
+    } else {
+        launch_rollout_form<Env, false, false, SAMPLED>(out_mode, q, grid, st);
+    }
+}
+
+template <class Env>
+static void launch_rollout_env(int out_mode, const RolloutArgs &q, uint32_t t0, unsigned grid, hipStream_t st)
+{
+    if (q.s.step_noise != nullptr || q.s.reset_noise != nullptr) {       // injected draws (nig_rollout_noise has validated the request)
+        if constexpr (noise_rollout<Env>::value) launch_rollout_form<Env, false, true>(3, q, grid, st);
+        return;
+    }
+    launch_rollout_paired<Env, false>(out_mode, q, t0, grid, st);
+}
+
+// nig_rollout_sampled: the same selection on the twin kernels.  Declared everywhere, DEFINED (and with it every sampled kernel
+// instantiated) only in the env's sampled_*.hip translation unit (NIG_DEFINE_ENV_SAMPLED): the env_*.hip units hold exactly the
+// instantiations they held before the twins existed -- their code objects do not move by an instruction (profiles/isa_diff.py) --
+// and the twins compile beside them in parallel.
+template <class Env>
+void launch_rollout_sampled_env(int out_mode, const RolloutArgs &q, uint32_t t0, unsigned grid, hipStream_t st)
+#ifdef NIG_SAMPLED_TU
+{
+    launch_rollout_paired<Env, true>(out_mode, q, t0, grid, st);
+}
+#else
+;
+#endif
+
+// nig_rollout_mlp_ensemble: as the sampled twins, declared everywhere and DEFINED (its kernels instantiated) only in the env's
+// ensemble_*.hip translation unit (NIG_DEFINE_ENV_ENSEMBLE), so the env_*.hip units keep the instantiations they had.
+template <class Env>
+void launch_mlp_ensemble_env(int ens, const MlpEnsArgs &q, unsigned grid, hipStream_t st)
+#ifdef NIG_ENSEMBLE_TU
+{
+    if constexpr (Env::S % 2 == 0 && Env::A <= 16) {
+        if (ens == ENS_AVERAGE) hipLaunchKernelGGL((rollout_mlp_ensemble_kernel<Env, ENS_AVERAGE>), dim3(grid), dim3(BLOCK), 0, st, q);
+        else hipLaunchKernelGGL((rollout_mlp_ensemble_kernel<Env, ENS_VOTING>), dim3(grid), dim3(BLOCK), 0, st, q);
+    }
+}
+#else
+;
+#endif
+
+template <class Env>
+static void launch_policy(const PolicyArgs &q, unsigned /*grid*/, hipStream_t st)
+{
+    const LaunchPlan plan = plan_policy<PlanTraits<Env>>(q.pol_kind == NIG_POLICY_AFFINE, q.obs_out != nullptr, q.s.B, q.s.hflags, q.s.split_blocks);
+    PolicyArgs r = q;
+    for (const Segment &s : plan) {
+        void (*kernel)(const PolicyArgs) = rollout_policy_kernel<Env>;
+        unsigned threads = BLOCK;
+        // (RobotAssembly's observations of the transition stream ride in the BIG layout's P -> I slots)
+        if constexpr (split_rollout<Env>::value && (Env::SHARED_STEP_BLOCK || Env::KS == 0))
+            if (s.form == Form::ThreeWave) { kernel = split_policy_kernel<Env, BLOCK / 64>; threads = 192 * (BLOCK / 64); }
+        if constexpr (pair_rollout<Env>::value)
+            if (s.form == Form::PairedReg) { kernel = rollout_pg_pair_policy_kernel<PolicyArgs>; threads = 512; }
+        r.block0 = s.block0;
+        hipLaunchKernelGGL(kernel, dim3(s.grid), dim3(threads), 0, st, r);
+    }
+}
+
+template <class Env>
+static void launch_fill(float *act, int64_t ld_act, int64_t B, uint64_t env0, uint32_t seed_lo, uint32_t seed_hi, uint32_t t,
+                        unsigned grid, hipStream_t st)
+{
+    hipLaunchKernelGGL((fill_actions_kernel<Env>), dim3(grid), dim3(BLOCK), 0, st, act, ld_act, B, env0, seed_lo, seed_hi, t);
+}
+
+template <class Env>
+static const EnvLaunch *env_launch_table()
+{
+    static const EnvLaunch T = {launch_step<Env>, Env::HAS_ACT64 ? launch_step64<Env> : nullptr, launch_rollout_env<Env>, launch_policy<Env>,
+                                (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp<Env> : nullptr,
+                                (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp_shield<Env> : nullptr,
+                                launch_reset<Env>, launch_fill<Env>, rollout_rows_native<Env>, launch_rollout_sampled_env<Env>,
+                                (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp_ensemble_env<Env> : nullptr};
+    return &T;
+}
+
+}  // namespace nig
+
+// nig_mixed.hip
+void nig_launch_mixed_rollout(int out_mode, const nig::MixedArgs &m, unsigned grid, hipStream_t st);
+
+#define NIG_DEFINE_ENV_LAUNCH(EnvType, fn_name) \
+    const nig::EnvLaunch *fn_name() { return nig::env_launch_table<nig::EnvType>(); }
+// sampled_*.hip (compiled with NIG_SAMPLED_TU defined before this header): the env's nig_rollout_sampled launcher and kernels
+#define NIG_DEFINE_ENV_SAMPLED(EnvType) \
+    template void nig::launch_rollout_sampled_env<nig::EnvType>(int, const nig::RolloutArgs &, uint32_t, unsigned, hipStream_t);
+// ensemble_*.hip (compiled with NIG_ENSEMBLE_TU defined before this header): the env's nig_rollout_mlp_ensemble launcher and kernels
+#define NIG_DEFINE_ENV_ENSEMBLE(EnvType) \
+    template void nig::launch_mlp_ensemble_env<nig::EnvType>(int, const nig::MlpEnsArgs &, unsigned, hipStream_t);

@@ -10,7 +10,7 @@
 // per SIMD (168 registers; LDS, 45 KB per block, allows three).  PowerGrid's register-resident body wants ~185 and
 // spilled ~70 dwords here (round 2); since round 3 its whole blocks run the LDS-resident body (nig_pg_lds.hpp, ~110).
 // Round 4: ChemicalReactor and the four plants run their PAIRED bodies when the segment starts on an odd launch counter.
-#include "nig_kernels.hpp"
+#include "nig_launch.hpp"
 
 namespace nig {
 
@@ -88,7 +88,8 @@ __global__ void __launch_bounds__(BLOCK, 3) mixed_rollout_kernel(const MixedArgs
 void nig_launch_mixed_rollout(int out_mode, const nig::MixedArgs &m, unsigned grid, hipStream_t st)
 {
     using namespace nig;
-    if (out_mode == 0) hipLaunchKernelGGL((mixed_rollout_kernel<0>), dim3(grid), dim3(BLOCK), 0, st, m);
-    else if (out_mode == 1) hipLaunchKernelGGL((mixed_rollout_kernel<1>), dim3(grid), dim3(BLOCK), 0, st, m);
-    else hipLaunchKernelGGL((mixed_rollout_kernel<2>), dim3(grid), dim3(BLOCK), 0, st, m);
+    with_out_mode(out_mode, [&](auto OUT) {
+        constexpr int M = OUT() < 2 ? OUT() : 2;   // (the mixed trajectory is [row][lane] only: modes 2 and 3 are one kernel)
+        hipLaunchKernelGGL((mixed_rollout_kernel<M>), dim3(grid), dim3(BLOCK), 0, st, m);
+    });
 }

@@ -91,29 +91,13 @@ __global__ void __launch_bounds__(192 * NP, 1) split_sampled_kernel(const Rollou
 #include "nig_split_body.inc"
 }
 
-// whole blocks of 64*NP lanes, PAIRED start; the caller (launch_rollout_form) has checked that the form applies
-template <class Env, int NP, bool NOISE = false, bool SAMPLED = false>
-static void launch_split_blocks(int out_mode, const RolloutArgs &q, unsigned grid, hipStream_t st)
+// whole blocks of 64*NP lanes, PAIRED start; the caller (nig_launch.hpp, from the launch plan) has checked that the form applies
+// (NOISE, injected draws: the row-major full-output variant only -- OUT == 3)
+template <class Env, int NP, int OUT, bool NOISE = false, bool SAMPLED = false>
+static void launch_split_blocks(const RolloutArgs &q, unsigned grid, hipStream_t st)
 {
-    if constexpr (NOISE) {                         // injected draws: the row-major full-output variant only (nig_rollout_noise)
-        hipLaunchKernelGGL((split_rollout_kernel<Env, 3, NP, true>), dim3(grid), dim3(192 * NP), 0, st, q);
-        return;
-    }
-    if constexpr (SAMPLED) {
-        switch (out_mode) {
-        case 0: hipLaunchKernelGGL((split_sampled_kernel<Env, 0, NP>), dim3(grid), dim3(192 * NP), 0, st, q); break;
-        case 1: hipLaunchKernelGGL((split_sampled_kernel<Env, 1, NP>), dim3(grid), dim3(192 * NP), 0, st, q); break;
-        case 2: hipLaunchKernelGGL((split_sampled_kernel<Env, 2, NP>), dim3(grid), dim3(192 * NP), 0, st, q); break;
-        default: hipLaunchKernelGGL((split_sampled_kernel<Env, 3, NP>), dim3(grid), dim3(192 * NP), 0, st, q); break;
-        }
-        return;
-    }
-    switch (out_mode) {
-    case 0: hipLaunchKernelGGL((split_rollout_kernel<Env, 0, NP>), dim3(grid), dim3(192 * NP), 0, st, q); break;
-    case 1: hipLaunchKernelGGL((split_rollout_kernel<Env, 1, NP>), dim3(grid), dim3(192 * NP), 0, st, q); break;
-    case 2: hipLaunchKernelGGL((split_rollout_kernel<Env, 2, NP>), dim3(grid), dim3(192 * NP), 0, st, q); break;
-    default: hipLaunchKernelGGL((split_rollout_kernel<Env, 3, NP>), dim3(grid), dim3(192 * NP), 0, st, q); break;
-    }
+    if constexpr (SAMPLED) { hipLaunchKernelGGL((split_sampled_kernel<Env, OUT, NP>), dim3(grid), dim3(192 * NP), 0, st, q); return; }
+    hipLaunchKernelGGL((split_rollout_kernel<Env, OUT, NP, NOISE>), dim3(grid), dim3(192 * NP), 0, st, q);   // (no `else`: nig_launch.hpp)
 }
 
 }  // namespace nig

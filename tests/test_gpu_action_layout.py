@@ -76,7 +76,7 @@ def test_powergrid_wide_form_reads_a_row_major_ring_natively(ni, outputs, B):
                                               (66048 + 512, "aos", True)])
 def test_powergrid_small_batch_forms_and_the_row_major_ring(ni, B, outputs, native):
     """PowerGrid below the wide threshold, default knobs: every LDS-resident form reads the row-major slots natively (the
-    launcher's own predicate, rollout_rows_native), the paired regime's register-resident stepper (reward + flags / no outputs)
+    launcher's own predicate, rollout_rows_native in csrc/nig_launch.hpp, which asks the launch plan), the paired regime's register-resident stepper (reward + flags / no outputs)
     takes the row copy; bit-identical to rows either way."""
     ni.tune(wide_min_blocks=-1, split_blocks=-1)
     R = 600 if B < 4096 else 16

@@ -329,7 +329,7 @@ def test_rollout_frozen_lanes_rows(ni, knobs, key, B, autoreset, outputs):
     for a nig_reset while the others restart).  What the header now states: a frozen lane's row holds
     NIG_FLAG_INACTIVE | step, reward 0.0f and the state the lane holds -- written, at every pitch, and nothing else is.
     Kernel form: a handle on which a lane can be frozen takes rollout_kernel for every block, whatever the knobs say
-    (csrc/nig_kernels.hpp launch_rollout_form: the three-wave, wide and paired forms require `plain` = auto-reset and no
+    (csrc/nig_launch_plan.hpp plan_rollout: the three-wave, wide and paired forms require `plain` = auto-reset and no
     held lane), so frozen lanes do not exist in the other forms.  No naming rule covers such handles; the cases run with
     the knobs that would select each other form for a plain handle of the size (and with them off) and must give the
     same bits."""

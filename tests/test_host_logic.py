@@ -307,7 +307,7 @@ def test_bench_traffic_lookup_is_per_env_step_and_keyed_by_plan_length():
 
 
 def test_bench_names_the_kernel_the_library_launches():
-    """bench.py's roofline.kernel follows the host rule of csrc/nig_kernels.hpp launch_rollout_form: the three-wave
+    """bench.py's roofline.kernel follows the host rule of csrc/nig_launch_plan.hpp plan_rollout: the three-wave
     form for ChemicalReactor batches of whole 256-lane blocks that are at most one round (one block per CU) or whose
     last round is at least 3/4 full; everything else the one-wave rollout_kernel."""
     import types
