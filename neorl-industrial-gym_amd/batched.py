@@ -26,6 +26,27 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _rows(t: Optional[torch.Tensor], dtype, n_steps: Optional[int] = None):
+    """(pointer, row stride) of an optional per-step output: [rows, >=B] (stride of its rows; at least n_steps rows when
+    n_steps is given) or [B] (stride 0: every step overwrites it)."""
+    if t is None:
+        return None, 0
+    assert t.dtype == dtype and t.stride(-1) == 1
+    if t.dim() == 2:
+        assert n_steps is None or t.shape[0] >= n_steps
+        return C.c_void_p(t.data_ptr()), t.stride(0)
+    return C.c_void_p(t.data_ptr()), 0
+
+
+def _mlp_weights(weights, shapes):
+    """[(W, b), ...] -> the six contiguous float32 host arrays W1, b1, W2, b2, W3, b3, shapes asserted."""
+    W = [np.ascontiguousarray(np.asarray(x), dtype=np.float32) for pair in weights for x in pair]
+    if W[4].ndim == 1 and shapes[4][1:] == (1,):
+        W[4] = W[4].reshape(-1, 1)                     # a critic's head given as a vector
+    assert [w.shape for w in W] == shapes, [w.shape for w in W]
+    return W
+
+
 class StepInfo:
     """Lazy view of the per-lane flag words of one step (the batched `info`).
 
@@ -334,17 +355,8 @@ class BatchedIndustrialEnv:
     def _rollout_outputs(self, n_steps, reward_out, flags_out, obs_out):
         """The output arguments of nig_rollout / nig_rollout_sampled from the optional tensors, validated:
         (reward ptr, flags ptr, out_stride, obs ptr, ld_obs, obs_step_stride)."""
-        def out(t, dtype):
-            if t is None:
-                return None, 0
-            assert t.dtype == dtype and t.stride(-1) == 1
-            if t.dim() == 2:
-                assert t.shape[0] >= n_steps
-                return C.c_void_p(t.data_ptr()), t.stride(0)
-            return C.c_void_p(t.data_ptr()), 0
-
-        rp, rs = out(reward_out, torch.float32)
-        fp, fs = out(flags_out, torch.int32)
+        rp, rs = _rows(reward_out, torch.float32, n_steps)
+        fp, fs = _rows(flags_out, torch.int32, n_steps)
         assert (rp is None) == (fp is None), "reward_out and flags_out go together (both or neither)"
         assert rp is None or rs == fs, "reward/flags outputs must share their row stride"
         assert obs_out is None or rp is not None, "an observation trajectory needs reward_out and flags_out too"
@@ -411,28 +423,31 @@ class BatchedIndustrialEnv:
             _lib.check(self._L.nig_set_policy(self._h, C.byref(P), self._stream()))
         self._policy = policy
 
+    def _actor_shapes(self):
+        S, A, Hd = self.state_dim, self.action_dim, 256
+        return [(S, Hd), (Hd,), (Hd, Hd), (Hd,), (Hd, A), (A,)]
+
     def set_mlp_policy(self, weights):
         """Install the reference agents' actor (S->256->256->A, ReLU, tanh) for rollout_mlp():
         weights = [(W1 [S,256], b1), (W2 [256,256], b2), (W3 [256,A], b3)], host arrays, [in, out]."""
-        W = [np.ascontiguousarray(np.asarray(x), dtype=np.float32) for pair in weights for x in pair]
-        S, A, Hd = self.state_dim, self.action_dim, 256
-        assert [w.shape for w in W] == [(S, Hd), (Hd,), (Hd, Hd), (Hd,), (Hd, A), (A,)], [w.shape for w in W]
+        Hd = 256
+        W = _mlp_weights(weights, self._actor_shapes())
         with torch.cuda.device(self._dev_index):
             _lib.check(self._L.nig_set_mlp_policy(self._h, Hd, *[w.ctypes.data_as(C.c_void_p) for w in W], self._stream()))
 
     def rollout_mlp(self, n_steps: int, reward_out=None, flags_out=None, obs_out=None, act_out=None):
         """Closed loop with the installed MLP actor evaluated by f32 MFMA inside the env kernel
         (same outputs as rollout_policy)."""
-        self.rollout_policy(n_steps, reward_out, flags_out, obs_out, act_out, _fn=self._L.nig_rollout_mlp)
+        rp, fp, os_, op, so, ap, lda, sa = self._closed_loop_outputs(n_steps, reward_out, flags_out, obs_out, act_out)
+        with torch.cuda.device(self._dev_index):
+            _lib.check(self._L.nig_rollout_mlp(self._h, int(n_steps), rp, fp, os_, op, so, ap, lda, sa, self._stream()))
 
     def set_mlp_safety(self, weights, threshold: float):
         """Install the reference agents' safety critic ((S+A)->256->256->1, ReLU, sigmoid) for rollout_mlp_safe():
         weights = [(C1 [S+A,256], c1), (C2 [256,256], c2), (C3 [256,1], c3)], host arrays, [in, out].  The action
         is halved unless p < threshold (the threshold is used as given).  Replacing the actor keeps the critic."""
-        W = [np.ascontiguousarray(np.asarray(x), dtype=np.float32) for pair in weights for x in pair]
         D, Hd = self.state_dim + self.action_dim, 256
-        W[4] = W[4].reshape(-1, 1) if W[4].ndim == 1 else W[4]
-        assert [w.shape for w in W] == [(D, Hd), (Hd,), (Hd, Hd), (Hd,), (Hd, 1), (1,)], [w.shape for w in W]
+        W = _mlp_weights(weights, [(D, Hd), (Hd,), (Hd, Hd), (Hd,), (Hd, 1), (1,)])
         with torch.cuda.device(self._dev_index):
             _lib.check(self._L.nig_set_mlp_safety(self._h, Hd, *[w.ctypes.data_as(C.c_void_p) for w in W],
                                                   float(threshold), self._stream()))
@@ -441,8 +456,11 @@ class BatchedIndustrialEnv:
         """rollout_mlp() with the safety-critic shield (predict_with_safety on the device): act_out holds the action the
         env received; prob_out float32 [n_steps, >=B] the critic's p of the unshielded action (same row stride as
         reward_out / flags_out); flags carry FLAG_SHIELDED where the action was halved."""
-        self.rollout_policy(n_steps, reward_out, flags_out, obs_out, act_out, _fn=self._L.nig_rollout_mlp_safe,
-                            _prob=prob_out)
+        rp, fp, os_, op, so, ap, lda, sa = self._closed_loop_outputs(n_steps, reward_out, flags_out, obs_out, act_out)
+        pp, ps = _rows(prob_out, torch.float32, n_steps)
+        assert pp is None or (rp is None and fp is None) or ps == os_, "prob_out shares the reward/flags row stride"
+        with torch.cuda.device(self._dev_index):
+            _lib.check(self._L.nig_rollout_mlp_safe(self._h, int(n_steps), rp, fp, os_ or ps, op, so, ap, lda, sa, pp, self._stream()))
 
     def set_mlp_ensemble(self, members, weights=None, weight_sum=None, method: str = "mean", uncertainty_threshold: float = 0.2):
         """Install an ensemble of actors (agents/ensemble.py EnsembleAgent) for rollout_mlp_ensemble(): `members` = a list of
@@ -451,10 +469,8 @@ class BatchedIndustrialEnv:
         NumPy when None); "voting": both ignored.  policies.EnsemblePolicy.install() derives all of it from an agent."""
         if method not in ("mean", "weighted", "voting"):
             raise ValueError(f"Unknown ensemble method: {method}")
-        K, S, A, Hd = len(members), self.state_dim, self.action_dim, 256
-        W = [[np.ascontiguousarray(np.asarray(x), dtype=np.float32) for pair in m for x in pair] for m in members]
-        for w in W:
-            assert [x.shape for x in w] == [(S, Hd), (Hd,), (Hd, Hd), (Hd,), (Hd, A), (A,)], [x.shape for x in w]
+        K, Hd = len(members), 256
+        W = [_mlp_weights(m, self._actor_shapes()) for m in members]
         cols = [(C.c_void_p * K)(*[w[j].ctypes.data for w in W]) for j in range(6)] if K else [None] * 6
         wp, ws = None, 0.0
         if method != "voting":
@@ -472,26 +488,25 @@ class BatchedIndustrialEnv:
         to float32 for "mean" / "weighted"); unc_out float32 [n_steps, >=B] the members' disagreement (same row stride as
         reward_out / flags_out); member_act_out float32 [n_steps, K, A, >=B] every member's action (same pitches as act_out);
         flags carry FLAG_UNCERTAIN where the uncertainty exceeds the installed threshold."""
-        self.rollout_policy(n_steps, reward_out, flags_out, obs_out, act_out, _fn=self._L.nig_rollout_mlp_ensemble,
-                            _prob=unc_out, _members=member_act_out)
+        rp, fp, os_, op, so, ap, lda, sa = self._closed_loop_outputs(n_steps, reward_out, flags_out, obs_out, act_out)
+        pp, ps = _rows(unc_out, torch.float32, n_steps)
+        assert pp is None or (rp is None and fp is None) or ps == os_, "unc_out shares the reward/flags row stride"
+        mp = None
+        if member_act_out is not None:
+            K, m = getattr(self, "_ensemble_members", 0), member_act_out
+            assert m.dtype == torch.float32 and m.dim() == 4 and m.stride(3) == 1 and m.stride(0) == K * m.stride(1)
+            assert m.shape[0] >= n_steps and m.shape[1] == K and m.shape[2] == self.action_dim and m.shape[3] >= self.batch
+            assert ap is None or (m.stride(2), m.stride(1)) == (lda, sa), "member_act_out shares act_out's pitches"
+            mp, lda, sa = C.c_void_p(m.data_ptr()), m.stride(2), m.stride(1)
+        with torch.cuda.device(self._dev_index):
+            _lib.check(self._L.nig_rollout_mlp_ensemble(self._h, int(n_steps), rp, fp, os_ or ps, op, so, ap, lda, sa, pp, mp,
+                                                        self._stream()))
 
-    def rollout_policy(self, n_steps: int, reward_out: Optional[torch.Tensor] = None,
-                       flags_out: Optional[torch.Tensor] = None, obs_out: Optional[torch.Tensor] = None,
-                       act_out: Optional[torch.Tensor] = None, _fn=None, _prob=None, _members=None):
-        """n_steps closed-loop steps (action = installed policy(observation)) in ONE launch.
-        obs_out: float32 contiguous [n_steps, B, S] (observation the policy acted on);
-        act_out: float32 [n_steps, A, >=B]; reward_out / flags_out: [n_steps, >=B] or [B]."""
-        def out(t, dtype):
-            if t is None:
-                return None, 0
-            assert t.dtype == dtype and t.stride(-1) == 1
-            if t.dim() == 2:
-                assert t.shape[0] >= n_steps
-                return C.c_void_p(t.data_ptr()), t.stride(0)
-            return C.c_void_p(t.data_ptr()), 0
-
-        rp, rs = out(reward_out, torch.float32)
-        fp, fs = out(flags_out, torch.int32)
+    def _closed_loop_outputs(self, n_steps, reward_out, flags_out, obs_out, act_out):
+        """The output arguments the closed-loop rollouts share, from the optional tensors, validated:
+        (reward ptr, flags ptr, out_stride, obs ptr, obs_step_stride, act ptr, ld_act, act_step_stride)."""
+        rp, rs = _rows(reward_out, torch.float32, n_steps)
+        fp, fs = _rows(flags_out, torch.int32, n_steps)
         assert rp is None or fp is None or rs == fs
         op, so = None, 0
         if obs_out is not None:
@@ -503,26 +518,17 @@ class BatchedIndustrialEnv:
             assert act_out.dtype == torch.float32 and act_out.dim() == 3 and act_out.stride(2) == 1
             assert act_out.shape[0] >= n_steps and act_out.shape[1] == self.action_dim and act_out.shape[2] >= self.batch
             ap, lda, sa = C.c_void_p(act_out.data_ptr()), act_out.stride(1), act_out.stride(0)
+        return rp, fp, rs or fs, op, so, ap, lda, sa
+
+    def rollout_policy(self, n_steps: int, reward_out: Optional[torch.Tensor] = None,
+                       flags_out: Optional[torch.Tensor] = None, obs_out: Optional[torch.Tensor] = None,
+                       act_out: Optional[torch.Tensor] = None):
+        """n_steps closed-loop steps (action = installed policy(observation)) in ONE launch.
+        obs_out: float32 contiguous [n_steps, B, S] (observation the policy acted on);
+        act_out: float32 [n_steps, A, >=B]; reward_out / flags_out: [n_steps, >=B] or [B]."""
+        rp, fp, os_, op, so, ap, lda, sa = self._closed_loop_outputs(n_steps, reward_out, flags_out, obs_out, act_out)
         with torch.cuda.device(self._dev_index):
-            if _fn is self._L.nig_rollout_mlp_ensemble:
-                pp, ps = out(_prob, torch.float32)
-                assert pp is None or (rp is None and fp is None) or ps == (rs or fs), "unc_out shares the reward/flags row stride"
-                mp = None
-                if _members is not None:
-                    K, m = getattr(self, "_ensemble_members", 0), _members
-                    assert m.dtype == torch.float32 and m.dim() == 4 and m.stride(3) == 1 and m.stride(0) == K * m.stride(1)
-                    assert m.shape[0] >= n_steps and m.shape[1] == K and m.shape[2] == self.action_dim and m.shape[3] >= self.batch
-                    assert ap is None or (m.stride(2), m.stride(1)) == (lda, sa), "member_act_out shares act_out's pitches"
-                    mp, lda, sa = C.c_void_p(m.data_ptr()), m.stride(2), m.stride(1)
-                _lib.check(_fn(self._h, int(n_steps), rp, fp, rs or fs or ps, op, so, ap, lda, sa, pp, mp, self._stream()))
-                return
-            if _fn is self._L.nig_rollout_mlp_safe:
-                pp, ps = out(_prob, torch.float32)
-                assert pp is None or (rp is None and fp is None) or ps == (rs or fs), "prob_out shares the reward/flags row stride"
-                _lib.check(_fn(self._h, int(n_steps), rp, fp, rs or fs or ps, op, so, ap, lda, sa, pp, self._stream()))
-                return
-            _lib.check((_fn or self._L.nig_rollout_policy)(self._h, int(n_steps), rp, fp, rs or fs, op, so, ap, lda, sa,
-                                                           self._stream()))
+            _lib.check(self._L.nig_rollout_policy(self._h, int(n_steps), rp, fp, os_, op, so, ap, lda, sa, self._stream()))
 
     def get_dataset(self, quality: str = "mixed", scale: int = 1, chunk: int = 100):
         """Batched env.get_dataset(quality): every lane is one episode of the reference's
@@ -630,14 +636,8 @@ class StepPlan:
         self.env, self.n_steps = env, int(n_steps)
         self._keep = (action_ring, reward_ring, flags_ring)
 
-        def out(t, dtype):
-            if t is None:
-                return None, 0
-            assert t.dtype == dtype and t.stride(-1) == 1
-            return C.c_void_p(t.data_ptr()), (t.stride(0) if t.dim() == 2 else 0)
-
-        rp, rs = out(reward_ring, torch.float32)
-        fp, fs = out(flags_ring, torch.int32)
+        rp, rs = _rows(reward_ring, torch.float32)            # (a ring: no lower bound on its slots)
+        fp, fs = _rows(flags_ring, torch.int32)
         assert rs == fs or rp is None or fp is None, "reward/flags rings must share their slot stride"
         p = C.c_void_p()
         with torch.cuda.device(env._dev_index):

@@ -13,7 +13,7 @@ __global__ void __launch_bounds__(BLOCK) init_ws_kernel(uint32_t *ctr, long long
 {
     const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= ld) return;
-    ctr[i] = (i < B) ? NIG_CTR_DONE : NIG_CTR_DONE;   // nothing steps before the first reset
+    ctr[i] = NIG_CTR_DONE;   // nothing steps before the first reset
     life[i] = 0;
     if (ep_ret) ep_ret[i] = 0.0;
     if (tally) {
@@ -153,40 +153,46 @@ __global__ void __launch_bounds__(BLOCK) copy_rows_kernel(const float *src, int6
 using namespace nig;
 
 struct nig_handle {
-    int env;
-    int device;
-    unsigned cus;          // compute units of `device`: default of the kernel-form thresholds (nig_tune)
-    int64_t B;
-    uint64_t seed, env0;
-    int max_steps;
-    double dt;
-    uint32_t flags;
-    uint32_t t;            // RNG launch counter
-    uint32_t cmask;        // enabled built-in constraints (bit k)
-    nig_layout lay;
-    char *ws;
-    bool owns_ws;
-    double *scratch;       // reduce scratch [REDUCE_BLOCKS][NIG_T_ROWS] (inside workspace tail)
-    uint32_t *t_dev;       // device copy of t read by graph-replayed step kernels
-    float *state;          // state rows: inside the workspace, or an array bound by the caller
-    int64_t ld_state;
-    nig_policy *pol_dev;   // device copy of the installed policy
-    nig_policy pol_host;   // staging copy (must outlive the async H2D copy)
-    bool has_policy;
-    float *mlp_stream;     // device copy of the MFMA operand stream of the MLP actor (owned)
-    float *mlp_cstream;    // device copy of the MFMA operand stream of the safety critic (owned)
-    float mlp_threshold;   // shield threshold of nig_rollout_mlp_safe
+    int env = 0;
+    int device = 0;
+    unsigned cus = 0;          // compute units of `device`: default of the kernel-form thresholds (nig_tune)
+    int64_t B = 0;
+    uint64_t seed = 0, env0 = 0;
+    int max_steps = 0;
+    double dt = 0.0;
+    uint32_t flags = 0;
+    uint32_t t = 0;            // RNG launch counter
+    uint32_t cmask = 0;        // enabled built-in constraints (bit k)
+    nig_layout lay = {};
+    char *ws = nullptr;
+    bool owns_ws = false;
+    double *scratch = nullptr; // reduce scratch [REDUCE_BLOCKS][NIG_T_ROWS] (inside workspace tail)
+    uint32_t *t_dev = nullptr; // device copy of t read by graph-replayed step kernels
+    float *state = nullptr;    // state rows: inside the workspace, or an array bound by the caller
+    int64_t ld_state = 0;
+    nig_policy *pol_dev = nullptr;   // device copy of the installed policy
+    nig_policy pol_host = {};  // staging copy (must outlive the async H2D copy)
+    bool has_policy = false;
+    float *mlp_stream = nullptr;     // device copy of the MFMA operand stream of the MLP actor (owned)
+    float *mlp_cstream = nullptr;    // device copy of the MFMA operand stream of the safety critic (owned)
+    float mlp_threshold = 0.0f;      // shield threshold of nig_rollout_mlp_safe
     // nig_set_mlp_ensemble (owned): the members' operand streams back to back, MLP_STREAM_FLOATS floats each; their active weights
-    float *ens_stream; double *ens_w; int ens_members, ens_cap, ens_method; double ens_wsum; float ens_threshold;
-    float *act32;          // nig_step64 on an env that takes float32 actions: the narrowed rows [A][ld] (owned, lazy)
-    float *pid_mem;        // PID policies: per-lane integral / previous error, float [2*A][ld] (owned, lazy)
-    bool may_hold_done;    // some lane may carry NIG_CTR_DONE although the handle auto-resets (see HF_MAY_HOLD_DONE)
-    char *hst_pinned;      // host-buffer entry points: pinned staging + its device mirror (owned, lazy)
-    char *hst_dev;
-    size_t hst_bytes;
-    float *mirror; uint32_t ld_mirror;    // StepArgs::mirror of the next step launch (nig_step_host*), else NULL
-    float *act_soa; size_t act_soa_floats;   // nig_rollout with a row-major action ring on a kernel form that reads rows: the [A][ld] copy (owned, lazy)
+    float *ens_stream = nullptr; double *ens_w = nullptr; int ens_members = 0, ens_cap = 0, ens_method = 0; double ens_wsum = 0.0; float ens_threshold = 0.0f;
+    float *act32 = nullptr;    // nig_step64 on an env that takes float32 actions: the narrowed rows [A][ld] (owned, lazy)
+    float *pid_mem = nullptr;  // PID policies: per-lane integral / previous error, float [2*A][ld] (owned, lazy)
+    bool may_hold_done = true; // some lane may carry NIG_CTR_DONE although the handle auto-resets (see HF_MAY_HOLD_DONE)
+    char *hst_pinned = nullptr;      // host-buffer entry points: pinned staging + its device mirror (owned, lazy)
+    char *hst_dev = nullptr;
+    size_t hst_bytes = 0;
+    float *mirror = nullptr; uint32_t ld_mirror = 0;    // StepArgs::mirror of the next step launch (nig_step_host*), else NULL
+    float *act_soa = nullptr; size_t act_soa_floats = 0;   // nig_rollout with a row-major action ring on a kernel form that reads rows: the [A][ld] copy (owned, lazy)
 };
+
+// the handle's views of its workspace (nig_layout): per-lane counter words, lifetime violation counts, episode returns, tally rows
+static uint32_t *ws_ctr(const nig_handle *h) { return (uint32_t *)(h->ws + h->lay.off_ctr); }
+static long long *ws_life_viol(const nig_handle *h) { return (long long *)(h->ws + h->lay.off_life_viol); }
+static double *ws_ep_return(const nig_handle *h) { return h->lay.off_ep_return >= 0 ? (double *)(h->ws + h->lay.off_ep_return) : nullptr; }
+static double *ws_tally(const nig_handle *h) { return h->lay.off_tally >= 0 ? (double *)(h->ws + h->lay.off_tally) : nullptr; }
 
 struct nig_plan {
     nig_handle *h;
@@ -199,16 +205,20 @@ static unsigned grid_for(int64_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK)
 
 static thread_local char g_err[512] = "";
 
-static int fail(int code, const char *fmt, const char *detail = "")
-{
-    snprintf(g_err, sizeof g_err, fmt, detail);
-    return code;
-}
+static int fail(int code, const char *msg) { snprintf(g_err, sizeof g_err, "%s", msg); return code; }      // (msg is text, not a format)
+static int fail(int code, const char *fmt, const char *detail) { snprintf(g_err, sizeof g_err, fmt, detail); return code; }
+// "<fn>: <what>": the refusal of a check that several entry points share (formatted on refusal only)
+static int refuse(const char *fn, const char *what, int code = NIG_ERR_INVALID) { snprintf(g_err, sizeof g_err, "%s: %s", fn, what); return code; }
 
 #define HIP_TRY(expr)                                                        \
     do {                                                                     \
         hipError_t e_ = (expr);                                              \
         if (e_ != hipSuccess) return fail(NIG_ERR_HIP, #expr ": %s", hipGetErrorString(e_)); \
+    } while (0)
+#define NIG_TRY(expr)                                                        \
+    do {                                                                     \
+        const int rc_ = (expr);                                              \
+        if (rc_ != NIG_OK) return rc_;                                       \
     } while (0)
 
 static const nig_env_spec SPECS[NIG_NUM_ENVS] = {
@@ -256,14 +266,11 @@ namespace nig { static std::atomic<unsigned> g_diag_ring_fault{0u}; }   // NIG_R
 
 static StepArgs base_step_args(const nig_handle *h)
 {
-    const nig_layout &L = h->lay;
     StepArgs a;
     memset(&a, 0, sizeof a);
-    a.state = h->state; a.ld_state = (uint32_t)h->ld_state; a.ctr = (uint32_t *)(h->ws + L.off_ctr);
-    a.life_viol = (long long *)(h->ws + L.off_life_viol);
-    a.ep_ret = L.off_ep_return >= 0 ? (double *)(h->ws + L.off_ep_return) : nullptr;
-    a.tally = L.off_tally >= 0 ? (double *)(h->ws + L.off_tally) : nullptr;
-    a.ld = (uint32_t)L.ld; a.B = (uint32_t)h->B;
+    a.state = h->state; a.ld_state = (uint32_t)h->ld_state;
+    a.ctr = ws_ctr(h); a.life_viol = ws_life_viol(h); a.ep_ret = ws_ep_return(h); a.tally = ws_tally(h);
+    a.ld = (uint32_t)h->lay.ld; a.B = (uint32_t)h->B;
     a.env0 = h->env0; a.seed_lo = (uint32_t)h->seed; a.seed_hi = (uint32_t)(h->seed >> 32);
     a.split_blocks = nig::split_blocks_for(h->cus); a.wide_min_blocks = nig::wide_min_blocks_for(h->cus);
     a.max_steps = h->max_steps; a.dt32 = (float)h->dt; a.dt = h->dt; a.cmask = h->cmask;
@@ -344,6 +351,58 @@ unsigned wide_min_blocks_for(unsigned cus)
 }
 }
 
+// ---- argument contracts that several entry points share; `fn` names the entry point in the refusal -----------------------------
+// Per-step outputs: reward / flags rows of step k lie k * out_stride elements on (0: every step overwrites one row).  Checked in two
+// places of an entry point's order of checks: the stride first, the launch counter after the trajectory pitches.
+static int check_out_span(const char *fn, int32_t n_steps, int64_t out_stride)
+{
+    return (int64_t)n_steps * out_stride > 0xffffffffLL ? refuse(fn, "n_steps*out_stride >= 2^32") : NIG_OK;
+}
+static int check_out_stride(const nig_handle *h, const char *fn, int32_t n_steps, int64_t out_stride)
+{
+    if (out_stride != 0 && (out_stride < h->B || out_stride > NIG_MAX_PITCH)) return refuse(fn, "out_stride outside {0} U [batch, 2^26]");
+    return check_out_span(fn, n_steps, out_stride);
+}
+static int check_counter(const nig_handle *h, const char *fn, int32_t n_steps)
+{
+    return (int64_t)h->t + n_steps > 0xffffffffLL ? refuse(fn, "launch counter would wrap") : NIG_OK;
+}
+static int check_reward_flags(const char *fn, const float *reward_out, const uint32_t *flags_out)
+{
+    return (reward_out == nullptr) != (flags_out == nullptr) ? refuse(fn, "reward_out and flags_out go together (both or neither)") : NIG_OK;
+}
+
+// Closed-loop outputs (nig_rollout_policy / _mlp / _mlp_safe / _mlp_ensemble): the row-major observation trajectory and the action rows
+struct ClosedLoopOut {
+    float *reward; uint32_t *flags; int64_t out_stride;
+    float *obs; int64_t obs_step_stride;
+    float *act; int64_t ld_act, act_step_stride;
+};
+static int check_closed_loop(const nig_handle *h, const char *fn, const ClosedLoopOut &o)
+{
+    if (o.obs && (o.obs_step_stride < (int64_t)SPECS[h->env].state_dim * h->B || (o.obs_step_stride & 3) || ((uintptr_t)o.obs & 15)))
+        return refuse(fn, "obs_out needs 16-byte alignment and obs_step_stride >= S*batch (multiple of 4)");
+    if (o.act && (o.ld_act < h->B || o.ld_act > NIG_MAX_PITCH || o.act_step_stride < (int64_t)SPECS[h->env].action_dim * o.ld_act))
+        return refuse(fn, "bad action trajectory pitch");
+    return NIG_OK;
+}
+
+// The checks of both contracts, then the fields PolicyArgs and MlpArgs share (everything else of q: zero).
+template <class Args>
+static int closed_loop_args(const nig_handle *h, const char *fn, int32_t n_steps, const ClosedLoopOut &o, Args &q)
+{
+    NIG_TRY(check_out_stride(h, fn, n_steps, o.out_stride));
+    NIG_TRY(check_closed_loop(h, fn, o));
+    NIG_TRY(check_counter(h, fn, n_steps));
+    memset(&q, 0, sizeof q);
+    q.s = base_step_args(h);
+    q.s.reward = o.reward; q.s.flags = o.flags; q.s.t_off = h->t;
+    q.n_steps = n_steps; q.out_stride = (uint32_t)o.out_stride;
+    q.obs_out = o.obs; q.obs_step_stride = (uint64_t)o.obs_step_stride;
+    q.act_out = o.act; q.ld_act_out = (uint32_t)o.ld_act; q.act_step_stride = (uint64_t)o.act_step_stride;
+    return NIG_OK;
+}
+
 extern "C" {
 
 // 0.2.0: the fast-mode generator became "nig-philox-v2" (Philox4x32-7, float32 reset draws for ChemicalReactor / PowerGrid, round 3):
@@ -381,11 +440,11 @@ int nig_tune(int32_t key, int64_t value)
         nig::g_diag_ring_fault.store(value != 0 ? 1u : 0u, std::memory_order_relaxed);
         return NIG_OK;
 #else
-        return fail(NIG_ERR_UNSUPPORTED, "nig_tune: NIG_TUNE_DIAG_RING_FAULT exists in NIG_RING_SPIN_LIMIT test builds only%s");
+        return fail(NIG_ERR_UNSUPPORTED, "nig_tune: NIG_TUNE_DIAG_RING_FAULT exists in NIG_RING_SPIN_LIMIT test builds only");
 #endif
     }
     if ((key != NIG_TUNE_SPLIT_BLOCKS && key != NIG_TUNE_WIDE_MIN_BLOCKS) || value < -1 || value >= (int64_t)nig::TUNE_UNSET)
-        return fail(NIG_ERR_INVALID, "nig_tune: unknown key or value out of range%s");
+        return fail(NIG_ERR_INVALID, "nig_tune: unknown key or value out of range");
     // -1 = back to "no explicit setting": every handle uses its own device's default again
     (key == NIG_TUNE_WIDE_MIN_BLOCKS ? nig::g_wide_override : nig::g_split_override).store(value < 0 ? nig::TUNE_UNSET : (unsigned)value, std::memory_order_relaxed);
     return NIG_OK;
@@ -404,7 +463,7 @@ int64_t nig_handle_tune_get(const nig_handle *h, int32_t key)
 
 int nig_clock_stamp(void *stream, uint64_t *out)
 {
-    if (!out) return fail(NIG_ERR_INVALID, "nig_clock_stamp: NULL buffer%s");
+    if (!out) return fail(NIG_ERR_INVALID, "nig_clock_stamp: NULL buffer");
     hipLaunchKernelGGL(nig::clock_stamp_kernel, dim3(4096), dim3(64), 0, (hipStream_t)stream, (unsigned long long *)out);
     HIP_TRY(hipGetLastError());
     return NIG_OK;
@@ -422,7 +481,7 @@ const char *nig_env_name(int env) { return (env >= 0 && env < NIG_NUM_ENVS) ? NA
 
 int nig_env_spec_get(int env, nig_env_spec *out)
 {
-    if (env < 0 || env >= NIG_NUM_ENVS || !out) return fail(NIG_ERR_INVALID, "nig_env_spec_get: bad env id%s");
+    if (env < 0 || env >= NIG_NUM_ENVS || !out) return fail(NIG_ERR_INVALID, "nig_env_spec_get: bad env id");
     *out = SPECS[env];
     return NIG_OK;
 }
@@ -431,8 +490,8 @@ static int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 
 int nig_layout_query(int env, int64_t batch, uint32_t flags, nig_layout *out)
 {
-    if (env < 0 || env >= NIG_NUM_ENVS || !out) return fail(NIG_ERR_INVALID, "nig_layout_query: bad env id%s");
-    if (batch <= 0) return fail(NIG_ERR_INVALID, "nig_layout_query: batch must be positive%s");
+    if (env < 0 || env >= NIG_NUM_ENVS || !out) return fail(NIG_ERR_INVALID, "nig_layout_query: bad env id");
+    if (batch <= 0) return fail(NIG_ERR_INVALID, "nig_layout_query: batch must be positive");
     nig_layout L;
     L.batch = batch;
     L.ld = align_up(batch, 64);
@@ -458,37 +517,37 @@ int nig_layout_query(int env, int64_t batch, uint32_t flags, nig_layout *out)
 int nig_create(int env, int64_t batch, int device, uint64_t seed, uint64_t env_index0, int32_t max_episode_steps,
                double dt, uint32_t flags, void *workspace, nig_handle **out)
 {
-    if (!out) return fail(NIG_ERR_INVALID, "nig_create: out is NULL%s");
+    if (!out) return fail(NIG_ERR_INVALID, "nig_create: out is NULL");
     *out = nullptr;
-    if (env < 0 || env >= NIG_NUM_ENVS) return fail(NIG_ERR_INVALID, "nig_create: unknown env id%s");
-    if (batch <= 0 || batch > NIG_MAX_BATCH) return fail(NIG_ERR_INVALID, "nig_create: batch outside [1, 2^24]%s");
+    if (env < 0 || env >= NIG_NUM_ENVS) return fail(NIG_ERR_INVALID, "nig_create: unknown env id");
+    if (batch <= 0 || batch > NIG_MAX_BATCH) return fail(NIG_ERR_INVALID, "nig_create: batch outside [1, 2^24]");
     if (max_episode_steps < 0 || max_episode_steps > NIG_MAX_EPISODE_STEPS)
-        return fail(NIG_ERR_INVALID, "nig_create: max_episode_steps outside [1, 21845]%s");
-    if (dt < 0.0 || dt != dt) return fail(NIG_ERR_INVALID, "nig_create: bad dt%s");
+        return fail(NIG_ERR_INVALID, "nig_create: max_episode_steps outside [1, 21845]");
+    if (dt < 0.0 || dt != dt) return fail(NIG_ERR_INVALID, "nig_create: bad dt");
     if (SPECS[env].n_constraints > 3 && max_episode_steps > 16383)
-        return fail(NIG_ERR_INVALID, "nig_create: max_episode_steps > 16383 for an env with 4 safety conditions%s");
+        return fail(NIG_ERR_INVALID, "nig_create: max_episode_steps > 16383 for an env with 4 safety conditions");
     if (env == NIG_ENV_CHEMICAL_REACTOR && dt != 0.0 && dt != 0.1)
-        return fail(NIG_ERR_UNSUPPORTED, "nig_create: ChemicalReactor hard-codes dt=0.1 upstream (chemical_reactor.py:68)%s");
+        return fail(NIG_ERR_UNSUPPORTED, "nig_create: ChemicalReactor hard-codes dt=0.1 upstream (chemical_reactor.py:68)");
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0)
         return fail(NIG_ERR_NODEVICE, "nig_create: no HIP device (%s); there is no CPU fallback",
                     e != hipSuccess ? hipGetErrorString(e) : "device count is 0");
-    if (device < 0 || device >= ndev) return fail(NIG_ERR_INVALID, "nig_create: device index out of range%s");
+    if (device < 0 || device >= ndev) return fail(NIG_ERR_INVALID, "nig_create: device index out of range");
     HIP_TRY(hipSetDevice(device));
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
     nig::g_last_cus.store((unsigned)cus, std::memory_order_relaxed);
 
     nig_handle *h = new (std::nothrow) nig_handle();
-    if (!h) return fail(NIG_ERR_INVALID, "nig_create: out of host memory%s");
+    if (!h) return fail(NIG_ERR_INVALID, "nig_create: out of host memory");
     h->env = env; h->device = device; h->B = batch; h->seed = seed; h->env0 = env_index0; h->cus = (unsigned)cus;
     h->max_steps = max_episode_steps ? max_episode_steps : SPECS[env].max_episode_steps;
     h->dt = (dt != 0.0) ? dt : SPECS[env].dt;
-    h->flags = flags; h->t = 0; h->cmask = 0xFu;
+    h->flags = flags; h->cmask = 0xFu;
     nig_layout_query(env, batch, flags, &h->lay);
     if (workspace) {
-        if (((uintptr_t)workspace & 255u) != 0) { delete h; return fail(NIG_ERR_INVALID, "nig_create: workspace not 256-byte aligned%s"); }
+        if (((uintptr_t)workspace & 255u) != 0) { delete h; return fail(NIG_ERR_INVALID, "nig_create: workspace not 256-byte aligned"); }
         // the step kernel updates the episode tally and the lifetime violation count with hardware atomics executed at the
         // memory side: on host-pinned / fine-grained memory they would silently miscount
         hipPointerAttribute_t at;
@@ -503,7 +562,7 @@ int nig_create(int env, int64_t batch, int device, uint64_t seed, uint64_t env_i
                  (at.type == hipMemoryTypeDevice && at.device != device)) {
             delete h;
             return fail(NIG_ERR_INVALID, "nig_create: workspace must be ordinary device-local memory of `device` (hipMalloc / a torch CUDA tensor), "
-                                         "not host-pinned, managed or another device's memory%s");
+                                         "not host-pinned, managed or another device's memory");
         }
         h->ws = (char *)workspace; h->owns_ws = false;
     } else {
@@ -515,13 +574,10 @@ int nig_create(int env, int64_t batch, int device, uint64_t seed, uint64_t env_i
     h->pol_dev = (nig_policy *)(h->ws + h->lay.bytes - POLICY_BYTES);
     h->t_dev = (uint32_t *)(h->ws + h->lay.bytes - POLICY_BYTES - 256);
     h->scratch = (double *)(h->ws + h->lay.bytes - POLICY_BYTES - 256 - align_up((int64_t)REDUCE_BLOCKS * NIG_T_ROWS * 8, 256));
-    h->has_policy = false; h->mlp_stream = nullptr; h->mlp_cstream = nullptr; h->mlp_threshold = 0.0f; h->ens_stream = nullptr; h->ens_w = nullptr; h->ens_members = 0; h->ens_cap = 0; h->ens_method = 0; h->ens_wsum = 0.0; h->ens_threshold = 0.0f; h->act32 = nullptr; h->pid_mem = nullptr; h->may_hold_done = true; h->hst_pinned = nullptr; h->hst_dev = nullptr; h->hst_bytes = 0; h->mirror = nullptr; h->ld_mirror = 0; h->act_soa = nullptr; h->act_soa_floats = 0;
     h->state = (float *)(h->ws + h->lay.off_state); h->ld_state = h->lay.ld;
     const nig_layout &L = h->lay;
     hipLaunchKernelGGL(init_ws_kernel, dim3(grid_for(L.ld)), dim3(BLOCK), 0, (hipStream_t)0,
-                       (uint32_t *)(h->ws + L.off_ctr), (long long *)(h->ws + L.off_life_viol),
-                       L.off_ep_return >= 0 ? (double *)(h->ws + L.off_ep_return) : nullptr,
-                       L.off_tally >= 0 ? (double *)(h->ws + L.off_tally) : nullptr, L.ld, L.batch);
+                       ws_ctr(h), ws_life_viol(h), ws_ep_return(h), ws_tally(h), L.ld, L.batch);
     hipError_t le = hipGetLastError();
     if (le == hipSuccess) le = hipMemsetAsync(h->ws + L.off_state, 0, (size_t)SPECS[env].state_dim * L.ld * 4, (hipStream_t)0);
     if (le == hipSuccess) le = hipMemsetAsync(h->t_dev, 0, 256, (hipStream_t)0);      // launch counter of plans + the ring error word of test builds
@@ -554,7 +610,7 @@ int nig_destroy(nig_handle *h)
 
 int nig_get_layout(const nig_handle *h, nig_layout *out)
 {
-    if (!h || !out) return fail(NIG_ERR_INVALID, "nig_get_layout: NULL argument%s");
+    if (!h || !out) return fail(NIG_ERR_INVALID, "nig_get_layout: NULL argument");
     *out = h->lay;
     return NIG_OK;
 }
@@ -563,45 +619,42 @@ void *nig_workspace(const nig_handle *h) { return h ? (void *)h->ws : nullptr; }
 
 int nig_get_counter(const nig_handle *h, uint32_t *t)
 {
-    if (!h || !t) return fail(NIG_ERR_INVALID, "nig_get_counter: NULL argument%s");
+    if (!h || !t) return fail(NIG_ERR_INVALID, "nig_get_counter: NULL argument");
     *t = h->t;
     return NIG_OK;
 }
 
 int nig_bind_state(nig_handle *h, float *state, int64_t ld)
 {
-    if (!h) return fail(NIG_ERR_INVALID, "nig_bind_state: NULL handle%s");
+    if (!h) return fail(NIG_ERR_INVALID, "nig_bind_state: NULL handle");
     if (!state) { h->state = (float *)(h->ws + h->lay.off_state); h->ld_state = h->lay.ld; return NIG_OK; }
-    if (ld < h->B || ld > NIG_MAX_PITCH) return fail(NIG_ERR_INVALID, "nig_bind_state: ld outside [batch, 2^26]%s");
-    if (((uintptr_t)state & 3u) != 0) return fail(NIG_ERR_INVALID, "nig_bind_state: unaligned pointer%s");
+    if (ld < h->B || ld > NIG_MAX_PITCH) return fail(NIG_ERR_INVALID, "nig_bind_state: ld outside [batch, 2^26]");
+    if (((uintptr_t)state & 3u) != 0) return fail(NIG_ERR_INVALID, "nig_bind_state: unaligned pointer");
     h->state = state; h->ld_state = ld;
     return NIG_OK;
 }
 
 int nig_set_constraint_mask(nig_handle *h, uint32_t mask)
 {
-    if (!h) return fail(NIG_ERR_INVALID, "nig_set_constraint_mask: NULL handle%s");
+    if (!h) return fail(NIG_ERR_INVALID, "nig_set_constraint_mask: NULL handle");
     h->cmask = mask & 0xFu;
     return NIG_OK;
 }
 
 int nig_set_counter(nig_handle *h, uint32_t t)
 {
-    if (!h) return fail(NIG_ERR_INVALID, "nig_set_counter: NULL handle%s");
+    if (!h) return fail(NIG_ERR_INVALID, "nig_set_counter: NULL handle");
     h->t = t;
     return NIG_OK;
 }
 
 int nig_reset(nig_handle *h, const uint8_t *mask, const double *init_noise, int64_t ld_noise, void *stream)
 {
-    if (!h) return fail(NIG_ERR_INVALID, "nig_reset: NULL handle%s");
-    if (init_noise && ld_noise < h->B) return fail(NIG_ERR_INVALID, "nig_reset: ld_noise < batch%s");
-    const nig_layout &L = h->lay;
+    if (!h) return fail(NIG_ERR_INVALID, "nig_reset: NULL handle");
+    if (init_noise && ld_noise < h->B) return fail(NIG_ERR_INVALID, "nig_reset: ld_noise < batch");
     ResetArgs a;
-    a.state = h->state; a.ld_state = h->ld_state; a.ctr = (uint32_t *)(h->ws + L.off_ctr);
-    a.life_viol = (long long *)(h->ws + L.off_life_viol);
-    a.ep_ret = L.off_ep_return >= 0 ? (double *)(h->ws + L.off_ep_return) : nullptr;
-    a.ld = L.ld; a.B = h->B; a.mask = mask; a.noise = init_noise; a.ld_noise = ld_noise;
+    a.state = h->state; a.ld_state = h->ld_state; a.ctr = ws_ctr(h); a.life_viol = ws_life_viol(h); a.ep_ret = ws_ep_return(h);
+    a.ld = h->lay.ld; a.B = h->B; a.mask = mask; a.noise = init_noise; a.ld_noise = ld_noise;
     a.env0 = h->env0; a.seed_lo = (uint32_t)h->seed; a.seed_hi = (uint32_t)(h->seed >> 32); a.t = h->t;
     hipStream_t st = (hipStream_t)stream;
     launch_of(h->env)->reset(a, init_noise != nullptr, grid_for(a.B), st);
@@ -610,29 +663,43 @@ int nig_reset(nig_handle *h, const uint8_t *mask, const double *init_noise, int6
     return NIG_OK;
 }
 
+// Every argument check of nig_step / nig_step64 (`fn`: the entry point's name).  Parity mode = the caller supplies every value the
+// reference's RNG would have drawn.
+static int check_step(const nig_handle *h, const char *fn, const void *actions, int64_t ld_act, const double *step_noise,
+                      const double *reset_noise, int64_t ld_noise, const float *final_obs, int64_t ld_obs)
+{
+    if (!h) return refuse(fn, "NULL handle");
+    if (!actions || ld_act < h->B || ld_act > NIG_MAX_PITCH) return refuse(fn, "actions NULL or ld_act outside [batch, 2^26]");
+    if (step_noise || reset_noise) {
+        if (SPECS[h->env].k_step > 0 && !step_noise) return refuse(fn, "parity mode needs step_noise");
+        if ((h->flags & NIG_F_AUTORESET) != 0 && !reset_noise) return refuse(fn, "parity mode with auto-reset needs reset_noise");
+        if (ld_noise < h->B || ld_noise > NIG_MAX_PITCH) return refuse(fn, "ld_noise outside [batch, 2^26]");
+    }
+    if (final_obs && (ld_obs < h->B || ld_obs > NIG_MAX_PITCH)) return refuse(fn, "ld_obs outside [batch, 2^26]");
+    return NIG_OK;
+}
+
+// Counts the step and returns its kernel arguments, all but the action pointer (float32 or float64: the caller's).
+static StepArgs next_step_args(nig_handle *h, int64_t ld_act, const double *step_noise, const double *reset_noise, int64_t ld_noise,
+                               float *reward_out, double *reward64_out, uint32_t *flags_out, float *final_obs, int64_t ld_obs)
+{
+    h->t += 1;
+    StepArgs a = base_step_args(h);
+    a.ld_act = (uint32_t)ld_act;
+    a.step_noise = step_noise; a.reset_noise = reset_noise; a.ld_noise = (uint32_t)ld_noise;
+    a.reward = reward_out; a.reward64 = reward64_out; a.flags = flags_out; a.final_obs = final_obs; a.ld_obs = (uint32_t)ld_obs;
+    a.t_off = h->t;
+    return a;
+}
+
 int nig_step(nig_handle *h, const float *actions, int64_t ld_act, const double *step_noise, const double *reset_noise,
              int64_t ld_noise, float *reward_out, double *reward64_out, uint32_t *flags_out, float *final_obs,
              int64_t ld_obs, void *stream)
 {
-    if (!h) return fail(NIG_ERR_INVALID, "nig_step: NULL handle%s");
-    if (!actions || ld_act < h->B || ld_act > NIG_MAX_PITCH) return fail(NIG_ERR_INVALID, "nig_step: actions NULL or ld_act outside [batch, 2^26]%s");
-    const nig_env_spec &sp = SPECS[h->env];
-    const bool autoreset = (h->flags & NIG_F_AUTORESET) != 0;
-    // parity mode = the caller supplies every value the reference's RNG would have drawn
-    const bool parity = (step_noise != nullptr) || (reset_noise != nullptr);
-    if (parity) {
-        if (sp.k_step > 0 && !step_noise) return fail(NIG_ERR_INVALID, "nig_step: parity mode needs step_noise%s");
-        if (autoreset && !reset_noise) return fail(NIG_ERR_INVALID, "nig_step: parity mode with auto-reset needs reset_noise%s");
-        if (ld_noise < h->B || ld_noise > NIG_MAX_PITCH) return fail(NIG_ERR_INVALID, "nig_step: ld_noise outside [batch, 2^26]%s");
-    }
-    if (final_obs && (ld_obs < h->B || ld_obs > NIG_MAX_PITCH)) return fail(NIG_ERR_INVALID, "nig_step: ld_obs outside [batch, 2^26]%s");
-    h->t += 1;
-    StepArgs a = base_step_args(h);
-    a.actions = actions; a.ld_act = (uint32_t)ld_act;
-    a.step_noise = step_noise; a.reset_noise = reset_noise; a.ld_noise = (uint32_t)ld_noise;
-    a.reward = reward_out; a.reward64 = reward64_out; a.flags = flags_out; a.final_obs = final_obs; a.ld_obs = (uint32_t)ld_obs;
-    a.t_ptr = nullptr; a.t_off = h->t;
-    dispatch_step(h, a, parity, (hipStream_t)stream);
+    NIG_TRY(check_step(h, "nig_step", actions, ld_act, step_noise, reset_noise, ld_noise, final_obs, ld_obs));
+    StepArgs a = next_step_args(h, ld_act, step_noise, reset_noise, ld_noise, reward_out, reward64_out, flags_out, final_obs, ld_obs);
+    a.actions = actions;
+    dispatch_step(h, a, step_noise || reset_noise, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return NIG_OK;
 }
@@ -641,18 +708,8 @@ int nig_step64(nig_handle *h, const double *actions, int64_t ld_act, const doubl
                int64_t ld_noise, float *reward_out, double *reward64_out, uint32_t *flags_out, float *final_obs,
                int64_t ld_obs, void *stream)
 {
-    if (!h) return fail(NIG_ERR_INVALID, "nig_step64: NULL handle%s");
-    if (!actions || ld_act < h->B || ld_act > NIG_MAX_PITCH) return fail(NIG_ERR_INVALID, "nig_step64: actions NULL or ld_act outside [batch, 2^26]%s");
     // every argument is checked before anything is launched: a refused call enqueues nothing (the narrowing copy below included)
-    const nig_env_spec &sp = SPECS[h->env];
-    const bool autoreset = (h->flags & NIG_F_AUTORESET) != 0;
-    const bool parity = (step_noise != nullptr) || (reset_noise != nullptr);
-    if (parity) {
-        if (sp.k_step > 0 && !step_noise) return fail(NIG_ERR_INVALID, "nig_step64: parity mode needs step_noise%s");
-        if (autoreset && !reset_noise) return fail(NIG_ERR_INVALID, "nig_step64: parity mode with auto-reset needs reset_noise%s");
-        if (ld_noise < h->B || ld_noise > NIG_MAX_PITCH) return fail(NIG_ERR_INVALID, "nig_step64: ld_noise outside [batch, 2^26]%s");
-    }
-    if (final_obs && (ld_obs < h->B || ld_obs > NIG_MAX_PITCH)) return fail(NIG_ERR_INVALID, "nig_step64: ld_obs outside [batch, 2^26]%s");
+    NIG_TRY(check_step(h, "nig_step64", actions, ld_act, step_noise, reset_noise, ld_noise, final_obs, ld_obs));
     const EnvLaunch *L = launch_of(h->env);
     if (!L->step64) {                             // this env's own arithmetic takes the action as float32
         const int A = SPECS[h->env].action_dim;
@@ -663,122 +720,140 @@ int nig_step64(nig_handle *h, const double *actions, int64_t ld_act, const doubl
         return nig_step(h, h->act32, h->lay.ld, step_noise, reset_noise, ld_noise, reward_out, reward64_out, flags_out,
                         final_obs, ld_obs, stream);
     }
-    h->t += 1;
-    StepArgs a = base_step_args(h);
-    a.actions64 = actions; a.ld_act = (uint32_t)ld_act;
-    a.step_noise = step_noise; a.reset_noise = reset_noise; a.ld_noise = (uint32_t)ld_noise;
-    a.reward = reward_out; a.reward64 = reward64_out; a.flags = flags_out; a.final_obs = final_obs; a.ld_obs = (uint32_t)ld_obs;
-    a.t_ptr = nullptr; a.t_off = h->t;
-    L->step64(a, parity, grid_for(h->B), (hipStream_t)stream);
+    StepArgs a = next_step_args(h, ld_act, step_noise, reset_noise, ld_noise, reward_out, reward64_out, flags_out, final_obs, ld_obs);
+    a.actions64 = actions;
+    L->step64(a, step_noise || reset_noise, grid_for(h->B), (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return NIG_OK;
 }
 
-static int rollout_impl(nig_handle *h, int32_t n_steps, const float *action_ring, int64_t ld_act, int64_t slot_stride,
-                        int32_t ring_len, const double *step_noise, int64_t step_noise_stride, const double *reset_noise,
-                        int64_t reset_noise_stride, int64_t ld_noise, float *reward_out, uint32_t *flags_out, int64_t out_stride,
-                        float *obs_out, int64_t ld_obs, int64_t obs_step_stride, void *stream, bool sampled = false)
+// ---- fused rollout ---------------------------------------------------------------------------------------------------------
+// What nig_rollout / nig_rollout_sampled / nig_rollout_noise (and nig_rollout_mixed_obs, per segment) ask for
+struct RolloutSpec {
+    int32_t n_steps;
+    const float *action_ring; int64_t ld_act, slot_stride; int32_t ring_len;      // (sampled: not looked at)
+    const double *step_noise; int64_t step_noise_stride; const double *reset_noise; int64_t reset_noise_stride, ld_noise;
+    float *reward_out; uint32_t *flags_out; int64_t out_stride;
+    float *obs_out; int64_t ld_obs, obs_step_stride;
+    bool sampled;
+};
+
+// The kernel arguments of handle h's lanes, which start `lane0` columns into every array of the request (recorded draws apart)
+static RolloutArgs rollout_args(const nig_handle *h, const RolloutSpec &c, int64_t lane0)
 {
-    // sampled (nig_rollout_sampled): no ring -- the four ring arguments are not looked at, every other check is this function's
-    if (!h || n_steps <= 0 || (!sampled && (!action_ring || ring_len <= 0))) return fail(NIG_ERR_INVALID, "nig_rollout: bad argument%s");
-    if (sampled) { action_ring = nullptr; ld_act = h->lay.ld; slot_stride = 0; ring_len = 1; }
-    // ld_act == 0: the ring is ROW-MAJOR, slot s = [B][A] at action_ring + s * slot_stride (what an agent's batched output looks like)
-    const bool act_aos = !sampled && ld_act == 0;
-    const int A_ = SPECS[h->env].action_dim;
-    if (sampled) {
-    } else if (act_aos) {
-        if (step_noise || reset_noise) return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_noise: the recorded-draw launches take [A][ld_act] action rows%s");
-        if (slot_stride < (int64_t)A_ * h->B || slot_stride > 0xffffffffLL)
-            return fail(NIG_ERR_INVALID, "nig_rollout: row-major action ring: slot_stride smaller than one [batch][A] slot (or >= 2^32)%s");
-    } else {
-    if (ld_act < h->B || ld_act > NIG_MAX_PITCH) return fail(NIG_ERR_INVALID, "nig_rollout: ld_act outside {0} U [batch, 2^26]%s");
-    if (slot_stride < (int64_t)A_ * ld_act || slot_stride > 0xffffffffLL)
-        return fail(NIG_ERR_INVALID, "nig_rollout: slot_stride smaller than one [A][ld_act] slot (or >= 2^32)%s");
-    }
-    if (out_stride != 0 && (out_stride < h->B || out_stride > NIG_MAX_PITCH))
-        return fail(NIG_ERR_INVALID, "nig_rollout: out_stride outside {0} U [batch, 2^26]%s");
-    if ((int64_t)n_steps * out_stride > 0xffffffffLL) return fail(NIG_ERR_INVALID, "nig_rollout: n_steps*out_stride >= 2^32%s");
-    const bool obs_aos = obs_out && ld_obs == 0;
-    if (obs_out && !obs_aos && (ld_obs < h->B || ld_obs > NIG_MAX_PITCH ||
-                                (obs_step_stride != 0 && obs_step_stride < (int64_t)SPECS[h->env].state_dim * ld_obs)))
-        return fail(NIG_ERR_INVALID, "nig_rollout: bad observation trajectory pitch%s");
-    if (obs_aos && ((obs_step_stride != 0 && obs_step_stride < (int64_t)SPECS[h->env].state_dim * h->B) || (obs_step_stride & 3) || ((uintptr_t)obs_out & 15)))
-        return fail(NIG_ERR_INVALID, "nig_rollout: row-major trajectory needs 16-byte alignment and obs_step_stride 0 or >= S*batch (multiple of 4)%s");
-    if ((int64_t)h->t + n_steps > 0xffffffffLL) return fail(NIG_ERR_INVALID, "nig_rollout: launch counter would wrap%s");
     RolloutArgs q;
     memset(&q, 0, sizeof q);
     q.s = base_step_args(h);
-    q.s.actions = action_ring; q.s.ld_act = (uint32_t)ld_act;
-    q.s.reward = reward_out; q.s.flags = flags_out;
-    q.s.t_ptr = nullptr; q.s.t_off = h->t;
-    q.n_steps = n_steps; q.it0 = 0; q.ring_len = ring_len; q.slot_stride = (uint32_t)slot_stride; q.out_stride = (uint32_t)out_stride;
-    q.obs_out = obs_out; q.ld_obs_out = (uint32_t)ld_obs; q.obs_step_stride = (uint64_t)obs_step_stride; q.obs_aos = obs_aos ? 1 : 0;
+    q.s.actions = c.action_ring ? c.action_ring + lane0 : nullptr; q.s.ld_act = (uint32_t)c.ld_act;
+    q.s.reward = c.reward_out ? c.reward_out + lane0 : nullptr;
+    q.s.flags = c.flags_out ? c.flags_out + lane0 : nullptr;
+    q.s.t_off = h->t;
+    q.n_steps = c.n_steps; q.ring_len = c.ring_len; q.slot_stride = (uint32_t)c.slot_stride; q.out_stride = (uint32_t)c.out_stride;
+    q.obs_out = c.obs_out ? c.obs_out + lane0 : nullptr; q.ld_obs_out = (uint32_t)c.ld_obs; q.obs_step_stride = (uint64_t)c.obs_step_stride;
+    q.obs_aos = (c.obs_out && c.ld_obs == 0) ? 1 : 0;
+    return q;
+}
+
+static int rollout_impl(nig_handle *h, RolloutSpec c, void *stream)
+{
+    const char *const fn = "nig_rollout";
+    // 1. validate
+    if (!h || c.n_steps <= 0 || (!c.sampled && (!c.action_ring || c.ring_len <= 0))) return refuse(fn, "bad argument");
+    const nig_env_spec &sp = SPECS[h->env];
+    // ld_act == 0: the ring is ROW-MAJOR, slot s = [B][A] at action_ring + s * slot_stride (what an agent's batched output looks like)
+    const bool act_aos = !c.sampled && c.ld_act == 0;
+    const bool noise = c.step_noise || c.reset_noise;      // nig_rollout_noise: the reference's recorded draws
+    if (c.sampled) {                                       // no ring: the kernel's ring fields take fixed values
+        c.action_ring = nullptr; c.ld_act = h->lay.ld; c.slot_stride = 0; c.ring_len = 1;
+    } else if (act_aos) {
+        if (noise) return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_noise: the recorded-draw launches take [A][ld_act] action rows");
+        if (c.slot_stride < (int64_t)sp.action_dim * h->B || c.slot_stride > 0xffffffffLL)
+            return refuse(fn, "row-major action ring: slot_stride smaller than one [batch][A] slot (or >= 2^32)");
+    } else {
+        if (c.ld_act < h->B || c.ld_act > NIG_MAX_PITCH) return refuse(fn, "ld_act outside {0} U [batch, 2^26]");
+        if (c.slot_stride < (int64_t)sp.action_dim * c.ld_act || c.slot_stride > 0xffffffffLL)
+            return refuse(fn, "slot_stride smaller than one [A][ld_act] slot (or >= 2^32)");
+    }
+    NIG_TRY(check_out_stride(h, fn, c.n_steps, c.out_stride));
+    const bool obs_aos = c.obs_out && c.ld_obs == 0;
+    if (c.obs_out && !obs_aos && (c.ld_obs < h->B || c.ld_obs > NIG_MAX_PITCH ||
+                                  (c.obs_step_stride != 0 && c.obs_step_stride < (int64_t)sp.state_dim * c.ld_obs)))
+        return refuse(fn, "bad observation trajectory pitch");
+    if (obs_aos && ((c.obs_step_stride != 0 && c.obs_step_stride < (int64_t)sp.state_dim * h->B) || (c.obs_step_stride & 3) || ((uintptr_t)c.obs_out & 15)))
+        return refuse(fn, "row-major trajectory needs 16-byte alignment and obs_step_stride 0 or >= S*batch (multiple of 4)");
+    NIG_TRY(check_counter(h, fn, c.n_steps));
+    NIG_TRY(check_reward_flags(fn, c.reward_out, c.flags_out));
+    if (c.obs_out && !c.reward_out) return refuse(fn, "an observation trajectory needs reward_out and flags_out too");
+    const int out_mode = !c.reward_out ? 0 : (!c.obs_out ? 1 : (obs_aos ? 3 : 2));
+    if (noise) {
+        const char *const nf = "nig_rollout_noise";
+        if (h->env > NIG_ENV_ROBOT_ASSEMBLY)
+            return refuse(nf, "only the envs the reference can record draws for (ChemicalReactor, PowerGrid, RobotAssembly)", NIG_ERR_UNSUPPORTED);
+        if (out_mode != 3)
+            return refuse(nf, "the injected-draw kernels exist for the row-major trajectory (obs_out with ld_obs == 0) only", NIG_ERR_UNSUPPORTED);
+        if (c.ring_len < c.n_steps) return refuse(nf, "recorded draws belong to recorded actions: ring_len >= n_steps");
+        if (c.ld_noise < h->B || c.ld_noise > NIG_MAX_PITCH) return refuse(nf, "ld_noise outside [batch, 2^26]");
+        if (sp.k_step > 0 && (!c.step_noise || c.step_noise_stride < (int64_t)sp.k_step * c.ld_noise))
+            return refuse(nf, "step_noise NULL or its step stride smaller than one [k_step][ld_noise] row set");
+        if ((h->flags & NIG_F_AUTORESET) != 0 && sp.k_reset > 0 && (!c.reset_noise || c.reset_noise_stride < (int64_t)sp.k_reset * c.ld_noise))
+            return refuse(nf, "an auto-reset handle needs reset_noise, step stride >= one [k_reset][ld_noise] row set");
+    }
+    // 2. kernel arguments
+    RolloutArgs q = rollout_args(h, c, 0);
     hipStream_t st = (hipStream_t)stream;
-    if ((reward_out == nullptr) != (flags_out == nullptr))
-        return fail(NIG_ERR_INVALID, "nig_rollout: reward_out and flags_out go together (both or neither)%s");
-    if (obs_out && !reward_out)
-        return fail(NIG_ERR_INVALID, "nig_rollout: an observation trajectory needs reward_out and flags_out too%s");
-    const int out_mode = !reward_out ? 0 : (!obs_out ? 1 : (obs_aos ? 3 : 2));
+    // 3. row-major action ring
     if (act_aos) {
         // NATIVE where every kernel of the launch reads a lane's actions as contiguous bytes: PowerGrid's LDS-resident body
         // (csrc/nig_pg_lds.hpp: two 16-byte loads per lane, 2 KiB contiguous per wave instead of eight 256-byte row segments) in its
         // wide 512 / 256 and paired forms -- the launcher's own predicate (rollout_rows_native, next to launch_rollout_form) -- and
         // 16-byte aligned slots.  Every other launch reads [A][ld] rows: the ring is transposed into a buffer the handle owns, on
         // the caller's stream, per call.
-        const bool native = launch_of(h->env)->rows_native(out_mode, q) && ((uintptr_t)action_ring & 15) == 0 && (slot_stride & 3) == 0;
+        const int A = sp.action_dim;
+        const bool native = launch_of(h->env)->rows_native(out_mode, q) && ((uintptr_t)c.action_ring & 15) == 0 && (c.slot_stride & 3) == 0;
         if (!native) {
-            if ((int64_t)A_ * h->lay.ld > 0xffffffffLL) return fail(NIG_ERR_INVALID, "nig_rollout: row-major action ring: batch too large for the row copy%s");
-            const int used = ring_len < n_steps ? ring_len : n_steps;     // the slots this call reads: step k takes slot k % ring_len, from 0
-            const size_t need = (size_t)used * A_ * (size_t)h->lay.ld;
+            if ((int64_t)A * h->lay.ld > 0xffffffffLL) return refuse(fn, "row-major action ring: batch too large for the row copy");
+            const int used = c.ring_len < c.n_steps ? c.ring_len : c.n_steps;     // the slots this call reads: step k takes slot k % ring_len, from 0
+            const size_t need = (size_t)used * A * (size_t)h->lay.ld;
             if (h->act_soa_floats < need) {
                 if (h->act_soa) { HIP_TRY(hipStreamSynchronize(st)); (void)hipFree(h->act_soa); h->act_soa = nullptr; h->act_soa_floats = 0; }
                 HIP_TRY(hipMalloc((void **)&h->act_soa, need * sizeof(float)));
                 h->act_soa_floats = need;
             }
             hipLaunchKernelGGL(nig::action_rows_kernel, dim3(grid_for(h->B), (unsigned)(used < 65535 ? used : 65535)), dim3(BLOCK), 0, st,
-                               action_ring, slot_stride, h->act_soa, h->lay.ld, h->B, A_, used);
+                               c.action_ring, c.slot_stride, h->act_soa, h->lay.ld, h->B, A, used);
             HIP_TRY(hipGetLastError());
-            q.s.actions = h->act_soa; q.s.ld_act = (uint32_t)h->lay.ld; q.slot_stride = (uint32_t)((int64_t)A_ * h->lay.ld);
+            q.s.actions = h->act_soa; q.s.ld_act = (uint32_t)h->lay.ld; q.slot_stride = (uint32_t)((int64_t)A * h->lay.ld);
         }
     }
-    if (step_noise || reset_noise) {               // nig_rollout_noise: the reference's recorded draws
-        const nig_env_spec &sp = SPECS[h->env];
-        if (h->env > NIG_ENV_ROBOT_ASSEMBLY)
-            return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_noise: only the envs the reference can record draws for (ChemicalReactor, PowerGrid, RobotAssembly)%s");
-        if (out_mode != 3)
-            return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_noise: the injected-draw kernels exist for the row-major trajectory (obs_out with ld_obs == 0) only%s");
-        if (ring_len < n_steps) return fail(NIG_ERR_INVALID, "nig_rollout_noise: recorded draws belong to recorded actions: ring_len >= n_steps%s");
-        if (ld_noise < h->B || ld_noise > NIG_MAX_PITCH) return fail(NIG_ERR_INVALID, "nig_rollout_noise: ld_noise outside [batch, 2^26]%s");
-        if (sp.k_step > 0 && (!step_noise || step_noise_stride < (int64_t)sp.k_step * ld_noise))
-            return fail(NIG_ERR_INVALID, "nig_rollout_noise: step_noise NULL or its step stride smaller than one [k_step][ld_noise] row set%s");
-        if ((h->flags & NIG_F_AUTORESET) != 0 && sp.k_reset > 0 && (!reset_noise || reset_noise_stride < (int64_t)sp.k_reset * ld_noise))
-            return fail(NIG_ERR_INVALID, "nig_rollout_noise: an auto-reset handle needs reset_noise, step stride >= one [k_reset][ld_noise] row set%s");
-        q.s.step_noise = sp.k_step > 0 ? step_noise : nullptr;
-        q.s.reset_noise = reset_noise;
-        if (!q.s.step_noise && !q.s.reset_noise) q.s.reset_noise = reset_noise ? reset_noise : step_noise;   // (keeps the launcher on the injected-draw path)
-        q.s.ld_noise = (uint32_t)ld_noise;
-        q.nz_step_stride = (uint64_t)step_noise_stride; q.nz_reset_stride = (uint64_t)reset_noise_stride;
+    // 4. recorded draws
+    if (noise) {
+        q.s.step_noise = sp.k_step > 0 ? c.step_noise : nullptr;
+        q.s.reset_noise = c.reset_noise;
+        if (!q.s.step_noise && !q.s.reset_noise) q.s.reset_noise = c.step_noise;   // (keeps the launcher on the injected-draw path)
+        q.s.ld_noise = (uint32_t)c.ld_noise;
+        q.nz_step_stride = (uint64_t)c.step_noise_stride; q.nz_reset_stride = (uint64_t)c.reset_noise_stride;
     }
-    if (sampled) launch_of(h->env)->rollout_sampled(out_mode, q, h->t + 1u, grid_for(h->B), st);
+    // 5. launch
+    if (c.sampled) launch_of(h->env)->rollout_sampled(out_mode, q, h->t + 1u, grid_for(h->B), st);
     else launch_of(h->env)->rollout(out_mode, q, h->t + 1u, grid_for(h->B), st);
     HIP_TRY(hipGetLastError());
-    h->t += (uint32_t)n_steps;
-    return ring_check(h, st, "nig_rollout");
+    h->t += (uint32_t)c.n_steps;
+    return ring_check(h, st, fn);
 }
 
 int nig_rollout(nig_handle *h, int32_t n_steps, const float *action_ring, int64_t ld_act, int64_t slot_stride,
                 int32_t ring_len, float *reward_out, uint32_t *flags_out, int64_t out_stride,
                 float *obs_out, int64_t ld_obs, int64_t obs_step_stride, void *stream)
 {
-    return rollout_impl(h, n_steps, action_ring, ld_act, slot_stride, ring_len, nullptr, 0, nullptr, 0, 0, reward_out, flags_out,
-                        out_stride, obs_out, ld_obs, obs_step_stride, stream);
+    return rollout_impl(h, {n_steps, action_ring, ld_act, slot_stride, ring_len, nullptr, 0, nullptr, 0, 0, reward_out, flags_out,
+                            out_stride, obs_out, ld_obs, obs_step_stride, false}, stream);
 }
 
 int nig_rollout_sampled(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
                         float *obs_out, int64_t ld_obs, int64_t obs_step_stride, void *stream)
 {
-    return rollout_impl(h, n_steps, nullptr, 0, 0, 0, nullptr, 0, nullptr, 0, 0, reward_out, flags_out,
-                        out_stride, obs_out, ld_obs, obs_step_stride, stream, true);
+    return rollout_impl(h, {n_steps, nullptr, 0, 0, 0, nullptr, 0, nullptr, 0, 0, reward_out, flags_out,
+                            out_stride, obs_out, ld_obs, obs_step_stride, true}, stream);
 }
 
 int nig_rollout_noise(nig_handle *h, int32_t n_steps, const float *action_ring, int64_t ld_act, int64_t slot_stride,
@@ -786,18 +861,18 @@ int nig_rollout_noise(nig_handle *h, int32_t n_steps, const float *action_ring, 
                       int64_t reset_noise_stride, int64_t ld_noise, float *reward_out, uint32_t *flags_out, int64_t out_stride,
                       float *obs_out, int64_t obs_step_stride, void *stream)
 {
-    if (!step_noise && !reset_noise) return fail(NIG_ERR_INVALID, "nig_rollout_noise: no recorded draws given (use nig_rollout)%s");
-    return rollout_impl(h, n_steps, action_ring, ld_act, slot_stride, ring_len, step_noise, step_noise_stride, reset_noise,
-                        reset_noise_stride, ld_noise, reward_out, flags_out, out_stride, obs_out, 0, obs_step_stride, stream);
+    if (!step_noise && !reset_noise) return fail(NIG_ERR_INVALID, "nig_rollout_noise: no recorded draws given (use nig_rollout)");
+    return rollout_impl(h, {n_steps, action_ring, ld_act, slot_stride, ring_len, step_noise, step_noise_stride, reset_noise,
+                            reset_noise_stride, ld_noise, reward_out, flags_out, out_stride, obs_out, 0, obs_step_stride, false}, stream);
 }
 
 int nig_set_policy(nig_handle *h, const nig_policy *policy, void *stream)
 {
-    if (!h || !policy) return fail(NIG_ERR_INVALID, "nig_set_policy: NULL argument%s");
+    if (!h || !policy) return fail(NIG_ERR_INVALID, "nig_set_policy: NULL argument");
     static_assert(sizeof(nig_policy) <= POLICY_BYTES, "policy struct outgrew its device slot");
     if (policy->kind != NIG_POLICY_AFFINE && policy->kind != NIG_POLICY_PID)
-        return fail(NIG_ERR_INVALID, "nig_set_policy: unknown policy kind%s");
-    if (!(policy->clip_lo <= policy->clip_hi)) return fail(NIG_ERR_INVALID, "nig_set_policy: clip_lo > clip_hi%s");
+        return fail(NIG_ERR_INVALID, "nig_set_policy: unknown policy kind");
+    if (!(policy->clip_lo <= policy->clip_hi)) return fail(NIG_ERR_INVALID, "nig_set_policy: clip_lo > clip_hi");
     h->pol_host = *policy;
     // recompute the non-zero column mask here so a caller cannot get it wrong
     uint32_t cm = 0;
@@ -820,25 +895,12 @@ int nig_rollout_policy(nig_handle *h, int32_t n_steps, float *reward_out, uint32
                        float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
                        int64_t act_step_stride, void *stream)
 {
-    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_policy: bad argument%s");
-    if (!h->has_policy) return fail(NIG_ERR_INVALID, "nig_rollout_policy: no policy installed (nig_set_policy)%s");
-    if (out_stride != 0 && (out_stride < h->B || out_stride > NIG_MAX_PITCH))
-        return fail(NIG_ERR_INVALID, "nig_rollout_policy: out_stride outside {0} U [batch, 2^26]%s");
-    if ((int64_t)n_steps * out_stride > 0xffffffffLL) return fail(NIG_ERR_INVALID, "nig_rollout_policy: n_steps*out_stride >= 2^32%s");
-    if (obs_out && (obs_step_stride < (int64_t)SPECS[h->env].state_dim * h->B || (obs_step_stride & 3) || ((uintptr_t)obs_out & 15)))
-        return fail(NIG_ERR_INVALID, "nig_rollout_policy: obs_out needs 16-byte alignment and obs_step_stride >= S*batch (multiple of 4)%s");
-    if (act_out && (ld_act < h->B || ld_act > NIG_MAX_PITCH || act_step_stride < (int64_t)SPECS[h->env].action_dim * ld_act))
-        return fail(NIG_ERR_INVALID, "nig_rollout_policy: bad action trajectory pitch%s");
-    if ((int64_t)h->t + n_steps > 0xffffffffLL) return fail(NIG_ERR_INVALID, "nig_rollout_policy: launch counter would wrap%s");
+    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_policy: bad argument");
+    if (!h->has_policy) return fail(NIG_ERR_INVALID, "nig_rollout_policy: no policy installed (nig_set_policy)");
     PolicyArgs q;
-    memset(&q, 0, sizeof q);
-    q.s = base_step_args(h);
-    q.s.reward = reward_out; q.s.flags = flags_out;
-    q.s.t_ptr = nullptr; q.s.t_off = h->t;
-    q.pol = h->pol_dev; q.n_steps = n_steps; q.out_stride = (uint32_t)out_stride;
+    NIG_TRY(closed_loop_args(h, "nig_rollout_policy", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, q));
+    q.pol = h->pol_dev;
     q.pid = (h->pol_host.kind == NIG_POLICY_PID) ? h->pid_mem : nullptr;
-    q.obs_out = obs_out; q.obs_step_stride = (uint64_t)obs_step_stride;
-    q.act_out = act_out; q.ld_act_out = (uint32_t)ld_act; q.act_step_stride = (uint64_t)act_step_stride;
     q.pol_kind = h->pol_host.kind;
     hipStream_t st = (hipStream_t)stream;
     launch_of(h->env)->policy(q, grid_for(h->B), st);
@@ -850,31 +912,40 @@ int nig_rollout_policy(nig_handle *h, int32_t n_steps, float *reward_out, uint32
 // Row of a 32x32 MFMA result tile held in register t by lane half hf (MI355X_MICROARCH / guide section 3).
 static inline int mfma_row(int t, int hf) { return (t & 3) + 8 * (t >> 2) + 4 * hf; }
 
-// The MFMA operand stream of one actor (S -> 256 -> 256 -> A), written into the zeroed host[MLP_STREAM_FLOATS]: the one builder of
+// MFMA operand streams, built in exactly the order the kernels consume them, chunk by chunk (a chunk = one fill of an LDS buffer,
+// MLP_CHREC record slots, zero padded).  Record = 64 floats; lane l = (i = l & 31, hf = l >> 5) holds W[k(hf)][32*tile + i].
+static float *stream_rec(float *host, int chunk, int r) { return host + ((size_t)chunk * MLP_CHREC + r) * 64; }
+
+// Layer 2 of hidden tile m2 at the head of `chunk` (actor and critic alike): the weight records, k following the accumulator
+// register order of h1, then the bias record.  Returns the index of the next record.
+static int put_layer2(float *host, int chunk, int m2, const float *W2, const float *b2)
+{
+    const int H = MLP_H;
+    int r = 0;
+    for (int kt = 0; kt < MLP_MT; ++kt)
+        for (int t = 0; t < 16; ++t, ++r)
+            for (int l = 0; l < 64; ++l)
+                stream_rec(host, chunk, r)[l] = W2[(size_t)(32 * kt + mfma_row(t, l >> 5)) * H + 32 * m2 + (l & 31)];
+    for (int l = 0; l < 32; ++l) stream_rec(host, chunk, r)[l] = b2[32 * m2 + l];
+    return r + 1;
+}
+
+// The operand stream of one actor (S -> 256 -> 256 -> A), written into the zeroed host[MLP_STREAM_FLOATS]: the one builder of
 // nig_set_mlp_policy and of every member of nig_set_mlp_ensemble.  False: internal record count mismatch.
 static bool build_mlp_stream(int S, int A, const float *W1, const float *b1, const float *W2, const float *b2, const float *W3,
                              const float *b3, float *host)
 {
     const int H = MLP_H;
-    // Build the operand stream in exactly the order rollout_mlp_kernel consumes it, chunk by chunk (a chunk = one
-    // fill of an LDS buffer, MLP_CHREC record slots, zero padded).  Record = 64 floats; lane l = (i = l & 31,
-    // hf = l >> 5) holds W[k(hf)][32*tile + i].
-    auto rec = [&](int chunk, int r) { return host + ((size_t)chunk * MLP_CHREC + r) * 64; };
+    auto rec = [&](int chunk, int r) { return stream_rec(host, chunk, r); };
     for (int m = 0; m < MLP_MT; ++m) {                      // chunk 0: layer 1, natural k order: k = 2*ks + hf
         const int R1 = S / 2 + 1;
         for (int ks = 0; ks < S / 2; ++ks)
             for (int l = 0; l < 64; ++l) rec(0, m * R1 + ks)[l] = W1[(size_t)(2 * ks + (l >> 5)) * H + 32 * m + (l & 31)];
         for (int l = 0; l < 32; ++l) rec(0, m * R1 + S / 2)[l] = b1[32 * m + l];
     }
-    for (int m2 = 0; m2 < MLP_MT; ++m2) {                   // chunk 1 + m2
-        int r = 0;
-        for (int kt = 0; kt < MLP_MT; ++kt)                   // layer 2: k follows the accumulator register order of h1
-            for (int t = 0; t < 16; ++t, ++r)
-                for (int l = 0; l < 64; ++l)
-                    rec(1 + m2, r)[l] = W2[(size_t)(32 * kt + mfma_row(t, l >> 5)) * H + 32 * m2 + (l & 31)];
-        for (int l = 0; l < 32; ++l) rec(1 + m2, r)[l] = b2[32 * m2 + l];
-        ++r;
-        for (int t = 0; t < 16; ++t, ++r)                     // head: rows i >= A are zero
+    for (int m2 = 0; m2 < MLP_MT; ++m2) {                   // chunk 1 + m2: layer 2, then the head (rows i >= A are zero)
+        int r = put_layer2(host, 1 + m2, m2, W2, b2);
+        for (int t = 0; t < 16; ++t, ++r)
             for (int l = 0; l < 64; ++l) {
                 if (A <= 4) {                                 // v_mfma_f32_4x4x1: lane 4 b + i of every 4-lane block holds head row i of ITS half's hidden row
                     if ((l & 3) < A) rec(1 + m2, r)[l] = W3[(size_t)(32 * m2 + mfma_row(t, l >> 5)) * A + (l & 3)];
@@ -892,81 +963,15 @@ static bool build_mlp_stream(int S, int A, const float *W1, const float *b1, con
     return true;
 }
 
-int nig_set_mlp_policy(nig_handle *h, int32_t hidden, const float *W1, const float *b1, const float *W2, const float *b2,
-                       const float *W3, const float *b3, void *stream)
+// The safety critic's stream ((S + A) -> 256 -> 256 -> 1) in the order rollout_mlp_shield_kernel consumes it (nig_kernels.hpp,
+// MLP_CDIM / MLP_CR1 / MLP_CL1), into the zeroed host[MLP_CSTREAM_FLOATS]: layer 1 on x = [s, a, 0-pad] in one chunk, or two
+// chunks of four tiles when eight tiles do not fit a chunk slot; then one chunk per hidden tile of layer 2 (128 records + bias +
+// 16 head records of the one-row 4 x 4 x 1 head), c3 after the last.  False: internal record count mismatch.
+static bool build_critic_stream(int S, int A, const float *C1, const float *c1, const float *C2, const float *c2, const float *C3,
+                                const float *c3, float *host)
 {
-    if (!h || !W1 || !b1 || !W2 || !b2 || !W3 || !b3) return fail(NIG_ERR_INVALID, "nig_set_mlp_policy: NULL argument%s");
-    if (hidden != MLP_H) return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_policy: hidden must be 256 (agents/networks.py default)%s");
-    const int S = SPECS[h->env].state_dim, A = SPECS[h->env].action_dim;
-    if (S % 2 != 0 || A > 16) return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_policy: env shape not supported (even state dim, at most 16 actions)%s");
-    float *host = (float *)calloc((size_t)MLP_STREAM_FLOATS, sizeof(float));
-    if (!host) return fail(NIG_ERR_INVALID, "nig_set_mlp_policy: out of host memory%s");
-    if (!build_mlp_stream(S, A, W1, b1, W2, b2, W3, b3, host)) { free(host); return fail(NIG_ERR_INVALID, "nig_set_mlp_policy: internal record count mismatch%s"); }
-    hipError_t e = hipSuccess;
-    if (!h->mlp_stream) e = hipMalloc((void **)&h->mlp_stream, (size_t)MLP_STREAM_FLOATS * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpyAsync(h->mlp_stream, host, (size_t)MLP_STREAM_FLOATS * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    free(host);
-    if (e != hipSuccess) return fail(NIG_ERR_HIP, "nig_set_mlp_policy: %s", hipGetErrorString(e));
-    return NIG_OK;
-}
-
-// argument checks and kernel arguments shared by nig_rollout_mlp and nig_rollout_mlp_safe
-static int mlp_args(nig_handle *h, const char *fn, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
-                    float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride, MlpArgs &q)
-{
-    char msg[160];
-    auto bad = [&](const char *what) { snprintf(msg, sizeof msg, "%s: %s", fn, what); return fail(NIG_ERR_INVALID, "%s", msg); };
-    if (out_stride != 0 && (out_stride < h->B || out_stride > NIG_MAX_PITCH)) return bad("out_stride outside {0} U [batch, 2^26]");
-    if ((int64_t)n_steps * out_stride > 0xffffffffLL) return bad("n_steps*out_stride >= 2^32");
-    if (obs_out && (obs_step_stride < (int64_t)SPECS[h->env].state_dim * h->B || (obs_step_stride & 3) || ((uintptr_t)obs_out & 15)))
-        return bad("obs_out needs 16-byte alignment and obs_step_stride >= S*batch (multiple of 4)");
-    if (act_out && (ld_act < h->B || ld_act > NIG_MAX_PITCH || act_step_stride < (int64_t)SPECS[h->env].action_dim * ld_act))
-        return bad("bad action trajectory pitch");
-    if ((int64_t)h->t + n_steps > 0xffffffffLL) return bad("launch counter would wrap");
-    memset(&q, 0, sizeof q);
-    q.s = base_step_args(h);
-    q.s.reward = reward_out; q.s.flags = flags_out;
-    q.s.t_ptr = nullptr; q.s.t_off = h->t;
-    q.wstream = h->mlp_stream; q.n_steps = n_steps; q.out_stride = (uint32_t)out_stride;
-    q.obs_out = obs_out; q.obs_step_stride = (uint64_t)obs_step_stride;
-    q.act_out = act_out; q.ld_act_out = (uint32_t)ld_act; q.act_step_stride = (uint64_t)act_step_stride;
-    return NIG_OK;
-}
-
-int nig_rollout_mlp(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
-                    float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
-                    void *stream)
-{
-    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp: bad argument%s");
-    if (!h->mlp_stream || !launch_of(h->env)->mlp) return fail(NIG_ERR_INVALID, "nig_rollout_mlp: no actor installed (nig_set_mlp_policy)%s");
-    MlpArgs q;
-    const int rc = mlp_args(h, "nig_rollout_mlp", n_steps, reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act,
-                            act_step_stride, q);
-    if (rc != NIG_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned grid = (unsigned)((h->B + BLOCK / 2 - 1) / (BLOCK / 2));     // 32 envs per wave, 128 per block
-    launch_of(h->env)->mlp(q, grid, st);
-    HIP_TRY(hipGetLastError());
-    h->t += (uint32_t)n_steps;
-    return NIG_OK;
-}
-
-int nig_set_mlp_safety(nig_handle *h, int32_t hidden, const float *C1, const float *c1, const float *C2, const float *c2,
-                       const float *C3, const float *c3, float threshold, void *stream)
-{
-    if (!h || !C1 || !c1 || !C2 || !c2 || !C3 || !c3) return fail(NIG_ERR_INVALID, "nig_set_mlp_safety: NULL argument%s");
-    if (hidden != MLP_H) return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_safety: hidden must be 256 (agents/networks.py default)%s");
-    const int S = SPECS[h->env].state_dim, A = SPECS[h->env].action_dim, H = MLP_H;
-    if (S % 2 != 0 || A > 16 || !launch_of(h->env)->mlp_shield)
-        return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_safety: env shape not supported (even state dim, at most 16 actions)%s");
-    float *host = (float *)calloc((size_t)MLP_CSTREAM_FLOATS, sizeof(float));
-    if (!host) return fail(NIG_ERR_INVALID, "nig_set_mlp_safety: out of host memory%s");
-    // The critic's stream in the order rollout_mlp_shield_kernel consumes it (nig_kernels.hpp, MLP_CDIM / MLP_CR1 / MLP_CL1):
-    // layer 1 on x = [s, a, 0-pad] in one chunk, or two chunks of four tiles when eight tiles do not fit a chunk slot; then one
-    // chunk per hidden tile of layer 2 (128 records + bias + 16 head records of the one-row 4 x 4 x 1 head), c3 after the last.
-    const int D = S + A, DP = (D + 1) & ~1, CR1 = DP / 2 + 1, CL1 = MLP_MT * CR1 <= MLP_CHREC ? 1 : 2, TPC = MLP_MT / CL1;
-    auto rec = [&](int chunk, int r) { return host + ((size_t)chunk * MLP_CHREC + r) * 64; };
+    const int H = MLP_H, D = S + A, DP = (D + 1) & ~1, CR1 = DP / 2 + 1, CL1 = MLP_MT * CR1 <= MLP_CHREC ? 1 : 2, TPC = MLP_MT / CL1;
+    auto rec = [&](int chunk, int r) { return stream_rec(host, chunk, r); };
     for (int m = 0; m < MLP_MT; ++m) {                      // layer 1, natural k order: k = 2*ks + hf (k >= S + A: zero pad)
         const int ch = m / TPC, base = (m % TPC) * CR1;
         for (int ks = 0; ks < DP / 2; ++ks)
@@ -977,24 +982,68 @@ int nig_set_mlp_safety(nig_handle *h, int32_t hidden, const float *C1, const flo
         for (int l = 0; l < 32; ++l) rec(ch, base + DP / 2)[l] = c1[32 * m + l];
     }
     for (int m2 = 0; m2 < MLP_MT; ++m2) {                   // chunk CL1 + m2: as the actor's, with a one-row head
-        int r = 0;
-        for (int kt = 0; kt < MLP_MT; ++kt)
-            for (int t = 0; t < 16; ++t, ++r)
-                for (int l = 0; l < 64; ++l)
-                    rec(CL1 + m2, r)[l] = C2[(size_t)(32 * kt + mfma_row(t, l >> 5)) * H + 32 * m2 + (l & 31)];
-        for (int l = 0; l < 32; ++l) rec(CL1 + m2, r)[l] = c2[32 * m2 + l];
-        ++r;
+        int r = put_layer2(host, CL1 + m2, m2, C2, c2);
         for (int t = 0; t < 16; ++t, ++r)                     // 4 x 4 x 1 head, row 0 only: lane 4 b holds C3 of its half's hidden row
             for (int l = 0; l < 64; l += 4) rec(CL1 + m2, r)[l] = C3[32 * m2 + mfma_row(t, l >> 5)];
-        if (r != MLP_PER) { free(host); return fail(NIG_ERR_INVALID, "nig_set_mlp_safety: internal record count mismatch%s"); }
+        if (r != MLP_PER) return false;
     }
     for (int l = 0; l < 64; l += 4) rec(CL1 + MLP_MT - 1, MLP_PER)[l] = c3[0];
+    return true;
+}
+
+// A built host image (malloc'd; freed here) -> the device stream *dev, allocated on first use; copied on `stream` and waited for.
+static int upload_stream(const char *fn, float **dev, float *host, size_t floats, void *stream)
+{
     hipError_t e = hipSuccess;
-    if (!h->mlp_cstream) e = hipMalloc((void **)&h->mlp_cstream, (size_t)MLP_CSTREAM_FLOATS * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpyAsync(h->mlp_cstream, host, (size_t)MLP_CSTREAM_FLOATS * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (!*dev) e = hipMalloc((void **)dev, floats * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpyAsync(*dev, host, floats * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     free(host);
-    if (e != hipSuccess) return fail(NIG_ERR_HIP, "nig_set_mlp_safety: %s", hipGetErrorString(e));
+    return e == hipSuccess ? NIG_OK : refuse(fn, hipGetErrorString(e), NIG_ERR_HIP);
+}
+
+static unsigned mlp_grid(const nig_handle *h) { return (unsigned)((h->B + BLOCK / 2 - 1) / (BLOCK / 2)); }   // 32 envs per wave, 128 per block
+
+int nig_set_mlp_policy(nig_handle *h, int32_t hidden, const float *W1, const float *b1, const float *W2, const float *b2,
+                       const float *W3, const float *b3, void *stream)
+{
+    if (!h || !W1 || !b1 || !W2 || !b2 || !W3 || !b3) return fail(NIG_ERR_INVALID, "nig_set_mlp_policy: NULL argument");
+    if (hidden != MLP_H) return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_policy: hidden must be 256 (agents/networks.py default)");
+    const int S = SPECS[h->env].state_dim, A = SPECS[h->env].action_dim;
+    if (S % 2 != 0 || A > 16) return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_policy: env shape not supported (even state dim, at most 16 actions)");
+    float *host = (float *)calloc((size_t)MLP_STREAM_FLOATS, sizeof(float));
+    if (!host) return fail(NIG_ERR_INVALID, "nig_set_mlp_policy: out of host memory");
+    if (!build_mlp_stream(S, A, W1, b1, W2, b2, W3, b3, host)) { free(host); return fail(NIG_ERR_INVALID, "nig_set_mlp_policy: internal record count mismatch"); }
+    return upload_stream("nig_set_mlp_policy", &h->mlp_stream, host, MLP_STREAM_FLOATS, stream);
+}
+
+int nig_rollout_mlp(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                    float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
+                    void *stream)
+{
+    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp: bad argument");
+    if (!h->mlp_stream || !launch_of(h->env)->mlp) return fail(NIG_ERR_INVALID, "nig_rollout_mlp: no actor installed (nig_set_mlp_policy)");
+    MlpArgs q;
+    NIG_TRY(closed_loop_args(h, "nig_rollout_mlp", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, q));
+    q.wstream = h->mlp_stream;
+    launch_of(h->env)->mlp(q, mlp_grid(h), (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    h->t += (uint32_t)n_steps;
+    return NIG_OK;
+}
+
+int nig_set_mlp_safety(nig_handle *h, int32_t hidden, const float *C1, const float *c1, const float *C2, const float *c2,
+                       const float *C3, const float *c3, float threshold, void *stream)
+{
+    if (!h || !C1 || !c1 || !C2 || !c2 || !C3 || !c3) return fail(NIG_ERR_INVALID, "nig_set_mlp_safety: NULL argument");
+    if (hidden != MLP_H) return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_safety: hidden must be 256 (agents/networks.py default)");
+    const int S = SPECS[h->env].state_dim, A = SPECS[h->env].action_dim;
+    if (S % 2 != 0 || A > 16 || !launch_of(h->env)->mlp_shield)
+        return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_safety: env shape not supported (even state dim, at most 16 actions)");
+    float *host = (float *)calloc((size_t)MLP_CSTREAM_FLOATS, sizeof(float));
+    if (!host) return fail(NIG_ERR_INVALID, "nig_set_mlp_safety: out of host memory");
+    if (!build_critic_stream(S, A, C1, c1, C2, c2, C3, c3, host)) { free(host); return fail(NIG_ERR_INVALID, "nig_set_mlp_safety: internal record count mismatch"); }
+    NIG_TRY(upload_stream("nig_set_mlp_safety", &h->mlp_cstream, host, MLP_CSTREAM_FLOATS, stream));
     h->mlp_threshold = threshold;
     return NIG_OK;
 }
@@ -1003,19 +1052,16 @@ int nig_rollout_mlp_safe(nig_handle *h, int32_t n_steps, float *reward_out, uint
                          float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
                          float *prob_out, void *stream)
 {
-    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_safe: bad argument%s");
-    if (!launch_of(h->env)->mlp_shield) return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_mlp_safe: env shape has no MFMA actor%s");
-    if (!h->mlp_stream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_safe: no actor installed (nig_set_mlp_policy)%s");
-    if (!h->mlp_cstream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_safe: no safety critic installed (nig_set_mlp_safety)%s");
+    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_safe: bad argument");
+    if (!launch_of(h->env)->mlp_shield) return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_mlp_safe: env shape has no MFMA actor");
+    if (!h->mlp_stream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_safe: no actor installed (nig_set_mlp_policy)");
+    if (!h->mlp_cstream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_safe: no safety critic installed (nig_set_mlp_safety)");
     MlpShieldArgs q;
     memset(&q, 0, sizeof q);
-    const int rc = mlp_args(h, "nig_rollout_mlp_safe", n_steps, reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out,
-                            ld_act, act_step_stride, q.m);
-    if (rc != NIG_OK) return rc;
+    NIG_TRY(closed_loop_args(h, "nig_rollout_mlp_safe", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, q.m));
+    q.m.wstream = h->mlp_stream;
     q.cstream = h->mlp_cstream; q.prob_out = prob_out; q.threshold = h->mlp_threshold;
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned grid = (unsigned)((h->B + BLOCK / 2 - 1) / (BLOCK / 2));     // 32 envs per wave, 128 per block
-    launch_of(h->env)->mlp_shield(q, grid, st);
+    launch_of(h->env)->mlp_shield(q, mlp_grid(h), (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     h->t += (uint32_t)n_steps;
     return NIG_OK;
@@ -1025,47 +1071,44 @@ int nig_set_mlp_ensemble(nig_handle *h, int32_t n_members, int32_t hidden, const
                          const float *const *W2, const float *const *b2, const float *const *W3, const float *const *b3,
                          int32_t method, const double *weights, double weight_sum, float uncertainty_threshold, void *stream)
 {
-    if (!h) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: NULL handle%s");
-    if (n_members < 1 || n_members > NIG_MAX_ENSEMBLE) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: n_members outside 1 .. NIG_MAX_ENSEMBLE%s");
-    if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: NULL member array (W1 / b1 / W2 / b2 / W3 / b3)%s");
+    if (!h) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: NULL handle");
+    if (n_members < 1 || n_members > NIG_MAX_ENSEMBLE) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: n_members outside 1 .. NIG_MAX_ENSEMBLE");
+    if (!W1 || !b1 || !W2 || !b2 || !W3 || !b3) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: NULL member array (W1 / b1 / W2 / b2 / W3 / b3)");
     for (int k = 0; k < n_members; ++k)
-        if (!W1[k] || !b1[k] || !W2[k] || !b2[k] || !W3[k] || !b3[k]) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: NULL member array (W1 / b1 / W2 / b2 / W3 / b3 of a member)%s");
-    if (method != NIG_ENSEMBLE_AVERAGE && method != NIG_ENSEMBLE_VOTING) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: unknown method%s");
+        if (!W1[k] || !b1[k] || !W2[k] || !b2[k] || !W3[k] || !b3[k]) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: NULL member array (W1 / b1 / W2 / b2 / W3 / b3 of a member)");
+    if (method != NIG_ENSEMBLE_AVERAGE && method != NIG_ENSEMBLE_VOTING) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: unknown method");
     double w[NIG_MAX_ENSEMBLE] = {0};
     if (method == NIG_ENSEMBLE_AVERAGE) {
-        if (!weights) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: NULL weights with NIG_ENSEMBLE_AVERAGE%s");
+        if (!weights) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: NULL weights with NIG_ENSEMBLE_AVERAGE");
         for (int k = 0; k < n_members; ++k) {
-            if (!std::isfinite(weights[k])) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: non-finite entry of weights%s");
+            if (!std::isfinite(weights[k])) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: non-finite entry of weights");
             w[k] = weights[k];
         }
-        if (!std::isfinite(weight_sum)) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: non-finite weight_sum%s");
-        if (weight_sum == 0.0) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: weight_sum is zero (np.average raises)%s");
+        if (!std::isfinite(weight_sum)) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: non-finite weight_sum");
+        if (weight_sum == 0.0) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: weight_sum is zero (np.average raises)");
     }
-    if (hidden != MLP_H) return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_ensemble: hidden must be 256 (agents/networks.py default)%s");
+    if (hidden != MLP_H) return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_ensemble: hidden must be 256 (agents/networks.py default)");
     const int S = SPECS[h->env].state_dim, A = SPECS[h->env].action_dim;
     if (S % 2 != 0 || A > 16 || !launch_of(h->env)->mlp_ensemble)
-        return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_ensemble: env shape not supported (even state dim, at most 16 actions)%s");
+        return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_ensemble: env shape not supported (even state dim, at most 16 actions)");
     float *host = (float *)calloc((size_t)n_members * MLP_STREAM_FLOATS, sizeof(float));
-    if (!host) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: out of host memory%s");
+    if (!host) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: out of host memory");
     for (int k = 0; k < n_members; ++k)
         if (!build_mlp_stream(S, A, W1[k], b1[k], W2[k], b2[k], W3[k], b3[k], host + (size_t)k * MLP_STREAM_FLOATS)) {
             free(host);
-            return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: internal record count mismatch%s");
+            return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: internal record count mismatch");
         }
-    hipError_t e = hipSuccess;
     h->ens_members = 0;                                     // no ensemble while the streams are being replaced
-    if (h->ens_cap < n_members) {
+    if (h->ens_cap < n_members) {                           // too small: upload_stream allocates the new one
         if (h->ens_stream) (void)hipFree(h->ens_stream);
         h->ens_stream = nullptr; h->ens_cap = 0;
-        e = hipMalloc((void **)&h->ens_stream, (size_t)n_members * MLP_STREAM_FLOATS * sizeof(float));
-        if (e == hipSuccess) h->ens_cap = n_members;
     }
-    if (e == hipSuccess && !h->ens_w) e = hipMalloc((void **)&h->ens_w, sizeof w);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->ens_stream, host, (size_t)n_members * MLP_STREAM_FLOATS * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)stream);
+    hipError_t e = hipSuccess;                              // the weights first, on the same stream: upload_stream waits for both copies
+    if (!h->ens_w) e = hipMalloc((void **)&h->ens_w, sizeof w);
     if (e == hipSuccess) e = hipMemcpyAsync(h->ens_w, w, sizeof w, hipMemcpyHostToDevice, (hipStream_t)stream);
-    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-    free(host);
-    if (e != hipSuccess) return fail(NIG_ERR_HIP, "nig_set_mlp_ensemble: %s", hipGetErrorString(e));
+    if (e != hipSuccess) { free(host); return fail(NIG_ERR_HIP, "nig_set_mlp_ensemble: %s", hipGetErrorString(e)); }
+    NIG_TRY(upload_stream("nig_set_mlp_ensemble", &h->ens_stream, host, (size_t)n_members * MLP_STREAM_FLOATS, stream));
+    if (h->ens_cap == 0) h->ens_cap = n_members;
     h->ens_members = n_members; h->ens_method = method; h->ens_wsum = weight_sum; h->ens_threshold = uncertainty_threshold;
     return NIG_OK;
 }
@@ -1074,22 +1117,19 @@ int nig_rollout_mlp_ensemble(nig_handle *h, int32_t n_steps, float *reward_out, 
                              float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
                              float *unc_out, float *member_act_out, void *stream)
 {
-    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_ensemble: bad argument (handle, n_steps)%s");
-    if (!launch_of(h->env)->mlp_ensemble) return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_mlp_ensemble: env shape has no MFMA actor%s");
-    if (h->ens_members < 1 || !h->ens_stream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_ensemble: no ensemble installed (nig_set_mlp_ensemble)%s");
+    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_ensemble: bad argument (handle, n_steps)");
+    if (!launch_of(h->env)->mlp_ensemble) return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_mlp_ensemble: env shape has no MFMA actor");
+    if (h->ens_members < 1 || !h->ens_stream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_ensemble: no ensemble installed (nig_set_mlp_ensemble)");
     MlpEnsArgs q;
     memset(&q, 0, sizeof q);
     // member_act_out shares act_out's pitches: the same checks apply to it when act_out is absent
-    const int rc = mlp_args(h, "nig_rollout_mlp_ensemble", n_steps, reward_out, flags_out, out_stride, obs_out, obs_step_stride,
-                            act_out ? act_out : member_act_out, ld_act, act_step_stride, q.m);
-    if (rc != NIG_OK) return rc;
+    NIG_TRY(closed_loop_args(h, "nig_rollout_mlp_ensemble", n_steps,
+                             {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out ? act_out : member_act_out, ld_act, act_step_stride}, q.m));
     q.m.act_out = act_out;
     q.m.wstream = h->ens_stream;
     q.n_members = h->ens_members; q.w = h->ens_w; q.wsum = h->ens_wsum; q.kf = (float)h->ens_members; q.threshold = h->ens_threshold;
     q.unc_out = unc_out; q.member_out = member_act_out;
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned grid = (unsigned)((h->B + BLOCK / 2 - 1) / (BLOCK / 2));     // 32 envs per wave, 128 per block
-    launch_of(h->env)->mlp_ensemble(h->ens_method == NIG_ENSEMBLE_AVERAGE ? ENS_AVERAGE : ENS_VOTING, q, grid, st);
+    launch_of(h->env)->mlp_ensemble(h->ens_method == NIG_ENSEMBLE_AVERAGE ? ENS_AVERAGE : ENS_VOTING, q, mlp_grid(h), (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     h->t += (uint32_t)n_steps;
     return NIG_OK;
@@ -1120,7 +1160,7 @@ constexpr int64_t HOST_ZERO_COPY_MAX = 1024;   // lanes up to which the host-buf
 static int host_stage_ensure(nig_handle *h, const HostStage &L)
 {
     if (h->hst_pinned && h->hst_bytes >= L.bytes) return NIG_OK;
-    if (h->B > 65536) return fail(NIG_ERR_UNSUPPORTED, "host-buffer entry points are for small batches (<= 65536 lanes)%s");
+    if (h->B > 65536) return fail(NIG_ERR_UNSUPPORTED, "host-buffer entry points are for small batches (<= 65536 lanes)");
     if (h->hst_dev) { (void)hipFree(h->hst_dev); h->hst_dev = nullptr; }
     if (h->hst_pinned) { (void)hipHostFree(h->hst_pinned); h->hst_pinned = nullptr; }
     HIP_TRY(hipHostMalloc((void **)&h->hst_pinned, L.bytes, hipHostMallocDefault));
@@ -1131,11 +1171,10 @@ static int host_stage_ensure(nig_handle *h, const HostStage &L)
 
 int nig_reset_host(nig_handle *h, const double *init_noise, float *state_out, void *stream)
 {
-    if (!h || !state_out) return fail(NIG_ERR_INVALID, "nig_reset_host: NULL argument%s");
+    if (!h || !state_out) return fail(NIG_ERR_INVALID, "nig_reset_host: NULL argument");
     const nig_env_spec &sp = SPECS[h->env];
     const HostStage L = host_stage_layout(h);
-    int rc = host_stage_ensure(h, L);
-    if (rc != NIG_OK) return rc;
+    NIG_TRY(host_stage_ensure(h, L));
     hipStream_t st = (hipStream_t)stream;
     const size_t B = (size_t)h->B;
     const double *dn = nullptr;
@@ -1144,8 +1183,7 @@ int nig_reset_host(nig_handle *h, const double *init_noise, float *state_out, vo
         HIP_TRY(hipMemcpyAsync(h->hst_dev + L.off_noise, h->hst_pinned + L.off_noise, (size_t)sp.k_reset * B * 8, hipMemcpyHostToDevice, st));
         dn = (const double *)(h->hst_dev + L.off_noise);
     }
-    rc = nig_reset(h, nullptr, dn, (int64_t)B, stream);
-    if (rc != NIG_OK) return rc;
+    NIG_TRY(nig_reset(h, nullptr, dn, (int64_t)B, stream));
     // gather the rows (ld apart on the device) into the contiguous staging image, then ONE download
     hipLaunchKernelGGL(copy_rows_kernel, dim3(grid_for(h->B)), dim3(BLOCK), 0, st, (const float *)h->state, h->ld_state,
                        (float *)(h->hst_dev + L.off_state), (int64_t)B, sp.state_dim, h->B);
@@ -1173,11 +1211,10 @@ int nig_step_host64(nig_handle *h, const double *actions, const double *step_noi
 static int step_host_impl(nig_handle *h, const void *actions, bool act64, const double *step_noise, float *state_out,
                           double *reward64_out, uint32_t *flags_out, void *stream)
 {
-    if (!h || !actions || !state_out || !reward64_out || !flags_out) return fail(NIG_ERR_INVALID, "nig_step_host: NULL argument%s");
+    if (!h || !actions || !state_out || !reward64_out || !flags_out) return fail(NIG_ERR_INVALID, "nig_step_host: NULL argument");
     const nig_env_spec &sp = SPECS[h->env];
     const HostStage L = host_stage_layout(h);
-    int rc = host_stage_ensure(h, L);
-    if (rc != NIG_OK) return rc;
+    NIG_TRY(host_stage_ensure(h, L));
     hipStream_t st = (hipStream_t)stream;
     const size_t B = (size_t)h->B;
     const size_t act_bytes = (size_t)sp.action_dim * B * (act64 ? 8 : 4);
@@ -1198,10 +1235,10 @@ static int step_host_impl(nig_handle *h, const void *actions, bool act64, const 
     if (!zero_copy) HIP_TRY(hipMemcpyAsync(h->hst_dev, h->hst_pinned, up, hipMemcpyHostToDevice, st));
     if (dn) dn = (const double *)(io + L.off_noise);
     h->mirror = (float *)(io + L.off_state); h->ld_mirror = (uint32_t)B;
-    rc = act64 ? nig_step64(h, (const double *)(io + L.off_act), (int64_t)B, dn, nullptr, (int64_t)B, nullptr,
-                            (double *)(io + L.off_rew), (uint32_t *)(io + L.off_flags), nullptr, 0, stream)
-               : nig_step(h, (const float *)(io + L.off_act), (int64_t)B, dn, nullptr, (int64_t)B, nullptr,
-                          (double *)(io + L.off_rew), (uint32_t *)(io + L.off_flags), nullptr, 0, stream);
+    const int rc = act64 ? nig_step64(h, (const double *)(io + L.off_act), (int64_t)B, dn, nullptr, (int64_t)B, nullptr,
+                                      (double *)(io + L.off_rew), (uint32_t *)(io + L.off_flags), nullptr, 0, stream)
+                         : nig_step(h, (const float *)(io + L.off_act), (int64_t)B, dn, nullptr, (int64_t)B, nullptr,
+                                    (double *)(io + L.off_rew), (uint32_t *)(io + L.off_flags), nullptr, 0, stream);
     h->mirror = nullptr;
     if (rc != NIG_OK) return rc;
     // (the state rows land next to reward64 and flags -- one download for everything the call returns -- written by the step
@@ -1217,15 +1254,15 @@ static int step_host_impl(nig_handle *h, const void *actions, bool act64, const 
 int nig_plan_create(nig_handle *h, int32_t n_steps, const float *action_ring, int64_t ld_act, int64_t slot_stride,
                     int32_t ring_len, float *reward_out, uint32_t *flags_out, int64_t out_stride, nig_plan **out)
 {
-    if (!out) return fail(NIG_ERR_INVALID, "nig_plan_create: out is NULL%s");
+    if (!out) return fail(NIG_ERR_INVALID, "nig_plan_create: out is NULL");
     *out = nullptr;
     if (!h || !action_ring || n_steps <= 0 || ring_len <= 0 || ld_act < h->B || ld_act > NIG_MAX_PITCH)
-        return fail(NIG_ERR_INVALID, "nig_plan_create: bad argument%s");
+        return fail(NIG_ERR_INVALID, "nig_plan_create: bad argument");
     if (slot_stride < (int64_t)SPECS[h->env].action_dim * ld_act)
-        return fail(NIG_ERR_INVALID, "nig_plan_create: slot_stride smaller than one [A][ld_act] slot%s");
-    if (out_stride != 0 && out_stride < h->B) return fail(NIG_ERR_INVALID, "nig_plan_create: out_stride < batch%s");
+        return fail(NIG_ERR_INVALID, "nig_plan_create: slot_stride smaller than one [A][ld_act] slot");
+    if (out_stride != 0 && out_stride < h->B) return fail(NIG_ERR_INVALID, "nig_plan_create: out_stride < batch");
     nig_plan *p = new (std::nothrow) nig_plan();
-    if (!p) return fail(NIG_ERR_INVALID, "nig_plan_create: out of host memory%s");
+    if (!p) return fail(NIG_ERR_INVALID, "nig_plan_create: out of host memory");
     p->h = h; p->n_steps = n_steps; p->graph = nullptr; p->exec = nullptr;
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t cs = nullptr;
@@ -1257,7 +1294,7 @@ int nig_plan_create(nig_handle *h, int32_t n_steps, const float *action_ring, in
 
 int nig_plan_launch(nig_plan *p, void *stream)
 {
-    if (!p) return fail(NIG_ERR_INVALID, "nig_plan_launch: NULL plan%s");
+    if (!p) return fail(NIG_ERR_INVALID, "nig_plan_launch: NULL plan");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(set_u32_kernel, dim3(1), dim3(1), 0, st, p->h->t_dev, p->h->t);
     HIP_TRY(hipGraphLaunch(p->exec, st));
@@ -1276,13 +1313,13 @@ int nig_plan_destroy(nig_plan *p)
 
 // ---- mixed batch -------------------------------------------------------------------------------
 struct nig_mixed {
-    int n;
-    int device;
-    nig_handle *seg[NIG_MIXED_MAX_SEGMENTS];
-    int64_t off[NIG_MIXED_MAX_SEGMENTS];
-    int64_t ld, lanes;
-    int s_max, a_max;
-    float *state;              // [s_max][ld], owned
+    int n = 0;
+    int device = 0;
+    nig_handle *seg[NIG_MIXED_MAX_SEGMENTS] = {};
+    int64_t off[NIG_MIXED_MAX_SEGMENTS] = {};
+    int64_t ld = 0, lanes = 0;
+    int s_max = 0, a_max = 0;
+    float *state = nullptr;    // [s_max][ld], owned
 };
 
 // relative cost of one env-step (fused rollout, measured per-env rates): launch order = most expensive first.  (Round 4,
@@ -1308,33 +1345,33 @@ int nig_rollout_mixed_obs(nig_handle *const *handles, const int64_t *lane_offset
                           float *obs_out, int64_t ld_obs, int64_t obs_step_stride, void *stream)
 {
     if (!handles || !lane_offsets || n_handles <= 0 || n_handles > NIG_MIXED_MAX_SEGMENTS)
-        return fail(NIG_ERR_INVALID, "nig_rollout_mixed: 1..12 handles%s");
-    if (!action_ring || n_steps <= 0 || ring_len <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mixed: bad argument%s");
-    if ((reward_out == nullptr) != (flags_out == nullptr))
-        return fail(NIG_ERR_INVALID, "nig_rollout_mixed: reward_out and flags_out go together (both or neither)%s");
+        return fail(NIG_ERR_INVALID, "nig_rollout_mixed: 1..12 handles");
+    const char *const fn = "nig_rollout_mixed";
+    if (!action_ring || n_steps <= 0 || ring_len <= 0) return refuse(fn, "bad argument");
+    NIG_TRY(check_reward_flags(fn, reward_out, flags_out));
     if (ld_act <= 0 || ld_act > NIG_MAX_PITCH || slot_stride > 0xffffffffLL)
-        return fail(NIG_ERR_INVALID, "nig_rollout_mixed: ld_act outside [1, 2^26] or slot_stride >= 2^32%s");
-    if (out_stride != 0 && out_stride > NIG_MAX_PITCH) return fail(NIG_ERR_INVALID, "nig_rollout_mixed: out_stride > 2^26%s");
-    if ((int64_t)n_steps * out_stride > 0xffffffffLL) return fail(NIG_ERR_INVALID, "nig_rollout_mixed: n_steps*out_stride >= 2^32%s");
-    if (obs_out && !reward_out) return fail(NIG_ERR_INVALID, "nig_rollout_mixed: an observation trajectory needs reward_out and flags_out too%s");
-    if (obs_out && (ld_obs <= 0 || ld_obs > NIG_MAX_PITCH)) return fail(NIG_ERR_INVALID, "nig_rollout_mixed: ld_obs outside [1, 2^26]%s");
+        return fail(NIG_ERR_INVALID, "nig_rollout_mixed: ld_act outside [1, 2^26] or slot_stride >= 2^32");
+    if (out_stride != 0 && out_stride > NIG_MAX_PITCH) return fail(NIG_ERR_INVALID, "nig_rollout_mixed: out_stride > 2^26");
+    NIG_TRY(check_out_span(fn, n_steps, out_stride));      // (no lower bound on out_stride here: the segments' fit, below)
+    if (obs_out && !reward_out) return fail(NIG_ERR_INVALID, "nig_rollout_mixed: an observation trajectory needs reward_out and flags_out too");
+    if (obs_out && (ld_obs <= 0 || ld_obs > NIG_MAX_PITCH)) return fail(NIG_ERR_INVALID, "nig_rollout_mixed: ld_obs outside [1, 2^26]");
     int order[NIG_MIXED_MAX_SEGMENTS];
     int a_max = 0, s_max = 0;
     for (int k = 0; k < n_handles; ++k) {
         const nig_handle *h = handles[k];
-        if (!h) return fail(NIG_ERR_INVALID, "nig_rollout_mixed: NULL handle%s");
-        if (h->device != handles[0]->device) return fail(NIG_ERR_INVALID, "nig_rollout_mixed: handles on different devices%s");
+        if (!h) return fail(NIG_ERR_INVALID, "nig_rollout_mixed: NULL handle");
+        if (h->device != handles[0]->device) return fail(NIG_ERR_INVALID, "nig_rollout_mixed: handles on different devices");
         if (lane_offsets[k] < 0 || lane_offsets[k] + h->B > ld_act || (out_stride != 0 && lane_offsets[k] + h->B > out_stride))
-            return fail(NIG_ERR_INVALID, "nig_rollout_mixed: a segment does not fit the row pitch%s");
-        if ((int64_t)h->t + n_steps > 0xffffffffLL) return fail(NIG_ERR_INVALID, "nig_rollout_mixed: launch counter would wrap%s");
+            return fail(NIG_ERR_INVALID, "nig_rollout_mixed: a segment does not fit the row pitch");
+        NIG_TRY(check_counter(h, fn, n_steps));
         if (SPECS[h->env].action_dim > a_max) a_max = SPECS[h->env].action_dim;
         if (SPECS[h->env].state_dim > s_max) s_max = SPECS[h->env].state_dim;
-        if (obs_out && lane_offsets[k] + h->B > ld_obs) return fail(NIG_ERR_INVALID, "nig_rollout_mixed: a segment does not fit ld_obs%s");
+        if (obs_out && lane_offsets[k] + h->B > ld_obs) return fail(NIG_ERR_INVALID, "nig_rollout_mixed: a segment does not fit ld_obs");
         order[k] = k;
     }
     if (obs_out && obs_step_stride != 0 && obs_step_stride < (int64_t)s_max * ld_obs)
-        return fail(NIG_ERR_INVALID, "nig_rollout_mixed: obs_step_stride smaller than one [S_max][ld_obs] step%s");
-    if (slot_stride < (int64_t)a_max * ld_act) return fail(NIG_ERR_INVALID, "nig_rollout_mixed: slot_stride smaller than one [A_max][ld_act] slot%s");
+        return fail(NIG_ERR_INVALID, "nig_rollout_mixed: obs_step_stride smaller than one [S_max][ld_obs] step");
+    if (slot_stride < (int64_t)a_max * ld_act) return fail(NIG_ERR_INVALID, "nig_rollout_mixed: slot_stride smaller than one [A_max][ld_act] slot");
     for (int i = 1; i < n_handles; ++i)           // insertion sort: most expensive env first, ties in segment order
         for (int j = i; j > 0 && env_cost(handles[order[j]]->env) > env_cost(handles[order[j - 1]]->env); --j) {
             const int tmp = order[j]; order[j] = order[j - 1]; order[j - 1] = tmp;
@@ -1342,19 +1379,12 @@ int nig_rollout_mixed_obs(nig_handle *const *handles, const int64_t *lane_offset
     MixedArgs m;
     memset(&m, 0, sizeof m);
     m.n_seg = n_handles;
+    const RolloutSpec c = {n_steps, action_ring, ld_act, slot_stride, ring_len, nullptr, 0, nullptr, 0, 0, reward_out, flags_out, out_stride,
+                           obs_out, obs_out ? ld_obs : 0, obs_out ? obs_step_stride : 0, false};
     uint32_t blocks = 0;
     for (int i = 0; i < n_handles; ++i) {
-        nig_handle *h = handles[order[i]];
-        const int64_t o = lane_offsets[order[i]];
-        RolloutArgs &q = m.seg[i];
-        q.s = base_step_args(h);
-        q.s.actions = action_ring + o; q.s.ld_act = (uint32_t)ld_act;
-        q.s.reward = reward_out ? reward_out + o : nullptr;
-        q.s.flags = flags_out ? flags_out + o : nullptr;
-        q.s.t_ptr = nullptr; q.s.t_off = h->t;
-        q.n_steps = n_steps; q.it0 = 0; q.ring_len = ring_len; q.slot_stride = (uint32_t)slot_stride;
-        q.out_stride = (uint32_t)out_stride; q.block0 = 0;
-        if (obs_out) { q.obs_out = obs_out + o; q.ld_obs_out = (uint32_t)ld_obs; q.obs_step_stride = (uint64_t)obs_step_stride; q.obs_aos = 0; }
+        const nig_handle *h = handles[order[i]];
+        m.seg[i] = rollout_args(h, c, lane_offsets[order[i]]);
         blocks += grid_for(h->B);
         m.blk_end[i] = blocks;
         m.env[i] = h->env;
@@ -1369,19 +1399,18 @@ int nig_rollout_mixed_obs(nig_handle *const *handles, const int64_t *lane_offset
 int nig_create_mixed(int32_t n_segments, const int32_t *env_ids, const int64_t *counts, int device, uint64_t seed,
                      uint64_t env_index0, uint32_t flags, nig_mixed **out)
 {
-    if (!out) return fail(NIG_ERR_INVALID, "nig_create_mixed: out is NULL%s");
+    if (!out) return fail(NIG_ERR_INVALID, "nig_create_mixed: out is NULL");
     *out = nullptr;
     if (!env_ids || !counts || n_segments <= 0 || n_segments > NIG_MIXED_MAX_SEGMENTS)
-        return fail(NIG_ERR_INVALID, "nig_create_mixed: 1..12 segments%s");
+        return fail(NIG_ERR_INVALID, "nig_create_mixed: 1..12 segments");
     nig_mixed *m = new (std::nothrow) nig_mixed();
-    if (!m) return fail(NIG_ERR_INVALID, "nig_create_mixed: out of host memory%s");
-    memset(m, 0, sizeof *m);
+    if (!m) return fail(NIG_ERR_INVALID, "nig_create_mixed: out of host memory");
     m->n = n_segments; m->device = device;
     int64_t off = 0;
     for (int k = 0; k < n_segments; ++k) {
         if (env_ids[k] < 0 || env_ids[k] >= NIG_NUM_ENVS || counts[k] <= 0 || counts[k] > NIG_MAX_BATCH) {
             delete m;
-            return fail(NIG_ERR_INVALID, "nig_create_mixed: bad env id or lane count%s");
+            return fail(NIG_ERR_INVALID, "nig_create_mixed: bad env id or lane count");
         }
         m->off[k] = off;
         off += align_up(counts[k], BLOCK);            // every segment starts on a block boundary
@@ -1390,7 +1419,7 @@ int nig_create_mixed(int32_t n_segments, const int32_t *env_ids, const int64_t *
         if (SPECS[env_ids[k]].action_dim > m->a_max) m->a_max = SPECS[env_ids[k]].action_dim;
     }
     m->ld = off;
-    if (m->ld > NIG_MAX_PITCH) { delete m; return fail(NIG_ERR_INVALID, "nig_create_mixed: more than 2^26 columns%s"); }
+    if (m->ld > NIG_MAX_PITCH) { delete m; return fail(NIG_ERR_INVALID, "nig_create_mixed: more than 2^26 columns"); }
     int rc = NIG_OK;
     for (int k = 0; k < n_segments && rc == NIG_OK; ++k)
         rc = nig_create(env_ids[k], counts[k], device, seed, env_index0 + (uint64_t)m->off[k], 0, 0.0, flags, nullptr, &m->seg[k]);
@@ -1417,7 +1446,7 @@ int nig_mixed_destroy(nig_mixed *m)
 
 int nig_mixed_get_info(const nig_mixed *m, nig_mixed_info *out)
 {
-    if (!m || !out) return fail(NIG_ERR_INVALID, "nig_mixed_get_info: NULL argument%s");
+    if (!m || !out) return fail(NIG_ERR_INVALID, "nig_mixed_get_info: NULL argument");
     memset(out, 0, sizeof *out);
     out->n_segments = m->n; out->state_dim_max = m->s_max; out->action_dim_max = m->a_max;
     out->lanes = m->lanes; out->ld = m->ld;
@@ -1431,32 +1460,29 @@ nig_handle *nig_mixed_segment(const nig_mixed *m, int32_t k) { return (m && k >=
 
 int nig_mixed_reset(nig_mixed *m, void *stream)
 {
-    if (!m) return fail(NIG_ERR_INVALID, "nig_mixed_reset: NULL handle%s");
+    if (!m) return fail(NIG_ERR_INVALID, "nig_mixed_reset: NULL handle");
     for (int k = 0; k < m->n; ++k) {
-        const int rc = nig_reset(m->seg[k], nullptr, nullptr, 0, stream);
-        if (rc != NIG_OK) return rc;
+        NIG_TRY(nig_reset(m->seg[k], nullptr, nullptr, 0, stream));
     }
     return NIG_OK;
 }
 
 int nig_mixed_fill_actions(nig_mixed *m, uint32_t t, float *actions, void *stream)
 {
-    if (!m || !actions) return fail(NIG_ERR_INVALID, "nig_mixed_fill_actions: NULL argument%s");
+    if (!m || !actions) return fail(NIG_ERR_INVALID, "nig_mixed_fill_actions: NULL argument");
     for (int k = 0; k < m->n; ++k) {
-        const int rc = nig_fill_actions(m->seg[k], t, actions + m->off[k], m->ld, stream);
-        if (rc != NIG_OK) return rc;
+        NIG_TRY(nig_fill_actions(m->seg[k], t, actions + m->off[k], m->ld, stream));
     }
     return NIG_OK;
 }
 
 int nig_mixed_step(nig_mixed *m, const float *actions, float *reward_out, uint32_t *flags_out, void *stream)
 {
-    if (!m || !actions) return fail(NIG_ERR_INVALID, "nig_mixed_step: NULL argument%s");
+    if (!m || !actions) return fail(NIG_ERR_INVALID, "nig_mixed_step: NULL argument");
     for (int k = 0; k < m->n; ++k) {              // one step kernel per segment (each its own env type), same stream
         const int64_t o = m->off[k];
-        const int rc = nig_step(m->seg[k], actions + o, m->ld, nullptr, nullptr, 0, reward_out ? reward_out + o : nullptr, nullptr,
-                                flags_out ? flags_out + o : nullptr, nullptr, 0, stream);
-        if (rc != NIG_OK) return rc;
+        NIG_TRY(nig_step(m->seg[k], actions + o, m->ld, nullptr, nullptr, 0, reward_out ? reward_out + o : nullptr, nullptr,
+                                flags_out ? flags_out + o : nullptr, nullptr, 0, stream));
     }
     return NIG_OK;
 }
@@ -1464,7 +1490,7 @@ int nig_mixed_step(nig_mixed *m, const float *actions, float *reward_out, uint32
 int nig_mixed_rollout(nig_mixed *m, int32_t n_steps, const float *action_ring, int64_t slot_stride, int32_t ring_len,
                       float *reward_out, uint32_t *flags_out, int64_t out_stride, void *stream)
 {
-    if (!m) return fail(NIG_ERR_INVALID, "nig_mixed_rollout: NULL handle%s");
+    if (!m) return fail(NIG_ERR_INVALID, "nig_mixed_rollout: NULL handle");
     return nig_rollout_mixed(m->seg, m->off, m->n, n_steps, action_ring, m->ld, slot_stride, ring_len, reward_out, flags_out,
                              out_stride, stream);
 }
@@ -1473,7 +1499,7 @@ int nig_mixed_rollout_obs(nig_mixed *m, int32_t n_steps, const float *action_rin
                           float *reward_out, uint32_t *flags_out, int64_t out_stride, float *obs_out, int64_t obs_step_stride,
                           void *stream)
 {
-    if (!m) return fail(NIG_ERR_INVALID, "nig_mixed_rollout_obs: NULL handle%s");
+    if (!m) return fail(NIG_ERR_INVALID, "nig_mixed_rollout_obs: NULL handle");
     return nig_rollout_mixed_obs(m->seg, m->off, m->n, n_steps, action_ring, m->ld, slot_stride, ring_len, reward_out, flags_out,
                                  out_stride, obs_out, m->ld, obs_step_stride, stream);
 }
@@ -1504,28 +1530,27 @@ static bool rccl_resolve(nccl_allgather_fn *ag, nccl_count_fn *cnt)
 int nig_reduce_metrics(nig_handle *const *handles, int32_t n_handles, void *comm, double *scratch, int64_t scratch_doubles,
                        double *out, void *stream)
 {
-    if (!handles || n_handles <= 0 || !scratch || !out) return fail(NIG_ERR_INVALID, "nig_reduce_metrics: NULL argument%s");
+    if (!handles || n_handles <= 0 || !scratch || !out) return fail(NIG_ERR_INVALID, "nig_reduce_metrics: NULL argument");
     int world = 1;
     nccl_allgather_fn allgather = nullptr;
     nccl_count_fn count = nullptr;
     if (comm) {
-        if (!rccl_resolve(&allgather, &count)) return fail(NIG_ERR_UNSUPPORTED, "nig_reduce_metrics: RCCL (librccl.so) not found in this process%s");
-        if (count(comm, &world) != 0 || world <= 0) return fail(NIG_ERR_INVALID, "nig_reduce_metrics: ncclCommCount failed%s");
+        if (!rccl_resolve(&allgather, &count)) return fail(NIG_ERR_UNSUPPORTED, "nig_reduce_metrics: RCCL (librccl.so) not found in this process");
+        if (count(comm, &world) != 0 || world <= 0) return fail(NIG_ERR_INVALID, "nig_reduce_metrics: ncclCommCount failed");
     }
     // scratch: [n_handles][ROWS] local partials | [ROWS] this rank's partial | [world][ROWS] gathered
     const int64_t need = ((int64_t)n_handles + 1 + world) * NIG_T_ROWS;
-    if (scratch_doubles < need) return fail(NIG_ERR_INVALID, "nig_reduce_metrics: scratch smaller than (n_handles + 1 + ranks) * NIG_T_ROWS doubles%s");
+    if (scratch_doubles < need) return fail(NIG_ERR_INVALID, "nig_reduce_metrics: scratch smaller than (n_handles + 1 + ranks) * NIG_T_ROWS doubles");
     hipStream_t st = (hipStream_t)stream;
     double *local = scratch, *mine = scratch + (int64_t)n_handles * NIG_T_ROWS, *all = mine + NIG_T_ROWS;
     for (int k = 0; k < n_handles; ++k) {
-        const int rc = nig_reduce_tally(handles[k], local + (int64_t)k * NIG_T_ROWS, stream);
-        if (rc != NIG_OK) return rc;
+        NIG_TRY(nig_reduce_tally(handles[k], local + (int64_t)k * NIG_T_ROWS, stream));
     }
     hipLaunchKernelGGL(combine_partials_kernel, dim3(1), dim3(64), 0, st, (const double *)local, n_handles, mine);
     if (comm) {
         // ncclAllGather (RCCL; over xGMI between the GPUs of a node): NIG_T_ROWS doubles per rank, rank order
         if (allgather(mine, all, (size_t)NIG_T_ROWS, /*ncclDouble*/ 8, comm, st) != 0)
-            return fail(NIG_ERR_HIP, "nig_reduce_metrics: ncclAllGather failed%s");
+            return fail(NIG_ERR_HIP, "nig_reduce_metrics: ncclAllGather failed");
         hipLaunchKernelGGL(combine_partials_kernel, dim3(1), dim3(64), 0, st, (const double *)all, world, out);
     } else {
         hipLaunchKernelGGL(combine_partials_kernel, dim3(1), dim3(64), 0, st, (const double *)mine, 1, out);
@@ -1536,7 +1561,7 @@ int nig_reduce_metrics(nig_handle *const *handles, int32_t n_handles, void *comm
 
 int nig_fill_actions(nig_handle *h, uint32_t t, float *actions, int64_t ld_act, void *stream)
 {
-    if (!h || !actions || ld_act < h->B) return fail(NIG_ERR_INVALID, "nig_fill_actions: bad argument%s");
+    if (!h || !actions || ld_act < h->B) return fail(NIG_ERR_INVALID, "nig_fill_actions: bad argument");
     hipStream_t st = (hipStream_t)stream;
     const uint32_t lo = (uint32_t)h->seed, hi = (uint32_t)(h->seed >> 32);
     launch_of(h->env)->fill(actions, ld_act, h->B, h->env0, lo, hi, t, grid_for(h->B), st);
@@ -1546,17 +1571,16 @@ int nig_fill_actions(nig_handle *h, uint32_t t, float *actions, int64_t ld_act, 
 
 int nig_set_state(nig_handle *h, const float *state, int64_t ld, const uint32_t *ctr, void *stream)
 {
-    if (!h) return fail(NIG_ERR_INVALID, "nig_set_state: NULL handle%s");
+    if (!h) return fail(NIG_ERR_INVALID, "nig_set_state: NULL handle");
     hipStream_t st = (hipStream_t)stream;
-    const nig_layout &L = h->lay;
     if (state) {
-        if (ld < h->B) return fail(NIG_ERR_INVALID, "nig_set_state: ld < batch%s");
+        if (ld < h->B) return fail(NIG_ERR_INVALID, "nig_set_state: ld < batch");
         hipLaunchKernelGGL(copy_rows_kernel, dim3(grid_for(h->B)), dim3(BLOCK), 0, st, state, ld,
                            h->state, h->ld_state, SPECS[h->env].state_dim, h->B);
         HIP_TRY(hipGetLastError());
     }
     if (ctr) {
-        HIP_TRY(hipMemcpyAsync(h->ws + L.off_ctr, ctr, (size_t)h->B * 4, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ws_ctr(h), ctr, (size_t)h->B * 4, hipMemcpyDeviceToDevice, st));
         h->may_hold_done = true;                  // the caller's counter words may mark lanes done
     }
     return NIG_OK;
@@ -1564,22 +1588,21 @@ int nig_set_state(nig_handle *h, const float *state, int64_t ld, const uint32_t 
 
 int nig_get_state(nig_handle *h, float *state, int64_t ld, uint32_t *ctr, void *stream)
 {
-    if (!h) return fail(NIG_ERR_INVALID, "nig_get_state: NULL handle%s");
+    if (!h) return fail(NIG_ERR_INVALID, "nig_get_state: NULL handle");
     hipStream_t st = (hipStream_t)stream;
-    const nig_layout &L = h->lay;
     if (state) {
-        if (ld < h->B) return fail(NIG_ERR_INVALID, "nig_get_state: ld < batch%s");
+        if (ld < h->B) return fail(NIG_ERR_INVALID, "nig_get_state: ld < batch");
         hipLaunchKernelGGL(copy_rows_kernel, dim3(grid_for(h->B)), dim3(BLOCK), 0, st,
                            (const float *)h->state, h->ld_state, state, ld, SPECS[h->env].state_dim, h->B);
         HIP_TRY(hipGetLastError());
     }
-    if (ctr) HIP_TRY(hipMemcpyAsync(ctr, h->ws + L.off_ctr, (size_t)h->B * 4, hipMemcpyDeviceToDevice, st));
+    if (ctr) HIP_TRY(hipMemcpyAsync(ctr, ws_ctr(h), (size_t)h->B * 4, hipMemcpyDeviceToDevice, st));
     return NIG_OK;
 }
 
 int nig_get_safety_metrics(nig_handle *h, const uint32_t *flags, int32_t *out, int64_t ld_out, void *stream)
 {
-    if (!h || !flags || !out || ld_out < h->B) return fail(NIG_ERR_INVALID, "nig_get_safety_metrics: bad argument%s");
+    if (!h || !flags || !out || ld_out < h->B) return fail(NIG_ERR_INVALID, "nig_get_safety_metrics: bad argument");
     hipLaunchKernelGGL(safety_metrics_kernel, dim3(grid_for(h->B)), dim3(BLOCK), 0, (hipStream_t)stream, flags, out, ld_out, h->B,
                        enabled_constraints(h));
     HIP_TRY(hipGetLastError());
@@ -1588,13 +1611,12 @@ int nig_get_safety_metrics(nig_handle *h, const uint32_t *flags, int32_t *out, i
 
 int nig_reduce_tally(nig_handle *h, double *partial_out, void *stream)
 {
-    if (!h || !partial_out) return fail(NIG_ERR_INVALID, "nig_reduce_tally: NULL argument%s");
-    if (h->lay.off_tally < 0) return fail(NIG_ERR_INVALID, "nig_reduce_tally: handle created without NIG_F_TALLY%s");
+    if (!h || !partial_out) return fail(NIG_ERR_INVALID, "nig_reduce_tally: NULL argument");
+    if (h->lay.off_tally < 0) return fail(NIG_ERR_INVALID, "nig_reduce_tally: handle created without NIG_F_TALLY");
     hipStream_t st = (hipStream_t)stream;
     int nblk = (int)((h->B + BLOCK - 1) / BLOCK);
     if (nblk > REDUCE_BLOCKS) nblk = REDUCE_BLOCKS;
-    hipLaunchKernelGGL(reduce_tally_stage1, dim3(nblk), dim3(BLOCK), 0, st, (const double *)(h->ws + h->lay.off_tally),
-                       h->lay.ld, h->B, h->scratch);
+    hipLaunchKernelGGL(reduce_tally_stage1, dim3(nblk), dim3(BLOCK), 0, st, (const double *)ws_tally(h), h->lay.ld, h->B, h->scratch);
     hipLaunchKernelGGL(reduce_tally_stage2, dim3(1), dim3(REDUCE_BLOCKS), 0, st, (const double *)h->scratch, nblk, partial_out);
     HIP_TRY(hipGetLastError());
     return NIG_OK;

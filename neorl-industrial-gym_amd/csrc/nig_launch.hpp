@@ -105,12 +105,11 @@ template <class Env, bool PAIRED, bool NOISE, bool SAMPLED, int OUT>
 static void launch_rollout_segment(const Segment &s, const RolloutArgs &r, hipStream_t st)
 {
     const dim3 grid(s.grid);
-    // (One-wave and three-wave: no `else` after the sampled launch, so a sampled_*.hip unit instantiates the ring-fed kernel
-    // beside its twin, unreachable there -- its code object has always held those copies and is required not to move by a
-    // symbol: profiles/isa_diff.py.)
+    // (Every form: `if constexpr (SAMPLED) ... else ...`, so a sampled_*.hip unit instantiates the twins alone and each kernel
+    // symbol of the library lives in exactly one code object.)
     auto one_wave = [&](auto FULL) {
-        if constexpr (SAMPLED) { hipLaunchKernelGGL((rollout_sampled_kernel<Env, OUT, PAIRED, FULL()>), grid, dim3(BLOCK), 0, st, r); return; }
-        hipLaunchKernelGGL((rollout_kernel<Env, OUT, PAIRED, FULL(), NOISE>), grid, dim3(BLOCK), 0, st, r);
+        if constexpr (SAMPLED) hipLaunchKernelGGL((rollout_sampled_kernel<Env, OUT, PAIRED, FULL()>), grid, dim3(BLOCK), 0, st, r);
+        else hipLaunchKernelGGL((rollout_kernel<Env, OUT, PAIRED, FULL(), NOISE>), grid, dim3(BLOCK), 0, st, r);
     };
     auto wide = [&](auto BLK) {
         if constexpr (SAMPLED) hipLaunchKernelGGL((rollout_sampled_wide_kernel<Env, OUT, BLK()>), grid, dim3(BLK()), 0, st, r);

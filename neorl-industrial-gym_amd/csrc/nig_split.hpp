@@ -96,8 +96,8 @@ __global__ void __launch_bounds__(192 * NP, 1) split_sampled_kernel(const Rollou
 template <class Env, int NP, int OUT, bool NOISE = false, bool SAMPLED = false>
 static void launch_split_blocks(const RolloutArgs &q, unsigned grid, hipStream_t st)
 {
-    if constexpr (SAMPLED) { hipLaunchKernelGGL((split_sampled_kernel<Env, OUT, NP>), dim3(grid), dim3(192 * NP), 0, st, q); return; }
-    hipLaunchKernelGGL((split_rollout_kernel<Env, OUT, NP, NOISE>), dim3(grid), dim3(192 * NP), 0, st, q);   // (no `else`: nig_launch.hpp)
+    if constexpr (SAMPLED) hipLaunchKernelGGL((split_sampled_kernel<Env, OUT, NP>), dim3(grid), dim3(192 * NP), 0, st, q);
+    else hipLaunchKernelGGL((split_rollout_kernel<Env, OUT, NP, NOISE>), dim3(grid), dim3(192 * NP), 0, st, q);
 }
 
 }  // namespace nig

@@ -1019,6 +1019,7 @@ class RefusalRig:
             r.env.set_policy(ni.behaviour_policy(NAME[key], "medium"))
             r.env.set_mlp_policy(_actor(S, A, 11))
             r.env.set_mlp_safety(_critic(S, A, 12), 0.5)
+            r.env.set_mlp_ensemble([_actor(S, A, 13), _actor(S, A, 14)], weights=[0.5, 0.5], method="mean")
         a = Arena("cuda")
         nk = max(K, KR, 1)
         self.ring = a.add("action_ring", "f32", Layout(R, A * ld, A, ld, B), role="in")
@@ -1142,10 +1143,10 @@ def _refusal_rows(key):
             L, h, st, B, T, R, S, A, ld = base(g)
             q = dict(out=ld, obs=P(g.obs), ostep=ceil4(S * B), lda=ld, astep=A * ld)
             q.update({k: f(g, v) for k, f in kw.items()})
-            extra = (P(g.pr),) if name == "nig_rollout_mlp_safe" else ()
+            extra = {"nig_rollout_mlp_safe": (P(g.pr),), "nig_rollout_mlp_ensemble": (P(g.pr), None)}.get(name, ())
             return getattr(L, name)(h, T, P(g.rew), P(g.fl), q["out"], q["obs"], q["ostep"], P(g.act), q["lda"], q["astep"], *extra, st)
         row(f"{name} {what}", call, good, bad, text)
-    for name in ("nig_rollout_policy", "nig_rollout_mlp", "nig_rollout_mlp_safe"):
+    for name in ("nig_rollout_policy", "nig_rollout_mlp", "nig_rollout_mlp_safe", "nig_rollout_mlp_ensemble"):
         closed(name, "out_stride", name + ": out_stride outside", "B", "B-1", out=val)
         closed(name, "obs_step_stride", name + ": obs_out needs 16-byte alignment", "S*B", "S*B-4", ostep=val)
         closed(name, "obs_step_stride == 0 (no overwrite form)", name + ": obs_out needs 16-byte alignment", "S*B", 0, ostep=val)
