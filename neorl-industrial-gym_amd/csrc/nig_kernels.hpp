@@ -94,6 +94,7 @@ constexpr uint32_t HF_MAY_HOLD_DONE = 0x10000u;
 constexpr uint32_t HF_DIAG_RING_FAULT = 0x20000u;
 }  // namespace nig
 #include "nig_ring.hpp"        // LDS ring counters of the cooperating-wave kernels (used from rollout_body's RING form on)
+#include "nig_episode.hpp"     // the episode bookkeeping every body below shares: counter / flag words, return, tallies, a launch's closing store
 namespace nig {
 
 // IndustrialEnv.step for one lane, entirely in registers (base.py:157-213): action clip, constraint
@@ -252,115 +253,6 @@ __device__ __forceinline__ void draw_one(const RngKey &k, NZ (&n)[Env::KS > 0 ? 
     if constexpr (Env::KS > 0) Env::draw_step(k, n);
 }
 
-// Stage the 12 KiB probit table (normal transform of the generator) in LDS.  Every thread of the block
-// must pass through here before any early exit.
-#define NIG_STAGE_PROBIT(tab)                                                         \
-    __shared__ float4 tab[768];                                                       \
-    for (int i_ = (int)threadIdx.x; i_ < 768; i_ += BLOCK) tab[i_] = NIG_PROBIT[i_];  \
-    __syncthreads()
-
-// Episode bookkeeping of one finished episode (utils.py:120-125), lane-private column of the tally.
-// All 11 rows are loaded before any is stored: one memory round trip instead of eleven dependent ones.
-__device__ __forceinline__ void flush_tally(double *T, uint32_t ld, double ret, int step, uint32_t viol_ep, int ncrit, int n_en)
-{
-    double v[NIG_T_ROWS];
-#pragma unroll
-    for (int r = 0; r < NIG_T_ROWS; ++r) v[r] = T[(size_t)r * ld];
-    const double len = (double)step;
-    v[NIG_T_EPISODES] += 1.0;
-    v[NIG_T_RET_SUM] += ret;
-    v[NIG_T_RET_SQ] += ret * ret;
-    v[NIG_T_RET_MIN] = fmin(v[NIG_T_RET_MIN], ret);
-    v[NIG_T_RET_MAX] = fmax(v[NIG_T_RET_MAX], ret);
-    v[NIG_T_LEN_SUM] += len;
-    v[NIG_T_LEN_SQ] += len * len;
-    v[NIG_T_VIOL] += (double)viol_ep;
-    v[NIG_T_CRIT] += (double)ncrit;            // a critical step always ends the episode
-    v[NIG_T_SHUTDOWN] += (ncrit > 0) ? 1.0 : 0.0;
-    v[NIG_T_SUCCESS] += (ret > 0.0) ? 1.0 : 0.0;
-    v[NIG_T_SATISFIED] += (double)(n_en * step - (int)viol_ep);   // sum over the episode's steps of constraints_satisfied
-    v[NIG_T_CONSTRAINTS] += (double)(n_en * step);
-#pragma unroll
-    for (int r = 0; r < NIG_T_ROWS; ++r) T[(size_t)r * ld] = v[r];
-}
-
-// The same bookkeeping as no-return float64 atomics into the lane's own column (global_atomic_add / min / max_f64,
-// executed at the memory side): nothing is loaded, nothing is waited for.  The step kernel used flush_tally, i.e. 13
-// loads, a wait and 13 stores behind the step of every finishing lane -- a third dependent memory round trip on the
-// critical path of a launch that is latency-bound at the headline batch (profiles/r03/step_api_probe.py: the tally cost
-// 0.8 us of a 5.1 us launch).  Each row is one IEEE operation on the same operands as in flush_tally, and a lane's column
-// is touched by that lane only (a kernel boundary orders consecutive steps), so the rows hold the same bits.
-__device__ __forceinline__ void flush_tally_atomic(double *T, uint32_t ld, double ret, int step, uint32_t viol_ep, int ncrit, int n_en)
-{
-    typedef __attribute__((address_space(1))) double gdouble;
-    auto add = [&](int r, double x) { (void)__builtin_amdgcn_global_atomic_fadd_f64((gdouble *)(T + (size_t)r * ld), x); };
-    const double len = (double)step;
-    add(NIG_T_EPISODES, 1.0);
-    add(NIG_T_RET_SUM, ret);
-    add(NIG_T_RET_SQ, ret * ret);
-    (void)__builtin_amdgcn_global_atomic_fmin_f64((gdouble *)(T + (size_t)NIG_T_RET_MIN * ld), ret);
-    (void)__builtin_amdgcn_global_atomic_fmax_f64((gdouble *)(T + (size_t)NIG_T_RET_MAX * ld), ret);
-    add(NIG_T_LEN_SUM, len);
-    add(NIG_T_LEN_SQ, len * len);
-    add(NIG_T_VIOL, (double)viol_ep);
-    add(NIG_T_CRIT, (double)ncrit);
-    add(NIG_T_SHUTDOWN, (ncrit > 0) ? 1.0 : 0.0);
-    add(NIG_T_SUCCESS, (ret > 0.0) ? 1.0 : 0.0);
-    add(NIG_T_SATISFIED, (double)(n_en * step - (int)viol_ep));
-    add(NIG_T_CONSTRAINTS, (double)(n_en * step));
-}
-
-// Which of the two the step kernel uses: the atomics unless the env says otherwise.  They execute at the memory side at
-// ~1.3 TB/s chip-wide (MI355X_MICROARCH.md "Global float atomics"): nothing for an env whose lanes finish rarely
-// (ChemicalReactor 0.3 % per step, RobotAssembly 2.4 %), but PowerGrid finishes 18 % of its lanes every step -- 19 bytes
-// of atomic traffic per env-step, ~16 % of its step launch at 262 144 lanes -- so it keeps the load / store flush.
-template <class E, class = void> struct tally_atomic : std::true_type {};
-template <class E> struct tally_atomic<E, std::void_t<decltype(E::TALLY_ATOMIC)>> : std::bool_constant<E::TALLY_ATOMIC> {};
-
-// Register-resident partial tally of one lane for the duration of a fused rollout.
-struct LaneTally {
-    double ret_sum, ret_sq, ret_min, ret_max, len_sq;
-    int episodes, len_sum, viol, crit, shutdown, success;
-    long long life;
-    __device__ __forceinline__ void clear()
-    {
-        ret_sum = 0.0; ret_sq = 0.0; ret_min = __builtin_inf(); ret_max = -__builtin_inf(); len_sq = 0.0;
-        episodes = 0; len_sum = 0; viol = 0; crit = 0; shutdown = 0; success = 0; life = 0;
-    }
-    __device__ __forceinline__ void episode(double ret, int step, uint32_t viol_ep, int ncrit)
-    {
-        const double len = (double)step;
-        episodes += 1; ret_sum += ret; ret_sq += ret * ret;
-        ret_min = fmin(ret_min, ret); ret_max = fmax(ret_max, ret);
-        len_sum += step; len_sq += len * len;
-        viol += (int)viol_ep; crit += ncrit; shutdown += (ncrit > 0) ? 1 : 0; success += (ret > 0.0) ? 1 : 0;
-    }
-    // merge into the lane's column of the global tally (same fp64 operation order per row as
-    // flush_tally would have produced when at most one episode finished; sums of several
-    // episodes are added as one partial -- integer rows exact, fp rows within 1 ulp of fp64)
-    __device__ __forceinline__ void merge(double *T, uint32_t ld, int n_en) const
-    {
-        double v[NIG_T_ROWS];
-#pragma unroll
-        for (int r = 0; r < NIG_T_ROWS; ++r) v[r] = T[(size_t)r * ld];
-        v[NIG_T_EPISODES] += (double)episodes;
-        v[NIG_T_RET_SUM] += ret_sum;
-        v[NIG_T_RET_SQ] += ret_sq;
-        v[NIG_T_RET_MIN] = fmin(v[NIG_T_RET_MIN], ret_min);
-        v[NIG_T_RET_MAX] = fmax(v[NIG_T_RET_MAX], ret_max);
-        v[NIG_T_LEN_SUM] += (double)len_sum;
-        v[NIG_T_LEN_SQ] += len_sq;
-        v[NIG_T_VIOL] += (double)viol;
-        v[NIG_T_CRIT] += (double)crit;
-        v[NIG_T_SHUTDOWN] += (double)shutdown;
-        v[NIG_T_SUCCESS] += (double)success;
-        v[NIG_T_SATISFIED] += (double)((long long)n_en * len_sum - viol);   // every step of a finished episode has n_en constraints
-        v[NIG_T_CONSTRAINTS] += (double)((long long)n_en * len_sum);
-#pragma unroll
-        for (int r = 0; r < NIG_T_ROWS; ++r) T[(size_t)r * ld] = v[r];
-    }
-};
-
 // Wave-cooperative reset (envs with COOP_RESET): the lanes of `m` (ballot of the finishing lanes of this wave)
 // get their initial states from work items (finishing lane, generator block) spread over all 64 lanes; an item
 // writes the state rows its block feeds into column `owner` of the wave-private LDS image img[RESET_ROWS][64], the owners
@@ -443,7 +335,7 @@ __global__ void __launch_bounds__(HELP ? 2 * BLK : BLK, (ACT64 || HELP ? 2 : (BL
     const unsigned tid = HELP ? (threadIdx.x & (unsigned)(BLOCK - 1)) : threadIdx.x;    // lane of the block (helper: the lane it works for)
     const uint32_t base = blockIdx.x * BLOCK;                  // block-uniform
     const bool in_range = base + tid < p.B;
-    const uint32_t t_now = (p.t_ptr ? *p.t_ptr : 0u) + p.t_off;     // (the pointer chase costs 0.03-0.05 us of the launch: measured with a build that skipped it)
+    const uint32_t t_now = launch_counter(p.t_ptr, p.t_off);        // (the pointer chase costs 0.03-0.05 us of the launch: measured with a build that skipped it)
     // The generator's table: staged in LDS when a lane looks up many normals per launch; an env with a couple of draws
     // per step reads its entries straight from the 12 KiB global table (L2-resident) -- staging 12 KiB per block plus a
     // block barrier costs more than two or three 16-byte loads per lane.  With helper waves THEY stage it, first thing.
@@ -540,18 +432,16 @@ __global__ void __launch_bounds__(HELP ? 2 * BLK : BLK, (ACT64 || HELP ? 2 : (BL
     step_core<Env>(s, a, nz, step_pre, p.max_steps, p.dt32, p.dt, p.cmask, n, res);
 
     const int step = step_pre + 1;
-    const uint32_t viol_ep = (ctr >> NIG_CTR_VIOL_SHIFT) + (uint32_t)res.nviol;   // base.py:182
+    const uint32_t viol_ep = episode_violations(ctr, res.nviol);
     const bool done = res.terminated || res.truncated;
     uint32_t fl = pack_flags<Env>(res, step);
-    uint32_t nctr = (uint32_t)step | (viol_ep << NIG_CTR_VIOL_SHIFT);
+    uint32_t nctr = counter_word(step, viol_ep);
     const bool autoreset = (p.hflags & NIG_F_AUTORESET) != 0;
     const bool need_reset = active && done && autoreset;
 
     // utils.py:99  episode_return += reward.  Computed for every lane, used by the tally's: a use inside the conditional
     // blocks below would let the compiler sink the LOAD of the running return down there, behind the step (one more round trip)
-    double ret;
-    if constexpr (Env::RET_F32 && !ACT64) ret = (double)((float)ret_prev + res.reward);   // float32 accumulation (CR, float32 rewards)
-    else ret = ret_prev + (double)res.reward;
+    double ret = add_reward<Env, ACT64>(ret_prev, res.reward);
     asm volatile("" :: "v"(ret));                 // (a use the sinking pass cannot move the load past)
     if (active) {
         if (done) {
@@ -570,7 +460,7 @@ __global__ void __launch_bounds__(HELP ? 2 * BLK : BLK, (ACT64 || HELP ? 2 : (BL
 #pragma unroll
                 for (int k = 0; k < S; ++k) (fo + k * p.ld_obs)[tid] = n[k];
             }
-            if (autoreset) { nctr = 0u; fl |= NIG_FLAG_DID_RESET; }
+            if (autoreset) { nctr = 0u; fl |= did_reset_flag(true); }
             else nctr |= NIG_CTR_DONE;
         }
         if constexpr (!COOP) {
@@ -881,23 +771,21 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs &q, const uint32_
         } else if constexpr (KS > 0 && !SHARE) draw_one<Env>(key, nz);
         step_core<Env>(s, a, nz, step_pre, p.max_steps, p.dt32, p.dt, p.cmask, n, res);
         const int step = step_pre + 1;
-        const uint32_t viol_ep = (ctr >> NIG_CTR_VIOL_SHIFT) + (uint32_t)res.nviol;
+        const uint32_t viol_ep = episode_violations(ctr, res.nviol);
         const bool done = (res.terminated || res.truncated) && !frozen;
         uint32_t fl = pack_flags<Env>(res, step);
         float rew = (float)res.reward;
         if (may_freeze) {                          // skipped wholesale (scalar branch) when no lane can be frozen
             if (frozen) {                          // untouched lane: discard the speculative step
-                fl = NIG_FLAG_INACTIVE | ((ctr & NIG_CTR_STEP_MASK) << NIG_FLAG_STEP_SHIFT);
+                fl = frozen_flag_word(ctr);
                 rew = 0.0f;
 #pragma unroll
                 for (int k = 0; k < S; ++k) n[k] = s[k];
             }
         }
         if (!frozen) {
-            ctr = (uint32_t)step | (viol_ep << NIG_CTR_VIOL_SHIFT);
-            if (tally) {
-                ret = ret + (ret_t)res.reward;
-            }
+            ctr = counter_word(step, viol_ep);
+            if (tally) ret = add_reward<Env>(ret, res.reward);
         }
         // Next step's process noise, first half: (second step of a pair) the Philox rounds of the next
         // pair, then the index arithmetic and the LDS table reads of the two draws.  The cubic that
@@ -946,12 +834,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs &q, const uint32_
             // issued above without a wait in between.)
             const unsigned lane = tid & 63u, wave_env0 = base + (tid & ~63u);
             const v4f *tr = s_tr + (tid >> 6) * Lds::TR_STRIDE;
-            // The reads below are OTHER lanes' writes.  The compiler reasons per thread: a lane's own piece 48 l + 16 can
-            // never be the address 16 l + 1024 k it reads, so without this fence it may sink that store out of the loop
-            // (it did, in the injected-draw variant -- the only one whose loop holds no other fence).  Wavefront scope:
-            // pins the compiler's order, emits no wait (the LDS pipeline executes a wave's operations in order).
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            image_rows_fence();                    // the reads below are OTHER lanes' writes
             v4f *oo = reinterpret_cast<v4f *>(obs_row);
             constexpr int NV = (16 * S + 63) / 64;  // float4 pieces per lane: the wave's block is 64*S floats = 16*S float4
             v4f v[NV];
@@ -979,7 +862,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs &q, const uint32_
         }
         if constexpr (OUT >= 1) {
             stream_store(rew_row + tid, rew);
-            stream_store(fl_row + tid, fl | ((done && autoreset) ? NIG_FLAG_DID_RESET : 0u));
+            stream_store(fl_row + tid, fl | did_reset_flag(done && autoreset));
         }
         }   // in_range
         if constexpr (OUT >= 1) { rew_row += q.out_stride; fl_row += q.out_stride; }
@@ -1099,12 +982,7 @@ __device__ __forceinline__ void rollout_body(const RolloutArgs &q, const uint32_
     if (!in_range) return;
 #pragma unroll
     for (int k = 0; k < S; ++k) (p.state + base + k * p.ld_state)[tid] = s[k];
-    (p.ctr + base)[tid] = ctr;
-    if (lt.life != 0) (p.life_viol + base)[tid] += lt.life;
-    if (tally) {
-        (p.ep_ret + base)[tid] = (double)ret;
-        if (lt.episodes > 0) lt.merge(p.tally + base + tid, p.ld, p.n_en);
-    }
+    store_episode(p.ctr, p.life_viol, p.ep_ret, p.tally, p.ld, p.n_en, base, tid, tally, ctr, lt.life, ret, lt);
 }
 
 template <class Env, int OUT, bool PAIRED, bool FULL, bool NOISE = false>
@@ -1503,7 +1381,9 @@ __global__ void __launch_bounds__(BLOCK) rollout_policy_kernel(const PolicyArgs 
         uint32_t *dst = reinterpret_cast<uint32_t *>(&s_pol);
         for (unsigned i = threadIdx.x; i < sizeof(nig_policy) / 4; i += BLOCK) dst[i] = src[i];
     }
-    NIG_STAGE_PROBIT(s_probit);                    // (ends with the block barrier that also publishes s_pol)
+    __shared__ float4 s_probit[768];
+    for (int i_ = (int)threadIdx.x; i_ < 768; i_ += BLOCK) s_probit[i_] = NIG_PROBIT[i_];
+    __syncthreads();                               // (the block barrier also publishes s_pol)
     const nig_policy *pol = &s_pol;
     const StepArgs &p = q.s;
     const unsigned tid = threadIdx.x;
@@ -1514,7 +1394,7 @@ __global__ void __launch_bounds__(BLOCK) rollout_policy_kernel(const PolicyArgs 
     } else {
         if (!in_range) return;
     }
-    const uint32_t t_base = (p.t_ptr ? *p.t_ptr : 0u) + p.t_off;
+    const uint32_t t_base = launch_counter(p.t_ptr, p.t_off);
     const uint64_t gi = p.env0 + (uint64_t)(base + tid);
     const bool autoreset = (p.hflags & NIG_F_AUTORESET) != 0;
     const bool tally = p.tally != nullptr;
@@ -1542,7 +1422,7 @@ __global__ void __launch_bounds__(BLOCK) rollout_policy_kernel(const PolicyArgs 
         const bool live = !(ctr & NIG_CTR_DONE);
         if (!live) {                               // frozen lane: base.py:159-160
             if (in_range) {
-                if (p.flags) (p.flags + base + orow)[tid] = NIG_FLAG_INACTIVE | ((ctr & NIG_CTR_STEP_MASK) << NIG_FLAG_STEP_SHIFT);
+                if (p.flags) (p.flags + base + orow)[tid] = frozen_flag_word(ctr);
                 if (p.reward) (p.reward + base + orow)[tid] = 0.0f;
             }
         } else {
@@ -1566,8 +1446,7 @@ __global__ void __launch_bounds__(BLOCK) rollout_policy_kernel(const PolicyArgs 
                     for (int k = 0; k < S; ++k) trf[k] = s[k];
                 }
                 v4f *oo = reinterpret_cast<v4f *>(q.obs_out + (size_t)it * q.obs_step_stride + (size_t)(base + (tid & ~63u)) * S);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // other lanes' writes are read below: see rollout_body
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                image_rows_fence();                // other lanes' writes are read below
                 constexpr int NV = (16 * S + 63) / 64;
 #pragma unroll
                 for (int k = 0; k < NV; ++k)
@@ -1593,19 +1472,15 @@ __global__ void __launch_bounds__(BLOCK) rollout_policy_kernel(const PolicyArgs 
         StepResult<Env> res;
         step_core<Env>(s, a, nz, step_pre, p.max_steps, p.dt32, p.dt, p.cmask, n, res);
         const int step = step_pre + 1;
-        const uint32_t viol_ep = (ctr >> NIG_CTR_VIOL_SHIFT) + (uint32_t)res.nviol;
+        const uint32_t viol_ep = episode_violations(ctr, res.nviol);
         const bool done = res.terminated || res.truncated;
-        uint32_t fl = pack_flags<Env>(res, step) | ((done && autoreset) ? NIG_FLAG_DID_RESET : 0u);
-        ctr = (uint32_t)step | (viol_ep << NIG_CTR_VIOL_SHIFT);
-        if (tally) {
-            if constexpr (Env::RET_F32) ret = (double)((float)ret + res.reward);
-            else ret = ret + (double)res.reward;
-        }
+        uint32_t fl = pack_flags<Env>(res, step) | did_reset_flag(done && autoreset);
+        ctr = counter_word(step, viol_ep);
+        if (tally) ret = add_reward<Env>(ret, res.reward);
         if (p.reward) stream_store(p.reward + base + orow + tid, (float)res.reward);
         if (p.flags) stream_store(p.flags + base + orow + tid, fl);
         if (done) {
-            lt.life += (long long)viol_ep;
-            if (tally) { lt.episode(ret, step, viol_ep, res.ncrit); ret = 0.0; }
+            ret = lt.finish(tally, ret, step, viol_ep, res.ncrit);
             if (autoreset) {
                 if constexpr (COOP) {
                     need_reset = true;
@@ -1635,12 +1510,7 @@ __global__ void __launch_bounds__(BLOCK) rollout_policy_kernel(const PolicyArgs 
     if (!in_range) return;
 #pragma unroll
     for (int k = 0; k < S; ++k) (p.state + base + k * p.ld_state)[tid] = s[k];
-    (p.ctr + base)[tid] = ctr;
-    if (lt.life != 0) (p.life_viol + base)[tid] += lt.life;
-    if (tally) {
-        (p.ep_ret + base)[tid] = ret;
-        if (lt.episodes > 0) lt.merge(p.tally + base + tid, p.ld, p.n_en);
-    }
+    store_episode(p.ctr, p.life_viol, p.ep_ret, p.tally, p.ld, p.n_en, base, tid, tally, ctr, lt.life, ret, lt);
     if (pid_mem) {
 #pragma unroll
         for (int j = 0; j < A; ++j) {
@@ -1786,7 +1656,7 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
     __shared__ __attribute__((aligned(16))) float s_w[2][MLP_CHREC * 64];
     __shared__ float4 s_probit_[mlp_two_blocks<Env> ? 1 : 768];
     if constexpr (!mlp_two_blocks<Env>) {
-        for (int i_ = (int)threadIdx.x; i_ < 768; i_ += BLOCK) s_probit_[i_] = NIG_PROBIT[i_];
+        stage_probit(s_probit_, threadIdx.x, BLOCK);
         __syncthreads();
     }
     const float4 *const s_probit = mlp_two_blocks<Env> ? NIG_PROBIT : s_probit_;
@@ -2063,9 +1933,9 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
         if constexpr (ACT64) step_core<Env>(s, a64, nz, step_pre, p.max_steps, p.dt32, p.dt, p.cmask, n, res);
         else step_core<Env>(s, a, nz, step_pre, p.max_steps, p.dt32, p.dt, p.cmask, n, res);
         const int step = step_pre + 1;
-        const uint32_t viol_ep = (ctr >> NIG_CTR_VIOL_SHIFT) + (uint32_t)res.nviol;
+        const uint32_t viol_ep = episode_violations(ctr, res.nviol);
         const bool done = (res.terminated || res.truncated) && !frozen;
-        uint32_t fl = pack_flags<Env>(res, step) | ((done && autoreset) ? NIG_FLAG_DID_RESET : 0u);
+        uint32_t fl = pack_flags<Env>(res, step) | did_reset_flag(done && autoreset);
         if constexpr (SHIELD) fl |= shield ? NIG_FLAG_SHIELDED : 0u;
         if constexpr (ENS != ENS_NONE) fl |= uncertain ? NIG_FLAG_UNCERTAIN : 0u;
         float rew = (float)res.reward;
@@ -2075,19 +1945,15 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
 #pragma unroll
             for (int k = 0; k < S; ++k) n[k] = s[k];
         } else {
-            ctr = (uint32_t)step | (viol_ep << NIG_CTR_VIOL_SHIFT);
-            if (tally) {
-                if constexpr (Env::RET_F32 && !ACT64) ret = (double)((float)ret + res.reward);
-                else ret = ret + (double)res.reward;
-            }
+            ctr = counter_word(step, viol_ep);
+            if (tally) ret = add_reward<Env, ACT64>(ret, res.reward);
         }
         if (writer) {
             if (p.reward) (p.reward + orow)[li] = rew;
             if (p.flags) (p.flags + orow)[li] = fl;
         }
         if (done) {
-            lt.life += (long long)viol_ep;
-            if (tally) { lt.episode(ret, step, viol_ep, res.ncrit); ret = 0.0; }
+            ret = lt.finish(tally, ret, step, viol_ep, res.ncrit);
             if (autoreset) {
                 double rn[KR > 0 ? KR : 1];
                 Env::draw_init(key, rn);
@@ -2103,12 +1969,7 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
     if (!writer) return;
 #pragma unroll
     for (int k = 0; k < S; ++k) (p.state + k * p.ld_state)[li] = s[k];
-    p.ctr[li] = ctr;
-    if (lt.life != 0) p.life_viol[li] += lt.life;
-    if (tally) {
-        p.ep_ret[li] = ret;
-        if (lt.episodes > 0) lt.merge(p.tally + li, p.ld, p.n_en);
-    }
+    store_episode(p.ctr, p.life_viol, p.ep_ret, p.tally, p.ld, p.n_en, 0u, li, tally, ctr, lt.life, ret, lt);   // (row offset 0: `li` counts from the batch's first lane)
 }
 
 template <class Env>
@@ -2141,7 +2002,9 @@ template <class Env, bool PARITY>
 __global__ void __launch_bounds__(BLOCK) reset_kernel(const ResetArgs p)
 {
     constexpr int S = Env::S, KR = Env::KR;
-    NIG_STAGE_PROBIT(s_probit);
+    __shared__ float4 s_probit[768];
+    stage_probit(s_probit, threadIdx.x, BLOCK);
+    __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= p.B) return;
     if (p.mask && !p.mask[i]) return;

@@ -276,8 +276,7 @@ __device__ __forceinline__ void pg_lds_rollout_body(const QA &q, const uint32_t 
 #pragma unroll
             for (int g = 0; g < 8; ++g) { const v4f w = mine[8 * g]; obs[4 * g] = w.x; obs[4 * g + 1] = w.y; obs[4 * g + 2] = w.z; obs[4 * g + 3] = w.w; }
             if (obs_row != nullptr) {              // (wave-uniform) the 64 observation rows in lane-contiguous order
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                image_rows_fence();                // other lanes' writes are read below
                 v4f *oo = reinterpret_cast<v4f *>(obs_row);
                 v4f tv[8];
 #pragma unroll
@@ -452,18 +451,18 @@ __device__ __forceinline__ void pg_lds_rollout_body(const QA &q, const uint32_t 
             StepResult<Env> res;
             post_finish<Env, double>(Env::reward_total(fr, Env::reward_volt(v), er, ap), Env::done_fv(n0, v), vb, step_pre, p.max_steps, res);
             const int step = step_pre + 1;
-            const uint32_t viol_ep = (ctr >> NIG_CTR_VIOL_SHIFT) + (uint32_t)res.nviol;
+            const uint32_t viol_ep = episode_violations(ctr, res.nviol);
             const bool done = res.terminated || res.truncated;
-            ctr = done ? 0u : ((uint32_t)step | (viol_ep << NIG_CTR_VIOL_SHIFT));
-            if (tally) ret = ret + res.reward;
+            ctr = done ? 0u : counter_word(step, viol_ep);
+            if (tally) ret = add_reward<Env>(ret, res.reward);
             if constexpr (OUT >= 1) {
                 stream_store(rew_row + tid, (float)res.reward);
-                stream_store(fl_row + tid, pack_flags<Env>(res, step) | (done ? NIG_FLAG_DID_RESET : 0u));
+                stream_store(fl_row + tid, pack_flags<Env>(res, step) | did_reset_flag(done));
                 rew_row += q.out_stride; fl_row += q.out_stride;
             }
             if constexpr (POLICY) {                // run-time switches, as in rollout_policy_kernel (either may be absent)
                 if (rew_row) { stream_store(rew_row + tid, (float)res.reward); rew_row += q.out_stride; }
-                if (fl_row) { stream_store(fl_row + tid, pack_flags<Env>(res, step) | (done ? NIG_FLAG_DID_RESET : 0u)); fl_row += q.out_stride; }
+                if (fl_row) { stream_store(fl_row + tid, pack_flags<Env>(res, step) | did_reset_flag(done)); fl_row += q.out_stride; }
             }
             if (done) {                            // (lt.viol doubles as the lifetime violation count: two registers less)
                 if (tally) { lt.episode(ret, step, viol_ep, res.ncrit); ret = 0.0; }
@@ -556,8 +555,7 @@ __device__ __forceinline__ void pg_lds_rollout_body(const QA &q, const uint32_t 
                 // the image now holds the wave's 64 post-step rows: row-major float4 64 j + lane sits at 64 j + rd
                 v4f *oo = reinterpret_cast<v4f *>(obs_row);
                 v4f v[8];
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // other lanes' writes are read below (compiler order only: rollout_body)
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                image_rows_fence();                // other lanes' writes are read below
 #ifdef NIG_DIAG_PG_NOLDSREAD           // (diagnostic builds only, profiles/r03/pg_store_probe2.sh: what do the transposed reads cost?)
 #pragma unroll
                 for (int j = 0; j < 8; ++j) { v4f w = {ngen7, l7, (float)j, ngen7}; v[j] = w; }
@@ -637,12 +635,8 @@ __device__ __forceinline__ void pg_lds_rollout_body(const QA &q, const uint32_t 
         float *r = p.state + base + (4 * g) * p.ld_state;
         r[tid] = v.x; (r + p.ld_state)[tid] = v.y; (r + 2 * p.ld_state)[tid] = v.z; (r + 3 * p.ld_state)[tid] = v.w;
     }
-    (p.ctr + base)[tid] = ctr;
-    if (lt.viol != 0) (p.life_viol + base)[tid] += (long long)lt.viol;    // base.py:183 total_violations of the finished episodes
-    if (tally) {
-        (p.ep_ret + base)[tid] = ret;
-        if (lt.episodes > 0) lt.merge(p.tally + base + tid, p.ld, p.n_en);
-    }
+    // (lt.viol: base.py:183 total_violations of the finished episodes, see the step's `done` clause)
+    store_episode(p.ctr, p.life_viol, p.ep_ret, p.tally, p.ld, p.n_en, base, tid, tally, ctr, lt.viol, ret, lt);
     if constexpr (PROD) NIG_RING_REPORT(p.ring_err, nz_sync, lane);
 }
 
@@ -660,7 +654,7 @@ __global__ void __launch_bounds__(512, 2) rollout_pg_pair_kernel(const RolloutAr
     static_assert(!(REG && NOISE), "recorded draws: the LDS-resident stepping body");
     __shared__ __attribute__((aligned(16))) unsigned char smem[PL::BYTES];
     float4 *const s_probit = reinterpret_cast<float4 *>(smem + PgLds<256>::OFF_PROBIT);
-    for (int i_ = (int)threadIdx.x; i_ < 768; i_ += 512) s_probit[i_] = NIG_PROBIT[i_];
+    stage_probit(s_probit, threadIdx.x, 512);
     if (threadIdx.x < 16u) reinterpret_cast<uint32_t *>(smem + PL::OFF_SYNC)[threadIdx.x] = 0u;
     __syncthreads();
     const uint32_t base = (blockIdx.x + q.block0) * 256u;
@@ -682,7 +676,7 @@ __global__ void __launch_bounds__(512, 2) pg_pair_sampled_kernel(const RolloutAr
     using PL = std::conditional_t<REG, PgPairRegLds<OUT>, PgPairLdsT<false>>;
     __shared__ __attribute__((aligned(16))) unsigned char smem[PL::BYTES];
     float4 *const s_probit = reinterpret_cast<float4 *>(smem + PgLds<256>::OFF_PROBIT);
-    for (int i_ = (int)threadIdx.x; i_ < 768; i_ += 512) s_probit[i_] = NIG_PROBIT[i_];
+    stage_probit(s_probit, threadIdx.x, 512);
     if (threadIdx.x < 16u) reinterpret_cast<uint32_t *>(smem + PL::OFF_SYNC)[threadIdx.x] = 0u;
     __syncthreads();
     const uint32_t base = (blockIdx.x + q.block0) * 256u;
@@ -792,16 +786,15 @@ __device__ __forceinline__ void pg_policy_reg_body(const QA &q, const uint32_t b
         StepResult<Env> res;
         step_core<Env>(s, a, nz, step_pre, p.max_steps, p.dt32, p.dt, p.cmask, n, res);
         const int step = step_pre + 1;
-        const uint32_t viol_ep = (ctr >> NIG_CTR_VIOL_SHIFT) + (uint32_t)res.nviol;
+        const uint32_t viol_ep = episode_violations(ctr, res.nviol);
         const bool done = res.terminated || res.truncated;
-        const uint32_t fl = pack_flags<Env>(res, step) | (done ? NIG_FLAG_DID_RESET : 0u);
-        ctr = (uint32_t)step | (viol_ep << NIG_CTR_VIOL_SHIFT);
-        if (tally) ret = ret + (double)res.reward;
+        const uint32_t fl = pack_flags<Env>(res, step) | did_reset_flag(done);
+        ctr = counter_word(step, viol_ep);
+        if (tally) ret = add_reward<Env>(ret, res.reward);
         if (rew_row) { stream_store(rew_row + tid, (float)res.reward); rew_row += q.out_stride; }
         if (fl_row) { stream_store(fl_row + tid, fl); fl_row += q.out_stride; }
         if (done) {
-            lt.life += (long long)viol_ep;
-            if (tally) { lt.episode(ret, step, viol_ep, res.ncrit); ret = 0.0; }
+            ret = lt.finish(tally, ret, step, viol_ep, res.ncrit);
             ctr = 0u;
         }
         const unsigned long long m = __ballot(done);
@@ -813,12 +806,7 @@ __device__ __forceinline__ void pg_policy_reg_body(const QA &q, const uint32_t b
     }
 #pragma unroll
     for (int k = 0; k < S; ++k) (p.state + base + k * p.ld_state)[tid] = s[k];
-    (p.ctr + base)[tid] = ctr;
-    if (lt.life != 0) (p.life_viol + base)[tid] += lt.life;
-    if (tally) {
-        (p.ep_ret + base)[tid] = ret;
-        if (lt.episodes > 0) lt.merge(p.tally + base + tid, p.ld, p.n_en);
-    }
+    store_episode(p.ctr, p.life_viol, p.ep_ret, p.tally, p.ld, p.n_en, base, tid, tally, ctr, lt.life, ret, lt);
     NIG_RING_REPORT(p.ring_err, nz_sync, lane);
 }
 
@@ -831,7 +819,7 @@ __global__ void __launch_bounds__(512, 2) rollout_pg_pair_policy_kernel(const QA
     using PL = PgPairLdsT<false, true>;
     __shared__ __attribute__((aligned(16))) unsigned char smem[PL::BYTES];
     float4 *const s_probit = reinterpret_cast<float4 *>(smem + PgLds<256>::OFF_PROBIT);
-    for (int i_ = (int)threadIdx.x; i_ < 768; i_ += 512) s_probit[i_] = NIG_PROBIT[i_];
+    stage_probit(s_probit, threadIdx.x, 512);
     {
         const uint32_t *src = reinterpret_cast<const uint32_t *>(q.pol);
         uint32_t *dst = reinterpret_cast<uint32_t *>(smem + PL::OFF_POL);

@@ -25,7 +25,7 @@
 
     const StepArgs &p = q.s;
     const uint32_t base = (blockIdx.x + q.block0) * (64u * NP) + pair * 64u;     // the triple's first lane
-    const uint32_t t_base = (p.t_ptr ? *p.t_ptr : 0u) + p.t_off + (uint32_t)q.it0;   // local step i uses t_base + i + 1
+    const uint32_t t_base = launch_counter(p.t_ptr, p.t_off) + (uint32_t)q.it0;      // local step i uses t_base + i + 1
     const int n = q.n_steps - q.it0;                                             // local steps [0, n)
 
     if (role == 0) {
@@ -240,11 +240,11 @@
         post_core<Env, float>(nx, a, vb, step_pre, p.max_steps, res);
 #endif
         const int step = step_pre + 1;
-        const uint32_t viol_ep = (ctr >> NIG_CTR_VIOL_SHIFT) + (uint32_t)res.nviol;
+        const uint32_t viol_ep = episode_violations(ctr, res.nviol);
         const bool done = res.terminated || res.truncated;
-        const uint32_t fl = pack_flags<Env>(res, step) | (done ? NIG_FLAG_DID_RESET : 0u);
-        ctr = (uint32_t)step | (viol_ep << NIG_CTR_VIOL_SHIFT);
-        if (tally) ret = ret + (ret_t)res.reward;
+        const uint32_t fl = pack_flags<Env>(res, step) | did_reset_flag(done);
+        ctr = counter_word(step, viol_ep);
+        if (tally) ret = add_reward<Env>(ret, res.reward);
         if constexpr (OUT == 3) {
             v4f *oo = reinterpret_cast<v4f *>(obs_row);
 #pragma unroll
@@ -265,8 +265,7 @@
         }
         if constexpr (OUT >= 2) obs_row += q.obs_step_stride;
         if (done) {
-            lt.life += (long long)viol_ep;
-            if (tally) { lt.episode((double)ret, step, viol_ep, res.ncrit); ret = (ret_t)0; }
+            ret = lt.finish(tally, ret, step, viol_ep, res.ncrit);
             ctr = 0u;
         }
         cslot = (cslot + 1 == K) ? 0 : cslot + 1;

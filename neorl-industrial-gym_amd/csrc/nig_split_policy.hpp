@@ -78,7 +78,7 @@ __global__ void __launch_bounds__(192 * NP, 1) split_policy_kernel(const PolicyA
 
     const StepArgs &p = q.s;
     const uint32_t base = blockIdx.x * (64u * NP) + pair * 64u;      // the triple's first lane
-    const uint32_t t_base = (p.t_ptr ? *p.t_ptr : 0u) + p.t_off;     // step i uses t_base + i + 1
+    const uint32_t t_base = launch_counter(p.t_ptr, p.t_off);        // step i uses t_base + i + 1
     const int n = q.n_steps;
     bool any_sigma, any_half, mix;                                   // wave-uniform switches of the policy
     policy_switches<A>(pol, any_sigma, any_half, mix);
@@ -283,29 +283,20 @@ __global__ void __launch_bounds__(192 * NP, 1) split_policy_kernel(const PolicyA
         StepResult<Env> res;
         post_core<Env, float>(nx, a, vb, step_pre, p.max_steps, res);
         const int step = step_pre + 1;
-        const uint32_t viol_ep = (ctr >> NIG_CTR_VIOL_SHIFT) + (uint32_t)res.nviol;
+        const uint32_t viol_ep = episode_violations(ctr, res.nviol);
         const bool done = res.terminated || res.truncated;
-        const uint32_t fl = pack_flags<Env>(res, step) | (done ? NIG_FLAG_DID_RESET : 0u);
-        ctr = (uint32_t)step | (viol_ep << NIG_CTR_VIOL_SHIFT);
-        if (tally) {
-            if constexpr (Env::RET_F32) ret = (double)((float)ret + res.reward);
-            else ret = ret + (double)res.reward;
-        }
+        const uint32_t fl = pack_flags<Env>(res, step) | did_reset_flag(done);
+        ctr = counter_word(step, viol_ep);
+        if (tally) ret = add_reward<Env>(ret, res.reward);
         if (p.reward) stream_store(p.reward + base + orow + lane, (float)res.reward);
         if (p.flags) stream_store(p.flags + base + orow + lane, fl);
         if (done) {
-            lt.life += (long long)viol_ep;
-            if (tally) { lt.episode(ret, step, viol_ep, res.ncrit); ret = 0.0; }
+            ret = lt.finish(tally, ret, step, viol_ep, res.ncrit);
             ctr = 0u;
         }
         cslot = (cslot + 1 == K) ? 0 : cslot + 1;
     }
-    (p.ctr + base)[lane] = ctr;
-    if (lt.life != 0) (p.life_viol + base)[lane] += lt.life;
-    if (tally) {
-        (p.ep_ret + base)[lane] = ret;
-        if (lt.episodes > 0) lt.merge(p.tally + base + lane, p.ld, p.n_en);
-    }
+    store_episode(p.ctr, p.life_viol, p.ep_ret, p.tally, p.ld, p.n_en, base, lane, tally, ctr, lt.life, ret, lt);
     NIG_RING_REPORT(p.ring_err, sync, lane);
 }
 

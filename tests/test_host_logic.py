@@ -289,7 +289,7 @@ def test_build_hash_covers_every_source_of_the_library():
     """Staleness is a content hash over csrc/*.hip, *.hpp, *.inc and include/nig.h (round 1 missed the .inc files)."""
     from neorl_industrial_gym_amd import _build
     names = {os.path.basename(p) for p in _build.sources() + _build.headers()}
-    for f in ("nig_api.hip", "nig_mixed.hip", "env_pg.hip", "nig_kernels.hpp", "nig_envs.hpp", "nig_detmath.hpp",
+    for f in ("nig_api.hip", "nig_mixed.hip", "env_pg.hip", "nig_kernels.hpp", "nig_episode.hpp", "nig_envs.hpp", "nig_detmath.hpp",
               "nig_probit_table.inc", "nig_spec_plants.inc", "nig.h"):
         assert f in names, f
 
