@@ -221,19 +221,20 @@ static int refuse(const char *fn, const char *what, int code = NIG_ERR_INVALID) 
         if (rc_ != NIG_OK) return rc_;                                       \
     } while (0)
 
-static const nig_env_spec SPECS[NIG_NUM_ENVS] = {
-    {12, 3, 3, 500, 2, 8, 0.1, {-100.0, -50.0, -25.0}, {1, 1, 0}, 1},
-    {32, 8, 3, 1000, 23, 31, 0.1, {-50.0, -30.0, -20.0}, {1, 1, 0}, 0},
-    {24, 7, 3, 1000, 0, 7, 0.1, {-100.0, -200.0, -50.0}, {1, 1, 0}, 0},
+// The static row of one environment, read off its struct in nig_envs.hpp (dt: the base default, base.py:28).
+template <class Env>
+constexpr nig_env_spec spec_row()
+{
+    return {Env::S, Env::A, Env::N_CONSTRAINTS, Env::MAX_STEPS, Env::KS, Env::KR, 0.1,
+            {Env::penalty(0), Env::penalty(1), Env::penalty(2)},
+            {(int32_t)(Env::CRIT_MASK & 1u), (int32_t)((Env::CRIT_MASK >> 1) & 1u), (int32_t)((Env::CRIT_MASK >> 2) & 1u)}, Env::RET_F32};
+}
+static constexpr nig_env_spec SPECS[NIG_NUM_ENVS] = {      // (constexpr: every row is evaluated at compile time)
+    spec_row<ChemicalReactor>(), spec_row<PowerGrid>(), spec_row<RobotAssembly>(),
     /* Advanced envs: 4 / 3 safety-metric conditions, no penalties through the base loop, deterministic */
-    {20, 6, 4, 1000, 0, 0, 0.1, {0.0, 0.0, 0.0}, {0, 0, 0}, 0},
-    {32, 8, 3, 500, 0, 0, 0.1, {0.0, 0.0, 0.0}, {0, 0, 0}, 0},
+    spec_row<AdvancedChemicalReactor>(), spec_row<AdvancedPowerGrid>(),
     /* build-specified plants (spec_plants.py): dims and constraint tables come from the generated data */
-#define NIG_SPEC_ROW(K) {SpecPlant<K>::S, SpecPlant<K>::A, 3, SpecPlant<K>::MAX_STEPS, SpecPlant<K>::KS, SpecPlant<K>::KR, 0.1, \
-                         {NIG_SPEC_PLANTS[K].pen[0], NIG_SPEC_PLANTS[K].pen[1], NIG_SPEC_PLANTS[K].pen[2]},                    \
-                         {NIG_SPEC_PLANTS[K].crit[0], NIG_SPEC_PLANTS[K].crit[1], NIG_SPEC_PLANTS[K].crit[2]}, 1}
-    NIG_SPEC_ROW(0), NIG_SPEC_ROW(1), NIG_SPEC_ROW(2), NIG_SPEC_ROW(3),
-#undef NIG_SPEC_ROW
+    spec_row<SpecPlant<0>>(), spec_row<SpecPlant<1>>(), spec_row<SpecPlant<2>>(), spec_row<SpecPlant<3>>(),
 };
 static const char *NAMES[NIG_NUM_ENVS] = {"ChemicalReactor-v0", "PowerGrid-v0", "RobotAssembly-v0",
                                           "AdvancedChemicalReactor-v0", "AdvancedPowerGrid-v0",

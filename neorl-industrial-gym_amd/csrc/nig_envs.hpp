@@ -55,6 +55,7 @@ struct ChemicalReactor {
     // chemical_reactor.py:38-60 (penalty, critical) in list order
     __device__ static constexpr float penalty(int k) { return k == 0 ? -100.0f : (k == 1 ? -50.0f : -25.0f); }
     static constexpr uint32_t CRIT_MASK = 0x3u;
+    static constexpr int N_CONSTRAINTS = 3;       // len(self.safety_constraints)
 
     // _get_initial_state :89-107 -- fp64 "mean + draw", stored float32
     __device__ static void init(const double (&n)[KR], float (&s)[S])
@@ -282,6 +283,7 @@ struct PowerGrid {
 
     __device__ static constexpr double penalty(int k) { return k == 0 ? -50.0 : (k == 1 ? -30.0 : -20.0); }  // :53-72
     static constexpr uint32_t CRIT_MASK = 0x3u;
+    static constexpr int N_CONSTRAINTS = 3;       // len(self.safety_constraints)
 
     __device__ static constexpr double base_load(int i)   // :82
     {
@@ -610,6 +612,7 @@ struct RobotAssembly {
 
     __device__ static constexpr double penalty(int k) { return k == 0 ? -100.0 : (k == 1 ? -200.0 : -50.0); }  // :56-75
     static constexpr uint32_t CRIT_MASK = 0x3u;
+    static constexpr int N_CONSTRAINTS = 3;       // len(self.safety_constraints)
     static constexpr double PI = 3.141592653589793;
 
     __device__ static constexpr double link(int i)    // :85
@@ -886,6 +889,7 @@ struct SpecPlant {
     __device__ static constexpr float penalty(int k) { return NIG_SPEC_PLANTS[K].pen[k]; }
     static constexpr uint32_t CRIT_MASK = (NIG_SPEC_PLANTS[K].crit[0] ? 1u : 0u) | (NIG_SPEC_PLANTS[K].crit[1] ? 2u : 0u) |
                                           (NIG_SPEC_PLANTS[K].crit[2] ? 4u : 0u);
+    static constexpr int N_CONSTRAINTS = 3;
 
     __device__ static void init(const double (&n)[KR], float (&s)[S])
     {
@@ -1066,6 +1070,7 @@ struct AdvancedChemicalReactor {
     static constexpr int ROLLOUT_WAVES = 3;       // same, for the fused rollout kernels
     using reward_t = float;    // float(total_reward) of a float32 scalar, :404
     static constexpr uint32_t CRIT_MASK = 0u;
+    static constexpr int N_CONSTRAINTS = 4;       // safety-metric conditions of the env's own step()
     __device__ static constexpr float penalty(int) { return 0.0f; }
     __device__ static constexpr float act_low(int j) { return j == 3 ? 273.15f : 0.0f; }                  // :148-155
     __device__ static constexpr float act_high(int j) { return j < 2 ? 0.01f : j == 2 ? 3000.0f : j == 3 ? 473.15f : j == 4 ? 100.0f : 1.0f; }
@@ -1168,6 +1173,7 @@ struct AdvancedPowerGrid {
     static constexpr int ROLLOUT_WAVES = 2;       // same, for the fused rollout kernels
     using reward_t = float;
     static constexpr uint32_t CRIT_MASK = 0u;
+    static constexpr int N_CONSTRAINTS = 3;       // safety-metric conditions of the env's own step()
     __device__ static constexpr float penalty(int) { return 0.0f; }
     __device__ static constexpr float H(int i) { return i == 0 ? 5.0f : i == 1 ? 4.0f : i == 2 ? 3.5f : 4.5f; }      // :79-85
     __device__ static constexpr float D(int i) { return i == 0 ? 1.0f : i == 1 ? 0.8f : i == 2 ? 0.9f : 1.1f; }

@@ -16,6 +16,7 @@
 // (ptr + base)[tid]: the uniform part stays in scalar registers.  The helpers wrap straight-line runs only; fences,
 // sched_barriers, the asm pins and the prologue s_waitcnt stay where the bodies have them.
 #pragma once
+#include "nig_device.hpp"
 
 namespace nig {
 

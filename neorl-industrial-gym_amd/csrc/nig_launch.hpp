@@ -254,6 +254,16 @@ static const EnvLaunch *env_launch_table()
     return &T;
 }
 
+// Mixed-batch launch (nig_mixed.hip): per-segment rollout arguments + the block -> segment table, in launch order.
+constexpr int MIXED_MAX_SEG = NIG_MIXED_MAX_SEGMENTS;
+struct MixedArgs {
+    RolloutArgs seg[MIXED_MAX_SEG];
+    uint32_t blk_end[MIXED_MAX_SEG];     // cumulative block count up to and including segment k
+    int env[MIXED_MAX_SEG];
+    int n_seg;
+};
+static_assert(sizeof(MixedArgs) <= 4000, "kernel argument segment is 4 KiB");
+
 }  // namespace nig
 
 // nig_mixed.hip

@@ -1,0 +1,475 @@
+// nig_mlp.hpp -- the fused MLP actor on MFMA with its safety-critic shield and its ensemble (device code only): MlpArgs,
+// MlpShieldArgs, MlpEnsArgs, rollout_mlp_body and its three kernels.
+#pragma once
+#include "nig_step.hpp"
+
+namespace nig {
+
+// ------------------------------------------------------------------------------------------
+// Fused MLP actor + env step (the one contraction on this path, so the one place for MFMA).
+//
+// One wavefront = 32 env instances.  Everything is computed TRANSPOSED, h^T = W^T x^T, so that
+//   * the A operand is the weight matrix (one float per lane, streamed from a pre-ordered
+//     array: record r = 64 floats = one 256-byte coalesced load),
+//   * the B operand has the env on the lane (l & 31) and the k index on the lane half (l >> 5),
+//   * the 32x32 result tile has the env on the lane again and the hidden unit in the register,
+// which makes an accumulator register of layer n directly usable as a B operand of layer n+1
+// (register t of a tile holds hidden rows rho_h(t) = (t&3) + 8(t>>2) + 4h of that tile for lane
+// half h; the weight stream is ordered to match).  No LDS, no transposes, no conversion.
+// v_mfma_f32_32x32x2_f32 is bit-for-bit fma(a1,b1, fma(a0,b0, c)) (k0 = lane half 0, then k1), so
+// the CPU oracle reproduces the actor exactly.  Biases ride along as one extra k-step per tile
+// (A = bias on half 0 / 0 on half 1, B = 1 / 0).
+// Both lane halves carry the full env state and run the env step redundantly (it is ~3 % of the
+// MFMA time); lanes 32-63 never store.
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+
+struct MlpArgs {
+    StepArgs s;
+    const float *wstream;       // MFMA operand stream built by nig_set_mlp_policy
+    int n_steps;
+    uint32_t out_stride;
+    float *obs_out; uint64_t obs_step_stride;
+    float *act_out; uint32_t ld_act_out; uint64_t act_step_stride;
+};
+
+constexpr int MLP_H = 256, MLP_MT = MLP_H / 32;
+// The operand stream is cut into 1 + MLP_MT CHUNKS of MLP_CHREC records (256 bytes each, padded): chunk 0 = layer 1
+// (MLP_MT tiles of S/2 weight records + 1 bias record), chunk 1 + m2 = hidden tile m2 of layer 2 with its slice of
+// the head (128 + 1 + 16 records; the last chunk also carries the head's bias record).  A chunk is what one fill of
+// an LDS buffer holds: MLP_PIECES wave-instructions of 1 KiB (64 lanes x 16 bytes, LDS-DMA).
+constexpr int MLP_PER = MLP_MT * 16 + 1 + 16;                 // 145 records per hidden tile
+constexpr int MLP_PIECES = (MLP_PER + 1 + 3) / 4;             // 37 KiB pieces per chunk
+constexpr int MLP_CHREC = MLP_PIECES * 4;                     // 148 records per chunk slot
+constexpr int MLP_CHUNKS = 1 + MLP_MT;
+constexpr int MLP_STREAM_FLOATS = MLP_CHUNKS * MLP_CHREC * 64;
+typedef __attribute__((address_space(3))) void nig_lds_void;
+typedef __attribute__((address_space(1))) const void nig_glb_void;
+
+// Two blocks per CU (round 4): the double-buffered weight image is 74 KiB per block; with the generator's 12 KiB table beside it
+// only ONE block fitted a CU's 160 KiB, i.e. one wave per SIMD, and every chunk barrier and ring refill was exposed MFMA idle
+// time (duty cycle 0.78, profiles/r04/mlp_cr65536_sq.txt).  An env with a couple of draws per step (KS <= 4) reads its table
+// entries from global memory (L2-resident, as step_kernel does) and the kernel is compiled for two waves per SIMD, so a second
+// block's waves fill the first's bubbles.
+// The head (layer 3) of an env with at most FOUR actions runs on v_mfma_f32_4x4x1_16B_f32 (round 5): sixteen 4 x 4 blocks of
+// four lanes, K = 1 -- lane l multiplies ITS OWN h2 value (B) with the four head weights held by the four lanes of its block
+// (A: lane 4 b + r holds W3[k][r]) into four accumulators, out[r] += W3[k][r] h2[k]: exactly a head of <= 4 rows, 8 cycles an
+// instruction, where the 32 x 32 x 2 tile spent 64 cycles on 32 rows of which 29 were zero padding (11 % of the step's MFMA
+// time).  Each lane half accumulates the hidden rows ITS accumulator registers hold (rho_h(t)), the two
+// partial sums meet in one v_add_f32 across the halves: a different summation order from the 32 x 32 x 2 head (k0, k1
+// interleaved), restated by the oracle (mlp_actor).
+// Heads of FIVE TO SIXTEEN actions take the same route on v_mfma_f32_16x16x1_4B_f32: four 16 x 16 blocks of sixteen lanes, K = 1,
+// 32 cycles.  Block b = lane >> 4 multiplies its lanes' own h2 values (B: hidden row rho_{b>>1}(t), envs 16 (b & 1) ..) with the
+// sixteen head weights its lanes hold (A: lane 16 b + r holds W3[k_b][r]) into registers 4 b .. 4 b + 3 (row r of env column c in
+// register 4 b + (r & 3) of lane 16 (r >> 2) + c): blocks 0 / 1 are lane half 0's fma chain for envs 0-15 / 16-31, blocks 2 / 3
+// lane half 1's -- the SAME two chains and the same joining add as the 4 x 4 x 1 head, so the oracle has one head for every env.
+// The 32 x 32 x 2 head (64 cycles for 32 rows, 24 of them padding with eight actions) is gone.
+template <class Env> constexpr bool mlp_head4 = Env::A <= 4;
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+
+template <class Env> constexpr bool mlp_two_blocks = true;       // (PowerGrid's 23 + 31 table reads per step / reset from L2 as well: they are noise beside 1 217 MFMAs)
+
+// Safety-critic shield (rollout_mlp_shield_kernel, agents/cql.py predict_with_safety): after the actor, a second pass of the
+// same scheme evaluates p = sigmoid(critic([s, a])), critic = (S + A) -> 256 -> 256 -> 1 ReLU MLP, and the env receives a * 0.5
+// unless p < threshold.  The critic's operand stream (nig_set_mlp_safety) is laid out like the actor's: layer 1 on the input
+// x = [s (S), a (A), 0-pad to even] in MLP_CL1<Env> chunks (one, or two of four tiles each when eight tiles of MLP_CR1 records
+// exceed a chunk slot: PowerGrid, AdvancedPowerGrid, SupplyChain), then one chunk per hidden tile of layer 2 with its slice of
+// a ONE-row head on v_mfma_f32_4x4x1 (the actor's mlp_head4 form with A = 1; the head's bias in record MLP_PER of the last).
+// Its chunks are consumed through the same double-buffered LDS image, so the fill of the next chunk stays in flight across
+// actor -> critic and critic -> next step's actor.
+template <class Env> constexpr int MLP_CDIM = (Env::S + Env::A + 1) & ~1;                    // critic input, padded to even
+template <class Env> constexpr int MLP_CR1 = MLP_CDIM<Env> / 2 + 1;                          // records per critic layer-1 tile
+template <class Env> constexpr int MLP_CL1 = MLP_MT * MLP_CR1<Env> <= MLP_CHREC ? 1 : 2;     // chunks of critic layer 1
+constexpr int MLP_CSTREAM_FLOATS = (2 + MLP_MT) * MLP_CHREC * 64;                          // room for either layer-1 form
+
+struct MlpShieldArgs {
+    MlpArgs m;
+    const float *cstream;       // critic operand stream built by nig_set_mlp_safety
+    float *prob_out;            // [n_steps][>= B] p of the unshielded action (row k at prob_out + k * m.out_stride), may be NULL
+    float threshold;            // shield when !(p < threshold)
+};
+
+// Ensemble actor (rollout_mlp_ensemble_kernel, agents/ensemble.py EnsembleAgent.predict / predict_with_uncertainty): ENS != 0 runs
+// n_members actor passes per step through the same double-buffered LDS image -- member k + 1's layer-1 chunk is in flight while
+// member k's last hidden tile is consumed, the next step's member 0 behind the last member -- and reduces the members' actions
+// p_k (float32, each bit for bit the single actor's) as they arrive, in registers that do not grow with the member count:
+//   action, ENS_AVERAGE ("mean" / "weighted"; float64, the env steps with step_core<Env, NZ, double> where the env has it):
+//       acc = (double)p_0 * w_0;  acc = acc + (double)p_k * w_k  (k = 1 .. K-1, products rounded);  action = acc / wsum
+//   action, ENS_VOTING (np.mean of a float32 array; float32):  acc = p_0;  acc = acc + p_k;  action = acc / (float)K
+//   uncertainty (float32), per action dimension about member 0, d_k = p_k - p_0:
+//       s1 = sum_k d_k,  s2 = sum_k d_k * d_k  (k = 1 .. K-1 in order, from 0),  v = max(s2 - (s1 * s1) / (float)K, 0),
+//       sd = sqrt(v / (float)K);   uncertainty = (sd_0 + sd_1 + ... + sd_{A-1}) / (float)A, summed in index order.
+//   The shifted form needs p_0, s1, s2 and the action's accumulator: 5 A registers (4 A for voting) whatever K is, where the
+//   reference's two-pass np.std needs all K A member actions at once.  It is exactly 0 for identical members, and because member
+//   0's own deviation from the mean is part of v, s2 <= (1 + K) v: the subtraction loses at most a factor 1 + K <= 9 of float32's
+//   precision (measured against np.std: tests/test_ensemble_host.py, 1e-5 relative).
+// Every division and the square root are IEEE correctly rounded: plain `/` and __builtin_sqrtf, which hipcc expands to the
+// v_div_scale / v_div_fmas / v_div_fixup sequences (float32: -fhip-fp32-correctly-rounded-divide-sqrt, the compiler's default,
+// denormals kept) -- the translation unit is compiled with -ffp-contract=off, so no product above fuses into a sum.
+constexpr int ENS_NONE = 0, ENS_AVERAGE = 1, ENS_VOTING = 2;
+struct MlpEnsArgs {
+    MlpArgs m;                  // m.wstream: the members' operand streams, MLP_STREAM_FLOATS floats apart, in member order
+    int n_members;
+    const double *w;            // device [n_members]: the active weights (ENS_AVERAGE)
+    double wsum;                // np.sum of the active weights, computed by the host
+    float kf;                   // (float)n_members
+    float threshold;            // NIG_FLAG_UNCERTAIN when uncertainty > threshold
+    float *unc_out;             // [n_steps][>= B], row k at unc_out + k * m.out_stride, may be NULL
+    float *member_out;          // member k of step it: [A][m.ld_act_out] at member_out + (it * n_members + k) * m.act_step_stride, may be NULL
+};
+
+template <class Env, bool SHIELD, int ENS = ENS_NONE>
+__device__ __attribute__((always_inline)) inline void rollout_mlp_body(const MlpArgs &q, const float *cstream, float *prob_out, float threshold,
+                                                                       [[maybe_unused]] const MlpEnsArgs *eq = nullptr)
+{
+    static_assert(!(SHIELD && ENS != ENS_NONE), "the ensemble has no shield");
+    // the env steps on the ensemble's float64 action where its NumPy arithmetic follows the action's type (nig_step64's rule)
+    constexpr bool ACT64 = ENS == ENS_AVERAGE && Env::HAS_ACT64;
+    using act_t = std::conditional_t<ACT64, double, float>;
+    constexpr int S = Env::S, A = Env::A, KS = Env::KS, KR = Env::KR;
+    constexpr int KSN = KS > 0 ? KS : 1;
+    static_assert(S % 2 == 0 && A <= 16, "MFMA actor needs an even state dim and at most 16 actions");
+    // Weight records are shared by the four waves of the block through LDS: round 1 let every wave stream all
+    // ~1 200 records of a step from L2 on its own (the same 256-byte lines requested by every wave of the chip at
+    // about the same time: 96 TFLOP/s of 155).  Now the block fills a double-buffered LDS image chunk by chunk with
+    // LDS-DMA (global_load_lds_dwordx4: 1 KiB per wave-instruction, no registers), nine fills per step, each wave a
+    // quarter of the pieces, the fill of chunk c+1 in flight while chunk c is consumed; an MFMA's A operand is one
+    // ds_read_b32.  L2 traffic per block and step: 311 KB instead of 4 x 311 KB.
+    __shared__ __attribute__((aligned(16))) float s_w[2][MLP_CHREC * 64];
+    __shared__ float4 s_probit_[mlp_two_blocks<Env> ? 1 : 768];
+    if constexpr (!mlp_two_blocks<Env>) {
+        stage_probit(s_probit_, threadIdx.x, BLOCK);
+        __syncthreads();
+    }
+    const float4 *const s_probit = mlp_two_blocks<Env> ? NIG_PROBIT : s_probit_;
+    const StepArgs &p = q.s;
+    const unsigned tid = threadIdx.x, lane = tid & 63u, half = lane >> 5, e = lane & 31u, wave = tid >> 6;
+    const uint32_t lane0 = blockIdx.x * (BLOCK / 2) + (tid >> 6) * 32u;     // first env of this wave
+    const uint32_t li = lane0 + e;
+    const bool in_range = li < p.B;
+    const bool writer = in_range && half == 0;
+    const uint32_t t_base = (p.t_ptr ? *p.t_ptr : 0u) + p.t_off;
+    const uint64_t gi = p.env0 + (uint64_t)li;
+    const bool autoreset = (p.hflags & NIG_F_AUTORESET) != 0;
+    const bool tally = p.tally != nullptr;
+
+    uint32_t ctr = in_range ? p.ctr[li] : (uint32_t)NIG_CTR_DONE;
+    float s[S], a[A], n[S];
+    typename Env::fast_noise_t nz[KSN];
+#pragma unroll
+    for (int k = 0; k < S; ++k) s[k] = in_range ? (p.state + k * p.ld_state)[li] : 0.0f;
+    double ret = (tally && in_range) ? p.ep_ret[li] : 0.0;
+    LaneTally lt;
+    lt.clear();
+    // fill LDS buffer `buf` with chunk `c` of the operand stream: this wave's quarter of the KiB pieces
+    const float *wsrc = q.wstream;                           // operand stream of the actor (ensemble: of the member) being filled from
+    auto fill = [&](int c, int buf, int pieces) __attribute__((always_inline)) {
+        const float *src = (ENS != ENS_NONE ? wsrc : q.wstream) + (size_t)c * (MLP_CHREC * 64) + lane * 4u;
+        for (int pc = (int)wave; pc < pieces; pc += BLOCK / 64)
+            __builtin_amdgcn_global_load_lds((nig_glb_void *)(src + pc * 256), (nig_lds_void *)(&s_w[buf][pc * 256]), 16, 0, 0);
+    };
+    [[maybe_unused]] auto cfill = [&](int c, int buf, int pieces) __attribute__((always_inline)) {   // the same from the critic's stream
+        const float *src = cstream + (size_t)c * (MLP_CHREC * 64) + lane * 4u;
+        for (int pc = (int)wave; pc < pieces; pc += BLOCK / 64)
+            __builtin_amdgcn_global_load_lds((nig_glb_void *)(src + pc * 256), (nig_lds_void *)(&s_w[buf][pc * 256]), 16, 0, 0);
+    };
+    constexpr int R1 = S / 2 + 1;                            // records per layer-1 tile
+    constexpr int PIECES0 = (MLP_MT * R1 + 3) / 4;           // pieces of chunk 0
+    static_assert(MLP_MT * R1 <= MLP_CHREC, "layer 1 must fit one chunk");
+    constexpr int CL1 = MLP_CL1<Env>, CR1 = MLP_CR1<Env>, CTPC = MLP_MT / CL1;   // critic: layer-1 chunks, records per tile, tiles per chunk
+    constexpr int CPIECES0 = (CTPC * CR1 + 3) / 4;           // pieces of a critic layer-1 chunk
+    static_assert(CTPC * CR1 <= MLP_CHREC, "a critic layer-1 chunk must fit one chunk slot");
+    fill(0, 0, PIECES0);
+    int gbuf = 0;                                            // buffer that holds (or receives) the chunk consumed next
+    const int n_members = ENS != ENS_NONE ? eq->n_members : 1;
+    for (int it = 0; it < q.n_steps; ++it) {
+        [[maybe_unused]] float e_p0[A], e_s1[A], e_s2[A], e_f[A];   // ensemble: member 0, sum d, sum d^2, float32 action sum
+        [[maybe_unused]] double e_d[A];                            // ensemble: float64 weighted action sum
+        int mem = 0;
+        do {                                                       // (one pass unless ENS)
+        // ---------------- actor: 3 layers of f32 MFMA, whole wave (EXEC all ones) ----------------
+        // chunk boundary: every wave's share of the fill has landed (the compiler drains vmcnt before the barrier)
+        // and every wave is done with the buffer the next fill overwrites
+        __syncthreads();
+#if defined(NIG_DIAG_MLP_SKIP) && (NIG_DIAG_MLP_SKIP & 2)
+        if (it == 0)
+#endif
+        fill(1, gbuf ^ 1, MLP_PIECES);
+        f32x16 h1[MLP_MT];
+        {
+            const float *wb = &s_w[gbuf][lane];
+#pragma unroll
+            for (int m = 0; m < MLP_MT; ++m) {
+                f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+                for (int ks = 0; ks < S / 2; ++ks) {
+                    const float b = half ? s[2 * ks + 1] : s[2 * ks];
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[(m * R1 + ks) * 64], b, acc, 0, 0, 0);
+                }
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[(m * R1 + R1 - 1) * 64], half ? 0.0f : 1.0f, acc, 0, 0, 0);   // + b1
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[r] = fmaxf(acc[r], 0.0f);                                   // ReLU
+                h1[m] = acc;
+            }
+        }
+        gbuf ^= 1;
+        f32x16 out = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        [[maybe_unused]] f32x4 out4 = {0, 0, 0, 0};          // mlp_head4: this lane half's partial sums of the (<= 4) head rows
+        constexpr int RING = 8;                             // LDS reads in flight ahead of their MFMA (~64 cycles apart)
+        for (int m2 = 0; m2 < MLP_MT; ++m2) {               // a real loop: the body is 145 MFMAs of straight-line code
+            __syncthreads();                                // chunk 1 + m2 is in s_w[gbuf]; s_w[gbuf ^ 1] is free
+#if defined(NIG_DIAG_MLP_SKIP) && (NIG_DIAG_MLP_SKIP & 2)     // (diagnostic, WRONG results: no LDS-DMA traffic after the first step)
+            if (it == 0) {
+#endif
+            if (m2 + 1 < MLP_MT) fill(2 + m2, gbuf ^ 1, MLP_PIECES);
+            else if constexpr (SHIELD) cfill(0, gbuf ^ 1, CPIECES0);  // the critic's layer 1 follows the actor
+            else if constexpr (ENS != ENS_NONE) {                     // layer 1 of the next member, or of member 0 for the next step
+                const bool more = mem + 1 < n_members;
+                wsrc = more ? wsrc + MLP_STREAM_FLOATS : q.wstream;
+                if (more || it + 1 < q.n_steps) fill(0, gbuf ^ 1, PIECES0);
+            }
+            else if (it + 1 < q.n_steps) fill(0, gbuf ^ 1, PIECES0);   // layer 1 of the NEXT step (the weights do not change)
+#if defined(NIG_DIAG_MLP_SKIP) && (NIG_DIAG_MLP_SKIP & 2)
+            }
+#endif
+            const float *wb = &s_w[gbuf][lane];
+            f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+            float ring[RING];
+#pragma unroll
+            for (int j = 0; j < RING; ++j) ring[j] = wb[j * 64];
+#pragma unroll
+            for (int i = 0; i < MLP_PER; ++i) {
+                const float aop = ring[i % RING];
+                if (i + RING < MLP_PER + 1) ring[i % RING] = wb[(i + RING) * 64];       // (+1: the head's bias record of the last chunk)
+                // pin the source order: hipcc's scheduler otherwise sinks every read to just before its use
+                __builtin_amdgcn_sched_barrier(0);
+                if (i < MLP_MT * 16) {
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aop, h1[i / 16][i % 16], acc, 0, 0, 0);
+                } else if (i == MLP_MT * 16) {
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aop, half ? 0.0f : 1.0f, acc, 0, 0, 0);      // + b2
+                } else if constexpr (mlp_head4<Env>) {  // this h2 tile is consumed at once by the head: 4 x 4 x 1, own value x the block's weights
+                    out4 = __builtin_amdgcn_mfma_f32_4x4x1f32(aop, fmaxf(acc[i - MLP_MT * 16 - 1], 0.0f), out4, 0, 0, 0);
+                } else {                                // 16 x 16 x 1, four blocks: own value x the block's sixteen weights
+                    out = __builtin_amdgcn_mfma_f32_16x16x1f32(aop, fmaxf(acc[i - MLP_MT * 16 - 1], 0.0f), out, 0, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (m2 + 1 == MLP_MT) {                          // record 145 of the last chunk: + b3
+                if constexpr (mlp_head4<Env>) out4 = __builtin_amdgcn_mfma_f32_4x4x1f32(ring[MLP_PER % RING], half ? 0.0f : 1.0f, out4, 0, 0, 0);
+                else out = __builtin_amdgcn_mfma_f32_16x16x1f32(ring[MLP_PER % RING], half ? 0.0f : 1.0f, out, 0, 0, 0);
+            }
+            gbuf ^= 1;
+        }
+        if constexpr (mlp_head4<Env>) {
+            // action r = this half's partial sum + the other half's (lane l and l + 32 carry the same env)
+#pragma unroll
+            for (int r = 0; r < A; ++r) a[r] = det_tanhf(out4[r] + __shfl_xor(out4[r], 32));
+        } else {
+            // head row r of env column c (env 16 beta + c, beta = block parity): lane 16 (r >> 2) + c, registers 4 beta + (r & 3)
+            // (lane half 0's chain) and 8 + 4 beta + (r & 3) (lane half 1's); hand every lane all A rows of its env
+            const int beta = (int)(e >> 4);
+#pragma unroll
+            for (int r = 0; r < A; ++r) {
+                const int src = 16 * (r >> 2) + (int)(e & 15u);
+                const float v0 = __shfl(out[r & 3] + out[8 + (r & 3)], src);
+                const float v1 = __shfl(out[4 + (r & 3)] + out[12 + (r & 3)], src);
+                a[r] = det_tanhf(beta ? v1 : v0);
+            }
+        }
+        if constexpr (ENS != ENS_NONE) {                     // fold member `mem` into the running sums (the law above)
+            if (writer && !(ctr & NIG_CTR_DONE) && eq->member_out) {
+                float *mo = eq->member_out + ((size_t)it * (size_t)n_members + (size_t)mem) * q.act_step_stride;
+#pragma unroll
+                for (int j = 0; j < A; ++j) (mo + j * q.ld_act_out)[li] = a[j];
+            }
+            if (mem == 0) {
+#pragma unroll
+                for (int j = 0; j < A; ++j) {
+                    e_p0[j] = a[j]; e_s1[j] = 0.0f; e_s2[j] = 0.0f;
+                    if constexpr (ENS == ENS_AVERAGE) e_d[j] = (double)a[j] * eq->w[0]; else e_f[j] = a[j];
+                }
+            } else {
+                [[maybe_unused]] const double wk = ENS == ENS_AVERAGE ? eq->w[mem] : 0.0;
+#pragma unroll
+                for (int j = 0; j < A; ++j) {
+                    const float d = a[j] - e_p0[j];
+                    e_s1[j] = e_s1[j] + d; e_s2[j] = e_s2[j] + d * d;
+                    if constexpr (ENS == ENS_AVERAGE) e_d[j] = e_d[j] + (double)a[j] * wk; else e_f[j] = e_f[j] + a[j];
+                }
+            }
+        }
+        } while (ENS != ENS_NONE && ++mem < n_members);
+        [[maybe_unused]] float unc = 0.0f;
+        [[maybe_unused]] bool uncertain = false;
+        [[maybe_unused]] double a64[ACT64 ? A : 1];
+        if constexpr (ENS != ENS_NONE) {                     // once per step: the ensemble's action, its uncertainty, the flag bit
+            const float kf = eq->kf;
+            float usum = 0.0f;
+#pragma unroll
+            for (int j = 0; j < A; ++j) {
+                float v = e_s2[j] - (e_s1[j] * e_s1[j]) / kf;
+                v = v > 0.0f ? v : 0.0f;
+                usum = usum + __builtin_sqrtf(v / kf);
+                if constexpr (ENS == ENS_AVERAGE) {
+                    const double x = e_d[j] / eq->wsum;
+                    if constexpr (ACT64) a64[j] = x;
+                    a[j] = (float)x;                         // act_out's word; the action itself for envs that take float32 (nig_step64's rule)
+                } else a[j] = e_f[j] / kf;
+            }
+            unc = usum / (float)A;
+            uncertain = unc > eq->threshold;
+        }
+        [[maybe_unused]] bool shield = false;
+        [[maybe_unused]] float prob = 0.0f;
+        if constexpr (SHIELD) {
+            // ---------------- safety critic on x = [s, a, 0]: the same three-layer scheme, one-row head ----------------
+            auto x = [&](int k) __attribute__((always_inline)) { return k < S ? s[k] : (k < S + A ? a[k - S] : 0.0f); };
+            f32x16 g1[MLP_MT];
+#pragma unroll
+            for (int c1 = 0; c1 < CL1; ++c1) {
+                __syncthreads();                            // critic layer-1 chunk c1 is in s_w[gbuf]
+                if (c1 + 1 < CL1) cfill(c1 + 1, gbuf ^ 1, CPIECES0);
+                else cfill(CL1, gbuf ^ 1, MLP_PIECES);
+                const float *wb = &s_w[gbuf][lane];
+#pragma unroll
+                for (int mm = 0; mm < CTPC; ++mm) {
+                    f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+                    for (int ks = 0; ks < CR1 - 1; ++ks)
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[(mm * CR1 + ks) * 64], half ? x(2 * ks + 1) : x(2 * ks), acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[(mm * CR1 + CR1 - 1) * 64], half ? 0.0f : 1.0f, acc, 0, 0, 0);   // + c1
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[r] = fmaxf(acc[r], 0.0f);
+                    g1[c1 * CTPC + mm] = acc;
+                }
+                gbuf ^= 1;
+            }
+            f32x4 z4 = {0, 0, 0, 0};
+            constexpr int RING = 8;
+            for (int m2 = 0; m2 < MLP_MT; ++m2) {
+                __syncthreads();                            // critic chunk CL1 + m2 is in s_w[gbuf]
+                if (m2 + 1 < MLP_MT) cfill(CL1 + 1 + m2, gbuf ^ 1, MLP_PIECES);
+                else if (it + 1 < q.n_steps) fill(0, gbuf ^ 1, PIECES0);   // the actor's layer 1 of the NEXT step
+                const float *wb = &s_w[gbuf][lane];
+                f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                float ring[RING];
+#pragma unroll
+                for (int j = 0; j < RING; ++j) ring[j] = wb[j * 64];
+#pragma unroll
+                for (int i = 0; i < MLP_PER; ++i) {
+                    const float aop = ring[i % RING];
+                    if (i + RING < MLP_PER + 1) ring[i % RING] = wb[(i + RING) * 64];
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (i < MLP_MT * 16)
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aop, g1[i / 16][i % 16], acc, 0, 0, 0);
+                    else if (i == MLP_MT * 16)
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aop, half ? 0.0f : 1.0f, acc, 0, 0, 0);      // + c2
+                    else
+                        z4 = __builtin_amdgcn_mfma_f32_4x4x1f32(aop, fmaxf(acc[i - MLP_MT * 16 - 1], 0.0f), z4, 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if (m2 + 1 == MLP_MT) z4 = __builtin_amdgcn_mfma_f32_4x4x1f32(ring[MLP_PER % RING], half ? 0.0f : 1.0f, z4, 0, 0, 0);   // + c3
+                gbuf ^= 1;
+            }
+            prob = det_sigmoidf(z4[0] + __shfl_xor(z4[0], 32));
+            shield = !(prob < threshold);
+#pragma unroll
+            for (int r = 0; r < A; ++r) a[r] = shield ? a[r] * 0.5f : a[r];
+        }
+
+#if defined(NIG_DIAG_MLP_SKIP) && (NIG_DIAG_MLP_SKIP & 1)     // (diagnostic builds only, WRONG results: the actor without the env step)
+#pragma unroll
+        for (int k = 0; k < S; ++k) s[k] = __builtin_fmaf(1e-9f, a[k % A], s[k]);
+        continue;
+#endif
+        // ---------------- IndustrialEnv.step (both lane halves, identical results) ----------------
+        const uint32_t orow = (uint32_t)it * q.out_stride;
+        const bool frozen = (ctr & NIG_CTR_DONE) != 0;
+        if (writer && !frozen) {
+            if (q.obs_out) {
+                float *oo = q.obs_out + (size_t)it * q.obs_step_stride + (size_t)li * S;
+                if constexpr (S % 4 == 0) {
+#pragma unroll
+                    for (int k = 0; k < S / 4; ++k) store16(oo + 4 * k, s[4 * k], s[4 * k + 1], s[4 * k + 2], s[4 * k + 3]);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < S; ++k) oo[k] = s[k];
+                }
+            }
+            if (q.act_out) {
+                float *ao = q.act_out + (size_t)it * q.act_step_stride;
+#pragma unroll
+                for (int j = 0; j < A; ++j) (ao + j * q.ld_act_out)[li] = a[j];
+            }
+            if constexpr (SHIELD) {
+                if (prob_out) (prob_out + (uint32_t)it * q.out_stride)[li] = prob;
+            }
+            if constexpr (ENS != ENS_NONE) {
+                if (eq->unc_out) (eq->unc_out + (uint32_t)it * q.out_stride)[li] = unc;
+            }
+        }
+        const RngKey key = make_key(gi, t_base + (uint32_t)it + 1u, p.seed_lo, p.seed_hi, s_probit);
+        if constexpr (KS > 0) Env::draw_step(key, nz); else nz[0] = 0;
+        const int step_pre = (int)(ctr & NIG_CTR_STEP_MASK);
+        StepResult<Env, reward_of<Env, act_t>> res;
+        if constexpr (ACT64) step_core<Env>(s, a64, nz, step_pre, p.max_steps, p.dt32, p.dt, p.cmask, n, res);
+        else step_core<Env>(s, a, nz, step_pre, p.max_steps, p.dt32, p.dt, p.cmask, n, res);
+        const int step = step_pre + 1;
+        const uint32_t viol_ep = episode_violations(ctr, res.nviol);
+        const bool done = (res.terminated || res.truncated) && !frozen;
+        uint32_t fl = pack_flags<Env>(res, step) | did_reset_flag(done && autoreset);
+        if constexpr (SHIELD) fl |= shield ? NIG_FLAG_SHIELDED : 0u;
+        if constexpr (ENS != ENS_NONE) fl |= uncertain ? NIG_FLAG_UNCERTAIN : 0u;
+        float rew = (float)res.reward;
+        if (frozen) {
+            fl = NIG_FLAG_INACTIVE | ((ctr & NIG_CTR_STEP_MASK) << NIG_FLAG_STEP_SHIFT);
+            rew = 0.0f;
+#pragma unroll
+            for (int k = 0; k < S; ++k) n[k] = s[k];
+        } else {
+            ctr = counter_word(step, viol_ep);
+            if (tally) ret = add_reward<Env, ACT64>(ret, res.reward);
+        }
+        if (writer) {
+            if (p.reward) (p.reward + orow)[li] = rew;
+            if (p.flags) (p.flags + orow)[li] = fl;
+        }
+        if (done) {
+            ret = lt.finish(tally, ret, step, viol_ep, res.ncrit);
+            if (autoreset) {
+                double rn[KR > 0 ? KR : 1];
+                Env::draw_init(key, rn);
+                Env::init(rn, n);
+                ctr = 0u;
+            } else {
+                ctr |= NIG_CTR_DONE;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < S; ++k) s[k] = n[k];
+    }
+    if (!writer) return;
+#pragma unroll
+    for (int k = 0; k < S; ++k) (p.state + k * p.ld_state)[li] = s[k];
+    store_episode(p.ctr, p.life_viol, p.ep_ret, p.tally, p.ld, p.n_en, 0u, li, tally, ctr, lt.life, ret, lt);   // (row offset 0: `li` counts from the batch's first lane)
+}
+
+template <class Env>
+__global__ void __launch_bounds__(BLOCK, mlp_two_blocks<Env> ? 2 : 1) rollout_mlp_kernel(const MlpArgs q)
+{
+    rollout_mlp_body<Env, false>(q, nullptr, nullptr, 0.0f);
+}
+
+template <class Env>
+__global__ void __launch_bounds__(BLOCK, mlp_two_blocks<Env> ? 2 : 1) rollout_mlp_shield_kernel(const MlpShieldArgs q)
+{
+    rollout_mlp_body<Env, true>(q.m, q.cstream, q.prob_out, q.threshold);
+}
+
+// ENS = ENS_AVERAGE / ENS_VOTING.  Instantiated in the env's ensemble_*.hip translation unit only (launch_mlp_ensemble_env).
+template <class Env, int ENS>
+__global__ void __launch_bounds__(BLOCK, mlp_two_blocks<Env> ? 2 : 1) rollout_mlp_ensemble_kernel(const MlpEnsArgs q)
+{
+    rollout_mlp_body<Env, false, ENS>(q.m, nullptr, nullptr, 0.0f, &q);
+}
+
+}  // namespace nig

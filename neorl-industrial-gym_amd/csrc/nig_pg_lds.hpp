@@ -25,6 +25,9 @@
 // Whole 512-lane blocks of an auto-reset handle without frozen lanes only; the host keeps every other case on
 // rollout_kernel.
 #pragma once
+#include "nig_policy.hpp"
+#include "nig_ring.hpp"
+#include "nig_rollout.hpp"
 
 namespace nig {
 

@@ -1,6 +1,7 @@
 // nig_ring.hpp -- LDS ring counters shared by the cooperating-wave kernels (nig_split.hpp, nig_split_policy.hpp, the
 // paired PowerGrid form of nig_pg_lds.hpp).  Included by nig_kernels.hpp.
 #pragma once
+#include "nig_device.hpp"
 
 namespace nig {
 

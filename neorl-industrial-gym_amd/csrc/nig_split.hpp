@@ -28,6 +28,8 @@
 // (tests/test_gpu_parity.py, tests/test_spec_envs.py: the fused-rollout tests run this form wherever it applies,
 // tests/test_gpu_split.py pins it against the one-wave form).
 #pragma once
+#include "nig_ring.hpp"
+#include "nig_rollout.hpp"
 
 namespace nig {
 

@@ -13,6 +13,8 @@
 //                acted on, row-major through the transposing image; the policy's action rows).
 // Bit-identical to rollout_policy_kernel (tests/test_gpu_split.py).
 #pragma once
+#include "nig_policy.hpp"
+#include "nig_ring.hpp"
 
 namespace nig {
 

@@ -162,7 +162,7 @@ def test_split_form_robot_assembly_long_run_at_full_size(ni):
 @pytest.mark.parametrize("B", [1024, 1000])
 def test_step_api_helper_waves_equal_the_plain_step_kernel(ni, name, B):
     """The step API at one wave per SIMD launches step_kernel with HELPER waves (restart states, the generator's table and,
-    for PowerGrid, the tally flush prepared beside the step: csrc/nig_kernels.hpp step_kernel, HELP); the knob at 0 keeps
+    for PowerGrid, the tally flush prepared beside the step: csrc/nig_step_kernel.hpp step_kernel, HELP); the knob at 0 keeps
     the plain kernel with its cooperative reset.  60 steps of 9-step episodes through both, whole blocks and a ragged
     last block: every per-step reward / flag row, the final state, counters, lifetime violations, returns and tallies
     are bit-identical."""

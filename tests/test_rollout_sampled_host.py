@@ -3,7 +3,7 @@ without a device can check it.
 
   * the export: declared in include/nig.h, listed in _lib.SYMBOLS, present in libnig.so, and refusing a NULL handle;
   * the action mapping: the kernels do not evaluate fill_actions_kernel's float64 expression
-    (float)(low + (high - low) * u), u = m * 2^-24, but csrc/nig_kernels.hpp action_from_word -- restated here in NumPy and
+    (float)(low + (high - low) * u), u = m * 2^-24, but csrc/nig_step.hpp action_from_word -- restated here in NumPy and
     compared with the float64 form over ALL 2^24 values of m, for every distinct (low, high) pair of the envs' action Boxes;
   * the generated ISA (same flags as tests/test_ring_isa.py): the sampled three-wave ChemicalReactor kernel and the sampled
     wide PowerGrid kernels hold no global load inside their step loops, and use no more scratch than their ring-fed twins."""
@@ -63,7 +63,7 @@ def action_boxes():
 
 
 def kernel_action_from_m(m, low, high):
-    """csrc/nig_kernels.hpp action_from_word on the word's top 24 bits, operation by operation in float32.
+    """csrc/nig_step.hpp action_from_word on the word's top 24 bits, operation by operation in float32.
     [-1, 1): fmaf(mf, 2^-23, -1) -- a fused multiply-add rounds the exact sum once; the exact sum is formed in float64 here
     (24-bit integer times a power of two, minus one: exact) and narrowed, which is that one rounding.
     low == 0: the float32 product high * (mf * 2^-24).
@@ -119,7 +119,7 @@ def test_action_mapping_equals_the_float64_form_for_every_word(box):
 
 def test_source_states_the_forms_the_test_restates():
     """the restatement above is of THIS text: if action_from_word changes, this test must be looked at again"""
-    src = open(os.path.join(CSRC, "nig_kernels.hpp")).read()
+    src = open(os.path.join(CSRC, "nig_step.hpp")).read()
     body = src[src.index("float action_from_word("):]
     body = body[:body.index("\n}\n")]
     assert "__builtin_fmaf(mf, 1.0f / 8388608.0f, -1.0f)" in body and "low == -1.0f && high == 1.0f" in body
