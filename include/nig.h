@@ -561,6 +561,60 @@ int nig_rollout_mlp_ensemble(nig_handle *h, int32_t n_steps, float *reward_out, 
                              float *member_act_out, void *stream);
 
 /*
+ * Sensor / actuator noise inside the closed loop ("nig-disturb-v1"): the policy sees a noisy observation, the plant
+ * receives a noisy action.  Stands in for the observation_noise / action_noise runs of the reference's
+ * RobustnessBenchmark (benchmarks/industrial_benchmarks.py:455-573) and for predict(obs, deterministic=False) of
+ * CQL / IQL / TD3BC, clip(actor + 0.1 N(0,1), -1, 1) (agents/cql.py:345-350).
+ * For a live lane with global index g, on the step with launch counter t, step_pre = the lane's step count before the
+ * step; float32 throughout, every product rounded before its sum:
+ *     td = (hold == NIG_HOLD_EPISODE) ? t - step_pre : t          uint32; the counter the episode's first step had
+ *     zo[0..S) = normals of generator stream "policy", blocks +32.. at key (g, td, seed): normal k = word k & 3 of block
+ *                +32 + (k >> 2);   za[0..A) = the same of blocks +48..
+ *     o_k = s_k + sigma_obs[k] * zo_k                             if any sigma_obs[k] != 0, else o = s (no draw is made)
+ *     u   = policy(o)                                             nig_rollout_policy_disturbed: the whole "nig-policy-v1" law
+ *                                                                 on o (PID: e = setpoint - o), its own draws keyed at t, its
+ *                                                                 own clip; nig_rollout_mlp_disturbed: the actor with its tanh
+ *     u_j = u_j + sigma_act[j] * za_j                             if any sigma_act[j] != 0
+ *     a_j = u_j < clip_lo ? clip_lo : u_j;  a_j = a_j > clip_hi ? clip_hi : a_j
+ *     IndustrialEnv.step(a) unchanged (the env's own clip follows).
+ * The policy stream's own blocks (+0 mixture draw, +1.. normals, +8.. uniform noise, +16.. random action) stay where they
+ * are, keyed at t.  NIG_HOLD_EPISODE is upstream's law: the reference calls jax.random.normal(episode_key, ...) with the same
+ * key on every step of an episode (industrial_benchmarks.py:492-508), i.e. one offset per episode.
+ */
+#define NIG_HOLD_STEP 0      /* fresh draws every step */
+#define NIG_HOLD_EPISODE 1   /* one draw vector per episode, reused on each of its steps: upstream's law */
+typedef struct nig_disturbance {
+    float sigma_obs[NIG_MAX_STATE_DIM];   /* >= 0, finite */
+    float sigma_act[NIG_MAX_ACTION_DIM];  /* >= 0, finite */
+    float clip_lo, clip_hi;               /* -inf / +inf = no clip; clip_lo <= clip_hi */
+    int32_t hold;
+} nig_disturbance;
+
+/* Install (copy) the disturbance the _disturbed rollouts apply; d == NULL removes it.  NIG_ERR_INVALID, the installed one
+ * kept: a negative / NaN / infinite sigma, clip_lo > clip_hi or a NaN bound, an unknown hold.  Only the two entry points
+ * below read it: nig_rollout_policy, nig_rollout_mlp, nig_rollout_mlp_safe and nig_rollout_mlp_ensemble ignore an installed
+ * disturbance (the shield and the ensemble have no disturbed form). */
+int nig_set_disturbance(nig_handle *h, const nig_disturbance *d /* host; NULL clears */, void *stream);
+
+/*
+ * nig_rollout_policy / nig_rollout_mlp (arguments, minima, alignment, frozen lanes, tallies, launch counter) under the
+ * installed disturbance.  obs_out holds the TRUE state s, act_out the action a the env received, and
+ *   seen_out  optional float row-major [n_steps][B][S]: the observation o the policy acted on, step k at
+ *             seen_out + k*seen_step_stride; obs_out's rules (16-byte aligned, stride >= S*B and a multiple of 4 floats);
+ *             frozen lanes leave their rows untouched.
+ * With all sigmas zero and infinite clip bounds a call equals its undisturbed twin bit for bit (seen_out == obs_out).
+ * nig_rollout_policy_disturbed always runs the one-wave closed-loop kernel, whatever the batch.
+ * NIG_ERR_INVALID (nothing launched or written): no disturbance installed, no policy / actor installed, and every
+ * refusal of the twin.  NIG_ERR_UNSUPPORTED: nig_rollout_mlp_disturbed on an env shape without the MFMA actor.
+ */
+int nig_rollout_policy_disturbed(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                                 float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
+                                 int64_t act_step_stride, float *seen_out, int64_t seen_step_stride, void *stream);
+int nig_rollout_mlp_disturbed(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                              float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
+                              int64_t act_step_stride, float *seen_out, int64_t seen_step_stride, void *stream);
+
+/*
  * Host-buffer forms for SMALL batches -- the single-env drop-in classes (env.reset() / env.step()
  * return NumPy arrays, base.py:133-213).  Inputs are host arrays, results are copied back to host
  * arrays; the library stages through pinned memory it owns and synchronises `stream` once before

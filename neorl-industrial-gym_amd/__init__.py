@@ -21,6 +21,7 @@ from .envs import (AdvancedChemicalReactorEnv, AdvancedPowerGridEnv, ChemicalRea
 from .policies import (DevicePolicy, EnsemblePolicy, MLPPolicy, behaviour_policy, constant_agent, mpc_agent,  # noqa: E402
                        pid_agent, random_agent)
 from .utils import evaluate_with_safety, make, make_batched, uniform_action_statistics  # noqa: E402
+from .disturbance import Disturbance, Disturbed, evaluate_robustness, robustness_scores  # noqa: E402
 
 def tune(split_blocks=None, wide_min_blocks=None):
     """Process-wide kernel-selection knobs of libnig (include/nig.h nig_tune); results never depend on them.
@@ -45,5 +46,5 @@ __all__ = [
     "ChemicalReactorEnv", "PowerGridEnv", "RobotAssemblyEnv", "AdvancedChemicalReactorEnv", "AdvancedPowerGridEnv",
     "HVACControlEnv", "WaterTreatmentEnv", "SteelAnnealingEnv", "SupplyChainEnv", "BatchedIndustrialEnv", "MixedBatchedEnv", "StepInfo",
     "make", "make_batched", "evaluate_with_safety", "uniform_action_statistics", "tune", "DevicePolicy", "MLPPolicy", "EnsemblePolicy", "behaviour_policy", "constant_agent",
-    "mpc_agent", "pid_agent", "random_agent",
+    "mpc_agent", "pid_agent", "random_agent", "Disturbance", "Disturbed", "evaluate_robustness", "robustness_scores",
 ]

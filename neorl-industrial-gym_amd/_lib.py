@@ -37,7 +37,7 @@ SYMBOLS = [
     "nig_version", "nig_last_error", "nig_env_id", "nig_env_name", "nig_env_spec_get", "nig_layout_query",
     "nig_create", "nig_destroy", "nig_get_layout", "nig_workspace", "nig_get_counter", "nig_set_counter",
     "nig_set_constraint_mask", "nig_reset", "nig_step", "nig_fill_actions", "nig_set_state", "nig_get_state",
-    "nig_get_safety_metrics", "nig_reduce_tally", "nig_plan_create", "nig_plan_launch", "nig_plan_destroy", "nig_rollout", "nig_rollout_sampled", "nig_rollout_noise", "nig_bind_state", "nig_set_policy", "nig_rollout_policy", "nig_set_mlp_policy", "nig_rollout_mlp", "nig_set_mlp_safety", "nig_rollout_mlp_safe", "nig_set_mlp_ensemble", "nig_rollout_mlp_ensemble", "nig_reset_host", "nig_step_host",
+    "nig_get_safety_metrics", "nig_reduce_tally", "nig_plan_create", "nig_plan_launch", "nig_plan_destroy", "nig_rollout", "nig_rollout_sampled", "nig_rollout_noise", "nig_bind_state", "nig_set_policy", "nig_rollout_policy", "nig_set_mlp_policy", "nig_rollout_mlp", "nig_set_mlp_safety", "nig_rollout_mlp_safe", "nig_set_mlp_ensemble", "nig_rollout_mlp_ensemble", "nig_set_disturbance", "nig_rollout_policy_disturbed", "nig_rollout_mlp_disturbed", "nig_reset_host", "nig_step_host",
     "nig_step64", "nig_step_host64", "nig_reduce_metrics",
     "nig_create_mixed", "nig_mixed_destroy", "nig_mixed_get_info", "nig_mixed_state", "nig_mixed_segment", "nig_mixed_reset",
     "nig_mixed_fill_actions", "nig_mixed_rollout", "nig_rollout_mixed", "nig_mixed_step", "nig_rollout_mixed_obs", "nig_mixed_rollout_obs",
@@ -67,6 +67,13 @@ class Policy(C.Structure):
 
 
 POLICY_AFFINE, POLICY_PID = 1, 2
+HOLD_STEP, HOLD_EPISODE = 0, 1
+
+
+class DisturbanceStruct(C.Structure):
+    """nig_disturbance (include/nig.h, "nig-disturb-v1")."""
+    _fields_ = [("sigma_obs", C.c_float * 32), ("sigma_act", C.c_float * 10), ("clip_lo", C.c_float), ("clip_hi", C.c_float),
+                ("hold", C.c_int32)]
 
 
 MIXED_MAX_SEGMENTS = 12
@@ -147,6 +154,9 @@ def lib():
     L.nig_rollout_mlp_safe.argtypes = [vp, i32, vp, vp, i64, vp, i64, vp, i64, i64, vp, vp]
     L.nig_set_mlp_ensemble.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, C.c_double, C.c_float, vp]
     L.nig_rollout_mlp_ensemble.argtypes = [vp, i32, vp, vp, i64, vp, i64, vp, i64, i64, vp, vp, vp]
+    L.nig_set_disturbance.argtypes = [vp, C.POINTER(DisturbanceStruct), vp]
+    L.nig_rollout_policy_disturbed.argtypes = [vp, i32, vp, vp, i64, vp, i64, vp, i64, i64, vp, i64, vp]
+    L.nig_rollout_mlp_disturbed.argtypes = [vp, i32, vp, vp, i64, vp, i64, vp, i64, i64, vp, i64, vp]
     L.nig_reset_host.argtypes = [vp, vp, vp, vp]
     L.nig_step_host.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.nig_step_host64.argtypes = [vp, vp, vp, vp, vp, vp, vp]

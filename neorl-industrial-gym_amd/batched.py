@@ -135,6 +135,7 @@ class BatchedIndustrialEnv:
             available = ", ".join(ENV_IDS.keys())
             raise ValueError(f"Unknown environment '{env_id}'. Available: {available}")
         self.env_id = env_id
+        self.seed, self.env_index0 = int(seed), int(env_index0)
         self._eid = ENV_IDS[env_id]
         self._L = _lib.lib()
         self.spec = _lib.env_spec(self._eid)
@@ -529,6 +530,40 @@ class BatchedIndustrialEnv:
         rp, fp, os_, op, so, ap, lda, sa = self._closed_loop_outputs(n_steps, reward_out, flags_out, obs_out, act_out)
         with torch.cuda.device(self._dev_index):
             _lib.check(self._L.nig_rollout_policy(self._h, int(n_steps), rp, fp, os_, op, so, ap, lda, sa, self._stream()))
+
+    # ------------------------------------------------------------------
+    def set_disturbance(self, disturbance):
+        """Install the sensor / actuator noise (disturbance.Disturbance) the _disturbed rollouts apply; None removes it.
+        The other rollouts ignore it."""
+        with torch.cuda.device(self._dev_index):
+            if disturbance is None:
+                _lib.check(self._L.nig_set_disturbance(self._h, None, self._stream()))
+            else:
+                D = disturbance.to_struct(self.state_dim, self.action_dim) if hasattr(disturbance, "to_struct") else disturbance
+                _lib.check(self._L.nig_set_disturbance(self._h, C.byref(D), self._stream()))
+        self._disturbance = disturbance
+
+    def _seen_rows(self, n_steps, seen_out):
+        if seen_out is None:
+            return None, 0
+        assert seen_out.dtype == torch.float32 and seen_out.is_contiguous()
+        assert seen_out.shape[0] >= n_steps and seen_out.shape[1:] == (self.batch, self.state_dim)
+        return C.c_void_p(seen_out.data_ptr()), seen_out.stride(0)
+
+    def rollout_policy_disturbed(self, n_steps: int, reward_out=None, flags_out=None, obs_out=None, act_out=None, seen_out=None):
+        """rollout_policy() under the installed disturbance ("nig-disturb-v1"): obs_out holds the TRUE state, seen_out
+        (float32 contiguous [n_steps, B, S]) the noisy observation the policy acted on, act_out the action the env received."""
+        rp, fp, os_, op, so, ap, lda, sa = self._closed_loop_outputs(n_steps, reward_out, flags_out, obs_out, act_out)
+        sp, ss = self._seen_rows(n_steps, seen_out)
+        with torch.cuda.device(self._dev_index):
+            _lib.check(self._L.nig_rollout_policy_disturbed(self._h, int(n_steps), rp, fp, os_, op, so, ap, lda, sa, sp, ss, self._stream()))
+
+    def rollout_mlp_disturbed(self, n_steps: int, reward_out=None, flags_out=None, obs_out=None, act_out=None, seen_out=None):
+        """rollout_mlp() under the installed disturbance; outputs as rollout_policy_disturbed()."""
+        rp, fp, os_, op, so, ap, lda, sa = self._closed_loop_outputs(n_steps, reward_out, flags_out, obs_out, act_out)
+        sp, ss = self._seen_rows(n_steps, seen_out)
+        with torch.cuda.device(self._dev_index):
+            _lib.check(self._L.nig_rollout_mlp_disturbed(self._h, int(n_steps), rp, fp, os_, op, so, ap, lda, sa, sp, ss, self._stream()))
 
     def get_dataset(self, quality: str = "mixed", scale: int = 1, chunk: int = 100):
         """Batched env.get_dataset(quality): every lane is one episode of the reference's

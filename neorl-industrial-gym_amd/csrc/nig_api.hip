@@ -178,6 +178,7 @@ struct nig_handle {
     float mlp_threshold = 0.0f;      // shield threshold of nig_rollout_mlp_safe
     // nig_set_mlp_ensemble (owned): the members' operand streams back to back, MLP_STREAM_FLOATS floats each; their active weights
     float *ens_stream = nullptr; double *ens_w = nullptr; int ens_members = 0, ens_cap = 0, ens_method = 0; double ens_wsum = 0.0; float ens_threshold = 0.0f;
+    nig_disturbance dist = {}; bool has_dist = false;      // nig_set_disturbance: what the _disturbed rollouts apply
     float *act32 = nullptr;    // nig_step64 on an env that takes float32 actions: the narrowed rows [A][ld] (owned, lazy)
     float *pid_mem = nullptr;  // PID policies: per-lane integral / previous error, float [2*A][ld] (owned, lazy)
     bool may_hold_done = true; // some lane may carry NIG_CTR_DONE although the handle auto-resets (see HF_MAY_HOLD_DONE)
@@ -379,10 +380,16 @@ struct ClosedLoopOut {
     float *obs; int64_t obs_step_stride;
     float *act; int64_t ld_act, act_step_stride;
 };
+// A row-major [n_steps][B][S] trajectory (obs_out, seen_out): 16-byte aligned, rows of step k at k * step_stride >= S * batch floats,
+// a multiple of 4 (there is no "overwrite" form)
+static int check_state_rows(const nig_handle *h, const char *fn, const float *rows, int64_t step_stride, const char *refusal)
+{
+    if (rows && (step_stride < (int64_t)SPECS[h->env].state_dim * h->B || (step_stride & 3) || ((uintptr_t)rows & 15))) return refuse(fn, refusal);
+    return NIG_OK;
+}
 static int check_closed_loop(const nig_handle *h, const char *fn, const ClosedLoopOut &o)
 {
-    if (o.obs && (o.obs_step_stride < (int64_t)SPECS[h->env].state_dim * h->B || (o.obs_step_stride & 3) || ((uintptr_t)o.obs & 15)))
-        return refuse(fn, "obs_out needs 16-byte alignment and obs_step_stride >= S*batch (multiple of 4)");
+    NIG_TRY(check_state_rows(h, fn, o.obs, o.obs_step_stride, "obs_out needs 16-byte alignment and obs_step_stride >= S*batch (multiple of 4)"));
     if (o.act && (o.ld_act < h->B || o.ld_act > NIG_MAX_PITCH || o.act_step_stride < (int64_t)SPECS[h->env].action_dim * o.ld_act))
         return refuse(fn, "bad action trajectory pitch");
     return NIG_OK;
@@ -401,6 +408,32 @@ static int closed_loop_args(const nig_handle *h, const char *fn, int32_t n_steps
     q.n_steps = n_steps; q.out_stride = (uint32_t)o.out_stride;
     q.obs_out = o.obs; q.obs_step_stride = (uint64_t)o.obs_step_stride;
     q.act_out = o.act; q.ld_act_out = (uint32_t)o.ld_act; q.act_step_stride = (uint64_t)o.act_step_stride;
+    return NIG_OK;
+}
+
+// nig_set_disturbance ("nig-disturb-v1"): finite sigmas >= 0 on the env's dimensions, ordered clip bounds (NaN refused), a known hold
+static int check_disturbance(const nig_handle *h, const char *fn, const nig_disturbance &d)
+{
+    for (int k = 0; k < SPECS[h->env].state_dim; ++k)
+        if (!(d.sigma_obs[k] >= 0.0f) || !std::isfinite(d.sigma_obs[k])) return refuse(fn, "sigma_obs must be finite and >= 0");
+    for (int j = 0; j < SPECS[h->env].action_dim; ++j)
+        if (!(d.sigma_act[j] >= 0.0f) || !std::isfinite(d.sigma_act[j])) return refuse(fn, "sigma_act must be finite and >= 0");
+    if (!(d.clip_lo <= d.clip_hi)) return refuse(fn, "clip_lo > clip_hi (or a NaN bound)");
+    if (d.hold != NIG_HOLD_STEP && d.hold != NIG_HOLD_EPISODE) return refuse(fn, "unknown hold (NIG_HOLD_STEP / NIG_HOLD_EPISODE)");
+    return NIG_OK;
+}
+
+// The _disturbed rollouts: an installed disturbance and seen_out's pitches (before the twin's own checks); then the kernel's copy.
+static int disturb_args(const nig_handle *h, const char *fn, float *seen_out, int64_t seen_step_stride, DisturbArgs &d)
+{
+    if (!h->has_dist) return refuse(fn, "no disturbance installed (nig_set_disturbance)");
+    NIG_TRY(check_state_rows(h, fn, seen_out, seen_step_stride, "seen_out needs 16-byte alignment and seen_step_stride >= S*batch (multiple of 4)"));
+    memset(&d, 0, sizeof d);
+    static_assert(sizeof d.sigma_obs == sizeof h->dist.sigma_obs && sizeof d.sigma_act == sizeof h->dist.sigma_act);
+    memcpy(d.sigma_obs, h->dist.sigma_obs, sizeof d.sigma_obs);
+    memcpy(d.sigma_act, h->dist.sigma_act, sizeof d.sigma_act);
+    d.clip_lo = h->dist.clip_lo; d.clip_hi = h->dist.clip_hi; d.hold = h->dist.hold;
+    d.seen_out = seen_out; d.seen_step_stride = (uint64_t)seen_step_stride;
     return NIG_OK;
 }
 
@@ -431,6 +464,9 @@ extern "C" {
 // Still 0.8.0: nig_set_mlp_ensemble / nig_rollout_mlp_ensemble (K MFMA actors per step, EnsembleAgent's action and uncertainty) and
 // NIG_FLAG_UNCERTAIN.  Additive: generator and every existing entry point's results unchanged.  The number did not move because
 // tests/test_rollout_sampled_host.py pins the string; a caller tells the two apart by the exported symbol.
+// Still 0.8.0, for the same reason (a minor bump is due with the next change that may touch that test): nig_set_disturbance /
+// nig_rollout_policy_disturbed / nig_rollout_mlp_disturbed ("nig-disturb-v1": sensor / actuator noise inside the closed loop; blocks
+// +32.. and +48.. of the generator's policy stream).  Additive: generator and every existing entry point's results unchanged.
 const char *nig_version(void) { return "nig 0.8.0 (gfx950; generator nig-philox-v3)"; }
 const char *nig_last_error(void) { return g_err; }
 
@@ -1131,6 +1167,52 @@ int nig_rollout_mlp_ensemble(nig_handle *h, int32_t n_steps, float *reward_out, 
     q.n_members = h->ens_members; q.w = h->ens_w; q.wsum = h->ens_wsum; q.kf = (float)h->ens_members; q.threshold = h->ens_threshold;
     q.unc_out = unc_out; q.member_out = member_act_out;
     launch_of(h->env)->mlp_ensemble(h->ens_method == NIG_ENSEMBLE_AVERAGE ? ENS_AVERAGE : ENS_VOTING, q, mlp_grid(h), (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    h->t += (uint32_t)n_steps;
+    return NIG_OK;
+}
+
+// ---- sensor / actuator noise in the closed loop ("nig-disturb-v1") --------------------------
+int nig_set_disturbance(nig_handle *h, const nig_disturbance *d, void * /*stream*/)
+{
+    if (!h) return fail(NIG_ERR_INVALID, "nig_set_disturbance: NULL handle");
+    if (!d) { h->has_dist = false; return NIG_OK; }
+    NIG_TRY(check_disturbance(h, "nig_set_disturbance", *d));
+    h->dist = *d;                                  // (travels in the kernel arguments: no device copy, nothing to wait for)
+    h->has_dist = true;
+    return NIG_OK;
+}
+
+int nig_rollout_policy_disturbed(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                                 float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
+                                 int64_t act_step_stride, float *seen_out, int64_t seen_step_stride, void *stream)
+{
+    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_policy_disturbed: bad argument");
+    if (!h->has_policy) return fail(NIG_ERR_INVALID, "nig_rollout_policy_disturbed: no policy installed (nig_set_policy)");
+    PolicyDistArgs q;
+    NIG_TRY(disturb_args(h, "nig_rollout_policy_disturbed", seen_out, seen_step_stride, q.d));
+    NIG_TRY(closed_loop_args(h, "nig_rollout_policy_disturbed", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, q.p));
+    q.p.pol = h->pol_dev;
+    q.p.pid = (h->pol_host.kind == NIG_POLICY_PID) ? h->pid_mem : nullptr;
+    q.p.pol_kind = h->pol_host.kind;
+    launch_of(h->env)->policy_disturbed(q, grid_for(h->B), (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    h->t += (uint32_t)n_steps;
+    return NIG_OK;
+}
+
+int nig_rollout_mlp_disturbed(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                              float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
+                              int64_t act_step_stride, float *seen_out, int64_t seen_step_stride, void *stream)
+{
+    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_disturbed: bad argument");
+    if (!launch_of(h->env)->mlp_disturbed) return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_mlp_disturbed: env shape has no MFMA actor");
+    if (!h->mlp_stream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_disturbed: no actor installed (nig_set_mlp_policy)");
+    MlpDistArgs q;
+    NIG_TRY(disturb_args(h, "nig_rollout_mlp_disturbed", seen_out, seen_step_stride, q.d));
+    NIG_TRY(closed_loop_args(h, "nig_rollout_mlp_disturbed", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, q.m));
+    q.m.wstream = h->mlp_stream;
+    launch_of(h->env)->mlp_disturbed(q, mlp_grid(h), (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     h->t += (uint32_t)n_steps;
     return NIG_OK;

@@ -284,7 +284,9 @@ constexpr int PHILOX_ROUNDS = 7;
 constexpr uint32_t STREAM_STEP = 0u;
 constexpr uint32_t STREAM_RESET = 0x40000000u;
 constexpr uint32_t STREAM_ACTION = 0x80000000u;
-constexpr uint32_t STREAM_POLICY = 0xC0000000u;   // +0: mixture draw, +1..: normals, +8..: uniform noise, +16..: random action
+constexpr uint32_t STREAM_POLICY = 0xC0000000u;   // +0: mixture draw, +1..: normals, +8..: uniform noise, +16..: random action (keyed at t);
+                                                  // "nig-disturb-v1" (nig_disturb.hpp, keyed at t or at the episode's first t): +32..: observation
+                                                  // normals, +48..: action normals
 
 struct u32x4 { uint32_t x, y, z, w; };
 

@@ -21,6 +21,8 @@ struct EnvLaunch {
     bool (*rows_native)(int out_mode, const RolloutArgs &);
     void (*rollout_sampled)(int out_mode, const RolloutArgs &, uint32_t t0, unsigned grid, hipStream_t);   // nig_rollout_sampled
     void (*mlp_ensemble)(int ens, const MlpEnsArgs &, unsigned grid, hipStream_t);   // nig_rollout_mlp_ensemble; nullptr as `mlp`
+    void (*policy_disturbed)(const PolicyDistArgs &, unsigned grid, hipStream_t);    // nig_rollout_policy_disturbed
+    void (*mlp_disturbed)(const MlpDistArgs &, unsigned grid, hipStream_t);          // nig_rollout_mlp_disturbed; nullptr as `mlp`
 };
 
 template <class Env>
@@ -218,6 +220,34 @@ void launch_mlp_ensemble_env(int ens, const MlpEnsArgs &q, unsigned grid, hipStr
 ;
 #endif
 
+// nig_rollout_policy_disturbed / nig_rollout_mlp_disturbed: as the twins above, declared everywhere and DEFINED (their kernels
+// instantiated) only in the env's disturbed_*.hip translation unit (NIG_DEFINE_ENV_DISTURBED).  The closed loop under a disturbance
+// has the one-wave form only (plan_policy_disturbed): the three-wave and paired PowerGrid closed loops have no disturbed twin.
+template <class Env>
+void launch_policy_disturbed_env(const PolicyDistArgs &q, unsigned /*grid*/, hipStream_t st)
+#ifdef NIG_DISTURBED_TU
+{
+    const LaunchPlan plan = plan_policy_disturbed(q.p.s.B);
+    PolicyDistArgs r = q;
+    for (const Segment &s : plan) {
+        r.p.block0 = s.block0;
+        hipLaunchKernelGGL((rollout_policy_disturbed_kernel<Env>), dim3(s.grid), dim3(BLOCK), 0, st, r);
+    }
+}
+#else
+;
+#endif
+
+template <class Env>
+void launch_mlp_disturbed_env(const MlpDistArgs &q, unsigned grid, hipStream_t st)
+#ifdef NIG_DISTURBED_TU
+{
+    if constexpr (Env::S % 2 == 0 && Env::A <= 16) hipLaunchKernelGGL((rollout_mlp_disturbed_kernel<Env>), dim3(grid), dim3(BLOCK), 0, st, q);
+}
+#else
+;
+#endif
+
 template <class Env>
 static void launch_policy(const PolicyArgs &q, unsigned /*grid*/, hipStream_t st)
 {
@@ -250,7 +280,9 @@ static const EnvLaunch *env_launch_table()
                                 (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp<Env> : nullptr,
                                 (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp_shield<Env> : nullptr,
                                 launch_reset<Env>, launch_fill<Env>, rollout_rows_native<Env>, launch_rollout_sampled_env<Env>,
-                                (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp_ensemble_env<Env> : nullptr};
+                                (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp_ensemble_env<Env> : nullptr,
+                                launch_policy_disturbed_env<Env>,
+                                (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp_disturbed_env<Env> : nullptr};
     return &T;
 }
 
@@ -277,3 +309,7 @@ void nig_launch_mixed_rollout(int out_mode, const nig::MixedArgs &m, unsigned gr
 // ensemble_*.hip (compiled with NIG_ENSEMBLE_TU defined before this header): the env's nig_rollout_mlp_ensemble launcher and kernels
 #define NIG_DEFINE_ENV_ENSEMBLE(EnvType) \
     template void nig::launch_mlp_ensemble_env<nig::EnvType>(int, const nig::MlpEnsArgs &, unsigned, hipStream_t);
+// disturbed_*.hip (compiled with NIG_DISTURBED_TU defined before this header): the env's nig_rollout_*_disturbed launchers and kernels
+#define NIG_DEFINE_ENV_DISTURBED(EnvType) \
+    template void nig::launch_policy_disturbed_env<nig::EnvType>(const nig::PolicyDistArgs &, unsigned, hipStream_t); \
+    template void nig::launch_mlp_disturbed_env<nig::EnvType>(const nig::MlpDistArgs &, unsigned, hipStream_t);

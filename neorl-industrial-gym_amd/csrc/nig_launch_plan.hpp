@@ -138,4 +138,14 @@ constexpr LaunchPlan plan_policy(bool affine, bool obs_stream, uint32_t B, uint3
     return p;
 }
 
+// nig_rollout_policy_disturbed: always the one-wave closed-loop kernel, at every batch size -- whole blocks and the ragged last
+// block in one launch, as plan_policy's last segment.  The three-wave and paired PowerGrid closed loops have no disturbed twin.
+constexpr LaunchPlan plan_policy_disturbed(uint32_t B)
+{
+    LaunchPlan p;
+    const uint32_t all = (B + PLAN_BLOCK - 1) / PLAN_BLOCK;
+    if (all > 0) p.add(Form::OneWaveRagged, all, all);
+    return p;
+}
+
 }  // namespace nig

@@ -1,7 +1,8 @@
 // nig_mlp.hpp -- the fused MLP actor on MFMA with its safety-critic shield and its ensemble (device code only): MlpArgs,
-// MlpShieldArgs, MlpEnsArgs, rollout_mlp_body and its three kernels.
+// MlpShieldArgs, MlpEnsArgs, MlpDistArgs, rollout_mlp_body and its four kernels.
 #pragma once
 #include "nig_step.hpp"
+#include "nig_disturb.hpp"
 
 namespace nig {
 
@@ -117,11 +118,22 @@ struct MlpEnsArgs {
     float *member_out;          // member k of step it: [A][m.ld_act_out] at member_out + (it * n_members + k) * m.act_step_stride, may be NULL
 };
 
-template <class Env, bool SHIELD, int ENS = ENS_NONE>
+// Disturbed actor (rollout_mlp_disturbed_kernel, include/nig.h "nig-disturb-v1"): DIST feeds layer 1 the noisy observation
+// o = s + sigma_obs * zo instead of s and adds sigma_act * za to the tanh head's action before the disturbance's clip.  The draws
+// depend on the lane's key only, so they are made at the top of the step, ahead of the first chunk barrier, while the LDS-DMA
+// fill of layer 1 is in flight; both lane halves compute the same o from the same key.  o[] is dead after layer 1.
+struct MlpDistArgs {
+    MlpArgs m;
+    DisturbArgs d;
+};
+
+template <class Env, bool SHIELD, int ENS = ENS_NONE, bool DIST = false>
 __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const MlpArgs &q, const float *cstream, float *prob_out, float threshold,
-                                                                       [[maybe_unused]] const MlpEnsArgs *eq = nullptr)
+                                                                       [[maybe_unused]] const MlpEnsArgs *eq = nullptr,
+                                                                       [[maybe_unused]] const DisturbArgs *dq = nullptr)
 {
     static_assert(!(SHIELD && ENS != ENS_NONE), "the ensemble has no shield");
+    static_assert(!DIST || (!SHIELD && ENS == ENS_NONE), "the shield and the ensemble have no disturbed form");
     // the env steps on the ensemble's float64 action where its NumPy arithmetic follows the action's type (nig_step64's rule)
     constexpr bool ACT64 = ENS == ENS_AVERAGE && Env::HAS_ACT64;
     using act_t = std::conditional_t<ACT64, double, float>;
@@ -181,7 +193,18 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
     fill(0, 0, PIECES0);
     int gbuf = 0;                                            // buffer that holds (or receives) the chunk consumed next
     const int n_members = ENS != ENS_NONE ? eq->n_members : 1;
+    [[maybe_unused]] bool d_obs = false, d_act = false;
+    if constexpr (DIST) disturb_switches<S, A>(*dq, d_obs, d_act);
     for (int it = 0; it < q.n_steps; ++it) {
+        [[maybe_unused]] float d_o[DIST ? S : 1], d_za[DIST ? A : 1];
+        if constexpr (DIST) {                                      // (before the chunk barrier: beside the fill of layer 1)
+            float zo[S];
+            disturb_draws<S, A>(*dq, d_obs, d_act, gi, t_base + (uint32_t)it + 1u, ctr & NIG_CTR_STEP_MASK, p.seed_lo, p.seed_hi, s_probit, zo, d_za);
+            disturb_obs<S>(*dq, d_obs, s, zo, d_o);
+            // seen_out's row leaves here, so that o[] is dead once layer 1 has read it
+            if (writer && !(ctr & NIG_CTR_DONE) && dq->seen_out) disturb_store_seen<S>(*dq, it, (size_t)li, d_o);
+        }
+        auto xin = [&](int k) __attribute__((always_inline)) { if constexpr (DIST) return d_o[k]; else return s[k]; };   // layer 1's input
         [[maybe_unused]] float e_p0[A], e_s1[A], e_s2[A], e_f[A];   // ensemble: member 0, sum d, sum d^2, float32 action sum
         [[maybe_unused]] double e_d[A];                            // ensemble: float64 weighted action sum
         int mem = 0;
@@ -202,7 +225,7 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
                 f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
                 for (int ks = 0; ks < S / 2; ++ks) {
-                    const float b = half ? s[2 * ks + 1] : s[2 * ks];
+                    const float b = half ? xin(2 * ks + 1) : xin(2 * ks);
                     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[(m * R1 + ks) * 64], b, acc, 0, 0, 0);
                 }
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[(m * R1 + R1 - 1) * 64], half ? 0.0f : 1.0f, acc, 0, 0, 0);   // + b1
@@ -298,6 +321,7 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
             }
         }
         } while (ENS != ENS_NONE && ++mem < n_members);
+        if constexpr (DIST) disturb_act<A>(*dq, d_act, d_za, a);
         [[maybe_unused]] float unc = 0.0f;
         [[maybe_unused]] bool uncertain = false;
         [[maybe_unused]] double a64[ACT64 ? A : 1];
@@ -470,6 +494,13 @@ template <class Env, int ENS>
 __global__ void __launch_bounds__(BLOCK, mlp_two_blocks<Env> ? 2 : 1) rollout_mlp_ensemble_kernel(const MlpEnsArgs q)
 {
     rollout_mlp_body<Env, false, ENS>(q.m, nullptr, nullptr, 0.0f, &q);
+}
+
+// Instantiated in the env's disturbed_*.hip translation unit only (launch_mlp_disturbed_env).
+template <class Env>
+__global__ void __launch_bounds__(BLOCK, mlp_two_blocks<Env> ? 2 : 1) rollout_mlp_disturbed_kernel(const MlpDistArgs q)
+{
+    rollout_mlp_body<Env, false, ENS_NONE, true>(q.m, nullptr, nullptr, 0.0f, nullptr, &q.d);
 }
 
 }  // namespace nig

@@ -264,6 +264,12 @@ class MLPPolicy:
         out = self.predict_device(o.reshape(-1, self.state_dim)).cpu().numpy()
         return out[0] if single else out
 
+    def exploring(self, sigma: float = 0.1):
+        """The reference agents' predict(obs, deterministic=False), clip(actor + sigma N(0,1), -1, 1) (agents/cql.py:345-350),
+        as a policy of its own (for evaluate_with_safety: fused into the env kernel when the actor is fusable)."""
+        from .disturbance import Disturbance, Disturbed
+        return Disturbed(self, Disturbance(action_noise=sigma, clip=(-1.0, 1.0)))
+
     def _threshold(self, safety_threshold):
         return safety_threshold or self.constraint_threshold           # cql.py:384 (0.0 / None fall back)
 

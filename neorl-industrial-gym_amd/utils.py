@@ -77,6 +77,8 @@ def _play_episode(agent, env, render):
     (return, length, sum of violation_count, sum of critical_violations, shutdown steps,
     per-step satisfaction rates).  `ret += reward` keeps the reward's own type, as upstream."""
     obs, _ = env.reset()
+    if hasattr(agent, "begin_episode"):
+        agent.begin_episode(1)
     ret, length, viol, crit, shut, rates = 0.0, 0, 0, 0, 0, []
     finished = False
     while not finished:
@@ -115,13 +117,33 @@ def _summarise(runs, n_episodes):
     }
 
 
+def _disturbed_route(agent, env):
+    """How a disturbance.Disturbed agent runs on `env`: ("fused-policy", DevicePolicy), ("fused-mlp", MLPPolicy) -- the inner
+    agent goes into the env kernel with the disturbance beside it -- or ("host", None): shielded, ensemble and non-fusable
+    agents keep the per-step loop with the wrapper's own draws.  A reference agent MLPPolicy.from_agent can read is upgraded."""
+    from .policies import MLPPolicy
+    inner = agent.agent
+    if hasattr(inner, "to_struct"):
+        return "fused-policy", inner
+    if not hasattr(inner, "fusable") and hasattr(inner, "state") and not hasattr(inner, "agents"):
+        try:
+            inner = MLPPolicy.from_agent(inner, device=env.device)
+        except Exception:
+            return "host", None
+    if (isinstance(inner, MLPPolicy) and inner.fusable and env.state_dim % 2 == 0 and env.action_dim <= 16
+            and env.state_dim <= 32 and env.action_dim <= 10):
+        return "fused-mlp", inner
+    return "host", None
+
+
 def _evaluate_batched(agent, env: BatchedIndustrialEnv, n_episodes: int, step_noise_fn=None, reset_noise_fn=None,
-                      group=None, reduce_across_ranks: bool = True) -> Dict[str, Any]:
+                      group=None, reduce_across_ranks: bool = True, round_hook=None) -> Dict[str, Any]:
     """Episodes in parallel lanes.  Rounds of up to B episodes: reset the needed lanes, step
     until every one of them is done (finished lanes are frozen by the kernel), tallies
     accumulate on the device; one reduction (+ all-gather across ranks) at the end.
 
-    step_noise_fn(round, t) / reset_noise_fn(round) may supply recorded draws (parity tests)."""
+    step_noise_fn(round, t) / reset_noise_fn(round) may supply recorded draws (parity tests).
+    round_hook(env, k): called after every round of k episodes (lanes [0, k) hold their finished episodes' counters)."""
     if not env.tally_enabled or env.autoreset:
         raise ValueError("batched evaluation needs make_batched(..., tally=True, autoreset=False)")
     B = env.batch
@@ -141,7 +163,17 @@ def _evaluate_batched(agent, env: BatchedIndustrialEnv, n_episodes: int, step_no
     ensemble = plain and hasattr(agent, "install") and getattr(agent, "fusable", False) and env.state_dim % 2 == 0 and env.action_dim <= 16
     fused_mlp = not hasattr(agent, "install") and getattr(agent, "fusable", False) and step_noise_fn is None and reset_noise_fn is None
     shielded = fused_mlp and getattr(agent, "safety_weights", None) is not None and hasattr(agent, "threshold")
-    if device_policy:
+    disturbed = None           # a disturbance.Disturbed whose inner agent runs in the env kernel: "fused-policy" / "fused-mlp"
+    if plain and hasattr(agent, "disturbance") and hasattr(agent, "agent"):
+        route, inner = _disturbed_route(agent, env)
+        if route != "host":
+            disturbed = route
+            (env.set_policy if route == "fused-policy" else lambda a: env.set_mlp_policy(a.weights))(inner)
+            env.set_disturbance(agent.disturbance)
+        device_policy = ensemble = fused_mlp = shielded = False
+    if disturbed:
+        device_policy = True
+    elif device_policy:
         env.set_policy(agent)
     elif ensemble:
         agent.install(env)
@@ -161,14 +193,21 @@ def _evaluate_batched(agent, env: BatchedIndustrialEnv, n_episodes: int, step_no
         # the Advanced envs truncate on the step AFTER the cap (advanced_chemical_reactor.py:351 and
         # advanced_power_grid.py:331 test episode_step before its increment): one step more for them
         extra = 1 if env.env_id.startswith("Advanced") else 0
-        (env.rollout_mlp_ensemble if ensemble else env.rollout_mlp_safe if shielded else env.rollout_mlp if fused_mlp
+        (env.rollout_policy_disturbed if disturbed == "fused-policy" else env.rollout_mlp_disturbed if disturbed
+         else env.rollout_mlp_ensemble if ensemble else env.rollout_mlp_safe if shielded else env.rollout_mlp if fused_mlp
          else env.rollout_policy)(env.max_episode_steps + extra)
+        if round_hook is not None:
+            round_hook(env, k)
         remaining -= k
+    if disturbed:
+        env.set_disturbance(None)
     while remaining > 0:
         k = min(B, remaining)
         mask = torch.zeros(B, dtype=torch.uint8, device=env.device)
         mask[:k] = 1
         env.reset(mask=mask, init_noise=None if reset_noise_fn is None else reset_noise_fn(rnd))
+        if hasattr(agent, "begin_episode"):
+            agent.begin_episode(B)
         t = 0
         while True:
             act = _predict(agent, env.obs)
@@ -176,6 +215,8 @@ def _evaluate_batched(agent, env: BatchedIndustrialEnv, n_episodes: int, step_no
             t += 1
             if _round_is_over(env, t, hasattr(agent, "predict_device")) or t > _lib.MAX_EPISODE_STEPS:
                 break
+        if round_hook is not None:
+            round_hook(env, k)
         remaining -= k
         rnd += 1
     partial = env.reduce_tally()
