@@ -721,6 +721,75 @@ int nig_get_safety_metrics(nig_handle *h, const uint32_t *flags, int32_t *out, i
 int nig_reduce_tally(nig_handle *h, double *partial_out, void *stream);
 
 /*
+ * Per-episode records ("episode log") from the per-step rows every rollout entry point writes.  The tally above can say
+ * thirteen sums about the episodes it saw; what the reference's evaluation layer does with single episodes -- median_return,
+ * violation_rate, metadata["individual_returns"] / ["episode_violations"] of SafetyBenchmark / PerformanceBenchmark
+ * (benchmarks/industrial_benchmarks.py:95-341), the per-episode lists benchmarks/statistical_analysis.py tests -- needs one
+ * number per episode.  The log is built from reward_out / flags_out rows alone, so it serves nig_rollout, _sampled, _policy,
+ * _mlp, _mlp_safe, _mlp_ensemble, the _disturbed twins, nig_step and nig_plan_* alike, in every kernel form.
+ *
+ * The law, per lane, per step row in order (csrc/nig_episodes.hpp episode_row: the one statement; episodes.episodes_from_rows
+ * restates it in NumPy):
+ *   - a flag word with NIG_FLAG_INACTIVE is skipped (frozen lane);
+ *   - otherwise return += reward -- in float32 for an env with nig_env_spec.reward_is_f32, (double)((float)ret + reward), which
+ *     is the kernels' own sum bit for bit; in float64 over the float rows for every other env (the kernels add the float64
+ *     reward there: a lane's return agrees within 2^-23 x the sum of |reward_k|) --, violations += bits 5-6 (+ 4 with
+ *     NIG_FLAG_NVIOL_HI), the four per-constraint bits, NIG_FLAG_SHIELDED and NIG_FLAG_UNCERTAIN are counted;
+ *   - on NIG_FLAG_TERMINATED | NIG_FLAG_TRUNCATED the episode becomes record number count[lane] if count[lane] < capacity,
+ *     count[lane] += 1 regardless (count > capacity tells an overflow), and the running values start over.
+ * The running values persist in the log between calls: rows cut into several calls give the records of one call.
+ *
+ * Layout: ONE caller-owned device allocation of nig_episode_log_layout.bytes (8-byte aligned), structure-of-arrays with row
+ * pitch ld (>= batch; any value, multiples of 64 not required), record k of lane i at element k*ld + i of
+ *   ret    double [capacity][ld]   episode return
+ *   w[0]   uint32 [capacity][ld]   NIG_CTR_* format: length (the done step's step field) | NIG_CTR_DONE | violations << 16
+ *   w[1]   uint32 [capacity][ld]   the done step's flag word & (TERMINATED | TRUNCATED | the NCRIT field | SHUTDOWN)
+ *   w[2]   uint32 [capacity][ld]   steps with constraint 0 violated (low 16 bits), constraint 1 (high 16 bits)
+ *   w[3]   uint32 [capacity][ld]   the same for constraint 2 and NIG_FLAG_VIOL3
+ *   w[4]   uint32 [capacity][ld]   NIG_FLAG_SHIELDED steps (low 16 bits), NIG_FLAG_UNCERTAIN steps (high 16 bits)
+ *   count  uint32 [ld]             finished episodes of the lane
+ *   carry  double [ld] + uint32 [4][ld]   the running return; running violations, w[2], w[3], w[4]
+ *   tally  double [NIG_T_ROWS + 1][ld], scratch double [256][NIG_T_ROWS]   work space of nig_reduce_episodes
+ * Written set (columns [0, batch) only -- the pad columns [batch, ld) of every row are never written):
+ *   nig_episode_log_init     count and carry;
+ *   nig_collect_episodes     count and carry, and of lane i the record rows [count_before, min(count_after, capacity)): never a
+ *                            record row at or beyond the lane's count, never one at or beyond capacity; reward / flags are inputs;
+ *   nig_reduce_episodes      tally and scratch; partial_out; the records are inputs.
+ */
+typedef struct nig_episode_log_layout {
+    int64_t batch, capacity, ld, bytes;
+    int64_t off_ret;         /* double [capacity][ld]                    */
+    int64_t off_w[5];        /* uint32 [capacity][ld] each               */
+    int64_t off_count;       /* uint32 [ld]                              */
+    int64_t off_carry_ret;   /* double [ld]                              */
+    int64_t off_carry_w;     /* uint32 [4][ld]                           */
+    int64_t off_tally;       /* double [NIG_T_ROWS + 1][ld]              */
+    int64_t off_scratch;     /* double [256][NIG_T_ROWS]                 */
+} nig_episode_log_layout;
+#define NIG_MAX_EPISODE_CAPACITY (1 << 20)   /* records per lane */
+
+/* Size / layout of a log of `capacity` records per lane for `batch` lanes at row pitch ld (0 = batch rounded up to 64).
+ * NIG_ERR_INVALID: batch outside [1, 2^24], capacity outside [1, 2^20], ld != 0 outside [batch, 2^26], NULL out. */
+int nig_episode_log_query(int64_t batch, int64_t capacity, int64_t ld, nig_episode_log_layout *out);
+/* Every entry point below takes the log with the (capacity, ld) its memory was sized for (ld 0 = the default pitch again), checks
+ * every argument before anything is enqueued (a refused call launches and writes nothing), and enqueues on `stream`.
+ * nig_episode_log_init: no episode finished, nothing running. */
+int nig_episode_log_init(nig_handle *h, void *log, int64_t capacity, int64_t ld, void *stream);
+/* n_steps (>= 1) step rows: reward float / flags uint32, both required, row of step k at base + k*out_stride, out_stride >= batch
+ * (<= 2^26; with n_steps == 1 it is not used and may be 0: the [B] arrays nig_step writes). */
+int nig_collect_episodes(nig_handle *h, int32_t n_steps, const float *reward, const uint32_t *flags, int64_t out_stride,
+                         void *log, int64_t capacity, int64_t ld, void *stream);
+/* The tally of the records that count: record (k, i) counts iff k < min(count[i], capacity) and k*batch + i < n_episodes (a
+ * fixed episode count per lane: the first n_episodes / batch episodes of every lane, one more of the first n_episodes % batch
+ * lanes -- the episodes the rounds of evaluate_with_safety play).  Each lane's counted records go, in order, through the
+ * arithmetic of the kernels' own tally (total_constraints = the handle's enabled constraints), the lanes are reduced as
+ * nig_reduce_tally reduces them: partial_out (DEVICE double [NIG_T_ROWS + 1]) holds the NIG_T_* rows, then the number of
+ * counted episodes with a non-zero violation count.  partial_out[NIG_T_EPISODES] < n_episodes: lanes had not finished their
+ * share, or capacity was too small.  NIG_ERR_INVALID: n_episodes outside [1, capacity*batch]. */
+int nig_reduce_episodes(nig_handle *h, void *log, int64_t capacity, int64_t ld, int64_t n_episodes, double *partial_out,
+                        void *stream);
+
+/*
  * The path's one exchange (BASELINE north_star: "an RCCL all-reduce over xGMI only for the final return /
  * safety-violation reduction"), for hosts that do not go through torch.distributed: reduce the tallies of this
  * rank's handles (one, or the segments of a mixed batch) to one partial vector, ncclAllGather the partial vectors

@@ -22,6 +22,7 @@ from .policies import (DevicePolicy, EnsemblePolicy, MLPPolicy, behaviour_policy
                        pid_agent, random_agent)
 from .utils import evaluate_with_safety, make, make_batched, uniform_action_statistics  # noqa: E402
 from .disturbance import Disturbance, Disturbed, evaluate_robustness, robustness_scores  # noqa: E402
+from .episodes import EpisodeLog, episodes_from_rows, evaluate_episodes  # noqa: E402
 
 def tune(split_blocks=None, wide_min_blocks=None):
     """Process-wide kernel-selection knobs of libnig (include/nig.h nig_tune); results never depend on them.
@@ -39,7 +40,7 @@ def tune(split_blocks=None, wide_min_blocks=None):
             "wide_min_blocks": int(L.nig_tune_get(_lib.TUNE_WIDE_MIN_BLOCKS))}
 
 
-__version__ = "0.8.0"        # 0.8.0: rollout_sampled, then EnsemblePolicy / rollout_mlp_ensemble (both additive; the number is pinned by tests/test_rollout_sampled_host.py); generator "nig-philox-v3" since round 4 (v2 + PowerGrid's reset load factors from spare low bytes; libnig: nig_version())
+__version__ = "0.8.0"        # 0.8.0: rollout_sampled, then EnsemblePolicy / rollout_mlp_ensemble, evaluate_robustness, EpisodeLog / evaluate_episodes (all additive; the number is pinned by tests/test_rollout_sampled_host.py); generator "nig-philox-v3" since round 4 (v2 + PowerGrid's reset load factors from spare low bytes; libnig: nig_version())
 GENERATOR = "nig-philox-v3"
 __all__ = [
     "__version__", "DatasetQuality", "SafetyConstraint", "SafetyMetrics", "IndustrialEnv",
@@ -47,4 +48,5 @@ __all__ = [
     "HVACControlEnv", "WaterTreatmentEnv", "SteelAnnealingEnv", "SupplyChainEnv", "BatchedIndustrialEnv", "MixedBatchedEnv", "StepInfo",
     "make", "make_batched", "evaluate_with_safety", "uniform_action_statistics", "tune", "DevicePolicy", "MLPPolicy", "EnsemblePolicy", "behaviour_policy", "constant_agent",
     "mpc_agent", "pid_agent", "random_agent", "Disturbance", "Disturbed", "evaluate_robustness", "robustness_scores",
+    "EpisodeLog", "episodes_from_rows", "evaluate_episodes",
 ]

@@ -42,6 +42,7 @@ SYMBOLS = [
     "nig_create_mixed", "nig_mixed_destroy", "nig_mixed_get_info", "nig_mixed_state", "nig_mixed_segment", "nig_mixed_reset",
     "nig_mixed_fill_actions", "nig_mixed_rollout", "nig_rollout_mixed", "nig_mixed_step", "nig_rollout_mixed_obs", "nig_mixed_rollout_obs",
     "nig_tune", "nig_tune_get", "nig_handle_tune_get", "nig_clock_stamp",
+    "nig_episode_log_query", "nig_episode_log_init", "nig_collect_episodes", "nig_reduce_episodes",
 ]
 
 
@@ -56,6 +57,13 @@ class Layout(C.Structure):
     _fields_ = [("batch", C.c_int64), ("ld", C.c_int64), ("bytes", C.c_int64), ("off_state", C.c_int64),
                 ("off_ctr", C.c_int64), ("off_life_viol", C.c_int64), ("off_ep_return", C.c_int64),
                 ("off_tally", C.c_int64)]
+
+
+class EpisodeLogLayout(C.Structure):
+    """nig_episode_log_layout (include/nig.h): byte offsets of an episode log's arrays."""
+    _fields_ = [("batch", C.c_int64), ("capacity", C.c_int64), ("ld", C.c_int64), ("bytes", C.c_int64),
+                ("off_ret", C.c_int64), ("off_w", C.c_int64 * 5), ("off_count", C.c_int64), ("off_carry_ret", C.c_int64),
+                ("off_carry_w", C.c_int64), ("off_tally", C.c_int64), ("off_scratch", C.c_int64)]
 
 
 class Policy(C.Structure):
@@ -179,6 +187,10 @@ def lib():
     L.nig_rollout_mixed.argtypes = [C.POINTER(vp), C.POINTER(i64), i32, i32, vp, i64, i64, i32, vp, vp, i64, vp]
     L.nig_rollout_mixed_obs.argtypes = [C.POINTER(vp), C.POINTER(i64), i32, i32, vp, i64, i64, i32, vp, vp, i64, vp, i64, i64, vp]
     L.nig_mixed_rollout_obs.argtypes = [vp, i32, vp, i64, i32, vp, vp, i64, vp, i64, vp]
+    L.nig_episode_log_query.argtypes = [i64, i64, i64, C.POINTER(EpisodeLogLayout)]
+    L.nig_episode_log_init.argtypes = [vp, vp, i64, i64, vp]
+    L.nig_collect_episodes.argtypes = [vp, i32, vp, vp, i64, vp, i64, i64, vp]
+    L.nig_reduce_episodes.argtypes = [vp, vp, i64, i64, i64, vp, vp]
     _lib = L
     return L
 
@@ -197,4 +209,10 @@ def env_spec(env_id: int) -> EnvSpec:
 def layout_query(env_id: int, batch: int, flags: int) -> Layout:
     lay = Layout()
     check(lib().nig_layout_query(env_id, batch, flags, C.byref(lay)))
+    return lay
+
+
+def episode_log_query(batch: int, capacity: int, ld: int = 0) -> EpisodeLogLayout:
+    lay = EpisodeLogLayout()
+    check(lib().nig_episode_log_query(batch, capacity, ld, C.byref(lay)))
     return lay

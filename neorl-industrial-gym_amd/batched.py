@@ -652,6 +652,16 @@ class BatchedIndustrialEnv:
             _lib.check(self._L.nig_get_safety_metrics(self._h, _ptr(self.flags), _ptr(out), self.batch, self._stream()))
         return out
 
+    def episode_log(self, capacity: int, ld: Optional[int] = None):
+        """A log of `capacity` per-episode records per lane (episodes.EpisodeLog; include/nig.h nig_episode_log_*), cleared."""
+        from .episodes import EpisodeLog
+        return EpisodeLog(self, capacity, ld)
+
+    def collect_episodes(self, log, n_steps: int, reward_rows: torch.Tensor, flag_rows: torch.Tensor):
+        """nig_collect_episodes: the n_steps reward / flag rows a rollout (or step) of this env wrote go into `log` -- finished
+        episodes become records, the running ones stay in the log's carry for the next call."""
+        log.collect(n_steps, reward_rows, flag_rows)
+
     def reduce_tally(self) -> torch.Tensor:
         """Device reduction of the per-lane tallies -> float64 [T_ROWS] partial vector."""
         out = torch.empty(_lib.T_ROWS, dtype=torch.float64, device=self.device)

@@ -5,6 +5,7 @@
 #include <atomic>
 
 #include "nig_launch.hpp"
+#include "nig_episodes.hpp"
 
 namespace nig {
 
@@ -467,6 +468,8 @@ extern "C" {
 // Still 0.8.0, for the same reason (a minor bump is due with the next change that may touch that test): nig_set_disturbance /
 // nig_rollout_policy_disturbed / nig_rollout_mlp_disturbed ("nig-disturb-v1": sensor / actuator noise inside the closed loop; blocks
 // +32.. and +48.. of the generator's policy stream).  Additive: generator and every existing entry point's results unchanged.
+// Still 0.8.0, for the same reason: nig_episode_log_query / _init, nig_collect_episodes, nig_reduce_episodes (per-episode records from the
+// reward / flag rows; csrc/nig_episodes.hpp).  Additive: no existing kernel or entry point changed.
 const char *nig_version(void) { return "nig 0.8.0 (gfx950; generator nig-philox-v3)"; }
 const char *nig_last_error(void) { return g_err; }
 
@@ -1701,6 +1704,86 @@ int nig_reduce_tally(nig_handle *h, double *partial_out, void *stream)
     if (nblk > REDUCE_BLOCKS) nblk = REDUCE_BLOCKS;
     hipLaunchKernelGGL(reduce_tally_stage1, dim3(nblk), dim3(BLOCK), 0, st, (const double *)ws_tally(h), h->lay.ld, h->B, h->scratch);
     hipLaunchKernelGGL(reduce_tally_stage2, dim3(1), dim3(REDUCE_BLOCKS), 0, st, (const double *)h->scratch, nblk, partial_out);
+    HIP_TRY(hipGetLastError());
+    return NIG_OK;
+}
+
+// ---- per-episode records from reward / flag rows (csrc/nig_episodes.hpp) ------------------------------------------------------
+// The shape of a log: what nig_episode_log_query refuses, every entry point refuses
+static int check_episode_log_shape(const char *fn, int64_t batch, int64_t capacity, int64_t ld)
+{
+    if (batch <= 0 || batch > NIG_MAX_BATCH) return refuse(fn, "batch outside [1, 2^24]");
+    if (capacity < 1 || capacity > NIG_MAX_EPISODE_CAPACITY) return refuse(fn, "capacity outside [1, 2^20]");
+    if (ld != 0 && (ld < batch || ld > NIG_MAX_PITCH)) return refuse(fn, "ld outside {0} U [batch, 2^26]");
+    return NIG_OK;
+}
+
+int nig_episode_log_query(int64_t batch, int64_t capacity, int64_t ld, nig_episode_log_layout *out)
+{
+    if (!out) return refuse("nig_episode_log_query", "out is NULL");
+    NIG_TRY(check_episode_log_shape("nig_episode_log_query", batch, capacity, ld));
+    *out = episode_log_layout(batch, capacity, ld);
+    return NIG_OK;
+}
+
+// A handle, a log (8-byte aligned: it holds doubles) and its shape; then the kernels' view of the log
+static int episode_log_args(const nig_handle *h, const char *fn, void *log, int64_t capacity, int64_t ld, EpisodeLogArgs &a)
+{
+    if (!h) return refuse(fn, "NULL handle");
+    if (!log || ((uintptr_t)log & 7u) != 0) return refuse(fn, "log NULL or not 8-byte aligned");
+    NIG_TRY(check_episode_log_shape(fn, h->B, capacity, ld));
+    const nig_episode_log_layout L = episode_log_layout(h->B, capacity, ld);
+    char *p = (char *)log;
+    a.ret = (double *)(p + L.off_ret);
+    for (int w = 0; w < 5; ++w) a.w[w] = (uint32_t *)(p + L.off_w[w]);
+    a.count = (uint32_t *)(p + L.off_count); a.carry_ret = (double *)(p + L.off_carry_ret); a.carry_w = (uint32_t *)(p + L.off_carry_w);
+    a.tally = (double *)(p + L.off_tally);
+    a.ld = L.ld; a.B = h->B; a.capacity = (uint32_t)capacity;
+    return NIG_OK;
+}
+
+int nig_episode_log_init(nig_handle *h, void *log, int64_t capacity, int64_t ld, void *stream)
+{
+    EpisodeLogArgs a;
+    NIG_TRY(episode_log_args(h, "nig_episode_log_init", log, capacity, ld, a));
+    hipLaunchKernelGGL(episode_log_init_kernel<>, dim3(grid_for(h->B)), dim3(BLOCK), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return NIG_OK;
+}
+
+int nig_collect_episodes(nig_handle *h, int32_t n_steps, const float *reward, const uint32_t *flags, int64_t out_stride,
+                         void *log, int64_t capacity, int64_t ld, void *stream)
+{
+    const char *fn = "nig_collect_episodes";
+    EpisodeLogArgs a;
+    NIG_TRY(episode_log_args(h, fn, log, capacity, ld, a));
+    if (n_steps < 1) return refuse(fn, "n_steps < 1");
+    if (!reward || !flags) return refuse(fn, "reward and flags rows are both required");
+    if (n_steps > 1 ? (out_stride < h->B || out_stride > NIG_MAX_PITCH) : (out_stride != 0 && (out_stride < h->B || out_stride > NIG_MAX_PITCH)))
+        return refuse(fn, "out_stride outside [batch, 2^26] (0 allowed with n_steps == 1)");
+    auto kernel = SPECS[h->env].reward_is_f32 ? collect_episodes_kernel<true> : collect_episodes_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(grid_for(h->B)), dim3(BLOCK), 0, (hipStream_t)stream, a, reward, flags, out_stride, (int)n_steps);
+    HIP_TRY(hipGetLastError());
+    return NIG_OK;
+}
+
+int nig_reduce_episodes(nig_handle *h, void *log, int64_t capacity, int64_t ld, int64_t n_episodes, double *partial_out,
+                        void *stream)
+{
+    const char *fn = "nig_reduce_episodes";
+    EpisodeLogArgs a;
+    NIG_TRY(episode_log_args(h, fn, log, capacity, ld, a));
+    if (!partial_out) return refuse(fn, "partial_out is NULL");
+    if (n_episodes < 1 || n_episodes > capacity * h->B) return refuse(fn, "n_episodes outside [1, capacity*batch]");
+    hipStream_t st = (hipStream_t)stream;
+    double *scratch = (double *)((char *)log + episode_log_layout(h->B, capacity, ld).off_scratch);
+    int nblk = (int)((h->B + BLOCK - 1) / BLOCK);
+    if (nblk > REDUCE_BLOCKS) nblk = REDUCE_BLOCKS;
+    hipLaunchKernelGGL(episode_tally_kernel<>, dim3(grid_for(h->B)), dim3(BLOCK), 0, st, a, n_episodes, enabled_constraints(h));
+    hipLaunchKernelGGL(reduce_tally_stage1, dim3(nblk), dim3(BLOCK), 0, st, (const double *)a.tally, a.ld, h->B, scratch);
+    hipLaunchKernelGGL(reduce_tally_stage2, dim3(1), dim3(REDUCE_BLOCKS), 0, st, (const double *)scratch, nblk, partial_out);
+    hipLaunchKernelGGL(episode_row_sum_kernel<>, dim3(1), dim3(BLOCK), 0, st, (const double *)(a.tally + (int64_t)NIG_T_ROWS * a.ld), h->B,
+                       partial_out + NIG_T_ROWS);
     HIP_TRY(hipGetLastError());
     return NIG_OK;
 }

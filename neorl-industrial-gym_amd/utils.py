@@ -136,20 +136,15 @@ def _disturbed_route(agent, env):
     return "host", None
 
 
-def _evaluate_batched(agent, env: BatchedIndustrialEnv, n_episodes: int, step_noise_fn=None, reset_noise_fn=None,
-                      group=None, reduce_across_ranks: bool = True, round_hook=None) -> Dict[str, Any]:
-    """Episodes in parallel lanes.  Rounds of up to B episodes: reset the needed lanes, step
-    until every one of them is done (finished lanes are frozen by the kernel), tallies
-    accumulate on the device; one reduction (+ all-gather across ranks) at the end.
-
-    step_noise_fn(round, t) / reset_noise_fn(round) may supply recorded draws (parity tests).
-    round_hook(env, k): called after every round of k episodes (lanes [0, k) hold their finished episodes' counters)."""
-    if not env.tally_enabled or env.autoreset:
-        raise ValueError("batched evaluation needs make_batched(..., tally=True, autoreset=False)")
-    B = env.batch
-    remaining, rnd = int(n_episodes), 0
-    device_policy = hasattr(agent, "to_struct") and step_noise_fn is None and reset_noise_fn is None
-    plain = step_noise_fn is None and reset_noise_fn is None
+def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
+    """Where `agent` runs on `env`, and its installation there -- the routing _evaluate_batched and episodes.evaluate_episodes
+    share.  Returns (agent, rollout, disturbed): `rollout` is the env method that plays n closed-loop steps with the agent in the
+    env kernel (rollout_policy, rollout_mlp, rollout_mlp_safe, rollout_mlp_ensemble or a _disturbed twin; policy, weights,
+    shield, ensemble and disturbance are installed on the handle), or None -- the agent stays on the host and takes the
+    per-step loop; `agent` may come back upgraded (a reference EnsembleAgent as an EnsemblePolicy); `disturbed` names the
+    fused route of a disturbance.Disturbed ("fused-policy" / "fused-mlp": the caller removes the disturbance afterwards).
+    plain = no recorded draws are injected (with them every agent takes the host loop)."""
+    device_policy = hasattr(agent, "to_struct") and plain
     if plain and all(hasattr(agent, k) for k in ("agents", "weights", "ensemble_method")) and not hasattr(agent, "install"):
         # the reference's EnsembleAgent: its K actors fused into the env kernel where members and env allow it (EnsemblePolicy);
         # otherwise the agent stays as it is and takes the host loop below
@@ -161,7 +156,7 @@ def _evaluate_batched(agent, env: BatchedIndustrialEnv, n_episodes: int, step_no
         except Exception:
             pass
     ensemble = plain and hasattr(agent, "install") and getattr(agent, "fusable", False) and env.state_dim % 2 == 0 and env.action_dim <= 16
-    fused_mlp = not hasattr(agent, "install") and getattr(agent, "fusable", False) and step_noise_fn is None and reset_noise_fn is None
+    fused_mlp = not hasattr(agent, "install") and getattr(agent, "fusable", False) and plain
     shielded = fused_mlp and getattr(agent, "safety_weights", None) is not None and hasattr(agent, "threshold")
     disturbed = None           # a disturbance.Disturbed whose inner agent runs in the env kernel: "fused-policy" / "fused-mlp"
     if plain and hasattr(agent, "disturbance") and hasattr(agent, "agent"):
@@ -183,7 +178,37 @@ def _evaluate_batched(agent, env: BatchedIndustrialEnv, n_episodes: int, step_no
         if shielded:        # MLPPolicy.shielded(): actor + safety critic + shield in the same kernel
             env.set_mlp_safety(agent.safety_weights, agent.threshold)
         device_policy = True
-    while remaining > 0 and device_policy:
+    rollout = None
+    if device_policy:
+        rollout = (env.rollout_policy_disturbed if disturbed == "fused-policy" else env.rollout_mlp_disturbed if disturbed
+                   else env.rollout_mlp_ensemble if ensemble else env.rollout_mlp_safe if shielded else env.rollout_mlp if fused_mlp
+                   else env.rollout_policy)
+    return agent, rollout, disturbed
+
+
+def _evaluate_batched(agent, env: BatchedIndustrialEnv, n_episodes: int, step_noise_fn=None, reset_noise_fn=None,
+                      group=None, reduce_across_ranks: bool = True, round_hook=None, episode_log=None, chunk: int = 250,
+                      launches=None) -> Dict[str, Any]:
+    """Episodes in parallel lanes.  Rounds of up to B episodes: reset the needed lanes, step
+    until every one of them is done (finished lanes are frozen by the kernel), tallies
+    accumulate on the device; one reduction (+ all-gather across ranks) at the end.
+
+    step_noise_fn(round, t) / reset_noise_fn(round) may supply recorded draws (parity tests).
+    round_hook(env, k): called after every round of k episodes (lanes [0, k) hold their finished episodes' counters).
+    episode_log (episodes.EpisodeLog): every launch writes its reward / flag rows and the log collects them -- a fused round in
+    pieces of `chunk` steps (a rollout cut into several launches equals one launch), the host loop step by step; `launches`
+    (a one-element list) counts the env launches then.  Without a log nothing changes."""
+    if not env.tally_enabled or env.autoreset:
+        raise ValueError("batched evaluation needs make_batched(..., tally=True, autoreset=False)")
+    B = env.batch
+    remaining, rnd = int(n_episodes), 0
+    plain = step_noise_fn is None and reset_noise_fn is None
+    agent, rollout, disturbed = _install_agent(agent, env, plain)
+    if episode_log is not None:
+        P = max(1, int(chunk))
+        rew = torch.empty(P, env.ld, dtype=torch.float32, device=env.device)
+        fl = torch.empty(P, env.ld, dtype=torch.int32, device=env.device)
+    while remaining > 0 and rollout is not None:
         # the agent runs ON the device: one fused launch plays every episode of the round to its end
         k = min(B, remaining)
         mask = torch.zeros(B, dtype=torch.uint8, device=env.device)
@@ -193,9 +218,15 @@ def _evaluate_batched(agent, env: BatchedIndustrialEnv, n_episodes: int, step_no
         # the Advanced envs truncate on the step AFTER the cap (advanced_chemical_reactor.py:351 and
         # advanced_power_grid.py:331 test episode_step before its increment): one step more for them
         extra = 1 if env.env_id.startswith("Advanced") else 0
-        (env.rollout_policy_disturbed if disturbed == "fused-policy" else env.rollout_mlp_disturbed if disturbed
-         else env.rollout_mlp_ensemble if ensemble else env.rollout_mlp_safe if shielded else env.rollout_mlp if fused_mlp
-         else env.rollout_policy)(env.max_episode_steps + extra)
+        if episode_log is None:
+            rollout(env.max_episode_steps + extra)
+        else:
+            for s0 in range(0, env.max_episode_steps + extra, P):
+                n = min(P, env.max_episode_steps + extra - s0)
+                rollout(n, rew, fl)
+                episode_log.collect(n, rew, fl)
+                if launches is not None:
+                    launches[0] += 1
         if round_hook is not None:
             round_hook(env, k)
         remaining -= k
@@ -212,6 +243,10 @@ def _evaluate_batched(agent, env: BatchedIndustrialEnv, n_episodes: int, step_no
         while True:
             act = _predict(agent, env.obs)
             env.step(act, step_noise=None if step_noise_fn is None else step_noise_fn(rnd, t), layout="aos")
+            if episode_log is not None:
+                episode_log.collect(1, env.reward, env.flags)
+                if launches is not None:
+                    launches[0] += 1
             t += 1
             if _round_is_over(env, t, hasattr(agent, "predict_device")) or t > _lib.MAX_EPISODE_STEPS:
                 break
