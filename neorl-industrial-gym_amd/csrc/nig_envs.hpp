@@ -249,7 +249,8 @@ struct ChemicalReactor {
     // _is_done :272-290
     __device__ static bool done(const float (&n)[S])
     {
-        return (n[8] > 0.5f) || (n[10] < 5.0f) || (n[10] > 95.0f) || (n[11] > 50.0f);
+        // all four compares, combined bitwise: a short-circuit || of per-lane values compiles to an EXEC-mask region
+        return (n[8] > 0.5f) | (n[10] < 5.0f) | (n[10] > 95.0f) | (n[11] > 50.0f);
     }
 };
 

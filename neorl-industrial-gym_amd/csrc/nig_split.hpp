@@ -28,6 +28,7 @@
 // (tests/test_gpu_parity.py, tests/test_spec_envs.py: the fused-rollout tests run this form wherever it applies,
 // tests/test_gpu_split.py pins it against the one-wave form).
 #pragma once
+#include <utility>
 #include "nig_ring.hpp"
 #include "nig_rollout.hpp"
 
@@ -59,6 +60,19 @@ struct SplitLds {
 };
 
 // (ring counters, waits, posts and the ordering assumption they rest on: nig_ring.hpp)
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>) in order: the step loops of the three roles are unrolled
+// with it over their static positions (ring slot, register set) -- nig_split_body.inc
+template <class F, int... R>
+__device__ __forceinline__ void split_unrolled_seq(F &&f, std::integer_sequence<int, R...>) { (f(std::integral_constant<int, R>{}), ...); }
+template <int N, class F>
+__device__ __forceinline__ void split_unrolled(F &&f) { split_unrolled_seq(f, std::make_integer_sequence<int, N>{}); }
+constexpr int split_lcm(int a, int b)
+{
+    int m = a;
+    while (m % b != 0) m += a;
+    return m;
+}
 
 // NP wave triples per block: wave w < NP integrates lanes base + 64 w .. + 63, wave NP + w is their producer and
 // wave 2 NP + w their recorder (a block's waves go to the CU's four SIMDs round-robin: with NP = 4 the three

@@ -9,6 +9,11 @@
     using Lds = SplitLds<Env, NP>;
     constexpr int K = Lds::K;
     constexpr int THREADS = 192 * NP;
+    // The ring slot of a step is a COMPILE-TIME constant in all three roles: every step loop is unrolled over the K slots
+    // (split_unrolled), so slot * HI_SLOT / slot * IH_SLOT ride in the DS instructions' offset fields on one per-lane base
+    // address per ring -- no slot counter, compare, select, multiply or address add per step.  (Largest offset: the last
+    // slot's last row, below K * IH_SLOT * 4 bytes; the field holds 16 bits.)
+    static_assert(K * Lds::IH_SLOT * 4 < 65536 && K * Lds::HI_SLOT * 4 < 65536, "slot offsets must fit the DS offset field");
     __shared__ __attribute__((aligned(16))) unsigned char smem[Lds::BYTES];
     float4 *const s_probit = reinterpret_cast<float4 *>(smem + Lds::OFF_PROBIT);
     const unsigned tid = threadIdx.x, lane = tid & 63u;
@@ -40,16 +45,23 @@
         // while step i is integrated; the counter is looked at afterwards, and only if the producer had not got
         // that far (it normally is several steps ahead) the wave spins and reads the slot again.  A read issued after
         // the counter read sees at least what the counter promised (DS operations of a wave execute in order).
-        // Two input register sets, the loop unrolled by two: no copies between them.
+        // Two input register sets and K ring slots, the loop unrolled by lcm(2, K): no copies between the sets, no slot arithmetic.
         float in0[KS + A], in1[KS + A];
-        auto read_inputs = [&](const int sl, float (&dst)[KS + A]) __attribute__((always_inline)) {
-            const float *hi = s_hi + sl * Lds::HI_SLOT;
+        const float *const hi_l = s_hi + lane;                               // per-lane bases: the slot is an immediate offset on them
+        v4f *const ih_row = reinterpret_cast<v4f *>(s_ih) + lane * (S / 4);
+        uint32_t *const ih_vb = reinterpret_cast<uint32_t *>(s_ih + S * 64) + lane;
+        auto read_inputs = [&](auto sl_tag, float (&dst)[KS + A]) __attribute__((always_inline)) {
+            constexpr int sl = decltype(sl_tag)::value;
 #pragma unroll
-            for (int k = 0; k < KS + A; ++k) dst[k] = hi[k * 64 + lane];
+            for (int k = 0; k < KS + A; ++k) dst[k] = hi_l[sl * Lds::HI_SLOT + k * 64];
         };
-        int slot = 0;
-        auto integrate = [&](const float (&in)[KS + A], float (&in_next)[KS + A], const int i) __attribute__((always_inline)) {
-            const int nslot = (slot + 1 == K) ? 0 : slot + 1;
+        // local step i: ring slot i mod K and input register set i mod 2, both static (r = i mod UI)
+        constexpr int UI = split_lcm(2, K);
+        auto integrate = [&](auto r_tag, const int i) __attribute__((always_inline)) {
+            constexpr int r = decltype(r_tag)::value, slot = r % K;
+            constexpr std::integral_constant<int, (slot + 1) % K> nslot{};
+            const float (&in)[KS + A] = (r & 1) ? in1 : in0;
+            float (&in_next)[KS + A] = (r & 1) ? in0 : in1;
             const uint32_t c_next = split_peek(sync + 0);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             read_inputs(nslot, in_next);
@@ -65,11 +77,9 @@
             StepResult<Env> res;
             post_core<Env, float>(nx, a, vb, step, p.max_steps, res);          // the reward part is dead here
             const bool done = res.terminated || res.truncated;
-            float *ih = s_ih + slot * Lds::IH_SLOT;
-            v4f *row = reinterpret_cast<v4f *>(ih) + lane * (S / 4);
 #pragma unroll
-            for (int k = 0; k < S / 4; ++k) { v4f v = {nx[4 * k], nx[4 * k + 1], nx[4 * k + 2], nx[4 * k + 3]}; row[k] = v; }
-            reinterpret_cast<uint32_t *>(ih + S * 64)[lane] = vb;
+            for (int k = 0; k < S / 4; ++k) { v4f v = {nx[4 * k], nx[4 * k + 1], nx[4 * k + 2], nx[4 * k + 3]}; ih_row[slot * (Lds::IH_SLOT / 4) + k] = v; }
+            ih_vb[slot * Lds::IH_SLOT] = vb;
             split_post(sync + 1, (uint32_t)i + 1u, lane);
             step = done ? 0 : step + 1;
             if constexpr (NOISE) {
@@ -92,16 +102,20 @@
                 split_wait(sync + 0, (uint32_t)i + 2u);
                 read_inputs(nslot, in_next);
             }
-            slot = nslot;
         };
         __builtin_amdgcn_s_waitcnt(0x0F70);       // state loads done: no vmcnt wait is carried into the loop
         __builtin_amdgcn_s_setprio(3);            // the critical path of the three: the SIMD's arbiter serves this wave first
-        if (n > 0) { split_wait(sync + 0, 1u); read_inputs(0, in0); }
+        if (n > 0) { split_wait(sync + 0, 1u); read_inputs(std::integral_constant<int, 0>{}, in0); }
         int i = 0;
-        for (; i + 2 <= n; i += 2) { integrate(in0, in1, i); integrate(in1, in0, i + 1); }
-        if (i < n) integrate(in0, in1, i);
+        for (; i + UI <= n; i += UI) split_unrolled<UI>([&](auto r_tag) __attribute__((always_inline)) { integrate(r_tag, i + decltype(r_tag)::value); });
+        // tail: at most UI - 1 steps, at their compile-time positions
+        split_unrolled<UI - 1>([&](auto r_tag) __attribute__((always_inline)) { if (i + decltype(r_tag)::value < n) integrate(r_tag, i + decltype(r_tag)::value); });
+        // (the store addresses are rebuilt from a fresh copy of the lane index: a per-lane address kept from the loads at the top
+        // would live across the unrolled loop, where RobotAssembly has no register to spare)
+        unsigned lane_st = lane;
+        asm volatile("" : "+v"(lane_st));
 #pragma unroll
-        for (int k = 0; k < S; ++k) (p.state + base + k * p.ld_state)[lane] = s[k];
+        for (int k = 0; k < S; ++k) (p.state + base + k * p.ld_state)[lane_st] = s[k];
         NIG_RING_REPORT(p.ring_err, sync, lane);
         return;
     }
@@ -124,11 +138,13 @@
             aslot = (aslot + 1 == q.ring_len) ? 0 : aslot + 1;
             act_next = (aslot == 0) ? ring : act_next + q.slot_stride;
         };
-        int pslot = 0;
+        float *const hi_l = s_hi + lane;                       // per-lane base: the slot is an immediate offset on it
         uint32_t freed = 0u;                                   // slots the recorder is known to be done with
-        // slot of local step j (r = j mod LA, static: action register set and position in the pair of launch counters)
-        auto produce = [&](auto r_tag, const int j) __attribute__((always_inline)) {
-            constexpr int r = decltype(r_tag)::value;
+        // local step j (u = j mod UP, static: ring slot u mod K, action register set r = u mod LA and position in the pair of
+        // launch counters)
+        constexpr int UP = split_lcm(LA, K);
+        auto produce = [&](auto u_tag, const int j) __attribute__((always_inline)) {
+            constexpr int r = decltype(u_tag)::value % LA, pslot = decltype(u_tag)::value % K;
             [[maybe_unused]] float (&ab)[A] = buf[r];
             typename Env::fast_noise_t nz[KN];
             if constexpr (KS > 0 && NOISE) {
@@ -155,41 +171,24 @@
             }
             clip_action<Env, float>(a);
             if (freed + (uint32_t)K < (uint32_t)j + 1u) freed = split_wait(sync + 2, (uint32_t)(j + 1 - K));   // the slot's previous use
-            float *hi = s_hi + pslot * Lds::HI_SLOT;
 #pragma unroll
-            for (int k = 0; k < KS; ++k) hi[k * 64 + lane] = (float)nz[k];    // exact: the fast-mode noise IS a float (nig_envs.hpp)
+            for (int k = 0; k < KS; ++k) hi_l[pslot * Lds::HI_SLOT + k * 64] = (float)nz[k];    // exact: the fast-mode noise IS a float (nig_envs.hpp)
 #pragma unroll
-            for (int k = 0; k < A; ++k) hi[(KS + k) * 64 + lane] = a[k];
+            for (int k = 0; k < A; ++k) hi_l[pslot * Lds::HI_SLOT + (KS + k) * 64] = a[k];
             NIG_RING_FAULT_GUARD(p.hflags, j) split_post(sync + 0, (uint32_t)j + 1u, lane);
             if constexpr (!SAMPLED) load_action(ab);     // this register set's next use: local step j + LA
-            pslot = (pslot + 1 == K) ? 0 : pslot + 1;
         };
-        // the loop is unrolled LA times so that every action register set and the position in the pair of launch counters
-        // are compile-time (LA even)
-        static_assert(LA % 2 == 0 && LA >= 2 && LA <= 8, "unrolled below for even depths up to 8");
+        // the loop is unrolled UP times so that the ring slot, every action register set and the position in the pair of launch
+        // counters are compile-time (LA even)
+        static_assert(LA % 2 == 0 && LA >= 2 && LA <= 8, "even look-ahead depths up to 8");
         if constexpr (!SAMPLED) {
 #pragma unroll
         for (int j = 0; j < LA; ++j) load_action(buf[j]);
         }
-        auto produce_k = [&](auto k_tag, const int j0) __attribute__((always_inline)) {
-            constexpr int k = decltype(k_tag)::value;
-            if constexpr (k < LA) produce(std::integral_constant<int, k>{}, j0 + k);
-        };
         int j = 0;
-        for (; j + LA <= n; j += LA) {
-            produce_k(std::integral_constant<int, 0>{}, j); produce_k(std::integral_constant<int, 1>{}, j);
-            produce_k(std::integral_constant<int, 2>{}, j); produce_k(std::integral_constant<int, 3>{}, j);
-            produce_k(std::integral_constant<int, 4>{}, j); produce_k(std::integral_constant<int, 5>{}, j);
-            produce_k(std::integral_constant<int, 6>{}, j); produce_k(std::integral_constant<int, 7>{}, j);
-        }
-        // tail: at most LA - 1 steps
-        auto tail_k = [&](auto k_tag) __attribute__((always_inline)) {
-            constexpr int k = decltype(k_tag)::value;
-            if constexpr (k < LA - 1) { if (j + k < n) produce(std::integral_constant<int, k>{}, j + k); }
-        };
-        tail_k(std::integral_constant<int, 0>{}); tail_k(std::integral_constant<int, 1>{}); tail_k(std::integral_constant<int, 2>{});
-        tail_k(std::integral_constant<int, 3>{}); tail_k(std::integral_constant<int, 4>{}); tail_k(std::integral_constant<int, 5>{});
-        tail_k(std::integral_constant<int, 6>{});
+        for (; j + UP <= n; j += UP) split_unrolled<UP>([&](auto u_tag) __attribute__((always_inline)) { produce(u_tag, j + decltype(u_tag)::value); });
+        // tail: at most UP - 1 steps
+        split_unrolled<UP - 1>([&](auto u_tag) __attribute__((always_inline)) { if (j + decltype(u_tag)::value < n) produce(u_tag, j + decltype(u_tag)::value); });
         NIG_RING_REPORT(p.ring_err, sync, lane);
         return;
     }
@@ -207,27 +206,29 @@
     float *obs_row = nullptr;
     if constexpr (OUT == 3) obs_row = q.obs_out + (size_t)q.it0 * q.obs_step_stride + (size_t)base * S;
     if constexpr (OUT == 2) obs_row = q.obs_out + (size_t)q.it0 * q.obs_step_stride + base;
-    int cslot = 0;
+    const v4f *const ih_row = reinterpret_cast<const v4f *>(s_ih) + lane * (S / 4);     // per-lane bases: the slot is an immediate offset on them
+    const v4f *const ih_img = reinterpret_cast<const v4f *>(s_ih) + lane;
+    const uint32_t *const ih_vb = reinterpret_cast<const uint32_t *>(s_ih + S * 64) + lane;
+    const float *const hi_a = s_hi + KS * 64 + lane;
     __builtin_amdgcn_s_waitcnt(0x0F70);           // counter / return loads done: the loop only ever stores
     uint32_t seen = 0u;
-    for (int i = 0; i < n; ++i) {
+    // local step i: ring slot i mod K, static
+    auto record = [&](auto sl_tag, const int i) __attribute__((always_inline)) {
+        constexpr int cslot = decltype(sl_tag)::value;
         if (seen < (uint32_t)i + 1u) seen = split_wait(sync + 1, (uint32_t)i + 1u);
         // what the integrator left: post-dynamics state (own row, and the wave's rows in lane-contiguous order),
         // violation bits of the pre-state; and the clipped action the step was handed (its P -> I slot is intact
         // until this wave says so)
-        const float *ih = s_ih + cslot * Lds::IH_SLOT;
-        const float *hi = s_hi + cslot * Lds::HI_SLOT;
         float nx[S], a[A];
-        const v4f *row = reinterpret_cast<const v4f *>(ih) + lane * (S / 4);
 #pragma unroll
-        for (int k = 0; k < S / 4; ++k) { const v4f v = row[k]; nx[4 * k] = v.x; nx[4 * k + 1] = v.y; nx[4 * k + 2] = v.z; nx[4 * k + 3] = v.w; }
-        const uint32_t vb = reinterpret_cast<const uint32_t *>(ih + S * 64)[lane];
+        for (int k = 0; k < S / 4; ++k) { const v4f v = ih_row[cslot * (Lds::IH_SLOT / 4) + k]; nx[4 * k] = v.x; nx[4 * k + 1] = v.y; nx[4 * k + 2] = v.z; nx[4 * k + 3] = v.w; }
+        const uint32_t vb = ih_vb[cslot * Lds::IH_SLOT];
 #pragma unroll
-        for (int k = 0; k < A; ++k) a[k] = hi[(KS + k) * 64 + lane];
+        for (int k = 0; k < A; ++k) a[k] = hi_a[cslot * Lds::HI_SLOT + k * 64];
         v4f tr[S / 4];
         if constexpr (OUT == 3) {                  // see rollout_body, OUT == 3
 #pragma unroll
-            for (int k = 0; k < S / 4; ++k) tr[k] = reinterpret_cast<const v4f *>(ih)[lane + 64u * k];
+            for (int k = 0; k < S / 4; ++k) tr[k] = ih_img[cslot * (Lds::IH_SLOT / 4) + 64 * k];
         }
         split_post(sync + 2, (uint32_t)i + 1u, lane);          // (DS order: the reads above execute before this write)
         const int step_pre = (int)(ctr & NIG_CTR_STEP_MASK);
@@ -268,8 +269,11 @@
             ret = lt.finish(tally, ret, step, viol_ep, res.ncrit);
             ctr = 0u;
         }
-        cslot = (cslot + 1 == K) ? 0 : cslot + 1;
-    }
+    };
+    int i = 0;
+    for (; i + K <= n; i += K) split_unrolled<K>([&](auto sl_tag) __attribute__((always_inline)) { record(sl_tag, i + decltype(sl_tag)::value); });
+    // tail: at most K - 1 steps
+    split_unrolled<K - 1>([&](auto sl_tag) __attribute__((always_inline)) { if (i + decltype(sl_tag)::value < n) record(sl_tag, i + decltype(sl_tag)::value); });
     (p.ctr + base)[lane] = ctr;
     if (lt.life != 0) (p.life_viol + base)[lane] += lt.life;
     if (tally) {

@@ -1,0 +1,140 @@
+#!/usr/bin/env python3
+"""Instructions per env-step, by class, of the step loops of the three-wave rollout kernels.  No GPU needed.
+
+    python profiles/isa_loops.py LISTING.s 'split_rollout_kernelINS_15ChemicalReactorELi3ELi4ELb0E' [more name fragments ...]
+
+LISTING.s is a device listing made with the build's own flags (see profiles/isa_diff.py).  The counting rule:
+
+  * The kernel's instructions form a graph: every instruction leads to the next one, a branch to its label (a conditional
+    branch to both).  A LOOP is a label that a later branch jumps back to.
+  * For every loop the SHORTEST path from the label round to itself is taken, counted in instructions.  That is the
+    iteration with every conditional side path NOT taken -- no spin on a ring counter, no re-read of a slot, no reset, no
+    finished episode.  Loops whose shortest iteration has fewer than 30 instructions (the spin loops) are dropped.
+  * The ring counters live at the DS offset of the store that zeroes them before the first barrier (+ 0, 4, 8: producer,
+    integrator, recorder).  A step posts to its role's counter exactly once, so the number of counter stores on the path is
+    the number of env-steps of the iteration, and the counter's index names the role.  Loops that post to no counter (the
+    cooperative reset's inner loops) are dropped.
+  * Classes by mnemonic: s_nop | SALU = every other s_* (waits and branches included) | VALU = v_* | DS = ds_* |
+    VMEM = global_* / flat_* / buffer_* / scratch_*.
+  * Reported: the iteration's counts divided by its steps.
+"""
+import re
+import sys
+from collections import deque
+
+ROLES = {0: "producer", 1: "integrator", 2: "recorder"}
+CLASSES = ["VALU", "SALU", "DS", "VMEM", "s_nop"]
+
+
+def kernel_body(lines, frag):
+    start = [i for i, l in enumerate(lines) if l.startswith("_ZN3nig") and frag in l and not l.startswith("\t") and ":" in l]
+    if not start:
+        raise SystemExit(f"no kernel matching {frag}")
+    i = j = start[0]
+    while not lines[j].startswith(".Lfunc_end"):
+        j += 1
+    return lines[i].split(":")[0], lines[i + 1:j]
+
+
+def klass(op):
+    if op == "s_nop":
+        return "s_nop"
+    if op.startswith("s_"):
+        return "SALU"
+    if op.startswith("v_"):
+        return "VALU"
+    if op.startswith("ds_"):
+        return "DS"
+    if op.startswith(("global_", "flat_", "buffer_", "scratch_")):
+        return "VMEM"
+    return "other"
+
+
+def program(body):
+    ins, labels = [], {}
+    for l in body:
+        t = l.split(";")[0].strip()
+        if not t:
+            continue
+        m = re.match(r"^(\.LBB\d+_\d+):", t)
+        if m:
+            labels[m.group(1)] = len(ins)
+        elif l.startswith("\t") and not t.startswith("."):
+            ins.append(t)
+    succ = []
+    for k, t in enumerate(ins):
+        op = t.split()[0]
+        if op == "s_branch":
+            succ.append([labels[t.split()[-1]]])
+        elif op.startswith("s_cbranch"):
+            succ.append([labels[t.split()[-1]], k + 1])
+        elif op == "s_endpgm":
+            succ.append([])
+        else:
+            succ.append([k + 1] if k + 1 < len(ins) else [])
+    return ins, succ
+
+
+def shortest_cycle(succ, h):
+    """instructions of the shortest path from h back to h (h included once)"""
+    prev, todo = {}, deque()
+    for s in succ[h]:
+        if s not in prev:
+            prev[s] = h
+            todo.append(s)
+    while todo:
+        k = todo.popleft()
+        if k == h:
+            break
+        for s in succ[k]:
+            if s not in prev:
+                prev[s] = k
+                todo.append(s)
+    if h not in prev:
+        return None
+    path, k = [], prev[h]
+    while k != h:
+        path.append(k)
+        k = prev[k]
+    path.append(h)
+    return path[::-1]
+
+
+def counter_offset(ins):
+    first_barrier = next(k for k, t in enumerate(ins) if t.split()[0] == "s_barrier")
+    init = [t for t in ins[:first_barrier] if t.split()[0] == "ds_write_b32"]
+    m = re.search(r"offset:(\d+)", init[-1])
+    return int(m.group(1)) if m else 0
+
+
+def report(path, frag):
+    lines = open(path).read().split("\n")
+    name, body = kernel_body(lines, frag)
+    ins, succ = program(body)
+    off = counter_offset(ins)
+    print(f"{name}\n  {len(ins)} instructions in the kernel; ring counters at DS offset {off}")
+    headers = sorted({t for k, ss in enumerate(succ) for t in ss if t <= k})
+    for h in headers:
+        cyc = shortest_cycle(succ, h)
+        if cyc is None or len(cyc) < 30:
+            continue
+        posts = []
+        for k in cyc:
+            t = ins[k]
+            m = re.search(r"offset:(\d+)", t)
+            if t.split()[0] == "ds_write_b32" and m and int(m.group(1)) - off in (0, 4, 8):
+                posts.append((int(m.group(1)) - off) // 4)
+        if not posts or len(set(posts)) != 1:
+            continue
+        steps = len(posts)
+        n = {c: 0 for c in CLASSES + ["other"]}
+        for k in cyc:
+            n[klass(ins[k].split()[0])] += 1
+        per = "  ".join(f"{c} {n[c] / steps:6.1f}" for c in CLASSES)
+        print(f"  {ROLES[posts[0]]:10s} {steps:2d} steps per iteration, {len(cyc):4d} instructions: per step {len(cyc) / steps:6.1f} = {per}"
+              + (f"  other {n['other'] / steps:.1f}" if n["other"] else ""))
+
+
+if __name__ == "__main__":
+    for frag in sys.argv[2:]:
+        report(sys.argv[1], frag)
