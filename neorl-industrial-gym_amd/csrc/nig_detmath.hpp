@@ -67,7 +67,7 @@ __device__ __forceinline__ float bits_f32(uint32_t u) { return __uint_as_float(u
 __device__ __forceinline__ uint32_t f32_bits(float f) { return __float_as_uint(f); }
 
 // e^x, float32, Cephes-style: k = floor(x*log2e + 1/2), two-constant Cody-Waite, degree-5
-// polynomial in fused multiply-adds, exact two-step scaling.  <= 1 ulp-ish; stands in for np.exp on float32
+// polynomial in fused multiply-adds, scaling by 2^k rounded once.  <= 1 ulp-ish; stands in for np.exp on float32
 // (chemical_reactor.py:177), which itself is only good to ~2 ulp.
 __device__ __forceinline__ float det_expf(float x)
 {
@@ -83,11 +83,13 @@ __device__ __forceinline__ float det_expf(float x)
     p = __builtin_fmaf(p, r, 5.0000001201e-1f);
     p = __builtin_fmaf(p, z, r);
     p = p + 1.0f;
-    // clamp only affects the out-of-range inputs that are overridden below
-    fk = fminf(fmaxf(fk, -200.0f), 200.0f);
-    const int k = (int)fk;
-    const int k1 = k / 2, k2 = k - k1;
-    float res = (p * bits_f32((uint32_t)(k1 + 127) << 23)) * bits_f32((uint32_t)(k2 + 127) << 23);
+    // p 2^k in ONE rounding and one instruction (v_ldexp_f32).  The former form -- k = k1 + k2, (p 2^k1) 2^k2, eleven
+    // instructions with the clamp and the two exponent words -- rounded once as well (the first product is exact), so the bits
+    // are the same for every input that is not overridden below: tests/expf_scale_check.c compares the two over the whole
+    // domain.  The oracle restates the two-step form.  The clamp keeps the conversion defined (a NaN becomes -200: v_med3_f32
+    // returns the minimum of the other two) and only affects the out-of-range inputs that are overridden below.
+    fk = __builtin_amdgcn_fmed3f(fk, -200.0f, 200.0f);
+    float res = __builtin_ldexpf(p, (int)fk);
     res = (x < -103.0f) ? 0.0f : res;
     res = (x > 88.72283f) ? __builtin_inff() : res;
     res = (x != x) ? x : res;

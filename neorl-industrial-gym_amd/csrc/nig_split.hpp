@@ -17,13 +17,15 @@
 // They exchange through two rings of K slots in LDS, each guarded by a monotonically increasing counter (slots
 // produced so far), plus the recorder's count of slots it is done with.  P -> I slot: the KS noise values and A
 // clipped actions of one step, [row][lane].  I -> C slot: the S post-dynamics state values row-major [lane][S]
-// (this IS the transposing image of the row-major trajectory) plus the violation bits of the pre-state; C also
+// (this IS the transposing image of the row-major trajectory) plus one word with the violation bits of the pre-state and
+// how the step ended (terminated, truncated: outcome_word, nig_step.hpp -- I decides it once, C takes it); C also
 // reads the clipped action back from the P -> I slot.  DS operations of one wave execute in order, so "write data,
 // then write counter" / "read counter, then read data" needs no wait in between; the wavefront-scope fences only
 // pin the compiler's order.  No block barrier inside the loop.  Flow control: P writes slot j only after C is
 // done with slot j - K; I needs P's slot j before it writes its own slot j, so it cannot overrun C either.
 //
-// The arithmetic is the other kernels': same clip, violated, dynamics, post_core, pack_flags, tally and reset
+// The arithmetic is the other kernels': same clip, violated, dynamics, post_core (I; C adds post_finish's penalties to the
+// same reward and reads pack_flags' bits off a table checked against it at compile time: post_record), tally and reset
 // calls on the same values with the same generator keys -- the results are bit-identical to rollout_kernel's
 // (tests/test_gpu_parity.py, tests/test_spec_envs.py: the fused-rollout tests run this form wherever it applies,
 // tests/test_gpu_split.py pins it against the one-wave form).

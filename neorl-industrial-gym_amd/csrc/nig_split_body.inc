@@ -79,7 +79,7 @@
             const bool done = res.terminated || res.truncated;
 #pragma unroll
             for (int k = 0; k < S / 4; ++k) { v4f v = {nx[4 * k], nx[4 * k + 1], nx[4 * k + 2], nx[4 * k + 3]}; ih_row[slot * (Lds::IH_SLOT / 4) + k] = v; }
-            ih_vb[slot * Lds::IH_SLOT] = vb;
+            ih_vb[slot * Lds::IH_SLOT] = outcome_word(vb, res.terminated, res.truncated);   // the recorder takes the outcome from here (post_record)
             split_post(sync + 1, (uint32_t)i + 1u, lane);
             step = done ? 0 : step + 1;
             if constexpr (NOISE) {
@@ -91,7 +91,7 @@
                     Env::init(rn, nx);
                 }
             } else {
-            const unsigned long long m = __ballot(done);
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(done);      // (the mask itself: __ballot takes an int, a 0 / 1 register and a compare back)
             if (m != 0ull)
                 coop_reset<Env>(m, done, lane, s_img, s_wlist, p.env0 + (uint64_t)base, t_base + (uint32_t)i + 1u,
                                 p.seed_lo, p.seed_hi, s_probit, nx);
@@ -222,7 +222,7 @@
         float nx[S], a[A];
 #pragma unroll
         for (int k = 0; k < S / 4; ++k) { const v4f v = ih_row[cslot * (Lds::IH_SLOT / 4) + k]; nx[4 * k] = v.x; nx[4 * k + 1] = v.y; nx[4 * k + 2] = v.z; nx[4 * k + 3] = v.w; }
-        const uint32_t vb = ih_vb[cslot * Lds::IH_SLOT];
+        const uint32_t word = ih_vb[cslot * Lds::IH_SLOT];     // violation bits and the step's outcome (outcome_word)
 #pragma unroll
         for (int k = 0; k < A; ++k) a[k] = hi_a[cslot * Lds::HI_SLOT + k * 64];
         v4f tr[S / 4];
@@ -231,19 +231,19 @@
             for (int k = 0; k < S / 4; ++k) tr[k] = ih_img[cslot * (Lds::IH_SLOT / 4) + 64 * k];
         }
         split_post(sync + 2, (uint32_t)i + 1u, lane);          // (DS order: the reads above execute before this write)
-        const int step_pre = (int)(ctr & NIG_CTR_STEP_MASK);
-        StepResult<Env> res;
+        const int step = (int)(ctr & NIG_CTR_STEP_MASK) + 1;
 #ifdef NIG_DIAG_SPLIT_REC_NOCOMPUTE    // (diagnostic builds only, profiles/r05: the recorder as a pure store wave -- no reward, penalties, flags or
         // tally arithmetic, the same LDS reads and the same stores -- the upper bound of what a fourth, store-only wave per triple
         // could give the headline, VERDICT r04 next #7; results are garbage)
-        res.reward = nx[0] + a[0]; res.terminated = false; res.truncated = false; res.nviol = (int)(vb & 1u); res.ncrit = 0; res.viol_bits = vb; res.shutdown = false;
+        StepRecord<Env> res;
+        res.reward = nx[0] + a[0]; res.flags = word; res.nviol = (int)(word & 1u); res.ncrit = 0; res.done = false;
 #else
-        post_core<Env, float>(nx, a, vb, step_pre, p.max_steps, res);
+        // the integrator decided how the step ended; reward, penalties and the flag word are this wave's
+        const StepRecord<Env> res = post_record<Env>(nx, a, word, step);
 #endif
-        const int step = step_pre + 1;
         const uint32_t viol_ep = episode_violations(ctr, res.nviol);
-        const bool done = res.terminated || res.truncated;
-        const uint32_t fl = pack_flags<Env>(res, step) | did_reset_flag(done);
+        const bool done = res.done;
+        const uint32_t fl = res.flags;
         ctr = counter_word(step, viol_ep);
         if (tally) ret = add_reward<Env>(ret, res.reward);
         if constexpr (OUT == 3) {

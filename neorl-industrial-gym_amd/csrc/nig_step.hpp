@@ -81,7 +81,7 @@ __device__ __forceinline__ void step_core(const float (&s)[Env::S], AT (&a)[Env:
 
 // The per-lane flag word of one step (include/nig.h NIG_FLAG_*).
 template <class Env, class R>
-__device__ __forceinline__ uint32_t pack_flags(const StepResult<Env, R> &res, int step)
+__device__ __forceinline__ constexpr uint32_t pack_flags(const StepResult<Env, R> &res, int step)
 {
     uint32_t f = (res.terminated ? NIG_FLAG_TERMINATED : 0u) | (res.truncated ? NIG_FLAG_TRUNCATED : 0u) |
                  ((res.viol_bits & 7u) << NIG_FLAG_VIOL_SHIFT) | (((uint32_t)res.nviol & 3u) << NIG_FLAG_NVIOL_SHIFT) |
@@ -90,6 +90,81 @@ __device__ __forceinline__ uint32_t pack_flags(const StepResult<Env, R> &res, in
     if constexpr (Env::CUSTOM_STEP)                // only the Advanced envs carry a 4th condition / a count of 4
         f |= ((res.viol_bits & 8u) ? NIG_FLAG_VIOL3 : 0u) | (((uint32_t)res.nviol & 4u) ? NIG_FLAG_NVIOL_HI : 0u);
     return f;
+}
+
+// ---- a step's outcome decided once, by the wave that needs it first (the three-wave form, nig_split_body.inc) ----------------
+// The integrator learns `terminated` and `truncated` from its own post_core call (it needs them for the reset) and hands them to
+// the recorder with the violation bits of the pre-state, in the one word it writes into its ring slot anyway:
+//   violation bits (0-2) | terminated << 8 | truncated << 9
+// -- bits 8-9 are NIG_FLAG_TERMINATED | NIG_FLAG_TRUNCATED eight places up.  The recorder no longer runs Env::done, the critical
+// test and the step compare on the same values again (post_record below).
+constexpr int OUTCOME_SHIFT = 8;
+__device__ __forceinline__ uint32_t outcome_word(uint32_t vb, bool terminated, bool truncated)
+{
+    return vb | (terminated ? NIG_FLAG_TERMINATED << OUTCOME_SHIFT : 0u) | (truncated ? NIG_FLAG_TRUNCATED << OUTCOME_SHIFT : 0u);
+}
+
+// Bits 2-9 of the flag word -- violation bits, violation count, critical count, shutdown -- are a function of the three violation
+// bits alone for an env that goes through post_finish: eight bytes in one 64-bit constant, byte vb = those bits for vb, from the
+// fields' own definitions (include/nig.h).  Two bit counts, three shifts, three ands, a select and three ors per step become a
+// shift of the constant.
+template <class Env>
+__device__ constexpr uint64_t violation_flag_table()
+{
+    uint64_t t = 0;
+    for (uint32_t vb = 0; vb < 8u; ++vb) {
+        const uint32_t nviol = (uint32_t)__builtin_popcount(vb), ncrit = (uint32_t)__builtin_popcount(vb & Env::CRIT_MASK);
+        const uint32_t f = (vb << NIG_FLAG_VIOL_SHIFT) | (nviol << NIG_FLAG_NVIOL_SHIFT) | (ncrit << NIG_FLAG_NCRIT_SHIFT) |
+                           (ncrit > 0u ? NIG_FLAG_SHUTDOWN : 0u);
+        t |= (uint64_t)(f >> NIG_FLAG_VIOL_SHIFT) << (8u * vb);
+    }
+    return t;
+}
+// the table against pack_flags on what post_finish makes of vb, all eight values: every bit of the word but the two outcome bits
+template <class Env>
+__device__ constexpr bool violation_flag_table_is_pack_flags(uint64_t table)
+{
+    for (uint32_t vb = 0; vb < 8u; ++vb) {
+        StepResult<Env> r{};
+        r.viol_bits = vb; r.nviol = __builtin_popcount(vb); r.ncrit = __builtin_popcount(vb & Env::CRIT_MASK);
+        r.terminated = false; r.truncated = false; r.shutdown = r.ncrit > 0;
+        if (pack_flags<Env>(r, 0) != (((uint32_t)(table >> (8u * vb)) & 0xFFu) << NIG_FLAG_VIOL_SHIFT)) return false;
+    }
+    return true;
+}
+
+// What the recorder makes of a step whose outcome is decided: the reward (base.py:176-183,195-198: post_finish's penalty and
+// shutdown adds, in its order, on Env::reward), the flag word, the two counts the episode bookkeeping takes.
+template <class Env>
+struct StepRecord {
+    typename Env::reward_t reward;
+    uint32_t flags;            // the whole word of pack_flags | did_reset_flag
+    int nviol, ncrit;
+    bool done;
+};
+template <class Env>
+__device__ __forceinline__ StepRecord<Env> post_record(const float (&n)[Env::S], const float (&a)[Env::A], uint32_t word, int step)
+{
+    using R = typename Env::reward_t;
+    constexpr uint64_t TABLE = violation_flag_table<Env>();
+    static_assert(!Env::CUSTOM_STEP && NIG_FLAG_SHUTDOWN >> NIG_FLAG_VIOL_SHIFT < 256u && violation_flag_table_is_pack_flags<Env>(TABLE),
+                  "the table is pack_flags' bits 2-9 for the eight values of the violation bits");
+    static_assert(NIG_FLAG_TERMINATED == 1u && NIG_FLAG_TRUNCATED == 2u, "outcome_word: the two bits as the flag word has them");
+    StepRecord<Env> out;
+    R r = Env::reward(n, a);                       // base.py:176
+#pragma unroll
+    for (int k = 0; k < 3; ++k)                   // base.py:179-183, constraint order
+        r = (word & (1u << k)) ? (R)(r + (R)Env::penalty(k)) : r;
+    if ((word & Env::CRIT_MASK) != 0u) r = r - (R)1000;     // base.py:195-198
+    out.reward = r;
+    // (a 64-bit shift takes the low six bits of its count: the outcome bits above them fall away)
+    const uint32_t fields = (uint32_t)(TABLE >> ((word << 3) & 63u)) & 0xFFu;
+    const uint32_t outcome = (word >> OUTCOME_SHIFT) & (NIG_FLAG_TERMINATED | NIG_FLAG_TRUNCATED);
+    out.done = outcome != 0u;
+    out.flags = outcome | (fields << NIG_FLAG_VIOL_SHIFT) | did_reset_flag(out.done) | ((uint32_t)step << NIG_FLAG_STEP_SHIFT);
+    out.nviol = (int)((fields >> (NIG_FLAG_NVIOL_SHIFT - NIG_FLAG_VIOL_SHIFT)) & 3u);
+    out.ncrit = (int)((fields >> (NIG_FLAG_NCRIT_SHIFT - NIG_FLAG_VIOL_SHIFT)) & 3u);
+    return out;
 }
 
 // Per-lane key of the counter-based generator: (global env index, launch counter t).

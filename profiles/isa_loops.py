@@ -14,6 +14,8 @@ LISTING.s is a device listing made with the build's own flags (see profiles/isa_
     integrator, recorder).  A step posts to its role's counter exactly once, so the number of counter stores on the path is
     the number of env-steps of the iteration, and the counter's index names the role.  Loops that post to no counter (the
     cooperative reset's inner loops) are dropped.
+  * A forward s_cbranch_execz whose skipped block holds a counter store (the post's `if (lane == 0)`) is not a side path:
+    lane 0 exists, the branch falls through.
   * Classes by mnemonic: s_nop | SALU = every other s_* (waits and branches included) | VALU = v_* | DS = ds_* |
     VMEM = global_* / flat_* / buffer_* / scratch_*.
   * Reported: the iteration's counts divided by its steps.
@@ -107,11 +109,25 @@ def counter_offset(ins):
     return int(m.group(1)) if m else 0
 
 
+def keep_posts(ins, succ, off):
+    """A post is `if (lane == 0) store`: s_and_saveexec, the store, s_or exec.  When the compiler keeps an s_cbranch_execz
+    round the store (it does when a wait lands in that block) the skip is never taken by a whole wave -- lane 0 exists --
+    so it is not a side path: the branch falls through."""
+    for k, t in enumerate(ins):
+        if t.split()[0] == "s_cbranch_execz" and len(succ[k]) == 2 and succ[k][0] > k:
+            for u in ins[k + 1:succ[k][0]]:
+                m = re.search(r"offset:(\d+)", u)
+                if u.split()[0] == "ds_write_b32" and m and int(m.group(1)) - off in (0, 4, 8):
+                    succ[k] = [k + 1]
+                    break
+
+
 def report(path, frag):
     lines = open(path).read().split("\n")
     name, body = kernel_body(lines, frag)
     ins, succ = program(body)
     off = counter_offset(ins)
+    keep_posts(ins, succ, off)
     print(f"{name}\n  {len(ins)} instructions in the kernel; ring counters at DS offset {off}")
     headers = sorted({t for k, ss in enumerate(succ) for t in ss if t <= k})
     for h in headers:
