@@ -711,10 +711,11 @@ class MixedBatchedEnv:
     each (every wavefront is homogeneous); all segments share ONE observation matrix
     `state_soa` [S_max, LD] (rows >= S of a segment stay zero) and one action matrix layout
     [A_max, LD].  Each segment is a BatchedIndustrialEnv bound to its columns; a step or rollout
-    launches one kernel per segment, each on its own HIP stream."""
+    launches one kernel per segment, each on its own HIP stream.  max_episode_steps (optional) replaces every segment's
+    own episode limit."""
 
     def __init__(self, segments, device="cuda:0", seed: int = 0x5EED, autoreset: bool = True, tally: bool = False,
-                 env_index0: int = 0, fused: bool = True):
+                 env_index0: int = 0, fused: bool = True, max_episode_steps: Optional[int] = None):
         self.device = torch.device(device)
         segs = list(segments.items()) if isinstance(segments, dict) else list(segments)
         self.S_max = max(int(_lib.env_spec(ENV_IDS[e]).state_dim) for e, _ in segs)
@@ -733,7 +734,7 @@ class MixedBatchedEnv:
         self.envs = []
         for (e, n), o in zip(segs, offs):
             self.envs.append(BatchedIndustrialEnv(e, int(n), device=device, seed=seed, env_index0=env_index0 + o,
-                                                  autoreset=autoreset, tally=tally,
+                                                  autoreset=autoreset, tally=tally, max_episode_steps=max_episode_steps,
                                                   bind_state=self.state_soa[:, o:o + int(n)]))
         self._streams = [torch.cuda.Stream(device=self.device) for _ in self.envs]
         self.fused = bool(fused)

@@ -35,7 +35,16 @@ and the two step-noise draws of launch counters 2k-1 and 2k come from ONE genera
 counter, 2-3 for the even one -- ChemicalReactor's rule; v1 drew a block per step and threw half of it away).
 ("v1", up to 0.3.0, rounded the product and the sum separately: twice the instructions on a device whose multiply-add is
 one instruction, and no CPU without an FMA unit is a target of the statement.)
-Each safety constraint is a box over a run of state rows.
+Each safety constraint is a box over a run of state rows: (name, first row, row count, lo, hi, penalty, critical).
+
+The step around the model is the base template: the action is clipped to [-1, 1]; a constraint holds when lo <= v <= hi
+(both bounds INCLUSIVE, a NaN row fails) for every row of its run, evaluated on the state BEFORE the step and only if it
+is enabled in the handle's constraint mask; each violated constraint adds its penalty to the reward, a violated critical
+one also subtracts 1000 and terminates the episode.  The bonus is decided by constraint 0 on the NEW state (mask or not).
+The coupling reads the OLD y_cidx.  done = (row, lo, hi): the episode terminates when y'_row < lo or y'_row > hi (strict);
+it is truncated when the step count reaches max_steps.  reset: y_i = float32(float64(y0_i) + float64(sd0_i) float64(z_i))
+with z a float32 standard normal, actuators 0.5, accounting rows 0.  tests/spec_plant_model.py evaluates exactly this text
+in float64, from the dicts below by name, and the kernels and the CPU statement are held against it.
 
 This file is the single source of the numbers: `python spec_plants.py` regenerates
 csrc/nig_spec_plants.inc and oracle/nig_spec_plants.inc (tests check they are current).

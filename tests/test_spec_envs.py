@@ -3,7 +3,8 @@
 The reference names them in its README (README.md:28-32) and ships no implementation, so there is
 NO reference parity to test: these tests pin the build-specified plants (spec_plants.py) as such --
 generated tables current, plants behave like controlled processes, and the HIP kernels equal the
-independent CPU statement bit for bit in every launch shape.
+independent CPU statement bit for bit in every launch shape.  The written model itself is evaluated independently and in
+float64 by tests/spec_plant_model.py; test_spec_plant_model.py and test_gpu_spec_plant_model.py hold both against it.
 """
 import os
 
