@@ -41,6 +41,10 @@ struct ChemicalReactor {
     // work item = (lane, generator block) -> four state rows through a wave-private LDS image: one short pass.
     static constexpr bool COOP_RESET = true;
     static constexpr int RESET_ITEMS = 2, RESET_ROWS = 8;
+    // Episodes last ~360 steps: a wave has a finishing lane in one step of six, and then nearly always exactly one.  The
+    // three-wave forms restart it by coop_reset's short path (nig_step.hpp, QUICK).  Envs whose waves finish several lanes
+    // in most steps (PowerGrid ~11, RobotAssembly most of them) do not define this and keep the work list.
+    static constexpr bool QUICK_RESET = true;
     using fast_noise_t = double;
     static constexpr int ID = 0, S = 12, A = 3, KS = 2, KR = 8, MAX_STEPS = 500;
     static constexpr bool COMPACT_RESET = false;
@@ -81,17 +85,35 @@ struct ChemicalReactor {
     // One work item of a cooperative reset: generator block `blk` (0 or 1) of the lane with key `k` -> image rows
     // 4 blk .. 4 blk + 3 = initial values of state rows {0,1,2,3} / {4,5,6,10}; same values, operation by operation,
     // as draw_init + init.
-    __device__ static void reset_item(const RngKey &k, uint32_t blk, float *img, unsigned owner)
+    // FETCH_FIRST: all four table fetches, then the cubics and the image stores (as step_noise_fetch / step_noise_eval).
+    // Normal by normal, an image store stands between two fetches; it may alias the table for all the compiler knows, so
+    // every fetch sits behind an LDS wait of its own: four dependent round trips where one wait would do.  The sixteen
+    // coefficient registers are live for a few instructions only, but in the one-wave kernels that is on top of the action
+    // register sets and costs them a wave per SIMD (rollout_kernel 119 -> 132 VGPRs): only the restart of the three-wave
+    // forms, whose integrator wave waits out every one of those trips, takes it (reset_item_quick).
+    template <bool FETCH_FIRST>
+    __device__ static void reset_item_as(const RngKey &k, uint32_t blk, float *img, unsigned owner)
     {
         const u32x4 x = k.block(STREAM_RESET + blk);
         const uint32_t w[4] = {x.x, x.y, x.z, x.w};
         const bool hi = blk != 0u;
         const float sd[4] = {hi ? 0.1f : 2.0f, hi ? 2.0f : 10000.0f, hi ? 1.0f : 5.0f, hi ? 5.0f : 3.0f};          // :93-103
         const float mean[4] = {hi ? 0.5f : 320.0f, hi ? 95.0f : 253312.5f, hi ? 295.0f : 50.0f, hi ? 60.0f : 30.0f};
+        if constexpr (FETCH_FIRST) {
+            ProbitFetch f[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) f[q] = probit_fetch(w[q], k.tab);
+            __builtin_amdgcn_sched_barrier(0);             // (left alone, hipcc issues the fetches in two pairs, the second behind the first's wait)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) img[(4u * blk + (uint32_t)q) * 64u + owner] = mean[q] + sd[q] * probit_eval(f[q]);
+        } else {
 #pragma unroll
         for (int q = 0; q < 4; ++q)     // == (float)((double)mean + (double)(sd * z)): exact in double, rounded once
             img[(4u * blk + (uint32_t)q) * 64u + owner] = mean[q] + sd[q] * probit_normal(w[q], k.tab);
+        }
     }
+    __device__ static void reset_item(const RngKey &k, uint32_t blk, float *img, unsigned owner) { reset_item_as<false>(k, blk, img, owner); }
+    __device__ static void reset_item_quick(const RngKey &k, uint32_t blk, float *img, unsigned owner) { reset_item_as<true>(k, blk, img, owner); }
     __device__ static void reset_readback(const float *img, unsigned lane, float (&s)[S])
     {
 #pragma unroll
@@ -385,10 +407,13 @@ struct PowerGrid {
         // V 1.0 + 0.01 z (:98), gen base_load + 2.0 z (:101), flows 10.0 z (:108)
         const float sd = blk < 2u ? 0.01f : (blk < 4u ? 2.0f : 10.0f);
         const uint32_t row0 = (blk < 4u ? 1u : 9u) + 4u * blk;
+        ProbitFetch f[4];                // the four table fetches before the first put: see ChemicalReactor::reset_item_as
+#pragma unroll
+        for (int q = 0; q < 4; ++q) f[q] = probit_fetch(w[q], k.tab);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const float off = blk < 2u ? 1.0f : (blk < 4u ? (float)(hi ? base_load(4 + q) : base_load(q)) : 0.0f);
-            const float v = off + sd * probit_normal(w[q], k.tab);      // flows: 0.0 + d == d (d is never -0.0)
+            const float v = off + sd * probit_eval(f[q]);               // flows: 0.0 + d == d (d is never -0.0)
             if (q < 3 || blk != 5u) put(row0 + (uint32_t)q, v);   // z[23] does not exist
         }
         if (blk == 0u) put(0u, 0.0f);

@@ -91,10 +91,19 @@
                     Env::init(rn, nx);
                 }
             } else {
+#ifdef NIG_DIAG_SPLIT_NORESTART        // (diagnostic builds only, profiles/split_restart: a finishing lane restarts from the MEANS of its initial
+            // state -- no ballot branch, no generator, no LDS trip; ring protocol and stores untouched, results are garbage: the
+            // launch-time difference to the production build is the upper bound of everything a cheaper restart can give)
+            if (done) {
+                double zero[Env::KR > 0 ? Env::KR : 1] = {};
+                Env::init(zero, nx);
+            }
+#else
             const unsigned long long m = __builtin_amdgcn_ballot_w64(done);      // (the mask itself: __ballot takes an int, a 0 / 1 register and a compare back)
             if (m != 0ull)
-                coop_reset<Env>(m, done, lane, s_img, s_wlist, p.env0 + (uint64_t)base, t_base + (uint32_t)i + 1u,
-                                p.seed_lo, p.seed_hi, s_probit, nx);
+                coop_reset<Env, quick_reset<Env>::value>(m, done, lane, s_img, s_wlist, p.env0 + (uint64_t)base, t_base + (uint32_t)i + 1u,
+                                                         p.seed_lo, p.seed_hi, s_probit, nx);
+#endif
             }
 #pragma unroll
             for (int k = 0; k < S; ++k) s[k] = nx[k];

@@ -221,8 +221,8 @@ __global__ void __launch_bounds__(192 * NP, 1) split_policy_kernel(const PolicyA
             step = done ? 0 : step + 1;
             const unsigned long long m = __ballot(done);
             if (m != 0ull)
-                coop_reset<Env>(m, done, lane, s_img, s_wlist, p.env0 + (uint64_t)base, t_base + (uint32_t)i + 1u,
-                                p.seed_lo, p.seed_hi, s_probit, nx);
+                coop_reset<Env, quick_reset<Env>::value>(m, done, lane, s_img, s_wlist, p.env0 + (uint64_t)base, t_base + (uint32_t)i + 1u,
+                                                         p.seed_lo, p.seed_hi, s_probit, nx);
 #pragma unroll
             for (int k = 0; k < S; ++k) s[k] = nx[k];
             slot = (slot + 1 == K) ? 0 : slot + 1;

@@ -244,13 +244,38 @@ __device__ __forceinline__ void draw_one(const RngKey &k, NZ (&n)[Env::KS > 0 ? 
 // read their column back.  No block barrier.  DS operations of one wave execute in order, so the reads see the
 // writes issued before them without a wait in between; the fences only pin the compiler's ordering.
 // `lane_gi0` = global env index of the wave's lane 0, `t` = launch counter of the step that finished.
+// QUICK (compile-time; the three-wave forms of an env with QUICK_RESET, whose integrator wave has nothing to overlap a
+// restart with): (1) a step with exactly ONE finishing lane -- nearly every restart of a wave whose lanes finish once in a
+// few hundred steps -- skips the work list.  `m` is wave-uniform, so its population count, the owner ctz(m) and the branch
+// live on the scalar unit; lanes 0 .. ITEMS-1 run the owner's items directly: no list write, no list read, no wait between
+// the ballot and the generator.  Two or more finishers take the list.  (2) The items are Env::reset_item_quick: the same
+// values by the same operations, scheduled for latency.
+template <class Env, class = void>
+struct quick_reset : std::false_type {};
 template <class Env>
+struct quick_reset<Env, std::enable_if_t<Env::QUICK_RESET>> : std::true_type {};
+
+template <class Env, bool QUICK = false>
 __device__ __forceinline__ void coop_reset(unsigned long long m, bool mine, unsigned lane, float *img, unsigned char *lst,
                                            uint64_t lane_gi0, uint32_t t, uint32_t seed_lo, uint32_t seed_hi,
                                            const float4 *tab, float (&n)[Env::S])
 {
     constexpr int ITEMS = Env::RESET_ITEMS;                   // work items per finishing lane (a power of two, or 6)
     static_assert((ITEMS & (ITEMS - 1)) == 0 || ITEMS == 6, "item index -> (lane, item): shift, or the divide-by-6 below");
+    if constexpr (QUICK) {
+        static_assert(ITEMS <= 64, "one pass of the wave covers a lone finisher's items");
+        if (__popc((uint32_t)m) + __popc((uint32_t)(m >> 32)) == 1) {      // (two 32-bit counts: hipcc compares a 64-bit count on the vector unit)
+            const unsigned owner = (unsigned)__builtin_ctzll(m);
+            if (lane < (unsigned)ITEMS) {
+                unsigned item = lane;                      // laundered like the list path's item index below, for the same reason
+                asm volatile("" : "+v"(item));
+                Env::reset_item_quick(make_key(lane_gi0 + owner, t, seed_lo, seed_hi, tab), item, img, owner);
+            }
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            if (mine) Env::reset_readback(img, lane, n);
+            return;
+        }
+    }
     const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));   // finishing lanes below this one (v_mbcnt: no per-lane mask register)
     if (mine) lst[rank] = (unsigned char)lane;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -265,7 +290,8 @@ __device__ __forceinline__ void coop_reset(unsigned long long m, bool mine, unsi
         if constexpr (ITEMS == 6) { li = ((unsigned)ii * 171u) >> 10; item = (unsigned)ii - 6u * li; }     // exact for ii < 515
         else { li = (unsigned)ii / (unsigned)ITEMS; item = (unsigned)ii % (unsigned)ITEMS; }
         const unsigned owner = lst[li];
-        Env::reset_item(make_key(lane_gi0 + owner, t, seed_lo, seed_hi, tab), item, img, owner);
+        if constexpr (QUICK) Env::reset_item_quick(make_key(lane_gi0 + owner, t, seed_lo, seed_hi, tab), item, img, owner);
+        else Env::reset_item(make_key(lane_gi0 + owner, t, seed_lo, seed_hi, tab), item, img, owner);
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     if (mine) Env::reset_readback(img, lane, n);
