@@ -949,88 +949,6 @@ int nig_rollout_policy(nig_handle *h, int32_t n_steps, float *reward_out, uint32
     return ring_check(h, st, "nig_rollout_policy");
 }
 
-// Row of a 32x32 MFMA result tile held in register t by lane half hf (MI355X_MICROARCH / guide section 3).
-static inline int mfma_row(int t, int hf) { return (t & 3) + 8 * (t >> 2) + 4 * hf; }
-
-// MFMA operand streams, built in exactly the order the kernels consume them, chunk by chunk (a chunk = one fill of an LDS buffer,
-// MLP_CHREC record slots, zero padded).  Record = 64 floats; lane l = (i = l & 31, hf = l >> 5) holds W[k(hf)][32*tile + i].
-static float *stream_rec(float *host, int chunk, int r) { return host + ((size_t)chunk * MLP_CHREC + r) * 64; }
-
-// Layer 2 of hidden tile m2 at the head of `chunk` (actor and critic alike): the weight records, k following the accumulator
-// register order of h1, then the bias record.  Returns the index of the next record.
-static int put_layer2(float *host, int chunk, int m2, const float *W2, const float *b2)
-{
-    const int H = MLP_H;
-    int r = 0;
-    for (int kt = 0; kt < MLP_MT; ++kt)
-        for (int t = 0; t < 16; ++t, ++r)
-            for (int l = 0; l < 64; ++l)
-                stream_rec(host, chunk, r)[l] = W2[(size_t)(32 * kt + mfma_row(t, l >> 5)) * H + 32 * m2 + (l & 31)];
-    for (int l = 0; l < 32; ++l) stream_rec(host, chunk, r)[l] = b2[32 * m2 + l];
-    return r + 1;
-}
-
-// The operand stream of one actor (S -> 256 -> 256 -> A), written into the zeroed host[MLP_STREAM_FLOATS]: the one builder of
-// nig_set_mlp_policy and of every member of nig_set_mlp_ensemble.  False: internal record count mismatch.
-static bool build_mlp_stream(int S, int A, const float *W1, const float *b1, const float *W2, const float *b2, const float *W3,
-                             const float *b3, float *host)
-{
-    const int H = MLP_H;
-    auto rec = [&](int chunk, int r) { return stream_rec(host, chunk, r); };
-    for (int m = 0; m < MLP_MT; ++m) {                      // chunk 0: layer 1, natural k order: k = 2*ks + hf
-        const int R1 = S / 2 + 1;
-        for (int ks = 0; ks < S / 2; ++ks)
-            for (int l = 0; l < 64; ++l) rec(0, m * R1 + ks)[l] = W1[(size_t)(2 * ks + (l >> 5)) * H + 32 * m + (l & 31)];
-        for (int l = 0; l < 32; ++l) rec(0, m * R1 + S / 2)[l] = b1[32 * m + l];
-    }
-    for (int m2 = 0; m2 < MLP_MT; ++m2) {                   // chunk 1 + m2: layer 2, then the head (rows i >= A are zero)
-        int r = put_layer2(host, 1 + m2, m2, W2, b2);
-        for (int t = 0; t < 16; ++t, ++r)
-            for (int l = 0; l < 64; ++l) {
-                if (A <= 4) {                                 // v_mfma_f32_4x4x1: lane 4 b + i of every 4-lane block holds head row i of ITS half's hidden row
-                    if ((l & 3) < A) rec(1 + m2, r)[l] = W3[(size_t)(32 * m2 + mfma_row(t, l >> 5)) * A + (l & 3)];
-                } else if ((l & 15) < A)                      // v_mfma_f32_16x16x1 (four blocks): lane 16 b + i holds head row i of block b's hidden row
-                    rec(1 + m2, r)[l] = W3[(size_t)(32 * m2 + mfma_row(t, l >> 5)) * A + (l & 15)];
-            }
-        if (r != MLP_PER) return false;
-    }
-    if (A <= 4) {                                                    // the head's bias rides at the end of the last chunk
-        for (int l = 0; l < 64; ++l)
-            if ((l & 3) < A) rec(MLP_MT, MLP_PER)[l] = b3[l & 3];    // (4 x 4 x 1: every block's row lanes; B = 1 on lane half 0, 0 on half 1)
-    } else
-        for (int l = 0; l < 64; ++l)
-            if ((l & 15) < A) rec(MLP_MT, MLP_PER)[l] = b3[l & 15];
-    return true;
-}
-
-// The safety critic's stream ((S + A) -> 256 -> 256 -> 1) in the order rollout_mlp_shield_kernel consumes it (nig_kernels.hpp,
-// MLP_CDIM / MLP_CR1 / MLP_CL1), into the zeroed host[MLP_CSTREAM_FLOATS]: layer 1 on x = [s, a, 0-pad] in one chunk, or two
-// chunks of four tiles when eight tiles do not fit a chunk slot; then one chunk per hidden tile of layer 2 (128 records + bias +
-// 16 head records of the one-row 4 x 4 x 1 head), c3 after the last.  False: internal record count mismatch.
-static bool build_critic_stream(int S, int A, const float *C1, const float *c1, const float *C2, const float *c2, const float *C3,
-                                const float *c3, float *host)
-{
-    const int H = MLP_H, D = S + A, DP = (D + 1) & ~1, CR1 = DP / 2 + 1, CL1 = MLP_MT * CR1 <= MLP_CHREC ? 1 : 2, TPC = MLP_MT / CL1;
-    auto rec = [&](int chunk, int r) { return stream_rec(host, chunk, r); };
-    for (int m = 0; m < MLP_MT; ++m) {                      // layer 1, natural k order: k = 2*ks + hf (k >= S + A: zero pad)
-        const int ch = m / TPC, base = (m % TPC) * CR1;
-        for (int ks = 0; ks < DP / 2; ++ks)
-            for (int l = 0; l < 64; ++l) {
-                const int k = 2 * ks + (l >> 5);
-                if (k < D) rec(ch, base + ks)[l] = C1[(size_t)k * H + 32 * m + (l & 31)];
-            }
-        for (int l = 0; l < 32; ++l) rec(ch, base + DP / 2)[l] = c1[32 * m + l];
-    }
-    for (int m2 = 0; m2 < MLP_MT; ++m2) {                   // chunk CL1 + m2: as the actor's, with a one-row head
-        int r = put_layer2(host, CL1 + m2, m2, C2, c2);
-        for (int t = 0; t < 16; ++t, ++r)                     // 4 x 4 x 1 head, row 0 only: lane 4 b holds C3 of its half's hidden row
-            for (int l = 0; l < 64; l += 4) rec(CL1 + m2, r)[l] = C3[32 * m2 + mfma_row(t, l >> 5)];
-        if (r != MLP_PER) return false;
-    }
-    for (int l = 0; l < 64; l += 4) rec(CL1 + MLP_MT - 1, MLP_PER)[l] = c3[0];
-    return true;
-}
-
 // A built host image (malloc'd; freed here) -> the device stream *dev, allocated on first use; copied on `stream` and waited for.
 static int upload_stream(const char *fn, float **dev, float *host, size_t floats, void *stream)
 {
@@ -1053,7 +971,7 @@ int nig_set_mlp_policy(nig_handle *h, int32_t hidden, const float *W1, const flo
     if (S % 2 != 0 || A > 16) return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_policy: env shape not supported (even state dim, at most 16 actions)");
     float *host = (float *)calloc((size_t)MLP_STREAM_FLOATS, sizeof(float));
     if (!host) return fail(NIG_ERR_INVALID, "nig_set_mlp_policy: out of host memory");
-    if (!build_mlp_stream(S, A, W1, b1, W2, b2, W3, b3, host)) { free(host); return fail(NIG_ERR_INVALID, "nig_set_mlp_policy: internal record count mismatch"); }
+    if (!put_network(S, A, W1, b1, W2, b2, W3, b3, host, MLP_STREAM_FLOATS)) { free(host); return fail(NIG_ERR_INVALID, "nig_set_mlp_policy: the operand stream does not fit its image, or an internal record count mismatch"); }
     return upload_stream("nig_set_mlp_policy", &h->mlp_stream, host, MLP_STREAM_FLOATS, stream);
 }
 
@@ -1082,7 +1000,7 @@ int nig_set_mlp_safety(nig_handle *h, int32_t hidden, const float *C1, const flo
         return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_safety: env shape not supported (even state dim, at most 16 actions)");
     float *host = (float *)calloc((size_t)MLP_CSTREAM_FLOATS, sizeof(float));
     if (!host) return fail(NIG_ERR_INVALID, "nig_set_mlp_safety: out of host memory");
-    if (!build_critic_stream(S, A, C1, c1, C2, c2, C3, c3, host)) { free(host); return fail(NIG_ERR_INVALID, "nig_set_mlp_safety: internal record count mismatch"); }
+    if (!put_network(S + A, 1, C1, c1, C2, c2, C3, c3, host, MLP_CSTREAM_FLOATS)) { free(host); return fail(NIG_ERR_INVALID, "nig_set_mlp_safety: the operand stream does not fit its image, or an internal record count mismatch"); }
     NIG_TRY(upload_stream("nig_set_mlp_safety", &h->mlp_cstream, host, MLP_CSTREAM_FLOATS, stream));
     h->mlp_threshold = threshold;
     return NIG_OK;
@@ -1134,9 +1052,9 @@ int nig_set_mlp_ensemble(nig_handle *h, int32_t n_members, int32_t hidden, const
     float *host = (float *)calloc((size_t)n_members * MLP_STREAM_FLOATS, sizeof(float));
     if (!host) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: out of host memory");
     for (int k = 0; k < n_members; ++k)
-        if (!build_mlp_stream(S, A, W1[k], b1[k], W2[k], b2[k], W3[k], b3[k], host + (size_t)k * MLP_STREAM_FLOATS)) {
+        if (!put_network(S, A, W1[k], b1[k], W2[k], b2[k], W3[k], b3[k], host + (size_t)k * MLP_STREAM_FLOATS, MLP_STREAM_FLOATS)) {
             free(host);
-            return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: internal record count mismatch");
+            return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: the operand stream does not fit its image, or an internal record count mismatch");
         }
     h->ens_members = 0;                                     // no ensemble while the streams are being replaced
     if (h->ens_cap < n_members) {                           // too small: upload_stream allocates the new one

@@ -1,8 +1,10 @@
 // nig_mlp.hpp -- the fused MLP actor on MFMA with its safety-critic shield and its ensemble (device code only): MlpArgs,
 // MlpShieldArgs, MlpEnsArgs, MlpDistArgs, rollout_mlp_body and its four kernels.
 #pragma once
+#include <type_traits>
 #include "nig_step.hpp"
 #include "nig_disturb.hpp"
+#include "nig_mlp_stream.hpp"         // the operand stream's constants and layer-1 shape (shared with the host's builder)
 
 namespace nig {
 
@@ -33,24 +35,15 @@ struct MlpArgs {
     float *act_out; uint32_t ld_act_out; uint64_t act_step_stride;
 };
 
-constexpr int MLP_H = 256, MLP_MT = MLP_H / 32;
-// The operand stream is cut into 1 + MLP_MT CHUNKS of MLP_CHREC records (256 bytes each, padded): chunk 0 = layer 1
-// (MLP_MT tiles of S/2 weight records + 1 bias record), chunk 1 + m2 = hidden tile m2 of layer 2 with its slice of
-// the head (128 + 1 + 16 records; the last chunk also carries the head's bias record).  A chunk is what one fill of
-// an LDS buffer holds: MLP_PIECES wave-instructions of 1 KiB (64 lanes x 16 bytes, LDS-DMA).
-constexpr int MLP_PER = MLP_MT * 16 + 1 + 16;                 // 145 records per hidden tile
-constexpr int MLP_PIECES = (MLP_PER + 1 + 3) / 4;             // 37 KiB pieces per chunk
-constexpr int MLP_CHREC = MLP_PIECES * 4;                     // 148 records per chunk slot
-constexpr int MLP_CHUNKS = 1 + MLP_MT;
-constexpr int MLP_STREAM_FLOATS = MLP_CHUNKS * MLP_CHREC * 64;
 typedef __attribute__((address_space(3))) void nig_lds_void;
 typedef __attribute__((address_space(1))) const void nig_glb_void;
 
-// Two blocks per CU (round 4): the double-buffered weight image is 74 KiB per block; with the generator's 12 KiB table beside it
-// only ONE block fitted a CU's 160 KiB, i.e. one wave per SIMD, and every chunk barrier and ring refill was exposed MFMA idle
-// time (duty cycle 0.78, profiles/r04/mlp_cr65536_sq.txt).  An env with a couple of draws per step (KS <= 4) reads its table
-// entries from global memory (L2-resident, as step_kernel does) and the kernel is compiled for two waves per SIMD, so a second
-// block's waves fill the first's bubbles.
+// Two blocks per CU: the double-buffered weight image is 74 KiB per block, so two blocks fit a CU's 160 KiB as long as nothing
+// else of size lives in LDS -- the generator's 12 KiB table does not: every env reads its table entries from global memory
+// (L2-resident, as step_kernel does; PowerGrid's 23 + 31 reads per step / reset are noise beside 1 217 MFMAs).  The kernels are
+// compiled for two waves per SIMD (__launch_bounds__(BLOCK, 2)), so a second block's waves fill the bubbles of the first: with
+// one block per CU every chunk barrier and ring refill was exposed MFMA idle time (duty cycle 0.78 against 0.875,
+// profiles/r04/mlp_cr65536_sq.txt, mlp_two_blocks.txt).
 // The head (layer 3) of an env with at most FOUR actions runs on v_mfma_f32_4x4x1_16B_f32 (round 5): sixteen 4 x 4 blocks of
 // four lanes, K = 1 -- lane l multiplies ITS OWN h2 value (B) with the four head weights held by the four lanes of its block
 // (A: lane 4 b + r holds W3[k][r]) into four accumulators, out[r] += W3[k][r] h2[k]: exactly a head of <= 4 rows, 8 cycles an
@@ -66,22 +59,14 @@ typedef __attribute__((address_space(1))) const void nig_glb_void;
 // The 32 x 32 x 2 head (64 cycles for 32 rows, 24 of them padding with eight actions) is gone.
 template <class Env> constexpr bool mlp_head4 = Env::A <= 4;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-template <class Env> constexpr bool mlp_two_blocks = true;       // (PowerGrid's 23 + 31 table reads per step / reset from L2 as well: they are noise beside 1 217 MFMAs)
+template <int N> using mlp_int = std::integral_constant<int, N>;      // a compile-time count handed to a lambda
 
 // Safety-critic shield (rollout_mlp_shield_kernel, agents/cql.py predict_with_safety): after the actor, a second pass of the
-// same scheme evaluates p = sigmoid(critic([s, a])), critic = (S + A) -> 256 -> 256 -> 1 ReLU MLP, and the env receives a * 0.5
-// unless p < threshold.  The critic's operand stream (nig_set_mlp_safety) is laid out like the actor's: layer 1 on the input
-// x = [s (S), a (A), 0-pad to even] in MLP_CL1<Env> chunks (one, or two of four tiles each when eight tiles of MLP_CR1 records
-// exceed a chunk slot: PowerGrid, AdvancedPowerGrid, SupplyChain), then one chunk per hidden tile of layer 2 with its slice of
-// a ONE-row head on v_mfma_f32_4x4x1 (the actor's mlp_head4 form with A = 1; the head's bias in record MLP_PER of the last).
-// Its chunks are consumed through the same double-buffered LDS image, so the fill of the next chunk stays in flight across
-// actor -> critic and critic -> next step's actor.
-template <class Env> constexpr int MLP_CDIM = (Env::S + Env::A + 1) & ~1;                    // critic input, padded to even
-template <class Env> constexpr int MLP_CR1 = MLP_CDIM<Env> / 2 + 1;                          // records per critic layer-1 tile
-template <class Env> constexpr int MLP_CL1 = MLP_MT * MLP_CR1<Env> <= MLP_CHREC ? 1 : 2;     // chunks of critic layer 1
-constexpr int MLP_CSTREAM_FLOATS = (2 + MLP_MT) * MLP_CHREC * 64;                          // room for either layer-1 form
-
+// same routines evaluates p = sigmoid(critic([s, a])), and the env receives a * 0.5 unless p < threshold.  The critic is the
+// network (S + A, 1) of nig_mlp_stream.hpp: layer 1 on x = [s (S), a (A), 0-pad to even] in mlp_layer1(S + A).chunks chunks
+// (two of four tiles each for PowerGrid, AdvancedPowerGrid, SupplyChain), a one-row head on v_mfma_f32_4x4x1 (the actor's
+// mlp_head4 form).  Its chunks are consumed through the same double-buffered LDS image, so the fill of the next chunk stays in
+// flight across actor -> critic and critic -> next step's actor.
 struct MlpShieldArgs {
     MlpArgs m;
     const float *cstream;       // critic operand stream built by nig_set_mlp_safety
@@ -147,12 +132,7 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
     // quarter of the pieces, the fill of chunk c+1 in flight while chunk c is consumed; an MFMA's A operand is one
     // ds_read_b32.  L2 traffic per block and step: 311 KB instead of 4 x 311 KB.
     __shared__ __attribute__((aligned(16))) float s_w[2][MLP_CHREC * 64];
-    __shared__ float4 s_probit_[mlp_two_blocks<Env> ? 1 : 768];
-    if constexpr (!mlp_two_blocks<Env>) {
-        stage_probit(s_probit_, threadIdx.x, BLOCK);
-        __syncthreads();
-    }
-    const float4 *const s_probit = mlp_two_blocks<Env> ? NIG_PROBIT : s_probit_;
+    const float4 *const s_probit = NIG_PROBIT;               // the generator's table stays in global memory: two blocks per CU
     const StepArgs &p = q.s;
     const unsigned tid = threadIdx.x, lane = tid & 63u, half = lane >> 5, e = lane & 31u, wave = tid >> 6;
     const uint32_t lane0 = blockIdx.x * (BLOCK / 2) + (tid >> 6) * 32u;     // first env of this wave
@@ -174,23 +154,73 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
     lt.clear();
     // fill LDS buffer `buf` with chunk `c` of the operand stream: this wave's quarter of the KiB pieces
     const float *wsrc = q.wstream;                           // operand stream of the actor (ensemble: of the member) being filled from
-    auto fill = [&](int c, int buf, int pieces) __attribute__((always_inline)) {
-        const float *src = (ENS != ENS_NONE ? wsrc : q.wstream) + (size_t)c * (MLP_CHREC * 64) + lane * 4u;
+    auto fill_from = [&](const float *stream, int c, int buf, int pieces) __attribute__((always_inline)) {
+        const float *src = stream + (size_t)c * (MLP_CHREC * 64) + lane * 4u;
         for (int pc = (int)wave; pc < pieces; pc += BLOCK / 64)
             __builtin_amdgcn_global_load_lds((nig_glb_void *)(src + pc * 256), (nig_lds_void *)(&s_w[buf][pc * 256]), 16, 0, 0);
     };
-    [[maybe_unused]] auto cfill = [&](int c, int buf, int pieces) __attribute__((always_inline)) {   // the same from the critic's stream
-        const float *src = cstream + (size_t)c * (MLP_CHREC * 64) + lane * 4u;
-        for (int pc = (int)wave; pc < pieces; pc += BLOCK / 64)
-            __builtin_amdgcn_global_load_lds((nig_glb_void *)(src + pc * 256), (nig_lds_void *)(&s_w[buf][pc * 256]), 16, 0, 0);
+    auto fill = [&](int c, int buf, int pieces) __attribute__((always_inline)) { fill_from(ENS != ENS_NONE ? wsrc : q.wstream, c, buf, pieces); };
+    [[maybe_unused]] auto cfill = [&](int c, int buf, int pieces) __attribute__((always_inline)) { fill_from(cstream, c, buf, pieces); };
+    constexpr MlpLayer1 L1 = mlp_layer1(S), C1 = mlp_layer1(S + A);   // layer 1 of the actor (S, A) and of the critic (S + A, 1)
+    static_assert(L1.chunks == 1, "the actor's layer 1 must fit one chunk");
+    static_assert(C1.fits(), "a critic layer-1 chunk must fit one chunk slot");
+    // ---------------- one network = layer 1, then MLP_MT chunks of layer 2 + head; the two routines every pass is made of ----------------
+    // Both consume the chunk that is in s_w[gbuf] and are straight-line code: the chunk barrier, the fill of the chunk that
+    // follows (the one thing that differs between actor, critic, ensemble member and step) and the loop over chunks stay in
+    // the body, where the compiler saw them before there were routines (nig_episode.hpp's rule; profiles/mlp_network/isa_diff.txt).
+    // Layer 1, one chunk of it: TILES hidden tiles of REC records each on the input x(k) -> ReLU'd tiles h[0 .. TILES).
+    auto layer1_chunk = [&](auto tiles_, auto rec_, const auto &x, f32x16 *h, int gbuf) __attribute__((always_inline)) {
+        constexpr int TILES = decltype(tiles_)::value, REC = decltype(rec_)::value;
+        const float *wb = &s_w[gbuf][lane];
+#pragma unroll
+        for (int mm = 0; mm < TILES; ++mm) {
+            f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+            for (int ks = 0; ks < REC - 1; ++ks) {
+                const float b = half ? x(2 * ks + 1) : x(2 * ks);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[(mm * REC + ks) * 64], b, acc, 0, 0, 0);
+            }
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[(mm * REC + REC - 1) * 64], half ? 0.0f : 1.0f, acc, 0, 0, 0);   // + bias
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = fmaxf(acc[r], 0.0f);                                   // ReLU
+            h[mm] = acc;
+        }
     };
-    constexpr int R1 = S / 2 + 1;                            // records per layer-1 tile
-    constexpr int PIECES0 = (MLP_MT * R1 + 3) / 4;           // pieces of chunk 0
-    static_assert(MLP_MT * R1 <= MLP_CHREC, "layer 1 must fit one chunk");
-    constexpr int CL1 = MLP_CL1<Env>, CR1 = MLP_CR1<Env>, CTPC = MLP_MT / CL1;   // critic: layer-1 chunks, records per tile, tiles per chunk
-    constexpr int CPIECES0 = (CTPC * CR1 + 3) / 4;           // pieces of a critic layer-1 chunk
-    static_assert(CTPC * CR1 <= MLP_CHREC, "a critic layer-1 chunk must fit one chunk slot");
-    fill(0, 0, PIECES0);
+    // Layer 2, hidden tile number `tiles` (counted from 1) on the layer-1 tiles h, consumed at once by its slice of the head:
+    // returns the head's accumulator `out` (this lane half's partial sums; its type names the instruction, f32x4: 4 x 4 x 1,
+    // f32x16: 16 x 16 x 1) with the tile's 16 hidden rows added, and the head's bias behind the last tile.  (The count and not
+    // a `bool last`: the caller would evaluate that ahead of the first sched_barrier, and the parent compares after the last.)
+    auto layer2_chunk = [&](const f32x16 *h, auto out, int tiles, int gbuf) __attribute__((always_inline)) {
+        constexpr int RING = 8;                             // LDS reads in flight ahead of their MFMA (~64 cycles apart)
+        const float *wb = &s_w[gbuf][lane];
+        f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        float ring[RING];
+#pragma unroll
+        for (int j = 0; j < RING; ++j) ring[j] = wb[j * 64];
+#pragma unroll
+        for (int i = 0; i < MLP_PER; ++i) {
+            const float aop = ring[i % RING];
+            if (i + RING < MLP_PER + 1) ring[i % RING] = wb[(i + RING) * 64];       // (+1: the head's bias record of the last chunk)
+            // pin the source order: hipcc's scheduler otherwise sinks every read to just before its use
+            __builtin_amdgcn_sched_barrier(0);
+            if (i < MLP_MT * 16) {
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aop, h[i / 16][i % 16], acc, 0, 0, 0);
+            } else if (i == MLP_MT * 16) {
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aop, half ? 0.0f : 1.0f, acc, 0, 0, 0);      // + bias
+            } else if constexpr (std::is_same_v<decltype(out), f32x4>) {      // own value x the weights of the lane's block
+                out = __builtin_amdgcn_mfma_f32_4x4x1f32(aop, fmaxf(acc[i - MLP_MT * 16 - 1], 0.0f), out, 0, 0, 0);
+            } else {
+                out = __builtin_amdgcn_mfma_f32_16x16x1f32(aop, fmaxf(acc[i - MLP_MT * 16 - 1], 0.0f), out, 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (tiles == MLP_MT) {                              // record 145 of the last chunk: + the head's bias
+            if constexpr (std::is_same_v<decltype(out), f32x4>) out = __builtin_amdgcn_mfma_f32_4x4x1f32(ring[MLP_PER % RING], half ? 0.0f : 1.0f, out, 0, 0, 0);
+            else out = __builtin_amdgcn_mfma_f32_16x16x1f32(ring[MLP_PER % RING], half ? 0.0f : 1.0f, out, 0, 0, 0);
+        }
+        return out;
+    };
+    fill(0, 0, L1.pieces);
     int gbuf = 0;                                            // buffer that holds (or receives) the chunk consumed next
     const int n_members = ENS != ENS_NONE ? eq->n_members : 1;
     [[maybe_unused]] bool d_obs = false, d_act = false;
@@ -210,82 +240,31 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
         int mem = 0;
         do {                                                       // (one pass unless ENS)
         // ---------------- actor: 3 layers of f32 MFMA, whole wave (EXEC all ones) ----------------
+        f32x16 h1[MLP_MT];
         // chunk boundary: every wave's share of the fill has landed (the compiler drains vmcnt before the barrier)
         // and every wave is done with the buffer the next fill overwrites
         __syncthreads();
-#if defined(NIG_DIAG_MLP_SKIP) && (NIG_DIAG_MLP_SKIP & 2)
-        if (it == 0)
-#endif
         fill(1, gbuf ^ 1, MLP_PIECES);
-        f32x16 h1[MLP_MT];
-        {
-            const float *wb = &s_w[gbuf][lane];
-#pragma unroll
-            for (int m = 0; m < MLP_MT; ++m) {
-                f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-                for (int ks = 0; ks < S / 2; ++ks) {
-                    const float b = half ? xin(2 * ks + 1) : xin(2 * ks);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[(m * R1 + ks) * 64], b, acc, 0, 0, 0);
-                }
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[(m * R1 + R1 - 1) * 64], half ? 0.0f : 1.0f, acc, 0, 0, 0);   // + b1
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = fmaxf(acc[r], 0.0f);                                   // ReLU
-                h1[m] = acc;
-            }
-        }
+        layer1_chunk(mlp_int<MLP_MT>{}, mlp_int<L1.records>{}, xin, h1, gbuf);
         gbuf ^= 1;
-        f32x16 out = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        [[maybe_unused]] f32x4 out4 = {0, 0, 0, 0};          // mlp_head4: this lane half's partial sums of the (<= 4) head rows
-        constexpr int RING = 8;                             // LDS reads in flight ahead of their MFMA (~64 cycles apart)
+        std::conditional_t<mlp_head4<Env>, f32x4, f32x16> out = {};     // this lane half's partial sums of the head rows
         for (int m2 = 0; m2 < MLP_MT; ++m2) {               // a real loop: the body is 145 MFMAs of straight-line code
             __syncthreads();                                // chunk 1 + m2 is in s_w[gbuf]; s_w[gbuf ^ 1] is free
-#if defined(NIG_DIAG_MLP_SKIP) && (NIG_DIAG_MLP_SKIP & 2)     // (diagnostic, WRONG results: no LDS-DMA traffic after the first step)
-            if (it == 0) {
-#endif
             if (m2 + 1 < MLP_MT) fill(2 + m2, gbuf ^ 1, MLP_PIECES);
-            else if constexpr (SHIELD) cfill(0, gbuf ^ 1, CPIECES0);  // the critic's layer 1 follows the actor
+            else if constexpr (SHIELD) cfill(0, gbuf ^ 1, C1.pieces);  // the critic's layer 1 follows the actor
             else if constexpr (ENS != ENS_NONE) {                     // layer 1 of the next member, or of member 0 for the next step
                 const bool more = mem + 1 < n_members;
                 wsrc = more ? wsrc + MLP_STREAM_FLOATS : q.wstream;
-                if (more || it + 1 < q.n_steps) fill(0, gbuf ^ 1, PIECES0);
+                if (more || it + 1 < q.n_steps) fill(0, gbuf ^ 1, L1.pieces);
             }
-            else if (it + 1 < q.n_steps) fill(0, gbuf ^ 1, PIECES0);   // layer 1 of the NEXT step (the weights do not change)
-#if defined(NIG_DIAG_MLP_SKIP) && (NIG_DIAG_MLP_SKIP & 2)
-            }
-#endif
-            const float *wb = &s_w[gbuf][lane];
-            f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-            float ring[RING];
-#pragma unroll
-            for (int j = 0; j < RING; ++j) ring[j] = wb[j * 64];
-#pragma unroll
-            for (int i = 0; i < MLP_PER; ++i) {
-                const float aop = ring[i % RING];
-                if (i + RING < MLP_PER + 1) ring[i % RING] = wb[(i + RING) * 64];       // (+1: the head's bias record of the last chunk)
-                // pin the source order: hipcc's scheduler otherwise sinks every read to just before its use
-                __builtin_amdgcn_sched_barrier(0);
-                if (i < MLP_MT * 16) {
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aop, h1[i / 16][i % 16], acc, 0, 0, 0);
-                } else if (i == MLP_MT * 16) {
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aop, half ? 0.0f : 1.0f, acc, 0, 0, 0);      // + b2
-                } else if constexpr (mlp_head4<Env>) {  // this h2 tile is consumed at once by the head: 4 x 4 x 1, own value x the block's weights
-                    out4 = __builtin_amdgcn_mfma_f32_4x4x1f32(aop, fmaxf(acc[i - MLP_MT * 16 - 1], 0.0f), out4, 0, 0, 0);
-                } else {                                // 16 x 16 x 1, four blocks: own value x the block's sixteen weights
-                    out = __builtin_amdgcn_mfma_f32_16x16x1f32(aop, fmaxf(acc[i - MLP_MT * 16 - 1], 0.0f), out, 0, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if (m2 + 1 == MLP_MT) {                          // record 145 of the last chunk: + b3
-                if constexpr (mlp_head4<Env>) out4 = __builtin_amdgcn_mfma_f32_4x4x1f32(ring[MLP_PER % RING], half ? 0.0f : 1.0f, out4, 0, 0, 0);
-                else out = __builtin_amdgcn_mfma_f32_16x16x1f32(ring[MLP_PER % RING], half ? 0.0f : 1.0f, out, 0, 0, 0);
-            }
+            else if (it + 1 < q.n_steps) fill(0, gbuf ^ 1, L1.pieces);   // layer 1 of the NEXT step (the weights do not change)
+            out = layer2_chunk(h1, out, m2 + 1, gbuf);
             gbuf ^= 1;
         }
         if constexpr (mlp_head4<Env>) {
             // action r = this half's partial sum + the other half's (lane l and l + 32 carry the same env)
 #pragma unroll
-            for (int r = 0; r < A; ++r) a[r] = det_tanhf(out4[r] + __shfl_xor(out4[r], 32));
+            for (int r = 0; r < A; ++r) a[r] = det_tanhf(out[r] + __shfl_xor(out[r], 32));
         } else {
             // head row r of env column c (env 16 beta + c, beta = block parity): lane 16 (r >> 2) + c, registers 4 beta + (r & 3)
             // (lane half 0's chain) and 8 + 4 beta + (r & 3) (lane half 1's); hand every lane all A rows of its env
@@ -345,53 +324,32 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
         [[maybe_unused]] bool shield = false;
         [[maybe_unused]] float prob = 0.0f;
         if constexpr (SHIELD) {
-            // ---------------- safety critic on x = [s, a, 0]: the same three-layer scheme, one-row head ----------------
+            // ---------------- safety critic on x = [s, a, 0]: the network (S + A, 1) ----------------
             auto x = [&](int k) __attribute__((always_inline)) { return k < S ? s[k] : (k < S + A ? a[k - S] : 0.0f); };
             f32x16 g1[MLP_MT];
-#pragma unroll
-            for (int c1 = 0; c1 < CL1; ++c1) {
-                __syncthreads();                            // critic layer-1 chunk c1 is in s_w[gbuf]
-                if (c1 + 1 < CL1) cfill(c1 + 1, gbuf ^ 1, CPIECES0);
-                else cfill(CL1, gbuf ^ 1, MLP_PIECES);
-                const float *wb = &s_w[gbuf][lane];
-#pragma unroll
-                for (int mm = 0; mm < CTPC; ++mm) {
-                    f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-                    for (int ks = 0; ks < CR1 - 1; ++ks)
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[(mm * CR1 + ks) * 64], half ? x(2 * ks + 1) : x(2 * ks), acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[(mm * CR1 + CR1 - 1) * 64], half ? 0.0f : 1.0f, acc, 0, 0, 0);   // + c1
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[r] = fmaxf(acc[r], 0.0f);
-                    g1[c1 * CTPC + mm] = acc;
-                }
+            // (one chunk: the actor's lines; two: a loop.  Only so do all eight shield kernels keep the parent's registers and
+            // scratch -- with a one-trip loop, or with the two chunks spelled out, some spill more: profiles/mlp_network/isa_diff.txt)
+            if constexpr (C1.chunks == 1) {
+                __syncthreads();                            // the critic's layer 1 is in s_w[gbuf]
+                cfill(1, gbuf ^ 1, MLP_PIECES);
+                layer1_chunk(mlp_int<MLP_MT>{}, mlp_int<C1.records>{}, x, g1, gbuf);
                 gbuf ^= 1;
+            } else {
+#pragma unroll
+                for (int c1 = 0; c1 < C1.chunks; ++c1) {
+                    __syncthreads();                        // critic layer-1 chunk c1 is in s_w[gbuf]
+                    if (c1 + 1 < C1.chunks) cfill(c1 + 1, gbuf ^ 1, C1.pieces);
+                    else cfill(C1.chunks, gbuf ^ 1, MLP_PIECES);
+                    layer1_chunk(mlp_int<C1.tiles>{}, mlp_int<C1.records>{}, x, g1 + c1 * C1.tiles, gbuf);
+                    gbuf ^= 1;
+                }
             }
             f32x4 z4 = {0, 0, 0, 0};
-            constexpr int RING = 8;
             for (int m2 = 0; m2 < MLP_MT; ++m2) {
-                __syncthreads();                            // critic chunk CL1 + m2 is in s_w[gbuf]
-                if (m2 + 1 < MLP_MT) cfill(CL1 + 1 + m2, gbuf ^ 1, MLP_PIECES);
-                else if (it + 1 < q.n_steps) fill(0, gbuf ^ 1, PIECES0);   // the actor's layer 1 of the NEXT step
-                const float *wb = &s_w[gbuf][lane];
-                f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-                float ring[RING];
-#pragma unroll
-                for (int j = 0; j < RING; ++j) ring[j] = wb[j * 64];
-#pragma unroll
-                for (int i = 0; i < MLP_PER; ++i) {
-                    const float aop = ring[i % RING];
-                    if (i + RING < MLP_PER + 1) ring[i % RING] = wb[(i + RING) * 64];
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (i < MLP_MT * 16)
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aop, g1[i / 16][i % 16], acc, 0, 0, 0);
-                    else if (i == MLP_MT * 16)
-                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aop, half ? 0.0f : 1.0f, acc, 0, 0, 0);      // + c2
-                    else
-                        z4 = __builtin_amdgcn_mfma_f32_4x4x1f32(aop, fmaxf(acc[i - MLP_MT * 16 - 1], 0.0f), z4, 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                if (m2 + 1 == MLP_MT) z4 = __builtin_amdgcn_mfma_f32_4x4x1f32(ring[MLP_PER % RING], half ? 0.0f : 1.0f, z4, 0, 0, 0);   // + c3
+                __syncthreads();                            // critic chunk C1.chunks + m2 is in s_w[gbuf]
+                if (m2 + 1 < MLP_MT) cfill(C1.chunks + 1 + m2, gbuf ^ 1, MLP_PIECES);
+                else if (it + 1 < q.n_steps) fill(0, gbuf ^ 1, L1.pieces);   // the actor's layer 1 of the NEXT step
+                z4 = layer2_chunk(g1, z4, m2 + 1, gbuf);
                 gbuf ^= 1;
             }
             prob = det_sigmoidf(z4[0] + __shfl_xor(z4[0], 32));
@@ -400,11 +358,6 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
             for (int r = 0; r < A; ++r) a[r] = shield ? a[r] * 0.5f : a[r];
         }
 
-#if defined(NIG_DIAG_MLP_SKIP) && (NIG_DIAG_MLP_SKIP & 1)     // (diagnostic builds only, WRONG results: the actor without the env step)
-#pragma unroll
-        for (int k = 0; k < S; ++k) s[k] = __builtin_fmaf(1e-9f, a[k % A], s[k]);
-        continue;
-#endif
         // ---------------- IndustrialEnv.step (both lane halves, identical results) ----------------
         const uint32_t orow = (uint32_t)it * q.out_stride;
         const bool frozen = (ctr & NIG_CTR_DONE) != 0;
@@ -478,27 +431,27 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
 }
 
 template <class Env>
-__global__ void __launch_bounds__(BLOCK, mlp_two_blocks<Env> ? 2 : 1) rollout_mlp_kernel(const MlpArgs q)
+__global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_kernel(const MlpArgs q)
 {
     rollout_mlp_body<Env, false>(q, nullptr, nullptr, 0.0f);
 }
 
 template <class Env>
-__global__ void __launch_bounds__(BLOCK, mlp_two_blocks<Env> ? 2 : 1) rollout_mlp_shield_kernel(const MlpShieldArgs q)
+__global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_shield_kernel(const MlpShieldArgs q)
 {
     rollout_mlp_body<Env, true>(q.m, q.cstream, q.prob_out, q.threshold);
 }
 
 // ENS = ENS_AVERAGE / ENS_VOTING.  Instantiated in the env's ensemble_*.hip translation unit only (launch_mlp_ensemble_env).
 template <class Env, int ENS>
-__global__ void __launch_bounds__(BLOCK, mlp_two_blocks<Env> ? 2 : 1) rollout_mlp_ensemble_kernel(const MlpEnsArgs q)
+__global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_ensemble_kernel(const MlpEnsArgs q)
 {
     rollout_mlp_body<Env, false, ENS>(q.m, nullptr, nullptr, 0.0f, &q);
 }
 
 // Instantiated in the env's disturbed_*.hip translation unit only (launch_mlp_disturbed_env).
 template <class Env>
-__global__ void __launch_bounds__(BLOCK, mlp_two_blocks<Env> ? 2 : 1) rollout_mlp_disturbed_kernel(const MlpDistArgs q)
+__global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_disturbed_kernel(const MlpDistArgs q)
 {
     rollout_mlp_body<Env, false, ENS_NONE, true>(q.m, nullptr, nullptr, 0.0f, nullptr, &q.d);
 }

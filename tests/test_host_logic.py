@@ -291,7 +291,7 @@ def test_build_hash_covers_every_source_of_the_library():
     names = {os.path.basename(p) for p in _build.sources() + _build.headers()}
     for f in ("nig_api.hip", "nig_mixed.hip", "env_pg.hip", "nig_kernels.hpp", "nig_episode.hpp", "nig_envs.hpp", "nig_detmath.hpp",
               "nig_device.hpp", "nig_step.hpp", "nig_step_kernel.hpp", "nig_rollout.hpp", "nig_rollout_wide.hpp", "nig_policy.hpp",
-              "nig_rollout_policy.hpp", "nig_mlp.hpp", "nig_probit_table.inc", "nig_spec_plants.inc", "nig.h"):
+              "nig_rollout_policy.hpp", "nig_mlp.hpp", "nig_mlp_stream.hpp", "nig_probit_table.inc", "nig_spec_plants.inc", "nig.h"):
         assert f in names, f
 
 
