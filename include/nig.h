@@ -81,7 +81,7 @@ extern "C" {
 #define NIG_FLAG_INACTIVE 0x800u        /* lane was already done (no auto-reset): untouched  */
 #define NIG_FLAG_VIOL3 0x1000u          /* 4th safety condition violated (Advanced envs)     */
 #define NIG_FLAG_NVIOL_HI 0x2000u       /* adds 4 to the violation count field (Advanced envs) */
-#define NIG_FLAG_SHIELDED 0x4000u       /* nig_rollout_mlp_safe: the safety critic halved the action */
+#define NIG_FLAG_SHIELDED 0x4000u       /* nig_rollout_mlp_safe: the safety critic halved the action (nig_rollout_mlp_search: replaced it) */
 #define NIG_FLAG_UNCERTAIN 0x8000u      /* nig_rollout_mlp_ensemble: uncertainty > threshold on this live step */
 #define NIG_FLAG_STEP_SHIFT 16          /* bits 16-31: current_step after this call          */
 
@@ -505,6 +505,43 @@ int nig_set_mlp_safety(nig_handle *h, int32_t hidden, const float *C1, const flo
 int nig_rollout_mlp_safe(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out,
                          int64_t out_stride, float *obs_out, int64_t obs_step_stride, float *act_out,
                          int64_t ld_act, int64_t act_step_stride, float *prob_out, void *stream);
+
+/*
+ * Safe-action search of the reference's safety-critical agents (agents/safety_critical.py:173-208,
+ * RiskAwareCQLAgent.get_safe_action), fused into the shield's kernel: where the critic finds the actor's
+ * action too risky, it scores n_candidates uniform actions and the env receives the least risky one.
+ * The law, "nig-search-v1".  For a live lane with global index g, on the step whose launch counter is t
+ * (the t its step noise is keyed at), thr the threshold installed with the critic, N = n_candidates:
+ *     a  = actor(s)                                  bit for bit nig_rollout_mlp's action
+ *     p0 = critic([s, a])                            bit for bit nig_rollout_mlp_safe's p
+ *     if (p0 < thr):   the env receives a;  risk = p0;  choice = -1;  no flag
+ *     else:
+ *         for c = 0 .. N-1:
+ *             u_c[j] = fmaf((float)(w >> 8), 2^-23, -1.0f),  j = 0 .. A-1,
+ *                      w = word (j & 3) of the generator's block 0xC0000100 + 4*c + (j >> 2) (policy stream,
+ *                      block 0x100 + 4*c + (j >> 2)) under the key (g, t, seed): uniform on [-1, 1) in steps
+ *                      of 2^-23, whatever the env's action Box (the reference draws uniform(-1, 1))
+ *             p_c    = critic([s, u_c])              the arithmetic of p0
+ *         best = the first c of least p_c: c = 0, then every c whose p_c < p_best in order; a NaN p_c is
+ *                taken only as c = 0 and gives way to the first p_c that is a number
+ *         the env receives u_best;  risk = p_best;  choice = best;  NIG_FLAG_SHIELDED ("the critic replaced
+ *         the action": no other flag bit is free)
+ * As the reference, the law returns the safest candidate even where p_best > p0.  A NaN p0 searches.
+ * Candidate passes run per 128-lane block and only in blocks with a live lane that searches; a lane's
+ * results do not depend on the other lanes of its block.  Cost: up to N + 1 critic passes per step.
+ *
+ * As nig_rollout_mlp_safe (arguments, minima, obs_out alignment, frozen lanes, tallies, launch counter; actor
+ * and critic from nig_set_mlp_policy / nig_set_mlp_safety, no other state).  prob_out: p0.  risk_out /
+ * choice_out (optional) float / int32 [n_steps][>= B], row k at base + k*out_stride like prob_out; frozen
+ * lanes leave their words untouched.  act_out: the action the env received.  NIG_ERR_INVALID (nothing
+ * launched or written): n_candidates outside 1 .. NIG_MAX_CANDIDATES, no actor or no critic, and every
+ * refusal of nig_rollout_mlp_safe; NIG_ERR_UNSUPPORTED where that is unsupported.
+ */
+#define NIG_MAX_CANDIDATES 128
+int nig_rollout_mlp_search(nig_handle *h, int32_t n_steps, int32_t n_candidates, float *reward_out,
+                           uint32_t *flags_out, int64_t out_stride, float *obs_out, int64_t obs_step_stride,
+                           float *act_out, int64_t ld_act, int64_t act_step_stride, float *prob_out,
+                           float *risk_out, int32_t *choice_out, void *stream);
 
 /*
  * Ensemble of MLP actors (agents/ensemble.py EnsembleAgent: predict, predict_with_uncertainty,

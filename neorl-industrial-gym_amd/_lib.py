@@ -23,6 +23,7 @@ FLAG_VIOL3, FLAG_NVIOL_HI = 0x1000, 0x2000
 FLAG_SHIELDED = 0x4000          # nig_rollout_mlp_safe: the safety critic halved the action
 FLAG_UNCERTAIN = 0x8000         # nig_rollout_mlp_ensemble: uncertainty > threshold on this live step
 MAX_ENSEMBLE = 8
+MAX_CANDIDATES = 128            # nig_rollout_mlp_search: n_candidates 1 .. NIG_MAX_CANDIDATES
 ENSEMBLE_AVERAGE, ENSEMBLE_VOTING = 0, 1
 CTR_STEP_MASK, CTR_DONE, CTR_VIOL_SHIFT = 0x7FFF, 0x8000, 16
 MAX_EPISODE_STEPS = 21845
@@ -37,7 +38,7 @@ SYMBOLS = [
     "nig_version", "nig_last_error", "nig_env_id", "nig_env_name", "nig_env_spec_get", "nig_layout_query",
     "nig_create", "nig_destroy", "nig_get_layout", "nig_workspace", "nig_get_counter", "nig_set_counter",
     "nig_set_constraint_mask", "nig_reset", "nig_step", "nig_fill_actions", "nig_set_state", "nig_get_state",
-    "nig_get_safety_metrics", "nig_reduce_tally", "nig_plan_create", "nig_plan_launch", "nig_plan_destroy", "nig_rollout", "nig_rollout_sampled", "nig_rollout_noise", "nig_bind_state", "nig_set_policy", "nig_rollout_policy", "nig_set_mlp_policy", "nig_rollout_mlp", "nig_set_mlp_safety", "nig_rollout_mlp_safe", "nig_set_mlp_ensemble", "nig_rollout_mlp_ensemble", "nig_set_disturbance", "nig_rollout_policy_disturbed", "nig_rollout_mlp_disturbed", "nig_reset_host", "nig_step_host",
+    "nig_get_safety_metrics", "nig_reduce_tally", "nig_plan_create", "nig_plan_launch", "nig_plan_destroy", "nig_rollout", "nig_rollout_sampled", "nig_rollout_noise", "nig_bind_state", "nig_set_policy", "nig_rollout_policy", "nig_set_mlp_policy", "nig_rollout_mlp", "nig_set_mlp_safety", "nig_rollout_mlp_safe", "nig_rollout_mlp_search", "nig_set_mlp_ensemble", "nig_rollout_mlp_ensemble", "nig_set_disturbance", "nig_rollout_policy_disturbed", "nig_rollout_mlp_disturbed", "nig_reset_host", "nig_step_host",
     "nig_step64", "nig_step_host64", "nig_reduce_metrics",
     "nig_create_mixed", "nig_mixed_destroy", "nig_mixed_get_info", "nig_mixed_state", "nig_mixed_segment", "nig_mixed_reset",
     "nig_mixed_fill_actions", "nig_mixed_rollout", "nig_rollout_mixed", "nig_mixed_step", "nig_rollout_mixed_obs", "nig_mixed_rollout_obs",
@@ -160,6 +161,7 @@ def lib():
     L.nig_rollout_mlp.argtypes = [vp, i32, vp, vp, i64, vp, i64, vp, i64, i64, vp]
     L.nig_set_mlp_safety.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, C.c_float, vp]
     L.nig_rollout_mlp_safe.argtypes = [vp, i32, vp, vp, i64, vp, i64, vp, i64, i64, vp, vp]
+    L.nig_rollout_mlp_search.argtypes = [vp, i32, i32, vp, vp, i64, vp, i64, vp, i64, i64, vp, vp, vp, vp]
     L.nig_set_mlp_ensemble.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, C.c_double, C.c_float, vp]
     L.nig_rollout_mlp_ensemble.argtypes = [vp, i32, vp, vp, i64, vp, i64, vp, i64, i64, vp, vp, vp]
     L.nig_set_disturbance.argtypes = [vp, C.POINTER(DisturbanceStruct), vp]

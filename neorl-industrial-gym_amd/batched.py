@@ -463,6 +463,23 @@ class BatchedIndustrialEnv:
         with torch.cuda.device(self._dev_index):
             _lib.check(self._L.nig_rollout_mlp_safe(self._h, int(n_steps), rp, fp, os_ or ps, op, so, ap, lda, sa, pp, self._stream()))
 
+    def rollout_mlp_search(self, n_steps: int, n_candidates: int, reward_out=None, flags_out=None, obs_out=None, act_out=None,
+                           prob_out=None, risk_out=None, choice_out=None):
+        """rollout_mlp_safe() with the safety-critical agents' get_safe_action in place of the halving ("nig-search-v1",
+        include/nig.h): where the installed critic's p of the actor's action is not below the installed threshold, the env
+        receives the first of least p among n_candidates (1 .. MAX_CANDIDATES) uniform actions of [-1, 1)
+        (policies.search_candidates restates the draws).  act_out holds the action the env received; prob_out float32 the
+        actor's action's p, risk_out float32 the received action's p, choice_out int32 the candidate's number (-1: the actor's
+        action was kept), each [n_steps, >=B] with the row stride of reward_out / flags_out; flags carry FLAG_SHIELDED where
+        a candidate was taken."""
+        rp, fp, os_, op, so, ap, lda, sa = self._closed_loop_outputs(n_steps, reward_out, flags_out, obs_out, act_out)
+        rows = [_rows(prob_out, torch.float32, n_steps), _rows(risk_out, torch.float32, n_steps), _rows(choice_out, torch.int32, n_steps)]
+        strides = {st for ptr, st in rows if ptr is not None} | ({os_} if (rp is not None or fp is not None) else set())
+        assert len(strides) <= 1, "prob_out, risk_out and choice_out share the reward/flags row stride"
+        with torch.cuda.device(self._dev_index):
+            _lib.check(self._L.nig_rollout_mlp_search(self._h, int(n_steps), int(n_candidates), rp, fp, strides.pop() if strides else 0,
+                                                      op, so, ap, lda, sa, rows[0][0], rows[1][0], rows[2][0], self._stream()))
+
     def set_mlp_ensemble(self, members, weights=None, weight_sum=None, method: str = "mean", uncertainty_threshold: float = 0.2):
         """Install an ensemble of actors (agents/ensemble.py EnsembleAgent) for rollout_mlp_ensemble(): `members` = a list of
         set_mlp_policy() weight lists.  method "mean" / "weighted": `weights` = the ACTIVE float64 weights of np.average (for

@@ -470,6 +470,9 @@ extern "C" {
 // +32.. and +48.. of the generator's policy stream).  Additive: generator and every existing entry point's results unchanged.
 // Still 0.8.0, for the same reason: nig_episode_log_query / _init, nig_collect_episodes, nig_reduce_episodes (per-episode records from the
 // reward / flag rows; csrc/nig_episodes.hpp).  Additive: no existing kernel or entry point changed.
+// Still 0.8.0, for the same reason: nig_rollout_mlp_search ("nig-search-v1": the safety-critical agents' get_safe_action -- the critic
+// scores n_candidates uniform actions where the actor's is too risky; blocks +0x100.. of the generator's policy stream).  Additive:
+// no new state on the handle, no existing kernel or entry point changed.
 const char *nig_version(void) { return "nig 0.8.0 (gfx950; generator nig-philox-v3)"; }
 const char *nig_last_error(void) { return g_err; }
 
@@ -1020,6 +1023,27 @@ int nig_rollout_mlp_safe(nig_handle *h, int32_t n_steps, float *reward_out, uint
     q.m.wstream = h->mlp_stream;
     q.cstream = h->mlp_cstream; q.prob_out = prob_out; q.threshold = h->mlp_threshold;
     launch_of(h->env)->mlp_shield(q, mlp_grid(h), (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    h->t += (uint32_t)n_steps;
+    return NIG_OK;
+}
+
+int nig_rollout_mlp_search(nig_handle *h, int32_t n_steps, int32_t n_candidates, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                           float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
+                           float *prob_out, float *risk_out, int32_t *choice_out, void *stream)
+{
+    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_search: bad argument");
+    if (!launch_of(h->env)->mlp_search) return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_mlp_search: env shape has no MFMA actor");
+    if (n_candidates < 1 || n_candidates > NIG_MAX_CANDIDATES) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_search: n_candidates outside 1 .. NIG_MAX_CANDIDATES");
+    if (!h->mlp_stream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_search: no actor installed (nig_set_mlp_policy)");
+    if (!h->mlp_cstream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_search: no safety critic installed (nig_set_mlp_safety)");
+    MlpSearchArgs q;
+    memset(&q, 0, sizeof q);
+    NIG_TRY(closed_loop_args(h, "nig_rollout_mlp_search", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, q.sh.m));
+    q.sh.m.wstream = h->mlp_stream;
+    q.sh.cstream = h->mlp_cstream; q.sh.prob_out = prob_out; q.sh.threshold = h->mlp_threshold;
+    q.n_candidates = n_candidates; q.risk_out = risk_out; q.choice_out = choice_out;
+    launch_of(h->env)->mlp_search(q, mlp_grid(h), (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     h->t += (uint32_t)n_steps;
     return NIG_OK;

@@ -23,6 +23,7 @@ struct EnvLaunch {
     void (*mlp_ensemble)(int ens, const MlpEnsArgs &, unsigned grid, hipStream_t);   // nig_rollout_mlp_ensemble; nullptr as `mlp`
     void (*policy_disturbed)(const PolicyDistArgs &, unsigned grid, hipStream_t);    // nig_rollout_policy_disturbed
     void (*mlp_disturbed)(const MlpDistArgs &, unsigned grid, hipStream_t);          // nig_rollout_mlp_disturbed; nullptr as `mlp`
+    void (*mlp_search)(const MlpSearchArgs &, unsigned grid, hipStream_t);           // nig_rollout_mlp_search; nullptr as `mlp`
 };
 
 template <class Env>
@@ -248,6 +249,18 @@ void launch_mlp_disturbed_env(const MlpDistArgs &q, unsigned grid, hipStream_t s
 ;
 #endif
 
+// nig_rollout_mlp_search: as the twins above, declared everywhere and DEFINED (its kernel instantiated) only in the env's
+// search_*.hip translation unit (NIG_DEFINE_ENV_SEARCH).
+template <class Env>
+void launch_mlp_search_env(const MlpSearchArgs &q, unsigned grid, hipStream_t st)
+#ifdef NIG_SEARCH_TU
+{
+    if constexpr (Env::S % 2 == 0 && Env::A <= 16) hipLaunchKernelGGL((rollout_mlp_search_kernel<Env>), dim3(grid), dim3(BLOCK), 0, st, q);
+}
+#else
+;
+#endif
+
 template <class Env>
 static void launch_policy(const PolicyArgs &q, unsigned /*grid*/, hipStream_t st)
 {
@@ -282,7 +295,8 @@ static const EnvLaunch *env_launch_table()
                                 launch_reset<Env>, launch_fill<Env>, rollout_rows_native<Env>, launch_rollout_sampled_env<Env>,
                                 (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp_ensemble_env<Env> : nullptr,
                                 launch_policy_disturbed_env<Env>,
-                                (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp_disturbed_env<Env> : nullptr};
+                                (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp_disturbed_env<Env> : nullptr,
+                                (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp_search_env<Env> : nullptr};
     return &T;
 }
 
@@ -313,3 +327,6 @@ void nig_launch_mixed_rollout(int out_mode, const nig::MixedArgs &m, unsigned gr
 #define NIG_DEFINE_ENV_DISTURBED(EnvType) \
     template void nig::launch_policy_disturbed_env<nig::EnvType>(const nig::PolicyDistArgs &, unsigned, hipStream_t); \
     template void nig::launch_mlp_disturbed_env<nig::EnvType>(const nig::MlpDistArgs &, unsigned, hipStream_t);
+// search_*.hip (compiled with NIG_SEARCH_TU defined before this header): the env's nig_rollout_mlp_search launcher and kernel
+#define NIG_DEFINE_ENV_SEARCH(EnvType) \
+    template void nig::launch_mlp_search_env<nig::EnvType>(const nig::MlpSearchArgs &, unsigned, hipStream_t);

@@ -1,5 +1,5 @@
 // nig_mlp.hpp -- the fused MLP actor on MFMA with its safety-critic shield and its ensemble (device code only): MlpArgs,
-// MlpShieldArgs, MlpEnsArgs, MlpDistArgs, rollout_mlp_body and its four kernels.
+// MlpShieldArgs, MlpEnsArgs, MlpDistArgs, MlpSearchArgs, rollout_mlp_body and its five kernels.
 #pragma once
 #include <type_traits>
 #include "nig_step.hpp"
@@ -112,12 +112,46 @@ struct MlpDistArgs {
     DisturbArgs d;
 };
 
-template <class Env, bool SHIELD, int ENS = ENS_NONE, bool DIST = false>
+// Safe-action search (rollout_mlp_search_kernel, agents/safety_critical.py RiskAwareCQLAgent.get_safe_action; include/nig.h
+// "nig-search-v1"): SEARCH is the shield's form with another correction.  Where the critic's p0 of the actor's action is not below
+// the threshold, n_candidates uniform actions of [-1, 1) are scored by the same critic pass -- through the same double-buffered LDS
+// image, the critic's stream cycled once per pass, candidate c + 1's layer-1 chunk in flight while candidate c's last hidden tile is
+// consumed, the next step's actor behind the last -- and the env receives the first one of least p.  MFMA passes and chunk
+// barriers are block-wide, so the block votes (__syncthreads_or) and runs no candidate pass when none of its live lanes asks
+// for one; the fill that follows p0's pass is issued after the vote (one exposed fill per step).  A lane that keeps its action
+// ignores the candidates, so no lane's result depends on its block's vote.  A candidate is a function of (lane key, c) alone: it is
+// drawn ahead of its pass's first chunk barrier, is dead after layer 1, and the winner is drawn again from its number at the end --
+// the running best is (p_best, choice): two registers, whatever n_candidates and A are.
+constexpr uint32_t SEARCH_BLOCK0 = 0x100u;       // candidate c, action j: word j & 3 of block STREAM_POLICY + SEARCH_BLOCK0 + 4 c + (j >> 2)
+struct MlpSearchArgs {
+    MlpShieldArgs sh;           // sh.prob_out: p0, the actor's action's p
+    int n_candidates;           // 1 .. NIG_MAX_CANDIDATES
+    float *risk_out;            // [n_steps][>= B] p of the action the env received, row k at risk_out + k * m.out_stride, may be NULL
+    int32_t *choice_out;        // [n_steps][>= B] the candidate's number, -1 where the actor's action was kept, may be NULL
+};
+
+// candidate c of the key's lane and step (action_from_word's [-1, 1) form, whatever the env's Box)
+template <int A>
+__device__ __forceinline__ void search_candidate(const RngKey &key, int c, float (&u)[A])
+{
+#pragma unroll
+    for (int j4 = 0; 4 * j4 < A; ++j4) {
+        const u32x4 x = key.block(STREAM_POLICY + SEARCH_BLOCK0 + 4u * (uint32_t)c + (uint32_t)j4);
+        const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (4 * j4 + k < A) u[4 * j4 + k] = action_from_word(w[k], -1.0f, 1.0f);
+    }
+}
+
+template <class Env, bool SHIELD, int ENS = ENS_NONE, bool DIST = false, bool SEARCH = false>
 __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const MlpArgs &q, const float *cstream, float *prob_out, float threshold,
                                                                        [[maybe_unused]] const MlpEnsArgs *eq = nullptr,
-                                                                       [[maybe_unused]] const DisturbArgs *dq = nullptr)
+                                                                       [[maybe_unused]] const DisturbArgs *dq = nullptr,
+                                                                       [[maybe_unused]] const MlpSearchArgs *sq = nullptr)
 {
     static_assert(!(SHIELD && ENS != ENS_NONE), "the ensemble has no shield");
+    static_assert(!SEARCH || SHIELD, "the search is a form of the shield");
     static_assert(!DIST || (!SHIELD && ENS == ENS_NONE), "the shield and the ensemble have no disturbed form");
     // the env steps on the ensemble's float64 action where its NumPy arithmetic follows the action's type (nig_step64's rule)
     constexpr bool ACT64 = ENS == ENS_AVERAGE && Env::HAS_ACT64;
@@ -141,6 +175,12 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
     const bool writer = in_range && half == 0;
     const uint32_t t_base = (p.t_ptr ? *p.t_ptr : 0u) + p.t_off;
     const uint64_t gi = p.env0 + (uint64_t)li;
+    // the lane's global index where a step needs it; the search forms it anew each time (as its output addresses, below: nothing
+    // that a step can form from the lane index is kept in registers across the candidate passes)
+    auto lane_gi = [&]() __attribute__((always_inline)) {
+        if constexpr (SEARCH) { uint32_t l = li; asm volatile("" : "+v"(l)); return p.env0 + (uint64_t)l; }
+        else return gi;
+    };
     const bool autoreset = (p.hflags & NIG_F_AUTORESET) != 0;
     const bool tally = p.tally != nullptr;
 
@@ -323,9 +363,16 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
         }
         [[maybe_unused]] bool shield = false;
         [[maybe_unused]] float prob = 0.0f;
+        [[maybe_unused]] float s_best = 0.0f;                      // search: p of the action the env receives, as far as the passes have come
+        [[maybe_unused]] int s_choice = -1, s_cand = -1, s_passes = 0;   // search: the best's number; this pass (-1: the actor's action); how many
+        [[maybe_unused]] float s_u[SEARCH ? A : 1];                // search: this pass's candidate (dead after layer 1)
         if constexpr (SHIELD) {
+            do {                                                   // (one pass unless SEARCH)
             // ---------------- safety critic on x = [s, a, 0]: the network (S + A, 1) ----------------
-            auto x = [&](int k) __attribute__((always_inline)) { return k < S ? s[k] : (k < S + A ? a[k - S] : 0.0f); };
+            auto x = [&](int k) __attribute__((always_inline)) {
+                if constexpr (SEARCH) return k < S ? s[k] : (k < S + A ? (s_cand < 0 ? a[k - S] : s_u[k - S]) : 0.0f);
+                else return k < S ? s[k] : (k < S + A ? a[k - S] : 0.0f);
+            };
             f32x16 g1[MLP_MT];
             // (one chunk: the actor's lines; two: a loop.  Only so do all eight shield kernels keep the parent's registers and
             // scratch -- with a one-trip loop, or with the two chunks spelled out, some spill more: profiles/mlp_network/isa_diff.txt)
@@ -348,22 +395,55 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
             for (int m2 = 0; m2 < MLP_MT; ++m2) {
                 __syncthreads();                            // critic chunk C1.chunks + m2 is in s_w[gbuf]
                 if (m2 + 1 < MLP_MT) cfill(C1.chunks + 1 + m2, gbuf ^ 1, MLP_PIECES);
+                else if constexpr (SEARCH) {                       // (behind p0's pass the fill waits for the block's vote, below)
+                    if (s_cand >= 0) {
+                        if (s_cand + 1 < s_passes) cfill(0, gbuf ^ 1, C1.pieces);      // the next candidate's layer 1
+                        else if (it + 1 < q.n_steps) fill(0, gbuf ^ 1, L1.pieces);
+                    }
+                }
                 else if (it + 1 < q.n_steps) fill(0, gbuf ^ 1, L1.pieces);   // the actor's layer 1 of the NEXT step
                 z4 = layer2_chunk(g1, z4, m2 + 1, gbuf);
                 gbuf ^= 1;
             }
             prob = det_sigmoidf(z4[0] + __shfl_xor(z4[0], 32));
-            shield = !(prob < threshold);
+            if constexpr (SEARCH) {
+                if (s_cand < 0) {
+                    s_best = prob;
+                    shield = !(prob < threshold) && !(ctr & NIG_CTR_DONE);     // (lanes past the batch are frozen: they never ask)
+                    // p0 leaves here, so that it is dead during the candidate passes
+                    if (writer && !(ctr & NIG_CTR_DONE) && prob_out) {
+                        uint32_t lo = li;
+                        asm volatile("" : "+v"(lo));
+                        (prob_out + (uint32_t)it * q.out_stride)[lo] = prob;
+                    }
+                    s_passes = __syncthreads_or(shield) ? sq->n_candidates : 0;
+                    // every wave is past the barrier behind which s_w[gbuf] was last read: it takes the chunk consumed next
+                    if (s_passes > 0) cfill(0, gbuf, C1.pieces);
+                    else if (it + 1 < q.n_steps) fill(0, gbuf, L1.pieces);
+                } else if (shield && (s_cand == 0 || prob < s_best || (s_best != s_best && prob == prob))) {   // the first of least p; a NaN never wins
+                    s_best = prob; s_choice = s_cand;
+                }
+                if (++s_cand < s_passes)                           // (beside the fill of its layer 1, ahead of the chunk barrier)
+                    search_candidate<A>(make_key(lane_gi(), t_base + (uint32_t)it + 1u, p.seed_lo, p.seed_hi, s_probit), s_cand, s_u);
+            }
+            } while (SEARCH && s_cand < s_passes);
+            if constexpr (SEARCH) {
+                if (shield) search_candidate<A>(make_key(lane_gi(), t_base + (uint32_t)it + 1u, p.seed_lo, p.seed_hi, s_probit), s_choice, a);
+            } else {
+                shield = !(prob < threshold);
 #pragma unroll
-            for (int r = 0; r < A; ++r) a[r] = shield ? a[r] * 0.5f : a[r];
+                for (int r = 0; r < A; ++r) a[r] = shield ? a[r] * 0.5f : a[r];
+            }
         }
 
         // ---------------- IndustrialEnv.step (both lane halves, identical results) ----------------
         const uint32_t orow = (uint32_t)it * q.out_stride;
+        uint32_t lo = li;                                          // the lane's index in this step's output addresses
+        if constexpr (SEARCH) asm volatile("" : "+v"(lo));         // (formed here, step by step: no address is kept in registers across the passes)
         const bool frozen = (ctr & NIG_CTR_DONE) != 0;
         if (writer && !frozen) {
             if (q.obs_out) {
-                float *oo = q.obs_out + (size_t)it * q.obs_step_stride + (size_t)li * S;
+                float *oo = q.obs_out + (size_t)it * q.obs_step_stride + (size_t)lo * S;
                 if constexpr (S % 4 == 0) {
 #pragma unroll
                     for (int k = 0; k < S / 4; ++k) store16(oo + 4 * k, s[4 * k], s[4 * k + 1], s[4 * k + 2], s[4 * k + 3]);
@@ -375,16 +455,20 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
             if (q.act_out) {
                 float *ao = q.act_out + (size_t)it * q.act_step_stride;
 #pragma unroll
-                for (int j = 0; j < A; ++j) (ao + j * q.ld_act_out)[li] = a[j];
+                for (int j = 0; j < A; ++j) (ao + j * q.ld_act_out)[lo] = a[j];
             }
-            if constexpr (SHIELD) {
-                if (prob_out) (prob_out + (uint32_t)it * q.out_stride)[li] = prob;
+            if constexpr (SHIELD && !SEARCH) {
+                if (prob_out) (prob_out + (uint32_t)it * q.out_stride)[lo] = prob;
+            }
+            if constexpr (SEARCH) {
+                if (sq->risk_out) (sq->risk_out + (uint32_t)it * q.out_stride)[lo] = s_best;
+                if (sq->choice_out) (sq->choice_out + (uint32_t)it * q.out_stride)[lo] = s_choice;
             }
             if constexpr (ENS != ENS_NONE) {
-                if (eq->unc_out) (eq->unc_out + (uint32_t)it * q.out_stride)[li] = unc;
+                if (eq->unc_out) (eq->unc_out + (uint32_t)it * q.out_stride)[lo] = unc;
             }
         }
-        const RngKey key = make_key(gi, t_base + (uint32_t)it + 1u, p.seed_lo, p.seed_hi, s_probit);
+        const RngKey key = make_key(lane_gi(), t_base + (uint32_t)it + 1u, p.seed_lo, p.seed_hi, s_probit);
         if constexpr (KS > 0) Env::draw_step(key, nz); else nz[0] = 0;
         const int step_pre = (int)(ctr & NIG_CTR_STEP_MASK);
         StepResult<Env, reward_of<Env, act_t>> res;
@@ -407,8 +491,8 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
             if (tally) ret = add_reward<Env, ACT64>(ret, res.reward);
         }
         if (writer) {
-            if (p.reward) (p.reward + orow)[li] = rew;
-            if (p.flags) (p.flags + orow)[li] = fl;
+            if (p.reward) (p.reward + orow)[lo] = rew;
+            if (p.flags) (p.flags + orow)[lo] = fl;
         }
         if (done) {
             ret = lt.finish(tally, ret, step, viol_ep, res.ncrit);
@@ -440,6 +524,13 @@ template <class Env>
 __global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_shield_kernel(const MlpShieldArgs q)
 {
     rollout_mlp_body<Env, true>(q.m, q.cstream, q.prob_out, q.threshold);
+}
+
+// Instantiated in the env's search_*.hip translation unit only (launch_mlp_search_env).
+template <class Env>
+__global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_search_kernel(const MlpSearchArgs q)
+{
+    rollout_mlp_body<Env, true, ENS_NONE, false, true>(q.sh.m, q.sh.cstream, q.sh.prob_out, q.sh.threshold, nullptr, nullptr, &q);
 }
 
 // ENS = ENS_AVERAGE / ENS_VOTING.  Instantiated in the env's ensemble_*.hip translation unit only (launch_mlp_ensemble_env).

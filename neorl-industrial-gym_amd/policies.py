@@ -197,6 +197,60 @@ def _spec_behaviour(P, quality: str) -> DevicePolicy:
     return DevicePolicy(S, A, W=W, b=b, sigma=[sigma] * A, p_uniform=eps, uniform_range=1.0, clip=(-1.0, 1.0))
 
 
+_PHILOX_M0, _PHILOX_M1, _PHILOX_W0, _PHILOX_W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+STREAM_POLICY, SEARCH_BLOCK0 = 0xC0000000, 0x100     # csrc/nig_detmath.hpp, csrc/nig_mlp.hpp
+
+
+def philox4x32_7(ctr, key):
+    """Philox4x32 with seven rounds (the library's generator, csrc/nig_detmath.hpp) of counters ctr [n, 4] under keys
+    key [n, 2] (or one key [2]) -> uint32 [n, 4]."""
+    c = np.asarray(ctr, dtype=np.uint64).reshape(-1, 4) & np.uint64(0xFFFFFFFF)
+    k = np.broadcast_to(np.asarray(key, dtype=np.uint64).reshape(-1, 2), (c.shape[0], 2)) & np.uint64(0xFFFFFFFF)
+    c0, c1, c2, c3 = (c[:, i].copy() for i in range(4))
+    k0, k1 = k[:, 0].copy(), k[:, 1].copy()
+    lo32, sh = np.uint64(0xFFFFFFFF), np.uint64(32)
+    for _ in range(7):
+        p0, p1 = np.uint64(_PHILOX_M0) * c0, np.uint64(_PHILOX_M1) * c2         # 32 x 32 -> 64 bits: no overflow
+        c0, c1, c2, c3 = (p1 >> sh) ^ c1 ^ k0, p1 & lo32, (p0 >> sh) ^ c3 ^ k1, p0 & lo32
+        k0, k1 = (k0 + np.uint64(_PHILOX_W0)) & lo32, (k1 + np.uint64(_PHILOX_W1)) & lo32
+    return np.stack([c0, c1, c2, c3], axis=1).astype(np.uint32)
+
+
+def search_candidates(seed: int, env_index: int, t: int, n_candidates: int, action_dim: int):
+    """The candidate actions nig_rollout_mlp_search draws for lane `env_index` (its global index) on the step whose launch
+    counter is t: float32 [n_candidates, action_dim], the one host statement of "nig-search-v1"'s draws (include/nig.h).
+    Action j of candidate c is fmaf(w >> 8, 2^-23, -1) -- uniform on [-1, 1), a multiple of 2^-23, so the float32 arithmetic
+    below rounds nothing -- of word j & 3 of the policy stream's block 0x100 + 4 c + (j >> 2) under the key (env_index, t, seed)."""
+    N, A = int(n_candidates), int(action_dim)
+    nb = (A + 3) // 4
+    assert N >= 1 and 1 <= nb <= 4
+    blocks = STREAM_POLICY + SEARCH_BLOCK0 + 4 * np.arange(N, dtype=np.uint64)[:, None] + np.arange(nb, dtype=np.uint64)[None, :]
+    ctr = np.empty((N * nb, 4), dtype=np.uint64)
+    ctr[:, 0], ctr[:, 1], ctr[:, 2] = int(env_index) & 0xFFFFFFFF, (int(env_index) >> 32) & 0xFFFFFFFF, int(t) & 0xFFFFFFFF
+    ctr[:, 3] = blocks.reshape(-1)
+    w = philox4x32_7(ctr, [int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF]).reshape(N, 4 * nb)[:, :A]
+    return ((w >> np.uint32(8)).astype(f32) * f32(2.0 ** -23) - f32(1.0)).astype(f32)
+
+
+def pad_critic(weights, hidden: int = 256):
+    """A critic [(C1 [D,h], c1 [h]), (C2 [h,h], c2 [h]), (C3 [h,1], c3 [1])] with h <= hidden (the reference's RiskEstimator:
+    128) as the `hidden`-wide network set_mlp_safety() takes: C1's columns, C2's rows and columns, C3's rows and the biases
+    padded with zeros.  The added units are exactly 0 after ReLU and every added term is an exact zero, so the padded
+    network computes the h-wide one's number.  hidden-wide weights come back as float32 copies; anything else is refused."""
+    if len(weights) != 3:
+        raise ValueError(f"a critic has three layers, got {len(weights)}")
+    (C1, c1), (C2, c2), (C3, c3) = [(np.asarray(W, dtype=f32), np.asarray(b, dtype=f32).reshape(-1)) for W, b in weights]
+    C3 = C3.reshape(C3.shape[0], -1)
+    h = C1.shape[1]
+    if not (1 <= h <= hidden and C2.shape == (h, h) and C3.shape == (h, 1) and c1.shape == (h,) and c2.shape == (h,) and c3.shape == (1,)):
+        raise ValueError(f"cannot pad a critic of shapes {[np.shape(W) for W, _ in weights]} to hidden width {hidden}")
+    P1, p1 = np.zeros((C1.shape[0], hidden), dtype=f32), np.zeros(hidden, dtype=f32)
+    P2, p2 = np.zeros((hidden, hidden), dtype=f32), np.zeros(hidden, dtype=f32)
+    P3 = np.zeros((hidden, 1), dtype=f32)
+    P1[:, :h], p1[:h], P2[:h, :h], p2[:h], P3[:h] = C1, c1, C2, c2, C3
+    return [(P1, p1), (P2, p2), (P3, c3.copy())]
+
+
 class MLPPolicy:
     """The deterministic actor of the reference's agents -- (S -> 256 -> 256 -> A) ReLU MLP with a
     tanh head (agents/networks.py:47-70,125-144; cql.py:339-343) -- kept on the GPU.
@@ -237,13 +291,24 @@ class MLPPolicy:
                                   for W, b in self.safety_weights]
 
     @classmethod
-    def from_agent(cls, agent, device="cuda:0"):
+    def from_agent(cls, agent, device="cuda:0", critic: str = "safety"):
         """The actor (and, when the agent has one, the safety critic with the agent's constraint_threshold) of a
         reference agent: agent.state["actor"].params / agent.state["safety"].params, Flax trees
         {"params": {"MLP_0": {"Dense_0|1|2": {"kernel", "bias"}}}} (any nested mapping of array-likes).  LayerNorm
-        networks are refused (ValueError); Dropout has no parameters and is inert at training=False."""
+        networks are refused (ValueError); Dropout has no parameters and is inert at training=False.
+        critic="risk": the critic is the RiskEstimator of the safety-critical agents (agents/safety_critical.py:113-149),
+        agent.risk_state.params = {"params": {"layers_0", "layers_1", "risk_head"}} (modules built in setup), with
+        agent.uncertainty_threshold as the threshold -- what get_safe_action / searching() score with."""
+        if critic not in ("safety", "risk"):
+            raise ValueError(f"critic is 'safety' or 'risk', not {critic!r}")
         state = agent.state
         actor = _dense_layers(state["actor"].params, "actor")
+        if critic == "risk":
+            rs = getattr(agent, "risk_state", None)
+            if rs is None or getattr(rs, "params", None) is None:
+                raise ValueError("critic='risk' needs agent.risk_state.params (a safety-critical agent's RiskEstimator)")
+            return cls(actor, device=device, safety_weights=_named_layers(rs.params, ("layers_0", "layers_1", "risk_head"), "risk"),
+                       constraint_threshold=getattr(agent, "uncertainty_threshold", 0.1))
         safety = state.get("safety") if hasattr(state, "get") else None
         critic = None if safety is None or getattr(safety, "params", None) is None else _dense_layers(safety.params, "safety")
         return cls(actor, device=device, safety_weights=critic,
@@ -309,6 +374,84 @@ class MLPPolicy:
         if self.safety_layers is None:
             raise RuntimeError("Safety critic must be trained")
         return ShieldedMLPPolicy(self, self._threshold(safety_threshold))
+
+
+    # ---- get_safe_action of the safety-critical agents (agents/safety_critical.py:173-208) ----
+    def _search_threshold(self, safety_threshold):
+        return self.constraint_threshold if safety_threshold is None else float(safety_threshold)   # (0.0 is a threshold here)
+
+    def get_safe_action_device(self, obs, preferred=None, n_candidates: int = 100, safety_threshold=None, generator=None):
+        """RiskAwareCQLAgent.get_safe_action on device tensors, a batch of states at once: the critic scores `preferred`
+        (default: the actor's action); rows whose risk is not below the threshold (default: constraint_threshold) get the
+        first of least risk among n_candidates uniform actions, even where that risk is above the preferred action's (as the
+        reference).  The law of nig_rollout_mlp_search with torch's draws, u = torch.rand((n, n_candidates, A), generator=
+        generator) * 2 - 1 in one call, and torch's GEMMs: it agrees with the kernel in distribution, not draw for draw.
+        Returns (actions [n, A], {"risk" [n]: of the returned action, "corrected" [n] bool, "choice" [n]: the candidate's
+        number, -1 where the preferred action was kept})."""
+        import torch
+        a = self.predict_device(obs) if preferred is None else preferred
+        p0 = self.safety_probs_device(obs, a)
+        corrected = ~(p0 < self._search_threshold(safety_threshold))
+        n, N = obs.shape[0], int(n_candidates)
+        u = torch.rand((n, N, self.action_dim), generator=generator, dtype=torch.float32, device=obs.device) * 2.0 - 1.0
+        best = torch.zeros(n, dtype=torch.int64, device=obs.device)
+        p_best = self.safety_probs_device(obs, u[:, 0])
+        for c in range(1, N):                                  # the running first minimum: memory does not grow with N
+            pc = self.safety_probs_device(obs, u[:, c])
+            take = (pc < p_best) | (torch.isnan(p_best) & ~torch.isnan(pc))
+            p_best = torch.where(take, pc, p_best)
+            best = torch.where(take, torch.full_like(best, c), best)
+        u_best = u[torch.arange(n, device=obs.device), best]
+        info = {"risk": torch.where(corrected, p_best, p0), "corrected": corrected,
+                "choice": torch.where(corrected, best, torch.full_like(best, -1))}
+        return torch.where(corrected[:, None], u_best, a), info
+
+    def get_safe_action(self, observations, preferred=None, n_candidates: int = 100, safety_threshold=None, generator=None):
+        """get_safe_action_device on host arrays: (actions, {"risk", "corrected", "choice"}) as NumPy arrays (scalars in the
+        dict for a single observation, the reference's form)."""
+        import torch
+        if self.safety_layers is None:
+            raise RuntimeError("Safety critic must be trained")
+        o = torch.as_tensor(np.asarray(observations, dtype=f32), device=self.device)
+        single = o.dim() == 1
+        pa = None if preferred is None else torch.as_tensor(np.asarray(preferred, dtype=f32), device=self.device).reshape(-1, self.action_dim)
+        a, info = self.get_safe_action_device(o.reshape(-1, self.state_dim), pa, n_candidates, safety_threshold, generator)
+        a, info = a.cpu().numpy(), {k: v.cpu().numpy() for k, v in info.items()}
+        if single:
+            return a[0], {"risk": float(info["risk"][0]), "corrected": bool(info["corrected"][0]), "choice": int(info["choice"][0])}
+        return a, info
+
+    def searching(self, n_candidates: int = 100, safety_threshold=None):
+        """The policy that acts with get_safe_action's actions (for evaluate_with_safety / evaluate_episodes)."""
+        if self.safety_layers is None:
+            raise RuntimeError("Safety critic must be trained")
+        return SearchShieldPolicy(self, n_candidates, self._search_threshold(safety_threshold))
+
+
+class SearchShieldPolicy:
+    """MLPPolicy.searching(): predict / predict_device give get_safe_action's actions.  When the actor has the reference shape
+    and the critic three layers of hidden width <= 256 (padded to 256 by pad_critic: the reference's RiskEstimator is 128 wide),
+    evaluate_with_safety runs it fused into the env kernel (BatchedIndustrialEnv.rollout_mlp_search); otherwise, and under a
+    disturbance.Disturbed wrapper, through torch GEMMs with torch's draws."""
+    is_trained = True
+
+    def __init__(self, base: MLPPolicy, n_candidates: int, threshold: float):
+        if not 1 <= int(n_candidates) <= _lib.MAX_CANDIDATES:
+            raise ValueError(f"n_candidates must lie in 1 .. {_lib.MAX_CANDIDATES}, got {n_candidates}")
+        self.base = base
+        self.n_candidates, self.threshold = int(n_candidates), float(threshold)
+        self.state_dim, self.action_dim = base.state_dim, base.action_dim
+        self.weights = base.weights
+        sw = base.safety_weights
+        h = sw[0][0].shape[1]
+        self.fusable = base.fusable and len(sw) == 3 and h <= 256 and sw[1][0].shape == (h, h)
+        self.safety_weights = pad_critic(sw) if self.fusable else sw        # what set_mlp_safety takes
+
+    def predict_device(self, obs):
+        return self.base.get_safe_action_device(obs, None, self.n_candidates, self.threshold)[0]
+
+    def predict(self, observations, deterministic: bool = True):
+        return self.base.get_safe_action(observations, None, self.n_candidates, self.threshold)[0]
 
 
 class ShieldedMLPPolicy:
@@ -511,6 +654,20 @@ class EnsemblePolicy:
         dist = [np.mean(np.abs(preds[i] - preds[j])) for i in range(K) for j in range(i + 1, K)]
         unc = ensemble_uncertainty(preds.reshape(K, -1, preds.shape[-1]))
         return {"diversity_score": float(np.mean(dist)), "disagreement": float(np.mean(unc)), "n_agents": K}
+
+
+def _named_layers(tree, names, what):
+    """[(kernel, bias), ...] of the modules `names` of a Flax parameter tree (any nested mapping), found under any chain of
+    single-child mappings (the tree's "params")."""
+    t = tree
+    while hasattr(t, "items") and not all(n in t.keys() for n in names):
+        subs = [v for v in t.values() if hasattr(v, "items")]
+        if len(subs) != 1:
+            raise ValueError(f"{what}: cannot find the layers {list(names)} of the parameter tree (keys {list(t.keys())})")
+        t = subs[0]
+    if not hasattr(t, "items"):
+        raise ValueError(f"{what}: cannot find the layers {list(names)} of the parameter tree")
+    return [(np.asarray(t[n]["kernel"], dtype=f32), np.asarray(t[n]["bias"], dtype=f32)) for n in names]
 
 
 def _dense_layers(tree, what):
