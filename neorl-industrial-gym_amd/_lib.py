@@ -34,19 +34,6 @@ TUNE_SPLIT_BLOCKS = 0
 TUNE_WIDE_MIN_BLOCKS = 1
 TUNE_DIAG_RING_FAULT = 2
 
-SYMBOLS = [
-    "nig_version", "nig_last_error", "nig_env_id", "nig_env_name", "nig_env_spec_get", "nig_layout_query",
-    "nig_create", "nig_destroy", "nig_get_layout", "nig_workspace", "nig_get_counter", "nig_set_counter",
-    "nig_set_constraint_mask", "nig_reset", "nig_step", "nig_fill_actions", "nig_set_state", "nig_get_state",
-    "nig_get_safety_metrics", "nig_reduce_tally", "nig_plan_create", "nig_plan_launch", "nig_plan_destroy", "nig_rollout", "nig_rollout_sampled", "nig_rollout_noise", "nig_bind_state", "nig_set_policy", "nig_rollout_policy", "nig_set_mlp_policy", "nig_rollout_mlp", "nig_set_mlp_safety", "nig_rollout_mlp_safe", "nig_rollout_mlp_search", "nig_set_mlp_ensemble", "nig_rollout_mlp_ensemble", "nig_set_disturbance", "nig_rollout_policy_disturbed", "nig_rollout_mlp_disturbed", "nig_reset_host", "nig_step_host",
-    "nig_step64", "nig_step_host64", "nig_reduce_metrics",
-    "nig_create_mixed", "nig_mixed_destroy", "nig_mixed_get_info", "nig_mixed_state", "nig_mixed_segment", "nig_mixed_reset",
-    "nig_mixed_fill_actions", "nig_mixed_rollout", "nig_rollout_mixed", "nig_mixed_step", "nig_rollout_mixed_obs", "nig_mixed_rollout_obs",
-    "nig_tune", "nig_tune_get", "nig_handle_tune_get", "nig_clock_stamp",
-    "nig_episode_log_query", "nig_episode_log_init", "nig_collect_episodes", "nig_reduce_episodes",
-]
-
-
 class EnvSpec(C.Structure):
     _fields_ = [("state_dim", C.c_int32), ("action_dim", C.c_int32), ("n_constraints", C.c_int32),
                 ("max_episode_steps", C.c_int32), ("k_step", C.c_int32), ("k_reset", C.c_int32),
@@ -96,6 +83,81 @@ class MixedInfo(C.Structure):
                 ("count", C.c_int64 * MIXED_MAX_SEGMENTS)]
 
 
+# The C ABI as ctypes sees it: symbol -> (restype, argtypes).
+cp, vp, ci, i32, i64, u32, u64, f32, f64, P = (C.c_char_p, C.c_void_p, C.c_int, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64,
+                                               C.c_float, C.c_double, C.POINTER)
+# what the closed-loop rollouts share: handle, n_steps, reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act,
+# act_step_stride; each adds its own outputs and the stream (nig_rollout_mlp_search: n_candidates after n_steps)
+CLOSED_LOOP = [vp, i32, vp, vp, i64, vp, i64, vp, i64, i64]
+PROTOTYPES = {
+    "nig_version": (cp, []),
+    "nig_last_error": (cp, []),
+    "nig_tune": (ci, [i32, i64]),
+    "nig_tune_get": (i64, [i32]),
+    "nig_handle_tune_get": (i64, [vp, i32]),
+    "nig_clock_stamp": (ci, [vp, vp]),
+    "nig_env_id": (ci, [cp]),
+    "nig_env_name": (cp, [ci]),
+    "nig_env_spec_get": (ci, [ci, P(EnvSpec)]),
+    "nig_layout_query": (ci, [ci, i64, u32, P(Layout)]),
+    "nig_create": (ci, [ci, i64, ci, u64, u64, i32, f64, u32, vp, P(vp)]),
+    "nig_destroy": (ci, [vp]),
+    "nig_get_layout": (ci, [vp, P(Layout)]),
+    "nig_workspace": (vp, [vp]),
+    "nig_get_counter": (ci, [vp, P(u32)]),
+    "nig_set_counter": (ci, [vp, u32]),
+    "nig_set_constraint_mask": (ci, [vp, u32]),
+    "nig_reset": (ci, [vp, vp, vp, i64, vp]),
+    "nig_step": (ci, [vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, i64, vp]),
+    "nig_fill_actions": (ci, [vp, u32, vp, i64, vp]),
+    "nig_set_state": (ci, [vp, vp, i64, vp, vp]),
+    "nig_get_state": (ci, [vp, vp, i64, vp, vp]),
+    "nig_get_safety_metrics": (ci, [vp, vp, vp, i64, vp]),
+    "nig_reduce_tally": (ci, [vp, vp, vp]),
+    "nig_plan_create": (ci, [vp, i32, vp, i64, i64, i32, vp, vp, i64, P(vp)]),
+    "nig_plan_launch": (ci, [vp, vp]),
+    "nig_plan_destroy": (ci, [vp]),
+    "nig_bind_state": (ci, [vp, vp, i64]),
+    "nig_set_policy": (ci, [vp, P(Policy), vp]),
+    "nig_rollout_policy": (ci, CLOSED_LOOP + [vp]),
+    "nig_set_mlp_policy": (ci, [vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "nig_rollout_mlp": (ci, CLOSED_LOOP + [vp]),
+    "nig_set_mlp_safety": (ci, [vp, i32, vp, vp, vp, vp, vp, vp, f32, vp]),
+    "nig_rollout_mlp_safe": (ci, CLOSED_LOOP + [vp, vp]),
+    "nig_rollout_mlp_search": (ci, CLOSED_LOOP[:2] + [i32] + CLOSED_LOOP[2:] + [vp, vp, vp, vp]),
+    "nig_set_mlp_ensemble": (ci, [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, f64, f32, vp]),
+    "nig_rollout_mlp_ensemble": (ci, CLOSED_LOOP + [vp, vp, vp]),
+    "nig_set_disturbance": (ci, [vp, P(DisturbanceStruct), vp]),
+    "nig_rollout_policy_disturbed": (ci, CLOSED_LOOP + [vp, i64, vp]),
+    "nig_rollout_mlp_disturbed": (ci, CLOSED_LOOP + [vp, i64, vp]),
+    "nig_reset_host": (ci, [vp, vp, vp, vp]),
+    "nig_step_host": (ci, [vp, vp, vp, vp, vp, vp, vp]),
+    "nig_step_host64": (ci, [vp, vp, vp, vp, vp, vp, vp]),
+    "nig_reduce_metrics": (ci, [P(vp), i32, vp, vp, i64, vp, vp]),
+    "nig_step64": (ci, [vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, i64, vp]),
+    "nig_rollout": (ci, [vp, i32, vp, i64, i64, i32, vp, vp, i64, vp, i64, i64, vp]),
+    "nig_rollout_sampled": (ci, [vp, i32, vp, vp, i64, vp, i64, i64, vp]),
+    "nig_rollout_noise": (ci, [vp, i32, vp, i64, i64, i32, vp, i64, vp, i64, i64, vp, vp, i64, vp, i64, vp]),
+    "nig_create_mixed": (ci, [i32, P(i32), P(i64), ci, u64, u64, u32, P(vp)]),
+    "nig_mixed_destroy": (ci, [vp]),
+    "nig_mixed_get_info": (ci, [vp, P(MixedInfo)]),
+    "nig_mixed_state": (vp, [vp]),
+    "nig_mixed_segment": (vp, [vp, i32]),
+    "nig_mixed_reset": (ci, [vp, vp]),
+    "nig_mixed_fill_actions": (ci, [vp, u32, vp, vp]),
+    "nig_mixed_rollout": (ci, [vp, i32, vp, i64, i32, vp, vp, i64, vp]),
+    "nig_mixed_step": (ci, [vp, vp, vp, vp, vp]),
+    "nig_rollout_mixed": (ci, [P(vp), P(i64), i32, i32, vp, i64, i64, i32, vp, vp, i64, vp]),
+    "nig_rollout_mixed_obs": (ci, [P(vp), P(i64), i32, i32, vp, i64, i64, i32, vp, vp, i64, vp, i64, i64, vp]),
+    "nig_mixed_rollout_obs": (ci, [vp, i32, vp, i64, i32, vp, vp, i64, vp, i64, vp]),
+    "nig_episode_log_query": (ci, [i64, i64, i64, P(EpisodeLogLayout)]),
+    "nig_episode_log_init": (ci, [vp, vp, i64, i64, vp]),
+    "nig_collect_episodes": (ci, [vp, i32, vp, vp, i64, vp, i64, i64, vp]),
+    "nig_reduce_episodes": (ci, [vp, vp, i64, i64, i64, vp, vp]),
+}
+SYMBOLS = list(PROTOTYPES)
+
+
 class NigError(RuntimeError):
     pass
 
@@ -122,77 +184,8 @@ def lib():
             f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             "(hipcc --offload-arch=gfx950).  This package has no CPU fallback.")
     L = C.CDLL(path)
-    vp, i64, u32, u64, i32 = C.c_void_p, C.c_int64, C.c_uint32, C.c_uint64, C.c_int32
-    L.nig_version.restype = C.c_char_p
-    L.nig_last_error.restype = C.c_char_p
-    L.nig_tune.argtypes = [C.c_int32, C.c_int64]
-    L.nig_tune_get.argtypes = [C.c_int32]
-    L.nig_tune_get.restype = C.c_int64
-    L.nig_handle_tune_get.argtypes = [C.c_void_p, C.c_int32]
-    L.nig_handle_tune_get.restype = C.c_int64
-    L.nig_clock_stamp.argtypes = [C.c_void_p, C.c_void_p]
-    L.nig_env_id.argtypes = [C.c_char_p]
-    L.nig_env_name.restype = C.c_char_p
-    L.nig_env_name.argtypes = [C.c_int]
-    L.nig_env_spec_get.argtypes = [C.c_int, C.POINTER(EnvSpec)]
-    L.nig_layout_query.argtypes = [C.c_int, i64, u32, C.POINTER(Layout)]
-    L.nig_create.argtypes = [C.c_int, i64, C.c_int, u64, u64, i32, C.c_double, u32, vp, C.POINTER(vp)]
-    L.nig_destroy.argtypes = [vp]
-    L.nig_get_layout.argtypes = [vp, C.POINTER(Layout)]
-    L.nig_workspace.restype = vp
-    L.nig_workspace.argtypes = [vp]
-    L.nig_get_counter.argtypes = [vp, C.POINTER(u32)]
-    L.nig_set_counter.argtypes = [vp, u32]
-    L.nig_set_constraint_mask.argtypes = [vp, u32]
-    L.nig_reset.argtypes = [vp, vp, vp, i64, vp]
-    L.nig_step.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, i64, vp]
-    L.nig_fill_actions.argtypes = [vp, u32, vp, i64, vp]
-    L.nig_set_state.argtypes = [vp, vp, i64, vp, vp]
-    L.nig_get_state.argtypes = [vp, vp, i64, vp, vp]
-    L.nig_get_safety_metrics.argtypes = [vp, vp, vp, i64, vp]
-    L.nig_reduce_tally.argtypes = [vp, vp, vp]
-    L.nig_plan_create.argtypes = [vp, i32, vp, i64, i64, i32, vp, vp, i64, C.POINTER(vp)]
-    L.nig_plan_launch.argtypes = [vp, vp]
-    L.nig_plan_destroy.argtypes = [vp]
-    L.nig_bind_state.argtypes = [vp, vp, i64]
-    L.nig_set_policy.argtypes = [vp, C.POINTER(Policy), vp]
-    L.nig_rollout_policy.argtypes = [vp, i32, vp, vp, i64, vp, i64, vp, i64, i64, vp]
-    L.nig_set_mlp_policy.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
-    L.nig_rollout_mlp.argtypes = [vp, i32, vp, vp, i64, vp, i64, vp, i64, i64, vp]
-    L.nig_set_mlp_safety.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, C.c_float, vp]
-    L.nig_rollout_mlp_safe.argtypes = [vp, i32, vp, vp, i64, vp, i64, vp, i64, i64, vp, vp]
-    L.nig_rollout_mlp_search.argtypes = [vp, i32, i32, vp, vp, i64, vp, i64, vp, i64, i64, vp, vp, vp, vp]
-    L.nig_set_mlp_ensemble.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, C.c_double, C.c_float, vp]
-    L.nig_rollout_mlp_ensemble.argtypes = [vp, i32, vp, vp, i64, vp, i64, vp, i64, i64, vp, vp, vp]
-    L.nig_set_disturbance.argtypes = [vp, C.POINTER(DisturbanceStruct), vp]
-    L.nig_rollout_policy_disturbed.argtypes = [vp, i32, vp, vp, i64, vp, i64, vp, i64, i64, vp, i64, vp]
-    L.nig_rollout_mlp_disturbed.argtypes = [vp, i32, vp, vp, i64, vp, i64, vp, i64, i64, vp, i64, vp]
-    L.nig_reset_host.argtypes = [vp, vp, vp, vp]
-    L.nig_step_host.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    L.nig_step_host64.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    L.nig_reduce_metrics.argtypes = [C.POINTER(vp), i32, vp, vp, i64, vp, vp]
-    L.nig_step64.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, i64, vp]
-    L.nig_rollout.argtypes = [vp, i32, vp, i64, i64, i32, vp, vp, i64, vp, i64, i64, vp]
-    L.nig_rollout_sampled.argtypes = [vp, i32, vp, vp, i64, vp, i64, i64, vp]
-    L.nig_rollout_noise.argtypes = [vp, i32, vp, i64, i64, i32, vp, i64, vp, i64, i64, vp, vp, i64, vp, i64, vp]
-    L.nig_create_mixed.argtypes = [i32, C.POINTER(i32), C.POINTER(i64), C.c_int, u64, u64, u32, C.POINTER(vp)]
-    L.nig_mixed_destroy.argtypes = [vp]
-    L.nig_mixed_get_info.argtypes = [vp, C.POINTER(MixedInfo)]
-    L.nig_mixed_state.restype = vp
-    L.nig_mixed_state.argtypes = [vp]
-    L.nig_mixed_segment.restype = vp
-    L.nig_mixed_segment.argtypes = [vp, i32]
-    L.nig_mixed_reset.argtypes = [vp, vp]
-    L.nig_mixed_fill_actions.argtypes = [vp, u32, vp, vp]
-    L.nig_mixed_rollout.argtypes = [vp, i32, vp, i64, i32, vp, vp, i64, vp]
-    L.nig_mixed_step.argtypes = [vp, vp, vp, vp, vp]
-    L.nig_rollout_mixed.argtypes = [C.POINTER(vp), C.POINTER(i64), i32, i32, vp, i64, i64, i32, vp, vp, i64, vp]
-    L.nig_rollout_mixed_obs.argtypes = [C.POINTER(vp), C.POINTER(i64), i32, i32, vp, i64, i64, i32, vp, vp, i64, vp, i64, i64, vp]
-    L.nig_mixed_rollout_obs.argtypes = [vp, i32, vp, i64, i32, vp, vp, i64, vp, i64, vp]
-    L.nig_episode_log_query.argtypes = [i64, i64, i64, C.POINTER(EpisodeLogLayout)]
-    L.nig_episode_log_init.argtypes = [vp, vp, i64, i64, vp]
-    L.nig_collect_episodes.argtypes = [vp, i32, vp, vp, i64, vp, i64, i64, vp]
-    L.nig_reduce_episodes.argtypes = [vp, vp, i64, i64, i64, vp, vp]
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        getattr(L, name).restype, getattr(L, name).argtypes = restype, argtypes
     _lib = L
     return L
 

@@ -439,9 +439,7 @@ class BatchedIndustrialEnv:
     def rollout_mlp(self, n_steps: int, reward_out=None, flags_out=None, obs_out=None, act_out=None):
         """Closed loop with the installed MLP actor evaluated by f32 MFMA inside the env kernel
         (same outputs as rollout_policy)."""
-        rp, fp, os_, op, so, ap, lda, sa = self._closed_loop_outputs(n_steps, reward_out, flags_out, obs_out, act_out)
-        with torch.cuda.device(self._dev_index):
-            _lib.check(self._L.nig_rollout_mlp(self._h, int(n_steps), rp, fp, os_, op, so, ap, lda, sa, self._stream()))
+        self._closed_loop(self._L.nig_rollout_mlp, n_steps, reward_out, flags_out, obs_out, act_out)
 
     def set_mlp_safety(self, weights, threshold: float):
         """Install the reference agents' safety critic ((S+A)->256->256->1, ReLU, sigmoid) for rollout_mlp_safe():
@@ -457,11 +455,8 @@ class BatchedIndustrialEnv:
         """rollout_mlp() with the safety-critic shield (predict_with_safety on the device): act_out holds the action the
         env received; prob_out float32 [n_steps, >=B] the critic's p of the unshielded action (same row stride as
         reward_out / flags_out); flags carry FLAG_SHIELDED where the action was halved."""
-        rp, fp, os_, op, so, ap, lda, sa = self._closed_loop_outputs(n_steps, reward_out, flags_out, obs_out, act_out)
-        pp, ps = _rows(prob_out, torch.float32, n_steps)
-        assert pp is None or (rp is None and fp is None) or ps == os_, "prob_out shares the reward/flags row stride"
-        with torch.cuda.device(self._dev_index):
-            _lib.check(self._L.nig_rollout_mlp_safe(self._h, int(n_steps), rp, fp, os_ or ps, op, so, ap, lda, sa, pp, self._stream()))
+        self._closed_loop(self._L.nig_rollout_mlp_safe, n_steps, reward_out, flags_out, obs_out, act_out,
+                          rows=[("prob_out", prob_out, torch.float32)])
 
     def rollout_mlp_search(self, n_steps: int, n_candidates: int, reward_out=None, flags_out=None, obs_out=None, act_out=None,
                            prob_out=None, risk_out=None, choice_out=None):
@@ -472,13 +467,8 @@ class BatchedIndustrialEnv:
         actor's action's p, risk_out float32 the received action's p, choice_out int32 the candidate's number (-1: the actor's
         action was kept), each [n_steps, >=B] with the row stride of reward_out / flags_out; flags carry FLAG_SHIELDED where
         a candidate was taken."""
-        rp, fp, os_, op, so, ap, lda, sa = self._closed_loop_outputs(n_steps, reward_out, flags_out, obs_out, act_out)
-        rows = [_rows(prob_out, torch.float32, n_steps), _rows(risk_out, torch.float32, n_steps), _rows(choice_out, torch.int32, n_steps)]
-        strides = {st for ptr, st in rows if ptr is not None} | ({os_} if (rp is not None or fp is not None) else set())
-        assert len(strides) <= 1, "prob_out, risk_out and choice_out share the reward/flags row stride"
-        with torch.cuda.device(self._dev_index):
-            _lib.check(self._L.nig_rollout_mlp_search(self._h, int(n_steps), int(n_candidates), rp, fp, strides.pop() if strides else 0,
-                                                      op, so, ap, lda, sa, rows[0][0], rows[1][0], rows[2][0], self._stream()))
+        self._closed_loop(self._L.nig_rollout_mlp_search, n_steps, reward_out, flags_out, obs_out, act_out, head=(int(n_candidates),),
+                          rows=[("prob_out", prob_out, torch.float32), ("risk_out", risk_out, torch.float32), ("choice_out", choice_out, torch.int32)])
 
     def set_mlp_ensemble(self, members, weights=None, weight_sum=None, method: str = "mean", uncertainty_threshold: float = 0.2):
         """Install an ensemble of actors (agents/ensemble.py EnsembleAgent) for rollout_mlp_ensemble(): `members` = a list of
@@ -506,19 +496,33 @@ class BatchedIndustrialEnv:
         to float32 for "mean" / "weighted"); unc_out float32 [n_steps, >=B] the members' disagreement (same row stride as
         reward_out / flags_out); member_act_out float32 [n_steps, K, A, >=B] every member's action (same pitches as act_out);
         flags carry FLAG_UNCERTAIN where the uncertainty exceeds the installed threshold."""
-        rp, fp, os_, op, so, ap, lda, sa = self._closed_loop_outputs(n_steps, reward_out, flags_out, obs_out, act_out)
-        pp, ps = _rows(unc_out, torch.float32, n_steps)
-        assert pp is None or (rp is None and fp is None) or ps == os_, "unc_out shares the reward/flags row stride"
-        mp = None
+        mp, pitches = None, None
         if member_act_out is not None:
             K, m = getattr(self, "_ensemble_members", 0), member_act_out
             assert m.dtype == torch.float32 and m.dim() == 4 and m.stride(3) == 1 and m.stride(0) == K * m.stride(1)
             assert m.shape[0] >= n_steps and m.shape[1] == K and m.shape[2] == self.action_dim and m.shape[3] >= self.batch
-            assert ap is None or (m.stride(2), m.stride(1)) == (lda, sa), "member_act_out shares act_out's pitches"
-            mp, lda, sa = C.c_void_p(m.data_ptr()), m.stride(2), m.stride(1)
+            mp, pitches = C.c_void_p(m.data_ptr()), (m.stride(2), m.stride(1))
+        self._closed_loop(self._L.nig_rollout_mlp_ensemble, n_steps, reward_out, flags_out, obs_out, act_out,
+                          rows=[("unc_out", unc_out, torch.float32)], tail=(mp,), member_pitches=pitches)
+
+    def _closed_loop(self, fn, n_steps, reward_out, flags_out, obs_out, act_out, head=(), rows=(), tail=(), member_pitches=None):
+        """One closed-loop call of the C ABI: fn(handle, n_steps, *head, <the eight output arguments the closed loops share: reward
+        ptr, flags ptr, out_stride, obs ptr, obs_step_stride, act ptr, ld_act, act_step_stride>, <a pointer per entry of `rows`>,
+        *tail, stream), the four optional output tensors validated.  rows: (name, tensor or None, dtype) of the variant's extra
+        per-step rows [n_steps, >=B], which share the row stride of reward_out / flags_out.  member_pitches: (ld_act,
+        act_step_stride) of the ensemble's member_act_out, which shares act_out's pitches and states them where act_out is absent."""
+        rp, fp, os_, op, so, ap, lda, sa = self._closed_loop_outputs(n_steps, reward_out, flags_out, obs_out, act_out)
+        extra = [_rows(t, dtype, n_steps) for _, t, dtype in rows]
+        strides = {st for ptr, st in extra if ptr is not None} | ({os_} if (rp is not None or fp is not None) else set())
+        names = [name for name, _, _ in rows]
+        assert len(strides) <= 1, (f"{', '.join(names[:-1])} and {names[-1]} share" if len(names) > 1 else f"{names[0]} shares") \
+            + " the reward/flags row stride"
+        if member_pitches is not None:
+            assert ap is None or member_pitches == (lda, sa), "member_act_out shares act_out's pitches"
+            lda, sa = member_pitches
         with torch.cuda.device(self._dev_index):
-            _lib.check(self._L.nig_rollout_mlp_ensemble(self._h, int(n_steps), rp, fp, os_ or ps, op, so, ap, lda, sa, pp, mp,
-                                                        self._stream()))
+            _lib.check(fn(self._h, int(n_steps), *head, rp, fp, strides.pop() if strides else 0, op, so, ap, lda, sa,
+                          *[ptr for ptr, _ in extra], *tail, self._stream()))
 
     def _closed_loop_outputs(self, n_steps, reward_out, flags_out, obs_out, act_out):
         """The output arguments the closed-loop rollouts share, from the optional tensors, validated:
@@ -544,9 +548,7 @@ class BatchedIndustrialEnv:
         """n_steps closed-loop steps (action = installed policy(observation)) in ONE launch.
         obs_out: float32 contiguous [n_steps, B, S] (observation the policy acted on);
         act_out: float32 [n_steps, A, >=B]; reward_out / flags_out: [n_steps, >=B] or [B]."""
-        rp, fp, os_, op, so, ap, lda, sa = self._closed_loop_outputs(n_steps, reward_out, flags_out, obs_out, act_out)
-        with torch.cuda.device(self._dev_index):
-            _lib.check(self._L.nig_rollout_policy(self._h, int(n_steps), rp, fp, os_, op, so, ap, lda, sa, self._stream()))
+        self._closed_loop(self._L.nig_rollout_policy, n_steps, reward_out, flags_out, obs_out, act_out)
 
     # ------------------------------------------------------------------
     def set_disturbance(self, disturbance):
@@ -570,17 +572,13 @@ class BatchedIndustrialEnv:
     def rollout_policy_disturbed(self, n_steps: int, reward_out=None, flags_out=None, obs_out=None, act_out=None, seen_out=None):
         """rollout_policy() under the installed disturbance ("nig-disturb-v1"): obs_out holds the TRUE state, seen_out
         (float32 contiguous [n_steps, B, S]) the noisy observation the policy acted on, act_out the action the env received."""
-        rp, fp, os_, op, so, ap, lda, sa = self._closed_loop_outputs(n_steps, reward_out, flags_out, obs_out, act_out)
-        sp, ss = self._seen_rows(n_steps, seen_out)
-        with torch.cuda.device(self._dev_index):
-            _lib.check(self._L.nig_rollout_policy_disturbed(self._h, int(n_steps), rp, fp, os_, op, so, ap, lda, sa, sp, ss, self._stream()))
+        self._closed_loop(self._L.nig_rollout_policy_disturbed, n_steps, reward_out, flags_out, obs_out, act_out,
+                          tail=self._seen_rows(n_steps, seen_out))
 
     def rollout_mlp_disturbed(self, n_steps: int, reward_out=None, flags_out=None, obs_out=None, act_out=None, seen_out=None):
         """rollout_mlp() under the installed disturbance; outputs as rollout_policy_disturbed()."""
-        rp, fp, os_, op, so, ap, lda, sa = self._closed_loop_outputs(n_steps, reward_out, flags_out, obs_out, act_out)
-        sp, ss = self._seen_rows(n_steps, seen_out)
-        with torch.cuda.device(self._dev_index):
-            _lib.check(self._L.nig_rollout_mlp_disturbed(self._h, int(n_steps), rp, fp, os_, op, so, ap, lda, sa, sp, ss, self._stream()))
+        self._closed_loop(self._L.nig_rollout_mlp_disturbed, n_steps, reward_out, flags_out, obs_out, act_out,
+                          tail=self._seen_rows(n_steps, seen_out))
 
     def get_dataset(self, quality: str = "mixed", scale: int = 1, chunk: int = 100):
         """Batched env.get_dataset(quality): every lane is one episode of the reference's

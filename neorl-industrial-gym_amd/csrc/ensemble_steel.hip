@@ -1,4 +1,3 @@
-// SteelAnnealing's kernels of nig_rollout_mlp_ensemble (the fused ensemble actor) -- a translation unit of their own
-#define NIG_ENSEMBLE_TU
-#include "nig_launch.hpp"
+// SteelAnnealing's kernels of nig_rollout_mlp_ensemble (the fused ensemble actor) -- a translation unit of their own (launcher: nig_launch_families.hpp)
+#include "nig_launch_families.hpp"
 NIG_DEFINE_ENV_ENSEMBLE(SteelAnnealing)

@@ -1,5 +1,5 @@
 // nig_api.hip -- C ABI of libnig.so (include/nig.h) and the environment-independent kernels.
-// The per-environment kernels are instantiated in env_*.hip and reached through nig::EnvLaunch.
+// The per-environment kernels are instantiated in env_*.hip and the family units beside them, and reached through nig::EnvLaunch.
 #include <dlfcn.h>
 
 #include <atomic>
@@ -231,35 +231,22 @@ constexpr nig_env_spec spec_row()
             {Env::penalty(0), Env::penalty(1), Env::penalty(2)},
             {(int32_t)(Env::CRIT_MASK & 1u), (int32_t)((Env::CRIT_MASK >> 1) & 1u), (int32_t)((Env::CRIT_MASK >> 2) & 1u)}, Env::RET_F32};
 }
-static constexpr nig_env_spec SPECS[NIG_NUM_ENVS] = {      // (constexpr: every row is evaluated at compile time)
-    spec_row<ChemicalReactor>(), spec_row<PowerGrid>(), spec_row<RobotAssembly>(),
-    /* Advanced envs: 4 / 3 safety-metric conditions, no penalties through the base loop, deterministic */
-    spec_row<AdvancedChemicalReactor>(), spec_row<AdvancedPowerGrid>(),
-    /* build-specified plants (spec_plants.py): dims and constraint tables come from the generated data */
-    spec_row<SpecPlant<0>>(), spec_row<SpecPlant<1>>(), spec_row<SpecPlant<2>>(), spec_row<SpecPlant<3>>(),
-};
-static const char *NAMES[NIG_NUM_ENVS] = {"ChemicalReactor-v0", "PowerGrid-v0", "RobotAssembly-v0",
-                                          "AdvancedChemicalReactor-v0", "AdvancedPowerGrid-v0",
-                                          "HVACControl-v0", "WaterTreatment-v0", "SteelAnnealing-v0", "SupplyChain-v0"};
+// the tables indexed by env id, from NIG_ENV_LIST (which checks that position is id)
+#define NIG_ENV_SPEC(EnvType, key, id) spec_row<EnvType>(),
+#define NIG_ENV_NAME(EnvType, key, id) #EnvType "-v0",
+#define NIG_ENV_TABLE(EnvType, key, id) nig_launch_##key(),
+static constexpr nig_env_spec SPECS[NIG_NUM_ENVS] = {NIG_ENV_LIST(NIG_ENV_SPEC)};      // (constexpr: every row is evaluated at compile time)
+static const char *NAMES[NIG_NUM_ENVS] = {NIG_ENV_LIST(NIG_ENV_NAME)};
 
 // per-environment kernel launchers (env_*.hip)
-const EnvLaunch *nig_launch_cr();
-const EnvLaunch *nig_launch_pg();
-const EnvLaunch *nig_launch_ra();
-const EnvLaunch *nig_launch_acr();
-const EnvLaunch *nig_launch_apg();
-const EnvLaunch *nig_launch_hvac();
-const EnvLaunch *nig_launch_water();
-const EnvLaunch *nig_launch_steel();
-const EnvLaunch *nig_launch_supply();
-
 static const EnvLaunch *launch_of(int env)
 {
-    static const EnvLaunch *const T[NIG_NUM_ENVS] = {nig_launch_cr(), nig_launch_pg(), nig_launch_ra(), nig_launch_acr(),
-                                                     nig_launch_apg(), nig_launch_hvac(), nig_launch_water(),
-                                                     nig_launch_steel(), nig_launch_supply()};
+    static const EnvLaunch *const T[NIG_NUM_ENVS] = {NIG_ENV_LIST(NIG_ENV_TABLE)};
     return T[env];
 }
+#undef NIG_ENV_SPEC
+#undef NIG_ENV_NAME
+#undef NIG_ENV_TABLE
 
 // SafetyMetrics.total_constraints of this handle: built-in constraints still enabled (base.py:115,224-228)
 static int enabled_constraints(const nig_handle *h);
@@ -396,14 +383,13 @@ static int check_closed_loop(const nig_handle *h, const char *fn, const ClosedLo
     return NIG_OK;
 }
 
-// The checks of both contracts, then the fields PolicyArgs and MlpArgs share (everything else of q: zero).
+// The checks of both contracts, then the fields PolicyArgs and MlpArgs share (everything else of q stays as it is: zero).
 template <class Args>
 static int closed_loop_args(const nig_handle *h, const char *fn, int32_t n_steps, const ClosedLoopOut &o, Args &q)
 {
     NIG_TRY(check_out_stride(h, fn, n_steps, o.out_stride));
     NIG_TRY(check_closed_loop(h, fn, o));
     NIG_TRY(check_counter(h, fn, n_steps));
-    memset(&q, 0, sizeof q);
     q.s = base_step_args(h);
     q.s.reward = o.reward; q.s.flags = o.flags; q.s.t_off = h->t;
     q.n_steps = n_steps; q.out_stride = (uint32_t)o.out_stride;
@@ -436,6 +422,45 @@ static int disturb_args(const nig_handle *h, const char *fn, float *seen_out, in
     d.clip_lo = h->dist.clip_lo; d.clip_hi = h->dist.clip_hi; d.hold = h->dist.hold;
     d.seen_out = seen_out; d.seen_step_stride = (uint64_t)seen_step_stride;
     return NIG_OK;
+}
+
+// ---- the closed loop: what nig_rollout_policy / _mlp / _mlp_safe / _mlp_search / _mlp_ensemble / _policy_disturbed / _mlp_disturbed
+// do after their own prerequisites.  A variant's argument block holds the shared fields as PolicyArgs or MlpArgs, which also says
+// what grid its kernels take: a thread per env for the policy kernels, 32 envs per wave (128 per block) for the MFMA kernels.
+static PolicyArgs &shared_args(PolicyArgs &q) { return q; }
+static PolicyArgs &shared_args(PolicyDistArgs &q) { return q.p; }
+static MlpArgs &shared_args(MlpArgs &q) { return q; }
+static MlpArgs &shared_args(MlpSearchArgs &q) { return q.sh.m; }
+template <class Args> static MlpArgs &shared_args(Args &q) { return q.m; }      // MlpShieldArgs, MlpEnsArgs, MlpDistArgs
+static unsigned closed_loop_grid(const nig_handle *h, const PolicyArgs &) { return grid_for(h->B); }
+static unsigned closed_loop_grid(const nig_handle *h, const MlpArgs &) { return (unsigned)((h->B + BLOCK / 2 - 1) / (BLOCK / 2)); }
+
+// The zeroed block, the argument checks and the shared fields; `variant(q)` fills the variant's own fields and returns the launcher
+// (an EnvLaunch entry, or a callable of its shape); then the launch, its error and the launch counter.  No synchronisation.
+template <class Args, class Variant>
+static int closed_loop(nig_handle *h, const char *fn, int32_t n_steps, const ClosedLoopOut &o, void *stream, Variant &&variant)
+{
+    Args q;
+    memset(&q, 0, sizeof q);
+    auto &shared = shared_args(q);
+    NIG_TRY(closed_loop_args(h, fn, n_steps, o, shared));
+    const auto launch = variant(q);
+    launch(q, closed_loop_grid(h, shared), (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    h->t += (uint32_t)n_steps;
+    return NIG_OK;
+}
+
+static void policy_fields(const nig_handle *h, PolicyArgs &q)
+{
+    q.pol = h->pol_dev;
+    q.pid = (h->pol_host.kind == NIG_POLICY_PID) ? h->pid_mem : nullptr;
+    q.pol_kind = h->pol_host.kind;
+}
+static void shield_fields(const nig_handle *h, float *prob_out, MlpShieldArgs &q)
+{
+    q.m.wstream = h->mlp_stream;
+    q.cstream = h->mlp_cstream; q.prob_out = prob_out; q.threshold = h->mlp_threshold;
 }
 
 extern "C" {
@@ -940,16 +965,29 @@ int nig_rollout_policy(nig_handle *h, int32_t n_steps, float *reward_out, uint32
 {
     if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_policy: bad argument");
     if (!h->has_policy) return fail(NIG_ERR_INVALID, "nig_rollout_policy: no policy installed (nig_set_policy)");
-    PolicyArgs q;
-    NIG_TRY(closed_loop_args(h, "nig_rollout_policy", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, q));
-    q.pol = h->pol_dev;
-    q.pid = (h->pol_host.kind == NIG_POLICY_PID) ? h->pid_mem : nullptr;
-    q.pol_kind = h->pol_host.kind;
-    hipStream_t st = (hipStream_t)stream;
-    launch_of(h->env)->policy(q, grid_for(h->B), st);
-    HIP_TRY(hipGetLastError());
-    h->t += (uint32_t)n_steps;
-    return ring_check(h, st, "nig_rollout_policy");
+    NIG_TRY(closed_loop<PolicyArgs>(h, "nig_rollout_policy", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](PolicyArgs &q) {
+        policy_fields(h, q);
+        return launch_of(h->env)->policy;
+    }));
+    return ring_check(h, (hipStream_t)stream, "nig_rollout_policy");      // (the one closed loop with cooperating-wave forms)
+}
+
+// nig_set_mlp_policy / _safety / _ensemble: `count` operand-stream images of `floats` floats, back to back, network k (in_dim -> 256 ->
+// 256 -> rows) from the k-th entry of the six arrays; refuses another hidden width and an env without the MFMA actor.  *host: calloc'd.
+static int build_network_images(const nig_handle *h, const char *fn, int32_t hidden, int in_dim, int rows, size_t floats, int count,
+                                const float *const *W1, const float *const *b1, const float *const *W2, const float *const *b2,
+                                const float *const *W3, const float *const *b3, float **host)
+{
+    if (hidden != MLP_H) return refuse(fn, "hidden must be 256 (agents/networks.py default)", NIG_ERR_UNSUPPORTED);
+    if (!launch_of(h->env)->mlp) return refuse(fn, "env shape not supported (even state dim, at most 16 actions)", NIG_ERR_UNSUPPORTED);
+    *host = (float *)calloc((size_t)count * floats, sizeof(float));
+    if (!*host) return refuse(fn, "out of host memory");
+    for (int k = 0; k < count; ++k)
+        if (!put_network(in_dim, rows, W1[k], b1[k], W2[k], b2[k], W3[k], b3[k], *host + (size_t)k * floats, floats)) {
+            free(*host);
+            return refuse(fn, "the operand stream does not fit its image, or an internal record count mismatch");
+        }
+    return NIG_OK;
 }
 
 // A built host image (malloc'd; freed here) -> the device stream *dev, allocated on first use; copied on `stream` and waited for.
@@ -963,18 +1001,13 @@ static int upload_stream(const char *fn, float **dev, float *host, size_t floats
     return e == hipSuccess ? NIG_OK : refuse(fn, hipGetErrorString(e), NIG_ERR_HIP);
 }
 
-static unsigned mlp_grid(const nig_handle *h) { return (unsigned)((h->B + BLOCK / 2 - 1) / (BLOCK / 2)); }   // 32 envs per wave, 128 per block
-
 int nig_set_mlp_policy(nig_handle *h, int32_t hidden, const float *W1, const float *b1, const float *W2, const float *b2,
                        const float *W3, const float *b3, void *stream)
 {
     if (!h || !W1 || !b1 || !W2 || !b2 || !W3 || !b3) return fail(NIG_ERR_INVALID, "nig_set_mlp_policy: NULL argument");
-    if (hidden != MLP_H) return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_policy: hidden must be 256 (agents/networks.py default)");
     const int S = SPECS[h->env].state_dim, A = SPECS[h->env].action_dim;
-    if (S % 2 != 0 || A > 16) return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_policy: env shape not supported (even state dim, at most 16 actions)");
-    float *host = (float *)calloc((size_t)MLP_STREAM_FLOATS, sizeof(float));
-    if (!host) return fail(NIG_ERR_INVALID, "nig_set_mlp_policy: out of host memory");
-    if (!put_network(S, A, W1, b1, W2, b2, W3, b3, host, MLP_STREAM_FLOATS)) { free(host); return fail(NIG_ERR_INVALID, "nig_set_mlp_policy: the operand stream does not fit its image, or an internal record count mismatch"); }
+    float *host = nullptr;
+    NIG_TRY(build_network_images(h, "nig_set_mlp_policy", hidden, S, A, MLP_STREAM_FLOATS, 1, &W1, &b1, &W2, &b2, &W3, &b3, &host));
     return upload_stream("nig_set_mlp_policy", &h->mlp_stream, host, MLP_STREAM_FLOATS, stream);
 }
 
@@ -984,26 +1017,19 @@ int nig_rollout_mlp(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t 
 {
     if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp: bad argument");
     if (!h->mlp_stream || !launch_of(h->env)->mlp) return fail(NIG_ERR_INVALID, "nig_rollout_mlp: no actor installed (nig_set_mlp_policy)");
-    MlpArgs q;
-    NIG_TRY(closed_loop_args(h, "nig_rollout_mlp", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, q));
-    q.wstream = h->mlp_stream;
-    launch_of(h->env)->mlp(q, mlp_grid(h), (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    h->t += (uint32_t)n_steps;
-    return NIG_OK;
+    return closed_loop<MlpArgs>(h, "nig_rollout_mlp", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpArgs &q) {
+        q.wstream = h->mlp_stream;
+        return launch_of(h->env)->mlp;
+    });
 }
 
 int nig_set_mlp_safety(nig_handle *h, int32_t hidden, const float *C1, const float *c1, const float *C2, const float *c2,
                        const float *C3, const float *c3, float threshold, void *stream)
 {
     if (!h || !C1 || !c1 || !C2 || !c2 || !C3 || !c3) return fail(NIG_ERR_INVALID, "nig_set_mlp_safety: NULL argument");
-    if (hidden != MLP_H) return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_safety: hidden must be 256 (agents/networks.py default)");
     const int S = SPECS[h->env].state_dim, A = SPECS[h->env].action_dim;
-    if (S % 2 != 0 || A > 16 || !launch_of(h->env)->mlp_shield)
-        return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_safety: env shape not supported (even state dim, at most 16 actions)");
-    float *host = (float *)calloc((size_t)MLP_CSTREAM_FLOATS, sizeof(float));
-    if (!host) return fail(NIG_ERR_INVALID, "nig_set_mlp_safety: out of host memory");
-    if (!put_network(S + A, 1, C1, c1, C2, c2, C3, c3, host, MLP_CSTREAM_FLOATS)) { free(host); return fail(NIG_ERR_INVALID, "nig_set_mlp_safety: the operand stream does not fit its image, or an internal record count mismatch"); }
+    float *host = nullptr;
+    NIG_TRY(build_network_images(h, "nig_set_mlp_safety", hidden, S + A, 1, MLP_CSTREAM_FLOATS, 1, &C1, &c1, &C2, &c2, &C3, &c3, &host));
     NIG_TRY(upload_stream("nig_set_mlp_safety", &h->mlp_cstream, host, MLP_CSTREAM_FLOATS, stream));
     h->mlp_threshold = threshold;
     return NIG_OK;
@@ -1017,15 +1043,10 @@ int nig_rollout_mlp_safe(nig_handle *h, int32_t n_steps, float *reward_out, uint
     if (!launch_of(h->env)->mlp_shield) return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_mlp_safe: env shape has no MFMA actor");
     if (!h->mlp_stream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_safe: no actor installed (nig_set_mlp_policy)");
     if (!h->mlp_cstream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_safe: no safety critic installed (nig_set_mlp_safety)");
-    MlpShieldArgs q;
-    memset(&q, 0, sizeof q);
-    NIG_TRY(closed_loop_args(h, "nig_rollout_mlp_safe", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, q.m));
-    q.m.wstream = h->mlp_stream;
-    q.cstream = h->mlp_cstream; q.prob_out = prob_out; q.threshold = h->mlp_threshold;
-    launch_of(h->env)->mlp_shield(q, mlp_grid(h), (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    h->t += (uint32_t)n_steps;
-    return NIG_OK;
+    return closed_loop<MlpShieldArgs>(h, "nig_rollout_mlp_safe", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpShieldArgs &q) {
+        shield_fields(h, prob_out, q);
+        return launch_of(h->env)->mlp_shield;
+    });
 }
 
 int nig_rollout_mlp_search(nig_handle *h, int32_t n_steps, int32_t n_candidates, float *reward_out, uint32_t *flags_out, int64_t out_stride,
@@ -1037,16 +1058,11 @@ int nig_rollout_mlp_search(nig_handle *h, int32_t n_steps, int32_t n_candidates,
     if (n_candidates < 1 || n_candidates > NIG_MAX_CANDIDATES) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_search: n_candidates outside 1 .. NIG_MAX_CANDIDATES");
     if (!h->mlp_stream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_search: no actor installed (nig_set_mlp_policy)");
     if (!h->mlp_cstream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_search: no safety critic installed (nig_set_mlp_safety)");
-    MlpSearchArgs q;
-    memset(&q, 0, sizeof q);
-    NIG_TRY(closed_loop_args(h, "nig_rollout_mlp_search", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, q.sh.m));
-    q.sh.m.wstream = h->mlp_stream;
-    q.sh.cstream = h->mlp_cstream; q.sh.prob_out = prob_out; q.sh.threshold = h->mlp_threshold;
-    q.n_candidates = n_candidates; q.risk_out = risk_out; q.choice_out = choice_out;
-    launch_of(h->env)->mlp_search(q, mlp_grid(h), (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    h->t += (uint32_t)n_steps;
-    return NIG_OK;
+    return closed_loop<MlpSearchArgs>(h, "nig_rollout_mlp_search", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpSearchArgs &q) {
+        shield_fields(h, prob_out, q.sh);
+        q.n_candidates = n_candidates; q.risk_out = risk_out; q.choice_out = choice_out;
+        return launch_of(h->env)->mlp_search;
+    });
 }
 
 int nig_set_mlp_ensemble(nig_handle *h, int32_t n_members, int32_t hidden, const float *const *W1, const float *const *b1,
@@ -1069,17 +1085,9 @@ int nig_set_mlp_ensemble(nig_handle *h, int32_t n_members, int32_t hidden, const
         if (!std::isfinite(weight_sum)) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: non-finite weight_sum");
         if (weight_sum == 0.0) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: weight_sum is zero (np.average raises)");
     }
-    if (hidden != MLP_H) return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_ensemble: hidden must be 256 (agents/networks.py default)");
     const int S = SPECS[h->env].state_dim, A = SPECS[h->env].action_dim;
-    if (S % 2 != 0 || A > 16 || !launch_of(h->env)->mlp_ensemble)
-        return fail(NIG_ERR_UNSUPPORTED, "nig_set_mlp_ensemble: env shape not supported (even state dim, at most 16 actions)");
-    float *host = (float *)calloc((size_t)n_members * MLP_STREAM_FLOATS, sizeof(float));
-    if (!host) return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: out of host memory");
-    for (int k = 0; k < n_members; ++k)
-        if (!put_network(S, A, W1[k], b1[k], W2[k], b2[k], W3[k], b3[k], host + (size_t)k * MLP_STREAM_FLOATS, MLP_STREAM_FLOATS)) {
-            free(host);
-            return fail(NIG_ERR_INVALID, "nig_set_mlp_ensemble: the operand stream does not fit its image, or an internal record count mismatch");
-        }
+    float *host = nullptr;
+    NIG_TRY(build_network_images(h, "nig_set_mlp_ensemble", hidden, S, A, MLP_STREAM_FLOATS, n_members, W1, b1, W2, b2, W3, b3, &host));
     h->ens_members = 0;                                     // no ensemble while the streams are being replaced
     if (h->ens_cap < n_members) {                           // too small: upload_stream allocates the new one
         if (h->ens_stream) (void)hipFree(h->ens_stream);
@@ -1102,19 +1110,18 @@ int nig_rollout_mlp_ensemble(nig_handle *h, int32_t n_steps, float *reward_out, 
     if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_ensemble: bad argument (handle, n_steps)");
     if (!launch_of(h->env)->mlp_ensemble) return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_mlp_ensemble: env shape has no MFMA actor");
     if (h->ens_members < 1 || !h->ens_stream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_ensemble: no ensemble installed (nig_set_mlp_ensemble)");
-    MlpEnsArgs q;
-    memset(&q, 0, sizeof q);
     // member_act_out shares act_out's pitches: the same checks apply to it when act_out is absent
-    NIG_TRY(closed_loop_args(h, "nig_rollout_mlp_ensemble", n_steps,
-                             {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out ? act_out : member_act_out, ld_act, act_step_stride}, q.m));
-    q.m.act_out = act_out;
-    q.m.wstream = h->ens_stream;
-    q.n_members = h->ens_members; q.w = h->ens_w; q.wsum = h->ens_wsum; q.kf = (float)h->ens_members; q.threshold = h->ens_threshold;
-    q.unc_out = unc_out; q.member_out = member_act_out;
-    launch_of(h->env)->mlp_ensemble(h->ens_method == NIG_ENSEMBLE_AVERAGE ? ENS_AVERAGE : ENS_VOTING, q, mlp_grid(h), (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    h->t += (uint32_t)n_steps;
-    return NIG_OK;
+    return closed_loop<MlpEnsArgs>(h, "nig_rollout_mlp_ensemble", n_steps,
+                                   {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out ? act_out : member_act_out, ld_act, act_step_stride},
+                                   stream, [&](MlpEnsArgs &q) {
+        q.m.act_out = act_out;
+        q.m.wstream = h->ens_stream;
+        q.n_members = h->ens_members; q.w = h->ens_w; q.wsum = h->ens_wsum; q.kf = (float)h->ens_members; q.threshold = h->ens_threshold;
+        q.unc_out = unc_out; q.member_out = member_act_out;
+        return [h](const MlpEnsArgs &e, unsigned grid, hipStream_t st) {
+            launch_of(h->env)->mlp_ensemble(h->ens_method == NIG_ENSEMBLE_AVERAGE ? ENS_AVERAGE : ENS_VOTING, e, grid, st);
+        };
+    });
 }
 
 // ---- sensor / actuator noise in the closed loop ("nig-disturb-v1") --------------------------
@@ -1134,16 +1141,13 @@ int nig_rollout_policy_disturbed(nig_handle *h, int32_t n_steps, float *reward_o
 {
     if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_policy_disturbed: bad argument");
     if (!h->has_policy) return fail(NIG_ERR_INVALID, "nig_rollout_policy_disturbed: no policy installed (nig_set_policy)");
-    PolicyDistArgs q;
-    NIG_TRY(disturb_args(h, "nig_rollout_policy_disturbed", seen_out, seen_step_stride, q.d));
-    NIG_TRY(closed_loop_args(h, "nig_rollout_policy_disturbed", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, q.p));
-    q.p.pol = h->pol_dev;
-    q.p.pid = (h->pol_host.kind == NIG_POLICY_PID) ? h->pid_mem : nullptr;
-    q.p.pol_kind = h->pol_host.kind;
-    launch_of(h->env)->policy_disturbed(q, grid_for(h->B), (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    h->t += (uint32_t)n_steps;
-    return NIG_OK;
+    DisturbArgs d;
+    NIG_TRY(disturb_args(h, "nig_rollout_policy_disturbed", seen_out, seen_step_stride, d));
+    return closed_loop<PolicyDistArgs>(h, "nig_rollout_policy_disturbed", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](PolicyDistArgs &q) {
+        q.d = d;
+        policy_fields(h, q.p);
+        return launch_of(h->env)->policy_disturbed;
+    });
 }
 
 int nig_rollout_mlp_disturbed(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
@@ -1153,14 +1157,13 @@ int nig_rollout_mlp_disturbed(nig_handle *h, int32_t n_steps, float *reward_out,
     if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_disturbed: bad argument");
     if (!launch_of(h->env)->mlp_disturbed) return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_mlp_disturbed: env shape has no MFMA actor");
     if (!h->mlp_stream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_disturbed: no actor installed (nig_set_mlp_policy)");
-    MlpDistArgs q;
-    NIG_TRY(disturb_args(h, "nig_rollout_mlp_disturbed", seen_out, seen_step_stride, q.d));
-    NIG_TRY(closed_loop_args(h, "nig_rollout_mlp_disturbed", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, q.m));
-    q.m.wstream = h->mlp_stream;
-    launch_of(h->env)->mlp_disturbed(q, mlp_grid(h), (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    h->t += (uint32_t)n_steps;
-    return NIG_OK;
+    DisturbArgs d;
+    NIG_TRY(disturb_args(h, "nig_rollout_mlp_disturbed", seen_out, seen_step_stride, d));
+    return closed_loop<MlpDistArgs>(h, "nig_rollout_mlp_disturbed", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpDistArgs &q) {
+        q.d = d;
+        q.m.wstream = h->mlp_stream;
+        return launch_of(h->env)->mlp_disturbed;
+    });
 }
 
 // ---- host-buffer entry points (small batches) -------------------------------------------------

@@ -1,29 +1,55 @@
-// nig_launch.hpp -- the host side of libnig.so's kernels: the per-environment launch table.  Each env_*.hip instantiates
-// its kernels through NIG_DEFINE_ENV_LAUNCH; nig_api.hip reaches them through these function pointers only.  Which kernel
-// form a rollout launch takes is decided in nig_launch_plan.hpp; the functions here run its plans.
+// nig_launch.hpp -- the host side of libnig.so's kernels: the list of environments and the per-environment launch table.  An
+// env_<key>.hip instantiates the env's kernels by defining its table (NIG_DEFINE_ENV_LAUNCH); nig_api.hip reaches them through the
+// table's function pointers only.  The launchers of the kernel families with translation units of their own (sampled_, ensemble_,
+// disturbed_, search_<key>.hip) are DECLARED here and defined in nig_launch_families.hpp, which those units alone include.  Which
+// kernel form a rollout launch takes is decided in nig_launch_plan.hpp; the functions here run its plans.
 #pragma once
 #include "nig_kernels.hpp"
 #include "nig_launch_plan.hpp"
 
+// The environments, once, in id order: (type in nig_envs.hpp, key of its translation units and of nig_launch_<key>(), id in nig.h).
+// From it: nig_api.hip's spec rows, names ("<type>-v0") and launch tables; the declarations below; tests/launch_plan_probe.hip's dispatch.
+#define NIG_ENV_LIST(X)                                                                                         \
+    X(ChemicalReactor, cr, NIG_ENV_CHEMICAL_REACTOR) X(PowerGrid, pg, NIG_ENV_POWER_GRID)                       \
+    X(RobotAssembly, ra, NIG_ENV_ROBOT_ASSEMBLY) X(AdvancedChemicalReactor, acr, NIG_ENV_ADV_CHEMICAL_REACTOR)  \
+    X(AdvancedPowerGrid, apg, NIG_ENV_ADV_POWER_GRID) X(HVACControl, hvac, NIG_ENV_HVAC_CONTROL)                \
+    X(WaterTreatment, water, NIG_ENV_WATER_TREATMENT) X(SteelAnnealing, steel, NIG_ENV_STEEL_ANNEALING)         \
+    X(SupplyChain, supply, NIG_ENV_SUPPLY_CHAIN)
+
 namespace nig {
 
+// an entry's position in the list is its NIG_ENV_* id and its struct's ID: the tables built from the list are indexed by env id
+#define NIG_ENV_POSITION(EnvType, key, id) list_position_##key,
+enum { NIG_ENV_LIST(NIG_ENV_POSITION) list_length };
+#undef NIG_ENV_POSITION
+#define NIG_ENV_CHECK(EnvType, key, id) \
+    static_assert(list_position_##key == id && EnvType::ID == id, "NIG_ENV_LIST: " #EnvType " is not at the position of " #id);
+NIG_ENV_LIST(NIG_ENV_CHECK)
+#undef NIG_ENV_CHECK
+static_assert(list_length == NIG_NUM_ENVS);
+
 struct EnvLaunch {
+    // the env's own translation unit, env_<key>.hip (defined below)
     void (*step)(const StepArgs &, bool parity, unsigned grid, hipStream_t);
     void (*step64)(const StepArgs &, bool parity, unsigned grid, hipStream_t);   // float64 action rows; nullptr: the env takes float32
-    void (*rollout)(int out_mode, const RolloutArgs &, uint32_t t0, unsigned grid, hipStream_t);
-    void (*policy)(const PolicyArgs &, unsigned grid, hipStream_t);
-    void (*mlp)(const MlpArgs &, unsigned grid, hipStream_t);      // nullptr: env shape not supported by the MFMA actor
-    void (*mlp_shield)(const MlpShieldArgs &, unsigned grid, hipStream_t);   // the same with the safety-critic shield
     void (*reset)(const ResetArgs &, bool parity, unsigned grid, hipStream_t);
     void (*fill)(float *act, int64_t ld_act, int64_t B, uint64_t env0, uint32_t seed_lo, uint32_t seed_hi, uint32_t t,
                  unsigned grid, hipStream_t);
+    void (*rollout)(int out_mode, const RolloutArgs &, uint32_t t0, unsigned grid, hipStream_t);
     // does `rollout` read a ROW-MAJOR action ring ([B][A] slots, RolloutArgs.s.ld_act == 0) natively for this request?
     bool (*rows_native)(int out_mode, const RolloutArgs &);
-    void (*rollout_sampled)(int out_mode, const RolloutArgs &, uint32_t t0, unsigned grid, hipStream_t);   // nig_rollout_sampled
-    void (*mlp_ensemble)(int ens, const MlpEnsArgs &, unsigned grid, hipStream_t);   // nig_rollout_mlp_ensemble; nullptr as `mlp`
-    void (*policy_disturbed)(const PolicyDistArgs &, unsigned grid, hipStream_t);    // nig_rollout_policy_disturbed
-    void (*mlp_disturbed)(const MlpDistArgs &, unsigned grid, hipStream_t);          // nig_rollout_mlp_disturbed; nullptr as `mlp`
-    void (*mlp_search)(const MlpSearchArgs &, unsigned grid, hipStream_t);           // nig_rollout_mlp_search; nullptr as `mlp`
+    void (*policy)(const PolicyArgs &, unsigned grid, hipStream_t);
+    void (*mlp)(const MlpArgs &, unsigned grid, hipStream_t);                // nullptr: the env has no MFMA actor (has_mlp_actor)
+    void (*mlp_shield)(const MlpShieldArgs &, unsigned grid, hipStream_t);   // the same with the safety-critic shield; nullptr as `mlp`
+    // sampled_<key>.hip (nig_launch_families.hpp): nig_rollout_sampled
+    void (*rollout_sampled)(int out_mode, const RolloutArgs &, uint32_t t0, unsigned grid, hipStream_t);
+    // ensemble_<key>.hip: nig_rollout_mlp_ensemble; nullptr as `mlp`
+    void (*mlp_ensemble)(int ens, const MlpEnsArgs &, unsigned grid, hipStream_t);
+    // disturbed_<key>.hip: nig_rollout_policy_disturbed, nig_rollout_mlp_disturbed (nullptr as `mlp`)
+    void (*policy_disturbed)(const PolicyDistArgs &, unsigned grid, hipStream_t);
+    void (*mlp_disturbed)(const MlpDistArgs &, unsigned grid, hipStream_t);
+    // search_<key>.hip: nig_rollout_mlp_search; nullptr as `mlp`
+    void (*mlp_search)(const MlpSearchArgs &, unsigned grid, hipStream_t);
 };
 
 template <class Env>
@@ -33,18 +59,22 @@ static void launch_reset(const ResetArgs &a, bool parity, unsigned grid, hipStre
     else hipLaunchKernelGGL((reset_kernel<Env, false>), dim3(grid), dim3(BLOCK), 0, st, a);
 }
 
-// the MFMA actor exists for even state dims and at most 16 actions (nig_set_mlp_policy refuses the others)
-template <class Env>
-static void launch_mlp(const MlpArgs &q, unsigned grid, hipStream_t st)
+// The MFMA actor's kernels that differ in their argument type alone, by that type, and their one launcher: the kernel is compiled
+// only for an env that has the actor.  (The ensemble's launcher chooses between two kernels at run time: nig_launch_families.hpp.)
+template <class Env> constexpr auto mlp_kernel(const MlpArgs &) { return rollout_mlp_kernel<Env>; }
+template <class Env> constexpr auto mlp_kernel(const MlpShieldArgs &) { return rollout_mlp_shield_kernel<Env>; }
+template <class Env> constexpr auto mlp_kernel(const MlpDistArgs &) { return rollout_mlp_disturbed_kernel<Env>; }
+template <class Env> constexpr auto mlp_kernel(const MlpSearchArgs &) { return rollout_mlp_search_kernel<Env>; }
+
+template <class Env, class Args>
+static void launch_mlp(const Args &q, unsigned grid, hipStream_t st)
 {
-    if constexpr (Env::S % 2 == 0 && Env::A <= 16) hipLaunchKernelGGL((rollout_mlp_kernel<Env>), dim3(grid), dim3(BLOCK), 0, st, q);
+    if constexpr (has_mlp_actor<Env>) hipLaunchKernelGGL(mlp_kernel<Env>(q), dim3(grid), dim3(BLOCK), 0, st, q);
 }
 
-template <class Env>
-static void launch_mlp_shield(const MlpShieldArgs &q, unsigned grid, hipStream_t st)
-{
-    if constexpr (Env::S % 2 == 0 && Env::A <= 16) hipLaunchKernelGGL((rollout_mlp_shield_kernel<Env>), dim3(grid), dim3(BLOCK), 0, st, q);
-}
+// a table slot of the MFMA actor: null for an env without it, which is how nig_api.hip asks "is this shape supported"
+template <class Env, class F>
+constexpr F *mlp_slot(F *f) { return has_mlp_actor<Env> ? f : nullptr; }
 
 template <class Env>
 static void launch_step(const StepArgs &a, bool parity, unsigned grid, hipStream_t st)
@@ -192,74 +222,16 @@ static void launch_rollout_env(int out_mode, const RolloutArgs &q, uint32_t t0, 
     launch_rollout_paired<Env, false>(out_mode, q, t0, grid, st);
 }
 
-// nig_rollout_sampled: the same selection on the twin kernels.  Declared everywhere, DEFINED (and with it every sampled kernel
-// instantiated) only in the env's sampled_*.hip translation unit (NIG_DEFINE_ENV_SAMPLED): the env_*.hip units hold exactly the
-// instantiations they held before the twins existed -- their code objects do not move by an instruction (profiles/isa_diff.py) --
-// and the twins compile beside them in parallel.
-template <class Env>
-void launch_rollout_sampled_env(int out_mode, const RolloutArgs &q, uint32_t t0, unsigned grid, hipStream_t st)
-#ifdef NIG_SAMPLED_TU
-{
-    launch_rollout_paired<Env, true>(out_mode, q, t0, grid, st);
-}
-#else
-;
-#endif
-
-// nig_rollout_mlp_ensemble: as the sampled twins, declared everywhere and DEFINED (its kernels instantiated) only in the env's
-// ensemble_*.hip translation unit (NIG_DEFINE_ENV_ENSEMBLE), so the env_*.hip units keep the instantiations they had.
-template <class Env>
-void launch_mlp_ensemble_env(int ens, const MlpEnsArgs &q, unsigned grid, hipStream_t st)
-#ifdef NIG_ENSEMBLE_TU
-{
-    if constexpr (Env::S % 2 == 0 && Env::A <= 16) {
-        if (ens == ENS_AVERAGE) hipLaunchKernelGGL((rollout_mlp_ensemble_kernel<Env, ENS_AVERAGE>), dim3(grid), dim3(BLOCK), 0, st, q);
-        else hipLaunchKernelGGL((rollout_mlp_ensemble_kernel<Env, ENS_VOTING>), dim3(grid), dim3(BLOCK), 0, st, q);
-    }
-}
-#else
-;
-#endif
-
-// nig_rollout_policy_disturbed / nig_rollout_mlp_disturbed: as the twins above, declared everywhere and DEFINED (their kernels
-// instantiated) only in the env's disturbed_*.hip translation unit (NIG_DEFINE_ENV_DISTURBED).  The closed loop under a disturbance
-// has the one-wave form only (plan_policy_disturbed): the three-wave and paired PowerGrid closed loops have no disturbed twin.
-template <class Env>
-void launch_policy_disturbed_env(const PolicyDistArgs &q, unsigned /*grid*/, hipStream_t st)
-#ifdef NIG_DISTURBED_TU
-{
-    const LaunchPlan plan = plan_policy_disturbed(q.p.s.B);
-    PolicyDistArgs r = q;
-    for (const Segment &s : plan) {
-        r.p.block0 = s.block0;
-        hipLaunchKernelGGL((rollout_policy_disturbed_kernel<Env>), dim3(s.grid), dim3(BLOCK), 0, st, r);
-    }
-}
-#else
-;
-#endif
-
-template <class Env>
-void launch_mlp_disturbed_env(const MlpDistArgs &q, unsigned grid, hipStream_t st)
-#ifdef NIG_DISTURBED_TU
-{
-    if constexpr (Env::S % 2 == 0 && Env::A <= 16) hipLaunchKernelGGL((rollout_mlp_disturbed_kernel<Env>), dim3(grid), dim3(BLOCK), 0, st, q);
-}
-#else
-;
-#endif
-
-// nig_rollout_mlp_search: as the twins above, declared everywhere and DEFINED (its kernel instantiated) only in the env's
-// search_*.hip translation unit (NIG_DEFINE_ENV_SEARCH).
-template <class Env>
-void launch_mlp_search_env(const MlpSearchArgs &q, unsigned grid, hipStream_t st)
-#ifdef NIG_SEARCH_TU
-{
-    if constexpr (Env::S % 2 == 0 && Env::A <= 16) hipLaunchKernelGGL((rollout_mlp_search_kernel<Env>), dim3(grid), dim3(BLOCK), 0, st, q);
-}
-#else
-;
-#endif
+// The launchers of the kernel families in translation units of their own: declared here, defined in nig_launch_families.hpp.  A
+// unit that includes this header alone -- env_*.hip, nig_api.hip, nig_mixed.hip -- can name them (the table below does) but cannot
+// instantiate them, so the env_*.hip units hold exactly the instantiations they held before a family existed: their code objects do
+// not move by an instruction (profiles/isa_diff.py), each kernel symbol of the library lives in one code object, and the families
+// compile beside them in parallel.
+template <class Env> void launch_rollout_sampled_env(int out_mode, const RolloutArgs &q, uint32_t t0, unsigned grid, hipStream_t st);
+template <class Env> void launch_mlp_ensemble_env(int ens, const MlpEnsArgs &q, unsigned grid, hipStream_t st);
+template <class Env> void launch_policy_disturbed_env(const PolicyDistArgs &q, unsigned grid, hipStream_t st);
+template <class Env> void launch_mlp_disturbed_env(const MlpDistArgs &q, unsigned grid, hipStream_t st);
+template <class Env> void launch_mlp_search_env(const MlpSearchArgs &q, unsigned grid, hipStream_t st);
 
 template <class Env>
 static void launch_policy(const PolicyArgs &q, unsigned /*grid*/, hipStream_t st)
@@ -286,17 +258,28 @@ static void launch_fill(float *act, int64_t ld_act, int64_t B, uint64_t env0, ui
     hipLaunchKernelGGL((fill_actions_kernel<Env>), dim3(grid), dim3(BLOCK), 0, st, act, ld_act, B, env0, seed_lo, seed_hi, t);
 }
 
+// Filled by name: a member added to EnvLaunch moves no other.
 template <class Env>
 static const EnvLaunch *env_launch_table()
 {
-    static const EnvLaunch T = {launch_step<Env>, Env::HAS_ACT64 ? launch_step64<Env> : nullptr, launch_rollout_env<Env>, launch_policy<Env>,
-                                (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp<Env> : nullptr,
-                                (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp_shield<Env> : nullptr,
-                                launch_reset<Env>, launch_fill<Env>, rollout_rows_native<Env>, launch_rollout_sampled_env<Env>,
-                                (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp_ensemble_env<Env> : nullptr,
-                                launch_policy_disturbed_env<Env>,
-                                (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp_disturbed_env<Env> : nullptr,
-                                (Env::S % 2 == 0 && Env::A <= 16) ? launch_mlp_search_env<Env> : nullptr};
+    static const EnvLaunch T = [] {
+        EnvLaunch t = {};
+        t.step = launch_step<Env>;
+        t.step64 = Env::HAS_ACT64 ? launch_step64<Env> : nullptr;
+        t.reset = launch_reset<Env>;
+        t.fill = launch_fill<Env>;
+        t.rollout = launch_rollout_env<Env>;
+        t.rows_native = rollout_rows_native<Env>;
+        t.policy = launch_policy<Env>;
+        t.mlp = mlp_slot<Env>(launch_mlp<Env, MlpArgs>);
+        t.mlp_shield = mlp_slot<Env>(launch_mlp<Env, MlpShieldArgs>);
+        t.rollout_sampled = launch_rollout_sampled_env<Env>;
+        t.mlp_ensemble = mlp_slot<Env>(launch_mlp_ensemble_env<Env>);
+        t.policy_disturbed = launch_policy_disturbed_env<Env>;
+        t.mlp_disturbed = mlp_slot<Env>(launch_mlp_disturbed_env<Env>);
+        t.mlp_search = mlp_slot<Env>(launch_mlp_search_env<Env>);
+        return t;
+    }();
     return &T;
 }
 
@@ -315,18 +298,9 @@ static_assert(sizeof(MixedArgs) <= 4000, "kernel argument segment is 4 KiB");
 // nig_mixed.hip
 void nig_launch_mixed_rollout(int out_mode, const nig::MixedArgs &m, unsigned grid, hipStream_t st);
 
+// the launch table of every environment, nig_launch_<key>(): defined by env_<key>.hip
+#define NIG_ENV_DECLARE(EnvType, key, id) const nig::EnvLaunch *nig_launch_##key();
+NIG_ENV_LIST(NIG_ENV_DECLARE)
+#undef NIG_ENV_DECLARE
 #define NIG_DEFINE_ENV_LAUNCH(EnvType, fn_name) \
     const nig::EnvLaunch *fn_name() { return nig::env_launch_table<nig::EnvType>(); }
-// sampled_*.hip (compiled with NIG_SAMPLED_TU defined before this header): the env's nig_rollout_sampled launcher and kernels
-#define NIG_DEFINE_ENV_SAMPLED(EnvType) \
-    template void nig::launch_rollout_sampled_env<nig::EnvType>(int, const nig::RolloutArgs &, uint32_t, unsigned, hipStream_t);
-// ensemble_*.hip (compiled with NIG_ENSEMBLE_TU defined before this header): the env's nig_rollout_mlp_ensemble launcher and kernels
-#define NIG_DEFINE_ENV_ENSEMBLE(EnvType) \
-    template void nig::launch_mlp_ensemble_env<nig::EnvType>(int, const nig::MlpEnsArgs &, unsigned, hipStream_t);
-// disturbed_*.hip (compiled with NIG_DISTURBED_TU defined before this header): the env's nig_rollout_*_disturbed launchers and kernels
-#define NIG_DEFINE_ENV_DISTURBED(EnvType) \
-    template void nig::launch_policy_disturbed_env<nig::EnvType>(const nig::PolicyDistArgs &, unsigned, hipStream_t); \
-    template void nig::launch_mlp_disturbed_env<nig::EnvType>(const nig::MlpDistArgs &, unsigned, hipStream_t);
-// search_*.hip (compiled with NIG_SEARCH_TU defined before this header): the env's nig_rollout_mlp_search launcher and kernel
-#define NIG_DEFINE_ENV_SEARCH(EnvType) \
-    template void nig::launch_mlp_search_env<nig::EnvType>(const nig::MlpSearchArgs &, unsigned, hipStream_t);

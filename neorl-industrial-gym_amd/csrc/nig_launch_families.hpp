@@ -1,0 +1,59 @@
+// nig_launch_families.hpp -- the definitions of the family launchers nig_launch.hpp declares: the kernels of nig_rollout_sampled,
+// nig_rollout_mlp_ensemble, nig_rollout_policy_disturbed / nig_rollout_mlp_disturbed and nig_rollout_mlp_search.  Included by the
+// family translation units alone (sampled_, ensemble_, disturbed_, search_<key>.hip).  A template that is defined but not
+// instantiated emits nothing: each unit explicitly instantiates the launcher of its own family for its own env, and with it that
+// family's kernels and no other's.
+#pragma once
+#include "nig_launch.hpp"
+
+namespace nig {
+
+// nig_rollout_sampled: launch_rollout_env's selection on the twin kernels that draw their actions
+template <class Env>
+void launch_rollout_sampled_env(int out_mode, const RolloutArgs &q, uint32_t t0, unsigned grid, hipStream_t st)
+{
+    launch_rollout_paired<Env, true>(out_mode, q, t0, grid, st);
+}
+
+// nig_rollout_mlp_ensemble: one kernel per combination rule
+template <class Env>
+void launch_mlp_ensemble_env(int ens, const MlpEnsArgs &q, unsigned grid, hipStream_t st)
+{
+    if constexpr (has_mlp_actor<Env>) {
+        if (ens == ENS_AVERAGE) hipLaunchKernelGGL((rollout_mlp_ensemble_kernel<Env, ENS_AVERAGE>), dim3(grid), dim3(BLOCK), 0, st, q);
+        else hipLaunchKernelGGL((rollout_mlp_ensemble_kernel<Env, ENS_VOTING>), dim3(grid), dim3(BLOCK), 0, st, q);
+    }
+}
+
+// nig_rollout_policy_disturbed.  The closed loop under a disturbance has the one-wave form only (plan_policy_disturbed): the
+// three-wave and paired PowerGrid closed loops have no disturbed twin.
+template <class Env>
+void launch_policy_disturbed_env(const PolicyDistArgs &q, unsigned /*grid*/, hipStream_t st)
+{
+    const LaunchPlan plan = plan_policy_disturbed(q.p.s.B);
+    PolicyDistArgs r = q;
+    for (const Segment &s : plan) {
+        r.p.block0 = s.block0;
+        hipLaunchKernelGGL((rollout_policy_disturbed_kernel<Env>), dim3(s.grid), dim3(BLOCK), 0, st, r);
+    }
+}
+
+// nig_rollout_mlp_disturbed, nig_rollout_mlp_search
+template <class Env>
+void launch_mlp_disturbed_env(const MlpDistArgs &q, unsigned grid, hipStream_t st) { launch_mlp<Env>(q, grid, st); }
+
+template <class Env>
+void launch_mlp_search_env(const MlpSearchArgs &q, unsigned grid, hipStream_t st) { launch_mlp<Env>(q, grid, st); }
+
+}  // namespace nig
+
+// the one line of a family translation unit: the explicit instantiation of its env's launcher(s)
+#define NIG_DEFINE_ENV_SAMPLED(EnvType) \
+    template void nig::launch_rollout_sampled_env<nig::EnvType>(int, const nig::RolloutArgs &, uint32_t, unsigned, hipStream_t);
+#define NIG_DEFINE_ENV_ENSEMBLE(EnvType) \
+    template void nig::launch_mlp_ensemble_env<nig::EnvType>(int, const nig::MlpEnsArgs &, unsigned, hipStream_t);
+#define NIG_DEFINE_ENV_DISTURBED(EnvType) \
+    template void nig::launch_policy_disturbed_env<nig::EnvType>(const nig::PolicyDistArgs &, unsigned, hipStream_t); \
+    template void nig::launch_mlp_disturbed_env<nig::EnvType>(const nig::MlpDistArgs &, unsigned, hipStream_t);
+#define NIG_DEFINE_ENV_SEARCH(EnvType) \
+    template void nig::launch_mlp_search_env<nig::EnvType>(const nig::MlpSearchArgs &, unsigned, hipStream_t);

@@ -57,6 +57,10 @@ typedef __attribute__((address_space(1))) const void nig_glb_void;
 // register 4 b + (r & 3) of lane 16 (r >> 2) + c): blocks 0 / 1 are lane half 0's fma chain for envs 0-15 / 16-31, blocks 2 / 3
 // lane half 1's -- the SAME two chains and the same joining add as the 4 x 4 x 1 head, so the oracle has one head for every env.
 // The 32 x 32 x 2 head (64 cycles for 32 rows, 24 of them padding with eight actions) is gone.
+// The one statement of which envs have the MFMA actor: an even state dim (layer 1 takes the state two rows per k-step) and a head of
+// at most 16 rows.  The body asserts it, the launchers (nig_launch.hpp) compile a kernel only where it holds and leave the env's
+// table slot null elsewhere, which is what the C ABI asks.
+template <class Env> constexpr bool has_mlp_actor = Env::S % 2 == 0 && Env::A <= 16;
 template <class Env> constexpr bool mlp_head4 = Env::A <= 4;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 template <int N> using mlp_int = std::integral_constant<int, N>;      // a compile-time count handed to a lambda
@@ -158,7 +162,7 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
     using act_t = std::conditional_t<ACT64, double, float>;
     constexpr int S = Env::S, A = Env::A, KS = Env::KS, KR = Env::KR;
     constexpr int KSN = KS > 0 ? KS : 1;
-    static_assert(S % 2 == 0 && A <= 16, "MFMA actor needs an even state dim and at most 16 actions");
+    static_assert(has_mlp_actor<Env>, "MFMA actor needs an even state dim and at most 16 actions");
     // Weight records are shared by the four waves of the block through LDS: round 1 let every wave stream all
     // ~1 200 records of a step from L2 on its own (the same 256-byte lines requested by every wave of the chip at
     // about the same time: 96 TFLOP/s of 155).  Now the block fills a double-buffered LDS image chunk by chunk with

@@ -1,4 +1,3 @@
-// SteelAnnealing's kernels of nig_rollout_sampled (the fused rollout that draws its actions) -- a translation unit of their own
-#define NIG_SAMPLED_TU
-#include "nig_launch.hpp"
+// SteelAnnealing's kernels of nig_rollout_sampled (the fused rollout that draws its actions) -- a translation unit of their own (launcher: nig_launch_families.hpp)
+#include "nig_launch_families.hpp"
 NIG_DEFINE_ENV_SAMPLED(SteelAnnealing)

@@ -73,16 +73,10 @@ int main()
     char what;
     std::string env;
     while (std::cin >> what >> env) {
-        if (env == "cr") one_case<ChemicalReactor>(what);
-        else if (env == "pg") one_case<PowerGrid>(what);
-        else if (env == "ra") one_case<RobotAssembly>(what);
-        else if (env == "rar") one_case<RobotAssembly, RobotAssemblyRounds>(what);
-        else if (env == "acr") one_case<AdvancedChemicalReactor>(what);
-        else if (env == "apg") one_case<AdvancedPowerGrid>(what);
-        else if (env == "hvac") one_case<HVACControl>(what);
-        else if (env == "water") one_case<WaterTreatment>(what);
-        else if (env == "steel") one_case<SteelAnnealing>(what);
-        else if (env == "supply") one_case<SupplyChain>(what);
+        if (env == "rar") one_case<RobotAssembly, RobotAssemblyRounds>(what);
+#define NIG_PROBE_CASE(EnvType, key, id) else if (env == #key) one_case<EnvType>(what);
+        NIG_ENV_LIST(NIG_PROBE_CASE)       // the library's own list of environments, by the key of their translation units
+#undef NIG_PROBE_CASE
         else return 2;
     }
     return 0;
