@@ -81,8 +81,8 @@ extern "C" {
 #define NIG_FLAG_INACTIVE 0x800u        /* lane was already done (no auto-reset): untouched  */
 #define NIG_FLAG_VIOL3 0x1000u          /* 4th safety condition violated (Advanced envs)     */
 #define NIG_FLAG_NVIOL_HI 0x2000u       /* adds 4 to the violation count field (Advanced envs) */
-#define NIG_FLAG_SHIELDED 0x4000u       /* nig_rollout_mlp_safe: the safety critic halved the action (nig_rollout_mlp_search: replaced it) */
-#define NIG_FLAG_UNCERTAIN 0x8000u      /* nig_rollout_mlp_ensemble: uncertainty > threshold on this live step */
+#define NIG_FLAG_SHIELDED 0x4000u       /* nig_rollout_mlp_safe: the safety critic halved the action (nig_rollout_mlp_search: replaced it; nig_rollout_mlp_gated: the gate replaced it by zero) */
+#define NIG_FLAG_UNCERTAIN 0x8000u      /* nig_rollout_mlp_ensemble: uncertainty > threshold on this live step (nig_rollout_mlp_gated: some sd[c] is not below the spread limit) */
 #define NIG_FLAG_STEP_SHIFT 16          /* bits 16-31: current_step after this call          */
 
 /* per-lane counter word kept by the library */
@@ -598,6 +598,59 @@ int nig_rollout_mlp_ensemble(nig_handle *h, int32_t n_steps, float *reward_out, 
                              float *member_act_out, void *stream);
 
 /*
+ * Safety-ensemble gate of the reference's SafeEnsembleAgent.get_safe_action (agents/safety_critical.py:391-532),
+ * fused into the shield's kernel: K safety predictors with one head row per constraint score the actor's
+ * action; the env receives it only if every constraint's violation probability and every spread is small,
+ * and the zero action otherwise.  A member is a (S + A) -> 256 -> 256 -> C ReLU MLP in nig_set_mlp_safety's
+ * layouts with C3 [hidden][n_outputs], c3 [n_outputs]; hidden must be 256 (policies.pad_safety_member pads the
+ * reference's 128-wide members).  With K = 1, T = 1 and an infinite spread limit the gate is
+ * ConstrainedIQLAgent's acceptance test all(sigmoid(predictor(s, a)) < thr).
+ * The law, "nig-gate-v1".  Installed: K = n_members, C = n_outputs, T = temperature, thr = prob_threshold,
+ * umax = uncertainty_threshold.  For a live lane on a step:
+ *     a        = actor(s)                          bit for bit nig_rollout_mlp's action
+ *     z_m[c]   = head row c of member m on [s, a]  m = 0 .. K-1, c = 0 .. C-1; each row the two lane-half fma
+ *                                                  chains joined by one add, exactly the arithmetic of
+ *                                                  nig_rollout_mlp_safe's one-row head on C3[:, c], c3[c];
+ *                                                  rows do not interact
+ *     acc[c]   = z_0[c];  acc[c] = acc[c] + z_m[c]   (m = 1 .. K-1 in order);   mean[c] = acc[c] / (float)K
+ *     d_m      = z_m[c] - z_0[c];  s1 = s1 + d_m;  s2 = s2 + d_m * d_m   (m = 1 .. K-1 in order, from 0)
+ *     v        = s2 - (s1 * s1) / (float)K;  v = v < 0 ? 0 : v  (a NaN stays a NaN);  sd[c] = sqrt(v / (float)K)
+ *     pen      = sd[c] > 1 ? 1 : sd[c]
+ *     p[c]     = det_sigmoidf(mean[c] / T) + 0.5f * pen;   p[c] = p[c] < 0 ? 0 : (p[c] > 1 ? 1 : p[c])
+ *     safe     = p[c] < thr for every c;   certain = sd[c] < umax for every c      (false on NaN)
+ *     the env receives a if safe && certain, else the zero action ("reject_conservative")
+ *     flags:   NIG_FLAG_SHIELDED where the action was replaced;  NIG_FLAG_UNCERTAIN where !certain
+ * Every division and the square root are IEEE correctly rounded; no product is fused into a sum.  The spread
+ * is the ensemble actor's shifted variance (4 C registers whatever K is; exactly 0 for identical members and
+ * for K = 1) with one deliberate difference: the clamp keeps a NaN, so that a member whose logit is -inf
+ * rejects (the reference's jnp.std is NaN there and NaN < umax is false).  Against the reference's float64
+ * two-pass formula p and sd agree to 1e-5 relative.  A disturbance installed on the handle is ignored.
+ * C1 .. c3: host arrays [n_members] of host pointers.  NIG_ERR_INVALID: n_members outside
+ * 1 .. NIG_MAX_ENSEMBLE, n_outputs outside 1 .. 4, a NULL array or member pointer, a temperature that is not
+ * finite or <= 0, a NaN threshold.  NIG_ERR_UNSUPPORTED: hidden != 256, an env shape without the MFMA actor.
+ * The handle's actor, single critic and actor ensemble are left alone, and vice versa.
+ */
+int nig_set_mlp_safety_ensemble(nig_handle *h, int32_t n_members, int32_t hidden, int32_t n_outputs,
+                                const float *const *C1, const float *const *c1, const float *const *C2,
+                                const float *const *c2, const float *const *C3, const float *const *c3,
+                                float temperature, float prob_threshold, float uncertainty_threshold, void *stream);
+
+/*
+ * As nig_rollout_mlp (arguments, minima, obs_out alignment, frozen lanes, tallies, launch counter), with the
+ * installed gate.  act_out: the action the env received.  prob_out / unc_out (optional) float: row c of
+ * step k at base + k*c_step_stride + c*ld_c, c = 0 .. C-1 (p[c] / sd[c]).  logit_out (optional) float: member m
+ * of step k is one [C][ld_c] block at logit_out + (k*n_members + m)*c_step_stride (member_act_out's
+ * convention).  Frozen lanes leave their words untouched; rows >= C of a block are never written.  With any of
+ * the three: ld_c in [batch, 2^26] and c_step_stride >= C*ld_c.  NIG_ERR_INVALID (nothing launched or
+ * written): no actor or no members installed, a bad ld_c / c_step_stride, and every refusal of nig_rollout_mlp;
+ * NIG_ERR_UNSUPPORTED for an env shape without the MFMA actor.
+ */
+int nig_rollout_mlp_gated(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out,
+                          int64_t out_stride, float *obs_out, int64_t obs_step_stride, float *act_out,
+                          int64_t ld_act, int64_t act_step_stride, float *prob_out, float *unc_out,
+                          float *logit_out, int64_t ld_c, int64_t c_step_stride, void *stream);
+
+/*
  * Sensor / actuator noise inside the closed loop ("nig-disturb-v1"): the policy sees a noisy observation, the plant
  * receives a noisy action.  Stands in for the observation_noise / action_noise runs of the reference's
  * RobustnessBenchmark (benchmarks/industrial_benchmarks.py:455-573) and for predict(obs, deterministic=False) of
@@ -629,7 +682,7 @@ typedef struct nig_disturbance {
 
 /* Install (copy) the disturbance the _disturbed rollouts apply; d == NULL removes it.  NIG_ERR_INVALID, the installed one
  * kept: a negative / NaN / infinite sigma, clip_lo > clip_hi or a NaN bound, an unknown hold.  Only the two entry points
- * below read it: nig_rollout_policy, nig_rollout_mlp, nig_rollout_mlp_safe and nig_rollout_mlp_ensemble ignore an installed
+ * below read it: nig_rollout_policy, nig_rollout_mlp, nig_rollout_mlp_safe, nig_rollout_mlp_gated and nig_rollout_mlp_ensemble ignore an installed
  * disturbance (the shield and the ensemble have no disturbed form). */
 int nig_set_disturbance(nig_handle *h, const nig_disturbance *d /* host; NULL clears */, void *stream);
 

@@ -470,6 +470,43 @@ class BatchedIndustrialEnv:
         self._closed_loop(self._L.nig_rollout_mlp_search, n_steps, reward_out, flags_out, obs_out, act_out, head=(int(n_candidates),),
                           rows=[("prob_out", prob_out, torch.float32), ("risk_out", risk_out, torch.float32), ("choice_out", choice_out, torch.int32)])
 
+    def set_mlp_safety_ensemble(self, members, temperature: float = 1.0, threshold: float = 0.1, max_uncertainty: float = 0.2):
+        """Install the safety ensemble of SafeEnsembleAgent (agents/safety_critical.py) for rollout_mlp_gated(): `members` = a
+        list of 1 .. MAX_ENSEMBLE set_mlp_safety() weight lists whose heads have the same 1 .. 4 columns, one per constraint
+        (C3 [256, C], c3 [C]).  The law "nig-gate-v1" (include/nig.h) takes the temperature and the two limits as given.
+        The actor, the single critic and the actor ensemble stay as they are."""
+        K, Hd, D = len(members), 256, self.state_dim + self.action_dim
+        n_out = int(np.asarray(members[0][2][1]).size) if K else 0
+        W = [_mlp_weights(m, [(D, Hd), (Hd,), (Hd, Hd), (Hd,), (Hd, n_out), (n_out,)]) for m in members]
+        cols = [(C.c_void_p * K)(*[w[j].ctypes.data for w in W]) for j in range(6)] if K else [None] * 6
+        with torch.cuda.device(self._dev_index):
+            _lib.check(self._L.nig_set_mlp_safety_ensemble(self._h, K, Hd, n_out, *cols, float(temperature), float(threshold),
+                                                           float(max_uncertainty), self._stream()))
+        self._gate_shape = (K, n_out)
+
+    def rollout_mlp_gated(self, n_steps: int, reward_out=None, flags_out=None, obs_out=None, act_out=None, prob_out=None,
+                          unc_out=None, logit_out=None):
+        """rollout_mlp() with the installed safety ensemble's gate (SafeEnsembleAgent.get_safe_action on the device): the env
+        receives the actor's action where every constraint's violation probability is below the threshold and every spread
+        below the limit, the zero action elsewhere.  act_out holds the action the env received; prob_out / unc_out float32
+        [n_steps, C, >=B] p and sd per constraint; logit_out float32 [n_steps, K, C, >=B] every member's logits (the three
+        share their pitches); flags carry FLAG_SHIELDED where the action was replaced and FLAG_UNCERTAIN where a spread is not
+        below the limit."""
+        K, Cn = getattr(self, "_gate_shape", (0, 0))
+        ptrs, pitches = [], set()
+        for name, t, lead in (("prob_out", prob_out, ()), ("unc_out", unc_out, ()), ("logit_out", logit_out, (K,))):
+            if t is None:
+                ptrs.append(None)
+                continue
+            assert t.dtype == torch.float32 and t.dim() == 3 + len(lead) and t.stride(-1) == 1, name
+            assert t.shape[0] >= n_steps and tuple(t.shape[1:-1]) == lead + (Cn,) and t.shape[-1] >= self.batch, name
+            assert not lead or t.stride(0) == K * t.stride(1), name
+            ptrs.append(C.c_void_p(t.data_ptr()))
+            pitches.add((t.stride(-2), t.stride(-3)))
+        assert len(pitches) <= 1, "prob_out, unc_out and logit_out share their pitches"
+        ld_c, c_step = pitches.pop() if pitches else (0, 0)
+        self._closed_loop(self._L.nig_rollout_mlp_gated, n_steps, reward_out, flags_out, obs_out, act_out, tail=(*ptrs, ld_c, c_step))
+
     def set_mlp_ensemble(self, members, weights=None, weight_sum=None, method: str = "mean", uncertainty_threshold: float = 0.2):
         """Install an ensemble of actors (agents/ensemble.py EnsembleAgent) for rollout_mlp_ensemble(): `members` = a list of
         set_mlp_policy() weight lists.  method "mean" / "weighted": `weights` = the ACTIVE float64 weights of np.average (for

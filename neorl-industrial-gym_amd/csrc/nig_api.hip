@@ -178,6 +178,8 @@ struct nig_handle {
     float *mlp_cstream = nullptr;    // device copy of the MFMA operand stream of the safety critic (owned)
     float mlp_threshold = 0.0f;      // shield threshold of nig_rollout_mlp_safe
     // nig_set_mlp_ensemble (owned): the members' operand streams back to back, MLP_STREAM_FLOATS floats each; their active weights
+    // nig_set_mlp_safety_ensemble: the gate's member streams (owned), MLP_CSTREAM_FLOATS apart, and its law's parameters
+    float *gate_stream = nullptr; int gate_members = 0, gate_cap = 0, gate_outputs = 0; float gate_T = 1.0f, gate_thr = 0.0f, gate_umax = 0.0f;
     float *ens_stream = nullptr; double *ens_w = nullptr; int ens_members = 0, ens_cap = 0, ens_method = 0; double ens_wsum = 0.0; float ens_threshold = 0.0f;
     nig_disturbance dist = {}; bool has_dist = false;      // nig_set_disturbance: what the _disturbed rollouts apply
     float *act32 = nullptr;    // nig_step64 on an env that takes float32 actions: the narrowed rows [A][ld] (owned, lazy)
@@ -424,14 +426,14 @@ static int disturb_args(const nig_handle *h, const char *fn, float *seen_out, in
     return NIG_OK;
 }
 
-// ---- the closed loop: what nig_rollout_policy / _mlp / _mlp_safe / _mlp_search / _mlp_ensemble / _policy_disturbed / _mlp_disturbed
+// ---- the closed loop: what nig_rollout_policy / _mlp / _mlp_safe / _mlp_search / _mlp_gated / _mlp_ensemble / _policy_disturbed / _mlp_disturbed
 // do after their own prerequisites.  A variant's argument block holds the shared fields as PolicyArgs or MlpArgs, which also says
 // what grid its kernels take: a thread per env for the policy kernels, 32 envs per wave (128 per block) for the MFMA kernels.
 static PolicyArgs &shared_args(PolicyArgs &q) { return q; }
 static PolicyArgs &shared_args(PolicyDistArgs &q) { return q.p; }
 static MlpArgs &shared_args(MlpArgs &q) { return q; }
 static MlpArgs &shared_args(MlpSearchArgs &q) { return q.sh.m; }
-template <class Args> static MlpArgs &shared_args(Args &q) { return q.m; }      // MlpShieldArgs, MlpEnsArgs, MlpDistArgs
+template <class Args> static MlpArgs &shared_args(Args &q) { return q.m; }      // MlpShieldArgs, MlpEnsArgs, MlpDistArgs, MlpGateArgs
 static unsigned closed_loop_grid(const nig_handle *h, const PolicyArgs &) { return grid_for(h->B); }
 static unsigned closed_loop_grid(const nig_handle *h, const MlpArgs &) { return (unsigned)((h->B + BLOCK / 2 - 1) / (BLOCK / 2)); }
 
@@ -498,6 +500,9 @@ extern "C" {
 // Still 0.8.0, for the same reason: nig_rollout_mlp_search ("nig-search-v1": the safety-critical agents' get_safe_action -- the critic
 // scores n_candidates uniform actions where the actor's is too risky; blocks +0x100.. of the generator's policy stream).  Additive:
 // no new state on the handle, no existing kernel or entry point changed.
+// Still 0.8.0, for the same reason: nig_set_mlp_safety_ensemble / nig_rollout_mlp_gated ("nig-gate-v1": SafeEnsembleAgent's
+// get_safe_action -- K safety predictors of up to four head rows vote on the actor's action).  Additive: no existing kernel or entry
+// point changed.
 const char *nig_version(void) { return "nig 0.8.0 (gfx950; generator nig-philox-v3)"; }
 const char *nig_last_error(void) { return g_err; }
 
@@ -666,6 +671,7 @@ int nig_destroy(nig_handle *h)
     if (h->mlp_cstream) (void)hipFree(h->mlp_cstream);
     if (h->ens_stream) (void)hipFree(h->ens_stream);
     if (h->ens_w) (void)hipFree(h->ens_w);
+    if (h->gate_stream) (void)hipFree(h->gate_stream);
     if (h->pid_mem) (void)hipFree(h->pid_mem);
     if (h->act32) (void)hipFree(h->act32);
     if (h->act_soa) (void)hipFree(h->act_soa);
@@ -1121,6 +1127,59 @@ int nig_rollout_mlp_ensemble(nig_handle *h, int32_t n_steps, float *reward_out, 
         return [h](const MlpEnsArgs &e, unsigned grid, hipStream_t st) {
             launch_of(h->env)->mlp_ensemble(h->ens_method == NIG_ENSEMBLE_AVERAGE ? ENS_AVERAGE : ENS_VOTING, e, grid, st);
         };
+    });
+}
+
+// ---- the safety-ensemble gate ("nig-gate-v1") ------------------------------------------------
+int nig_set_mlp_safety_ensemble(nig_handle *h, int32_t n_members, int32_t hidden, int32_t n_outputs,
+                                const float *const *C1, const float *const *c1, const float *const *C2, const float *const *c2,
+                                const float *const *C3, const float *const *c3, float temperature, float prob_threshold,
+                                float uncertainty_threshold, void *stream)
+{
+    const char *const fn = "nig_set_mlp_safety_ensemble";
+    if (!h) return fail(NIG_ERR_INVALID, "nig_set_mlp_safety_ensemble: NULL handle");
+    if (n_members < 1 || n_members > NIG_MAX_ENSEMBLE) return refuse(fn, "n_members outside 1 .. NIG_MAX_ENSEMBLE");
+    if (n_outputs < 1 || n_outputs > 4) return refuse(fn, "n_outputs outside 1 .. 4");
+    if (!C1 || !c1 || !C2 || !c2 || !C3 || !c3) return refuse(fn, "NULL member array (C1 / c1 / C2 / c2 / C3 / c3)");
+    for (int k = 0; k < n_members; ++k)
+        if (!C1[k] || !c1[k] || !C2[k] || !c2[k] || !C3[k] || !c3[k]) return refuse(fn, "NULL member array (C1 / c1 / C2 / c2 / C3 / c3 of a member)");
+    if (!std::isfinite(temperature) || !(temperature > 0.0f)) return refuse(fn, "temperature must be finite and > 0");
+    if (prob_threshold != prob_threshold || uncertainty_threshold != uncertainty_threshold) return refuse(fn, "a NaN threshold");
+    const int S = SPECS[h->env].state_dim, A = SPECS[h->env].action_dim;
+    float *host = nullptr;
+    NIG_TRY(build_network_images(h, fn, hidden, S + A, n_outputs, MLP_CSTREAM_FLOATS, n_members, C1, c1, C2, c2, C3, c3, &host));
+    h->gate_members = 0;                                    // no gate while the streams are being replaced
+    if (h->gate_cap < n_members) {                          // too small: upload_stream allocates the new one
+        if (h->gate_stream) (void)hipFree(h->gate_stream);
+        h->gate_stream = nullptr; h->gate_cap = 0;
+    }
+    NIG_TRY(upload_stream(fn, &h->gate_stream, host, (size_t)n_members * MLP_CSTREAM_FLOATS, stream));
+    if (h->gate_cap == 0) h->gate_cap = n_members;
+    h->gate_members = n_members; h->gate_outputs = n_outputs;
+    h->gate_T = temperature; h->gate_thr = prob_threshold; h->gate_umax = uncertainty_threshold;
+    return NIG_OK;
+}
+
+int nig_rollout_mlp_gated(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                          float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
+                          float *prob_out, float *unc_out, float *logit_out, int64_t ld_c, int64_t c_step_stride, void *stream)
+{
+    const char *const fn = "nig_rollout_mlp_gated";
+    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_gated: bad argument");
+    if (!launch_of(h->env)->mlp_gated) return refuse(fn, "env shape has no MFMA actor", NIG_ERR_UNSUPPORTED);
+    if (!h->mlp_stream) return refuse(fn, "no actor installed (nig_set_mlp_policy)");
+    if (h->gate_members < 1 || !h->gate_stream) return refuse(fn, "no safety ensemble installed (nig_set_mlp_safety_ensemble)");
+    if (prob_out || unc_out || logit_out) {
+        if (ld_c < h->B || ld_c > NIG_MAX_PITCH) return refuse(fn, "ld_c outside [batch, 2^26]");
+        if (c_step_stride < (int64_t)h->gate_outputs * ld_c) return refuse(fn, "c_step_stride smaller than one [n_outputs][ld_c] block");
+    }
+    return closed_loop<MlpGateArgs>(h, fn, n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpGateArgs &q) {
+        q.m.wstream = h->mlp_stream;
+        q.cstreams = h->gate_stream; q.n_members = h->gate_members; q.n_outputs = h->gate_outputs; q.kf = (float)h->gate_members;
+        q.temperature = h->gate_T; q.threshold = h->gate_thr; q.umax = h->gate_umax;
+        q.prob_out = prob_out; q.unc_out = unc_out; q.logit_out = logit_out;
+        q.ld_c = (uint32_t)ld_c; q.c_step_stride = (uint64_t)c_step_stride;
+        return launch_of(h->env)->mlp_gated;
     });
 }
 

@@ -1,5 +1,5 @@
 // nig_mlp.hpp -- the fused MLP actor on MFMA with its safety-critic shield and its ensemble (device code only): MlpArgs,
-// MlpShieldArgs, MlpEnsArgs, MlpDistArgs, MlpSearchArgs, rollout_mlp_body and its five kernels.
+// MlpShieldArgs, MlpEnsArgs, MlpDistArgs, MlpSearchArgs, MlpGateArgs, rollout_mlp_body and its six kernels.
 #pragma once
 #include <type_traits>
 #include "nig_step.hpp"
@@ -148,14 +148,41 @@ __device__ __forceinline__ void search_candidate(const RngKey &key, int c, float
     }
 }
 
-template <class Env, bool SHIELD, int ENS = ENS_NONE, bool DIST = false, bool SEARCH = false>
+// Safety-ensemble gate (rollout_mlp_gated_kernel, agents/safety_critical.py SafeEnsembleAgent.get_safe_action; include/nig.h
+// "nig-gate-v1"): GATE is the shield's form with n_members critics of n_outputs <= 4 head rows each.  The members' passes run through
+// the same double-buffered LDS image, member m's stream at cstreams + m * MLP_CSTREAM_FLOATS -- the ensemble actor's fill chain on
+// the critic's two layer-1 shapes: member m + 1's layer-1 chunk is in flight while member m's last hidden tile is consumed, the
+// next step's actor layer 1 behind the last member.  The head stays f32x4 on v_mfma_f32_4x4x1: row c of a member is the shield's
+// one-row head on column c (rows do not interact), rows >= n_outputs carry zero weights and stay out of the vote and of every
+// output.  The members' logits are reduced as they arrive by the ensemble actor's shifted sums about member 0 -- z_0, s1, s2 and
+// the running sum: 16 registers whatever K is -- except that the variance's clamp keeps a NaN (v < 0 ? 0 : v): a member whose
+// logit is -inf must reject.  Every pass is needed by every block: there is no vote.  As the search, the form keeps nothing across
+// the passes that a step can form again from the lane index.
+struct MlpGateArgs {
+    MlpArgs m;
+    const float *cstreams;      // the members' operand streams built by nig_set_mlp_safety_ensemble, MLP_CSTREAM_FLOATS floats apart
+    int n_members;              // K, 1 .. NIG_MAX_ENSEMBLE
+    int n_outputs;              // C, 1 .. 4: the head rows that vote
+    float kf;                   // (float)n_members
+    float temperature;          // T
+    float threshold;            // reject unless p[c] < threshold for every c
+    float umax;                 // reject (NIG_FLAG_UNCERTAIN) unless sd[c] < umax for every c
+    float *prob_out;            // p: row c of step k at prob_out + k * c_step_stride + c * ld_c, may be NULL
+    float *unc_out;             // sd: the same layout, may be NULL
+    float *logit_out;           // z: member m of step k is [C][ld_c] at logit_out + (k * n_members + m) * c_step_stride, may be NULL
+    uint32_t ld_c; uint64_t c_step_stride;
+};
+
+template <class Env, bool SHIELD, int ENS = ENS_NONE, bool DIST = false, bool SEARCH = false, bool GATE = false>
 __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const MlpArgs &q, const float *cstream, float *prob_out, float threshold,
                                                                        [[maybe_unused]] const MlpEnsArgs *eq = nullptr,
                                                                        [[maybe_unused]] const DisturbArgs *dq = nullptr,
-                                                                       [[maybe_unused]] const MlpSearchArgs *sq = nullptr)
+                                                                       [[maybe_unused]] const MlpSearchArgs *sq = nullptr,
+                                                                       [[maybe_unused]] const MlpGateArgs *gq = nullptr)
 {
     static_assert(!(SHIELD && ENS != ENS_NONE), "the ensemble has no shield");
     static_assert(!SEARCH || SHIELD, "the search is a form of the shield");
+    static_assert(!GATE || (SHIELD && !SEARCH), "the gate is a form of the shield; it has no searching twin");
     static_assert(!DIST || (!SHIELD && ENS == ENS_NONE), "the shield and the ensemble have no disturbed form");
     // the env steps on the ensemble's float64 action where its NumPy arithmetic follows the action's type (nig_step64's rule)
     constexpr bool ACT64 = ENS == ENS_AVERAGE && Env::HAS_ACT64;
@@ -182,7 +209,7 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
     // the lane's global index where a step needs it; the search forms it anew each time (as its output addresses, below: nothing
     // that a step can form from the lane index is kept in registers across the candidate passes)
     auto lane_gi = [&]() __attribute__((always_inline)) {
-        if constexpr (SEARCH) { uint32_t l = li; asm volatile("" : "+v"(l)); return p.env0 + (uint64_t)l; }
+        if constexpr (SEARCH || GATE) { uint32_t l = li; asm volatile("" : "+v"(l)); return p.env0 + (uint64_t)l; }
         else return gi;
     };
     const bool autoreset = (p.hflags & NIG_F_AUTORESET) != 0;
@@ -204,7 +231,8 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
             __builtin_amdgcn_global_load_lds((nig_glb_void *)(src + pc * 256), (nig_lds_void *)(&s_w[buf][pc * 256]), 16, 0, 0);
     };
     auto fill = [&](int c, int buf, int pieces) __attribute__((always_inline)) { fill_from(ENS != ENS_NONE ? wsrc : q.wstream, c, buf, pieces); };
-    [[maybe_unused]] auto cfill = [&](int c, int buf, int pieces) __attribute__((always_inline)) { fill_from(cstream, c, buf, pieces); };
+    [[maybe_unused]] const float *gsrc = cstream;            // gate: operand stream of the member being filled from
+    [[maybe_unused]] auto cfill = [&](int c, int buf, int pieces) __attribute__((always_inline)) { fill_from(GATE ? gsrc : cstream, c, buf, pieces); };
     constexpr MlpLayer1 L1 = mlp_layer1(S), C1 = mlp_layer1(S + A);   // layer 1 of the actor (S, A) and of the critic (S + A, 1)
     static_assert(L1.chunks == 1, "the actor's layer 1 must fit one chunk");
     static_assert(C1.fits(), "a critic layer-1 chunk must fit one chunk slot");
@@ -281,6 +309,9 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
         auto xin = [&](int k) __attribute__((always_inline)) { if constexpr (DIST) return d_o[k]; else return s[k]; };   // layer 1's input
         [[maybe_unused]] float e_p0[A], e_s1[A], e_s2[A], e_f[A];   // ensemble: member 0, sum d, sum d^2, float32 action sum
         [[maybe_unused]] double e_d[A];                            // ensemble: float64 weighted action sum
+        [[maybe_unused]] float g_z0[GATE ? 4 : 1], g_s1[GATE ? 4 : 1], g_s2[GATE ? 4 : 1], g_acc[GATE ? 4 : 1];   // gate: member 0, sum d, sum d^2, logit sum
+        [[maybe_unused]] int g_mem = 0;                            // gate: this pass's member
+        [[maybe_unused]] bool g_uncertain = false;
         int mem = 0;
         do {                                                       // (one pass unless ENS)
         // ---------------- actor: 3 layers of f32 MFMA, whole wave (EXEC all ones) ----------------
@@ -371,7 +402,7 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
         [[maybe_unused]] int s_choice = -1, s_cand = -1, s_passes = 0;   // search: the best's number; this pass (-1: the actor's action); how many
         [[maybe_unused]] float s_u[SEARCH ? A : 1];                // search: this pass's candidate (dead after layer 1)
         if constexpr (SHIELD) {
-            do {                                                   // (one pass unless SEARCH)
+            do {                                                   // (one pass unless SEARCH or GATE)
             // ---------------- safety critic on x = [s, a, 0]: the network (S + A, 1) ----------------
             auto x = [&](int k) __attribute__((always_inline)) {
                 if constexpr (SEARCH) return k < S ? s[k] : (k < S + A ? (s_cand < 0 ? a[k - S] : s_u[k - S]) : 0.0f);
@@ -405,11 +436,39 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
                         else if (it + 1 < q.n_steps) fill(0, gbuf ^ 1, L1.pieces);
                     }
                 }
+                else if constexpr (GATE) {                         // layer 1 of the next member, or of the actor for the next step
+                    const bool more = g_mem + 1 < gq->n_members;
+                    gsrc = more ? gsrc + MLP_CSTREAM_FLOATS : cstream;
+                    if (more) cfill(0, gbuf ^ 1, C1.pieces);
+                    else if (it + 1 < q.n_steps) fill(0, gbuf ^ 1, L1.pieces);
+                }
                 else if (it + 1 < q.n_steps) fill(0, gbuf ^ 1, L1.pieces);   // the actor's layer 1 of the NEXT step
                 z4 = layer2_chunk(g1, z4, m2 + 1, gbuf);
                 gbuf ^= 1;
             }
-            prob = det_sigmoidf(z4[0] + __shfl_xor(z4[0], 32));
+            if constexpr (GATE) {                                  // fold member `g_mem` into the running sums (the law, include/nig.h)
+                float z[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) z[c] = z4[c] + __shfl_xor(z4[c], 32);
+                if (writer && !(ctr & NIG_CTR_DONE) && gq->logit_out) {   // the logits leave here
+                    uint32_t lo = li;
+                    asm volatile("" : "+v"(lo));
+                    float *zo = gq->logit_out + ((size_t)it * (size_t)gq->n_members + (size_t)g_mem) * gq->c_step_stride;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+                        if (c < gq->n_outputs) (zo + c * gq->ld_c)[lo] = z[c];
+                }
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    if (g_mem == 0) { g_z0[c] = z[c]; g_acc[c] = z[c]; g_s1[c] = 0.0f; g_s2[c] = 0.0f; }
+                    else {
+                        const float d = z[c] - g_z0[c];
+                        g_s1[c] = g_s1[c] + d; g_s2[c] = g_s2[c] + d * d;
+                        g_acc[c] = g_acc[c] + z[c];
+                    }
+                }
+            }
+            else prob = det_sigmoidf(z4[0] + __shfl_xor(z4[0], 32));
             if constexpr (SEARCH) {
                 if (s_cand < 0) {
                     s_best = prob;
@@ -430,9 +489,35 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
                 if (++s_cand < s_passes)                           // (beside the fill of its layer 1, ahead of the chunk barrier)
                     search_candidate<A>(make_key(lane_gi(), t_base + (uint32_t)it + 1u, p.seed_lo, p.seed_hi, s_probit), s_cand, s_u);
             }
-            } while (SEARCH && s_cand < s_passes);
+            } while (GATE ? ++g_mem < gq->n_members : (SEARCH && s_cand < s_passes));
             if constexpr (SEARCH) {
                 if (shield) search_candidate<A>(make_key(lane_gi(), t_base + (uint32_t)it + 1u, p.seed_lo, p.seed_hi, s_probit), s_choice, a);
+            } else if constexpr (GATE) {                           // once per step: p and sd of every row, the vote, the zero action
+                const float kf = gq->kf;
+                const bool live_writer = writer && !(ctr & NIG_CTR_DONE);
+                uint32_t lo = li;
+                asm volatile("" : "+v"(lo));
+                const size_t crow = (size_t)it * gq->c_step_stride + lo;
+                bool safe = true, certain = true;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    float v = g_s2[c] - (g_s1[c] * g_s1[c]) / kf;
+                    v = v < 0.0f ? 0.0f : v;                       // (a NaN stays a NaN)
+                    const float sd = __builtin_sqrtf(v / kf);
+                    const float pen = sd > 1.0f ? 1.0f : sd;
+                    float pc = det_sigmoidf((g_acc[c] / kf) / gq->temperature) + 0.5f * pen;
+                    pc = pc < 0.0f ? 0.0f : (pc > 1.0f ? 1.0f : pc);
+                    if (c < gq->n_outputs) {
+                        safe = safe && pc < gq->threshold;
+                        certain = certain && sd < gq->umax;
+                        if (live_writer && gq->prob_out) (gq->prob_out + crow)[(size_t)c * gq->ld_c] = pc;
+                        if (live_writer && gq->unc_out) (gq->unc_out + crow)[(size_t)c * gq->ld_c] = sd;
+                    }
+                }
+                g_uncertain = !certain;
+                shield = !(safe && certain);
+#pragma unroll
+                for (int r = 0; r < A; ++r) a[r] = shield ? 0.0f : a[r];     // "reject_conservative"
             } else {
                 shield = !(prob < threshold);
 #pragma unroll
@@ -443,7 +528,7 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
         // ---------------- IndustrialEnv.step (both lane halves, identical results) ----------------
         const uint32_t orow = (uint32_t)it * q.out_stride;
         uint32_t lo = li;                                          // the lane's index in this step's output addresses
-        if constexpr (SEARCH) asm volatile("" : "+v"(lo));         // (formed here, step by step: no address is kept in registers across the passes)
+        if constexpr (SEARCH || GATE) asm volatile("" : "+v"(lo)); // (formed here, step by step: no address is kept in registers across the passes)
         const bool frozen = (ctr & NIG_CTR_DONE) != 0;
         if (writer && !frozen) {
             if (q.obs_out) {
@@ -461,7 +546,7 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
 #pragma unroll
                 for (int j = 0; j < A; ++j) (ao + j * q.ld_act_out)[lo] = a[j];
             }
-            if constexpr (SHIELD && !SEARCH) {
+            if constexpr (SHIELD && !SEARCH && !GATE) {
                 if (prob_out) (prob_out + (uint32_t)it * q.out_stride)[lo] = prob;
             }
             if constexpr (SEARCH) {
@@ -484,6 +569,7 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
         uint32_t fl = pack_flags<Env>(res, step) | did_reset_flag(done && autoreset);
         if constexpr (SHIELD) fl |= shield ? NIG_FLAG_SHIELDED : 0u;
         if constexpr (ENS != ENS_NONE) fl |= uncertain ? NIG_FLAG_UNCERTAIN : 0u;
+        if constexpr (GATE) fl |= g_uncertain ? NIG_FLAG_UNCERTAIN : 0u;
         float rew = (float)res.reward;
         if (frozen) {
             fl = NIG_FLAG_INACTIVE | ((ctr & NIG_CTR_STEP_MASK) << NIG_FLAG_STEP_SHIFT);
@@ -535,6 +621,13 @@ template <class Env>
 __global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_search_kernel(const MlpSearchArgs q)
 {
     rollout_mlp_body<Env, true, ENS_NONE, false, true>(q.sh.m, q.sh.cstream, q.sh.prob_out, q.sh.threshold, nullptr, nullptr, &q);
+}
+
+// Instantiated in the env's gated_*.hip translation unit only (launch_mlp_gated_env).
+template <class Env>
+__global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_gated_kernel(const MlpGateArgs q)
+{
+    rollout_mlp_body<Env, true, ENS_NONE, false, false, true>(q.m, q.cstreams, nullptr, q.threshold, nullptr, nullptr, nullptr, &q);
 }
 
 // ENS = ENS_AVERAGE / ENS_VOTING.  Instantiated in the env's ensemble_*.hip translation unit only (launch_mlp_ensemble_env).

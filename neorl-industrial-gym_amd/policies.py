@@ -251,6 +251,25 @@ def pad_critic(weights, hidden: int = 256):
     return [(P1, p1), (P2, p2), (P3, c3.copy())]
 
 
+def pad_safety_member(weights, hidden: int = 256):
+    """pad_critic for a head of 1 .. 4 columns: a safety-ensemble member [(C1 [D,h], c1 [h]), (C2 [h,h], c2 [h]), (C3 [h,C], c3 [C])]
+    with h <= hidden (the reference's SafetyEnsembleMember: 128) as the `hidden`-wide network set_mlp_safety_ensemble() takes.
+    The added units are exactly 0 after ReLU and every added term is an exact zero, so each padded row computes the h-wide
+    one's number.  hidden-wide weights come back as float32 copies; anything else is refused."""
+    if len(weights) != 3:
+        raise ValueError(f"a safety-ensemble member has three layers, got {len(weights)}")
+    (C1, c1), (C2, c2), (C3, c3) = [(np.asarray(W, dtype=f32), np.asarray(b, dtype=f32).reshape(-1)) for W, b in weights]
+    C3 = C3.reshape(C3.shape[0], -1)
+    h, n = C1.shape[1], c3.shape[0]
+    if not (1 <= h <= hidden and 1 <= n <= 4 and C2.shape == (h, h) and C3.shape == (h, n) and c1.shape == (h,) and c2.shape == (h,)):
+        raise ValueError(f"cannot pad a member of shapes {[np.shape(W) for W, _ in weights]} to hidden width {hidden} and a head of 1 .. 4 columns")
+    P1, p1 = np.zeros((C1.shape[0], hidden), dtype=f32), np.zeros(hidden, dtype=f32)
+    P2, p2 = np.zeros((hidden, hidden), dtype=f32), np.zeros(hidden, dtype=f32)
+    P3 = np.zeros((hidden, n), dtype=f32)
+    P1[:, :h], p1[:h], P2[:h, :h], p2[:h], P3[:h] = C1, c1, C2, c2, C3
+    return [(P1, p1), (P2, p2), (P3, c3.copy())]
+
+
 class MLPPolicy:
     """The deterministic actor of the reference's agents -- (S -> 256 -> 256 -> A) ReLU MLP with a
     tanh head (agents/networks.py:47-70,125-144; cql.py:339-343) -- kept on the GPU.
@@ -473,6 +492,145 @@ class ShieldedMLPPolicy:
 
     def predict(self, observations, deterministic: bool = True):
         return self.base.predict_with_safety(observations, self.threshold)[0]
+
+
+class SafetyEnsemblePolicy:
+    """The reference's SafeEnsembleAgent.get_safe_action (agents/safety_critical.py:391-532) over an actor and K safety
+    predictors with one head column per constraint, kept on the GPU: the actor's action is accepted where every constraint's
+    violation probability p = clip(sigmoid(mean / T) + 0.5 min(sd, 1), 0, 1) is below `threshold` and every spread sd of the
+    members' logits below `max_uncertainty`; the zero action is commanded elsewhere.  The arithmetic is the law "nig-gate-v1"
+    of include/nig.h in torch (float32, the shifted variance about member 0, the clamp that keeps a NaN).
+
+    `actor`: an MLPPolicy or a weight list; `members`: weight lists [(C1 [S+A,h], c1), (C2 [h,h], c2), (C3 [h,C], c3)] with the
+    same C in 1 .. 4.  When the actor has the reference shape and every member three layers of hidden width <= 256 (padded to 256
+    by pad_safety_member: the reference's members are 128 wide) and there are at most 8 members (`fusable`),
+    evaluate_with_safety / evaluate_episodes run the gate fused into the env kernel (BatchedIndustrialEnv.rollout_mlp_gated);
+    otherwise through torch GEMMs."""
+    is_trained = True
+
+    def __init__(self, actor, members, temperature: float = 1.0, threshold: float = 0.1, max_uncertainty: float = 0.2, device="cuda:0"):
+        import torch
+        self.actor = actor if hasattr(actor, "predict_device") else MLPPolicy(actor, device=device)
+        self.device = torch.device(getattr(self.actor, "device", device))
+        self.state_dim, self.action_dim = self.actor.state_dim, self.actor.action_dim
+        self.weights = self.actor.weights
+        self.members = [[(np.asarray(W, dtype=f32).reshape(np.shape(W)[0], -1), np.asarray(b, dtype=f32).reshape(-1)) for W, b in m]
+                        for m in members]
+        if not self.members:
+            raise RuntimeError("No members in the safety ensemble")
+        self.n_outputs = self.members[0][-1][0].shape[1]
+        for m in self.members:
+            if m[0][0].shape[0] != self.state_dim + self.action_dim or m[-1][0].shape[1] != self.n_outputs or m[-1][1].shape != (self.n_outputs,):
+                raise ValueError(f"safety-ensemble members must map S+A={self.state_dim + self.action_dim} inputs to the same number of "
+                                 f"constraints, got {[w.shape for w, _ in m]}")
+        self.temperature, self.threshold, self.max_uncertainty = float(temperature), float(threshold), float(max_uncertainty)
+        if not (np.isfinite(self.temperature) and self.temperature > 0):
+            raise ValueError(f"temperature must be finite and > 0, got {temperature}")
+        if np.isnan(self.threshold) or np.isnan(self.max_uncertainty):
+            raise ValueError("a NaN threshold")
+        self.member_layers = [[(torch.as_tensor(W, device=self.device).contiguous(), torch.as_tensor(b, device=self.device).contiguous())
+                               for W, b in m] for m in self.members]
+
+        def paddable(m):
+            h = m[0][0].shape[1]
+            return len(m) == 3 and h <= 256 and m[1][0].shape == (h, h) and m[2][0].shape[0] == h
+        self.fusable = (bool(getattr(self.actor, "fusable", False)) and len(self.members) <= _lib.MAX_ENSEMBLE
+                        and 1 <= self.n_outputs <= 4 and all(paddable(m) for m in self.members))
+
+    @classmethod
+    def from_agent(cls, actor_agent, safe_agent, device="cuda:0", max_uncertainty: float = 0.2):
+        """From a reference agent with an actor (MLPPolicy.from_agent) and a SafeEnsembleAgent: the members
+        safe_agent.ensemble_states[i].params = {"params": {"layers_0", "layers_1", "safety_head"}} in list order,
+        safe_agent.temperature, and safe_agent.uncertainty_threshold as the probability limit (safety_critical.py:512; the
+        spread limit is the reference's constant 0.2)."""
+        members = [_named_layers(st.params, ("layers_0", "layers_1", "safety_head"), "safety ensemble member") for st in safe_agent.ensemble_states]
+        return cls(MLPPolicy.from_agent(actor_agent, device=device), members, temperature=getattr(safe_agent, "temperature", 1.0),
+                   threshold=safe_agent.uncertainty_threshold, max_uncertainty=max_uncertainty, device=device)
+
+    def install(self, env):
+        """Install actor and members on a BatchedIndustrialEnv for rollout_mlp_gated()."""
+        env.set_mlp_policy(self.weights)
+        env.set_mlp_safety_ensemble([pad_safety_member(m) for m in self.members], self.temperature, self.threshold, self.max_uncertainty)
+
+    # ---- device (torch) forms of the law ----
+    def member_logits_device(self, obs, actions):
+        """z [K, n, C]: every member's head on [obs, actions]."""
+        import torch
+        x0 = torch.cat([obs, actions], dim=1)
+        out = []
+        for layers in self.member_layers:
+            x = x0
+            for i, (W, b) in enumerate(layers):
+                x = torch.addmm(b, x, W)
+                if i + 1 < len(layers):
+                    x = torch.relu(x)
+            out.append(x)
+        return torch.stack(out)
+
+    def _law_device(self, z):
+        """(p [n, C], sd [n, C]) of the members' logits z [K, n, C]: "nig-gate-v1"."""
+        import torch
+        K = z.shape[0]
+        kf = torch.tensor(K, dtype=torch.float32, device=z.device)
+        acc, s1, s2 = z[0], torch.zeros_like(z[0]), torch.zeros_like(z[0])
+        for m in range(1, K):
+            acc = acc + z[m]
+            d = z[m] - z[0]
+            s1 = s1 + d
+            s2 = s2 + d * d
+        v = s2 - (s1 * s1) / kf
+        v = torch.where(v < 0, torch.zeros_like(v), v)              # (a NaN stays a NaN)
+        sd = torch.sqrt(v / kf)
+        pen = torch.where(sd > 1, torch.ones_like(sd), sd)
+        p = torch.sigmoid((acc / kf) / self.temperature) + 0.5 * pen
+        p = torch.where(p < 0, torch.zeros_like(p), torch.where(p > 1, torch.ones_like(p), p))
+        return p, sd
+
+    def violation_probs_device(self, obs, actions):
+        """compute_safety_violation_probability on device tensors: (p [n, C], sd [n, C])."""
+        return self._law_device(self.member_logits_device(obs, actions))
+
+    def get_safe_action_device(self, obs, preferred=None):
+        """get_safe_action on device tensors, a batch of states at once: (actions [n, A], {"violation_prob" [n, C],
+        "uncertainty" [n, C], "accept" [n] bool, "certain" [n] bool})."""
+        import torch
+        a = self.actor.predict_device(obs) if preferred is None else preferred
+        p, sd = self.violation_probs_device(obs, a)
+        safe, certain = (p < self.threshold).all(dim=1), (sd < self.max_uncertainty).all(dim=1)
+        accept = safe & certain
+        return torch.where(accept[:, None], a, torch.zeros_like(a)), {"violation_prob": p, "uncertainty": sd, "accept": accept, "certain": certain}
+
+    def predict_device(self, obs):
+        return self.get_safe_action_device(obs)[0]
+
+    # ---- host forms (the reference's contract) ----
+    def _host(self, x, width):
+        import torch
+        t = torch.as_tensor(np.asarray(x, dtype=f32), device=self.device)
+        return t.reshape(-1, width), t.dim() == 1
+
+    def violation_probs(self, observations, actions):
+        """(violation_prob, uncertainty) as NumPy arrays, [C] for a single observation."""
+        o, single = self._host(observations, self.state_dim)
+        p, sd = self.violation_probs_device(o, self._host(actions, self.action_dim)[0])
+        p, sd = p.cpu().numpy(), sd.cpu().numpy()
+        return (p[0], sd[0]) if single else (p, sd)
+
+    def get_safe_action(self, observations, preferred=None):
+        """SafeEnsembleAgent.get_safe_action on host arrays, `preferred` defaulting to the actor's action: (action,
+        {"violation_prob", "uncertainty", "decision"}), decision "accept" or "reject_conservative" (an array of them for a
+        batch of observations, whose rows are decided one by one)."""
+        o, single = self._host(observations, self.state_dim)
+        pa = None if preferred is None else self._host(preferred, self.action_dim)[0]
+        a, info = self.get_safe_action_device(o, pa)
+        decision = np.where(info["accept"].cpu().numpy(), "accept", "reject_conservative")
+        a, p, sd = a.cpu().numpy(), info["violation_prob"].cpu().numpy(), info["uncertainty"].cpu().numpy()
+        if single:
+            return a[0], {"violation_prob": p[0], "uncertainty": sd[0], "decision": str(decision[0])}
+        return a, {"violation_prob": p, "uncertainty": sd, "decision": decision}
+
+    def predict(self, observations, deterministic: bool = True):
+        return self.get_safe_action(observations)[0]
 
 
 def ensemble_active_weights(weights, n_members: int, method: str):
