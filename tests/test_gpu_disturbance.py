@@ -11,10 +11,14 @@ import numpy as np
 import pytest
 import torch
 
+import closed_loop_matrix as M
 from test_gpu_ensemble import _bits, _members
 
 pytestmark = pytest.mark.gpu
 
+# Which env brings which kernel shape: tests/closed_loop_matrix.py.  The cases at B = 3000 run the envs the module began with;
+# the *_matrix tests run the disturbed MFMA actor on every env it is compiled for and the disturbed policy kernel (kinds mpc and
+# pid) on all nine, at the matrix's shapes, AdvancedChemicalReactor and AdvancedPowerGrid from per-lane distinct start states.
 B, T, MAXS, SEED = 3000, 14, 9, 0x5EED     # B: a partial last block of both kernels (128-env MLP blocks, 256-lane policy blocks)
 LAUNCHES = (5, 9)                          # two launches for one case
 FILL = -7.0                                # sentinel of the output buffers
@@ -32,8 +36,8 @@ def ni():
 
 def _agent(ni, name, kind):
     """(installer(env), kind, object): "actor" -> MLP weights; the others -> a DevicePolicy."""
-    from neorl_industrial_gym_amd.policies import _DIMS
-    S, A = _DIMS[name]
+    sp = ni._lib.env_spec(ni.batched.ENV_IDS[name])
+    S, A = sp.state_dim, sp.action_dim
     if kind == "actor":
         return _members(ni, name, 1, 500)[0]
     if kind == "mpc":
@@ -55,29 +59,55 @@ def _install(env, kind, agent):
         env.set_policy(agent)
 
 
-def _run(ni, name, kind, agent, dist, autoreset=True, disturbed=True, fill=FILL, launches=LAUNCHES):
-    env = ni.make_batched(name, B, autoreset=autoreset, tally=True, max_episode_steps=MAXS, seed=SEED)
+# The shape of a run: the module's own, and the closed-loop matrix's two (tests/closed_loop_matrix.py), which start the two envs
+# whose reset is the same for every lane from per-lane distinct states
+OWN = dict(B=B, T=T, max_steps=MAXS, launches=LAUNCHES, start=False)
+MATRIX_SHAPE = {b: dict(B=b, T=M.T_NEW, max_steps=M.MAXS_NEW, launches=(3, M.T_NEW - 3), start=True) for b in (M.B_BIG, M.B_SMALL)}
+
+
+def _run(ni, name, kind, agent, dist, autoreset=True, disturbed=True, fill=FILL, launches=None, shape=OWN):
+    B, T = shape["B"], shape["T"]
+    launches = shape["launches"] if launches is None else launches
+    env = ni.make_batched(name, B, autoreset=autoreset, tally=True, max_episode_steps=shape["max_steps"], seed=SEED)
     _install(env, kind, agent)
     if dist is not None:
         env.set_disturbance(dist)
-    dev, S, A = env.device, env.state_dim, env.action_dim
-    act = torch.full((T + 1, A, env.ld), fill, dtype=torch.float32, device=dev)       # (row T: behind the last step)
-    obs = torch.full((T + 1, B, S), fill, dtype=torch.float32, device=dev)
-    seen = torch.full((T + 1, B, S), fill, dtype=torch.float32, device=dev)
-    fl = torch.zeros(T + 1, env.ld, dtype=torch.int32, device=dev)
-    rw = torch.full((T + 1, env.ld), fill, dtype=torch.float32, device=dev)
+    dev, S, A, ld = env.device, env.state_dim, env.action_dim, env.ld
+    # (an observation step is a multiple of 4 floats: where B * S is none, the rows are padded and the C entry points are called
+    # directly -- the Python methods take contiguous [n, B, S] tensors)
+    ostep = (B * S + 3) // 4 * 4
+    act = torch.full((T + 1, A, ld), fill, dtype=torch.float32, device=dev)       # (row T: behind the last step)
+    obs = torch.full((T + 1, ostep), fill, dtype=torch.float32, device=dev)
+    seen = torch.full((T + 1, ostep), fill, dtype=torch.float32, device=dev)
+    fl = torch.zeros(T + 1, ld, dtype=torch.int32, device=dev)
+    rw = torch.full((T + 1, ld), fill, dtype=torch.float32, device=dev)
+    P = lambda t: C.c_void_p(t.data_ptr())
     env.reset()
+    if shape["start"]:
+        M.install_start(ni, env, M.KEY_OF[name], SEED)
     t0, k0 = env.counter, 0
     for n in launches:
-        if disturbed:
-            (env.rollout_mlp_disturbed if kind == "actor" else env.rollout_policy_disturbed)(n, rw[k0:], fl[k0:], obs[k0:], act[k0:], seen[k0:])
+        if ostep != B * S:
+            L = ni._lib.lib()
+            common = (env._h, n, P(rw[k0:]), P(fl[k0:]), ld, P(obs[k0:]), ostep, P(act[k0:]), ld, A * ld)
+            with torch.cuda.device(dev):
+                if disturbed:
+                    fn = L.nig_rollout_mlp_disturbed if kind == "actor" else L.nig_rollout_policy_disturbed
+                    ni._lib.check(fn(*common, P(seen[k0:]), ostep, env._stream()))
+                else:
+                    ni._lib.check((L.nig_rollout_mlp if kind == "actor" else L.nig_rollout_policy)(*common, env._stream()))
+        elif disturbed:
+            (env.rollout_mlp_disturbed if kind == "actor" else env.rollout_policy_disturbed)(n, rw[k0:], fl[k0:], obs[k0:].view(-1, B, S), act[k0:],
+                                                                                             seen[k0:].view(-1, B, S))
         else:
-            (env.rollout_mlp if kind == "actor" else env.rollout_policy)(n, rw[k0:], fl[k0:], obs[k0:], act[k0:])
+            (env.rollout_mlp if kind == "actor" else env.rollout_policy)(n, rw[k0:], fl[k0:], obs[k0:].view(-1, B, S), act[k0:])
         k0 += n
     assert k0 == T
     torch.cuda.synchronize()
     assert env.counter == t0 + T
-    o = dict(act_raw=act.cpu().numpy(), obs_raw=obs.cpu().numpy(), seen_raw=seen.cpu().numpy(), fl_raw=fl.cpu().numpy(), rw_raw=rw.cpu().numpy(),
+    assert bool((obs[:, B * S:] == fill).all()) and bool((seen[:, B * S:] == fill).all()), "the pad words of the observation rows"
+    o = dict(act_raw=act.cpu().numpy(), obs_raw=obs[:, :B * S].reshape(T + 1, B, S).cpu().numpy(), seen_raw=seen[:, :B * S].reshape(T + 1, B, S).cpu().numpy(),
+             fl_raw=fl.cpu().numpy(), rw_raw=rw.cpu().numpy(), B=B, T=T, shape=shape,
              t0=t0, state=env.get_state().cpu().numpy(), ctr=env.ctr.cpu().numpy().copy(), tally=env.tally.cpu().numpy().copy(),
              ep_return=env.ep_return.cpu().numpy().copy(), life=env.life_viol.cpu().numpy().copy())
     o.update(act=o["act_raw"][:T, :, :B].transpose(0, 2, 1), obs=o["obs_raw"][:T], seen=o["seen_raw"][:T], flags=o["fl_raw"][:T, :B],
@@ -104,10 +134,15 @@ def _draw_counter(ni, o, k, hold):
     """td of step k for every lane, rebuilt from the flag words: t for fresh draws, t - step_pre for held ones."""
     t = np.uint32(o["t0"] + k + 1)
     step_pre = ((o["flags"][k].astype(np.uint32) >> ni._lib.FLAG_STEP_SHIFT) & 0xFFFF) - 1
-    return np.full(B, t, dtype=np.uint32) if hold == "step" else (t - step_pre.astype(np.uint32)).astype(np.uint32)
+    return np.full(o["B"], t, dtype=np.uint32) if hold == "step" else (t - step_pre.astype(np.uint32)).astype(np.uint32)
 
 
-SIG = dict(cr=(0.5, 0.2), pg=(0.05, 0.3), ra=(0.02, 0.25), hvac=(0.3, 0.2))       # (unit of the env's states, of its actions)
+# (unit of the env's states, of its actions).  The envs the matrix adds: AdvancedChemicalReactor's temperatures are
+# ChemicalReactor's, AdvancedPowerGrid's per-unit voltages PowerGrid's; SteelAnnealing's zone temperatures are of the order of 700,
+# SupplyChain's stocks of 100 beside rates of 4 and fractions of 0.5, WaterTreatment's pH 7 beside fractions of 0.5; every policy
+# commands nominal actions in [-1, 1].
+SIG = dict(cr=(0.5, 0.2), pg=(0.05, 0.3), ra=(0.02, 0.25), hvac=(0.3, 0.2),
+           acr=(0.5, 0.2), apg=(0.05, 0.3), steel=(1.0, 0.2), supply=(0.3, 0.2), water=(0.2, 0.2))
 
 
 def _dist(ni, key, S, A, hold, clip=(-0.9, 0.8)):
@@ -121,17 +156,28 @@ def _dist(ni, key, S, A, hold, clip=(-0.9, 0.8)):
 _CACHE = {}
 
 
-def _case(ni, key, name, kind, hold):
-    """One disturbed run per (env, agent, hold), shared by the tests below and left unchanged."""
-    ck = (key, kind, hold)
+def _matrix_agent(ni, key, name, kind):
+    agent = _agent(ni, name, kind)
+    return M.continuing(key, agent) if kind == "actor" else agent
+
+
+def _case(ni, key, name, kind, hold, shape=OWN):
+    """One disturbed run per (env, agent, hold, shape), shared by the tests below and left unchanged."""
+    ck = (key, kind, hold, shape["B"], shape["T"])
     if ck not in _CACHE:
-        agent = _agent(ni, name, kind)
+        agent = _matrix_agent(ni, key, name, kind) if shape["start"] else _agent(ni, name, kind)
         probe = ni.make_batched(name, 1)
         S, A = probe.state_dim, probe.action_dim
         probe.close()
         d = _dist(ni, key, S, A, hold)
-        _CACHE[ck] = (agent, d, _run(ni, name, kind, agent, d))
+        _CACHE[ck] = (agent, d, _run(ni, name, kind, agent, d, shape=shape))
     return _CACHE[ck]
+
+
+# the matrix: the disturbed MFMA actor on every env it is compiled for, the disturbed policy kernel (mpc, pid) on all nine
+MATRIX = [(k, n, "actor") for k, n in M.MFMA_ENVS] + [(k, n, kind) for kind in ("mpc", "pid") for k, n in M.POLICY_ENVS_ALL]
+# (both holds run the same kernel: the larger batch takes the held vector, the smaller one the fresh draws)
+MATRIX_HOLD = {M.B_BIG: "episode", M.B_SMALL: "step"}
 
 
 CASES = [(k, n, "actor") for k, n in ACTOR_ENVS] + [(k, n, kind) for kind in ("mpc", "pid", "behaviour") for k, n in POLICY_ENVS]
@@ -141,10 +187,20 @@ CASES = [(k, n, "actor") for k, n in ACTOR_ENVS] + [(k, n, kind) for kind in ("m
 @pytest.mark.parametrize("autoreset", [False, True], ids=["frozen", "autoreset"])
 @pytest.mark.parametrize("key,name,kind", CASES + [("ra", "RobotAssembly-v0", "random")])
 def test_zero_is_off(ni, key, name, kind, autoreset):
-    agent = _agent(ni, name, kind)
-    for hold in ("step", "episode"):
-        a = _run(ni, name, kind, agent, ni.Disturbance(hold=hold), autoreset=autoreset)
-        b = _run(ni, name, kind, agent, None, autoreset=autoreset, disturbed=False)
+    _zero_is_off(ni, name, kind, _agent(ni, name, kind), autoreset, ("step", "episode"), OWN)
+
+
+@pytest.mark.parametrize("B", [M.B_BIG, M.B_SMALL])
+@pytest.mark.parametrize("key,name,kind", MATRIX)
+def test_zero_is_off_matrix(ni, key, name, kind, B):
+    """test_zero_is_off at the closed-loop matrix's shapes: 700 lanes that reset inside the launch, 5 that freeze."""
+    _zero_is_off(ni, name, kind, _matrix_agent(ni, key, name, kind), B == M.B_BIG, (MATRIX_HOLD[B],), MATRIX_SHAPE[B])
+
+
+def _zero_is_off(ni, name, kind, agent, autoreset, holds, shape):
+    for hold in holds:
+        a = _run(ni, name, kind, agent, ni.Disturbance(hold=hold), autoreset=autoreset, shape=shape)
+        b = _run(ni, name, kind, agent, None, autoreset=autoreset, disturbed=False, shape=shape)
         assert a["live"][0].all() and (autoreset or not a["live"][-1].all()), "episodes must end inside the run"
         for f in ("act_raw", "obs_raw", "fl_raw", "rw_raw", "state", "ctr", "tally", "ep_return", "life"):
             assert np.array_equal(_bits(a[f]) if a[f].dtype.kind == "f" else a[f], _bits(b[f]) if b[f].dtype.kind == "f" else b[f]), (hold, f)
@@ -163,7 +219,19 @@ def test_the_draws(ni, oracle, key, name, kind, hold):
         o = _run(ni, name, kind, agent, d)
     else:
         agent, d, o = _case(ni, key, name, kind, hold)
-    L = ni._lib
+    _the_draws(ni, oracle, key, d, o, hold)
+
+
+@pytest.mark.parametrize("B", [M.B_BIG, M.B_SMALL])
+@pytest.mark.parametrize("key,name,kind", MATRIX)
+def test_the_draws_matrix(ni, oracle, key, name, kind, B):
+    """test_the_draws at the closed-loop matrix's shapes."""
+    agent, d, o = _case(ni, key, name, kind, MATRIX_HOLD[B], MATRIX_SHAPE[B])
+    _the_draws(ni, oracle, key, d, o, MATRIX_HOLD[B])
+
+
+def _the_draws(ni, oracle, key, d, o, hold):
+    L, B, T = ni._lib, o["B"], o["T"]
     live = o["live"]
     assert live.all(), "auto-reset handle: every lane is live on every step"
     S = o["obs"].shape[2]
@@ -184,7 +252,10 @@ def test_the_draws(ni, oracle, key, name, kind, hold):
     if hold == "episode":       # the held vector: two consecutive steps of one episode see the same offset draws
         td0, td1 = _draw_counter(ni, o, 0, hold), _draw_counter(ni, o, 1, hold)
         same = (o["flags"][0] & L.FLAG_DID_RESET) == 0
-        assert same.any() and np.all(td0[same] == td1[same]) and np.all(td0[same] == np.uint32(o["t0"] + 1))
+        # (the plant: an AdvancedPowerGrid episode ends whenever a[4] or a[5] is below 0.95, and the disturbance's clip keeps every
+        # action at or below 0.8: each of its lanes resets on every step, so no lane holds a vector for two steps.  What holds for
+        # it is the statement above: every step's offsets are those of a fresh episode, t - 0.)
+        assert same.any() == (key != "apg") and np.all(td0[same] == td1[same]) and np.all(td0[same] == np.uint32(o["t0"] + 1))
 
 
 # ---- 3. the action ----------------------------------------------------------------------------------------------------------
@@ -200,12 +271,28 @@ def test_the_action(ni, oracle, key, name, kind, hold):
     """act_out == clip(policy(seen_out) + sigma_act * za): the policy is the oracle's actor, or the oracle's "nig-policy-v1" law
     at the step's own t (its draws keyed at t whatever the hold) with the PID memory carried from step to step."""
     agent, d, o = _case(ni, key, name, kind, hold)
+    _the_action(ni, oracle, key, kind, agent, d, o, hold)
+
+
+@pytest.mark.parametrize("B", [M.B_BIG, M.B_SMALL])
+@pytest.mark.parametrize("key,name,kind", MATRIX)
+def test_the_action_matrix(ni, oracle, key, name, kind, B):
+    """test_the_action at the closed-loop matrix's shapes.  On step 0 the actor's disturbed action on the envs only these cases
+    reach is also held to the actor in NumPy float64 (the same noise term added, the same clip)."""
+    agent, d, o = _case(ni, key, name, kind, MATRIX_HOLD[B], MATRIX_SHAPE[B])
+    _the_action(ni, oracle, key, kind, agent, d, o, MATRIX_HOLD[B])
+    if B == M.B_BIG and key in M.CLONED:
+        assert M.distinct_rows(o["obs"][0]) >= 600, "step 0: the lanes are no clones of each other"
+
+
+def _the_action(ni, oracle, key, kind, agent, d, o, hold):
+    B, T = o["B"], o["T"]
     S, A = o["obs"].shape[2], o["act"].shape[2]
     _, sig_a = d.sigmas(S, A)
     lo, hi = d.clip
     g = np.arange(B, dtype=np.uint64)
     P = None if kind == "actor" else _policy_struct(oracle, agent)
-    integ, eprev = np.zeros((B, 8), dtype=np.float32), np.zeros((B, 8), dtype=np.float32)
+    integ, eprev = np.zeros((B, 12), dtype=np.float32), np.zeros((B, 12), dtype=np.float32)     # (SupplyChain: 10 actions)
     clipped = 0
     for k in range(T):
         if kind == "actor":
@@ -219,6 +306,9 @@ def test_the_action(ni, oracle, key, name, kind, hold):
         x = np.where(x > hi, hi, x).astype(np.float32)
         clipped += int(((x == lo) | (x == hi)).sum())
         assert np.array_equal(_bits(o["act"][k]), _bits(x)), k
+        if k == 0 and kind == "actor" and o["shape"]["start"] and key in M.FLOAT64_KEYS:
+            x64 = np.clip(M.actor64(agent, o["seen"][0]) + (sig_a[None, :] * za).astype(np.float32), lo, hi)
+            assert M.worst(f"{key} B={B}: the disturbed action of step 0 against float64", o["act"][0], x64, M.ACT_ATOL) <= 1.0
     assert 0 < clipped < B * T * A, "the disturbance's clip must bind on some actions and not on others"
 
 
@@ -229,17 +319,32 @@ def test_the_plant_received_it(ni, key, name, kind):
     rows (rollout's row k is the state after step k: the disturbed run's row k + 1 where the episode goes on) and the final
     state, counters and tallies are the disturbed run's."""
     _, _, o = _case(ni, key, name, kind, "step")
-    L = ni._lib
-    env = ni.make_batched(name, B, autoreset=True, tally=True, max_episode_steps=MAXS, seed=SEED)
-    dev = env.device
+    _the_plant_received_it(ni, key, name, o)
+
+
+@pytest.mark.parametrize("B", [M.B_BIG, M.B_SMALL])
+@pytest.mark.parametrize("key,name,kind", MATRIX)
+def test_the_plant_received_it_matrix(ni, key, name, kind, B):
+    """test_the_plant_received_it at the closed-loop matrix's shapes."""
+    _, _, o = _case(ni, key, name, kind, MATRIX_HOLD[B], MATRIX_SHAPE[B])
+    _the_plant_received_it(ni, key, name, o)
+
+
+def _the_plant_received_it(ni, key, name, o):
+    L, B, T, shape = ni._lib, o["B"], o["T"], o["shape"]
+    env = ni.make_batched(name, B, autoreset=True, tally=True, max_episode_steps=shape["max_steps"], seed=SEED)
+    dev, S = env.device, env.state_dim
     ring = torch.from_numpy(np.ascontiguousarray(o["act_raw"][:T])).to(dev)
     rw = torch.zeros(T, env.ld, dtype=torch.float32, device=dev)
     fl = torch.zeros(T, env.ld, dtype=torch.int32, device=dev)
-    obs = torch.zeros(T, B, env.state_dim, dtype=torch.float32, device=dev)
+    ostep = (B * S + 3) // 4 * 4                    # (an observation step is a multiple of 4 floats)
+    obs = torch.zeros(T, ostep, dtype=torch.float32, device=dev).as_strided((T, B, S), (ostep, S, 1))
     env.reset()
+    if shape["start"]:
+        M.install_start(ni, env, key, SEED)
     assert env.counter == o["t0"]
     k0 = 0
-    for n in LAUNCHES:      # the same launches: a launch adds the episodes that ended in it to the tally as one fp64 partial
+    for n in shape["launches"]:      # the same launches: a launch adds the episodes that ended in it to the tally as one fp64 partial
         env.rollout(n, ring[k0:], rw[k0:], fl[k0:], obs[k0:])
         k0 += n
     torch.cuda.synchronize()
@@ -247,7 +352,9 @@ def test_the_plant_received_it(ni, key, name, kind):
     assert np.array_equal(fl[:, :B].cpu().numpy(), o["flags"])
     nxt = obs.cpu().numpy()
     cont = (o["flags"][:T - 1] & (L.FLAG_TERMINATED | L.FLAG_TRUNCATED | L.FLAG_DID_RESET)) == 0
-    assert cont.sum() > B
+    # (the plant: under the disturbance's clip at 0.8 every AdvancedPowerGrid episode ends on its first step -- a[4], a[5] < 0.95 --
+    # so none of its lanes goes on; rewards, flags, final state, counters and tallies below still are the ring rollout's)
+    assert cont.sum() > B if key != "apg" else cont.sum() == 0
     assert np.array_equal(_bits(nxt[:T - 1])[cont], _bits(o["obs"][1:])[cont])
     assert np.array_equal(_bits(env.get_state().cpu().numpy()), _bits(o["state"]))
     assert np.array_equal(env.ctr.cpu().numpy(), o["ctr"]) and np.array_equal(env.life_viol.cpu().numpy(), o["life"])

@@ -13,10 +13,15 @@ import numpy as np
 import pytest
 import torch
 
+import closed_loop_matrix as M
 from footprint import Arena, Layout
 from test_gpu_footprint import Rig, ceil4, clean, gap, pitch
 
 pytestmark = pytest.mark.gpu
+
+# Which env brings which kernel shape: tests/closed_loop_matrix.py.  The cases at B = 3000 below run the five envs the module
+# began with from reset(); the *_matrix tests run every env the family is compiled for (the average and the voting kernel of
+# each) at the matrix's shapes, AdvancedChemicalReactor and AdvancedPowerGrid from per-lane distinct start states.
 
 ENVS = [("cr", "ChemicalReactor-v0"), ("pg", "PowerGrid-v0"), ("ra", "RobotAssembly-v0"),
         ("acr", "AdvancedChemicalReactor-v0"), ("hvac", "HVACControl-v0")]
@@ -81,28 +86,40 @@ def _install(ni, env, members, method, w, thr):
     return aw
 
 
-def _run(ni, name, members, method, w, thr, B=B, T=T, autoreset=True, env_index0=0, launches=None, fill=0.0, max_steps=MAXS):
+def _run(ni, name, members, method, w, thr, B=B, T=T, autoreset=True, env_index0=0, launches=None, fill=0.0, max_steps=MAXS, start=False):
+    """start: give the lanes of an env whose reset is the same for every lane distinct start states (closed_loop_matrix)."""
     K = len(members)
     env = ni.make_batched(name, B, autoreset=autoreset, tally=True, max_episode_steps=max_steps, env_index0=env_index0, seed=SEED)
     _install(ni, env, members, method, w, thr)
     dev = env.device
     act = torch.full((T, env.action_dim, env.ld), fill, dtype=torch.float32, device=dev)
     mem = torch.full((T, K, env.action_dim, env.ld), fill, dtype=torch.float32, device=dev)
-    obs = torch.full((T, B, env.state_dim), fill, dtype=torch.float32, device=dev)
+    # (an observation step is a multiple of 4 floats: where B * S is none, the rows are padded and the C entry point is called
+    # directly -- the Python method takes a contiguous [n, B, S] tensor)
+    S, ostep = env.state_dim, (B * env.state_dim + 3) // 4 * 4
+    obs = torch.full((T, ostep), fill, dtype=torch.float32, device=dev)
     fl = torch.zeros(T, env.ld, dtype=torch.int32, device=dev)
     rw = torch.zeros(T, env.ld, dtype=torch.float32, device=dev)
     un = torch.full((T, env.ld), fill, dtype=torch.float32, device=dev)
+    P = lambda t: C.c_void_p(t.data_ptr())
     env.reset()
+    if start:
+        M.install_start(ni, env, M.KEY_OF[name], SEED)
     t0 = env.counter
     k0 = 0
     for n in (launches or (T,)):
-        env.rollout_mlp_ensemble(n, rw[k0:], fl[k0:], obs[k0:], act[k0:], un[k0:], mem[k0:])
+        if ostep != B * S:
+            with torch.cuda.device(dev):
+                ni._lib.check(ni._lib.lib().nig_rollout_mlp_ensemble(env._h, n, P(rw[k0:]), P(fl[k0:]), env.ld, P(obs[k0:]), ostep, P(act[k0:]), env.ld,
+                                                                     env.action_dim * env.ld, P(un[k0:]), P(mem[k0:]), env._stream()))
+        else:
+            env.rollout_mlp_ensemble(n, rw[k0:], fl[k0:], obs[k0:].view(-1, B, S), act[k0:], un[k0:], mem[k0:])
         k0 += n
     assert k0 == T
     torch.cuda.synchronize()
     assert env.counter == t0 + T
     out = dict(act=act[:, :, :B].permute(0, 2, 1).cpu().numpy(), mem=mem[:, :, :, :B].permute(0, 1, 3, 2).cpu().numpy(),
-               obs=obs.cpu().numpy(), flags=fl[:, :B].cpu().numpy(), rew=rw[:, :B].cpu().numpy(), unc=un[:, :B].cpu().numpy(), t0=t0)
+               obs=obs[:, :B * S].reshape(T, B, S).cpu().numpy(), flags=fl[:, :B].cpu().numpy(), rew=rw[:, :B].cpu().numpy(), unc=un[:, :B].cpu().numpy(), t0=t0)
     out["live"] = (out["flags"] & ni._lib.FLAG_INACTIVE) == 0
     out["uncertain"] = (out["flags"] & ni._lib.FLAG_UNCERTAIN) != 0
     return env, out
@@ -126,15 +143,43 @@ def test_members_action_and_uncertainty(ni, oracle, key, name, autoreset, method
     """Every member's action is the oracle's single actor on the recorded observation; act_out is the documented law on the
     recorded member actions; unc_out is the documented order bit for bit and np.std(...).mean(-1) to the parity bar; the flag
     is unc_out > threshold with the threshold at the median of a first run's uncertainties (both branches taken)."""
+    _members_action_and_uncertainty(ni, oracle, key, name, autoreset, method, w, dict(B=B, T=T, max_steps=MAXS))
+
+
+# the matrix's cases: both batch sizes, both kernels (average, voting), lanes that freeze and lanes that reset
+MATRIX_CASES = [(M.B_BIG, True, LAWS[0]), (M.B_BIG, False, LAWS[2]), (M.B_BIG, True, LAWS[1]), (M.B_SMALL, False, LAWS[0]), (M.B_SMALL, True, LAWS[2])]
+MATRIX_IDS = [f"{b}-{'autoreset' if ar else 'frozen'}-{law[0]}" for b, ar, law in MATRIX_CASES]
+
+
+def _matrix_members(ni, key, name, K, seed0):
+    return [M.continuing(key, m) for m in _members(ni, name, K, seed0)]
+
+
+@pytest.mark.parametrize("B,autoreset,law", MATRIX_CASES, ids=MATRIX_IDS)
+@pytest.mark.parametrize("key,name", M.MFMA_ENVS)
+def test_members_action_and_uncertainty_matrix(ni, oracle, key, name, B, autoreset, law):
+    """test_members_action_and_uncertainty on every MFMA env at the closed-loop matrix's shapes; on step 0 the member actions of
+    the envs only these cases reach are also held to the actor in NumPy float64."""
+    _members_action_and_uncertainty(ni, oracle, key, name, autoreset, law[0], law[1], dict(B=B, T=M.T_NEW, max_steps=M.MAXS_NEW, start=True))
+
+
+def _members_action_and_uncertainty(ni, oracle, key, name, autoreset, method, w, shape):
     S, A = _dims(ni, name)
+    T, start = shape["T"], shape.get("start", False)
     K = 3 if method != "voting" else 5
-    ms = _members(ni, name, K, 100)
-    env0, o0 = _run(ni, name, ms, method, w, 0.2, autoreset=autoreset)
+    ms = _matrix_members(ni, key, name, K, 100) if start else _members(ni, name, K, 100)
+    env0, o0 = _run(ni, name, ms, method, w, 0.2, autoreset=autoreset, **shape)
     env0.close()
     thr = float(np.median(o0["unc"][o0["live"]]))
-    env, o = _run(ni, name, ms, method, w, thr, autoreset=autoreset, fill=-7.0)
+    env, o = _run(ni, name, ms, method, w, thr, autoreset=autoreset, fill=-7.0, **shape)
     live = o["live"]
     assert live[0].all() and (autoreset or not live[-1].all()), "episodes must end inside the run"
+    if start and key in M.FLOAT64_KEYS:
+        for m in range(K):
+            assert M.worst(f"{key} {method} B={shape['B']}: member {m}'s actions of step 0 against float64", o["mem"][0, m],
+                           M.actor64(ms[m], o["obs"][0]), M.ACT_ATOL) <= 1.0
+    if start and key in M.CLONED and shape["B"] == M.B_BIG:
+        assert M.distinct_rows(o["mem"][0, 0]) >= 600 and M.distinct_rows(o["act"][0]) >= 600, "step 0: the lanes are no clones of each other"
     for k in range(T):
         for m in range(K):
             want = oracle.mlp_actions(key, ms[m], o["obs"][k])
@@ -169,10 +214,22 @@ def test_the_step_took_that_action(ni, key, name, autoreset, method, w):
     obs_out[k + 1] bit for bit on lanes that did not finish; reward and flag word (without NIG_FLAG_UNCERTAIN) are the rollout's
     on every live lane.  Where the float64 step applies, a third handle stepping on the float32-rounded action must differ
     from it in some state word -- otherwise this test could not tell the two instantiations apart."""
+    _the_step_took_that_action(ni, key, name, autoreset, method, w, dict(B=B, T=T, max_steps=MAXS))
+
+
+@pytest.mark.parametrize("B,autoreset,law", MATRIX_CASES, ids=MATRIX_IDS)
+@pytest.mark.parametrize("key,name", M.MFMA_ENVS)
+def test_the_step_took_that_action_matrix(ni, key, name, B, autoreset, law):
+    """test_the_step_took_that_action on every MFMA env at the closed-loop matrix's shapes."""
+    _the_step_took_that_action(ni, key, name, autoreset, law[0], law[1], dict(B=B, T=M.T_NEW, max_steps=M.MAXS_NEW, start=True))
+
+
+def _the_step_took_that_action(ni, key, name, autoreset, method, w, shape):
     S, A = _dims(ni, name)
-    ms = _members(ni, name, 3, 200)
+    B, T, MAXS, start = shape["B"], shape["T"], shape["max_steps"], shape.get("start", False)
+    ms = _matrix_members(ni, key, name, 3, 200) if start else _members(ni, name, 3, 200)
     L = ni._lib
-    env, o = _run(ni, name, ms, method, w, 0.2, autoreset=autoreset)
+    env, o = _run(ni, name, ms, method, w, 0.2, autoreset=autoreset, **shape)
     env.close()
     act, _, _ = _law(o, method, w)
     f64 = method != "voting" and key in ACT64
@@ -204,7 +261,9 @@ def test_the_step_took_that_action(ni, key, name, autoreset, method, w):
         assert np.array_equal((fl & ~L.FLAG_UNCERTAIN)[live[k]], f2[live[k]]), k
         if f64:
             differ += int((_bits(res[1][0])[cont] != _bits(nxt)[cont]).any(axis=1).sum())
-    assert checked > B
+    # (more than one compared step per lane on average; five lanes of a plant whose episodes may end on their first steps --
+    # RobotAssembly leaves its workspace -- need not reach that: there the loop must have compared something)
+    assert checked > (B if B > 100 else 0)
     if f64:
         print(f"{key} {method}: lane-steps on which the float32 and the float64 step differ: {differ} of {checked}")
         assert differ > 0, "no lane tells the float64 step from the float32 one"
@@ -218,15 +277,31 @@ def test_the_step_took_that_action(ni, key, name, autoreset, method, w):
 def test_one_voting_member_is_the_single_actor(ni, oracle, key, name, autoreset):
     """K = 1, VOTING: actions, flags, rewards, final state, counters and tallies bit for bit nig_rollout_mlp's with that actor
     (and the oracle's rollout), uncertainty exactly 0, and no UNCERTAIN bit at threshold 0 (0 > 0 is false)."""
+    _one_voting_member_is_the_single_actor(ni, oracle, key, name, autoreset, dict(B=B, T=T, max_steps=MAXS))
+
+
+@pytest.mark.parametrize("B,autoreset", [(M.B_BIG, True), (M.B_BIG, False), (M.B_SMALL, True)])
+@pytest.mark.parametrize("key,name", M.MFMA_ENVS)
+def test_one_voting_member_is_the_single_actor_matrix(ni, oracle, key, name, B, autoreset):
+    """test_one_voting_member_is_the_single_actor on every MFMA env at the closed-loop matrix's shapes.  The oracle's own rollout
+    starts from reset(); from the distinct start states of the two Advanced envs the oracle's actor on every recorded observation
+    and its env step on every recorded action take its place."""
+    _one_voting_member_is_the_single_actor(ni, oracle, key, name, autoreset, dict(B=B, T=M.T_NEW, max_steps=M.MAXS_NEW, start=True))
+
+
+def _one_voting_member_is_the_single_actor(ni, oracle, key, name, autoreset, shape):
     S, A = _dims(ni, name)
-    ws = _members(ni, name, 1, 301)[0]
-    env, o = _run(ni, name, [ws], "voting", None, 0.0, autoreset=autoreset)
+    B, T, MAXS, start = shape["B"], shape["T"], shape["max_steps"], shape.get("start", False)
+    ws = _matrix_members(ni, key, name, 1, 301)[0] if start else _members(ni, name, 1, 301)[0]
+    env, o = _run(ni, name, [ws], "voting", None, 0.0, autoreset=autoreset, **shape)
     ref = ni.make_batched(name, B, autoreset=autoreset, tally=True, max_episode_steps=MAXS, seed=SEED)
     ref.set_mlp_policy(ws)
     act = torch.zeros(T, A, ref.ld, dtype=torch.float32, device=ref.device)
     fl = torch.zeros(T, ref.ld, dtype=torch.int32, device=ref.device)
     rw = torch.zeros(T, ref.ld, dtype=torch.float32, device=ref.device)
     ref.reset()
+    if start:
+        M.install_start(ni, ref, key, SEED)
     ref.rollout_mlp(T, rw, fl, None, act)
     torch.cuda.synchronize()
     live = o["live"]
@@ -236,10 +311,19 @@ def test_one_voting_member_is_the_single_actor(ni, oracle, key, name, autoreset)
     for a, b in ((env.get_state(), ref.get_state()), (env.ctr, ref.ctr), (env.life_viol, ref.life_viol), (env.tally, ref.tally),
                  (env.ep_return, ref.ep_return)):
         assert torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8))
-    r = oracle.rollout_mlp(key, B, T, ws, max_steps=MAXS, autoreset=autoreset, nthreads=8, trajectories=True)
-    assert np.array_equal(_bits(o["act"])[live], _bits(r["act"])[live])
-    assert np.array_equal(_bits(env.get_state().cpu().numpy()), _bits(r["state"]))
-    assert np.array_equal(env.current_step.cpu().numpy(), r["step"]) and np.array_equal(env.done.cpu().numpy(), r["done"] != 0)
+    if start and key in M.CLONED:
+        for k in range(T):
+            assert np.array_equal(_bits(o["act"][k])[live[k]], _bits(oracle.mlp_actions(key, ws, o["obs"][k]))[live[k]]), k
+        assert M.check_env_steps(oracle, ni._lib, key, o["obs"], o["act"], o["flags"], SEED, MAXS) > 0
+        if B == M.B_BIG:
+            assert M.distinct_rows(o["act"][0]) >= 600, "step 0: the lanes are no clones of each other"
+    else:
+        r = oracle.rollout_mlp(key, B, T, ws, max_steps=MAXS, autoreset=autoreset, nthreads=8, trajectories=True)
+        assert np.array_equal(_bits(o["act"])[live], _bits(r["act"])[live])
+        assert np.array_equal(_bits(env.get_state().cpu().numpy()), _bits(r["state"]))
+        assert np.array_equal(env.current_step.cpu().numpy(), r["step"]) and np.array_equal(env.done.cpu().numpy(), r["done"] != 0)
+    if start and key in M.FLOAT64_KEYS:
+        assert M.worst(f"{key} B={B}: the voting member's actions of step 0 against float64", o["act"][0], M.actor64(ws, o["obs"][0]), M.ACT_ATOL) <= 1.0
     assert np.all(o["unc"][live] == 0.0) and not o["uncertain"].any()
     env.close(); ref.close()
 

@@ -11,13 +11,18 @@ import numpy as np
 import pytest
 import torch
 
+import closed_loop_matrix as M
 from footprint import Arena, Layout
 
 pytestmark = pytest.mark.gpu
 
 # ChemicalReactor: A = 3, 4x4x1 head, one-chunk critic layer 1; PowerGrid: A = 8, 16x16x1 head, two-chunk critic layer 1;
-# RobotAssembly: A = 7, a candidate spans two generator blocks with an unused word; HVACControl: a build-specified plant
-ENVS = [("cr", "ChemicalReactor-v0"), ("pg", "PowerGrid-v0"), ("ra", "RobotAssembly-v0"), ("hvac", "HVACControl-v0")]
+# RobotAssembly: A = 7, a candidate spans two generator blocks with an unused word; HVACControl: a build-specified plant;
+# SteelAnnealing and AdvancedChemicalReactor: A = 6, an even one-chunk critic layer 1 (width 26, no zero-padded k-step);
+# SupplyChain: A = 10, head rows 8 and 9 from the third source-lane group, a candidate spans three generator blocks, critic
+# width 38 (two chunks, 20 records, no padding record); AdvancedPowerGrid: PowerGrid's shapes.  The two Advanced envs draw
+# nothing, so their lanes start from closed_loop_matrix.start_states (from reset() they would all be clones).
+ENVS = M.MFMA_ENVS                                 # every env the family is compiled for (tests/closed_loop_matrix.py)
 T, MAXS, SEED = 7, 5, 0x5EED
 SHAPES = [(700, 5), (5, 1)]                        # (B, n_candidates)
 f32 = np.float32
@@ -66,6 +71,8 @@ def _run(ni, name, autoreset, ws, cw, thr, N, B, entry="search", env_index0=0, t
     ch = torch.zeros(n, env.ld, dtype=torch.int32, device=dev)
     env.counter = t0
     env.reset()
+    assert env_index0 == 0 or M.KEY_OF[name] not in M.CLONED
+    M.install_start(ni, env, M.KEY_OF[name], SEED)
     k = 0
     for m in cuts:
         s = slice(k, k + m)
@@ -127,7 +134,7 @@ def _nets(ni, key, name):
     probe = ni.make_batched(name, 1)
     S, A = probe.state_dim, probe.action_dim
     probe.close()
-    ws, cw = _random_actor(S, A, 31), _random_critic(S, A, 32)
+    ws, cw = M.matrix_actor(ni, key, _random_actor(S, A, 31), SEED), _random_critic(S, A, 32)
     env, o = _run(ni, name, True, ws, cw, 2.0, 1, 700, entry="safe")
     env.close()
     sc = (1.0 / (1.0 + np.abs(o["obs"][o["live"]]).mean(axis=0))).astype(f32)
@@ -159,6 +166,12 @@ def _check_law(ni, oracle, key, o, ws, cw, thr, N, candidates_only=False):
         raw = oracle.mlp_actions(key, ws, o["obs"][k])
         p0 = oracle.mlp_critic(key, cw, o["obs"][k], raw)
         assert np.array_equal(_bits(o["prob"][k])[lv], _bits(p0)[lv]), (k, "prob")
+        if k == 0 and key in M.FLOAT64_KEYS:       # the shapes only these envs bring, against the networks in NumPy float64
+            raw64 = M.actor64(ws, o["obs"][0])
+            assert M.worst(f"{key} B={B}: the actor's action of step 0 against float64", raw, raw64, M.ACT_ATOL) <= 1.0
+            assert M.worst(f"{key} B={B}: prob of step 0 against float64", o["prob"][0], M.critic64(cw, o["obs"][0], raw64), M.PROB_ATOL) <= 1.0
+            if not candidates_only:
+                assert M.worst(f"{key} B={B}: risk of step 0 against float64", o["risk"][0], M.critic64(cw, o["obs"][0], o["act"][0]), M.PROB_ATOL) <= 1.0
         with np.errstate(invalid="ignore"):
             want = lv & ~(p0 < thr)
         searched[k] = want
@@ -228,7 +241,16 @@ def test_always_search_takes_the_first_least_risky_candidate(ni, oracle, key, na
         cont = live[k, :n] & live[k + 1, :n] & ((fl & (L.FLAG_TERMINATED | L.FLAG_TRUNCATED | L.FLAG_DID_RESET)) == 0)
         checked += int(cont.sum())
         assert np.array_equal(_bits(o["obs"][k + 1, :n][cont]), _bits(r["state_next"][cont])), k
-    assert checked > 0                                                  # (the loop compared something)
+    if key == "apg":
+        # the plant: an AdvancedPowerGrid episode ends whenever a[4] or a[5] is below 0.95, which a uniform candidate of [-1, 1)
+        # almost always is, so (almost) no searched lane continues.  What holds instead: every live step's TERMINATED bit is the
+        # oracle's on that candidate, and step 0 -- the only step whose lanes are distinct -- is checked above lane by lane
+        M.check_env_steps(oracle, L, key, o["obs"], o["act"], o["flags"], SEED, MAXS)
+        assert ((o["flags"][0] & L.FLAG_TERMINATED) != 0).mean() > 0.9
+    else:
+        assert checked > 0                                              # (the loop compared something)
+    if B > 100 and key in M.CLONED:
+        assert M.distinct_rows(oracle.mlp_actions(key, ws, o["obs"][0])) >= 600, "step 0: the lanes are no clones of each other"
 
 
 # ---- 3 ---------------------------------------------------------------------------------------------------------------------

@@ -5,15 +5,17 @@ import numpy as np
 import pytest
 import torch
 
+import closed_loop_matrix as M
+
 pytestmark = pytest.mark.gpu
 
-ENVS = [("cr", "ChemicalReactor-v0"), ("pg", "PowerGrid-v0"), ("ra", "RobotAssembly-v0"),
-        ("acr", "AdvancedChemicalReactor-v0"), ("apg", "AdvancedPowerGrid-v0"), ("hvac", "HVACControl-v0"),
-        ("steel", "SteelAnnealing-v0"), ("supply", "SupplyChain-v0")]
+ENVS = M.MFMA_ENVS        # which env brings which kernel shape: tests/closed_loop_matrix.py
 # AdvancedPowerGrid resets every lane to the same state, draws no noise, and ends an episode whenever a voltage set-point
 # action (a[4], a[5]) lies below 0.95 -- which a halved tanh output always does.  So its lanes never spread p and never
 # continue an always-halved episode: the two tests that need that take the envs below, and
-# test_always_shield_ends_advanced_power_grid_episodes_like_the_oracle covers its always-shield case.
+# test_always_shield_ends_advanced_power_grid_episodes_like_the_oracle covers its always-shield case.  AdvancedChemicalReactor
+# resets every lane to one state too.  test_shield_matrix below runs both from per-lane distinct start states (never, always and
+# mixed), so that a p or an action row that reaches the wrong lane shows.
 ENVS_SPREAD = [e for e in ENVS if e[0] != "apg"]
 B, T, MAXS, SEED = 3000, 14, 9, 0x5EED        # B not a multiple of 128: a partial last block
 
@@ -186,6 +188,96 @@ def test_mixed_shield_decisions(ni, oracle, key, name, autoreset):
     frac = sh[live].mean()
     assert 0.1 <= frac <= 0.9, frac
     env.close()
+
+
+# ---- the closed-loop matrix's shapes (tests/closed_loop_matrix.py) ------------------------------------------------------------
+def _run_matrix(ni, key, autoreset, ws, cw, thr, B):
+    """rollout_mlp_safe at the matrix's T and episode cap through the C entry point (observation rows padded to a multiple of 4
+    floats where B * S is none); AdvancedChemicalReactor and AdvancedPowerGrid start from per-lane distinct states."""
+    import ctypes as C
+    T_, name = M.T_NEW, M.NAMES[key]
+    env = ni.make_batched(name, B, autoreset=autoreset, tally=True, max_episode_steps=M.MAXS_NEW, seed=SEED)
+    env.set_mlp_policy(ws)
+    env.set_mlp_safety(cw, thr)
+    dev, S, A, ld = env.device, env.state_dim, env.action_dim, env.ld
+    ostep = (B * S + 3) // 4 * 4
+    act = torch.zeros(T_, A, ld, dtype=torch.float32, device=dev)
+    obs = torch.zeros(T_, ostep, dtype=torch.float32, device=dev)
+    fl = torch.zeros(T_, ld, dtype=torch.int32, device=dev)
+    rw, pr = (torch.zeros(T_, ld, dtype=torch.float32, device=dev) for _ in range(2))
+    env.reset()
+    M.install_start(ni, env, key, SEED)
+    p = lambda x: C.c_void_p(x.data_ptr())
+    with torch.cuda.device(dev):
+        ni._lib.check(ni._lib.lib().nig_rollout_mlp_safe(env._h, T_, p(rw), p(fl), ld, p(obs), ostep, p(act), ld, A * ld, p(pr), env._stream()))
+    torch.cuda.synchronize()
+    o = dict(act=act[:, :, :B].permute(0, 2, 1).cpu().numpy(), obs=obs[:, :B * S].reshape(T_, B, S).cpu().numpy(), flags=fl[:, :B].cpu().numpy(),
+             prob=pr[:, :B].cpu().numpy())
+    o["live"] = (o["flags"] & ni._lib.FLAG_INACTIVE) == 0
+    o["shielded"] = (o["flags"] & ni._lib.FLAG_SHIELDED) != 0
+    env.close()
+    return o
+
+
+_MATRIX_NETS = {}
+
+
+def _matrix_nets(ni, key):
+    """(actor, critic whose state rows are scaled by the observed magnitudes so that p spreads, the median of step 0's p over
+    700 lanes)."""
+    if key not in _MATRIX_NETS:
+        probe = ni.make_batched(M.NAMES[key], 1)
+        S, A = probe.state_dim, probe.action_dim
+        probe.close()
+        ws, cw = M.matrix_actor(ni, key, _random_actor(S, A, 31), SEED), _random_critic(S, A, 32)
+        sc = M.state_scale(ni, key, SEED)
+        cw = [(np.concatenate([cw[0][0][:S] * np.float32(20.0) * sc[:, None], cw[0][0][S:]]).astype(np.float32), cw[0][1]), cw[1], cw[2]]
+        p0 = _run_matrix(ni, key, True, ws, cw, 2.0, M.B_BIG)["prob"][0]
+        assert len(np.unique(p0)) > 350, "the critic does not spread p over the lanes"
+        _MATRIX_NETS[key] = (ws, cw, float(np.median(p0)))
+    return _MATRIX_NETS[key]
+
+
+@pytest.mark.parametrize("mode", ["never", "always", "mixed"])
+@pytest.mark.parametrize("B,autoreset", [(M.B_BIG, True), (M.B_BIG, False), (M.B_SMALL, True)])
+@pytest.mark.parametrize("key,name", M.MFMA_ENVS)
+def test_shield_matrix(ni, oracle, key, name, B, autoreset, mode):
+    """The shield on every MFMA env at the matrix's shapes, on the device's own obs_out: p is oracle.mlp_critic of the oracle's
+    raw action, bit for bit; the action is the raw action where p < threshold and 0.5 x it elsewhere, with the flag; the next
+    observation is the oracle's step on that action.  AdvancedChemicalReactor and AdvancedPowerGrid start from per-lane distinct
+    states (from reset() their lanes are clones: a p or an action row stored to the wrong lane would pass).  Step 0 is also held
+    to the actor and the critic in NumPy float64."""
+    ws, cw, median = _matrix_nets(ni, key)
+    thr = {"never": 2.0, "always": 0.0, "mixed": median}[mode]
+    o = _run_matrix(ni, key, autoreset, ws, cw, thr, B)
+    live, sh = o["live"], o["shielded"]
+    assert live[0].all() and (autoreset or not live[-1].any())
+    for k in range(M.T_NEW):
+        lv = live[k]
+        raw = oracle.mlp_actions(key, ws, o["obs"][k])
+        pk = oracle.mlp_critic(key, cw, o["obs"][k], raw)
+        assert np.array_equal(o["prob"][k].view(np.uint32)[lv], pk.view(np.uint32)[lv]), k
+        want_sh = lv & ~(pk < np.float32(thr))
+        assert np.array_equal(sh[k], want_sh), k
+        want = np.where(want_sh[:, None], raw * np.float32(0.5), raw).astype(np.float32)
+        assert np.array_equal(o["act"][k].view(np.uint32)[lv], want.view(np.uint32)[lv]), k
+    checked = M.check_env_steps(oracle, ni._lib, key, o["obs"], o["act"], o["flags"], SEED, M.MAXS_NEW)
+    if key == "apg" and mode == "always":
+        # the plant: a halved set-point action is below 0.95, so every AdvancedPowerGrid episode ends on its first step (the
+        # oracle agrees, check_env_steps) and no lane ever continues
+        assert checked == 0 and ((o["flags"] & ni._lib.FLAG_TERMINATED) != 0)[live].all()
+    elif key != "apg" or B == M.B_BIG:
+        assert checked > 0
+    raw0 = M.actor64(ws, o["obs"][0])
+    if B == M.B_BIG:
+        assert key not in M.CLONED or M.distinct_rows(o["act"][0]) >= 600, M.distinct_rows(o["act"][0])
+        if mode == "mixed":
+            assert sh[0].any() and not sh[0].all()
+    if key not in M.FLOAT64_KEYS:
+        return
+    scale = np.where(sh[0][:, None], 0.5, 1.0)
+    assert M.worst(f"{key} {mode} B={B}: actions of step 0 against float64", o["act"][0], raw0 * scale, M.ACT_ATOL) <= 1.0
+    assert M.worst(f"{key} {mode} B={B}: p of step 0 against float64", o["prob"][0], M.critic64(cw, o["obs"][0], raw0), M.PROB_ATOL) <= 1.0
 
 
 def _spread_critic(ni, name, autoreset, ws, cw, S):
