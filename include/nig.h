@@ -81,7 +81,7 @@ extern "C" {
 #define NIG_FLAG_INACTIVE 0x800u        /* lane was already done (no auto-reset): untouched  */
 #define NIG_FLAG_VIOL3 0x1000u          /* 4th safety condition violated (Advanced envs)     */
 #define NIG_FLAG_NVIOL_HI 0x2000u       /* adds 4 to the violation count field (Advanced envs) */
-#define NIG_FLAG_SHIELDED 0x4000u       /* nig_rollout_mlp_safe: the safety critic halved the action (nig_rollout_mlp_search: replaced it; nig_rollout_mlp_gated: the gate replaced it by zero) */
+#define NIG_FLAG_SHIELDED 0x4000u       /* nig_rollout_mlp_safe: the safety critic halved the action (nig_rollout_mlp_search: replaced it; nig_rollout_mlp_gated: the gate replaced it by zero; nig_rollout_mlp_projected: the lane was projected) */
 #define NIG_FLAG_UNCERTAIN 0x8000u      /* nig_rollout_mlp_ensemble: uncertainty > threshold on this live step (nig_rollout_mlp_gated: some sd[c] is not below the spread limit) */
 #define NIG_FLAG_STEP_SHIFT 16          /* bits 16-31: current_step after this call          */
 
@@ -651,6 +651,62 @@ int nig_rollout_mlp_gated(nig_handle *h, int32_t n_steps, float *reward_out, uin
                           float *logit_out, int64_t ld_c, int64_t c_step_stride, void *stream);
 
 /*
+ * Constraint projection of the reference's ConstrainedIQLAgent.get_safe_action (agents/safety_critical.py:240-370),
+ * fused into the shield's kernel: a constraint predictor f(s, a) with one head row per constraint scores the actor's
+ * action; where some violation probability is not below the threshold, the action walks down the gradient of the
+ * summed positive logits until every logit is below the tolerance or the steps run out.  The predictor is a
+ * (S + A) -> 256 -> 256 -> C ReLU MLP in nig_set_mlp_safety_ensemble's member layouts (C3 [hidden][n_outputs],
+ * c3 [n_outputs]); hidden must be 256 (policies.pad_safety_member pads the reference's 128-wide predictor).
+ * The law, "nig-project-v1".  Installed: C = n_outputs, thr = threshold (the reference's uncertainty_threshold),
+ * tol = tolerance (constraint_tolerance); per call max_iters and step (the reference: 10 and 0.1).  All arithmetic is
+ * float32, no product is fused into a sum.  For a live lane on a step:
+ *     a0 = actor(s)                                    bit for bit nig_rollout_mlp's action
+ *     z  = f(s, a0);  p0[c] = det_sigmoidf(z[c])       each row the arithmetic of nig_rollout_mlp_gated's member rows
+ *     if p0[c] < thr for every c < C:                  the env receives a0; iters = -1; viol = p0
+ *     else (projected; NIG_FLAG_SHIELDED):
+ *         a = a0
+ *         for k = 0 .. max_iters-1:                    (z is pass 0's for k = 0)
+ *             if z[c] < tol for every c < C: break     (the raw logits, as the reference: safety_critical.py:352)
+ *             g = dG/da at (s, a),  G(a) = sum_c relu(f_c(s, a))
+ *             a = a - step * g;  a = a < -1 ? -1 : (a > 1 ? 1 : a)        (a NaN stays a NaN)
+ *             z = f(s, a)
+ *         iters = the gradient steps taken (0 .. max_iters);  viol[c] = det_sigmoidf(z[c]) of the action the env receives
+ * The gradient is the analytic backward pass with the derivative of relu at 0 taken as 0 (jax.nn.relu's):
+ *     g = W1[S:S+A, :] (m1 . (W2 (m2 . (W3 d)))),   d_c = (z_c > 0),  m1 / m2 = the masks (pre-activation > 0) of the
+ * two hidden layers of the forward pass that gave z, "." a select (mask ? x : 0, not a product).  It is evaluated as
+ * the network C -> 256 -> 256 -> A with the weights W3^T (zero-padded to four input rows), W2^T, W1[S:S+A, :]^T and
+ * zero biases in the forward pass's summation order (layer 1 in natural k order, layers 2 and 3 in the accumulator
+ * tiles' row order, the head as two lane-half fma chains joined by one add; tests/mlp_project_ref.c restates it).
+ * iters = 0 occurs: a lane whose p0 is not below thr but whose logits are all below tol is "projected" without a
+ * step (at the reference's defaults 0.1 and 0.01: -2.2 <~ z < 0.01).  Comparisons with NaN are false: such a lane is
+ * projected and walks until the steps run out; a NaN passes through the update.  A disturbance installed on the
+ * handle is ignored.  NIG_ERR_INVALID: a NULL argument, n_outputs outside 1 .. 4, a non-finite threshold or
+ * tolerance.  NIG_ERR_UNSUPPORTED: hidden != 256, an env shape without the MFMA actor.  The handle's actor, critic,
+ * gate and actor ensemble are left alone, and vice versa.
+ */
+#define NIG_MAX_PROJECT_ITERS 16
+int nig_set_mlp_constraint(nig_handle *h, int32_t hidden, int32_t n_outputs, const float *C1, const float *c1,
+                           const float *C2, const float *c2, const float *C3, const float *c3, float threshold,
+                           float tolerance, void *stream);
+
+/*
+ * As nig_rollout_mlp (arguments, minima, obs_out alignment, frozen lanes, tallies, launch counter), with the
+ * installed constraint projection.  act_out: the action the env received.  prob_out / viol_out (optional) float:
+ * row c of step k at base + k*c_step_stride + c*ld_c, c = 0 .. C-1 (p0[c] / viol[c]).  iters_out (optional) int32:
+ * row k at iters_out + k*out_stride.  grad_out (optional) float, act_out's layout and pitches: the FIRST gradient
+ * of the step, written where iters >= 1 and untouched elsewhere.  Frozen lanes leave their words untouched; rows
+ * >= C of a block are never written.  With prob_out or viol_out: ld_c in [batch, 2^26] and c_step_stride >= C*ld_c;
+ * with grad_out: ld_act in [batch, 2^26] and act_step_stride >= A*ld_act.  NIG_ERR_INVALID (nothing launched or
+ * written): no actor or no predictor installed, max_iters outside 1 .. NIG_MAX_PROJECT_ITERS, a non-finite step, a
+ * bad pitch, and every refusal of nig_rollout_mlp; NIG_ERR_UNSUPPORTED for an env shape without the MFMA actor.
+ */
+int nig_rollout_mlp_projected(nig_handle *h, int32_t n_steps, int32_t max_iters, float step, float *reward_out,
+                              uint32_t *flags_out, int64_t out_stride, float *obs_out, int64_t obs_step_stride,
+                              float *act_out, int64_t ld_act, int64_t act_step_stride, float *prob_out,
+                              float *viol_out, int32_t *iters_out, float *grad_out, int64_t ld_c,
+                              int64_t c_step_stride, void *stream);
+
+/*
  * Sensor / actuator noise inside the closed loop ("nig-disturb-v1"): the policy sees a noisy observation, the plant
  * receives a noisy action.  Stands in for the observation_noise / action_noise runs of the reference's
  * RobustnessBenchmark (benchmarks/industrial_benchmarks.py:455-573) and for predict(obs, deterministic=False) of
@@ -682,7 +738,7 @@ typedef struct nig_disturbance {
 
 /* Install (copy) the disturbance the _disturbed rollouts apply; d == NULL removes it.  NIG_ERR_INVALID, the installed one
  * kept: a negative / NaN / infinite sigma, clip_lo > clip_hi or a NaN bound, an unknown hold.  Only the two entry points
- * below read it: nig_rollout_policy, nig_rollout_mlp, nig_rollout_mlp_safe, nig_rollout_mlp_gated and nig_rollout_mlp_ensemble ignore an installed
+ * below read it: nig_rollout_policy, nig_rollout_mlp, nig_rollout_mlp_safe, nig_rollout_mlp_gated, nig_rollout_mlp_projected and nig_rollout_mlp_ensemble ignore an installed
  * disturbance (the shield and the ensemble have no disturbed form). */
 int nig_set_disturbance(nig_handle *h, const nig_disturbance *d /* host; NULL clears */, void *stream);
 

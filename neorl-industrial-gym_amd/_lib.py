@@ -20,9 +20,10 @@ FLAG_TERMINATED, FLAG_TRUNCATED = 0x1, 0x2
 FLAG_VIOL_SHIFT, FLAG_NVIOL_SHIFT, FLAG_NCRIT_SHIFT = 2, 5, 7
 FLAG_SHUTDOWN, FLAG_DID_RESET, FLAG_INACTIVE, FLAG_STEP_SHIFT = 0x200, 0x400, 0x800, 16
 FLAG_VIOL3, FLAG_NVIOL_HI = 0x1000, 0x2000
-FLAG_SHIELDED = 0x4000          # nig_rollout_mlp_safe: the safety critic halved the action (_search: replaced it; _gated: by zero)
+FLAG_SHIELDED = 0x4000          # nig_rollout_mlp_safe: the safety critic halved the action (_search: replaced it; _gated: by zero; _projected: the lane was projected)
 FLAG_UNCERTAIN = 0x8000         # nig_rollout_mlp_ensemble: uncertainty > threshold on this live step (_gated: some sd[c] not below the limit)
 MAX_ENSEMBLE = 8
+MAX_PROJECT_ITERS = 16          # nig_rollout_mlp_projected: max_iters 1 .. NIG_MAX_PROJECT_ITERS
 MAX_CANDIDATES = 128            # nig_rollout_mlp_search: n_candidates 1 .. NIG_MAX_CANDIDATES
 ENSEMBLE_AVERAGE, ENSEMBLE_VOTING = 0, 1
 CTR_STEP_MASK, CTR_DONE, CTR_VIOL_SHIFT = 0x7FFF, 0x8000, 16
@@ -127,6 +128,8 @@ PROTOTYPES = {
     "nig_rollout_mlp_search": (ci, CLOSED_LOOP[:2] + [i32] + CLOSED_LOOP[2:] + [vp, vp, vp, vp]),
     "nig_set_mlp_safety_ensemble": (ci, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, f32, f32, f32, vp]),
     "nig_rollout_mlp_gated": (ci, CLOSED_LOOP + [vp, vp, vp, i64, i64, vp]),
+    "nig_set_mlp_constraint": (ci, [vp, i32, i32, vp, vp, vp, vp, vp, vp, f32, f32, vp]),
+    "nig_rollout_mlp_projected": (ci, CLOSED_LOOP[:2] + [i32, f32] + CLOSED_LOOP[2:] + [vp, vp, vp, vp, i64, i64, vp]),
     "nig_set_mlp_ensemble": (ci, [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, f64, f32, vp]),
     "nig_rollout_mlp_ensemble": (ci, CLOSED_LOOP + [vp, vp, vp]),
     "nig_set_disturbance": (ci, [vp, P(DisturbanceStruct), vp]),

@@ -507,6 +507,54 @@ class BatchedIndustrialEnv:
         ld_c, c_step = pitches.pop() if pitches else (0, 0)
         self._closed_loop(self._L.nig_rollout_mlp_gated, n_steps, reward_out, flags_out, obs_out, act_out, tail=(*ptrs, ld_c, c_step))
 
+    def set_mlp_constraint(self, predictor, threshold: float = 0.1, tolerance: float = 0.01):
+        """Install the constraint predictor of ConstrainedIQLAgent (agents/safety_critical.py) for rollout_mlp_projected():
+        `predictor` = a set_mlp_safety() weight list whose head has 1 .. 4 columns, one per constraint (C3 [256, C], c3 [C]).  The
+        law "nig-project-v1" (include/nig.h) takes the acceptance threshold and the tolerance as given.  The actor, the critic,
+        the gate and the actor ensemble stay as they are."""
+        Hd, D = 256, self.state_dim + self.action_dim
+        n_out = int(np.asarray(predictor[2][1]).size)
+        W = _mlp_weights(predictor, [(D, Hd), (Hd,), (Hd, Hd), (Hd,), (Hd, n_out), (n_out,)])
+        with torch.cuda.device(self._dev_index):
+            _lib.check(self._L.nig_set_mlp_constraint(self._h, Hd, n_out, *[C.c_void_p(w.ctypes.data) for w in W], float(threshold),
+                                                      float(tolerance), self._stream()))
+        self._constraint_outputs = n_out
+
+    def rollout_mlp_projected(self, n_steps: int, max_iters: int = 10, step: float = 0.1, reward_out=None, flags_out=None, obs_out=None,
+                              act_out=None, prob_out=None, viol_out=None, iters_out=None, grad_out=None):
+        """rollout_mlp() with the installed constraint predictor's projection (ConstrainedIQLAgent.get_safe_action on the
+        device): the env receives the actor's action where every constraint's violation probability is below the threshold;
+        elsewhere the action after up to max_iters (1 .. MAX_PROJECT_ITERS) gradient steps of size `step` towards logits below the
+        tolerance.  act_out holds the action the env received; prob_out / viol_out float32 [n_steps, C, >=B] the probabilities of
+        the actor's action / of the action the env received (they share their pitches); iters_out int32 [n_steps, >=B] the
+        gradient steps taken, -1 where the actor's action was kept; grad_out float32 [n_steps, A, >=B] (act_out's pitches) the
+        first gradient, written where iters >= 1; flags carry FLAG_SHIELDED on projected lanes."""
+        Cn = getattr(self, "_constraint_outputs", 0)
+        ptrs, pitches = [], set()
+        for name, t in (("prob_out", prob_out), ("viol_out", viol_out)):
+            if t is None:
+                ptrs.append(None)
+                continue
+            assert t.dtype == torch.float32 and t.dim() == 3 and t.stride(-1) == 1, name
+            assert t.shape[0] >= n_steps and t.shape[1] == Cn and t.shape[-1] >= self.batch, name
+            ptrs.append(C.c_void_p(t.data_ptr()))
+            pitches.add((t.stride(1), t.stride(0)))
+        assert len(pitches) <= 1, "prob_out and viol_out share their pitches"
+        ld_c, c_step = pitches.pop() if pitches else (0, 0)
+        rp, fp, os_, op, so, ap, lda, sa = self._closed_loop_outputs(n_steps, reward_out, flags_out, obs_out, act_out)
+        ip, is_ = _rows(iters_out, torch.int32, n_steps)
+        strides = ({is_} if ip is not None else set()) | ({os_} if (rp is not None or fp is not None) else set())
+        assert len(strides) <= 1, "iters_out shares the reward/flags row stride"
+        gp = None
+        if grad_out is not None:
+            assert grad_out.dtype == torch.float32 and grad_out.dim() == 3 and grad_out.stride(2) == 1, "grad_out"
+            assert grad_out.shape[0] >= n_steps and grad_out.shape[1] == self.action_dim and grad_out.shape[2] >= self.batch, "grad_out"
+            assert ap is None or (grad_out.stride(1), grad_out.stride(0)) == (lda, sa), "grad_out shares act_out's pitches"
+            gp, lda, sa = C.c_void_p(grad_out.data_ptr()), grad_out.stride(1), grad_out.stride(0)
+        with torch.cuda.device(self._dev_index):
+            _lib.check(self._L.nig_rollout_mlp_projected(self._h, int(n_steps), int(max_iters), float(step), rp, fp, strides.pop() if strides else 0,
+                                                         op, so, ap, lda, sa, *ptrs, ip, gp, ld_c, c_step, self._stream()))
+
     def set_mlp_ensemble(self, members, weights=None, weight_sum=None, method: str = "mean", uncertainty_threshold: float = 0.2):
         """Install an ensemble of actors (agents/ensemble.py EnsembleAgent) for rollout_mlp_ensemble(): `members` = a list of
         set_mlp_policy() weight lists.  method "mean" / "weighted": `weights` = the ACTIVE float64 weights of np.average (for

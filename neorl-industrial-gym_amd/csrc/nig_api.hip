@@ -3,6 +3,7 @@
 #include <dlfcn.h>
 
 #include <atomic>
+#include <vector>
 
 #include "nig_launch.hpp"
 #include "nig_episodes.hpp"
@@ -180,6 +181,8 @@ struct nig_handle {
     // nig_set_mlp_ensemble (owned): the members' operand streams back to back, MLP_STREAM_FLOATS floats each; their active weights
     // nig_set_mlp_safety_ensemble: the gate's member streams (owned), MLP_CSTREAM_FLOATS apart, and its law's parameters
     float *gate_stream = nullptr; int gate_members = 0, gate_cap = 0, gate_outputs = 0; float gate_T = 1.0f, gate_thr = 0.0f, gate_umax = 0.0f;
+    // nig_set_mlp_constraint: the constraint predictor's forward and backward operand streams (owned) and its law's parameters
+    float *proj_cstream = nullptr, *proj_bstream = nullptr; int proj_outputs = 0; float proj_thr = 0.0f, proj_tol = 0.0f;
     float *ens_stream = nullptr; double *ens_w = nullptr; int ens_members = 0, ens_cap = 0, ens_method = 0; double ens_wsum = 0.0; float ens_threshold = 0.0f;
     nig_disturbance dist = {}; bool has_dist = false;      // nig_set_disturbance: what the _disturbed rollouts apply
     float *act32 = nullptr;    // nig_step64 on an env that takes float32 actions: the narrowed rows [A][ld] (owned, lazy)
@@ -426,14 +429,14 @@ static int disturb_args(const nig_handle *h, const char *fn, float *seen_out, in
     return NIG_OK;
 }
 
-// ---- the closed loop: what nig_rollout_policy / _mlp / _mlp_safe / _mlp_search / _mlp_gated / _mlp_ensemble / _policy_disturbed / _mlp_disturbed
+// ---- the closed loop: what nig_rollout_policy / _mlp / _mlp_safe / _mlp_search / _mlp_gated / _mlp_projected / _mlp_ensemble / _policy_disturbed / _mlp_disturbed
 // do after their own prerequisites.  A variant's argument block holds the shared fields as PolicyArgs or MlpArgs, which also says
 // what grid its kernels take: a thread per env for the policy kernels, 32 envs per wave (128 per block) for the MFMA kernels.
 static PolicyArgs &shared_args(PolicyArgs &q) { return q; }
 static PolicyArgs &shared_args(PolicyDistArgs &q) { return q.p; }
 static MlpArgs &shared_args(MlpArgs &q) { return q; }
 static MlpArgs &shared_args(MlpSearchArgs &q) { return q.sh.m; }
-template <class Args> static MlpArgs &shared_args(Args &q) { return q.m; }      // MlpShieldArgs, MlpEnsArgs, MlpDistArgs, MlpGateArgs
+template <class Args> static MlpArgs &shared_args(Args &q) { return q.m; }      // MlpShieldArgs, MlpEnsArgs, MlpDistArgs, MlpGateArgs, MlpProjectArgs
 static unsigned closed_loop_grid(const nig_handle *h, const PolicyArgs &) { return grid_for(h->B); }
 static unsigned closed_loop_grid(const nig_handle *h, const MlpArgs &) { return (unsigned)((h->B + BLOCK / 2 - 1) / (BLOCK / 2)); }
 
@@ -503,6 +506,9 @@ extern "C" {
 // Still 0.8.0, for the same reason: nig_set_mlp_safety_ensemble / nig_rollout_mlp_gated ("nig-gate-v1": SafeEnsembleAgent's
 // get_safe_action -- K safety predictors of up to four head rows vote on the actor's action).  Additive: no existing kernel or entry
 // point changed.
+// Still 0.8.0, for the same reason: nig_set_mlp_constraint / nig_rollout_mlp_projected ("nig-project-v1": ConstrainedIQLAgent's
+// get_safe_action -- a gradient projection of the actor's action towards the constraint predictor's feasible set).  Additive: no
+// existing kernel or entry point changed, no draw added.
 const char *nig_version(void) { return "nig 0.8.0 (gfx950; generator nig-philox-v3)"; }
 const char *nig_last_error(void) { return g_err; }
 
@@ -672,6 +678,8 @@ int nig_destroy(nig_handle *h)
     if (h->ens_stream) (void)hipFree(h->ens_stream);
     if (h->ens_w) (void)hipFree(h->ens_w);
     if (h->gate_stream) (void)hipFree(h->gate_stream);
+    if (h->proj_cstream) (void)hipFree(h->proj_cstream);
+    if (h->proj_bstream) (void)hipFree(h->proj_bstream);
     if (h->pid_mem) (void)hipFree(h->pid_mem);
     if (h->act32) (void)hipFree(h->act32);
     if (h->act_soa) (void)hipFree(h->act_soa);
@@ -1180,6 +1188,70 @@ int nig_rollout_mlp_gated(nig_handle *h, int32_t n_steps, float *reward_out, uin
         q.prob_out = prob_out; q.unc_out = unc_out; q.logit_out = logit_out;
         q.ld_c = (uint32_t)ld_c; q.c_step_stride = (uint64_t)c_step_stride;
         return launch_of(h->env)->mlp_gated;
+    });
+}
+
+// ---- the constraint projection ("nig-project-v1") ------------------------------------------
+int nig_set_mlp_constraint(nig_handle *h, int32_t hidden, int32_t n_outputs, const float *C1, const float *c1, const float *C2,
+                           const float *c2, const float *C3, const float *c3, float threshold, float tolerance, void *stream)
+{
+    const char *const fn = "nig_set_mlp_constraint";
+    if (!h) return fail(NIG_ERR_INVALID, "nig_set_mlp_constraint: NULL handle");
+    if (!C1 || !c1 || !C2 || !c2 || !C3 || !c3) return refuse(fn, "NULL argument (C1 / c1 / C2 / c2 / C3 / c3)");
+    if (n_outputs < 1 || n_outputs > 4) return refuse(fn, "n_outputs outside 1 .. 4");
+    if (!std::isfinite(threshold) || !std::isfinite(tolerance)) return refuse(fn, "threshold and tolerance must be finite");
+    const int S = SPECS[h->env].state_dim, A = SPECS[h->env].action_dim;
+    float *fwd = nullptr, *bwd = nullptr;
+    NIG_TRY(build_network_images(h, fn, hidden, S + A, n_outputs, MLP_CSTREAM_FLOATS, 1, &C1, &c1, &C2, &c2, &C3, &c3, &fwd));
+    // The backward network 4 -> 256 -> 256 -> A: W3^T zero-padded to four input rows, W2^T, W1[S:S+A, :]^T, zero biases -- an image
+    // of the same builder, so a backward pass is a forward pass of this stream (nig_mlp.hpp, MlpProjectArgs)
+    std::vector<float> T1((size_t)4 * MLP_H, 0.0f), T2((size_t)MLP_H * MLP_H), T3((size_t)MLP_H * A), zero(MLP_H, 0.0f);
+    for (int c = 0; c < n_outputs; ++c)
+        for (int u = 0; u < MLP_H; ++u) T1[(size_t)c * MLP_H + u] = C3[(size_t)u * n_outputs + c];
+    for (int k = 0; k < MLP_H; ++k)
+        for (int j = 0; j < MLP_H; ++j) T2[(size_t)j * MLP_H + k] = C2[(size_t)k * MLP_H + j];
+    for (int j = 0; j < A; ++j)
+        for (int u = 0; u < MLP_H; ++u) T3[(size_t)u * A + j] = C1[(size_t)(S + j) * MLP_H + u];
+    const float *t1 = T1.data(), *t2 = T2.data(), *t3 = T3.data(), *z = zero.data();
+    if (const int rc = build_network_images(h, fn, hidden, 4, A, MLP_STREAM_FLOATS, 1, &t1, &z, &t2, &z, &t3, &z, &bwd)) {
+        free(fwd);
+        return rc;
+    }
+    h->proj_outputs = 0;                                    // no projection while the streams are being replaced
+    if (const int rc = upload_stream(fn, &h->proj_cstream, fwd, MLP_CSTREAM_FLOATS, stream)) {
+        free(bwd);
+        return rc;
+    }
+    NIG_TRY(upload_stream(fn, &h->proj_bstream, bwd, MLP_STREAM_FLOATS, stream));
+    h->proj_outputs = n_outputs; h->proj_thr = threshold; h->proj_tol = tolerance;
+    return NIG_OK;
+}
+
+int nig_rollout_mlp_projected(nig_handle *h, int32_t n_steps, int32_t max_iters, float step, float *reward_out, uint32_t *flags_out,
+                              int64_t out_stride, float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
+                              int64_t act_step_stride, float *prob_out, float *viol_out, int32_t *iters_out, float *grad_out,
+                              int64_t ld_c, int64_t c_step_stride, void *stream)
+{
+    const char *const fn = "nig_rollout_mlp_projected";
+    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_projected: bad argument");
+    if (!launch_of(h->env)->mlp_projected) return refuse(fn, "env shape has no MFMA actor", NIG_ERR_UNSUPPORTED);
+    if (!h->mlp_stream) return refuse(fn, "no actor installed (nig_set_mlp_policy)");
+    if (h->proj_outputs < 1 || !h->proj_cstream || !h->proj_bstream) return refuse(fn, "no constraint predictor installed (nig_set_mlp_constraint)");
+    if (max_iters < 1 || max_iters > NIG_MAX_PROJECT_ITERS) return refuse(fn, "max_iters outside 1 .. NIG_MAX_PROJECT_ITERS");
+    if (!std::isfinite(step)) return refuse(fn, "step must be finite");
+    if (prob_out || viol_out) {
+        if (ld_c < h->B || ld_c > NIG_MAX_PITCH) return refuse(fn, "ld_c outside [batch, 2^26]");
+        if (c_step_stride < (int64_t)h->proj_outputs * ld_c) return refuse(fn, "c_step_stride smaller than one [n_outputs][ld_c] block");
+    }
+    if (grad_out && (ld_act < h->B || ld_act > NIG_MAX_PITCH || act_step_stride < (int64_t)SPECS[h->env].action_dim * ld_act))
+        return refuse(fn, "bad action trajectory pitch (grad_out takes act_out's)");
+    return closed_loop<MlpProjectArgs>(h, fn, n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpProjectArgs &q) {
+        q.m.wstream = h->mlp_stream;
+        q.cstream = h->proj_cstream; q.bstream = h->proj_bstream; q.n_outputs = h->proj_outputs; q.max_iters = max_iters;
+        q.threshold = h->proj_thr; q.tolerance = h->proj_tol; q.step = step;
+        q.prob_out = prob_out; q.viol_out = viol_out; q.iters_out = iters_out; q.grad_out = grad_out;
+        q.ld_c = (uint32_t)ld_c; q.c_step_stride = (uint64_t)c_step_stride;
+        return launch_of(h->env)->mlp_projected;
     });
 }
 

@@ -1,7 +1,7 @@
 // nig_launch.hpp -- the host side of libnig.so's kernels: the list of environments and the per-environment launch table.  An
 // env_<key>.hip instantiates the env's kernels by defining its table (NIG_DEFINE_ENV_LAUNCH); nig_api.hip reaches them through the
 // table's function pointers only.  The launchers of the kernel families with translation units of their own (sampled_, ensemble_,
-// disturbed_, search_, gated_<key>.hip) are DECLARED here and defined in nig_launch_families.hpp, which those units alone include.  Which
+// disturbed_, search_, gated_, projected_<key>.hip) are DECLARED here and defined in nig_launch_families.hpp, which those units alone include.  Which
 // kernel form a rollout launch takes is decided in nig_launch_plan.hpp; the functions here run its plans.
 #pragma once
 #include "nig_kernels.hpp"
@@ -52,6 +52,8 @@ struct EnvLaunch {
     void (*mlp_search)(const MlpSearchArgs &, unsigned grid, hipStream_t);
     // gated_<key>.hip: nig_rollout_mlp_gated; nullptr as `mlp`
     void (*mlp_gated)(const MlpGateArgs &, unsigned grid, hipStream_t);
+    // projected_<key>.hip: nig_rollout_mlp_projected; nullptr as `mlp`
+    void (*mlp_projected)(const MlpProjectArgs &, unsigned grid, hipStream_t);
 };
 
 template <class Env>
@@ -68,6 +70,7 @@ template <class Env> constexpr auto mlp_kernel(const MlpShieldArgs &) { return r
 template <class Env> constexpr auto mlp_kernel(const MlpDistArgs &) { return rollout_mlp_disturbed_kernel<Env>; }
 template <class Env> constexpr auto mlp_kernel(const MlpSearchArgs &) { return rollout_mlp_search_kernel<Env>; }
 template <class Env> constexpr auto mlp_kernel(const MlpGateArgs &) { return rollout_mlp_gated_kernel<Env>; }
+template <class Env> constexpr auto mlp_kernel(const MlpProjectArgs &) { return rollout_mlp_projected_kernel<Env>; }
 
 template <class Env, class Args>
 static void launch_mlp(const Args &q, unsigned grid, hipStream_t st)
@@ -236,6 +239,7 @@ template <class Env> void launch_policy_disturbed_env(const PolicyDistArgs &q, u
 template <class Env> void launch_mlp_disturbed_env(const MlpDistArgs &q, unsigned grid, hipStream_t st);
 template <class Env> void launch_mlp_search_env(const MlpSearchArgs &q, unsigned grid, hipStream_t st);
 template <class Env> void launch_mlp_gated_env(const MlpGateArgs &q, unsigned grid, hipStream_t st);
+template <class Env> void launch_mlp_projected_env(const MlpProjectArgs &q, unsigned grid, hipStream_t st);
 
 template <class Env>
 static void launch_policy(const PolicyArgs &q, unsigned /*grid*/, hipStream_t st)
@@ -283,6 +287,7 @@ static const EnvLaunch *env_launch_table()
         t.mlp_disturbed = mlp_slot<Env>(launch_mlp_disturbed_env<Env>);
         t.mlp_search = mlp_slot<Env>(launch_mlp_search_env<Env>);
         t.mlp_gated = mlp_slot<Env>(launch_mlp_gated_env<Env>);
+        t.mlp_projected = mlp_slot<Env>(launch_mlp_projected_env<Env>);
         return t;
     }();
     return &T;

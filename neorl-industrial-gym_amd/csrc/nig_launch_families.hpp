@@ -1,6 +1,7 @@
 // nig_launch_families.hpp -- the definitions of the family launchers nig_launch.hpp declares: the kernels of nig_rollout_sampled,
-// nig_rollout_mlp_ensemble, nig_rollout_policy_disturbed / nig_rollout_mlp_disturbed, nig_rollout_mlp_search and nig_rollout_mlp_gated.
-// Included by the family translation units alone (sampled_, ensemble_, disturbed_, search_, gated_<key>.hip).  A template that is defined but not
+// nig_rollout_mlp_ensemble, nig_rollout_policy_disturbed / nig_rollout_mlp_disturbed, nig_rollout_mlp_search, nig_rollout_mlp_gated and
+// nig_rollout_mlp_projected.
+// Included by the family translation units alone (sampled_, ensemble_, disturbed_, search_, gated_, projected_<key>.hip).  A template that is defined but not
 // instantiated emits nothing: each unit explicitly instantiates the launcher of its own family for its own env, and with it that
 // family's kernels and no other's.
 #pragma once
@@ -38,7 +39,7 @@ void launch_policy_disturbed_env(const PolicyDistArgs &q, unsigned /*grid*/, hip
     }
 }
 
-// nig_rollout_mlp_disturbed, nig_rollout_mlp_search, nig_rollout_mlp_gated
+// nig_rollout_mlp_disturbed, nig_rollout_mlp_search, nig_rollout_mlp_gated, nig_rollout_mlp_projected
 template <class Env>
 void launch_mlp_disturbed_env(const MlpDistArgs &q, unsigned grid, hipStream_t st) { launch_mlp<Env>(q, grid, st); }
 
@@ -47,6 +48,9 @@ void launch_mlp_search_env(const MlpSearchArgs &q, unsigned grid, hipStream_t st
 
 template <class Env>
 void launch_mlp_gated_env(const MlpGateArgs &q, unsigned grid, hipStream_t st) { launch_mlp<Env>(q, grid, st); }
+
+template <class Env>
+void launch_mlp_projected_env(const MlpProjectArgs &q, unsigned grid, hipStream_t st) { launch_mlp<Env>(q, grid, st); }
 
 }  // namespace nig
 
@@ -62,3 +66,5 @@ void launch_mlp_gated_env(const MlpGateArgs &q, unsigned grid, hipStream_t st) {
     template void nig::launch_mlp_search_env<nig::EnvType>(const nig::MlpSearchArgs &, unsigned, hipStream_t);
 #define NIG_DEFINE_ENV_GATED(EnvType) \
     template void nig::launch_mlp_gated_env<nig::EnvType>(const nig::MlpGateArgs &, unsigned, hipStream_t);
+#define NIG_DEFINE_ENV_PROJECTED(EnvType) \
+    template void nig::launch_mlp_projected_env<nig::EnvType>(const nig::MlpProjectArgs &, unsigned, hipStream_t);

@@ -1,5 +1,5 @@
 // nig_mlp.hpp -- the fused MLP actor on MFMA with its safety-critic shield and its ensemble (device code only): MlpArgs,
-// MlpShieldArgs, MlpEnsArgs, MlpDistArgs, MlpSearchArgs, MlpGateArgs, rollout_mlp_body and its six kernels.
+// MlpShieldArgs, MlpEnsArgs, MlpDistArgs, MlpSearchArgs, MlpGateArgs, MlpProjectArgs, rollout_mlp_body and its seven kernels.
 #pragma once
 #include <type_traits>
 #include "nig_step.hpp"
@@ -173,13 +173,47 @@ struct MlpGateArgs {
     uint32_t ld_c; uint64_t c_step_stride;
 };
 
-template <class Env, bool SHIELD, int ENS = ENS_NONE, bool DIST = false, bool SEARCH = false, bool GATE = false>
+// Constraint projection (rollout_mlp_projected_kernel, agents/safety_critical.py ConstrainedIQLAgent.get_safe_action; include/nig.h
+// "nig-project-v1"): PROJECT is the shield's form with a gradient descent on the action.  The constraint predictor f (S + A -> 256 ->
+// 256 -> C, C <= 4 head rows on v_mfma_f32_4x4x1: the gate's member) scores the actor's action; where some p0[c] is not below the
+// threshold the lane walks a <- clip(a - step * dG/da, -1, 1), G = sum_c relu(f_c), until every logit is below the tolerance or
+// max_iters steps are taken.  In this kernel's transposed layout a backward pass IS a forward pass of the transposed network
+// C -> 256 -> 256 -> A (weights W3^T zero-padded to four rows, W2^T, W1[S:S+A, :]^T, zero biases: an operand stream of put_network
+// like any other, at `bstream`) whose "activation" is a select on the forward pass's ReLU mask: output tile m of either hidden layer
+// holds unit 32 m + mfma_row(t, half) in register t in both directions, so the mask bit a backward tile needs sits in the lane that
+// recorded it -- 128 bits per lane and hidden layer, eight registers, alive from a forward pass to the backward pass behind it.  The
+// backward head has A rows: the actor's head instruction and decode, without the tanh.  Passes go through the same double-buffered
+// LDS image; behind every forward pass the block votes (__syncthreads_or over "live, projected, not yet satisfied, steps left") and
+// runs a backward + forward pair or leaves, the fill behind the vote exposed as in the search.  A lane that has stopped holds its
+// action: the further forward passes of its block recompute its logits from the same (s, a), bit for bit, so no lane's result
+// depends on its block's vote.  As the search and the gate, the form keeps nothing across the passes that a step can form again from
+// the lane index.
+constexpr int ACT_RELU = 0, ACT_RELU_RECORD = 1, ACT_SELECT = 2;   // a hidden layer's activation: ReLU; ReLU that records the lane's mask bits; select on a recorded bit
+struct MlpProjectArgs {
+    MlpArgs m;
+    const float *cstream;       // the predictor's operand stream (S + A, C) built by nig_set_mlp_constraint
+    const float *bstream;       // the backward network's operand stream (4, A), MLP_STREAM_FLOATS floats
+    int n_outputs;              // C, 1 .. 4
+    int max_iters;              // 1 .. NIG_MAX_PROJECT_ITERS
+    float threshold;            // project unless sigmoid(z[c]) < threshold for every c
+    float tolerance;            // stop once z[c] < tolerance for every c
+    float step;                 // the gradient step
+    float *prob_out;            // p0: row c of step k at prob_out + k * c_step_stride + c * ld_c, may be NULL
+    float *viol_out;            // sigmoid(z) of the action the env received: the same layout, may be NULL
+    int32_t *iters_out;         // [n_steps][>= B] gradient steps taken, -1 where the actor's action was kept, row k at iters_out + k * m.out_stride, may be NULL
+    float *grad_out;            // the first gradient of the step, act_out's layout; untouched where iters < 1, may be NULL
+    uint32_t ld_c; uint64_t c_step_stride;
+};
+
+template <class Env, bool SHIELD, int ENS = ENS_NONE, bool DIST = false, bool SEARCH = false, bool GATE = false, bool PROJECT = false>
 __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const MlpArgs &q, const float *cstream, float *prob_out, float threshold,
                                                                        [[maybe_unused]] const MlpEnsArgs *eq = nullptr,
                                                                        [[maybe_unused]] const DisturbArgs *dq = nullptr,
                                                                        [[maybe_unused]] const MlpSearchArgs *sq = nullptr,
-                                                                       [[maybe_unused]] const MlpGateArgs *gq = nullptr)
+                                                                       [[maybe_unused]] const MlpGateArgs *gq = nullptr,
+                                                                       [[maybe_unused]] const MlpProjectArgs *jq = nullptr)
 {
+    static_assert(!PROJECT || (SHIELD && !SEARCH && !GATE), "the projection is a form of the shield; it excludes the search and the gate");
     static_assert(!(SHIELD && ENS != ENS_NONE), "the ensemble has no shield");
     static_assert(!SEARCH || SHIELD, "the search is a form of the shield");
     static_assert(!GATE || (SHIELD && !SEARCH), "the gate is a form of the shield; it has no searching twin");
@@ -209,7 +243,7 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
     // the lane's global index where a step needs it; the search forms it anew each time (as its output addresses, below: nothing
     // that a step can form from the lane index is kept in registers across the candidate passes)
     auto lane_gi = [&]() __attribute__((always_inline)) {
-        if constexpr (SEARCH || GATE) { uint32_t l = li; asm volatile("" : "+v"(l)); return p.env0 + (uint64_t)l; }
+        if constexpr (SEARCH || GATE || PROJECT) { uint32_t l = li; asm volatile("" : "+v"(l)); return p.env0 + (uint64_t)l; }
         else return gi;
     };
     const bool autoreset = (p.hflags & NIG_F_AUTORESET) != 0;
@@ -241,8 +275,10 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
     // follows (the one thing that differs between actor, critic, ensemble member and step) and the loop over chunks stay in
     // the body, where the compiler saw them before there were routines (nig_episode.hpp's rule; profiles/mlp_network/isa_diff.txt).
     // Layer 1, one chunk of it: TILES hidden tiles of REC records each on the input x(k) -> ReLU'd tiles h[0 .. TILES).
-    auto layer1_chunk = [&](auto tiles_, auto rec_, const auto &x, f32x16 *h, int gbuf) __attribute__((always_inline)) {
-        constexpr int TILES = decltype(tiles_)::value, REC = decltype(rec_)::value;
+    // The activation `act_` is ReLU, ReLU that also records the lane's mask bits (tile mm, register r: bit 16 (mm & 1) + r of
+    // mk[mm >> 1]), or the backward pass's select on such a recorded bit; mk is unused with plain ReLU.
+    auto layer1_chunk = [&](auto tiles_, auto rec_, const auto &x, f32x16 *h, int gbuf, auto act_, [[maybe_unused]] uint32_t *mk) __attribute__((always_inline)) {
+        constexpr int TILES = decltype(tiles_)::value, REC = decltype(rec_)::value, ACT = decltype(act_)::value;
         const float *wb = &s_w[gbuf][lane];
 #pragma unroll
         for (int mm = 0; mm < TILES; ++mm) {
@@ -253,8 +289,22 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[(mm * REC + ks) * 64], b, acc, 0, 0, 0);
             }
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wb[(mm * REC + REC - 1) * 64], half ? 0.0f : 1.0f, acc, 0, 0, 0);   // + bias
+            if constexpr (ACT == ACT_SELECT) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[r] = fmaxf(acc[r], 0.0f);                                   // ReLU
+                for (int r = 0; r < 16; ++r) acc[r] = ((mk[mm >> 1] >> (16 * (mm & 1) + r)) & 1u) ? acc[r] : 0.0f;
+            } else {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[r] = fmaxf(acc[r], 0.0f);                               // ReLU
+            }
+            if constexpr (ACT == ACT_RELU_RECORD) {
+                uint32_t bits = 0u;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) bits |= (acc[r] > 0.0f ? 1u : 0u) << (16 * (mm & 1) + r);
+                mk[mm >> 1] = (mm & 1) ? (mk[mm >> 1] | bits) : bits;
+                // the word is formed HERE: hipcc otherwise sinks the compares to the word's first use, behind the block's vote, and
+                // keeps the tiles they read alive until then (the backward pass's tiles on top of them: 500 B of spills per lane)
+                asm volatile("" : "+v"(mk[mm >> 1]));
+            }
             h[mm] = acc;
         }
     };
@@ -262,8 +312,24 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
     // returns the head's accumulator `out` (this lane half's partial sums; its type names the instruction, f32x4: 4 x 4 x 1,
     // f32x16: 16 x 16 x 1) with the tile's 16 hidden rows added, and the head's bias behind the last tile.  (The count and not
     // a `bool last`: the caller would evaluate that ahead of the first sched_barrier, and the parent compares after the last.)
-    auto layer2_chunk = [&](const f32x16 *h, auto out, int tiles, int gbuf) __attribute__((always_inline)) {
+    // `act_` as in layer1_chunk: the tile's bits are bits 16 ((tiles - 1) & 1) .. of mk[(tiles - 1) >> 1]; the word is picked by a
+    // chain of selects, since `tiles` is a run-time count and a register array takes no run-time index.
+    auto layer2_chunk = [&](const f32x16 *h, auto out, int tiles, int gbuf, auto act_, [[maybe_unused]] uint32_t *mk) __attribute__((always_inline)) {
         constexpr int RING = 8;                             // LDS reads in flight ahead of their MFMA (~64 cycles apart)
+        constexpr int ACT = decltype(act_)::value;
+        [[maybe_unused]] uint32_t bits = 0u;                // ACT_RELU_RECORD: gathered here; ACT_SELECT: the tile's recorded bits
+        if constexpr (ACT == ACT_SELECT) {
+            const int tw = (tiles - 1) >> 1;
+            bits = (tw == 0 ? mk[0] : tw == 1 ? mk[1] : tw == 2 ? mk[2] : mk[3]) >> (16 * ((tiles - 1) & 1));
+        }
+        // the head's B operand: register t of the tile through the activation
+        auto hidden = [&](const f32x16 &acc, int t) __attribute__((always_inline)) {
+            if constexpr (ACT == ACT_SELECT) return ((bits >> t) & 1u) ? acc[t] : 0.0f;
+            else {
+                if constexpr (ACT == ACT_RELU_RECORD) bits |= (acc[t] > 0.0f ? 1u : 0u) << t;
+                return fmaxf(acc[t], 0.0f);
+            }
+        };
         const float *wb = &s_w[gbuf][lane];
         f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
         float ring[RING];
@@ -280,11 +346,20 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
             } else if (i == MLP_MT * 16) {
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aop, half ? 0.0f : 1.0f, acc, 0, 0, 0);      // + bias
             } else if constexpr (std::is_same_v<decltype(out), f32x4>) {      // own value x the weights of the lane's block
-                out = __builtin_amdgcn_mfma_f32_4x4x1f32(aop, fmaxf(acc[i - MLP_MT * 16 - 1], 0.0f), out, 0, 0, 0);
+                out = __builtin_amdgcn_mfma_f32_4x4x1f32(aop, hidden(acc, i - MLP_MT * 16 - 1), out, 0, 0, 0);
             } else {
-                out = __builtin_amdgcn_mfma_f32_16x16x1f32(aop, fmaxf(acc[i - MLP_MT * 16 - 1], 0.0f), out, 0, 0, 0);
+                out = __builtin_amdgcn_mfma_f32_16x16x1f32(aop, hidden(acc, i - MLP_MT * 16 - 1), out, 0, 0, 0);
             }
             __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (ACT == ACT_RELU_RECORD) {
+            const int tw = (tiles - 1) >> 1;
+            const bool hi = ((tiles - 1) & 1) != 0;
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                mk[w] = tw == w ? (hi ? (mk[w] | (bits << 16)) : bits) : mk[w];
+                asm volatile("" : "+v"(mk[w]));             // (formed here, as in layer1_chunk)
+            }
         }
         if (tiles == MLP_MT) {                              // record 145 of the last chunk: + the head's bias
             if constexpr (std::is_same_v<decltype(out), f32x4>) out = __builtin_amdgcn_mfma_f32_4x4x1f32(ring[MLP_PER % RING], half ? 0.0f : 1.0f, out, 0, 0, 0);
@@ -310,6 +385,8 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
         [[maybe_unused]] float e_p0[A], e_s1[A], e_s2[A], e_f[A];   // ensemble: member 0, sum d, sum d^2, float32 action sum
         [[maybe_unused]] double e_d[A];                            // ensemble: float64 weighted action sum
         [[maybe_unused]] float g_z0[GATE ? 4 : 1], g_s1[GATE ? 4 : 1], g_s2[GATE ? 4 : 1], g_acc[GATE ? 4 : 1];   // gate: member 0, sum d, sum d^2, logit sum
+        [[maybe_unused]] int j_iters = -1;                         // projection: gradient steps taken, -1 where the actor's action is kept
+        [[maybe_unused]] float j_z[PROJECT ? 4 : 1];               // projection: the logits of the last forward pass
         [[maybe_unused]] int g_mem = 0;                            // gate: this pass's member
         [[maybe_unused]] bool g_uncertain = false;
         int mem = 0;
@@ -320,7 +397,7 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
         // and every wave is done with the buffer the next fill overwrites
         __syncthreads();
         fill(1, gbuf ^ 1, MLP_PIECES);
-        layer1_chunk(mlp_int<MLP_MT>{}, mlp_int<L1.records>{}, xin, h1, gbuf);
+        layer1_chunk(mlp_int<MLP_MT>{}, mlp_int<L1.records>{}, xin, h1, gbuf, mlp_int<ACT_RELU>{}, nullptr);
         gbuf ^= 1;
         std::conditional_t<mlp_head4<Env>, f32x4, f32x16> out = {};     // this lane half's partial sums of the head rows
         for (int m2 = 0; m2 < MLP_MT; ++m2) {               // a real loop: the body is 145 MFMAs of straight-line code
@@ -333,7 +410,7 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
                 if (more || it + 1 < q.n_steps) fill(0, gbuf ^ 1, L1.pieces);
             }
             else if (it + 1 < q.n_steps) fill(0, gbuf ^ 1, L1.pieces);   // layer 1 of the NEXT step (the weights do not change)
-            out = layer2_chunk(h1, out, m2 + 1, gbuf);
+            out = layer2_chunk(h1, out, m2 + 1, gbuf, mlp_int<ACT_RELU>{}, nullptr);
             gbuf ^= 1;
         }
         if constexpr (mlp_head4<Env>) {
@@ -401,7 +478,116 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
         [[maybe_unused]] float s_best = 0.0f;                      // search: p of the action the env receives, as far as the passes have come
         [[maybe_unused]] int s_choice = -1, s_cand = -1, s_passes = 0;   // search: the best's number; this pass (-1: the actor's action); how many
         [[maybe_unused]] float s_u[SEARCH ? A : 1];                // search: this pass's candidate (dead after layer 1)
-        if constexpr (SHIELD) {
+        if constexpr (PROJECT) {
+            // ---------------- constraint projection: forward pass, vote, backward + forward pairs (the law, include/nig.h) ----------------
+            constexpr MlpLayer1 B1 = mlp_layer1(4);                // the backward network's layer 1: C <= 4 inputs, whatever C is
+            static_assert(B1.chunks == 1 && B1.tiles == MLP_MT, "the backward layer 1 is one chunk");
+            auto bfill = [&](int c, int buf, int pieces) __attribute__((always_inline)) { fill_from(jq->bstream, c, buf, pieces); };
+            auto x = [&](int k) __attribute__((always_inline)) { return k < S ? s[k] : (k < S + A ? a[k - S] : 0.0f); };
+            bool active = false;                                   // this lane is projected and has neither met the tolerance nor run out of steps
+            for (int pk = 0;; ++pk) {                              // pk: the gradient steps taken so far by the lanes still walking (block-uniform)
+                uint32_t m1[4], m2[4];                             // ReLU masks of the forward pass's two hidden layers (dead behind the backward pass)
+                f32x16 g1[MLP_MT];
+                if constexpr (C1.chunks == 1) {
+                    __syncthreads();                        // the predictor's layer 1 is in s_w[gbuf]
+                    cfill(1, gbuf ^ 1, MLP_PIECES);
+                    layer1_chunk(mlp_int<MLP_MT>{}, mlp_int<C1.records>{}, x, g1, gbuf, mlp_int<ACT_RELU_RECORD>{}, m1);
+                    gbuf ^= 1;
+                } else {
+#pragma unroll
+                    for (int c1 = 0; c1 < C1.chunks; ++c1) {
+                        __syncthreads();                    // predictor layer-1 chunk c1 is in s_w[gbuf]
+                        if (c1 + 1 < C1.chunks) cfill(c1 + 1, gbuf ^ 1, C1.pieces);
+                        else cfill(C1.chunks, gbuf ^ 1, MLP_PIECES);
+                        static_assert(C1.tiles % 2 == 0, "a layer-1 chunk's tiles fill whole mask words");
+                        layer1_chunk(mlp_int<C1.tiles>{}, mlp_int<C1.records>{}, x, g1 + c1 * C1.tiles, gbuf, mlp_int<ACT_RELU_RECORD>{}, m1 + c1 * (C1.tiles / 2));
+                        gbuf ^= 1;
+                    }
+                }
+                f32x4 z4 = {0, 0, 0, 0};
+                for (int t2 = 0; t2 < MLP_MT; ++t2) {
+                    __syncthreads();                        // predictor chunk C1.chunks + t2 is in s_w[gbuf]
+                    if (t2 + 1 < MLP_MT) cfill(C1.chunks + 1 + t2, gbuf ^ 1, MLP_PIECES);      // (behind the last chunk the fill waits for the block's vote)
+                    z4 = layer2_chunk(g1, z4, t2 + 1, gbuf, mlp_int<ACT_RELU_RECORD>{}, m2);
+                    gbuf ^= 1;
+                }
+#pragma unroll
+                for (int c = 0; c < 4; ++c) j_z[c] = z4[c] + __shfl_xor(z4[c], 32);
+                if (pk == 0) {                                     // the acceptance test on the actor's action
+                    const bool live_writer = writer && !(ctr & NIG_CTR_DONE);
+                    uint32_t lo = li;
+                    asm volatile("" : "+v"(lo));
+                    bool keep = true;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        if (c < jq->n_outputs) {
+                            const float p0 = det_sigmoidf(j_z[c]);
+                            keep = keep && p0 < threshold;
+                            // p0 leaves here, so that it is dead during the gradient passes
+                            if (live_writer && jq->prob_out) (jq->prob_out + (size_t)it * jq->c_step_stride + lo)[(size_t)c * jq->ld_c] = p0;
+                        }
+                    }
+                    shield = !keep && !(ctr & NIG_CTR_DONE);       // (lanes past the batch are frozen: they never ask)
+                    active = shield;
+                }
+                if (active) {                                      // the reference's loop head: the raw logits against the tolerance, then the step count
+                    bool met = true;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+                        if (c < jq->n_outputs) met = met && j_z[c] < jq->tolerance;
+                    if (met || pk >= jq->max_iters) { active = false; j_iters = pk; }
+                }
+                // every wave is past the barrier behind which s_w[gbuf] was last read: it takes the chunk consumed next
+                if (!__syncthreads_or(active)) {
+                    if (it + 1 < q.n_steps) fill(0, gbuf, L1.pieces);
+                    break;
+                }
+                bfill(0, gbuf, B1.pieces);
+                // ---- backward: dG/da on d_c = (z_c > 0), the transposed network with the masks' selects ----
+                auto xd = [&](int k) __attribute__((always_inline)) { return (k < jq->n_outputs && j_z[k] > 0.0f) ? 1.0f : 0.0f; };
+                __syncthreads();                            // the backward layer 1 is in s_w[gbuf]
+                bfill(1, gbuf ^ 1, MLP_PIECES);
+                f32x16 q1[MLP_MT];
+                layer1_chunk(mlp_int<MLP_MT>{}, mlp_int<B1.records>{}, xd, q1, gbuf, mlp_int<ACT_SELECT>{}, m2);
+                gbuf ^= 1;
+                std::conditional_t<mlp_head4<Env>, f32x4, f32x16> gout = {};
+                for (int t2 = 0; t2 < MLP_MT; ++t2) {
+                    __syncthreads();                        // backward chunk 1 + t2 is in s_w[gbuf]
+                    if (t2 + 1 < MLP_MT) bfill(2 + t2, gbuf ^ 1, MLP_PIECES);
+                    else cfill(0, gbuf ^ 1, C1.pieces);            // a forward pass follows every backward pass
+                    gout = layer2_chunk(q1, gout, t2 + 1, gbuf, mlp_int<ACT_SELECT>{}, m1);
+                    gbuf ^= 1;
+                }
+                float g[A];                                        // the actor's head decode, without the tanh
+                if constexpr (mlp_head4<Env>) {
+#pragma unroll
+                    for (int r = 0; r < A; ++r) g[r] = gout[r] + __shfl_xor(gout[r], 32);
+                } else {
+                    const int beta = (int)(e >> 4);
+#pragma unroll
+                    for (int r = 0; r < A; ++r) {
+                        const int src = 16 * (r >> 2) + (int)(e & 15u);
+                        const float v0 = __shfl(gout[r & 3] + gout[8 + (r & 3)], src);
+                        const float v1 = __shfl(gout[4 + (r & 3)] + gout[12 + (r & 3)], src);
+                        g[r] = beta ? v1 : v0;
+                    }
+                }
+                if (pk == 0 && writer && active && jq->grad_out) {   // the first gradient leaves here
+                    uint32_t lo = li;
+                    asm volatile("" : "+v"(lo));
+                    float *go = jq->grad_out + (size_t)it * q.act_step_stride;
+#pragma unroll
+                    for (int j = 0; j < A; ++j) (go + j * q.ld_act_out)[lo] = g[j];
+                }
+                if (active) {
+#pragma unroll
+                    for (int r = 0; r < A; ++r) {
+                        const float v = a[r] - jq->step * g[r];
+                        a[r] = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);      // (the select form: a NaN stays a NaN)
+                    }
+                }
+            }
+        } else if constexpr (SHIELD) {
             do {                                                   // (one pass unless SEARCH or GATE)
             // ---------------- safety critic on x = [s, a, 0]: the network (S + A, 1) ----------------
             auto x = [&](int k) __attribute__((always_inline)) {
@@ -414,7 +600,7 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
             if constexpr (C1.chunks == 1) {
                 __syncthreads();                            // the critic's layer 1 is in s_w[gbuf]
                 cfill(1, gbuf ^ 1, MLP_PIECES);
-                layer1_chunk(mlp_int<MLP_MT>{}, mlp_int<C1.records>{}, x, g1, gbuf);
+                layer1_chunk(mlp_int<MLP_MT>{}, mlp_int<C1.records>{}, x, g1, gbuf, mlp_int<ACT_RELU>{}, nullptr);
                 gbuf ^= 1;
             } else {
 #pragma unroll
@@ -422,7 +608,7 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
                     __syncthreads();                        // critic layer-1 chunk c1 is in s_w[gbuf]
                     if (c1 + 1 < C1.chunks) cfill(c1 + 1, gbuf ^ 1, C1.pieces);
                     else cfill(C1.chunks, gbuf ^ 1, MLP_PIECES);
-                    layer1_chunk(mlp_int<C1.tiles>{}, mlp_int<C1.records>{}, x, g1 + c1 * C1.tiles, gbuf);
+                    layer1_chunk(mlp_int<C1.tiles>{}, mlp_int<C1.records>{}, x, g1 + c1 * C1.tiles, gbuf, mlp_int<ACT_RELU>{}, nullptr);
                     gbuf ^= 1;
                 }
             }
@@ -443,7 +629,7 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
                     else if (it + 1 < q.n_steps) fill(0, gbuf ^ 1, L1.pieces);
                 }
                 else if (it + 1 < q.n_steps) fill(0, gbuf ^ 1, L1.pieces);   // the actor's layer 1 of the NEXT step
-                z4 = layer2_chunk(g1, z4, m2 + 1, gbuf);
+                z4 = layer2_chunk(g1, z4, m2 + 1, gbuf, mlp_int<ACT_RELU>{}, nullptr);
                 gbuf ^= 1;
             }
             if constexpr (GATE) {                                  // fold member `g_mem` into the running sums (the law, include/nig.h)
@@ -528,7 +714,7 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
         // ---------------- IndustrialEnv.step (both lane halves, identical results) ----------------
         const uint32_t orow = (uint32_t)it * q.out_stride;
         uint32_t lo = li;                                          // the lane's index in this step's output addresses
-        if constexpr (SEARCH || GATE) asm volatile("" : "+v"(lo)); // (formed here, step by step: no address is kept in registers across the passes)
+        if constexpr (SEARCH || GATE || PROJECT) asm volatile("" : "+v"(lo)); // (formed here, step by step: no address is kept in registers across the passes)
         const bool frozen = (ctr & NIG_CTR_DONE) != 0;
         if (writer && !frozen) {
             if (q.obs_out) {
@@ -546,7 +732,15 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
 #pragma unroll
                 for (int j = 0; j < A; ++j) (ao + j * q.ld_act_out)[lo] = a[j];
             }
-            if constexpr (SHIELD && !SEARCH && !GATE) {
+            if constexpr (PROJECT) {
+                if (jq->viol_out) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+                        if (c < jq->n_outputs) (jq->viol_out + (size_t)it * jq->c_step_stride + lo)[(size_t)c * jq->ld_c] = det_sigmoidf(j_z[c]);
+                }
+                if (jq->iters_out) (jq->iters_out + (uint32_t)it * q.out_stride)[lo] = j_iters;
+            }
+            if constexpr (SHIELD && !SEARCH && !GATE && !PROJECT) {
                 if (prob_out) (prob_out + (uint32_t)it * q.out_stride)[lo] = prob;
             }
             if constexpr (SEARCH) {
@@ -628,6 +822,13 @@ template <class Env>
 __global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_gated_kernel(const MlpGateArgs q)
 {
     rollout_mlp_body<Env, true, ENS_NONE, false, false, true>(q.m, q.cstreams, nullptr, q.threshold, nullptr, nullptr, nullptr, &q);
+}
+
+// Instantiated in the env's projected_*.hip translation unit only (launch_mlp_projected_env).
+template <class Env>
+__global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_projected_kernel(const MlpProjectArgs q)
+{
+    rollout_mlp_body<Env, true, ENS_NONE, false, false, false, true>(q.m, q.cstream, nullptr, q.threshold, nullptr, nullptr, nullptr, nullptr, &q);
 }
 
 // ENS = ENS_AVERAGE / ENS_VOTING.  Instantiated in the env's ensemble_*.hip translation unit only (launch_mlp_ensemble_env).

@@ -633,6 +633,137 @@ class SafetyEnsemblePolicy:
         return self.get_safe_action(observations)[0]
 
 
+class ConstraintProjectionPolicy:
+    """The reference's ConstrainedIQLAgent.get_safe_action (agents/safety_critical.py:240-370) over an actor and a constraint
+    predictor f(s, a) with one head column per constraint, kept on the GPU: the actor's action is kept where every
+    sigmoid(f_c) is below `threshold`; elsewhere it walks a <- clip(a - step * dG/da, -1, 1), G = sum_c relu(f_c), until every
+    logit is below `tolerance` or `max_iters` steps are taken (the reference: 10 steps of 0.1).  The arithmetic is the law
+    "nig-project-v1" of include/nig.h in torch (float32); the gradient is the analytic backward pass -- the transposed network
+    with a select on the forward pass's ReLU masks, derivative 0 at 0 -- not autograd.
+
+    `actor`: an MLPPolicy or a weight list; `predictor`: [(C1 [S+A,h], c1), (C2 [h,h], c2), (C3 [h,C], c3)], C in 1 .. 4.  When the
+    actor has the reference shape and the predictor three layers of hidden width <= 256 (padded to 256 by pad_safety_member:
+    the reference's ConstraintPredictor is 128 wide) and max_iters is at most 16 (`fusable`), evaluate_with_safety /
+    evaluate_episodes / evaluate_robustness run the projection fused into the env kernel
+    (BatchedIndustrialEnv.rollout_mlp_projected); otherwise through torch GEMMs."""
+    is_trained = True
+
+    def __init__(self, actor, predictor, threshold: float = 0.1, tolerance: float = 0.01, max_iters: int = 10, step: float = 0.1,
+                 device="cuda:0"):
+        import torch
+        self.actor = actor if hasattr(actor, "predict_device") else MLPPolicy(actor, device=device)
+        self.device = torch.device(getattr(self.actor, "device", device))
+        self.state_dim, self.action_dim = self.actor.state_dim, self.actor.action_dim
+        self.weights = self.actor.weights
+        self.predictor = [(np.asarray(W, dtype=f32).reshape(np.shape(W)[0], -1), np.asarray(b, dtype=f32).reshape(-1)) for W, b in predictor]
+        self.n_outputs = self.predictor[-1][0].shape[1]
+        if self.predictor[0][0].shape[0] != self.state_dim + self.action_dim or self.predictor[-1][1].shape != (self.n_outputs,):
+            raise ValueError(f"the constraint predictor must map S+A={self.state_dim + self.action_dim} inputs to its constraints, got "
+                             f"{[w.shape for w, _ in self.predictor]}")
+        self.threshold, self.tolerance, self.max_iters, self.step = float(threshold), float(tolerance), int(max_iters), float(step)
+        if not (np.isfinite(self.threshold) and np.isfinite(self.tolerance) and np.isfinite(self.step)):
+            raise ValueError("threshold, tolerance and step must be finite")
+        if self.max_iters < 1:
+            raise ValueError(f"max_iters must be at least 1, got {max_iters}")
+        self.predictor_layers = [(torch.as_tensor(W, device=self.device).contiguous(), torch.as_tensor(b, device=self.device).contiguous())
+                                 for W, b in self.predictor]
+        p = self.predictor
+        h = p[0][0].shape[1]
+        self.fusable = (bool(getattr(self.actor, "fusable", False)) and len(p) == 3 and h <= 256 and p[1][0].shape == (h, h)
+                        and p[2][0].shape[0] == h and 1 <= self.n_outputs <= 4 and self.max_iters <= _lib.MAX_PROJECT_ITERS)
+
+    @classmethod
+    def from_agent(cls, actor_agent, ciql_agent, device="cuda:0", max_iters: int = 10, step: float = 0.1):
+        """From a reference agent with an actor (MLPPolicy.from_agent) and a ConstrainedIQLAgent: the predictor
+        ciql_agent.constraint_state.params = {"params": {"layers_0", "layers_1", "constraint_head"}},
+        ciql_agent.uncertainty_threshold as the acceptance threshold and ciql_agent.constraint_tolerance as the tolerance
+        (safety_critical.py:330, 352; the step count and size are the reference's constants 10 and 0.1)."""
+        predictor = _named_layers(ciql_agent.constraint_state.params, ("layers_0", "layers_1", "constraint_head"), "constraint predictor")
+        return cls(MLPPolicy.from_agent(actor_agent, device=device), predictor, threshold=ciql_agent.uncertainty_threshold,
+                   tolerance=ciql_agent.constraint_tolerance, max_iters=max_iters, step=step, device=device)
+
+    def install(self, env):
+        """Install actor and predictor on a BatchedIndustrialEnv for rollout_mlp_projected(n, self.max_iters, self.step)."""
+        env.set_mlp_policy(self.weights)
+        env.set_mlp_constraint(pad_safety_member(self.predictor), self.threshold, self.tolerance)
+
+    # ---- device (torch) forms of the law ----
+    def _forward_device(self, obs, actions):
+        """(z [n, C], m1 [n, h], m2 [n, h]): the predictor's logits and the masks z > 0 of its two hidden layers."""
+        import torch
+        (W1, b1), (W2, b2), (W3, b3) = self.predictor_layers
+        y1 = torch.addmm(b1, torch.cat([obs, actions], dim=1), W1)
+        y2 = torch.addmm(b2, torch.relu(y1), W2)
+        return torch.addmm(b3, torch.relu(y2), W3), y1 > 0, y2 > 0
+
+    def _gradient_device(self, z, m1, m2):
+        """dG/da [n, A], G = sum_c relu(f_c): W1[S:S+A, :] (m1 . (W2 (m2 . (W3 d)))), d_c = (z_c > 0)."""
+        import torch
+        (W1, _), (W2, _), (W3, _) = self.predictor_layers
+        zero = torch.zeros((), dtype=z.dtype, device=z.device)
+        d = torch.where(z > 0, torch.ones_like(z), torch.zeros_like(z))
+        g2 = torch.where(m2, d @ W3.t(), zero)
+        g1 = torch.where(m1, g2 @ W2.t(), zero)
+        return g1 @ W1[self.state_dim:].t()
+
+    def violation_probs_device(self, obs, actions):
+        """sigmoid(f(obs, actions)) [n, C]."""
+        import torch
+        return torch.sigmoid(self._forward_device(obs, actions)[0])
+
+    def get_safe_action_device(self, obs, preferred=None):
+        """get_safe_action on device tensors, a batch of states at once: (actions [n, A], {"violations" [n, C]: sigmoid(f) of
+        the returned action, "projected" [n] bool, "iterations" [n] int32: gradient steps taken, -1 where the action was kept})."""
+        import torch
+        a = (self.actor.predict_device(obs) if preferred is None else preferred).clone()
+        z, m1, m2 = self._forward_device(obs, a)
+        projected = ~(torch.sigmoid(z) < self.threshold).all(dim=1)
+        active = projected.clone()
+        iters = torch.where(projected, 0, -1).to(torch.int32)
+        one = torch.ones((), dtype=a.dtype, device=a.device)
+        for _ in range(self.max_iters):
+            active = active & ~(z < self.tolerance).all(dim=1)          # (the raw logits, as the reference; false on NaN)
+            if not bool(active.any()):
+                break
+            v = a - self.step * self._gradient_device(z, m1, m2)
+            v = torch.where(v < -1, -one, torch.where(v > 1, one, v))   # (the select form: a NaN stays a NaN)
+            a = torch.where(active[:, None], v, a)
+            iters = iters + active.to(torch.int32)
+            z2, n1, n2 = self._forward_device(obs, a)
+            z, m1, m2 = torch.where(active[:, None], z2, z), torch.where(active[:, None], n1, m1), torch.where(active[:, None], n2, m2)
+        return a, {"violations": torch.sigmoid(z), "projected": projected, "iterations": iters}
+
+    def predict_device(self, obs):
+        return self.get_safe_action_device(obs)[0]
+
+    # ---- host forms (the reference's contract) ----
+    def _host(self, x, width):
+        import torch
+        t = torch.as_tensor(np.asarray(x, dtype=f32), device=self.device)
+        return t.reshape(-1, width), t.dim() == 1
+
+    def violation_probs(self, observations, actions):
+        """sigmoid(f) as a NumPy array, [C] for a single observation."""
+        o, single = self._host(observations, self.state_dim)
+        p = self.violation_probs_device(o, self._host(actions, self.action_dim)[0]).cpu().numpy()
+        return p[0] if single else p
+
+    def get_safe_action(self, observations, preferred=None):
+        """ConstrainedIQLAgent.get_safe_action on host arrays, `preferred` defaulting to the actor's action: (action,
+        {"violations", "projected", "iterations"}) -- the reference's dict plus the step count (arrays for a batch of
+        observations, whose rows are decided one by one)."""
+        o, single = self._host(observations, self.state_dim)
+        pa = None if preferred is None else self._host(preferred, self.action_dim)[0]
+        a, info = self.get_safe_action_device(o, pa)
+        a, info = a.cpu().numpy(), {k: v.cpu().numpy() for k, v in info.items()}
+        if single:
+            return a[0], {"violations": info["violations"][0], "projected": bool(info["projected"][0]), "iterations": int(info["iterations"][0])}
+        return a, info
+
+    def predict(self, observations, deterministic: bool = True):
+        return self.get_safe_action(observations)[0]
+
+
 def ensemble_active_weights(weights, n_members: int, method: str):
     """The weights np.average receives in agents/ensemble.py:236-249 and their NumPy sum: the FIRST n_members entries of the
     agent's weight vector (whichever members were trained), divided by their sum for "mean", as they are for "weighted"."""

@@ -139,7 +139,7 @@ def _disturbed_route(agent, env):
 def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
     """Where `agent` runs on `env`, and its installation there -- the routing _evaluate_batched and episodes.evaluate_episodes
     share.  Returns (agent, rollout, disturbed): `rollout` is the env method that plays n closed-loop steps with the agent in the
-    env kernel (rollout_policy, rollout_mlp, rollout_mlp_safe, rollout_mlp_search, rollout_mlp_gated, rollout_mlp_ensemble or a _disturbed twin; policy, weights,
+    env kernel (rollout_policy, rollout_mlp, rollout_mlp_safe, rollout_mlp_search, rollout_mlp_gated, rollout_mlp_projected, rollout_mlp_ensemble or a _disturbed twin; policy, weights,
     shield, ensemble and disturbance are installed on the handle), or None -- the agent stays on the host and takes the
     per-step loop; `agent` may come back upgraded (a reference EnsembleAgent as an EnsemblePolicy); `disturbed` names the
     fused route of a disturbance.Disturbed ("fused-policy" / "fused-mlp": the caller removes the disturbance afterwards).
@@ -157,6 +157,7 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
             pass
     ensemble = plain and hasattr(agent, "install") and getattr(agent, "fusable", False) and env.state_dim % 2 == 0 and env.action_dim <= 16
     gated = ensemble and hasattr(agent, "max_uncertainty")        # SafetyEnsemblePolicy: its install() puts actor and members on the handle
+    projecting = ensemble and hasattr(agent, "max_iters")         # ConstraintProjectionPolicy: install() puts actor and predictor on the handle
     fused_mlp = not hasattr(agent, "install") and getattr(agent, "fusable", False) and plain
     shielded = fused_mlp and getattr(agent, "safety_weights", None) is not None and hasattr(agent, "threshold")
     searching = shielded and hasattr(agent, "n_candidates")       # MLPPolicy.searching(): get_safe_action instead of the halving
@@ -167,7 +168,7 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
             disturbed = route
             (env.set_policy if route == "fused-policy" else lambda a: env.set_mlp_policy(a.weights))(inner)
             env.set_disturbance(agent.disturbance)
-        device_policy = ensemble = gated = fused_mlp = shielded = searching = False
+        device_policy = ensemble = gated = projecting = fused_mlp = shielded = searching = False
     if disturbed:
         device_policy = True
     elif device_policy:
@@ -184,7 +185,9 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
     rollout = None
     if device_policy:
         rollout = (env.rollout_policy_disturbed if disturbed == "fused-policy" else env.rollout_mlp_disturbed if disturbed
-                   else env.rollout_mlp_gated if gated else env.rollout_mlp_ensemble if ensemble
+                   else env.rollout_mlp_gated if gated
+                   else (lambda n, *a, **k: env.rollout_mlp_projected(n, agent.max_iters, agent.step, *a, **k)) if projecting
+                   else env.rollout_mlp_ensemble if ensemble
                    else (lambda n, *a, **k: env.rollout_mlp_search(n, agent.n_candidates, *a, **k)) if searching
                    else env.rollout_mlp_safe if shielded else env.rollout_mlp if fused_mlp
                    else env.rollout_policy)
