@@ -249,8 +249,69 @@ int nig_bind_state(nig_handle *h, float *state, int64_t ld);
 /* env.remove_safety_constraint(name) for a built-in constraint (base.py:224-228): bit k of
  * `mask` keeps constraint k enabled (default 0x7).  A disabled constraint is neither
  * counted nor penalised.  Constraints ADDED by the user (base.py:220-222) are arbitrary
- * Python callables and stay on the host side of the binding. */
+ * Python callables upstream; the declarative ones -- boxes over state and action rows -- run on the device
+ * (nig_set_limits below), every other callable stays on the host side of the binding. */
 int nig_set_constraint_mask(nig_handle *h, uint32_t mask);
+
+/*
+ * env.add_safety_constraint(c) for box constraints ("nig-limits-v1"; base.py:157-213,220-222).
+ *
+ * An added constraint lists rows of the step's PRE-STATE (bit r < S of `mask`: state row r) and of the CLIPPED action (bit
+ * S + j: action row j) -- the inputs the built-in constraints get -- and gives each listed row a closed interval [lo, hi] of
+ * float32 bounds (+-inf allowed).  It is violated when some listed row x has !(lo <= x && x <= hi): a NaN in a listed row
+ * violates, unlisted rows are never looked at.  Comparisons are exact; a float64 action (nig_step64_limited) is compared
+ * against the bound widened to double.
+ * Reward, in the reference's order and in the env's reward type R (float32 for ChemicalReactor with float32 actions, double
+ * otherwise):  r = reward(next, a);  r = R(r + R(penalty_k)) for each violated enabled built-in k = 0, 1, 2;
+ * r = R(r + R(penalty_c)) for each violated added constraint in installation order;  then, if ANY critical constraint (built-in
+ * or added) was violated:  terminated = true and r = r - 1000, once.
+ * The added constraints count: the episode's violation_count and total_violations, the tally rows VIOL, CRIT and SHUTDOWN,
+ * and SATISFIED / CONSTRAINTS, which take (enabled built-ins + added) per step.
+ * (The single env's Python path -- envs.py, arbitrary callables -- subtracts the 1000 BEFORE it adds the added constraints'
+ * penalties when a built-in critical violation and an added violation fall on the same step; the device follows base.py's
+ * order.  The two differ by floating-point rounding of that one reward at most.)
+ *
+ * The main flag word keeps its meaning: the VIOL bits, NVIOL and NCRIT describe the built-ins; TERMINATED and SHUTDOWN also
+ * fire for an added critical violation.  A second word per lane and step, xflags_out, carries the added constraints:
+ * bit c (0-3): added constraint c violated; bits 4-6: how many were; bits 8-10: how many critical ones were; 0 for a frozen
+ * lane.
+ *
+ * nig_set_limits copies n <= NIG_MAX_LIMITS constraints from the HOST array `limits` into the handle (it waits for the copy
+ * on `stream`); n == 0 removes them.  NIG_ERR_INVALID (the installed set stays): n outside 0 .. NIG_MAX_LIMITS, a mask bit
+ * >= S + A, an empty mask, lo > hi or a NaN bound on a listed row, a NaN penalty, or (built-in constraints + n) *
+ * max_episode_steps > 65535 (the counter word keeps the episode's violations in 16 bits).  NIG_ERR_UNSUPPORTED: the
+ * Advanced envs, which override step() wholesale.
+ * While limits are installed, every entry point that steps the env EXCEPT the _limited ones below returns
+ * NIG_ERR_UNSUPPORTED before anything is launched or written (nig_step*, nig_rollout*, the MFMA families, nig_plan_*,
+ * nig_step_host*, the mixed entry points given such a handle, nig_collect_episodes, which decodes the main flag word only).
+ */
+#define NIG_MAX_LIMITS 4
+#define NIG_LIMIT_ROWS 48              /* row capacity of a constraint's bounds (S + A <= 38) */
+typedef struct nig_limit {
+    uint64_t mask;                     /* bit r < S: state row r; bit S + j: action row j */
+    float lo[NIG_LIMIT_ROWS];          /* bounds of row (bit index) r; read for listed rows only */
+    float hi[NIG_LIMIT_ROWS];
+    double penalty;                    /* SafetyConstraint.penalty */
+    int32_t critical;                  /* SafetyConstraint.critical */
+    int32_t reserved;
+} nig_limit;
+int nig_set_limits(nig_handle *h, int32_t n, const nig_limit *limits /* host */, void *stream);
+/* number of installed limits (0 .. NIG_MAX_LIMITS), -1 for a NULL handle */
+int nig_get_limit_count(const nig_handle *h);
+#define NIG_XFLAG_NVIOL_SHIFT 4
+#define NIG_XFLAG_NCRIT_SHIFT 8
+
+/* nig_step / nig_step64 under the installed limits (NIG_ERR_INVALID without any): every argument as there, plus
+ * xflags_out uint32 [B] (may be NULL).  One plain 256-lane kernel form; finishing lanes of an auto-reset handle restart in
+ * place with the parent's draws. */
+int nig_step_limited(nig_handle *h, const float *actions, int64_t ld_act,
+                     const double *step_noise, const double *reset_noise, int64_t ld_noise,
+                     float *reward_out, double *reward64_out, uint32_t *flags_out, uint32_t *xflags_out,
+                     float *final_obs, int64_t ld_obs, void *stream);
+int nig_step64_limited(nig_handle *h, const double *actions, int64_t ld_act,
+                       const double *step_noise, const double *reset_noise, int64_t ld_noise,
+                       float *reward_out, double *reward64_out, uint32_t *flags_out, uint32_t *xflags_out,
+                       float *final_obs, int64_t ld_obs, void *stream);
 
 /*
  * IndustrialEnv.reset (base.py:133-155) for the lanes selected by `mask`
@@ -481,6 +542,21 @@ int nig_set_mlp_policy(nig_handle *h, int32_t hidden, const float *W1, const flo
 int nig_rollout_mlp(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out,
                     int64_t out_stride, float *obs_out, int64_t obs_step_stride,
                     float *act_out, int64_t ld_act, int64_t act_step_stride, void *stream);
+
+/*
+ * nig_rollout_policy / nig_rollout_mlp under the installed limits ("nig-limits-v1", nig_set_limits): every argument and
+ * refusal as the twin's, plus xflags_out uint32 [n_steps][>= B] (row k at xflags_out + k * out_stride; may be NULL; a frozen
+ * lane's word is 0).  NIG_ERR_INVALID without installed limits.  With limits that no state can violate (infinite bounds)
+ * every output equals the twin's but the tally's SATISFIED / CONSTRAINTS rows.  The policy twin has the one-wave kernel form
+ * only.  The kernels are the twins' bodies with the step law of nig_step_limited, so a rollout equals nig_step_limited fed
+ * with the rollout's own actions.
+ */
+int nig_rollout_policy_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out,
+                               int64_t out_stride, float *obs_out, int64_t obs_step_stride,
+                               float *act_out, int64_t ld_act, int64_t act_step_stride, uint32_t *xflags_out, void *stream);
+int nig_rollout_mlp_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out,
+                            int64_t out_stride, float *obs_out, int64_t obs_step_stride,
+                            float *act_out, int64_t ld_act, int64_t act_step_stride, uint32_t *xflags_out, void *stream);
 
 /*
  * Safety-critic shield of the reference agents' predict_with_safety (agents/cql.py, iql.py, td3bc.py):

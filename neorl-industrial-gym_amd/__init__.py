@@ -11,7 +11,7 @@ Everything numerical runs in libnig.so (csrc/, C ABI in include/nig.h).  There i
 fallback: importing the package without the built extension raises ImportError.
 """
 from . import _lib
-from .core import DatasetQuality, SafetyConstraint, SafetyMetrics
+from .core import BoxConstraint, DatasetQuality, SafetyConstraint, SafetyMetrics
 
 _lib.lib()   # fail loudly here if libnig.so is missing
 
@@ -43,7 +43,7 @@ def tune(split_blocks=None, wide_min_blocks=None):
 __version__ = "0.8.0"        # 0.8.0: rollout_sampled, then EnsemblePolicy / rollout_mlp_ensemble, evaluate_robustness, EpisodeLog / evaluate_episodes, SafetyEnsemblePolicy / rollout_mlp_gated, ConstraintProjectionPolicy / rollout_mlp_projected (all additive; the number is pinned by tests/test_rollout_sampled_host.py); generator "nig-philox-v3" since round 4 (v2 + PowerGrid's reset load factors from spare low bytes; libnig: nig_version())
 GENERATOR = "nig-philox-v3"
 __all__ = [
-    "__version__", "DatasetQuality", "SafetyConstraint", "SafetyMetrics", "IndustrialEnv",
+    "__version__", "BoxConstraint", "DatasetQuality", "SafetyConstraint", "SafetyMetrics", "IndustrialEnv",
     "ChemicalReactorEnv", "PowerGridEnv", "RobotAssemblyEnv", "AdvancedChemicalReactorEnv", "AdvancedPowerGridEnv",
     "HVACControlEnv", "WaterTreatmentEnv", "SteelAnnealingEnv", "SupplyChainEnv", "BatchedIndustrialEnv", "MixedBatchedEnv", "StepInfo",
     "make", "make_batched", "evaluate_with_safety", "uniform_action_statistics", "tune", "DevicePolicy", "MLPPolicy", "EnsemblePolicy", "SafetyEnsemblePolicy", "ConstraintProjectionPolicy", "behaviour_policy", "constant_agent",

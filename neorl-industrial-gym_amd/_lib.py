@@ -73,6 +73,16 @@ class DisturbanceStruct(C.Structure):
                 ("hold", C.c_int32)]
 
 
+MAX_LIMITS, LIMIT_ROWS = 4, 48        # nig_set_limits: added box constraints per handle, row capacity of their bounds
+XFLAG_NVIOL_SHIFT, XFLAG_NCRIT_SHIFT = 4, 8
+
+
+class LimitStruct(C.Structure):
+    """nig_limit (include/nig.h, "nig-limits-v1")."""
+    _fields_ = [("mask", C.c_uint64), ("lo", C.c_float * LIMIT_ROWS), ("hi", C.c_float * LIMIT_ROWS), ("penalty", C.c_double),
+                ("critical", C.c_int32), ("reserved", C.c_int32)]
+
+
 MIXED_MAX_SEGMENTS = 12
 
 
@@ -108,6 +118,12 @@ PROTOTYPES = {
     "nig_get_counter": (ci, [vp, P(u32)]),
     "nig_set_counter": (ci, [vp, u32]),
     "nig_set_constraint_mask": (ci, [vp, u32]),
+    "nig_set_limits": (ci, [vp, i32, P(LimitStruct), vp]),
+    "nig_get_limit_count": (ci, [vp]),
+    "nig_step_limited": (ci, [vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp]),
+    "nig_step64_limited": (ci, [vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp]),
+    "nig_rollout_policy_limited": (ci, CLOSED_LOOP + [vp, vp]),
+    "nig_rollout_mlp_limited": (ci, CLOSED_LOOP + [vp, vp]),
     "nig_reset": (ci, [vp, vp, vp, i64, vp]),
     "nig_step": (ci, [vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, i64, vp]),
     "nig_fill_actions": (ci, [vp, u32, vp, i64, vp]),

@@ -13,7 +13,24 @@ import numpy as np
 import torch
 
 from . import _lib
-from .core import SafetyMetrics, make_box
+from .core import BoxConstraint, SafetyConstraint, SafetyMetrics, make_box
+
+# the built-in constraints' names (the reference envs' own; remove_safety_constraint(name) clears the matching mask bit)
+BUILTIN_CONSTRAINTS = {
+    "ChemicalReactor-v0": ("temperature_limit", "pressure_limit", "level_safety"),
+    "PowerGrid-v0": ("frequency_stability", "voltage_limits", "generation_limits"),
+    "RobotAssembly-v0": ("force_limits", "collision_avoidance", "velocity_limits"),
+}
+
+
+def _builtin_names(env_id, n):
+    if env_id in BUILTIN_CONSTRAINTS:
+        return list(BUILTIN_CONSTRAINTS[env_id])
+    from . import spec_plants
+    plant = {"HVACControl-v0": "HVAC", "WaterTreatment-v0": "WATER", "SteelAnnealing-v0": "STEEL", "SupplyChain-v0": "SUPPLY"}.get(env_id)
+    if plant:
+        return [c[0] for c in getattr(spec_plants, plant)["constraints"]]
+    return [f"constraint_{k}" for k in range(n)]
 
 ENV_IDS = {"ChemicalReactor-v0": 0, "PowerGrid-v0": 1, "RobotAssembly-v0": 2,
            # candidate rows: registered upstream (utils.py:30-31) but not instantiable there
@@ -53,11 +70,17 @@ class StepInfo:
     Fields are torch tensors on the env's device, decoded on first use:
       terminated, truncated, done, violation_count, critical_violations, critical_shutdown,
       constraint_violated [3,B], did_reset, inactive, step.
+    With added box constraints on the env (add_safety_constraint) `xflags` is the step's second word per lane and the counts,
+    constraint_violated ([3 + n_added, B], the added ones behind the built-ins) and safety_metrics() cover all constraints.
     """
 
-    def __init__(self, flags: torch.Tensor, n_constraints: int = 3):
+    def __init__(self, flags: torch.Tensor, n_constraints: int = 3, xflags: Optional[torch.Tensor] = None, n_added: int = 0,
+                 n_enabled: Optional[int] = None):
         self.flags = flags
         self.n_constraints = n_constraints
+        self.xflags = xflags
+        self.n_added = int(n_added) if xflags is not None else 0
+        self.n_enabled = n_constraints if n_enabled is None else int(n_enabled)      # built-ins still enabled (set_constraint_mask)
 
     @property
     def terminated(self):
@@ -73,11 +96,13 @@ class StepInfo:
 
     @property
     def violation_count(self):
-        return ((self.flags >> _lib.FLAG_NVIOL_SHIFT) & 3) + ((self.flags >> 13) & 1) * 4
+        n = ((self.flags >> _lib.FLAG_NVIOL_SHIFT) & 3) + ((self.flags >> 13) & 1) * 4
+        return n if self.xflags is None else n + ((self.xflags >> _lib.XFLAG_NVIOL_SHIFT) & 7)
 
     @property
     def critical_violations(self):
-        return (self.flags >> _lib.FLAG_NCRIT_SHIFT) & 3
+        n = (self.flags >> _lib.FLAG_NCRIT_SHIFT) & 3
+        return n if self.xflags is None else n + ((self.xflags >> _lib.XFLAG_NCRIT_SHIFT) & 7)
 
     @property
     def critical_shutdown(self):
@@ -85,8 +110,11 @@ class StepInfo:
 
     @property
     def constraint_violated(self):
-        return torch.stack([((self.flags >> (_lib.FLAG_VIOL_SHIFT + k)) & 1) != 0 for k in range(3)]
-                           + [((self.flags >> 12) & 1) != 0])[:self.n_constraints]
+        builtin = torch.stack([((self.flags >> (_lib.FLAG_VIOL_SHIFT + k)) & 1) != 0 for k in range(3)]
+                              + [((self.flags >> 12) & 1) != 0])[:self.n_constraints]
+        if self.xflags is None:
+            return builtin
+        return torch.cat([builtin, torch.stack([((self.xflags >> c) & 1) != 0 for c in range(self.n_added)])])
 
     @property
     def did_reset(self):
@@ -106,8 +134,13 @@ class StepInfo:
         nv = ((f >> _lib.FLAG_NVIOL_SHIFT) & 3) + ((f >> 13) & 1) * 4
         nc = (f >> _lib.FLAG_NCRIT_SHIFT) & 3
         n = self.n_constraints
+        if self.xflags is not None:
+            x = int(self.xflags[lane].item())
+            nv += (x >> _lib.XFLAG_NVIOL_SHIFT) & 7
+            nc += (x >> _lib.XFLAG_NCRIT_SHIFT) & 7
+            n = self.n_enabled + self.n_added
         return SafetyMetrics(constraints_satisfied=n - nv, total_constraints=n, violation_count=nv,
-                             critical_violations=nc, safety_score=(n - nv) / n)
+                             critical_violations=nc, safety_score=(n - nv) / n if n else 1.0)
 
 
 class BatchedIndustrialEnv:
@@ -195,6 +228,10 @@ class BatchedIndustrialEnv:
         self.reward = torch.zeros(B, dtype=torch.float32, device=self.device)
         self.reward64 = torch.zeros(B, dtype=torch.float64, device=self.device)
         self.flags = torch.zeros(B, dtype=torch.int32, device=self.device)
+        self.xflags = torch.zeros(B, dtype=torch.int32, device=self.device)      # the added constraints' word of the last step
+        self._cmask = (1 << int(self.spec.n_constraints)) - 1
+        self._builtin_names = _builtin_names(env_id, int(self.spec.n_constraints))
+        self._added = []                # BoxConstraints installed on the handle, in installation order
         self._act_soa = torch.zeros(self.action_dim, ld, dtype=torch.float32, device=self.device)
         self.observation_space = make_box(-np.inf, np.inf, (self.state_dim,), np.float32)
         self.action_space = make_box(-1.0, 1.0, (self.action_dim,), np.float32)
@@ -238,6 +275,62 @@ class BatchedIndustrialEnv:
 
     def set_constraint_mask(self, mask: int):
         _lib.check(self._L.nig_set_constraint_mask(self._h, C.c_uint32(mask)))
+        self._cmask = int(mask) & ((1 << int(self.spec.n_constraints)) - 1)
+
+    # ---- added safety constraints (base.py:220-228; include/nig.h "nig-limits-v1") --------------------------------------------
+    @property
+    def safety_constraints(self):
+        """The constraints in force, the reference's list (base.py:51): the enabled built-ins as names-only SafetyConstraint
+        records (their check runs in the kernel), then the added BoxConstraints in installation order."""
+        builtin = [SafetyConstraint(name=n, check_fn=None, penalty=float(self.spec.penalty[k]) if k < 3 else 0.0,
+                                    critical=bool(self.spec.critical[k]) if k < 3 else False, description="built-in (device)")
+                   for k, n in enumerate(self._builtin_names) if (self._cmask >> k) & 1]
+        return builtin + list(self._added)
+
+    @property
+    def has_limits(self) -> bool:
+        return bool(self._added)
+
+    def _install_limits(self, added):
+        n = len(added)
+        arr = (_lib.LimitStruct * max(n, 1))()
+        for c, box in enumerate(added):
+            mask, rows = box.limit_rows(self.state_dim, self.action_dim)
+            arr[c].mask = mask
+            for bit, (lo, hi) in rows.items():
+                arr[c].lo[bit], arr[c].hi[bit] = float(lo), float(hi)
+            arr[c].penalty, arr[c].critical = float(box.penalty), int(bool(box.critical))
+        with torch.cuda.device(self._dev_index):
+            _lib.check(self._L.nig_set_limits(self._h, n, arr, self._stream()))
+        self._added = list(added)
+
+    def add_safety_constraint(self, constraint):
+        """env.add_safety_constraint (base.py:220-222) for a BoxConstraint: from the next step on it is checked, penalised and
+        counted on the device beside the built-ins (at most MAX_LIMITS added ones).  step(), rollout_policy_limited() and
+        rollout_mlp_limited() know the added constraints; every other stepping entry point refuses while any is installed."""
+        if not isinstance(constraint, BoxConstraint):
+            raise TypeError("BatchedIndustrialEnv evaluates added constraints on the device and takes BoxConstraint only (declarative "
+                            "bounds on state / action rows); an arbitrary check_fn callable runs on the single env: make(env_id)"
+                            ".add_safety_constraint(c)")
+        if len(self._added) >= _lib.MAX_LIMITS:
+            raise ValueError(f"at most {_lib.MAX_LIMITS} added constraints per batched env")
+        self._install_limits(self._added + [constraint])
+
+    def remove_safety_constraint(self, name: str):
+        """env.remove_safety_constraint (base.py:224-228): every constraint of that name goes -- an added one from the device
+        table, a built-in one by clearing its bit of the constraint mask."""
+        kept = [c for c in self._added if c.name != name]
+        if len(kept) != len(self._added):
+            self._install_limits(kept)
+        for k, n in enumerate(self._builtin_names):
+            if n == name and (self._cmask >> k) & 1:
+                self.set_constraint_mask(self._cmask & ~(1 << k))
+
+    def _refuse_limits(self, what: str):
+        if self._added:
+            raise RuntimeError(f"{what} does not know the added safety constraints ({', '.join(c.name for c in self._added)}): "
+                               "remove them first (remove_safety_constraint), or use evaluate_with_safety / step / "
+                               "rollout_policy_limited / rollout_mlp_limited")
 
     @property
     def current_step(self):
@@ -312,11 +405,21 @@ class BatchedIndustrialEnv:
             assert final_obs.dtype == torch.float32 and final_obs.shape[0] == self.state_dim and final_obs.stride(1) == 1
             ld_obs = final_obs.stride(0)
         with torch.cuda.device(self._dev_index):
-            _lib.check((self._L.nig_step64 if act64 else self._L.nig_step)(
-                self._h, _ptr(act), ld_act, _ptr(sn), _ptr(rn), B, _ptr(self.reward), _ptr(self.reward64),
-                _ptr(self.flags), _ptr(final_obs), ld_obs, self._stream()))
-        info = StepInfo(self.flags, int(self.spec.n_constraints))
+            if self._added:         # the added constraints are part of the step law: nig_step_limited, a second word per lane
+                _lib.check((self._L.nig_step64_limited if act64 else self._L.nig_step_limited)(
+                    self._h, _ptr(act), ld_act, _ptr(sn), _ptr(rn), B, _ptr(self.reward), _ptr(self.reward64),
+                    _ptr(self.flags), _ptr(self.xflags), _ptr(final_obs), ld_obs, self._stream()))
+            else:
+                _lib.check((self._L.nig_step64 if act64 else self._L.nig_step)(
+                    self._h, _ptr(act), ld_act, _ptr(sn), _ptr(rn), B, _ptr(self.reward), _ptr(self.reward64),
+                    _ptr(self.flags), _ptr(final_obs), ld_obs, self._stream()))
+        info = self._step_info()
         return self.obs, self.reward, info.terminated, info.truncated, info
+
+    def _step_info(self) -> StepInfo:
+        if self._added:
+            return StepInfo(self.flags, int(self.spec.n_constraints), self.xflags, len(self._added), bin(self._cmask).count("1"))
+        return StepInfo(self.flags, int(self.spec.n_constraints))
 
     def step_raw(self, act_soa: torch.Tensor, ld_act: int, reward=True, reward64=False, flags=True):
         """Hot-loop form: no tensor conversions, no decoding; `act_soa` is float32 [A, >=B]."""
@@ -635,6 +738,18 @@ class BatchedIndustrialEnv:
         act_out: float32 [n_steps, A, >=B]; reward_out / flags_out: [n_steps, >=B] or [B]."""
         self._closed_loop(self._L.nig_rollout_policy, n_steps, reward_out, flags_out, obs_out, act_out)
 
+    def rollout_policy_limited(self, n_steps: int, reward_out=None, flags_out=None, obs_out=None, act_out=None, xflags_out=None):
+        """rollout_policy() under the added safety constraints (add_safety_constraint; "nig-limits-v1"): xflags_out int32
+        [n_steps, >=B] (the row stride of reward_out / flags_out) is the added constraints' word of every step -- bit c: added
+        constraint c violated, bits 4-6 how many, bits 8-10 how many critical ones."""
+        self._closed_loop(self._L.nig_rollout_policy_limited, n_steps, reward_out, flags_out, obs_out, act_out,
+                          rows=[("xflags_out", xflags_out, torch.int32)])
+
+    def rollout_mlp_limited(self, n_steps: int, reward_out=None, flags_out=None, obs_out=None, act_out=None, xflags_out=None):
+        """rollout_mlp() under the added safety constraints; outputs as rollout_policy_limited()."""
+        self._closed_loop(self._L.nig_rollout_mlp_limited, n_steps, reward_out, flags_out, obs_out, act_out,
+                          rows=[("xflags_out", xflags_out, torch.int32)])
+
     # ------------------------------------------------------------------
     def set_disturbance(self, disturbance):
         """Install the sensor / actuator noise (disturbance.Disturbance) the _disturbed rollouts apply; None removes it.
@@ -672,6 +787,7 @@ class BatchedIndustrialEnv:
         the upstream episode count.  Needs batch >= episodes*scale and autoreset=False.
         Returns the D4RL-style dict as torch tensors on the device (episode-major order)."""
         from .policies import DATASET_SHAPE, behaviour_policy
+        self._refuse_limits("get_dataset")
         assert not self.autoreset, "dataset generation needs autoreset=False (one episode per lane)"
         n_eps, cap = DATASET_SHAPE[self.env_id][quality]
         n_eps *= int(scale)
@@ -750,6 +866,16 @@ class BatchedIndustrialEnv:
         out = torch.empty(5, self.batch, dtype=torch.int32, device=self.device)
         with torch.cuda.device(self._dev_index):
             _lib.check(self._L.nig_get_safety_metrics(self._h, _ptr(self.flags), _ptr(out), self.batch, self._stream()))
+        if self._added:             # the added constraints of the last step: counted in, satisfied where they did not fire
+            live = (self.flags & _lib.FLAG_INACTIVE) == 0
+            nv = torch.where(live, (self.xflags >> _lib.XFLAG_NVIOL_SHIFT) & 7, torch.zeros_like(self.xflags))
+            nc = torch.where(live, (self.xflags >> _lib.XFLAG_NCRIT_SHIFT) & 7, torch.zeros_like(self.xflags))
+            n = torch.where(live, torch.full_like(nv, len(self._added)), torch.zeros_like(nv))
+            out[0] += n - nv
+            out[1] += n
+            out[2] += nv
+            out[3] += nc
+            out[4] += n - nv
         return out
 
     def episode_log(self, capacity: int, ld: Optional[int] = None):

@@ -32,6 +32,49 @@ class SafetyConstraint:
     description: str = ""
 
 
+class BoxConstraint(SafetyConstraint):
+    """A SafetyConstraint that is a box over rows of the step's pre-state and clipped action ("nig-limits-v1", include/nig.h):
+    `bounds` maps ("state", r) / ("action", j) to a closed interval (lo, hi) of float32 bounds (+-inf allowed).  It holds while
+    every listed row x has lo <= x and x <= hi; a NaN in a listed row violates, unlisted rows are never looked at.  Its
+    check_fn is that statement in NumPy, so it works as any other constraint on the single env (and in the reference); being
+    declarative, it is also what BatchedIndustrialEnv.add_safety_constraint evaluates on the device."""
+
+    def __init__(self, name: str, bounds, penalty: float, critical: bool = False, description: str = ""):
+        rows = {}
+        for key, (lo, hi) in dict(bounds).items():
+            kind, r = key
+            if kind not in ("state", "action") or int(r) != r or int(r) < 0:
+                raise ValueError(f"BoxConstraint row {key!r}: ('state', r) or ('action', j) with a non-negative index")
+            lo, hi = np.float32(lo), np.float32(hi)
+            if not lo <= hi:
+                raise ValueError(f"BoxConstraint row {key!r}: lo > hi or a NaN bound")
+            rows[(kind, int(r))] = (lo, hi)
+        if not rows:
+            raise ValueError("BoxConstraint needs at least one row")
+        self.bounds = rows
+        super().__init__(name=name, check_fn=self.holds, penalty=float(penalty), critical=bool(critical), description=description)
+
+    def holds(self, state, action) -> bool:
+        """True while the constraint holds (SafetyConstraint.check_fn): exact comparisons, a float64 element against the
+        float32 bound widened by NumPy's promotion."""
+        for (kind, r), (lo, hi) in self.bounds.items():
+            x = (state if kind == "state" else action)[r]
+            if not (lo <= x and x <= hi):
+                return False
+        return True
+
+    def limit_rows(self, state_dim: int, action_dim: int):
+        """(mask, {bit: (lo, hi)}) in nig_limit's numbering: bit r < S is state row r, bit S + j action row j."""
+        mask, rows = 0, {}
+        for (kind, r), b in self.bounds.items():
+            if r >= (state_dim if kind == "state" else action_dim):
+                raise ValueError(f"BoxConstraint '{self.name}': {kind} row {r} does not exist (S = {state_dim}, A = {action_dim})")
+            bit = r if kind == "state" else state_dim + r
+            mask |= 1 << bit
+            rows[bit] = b
+        return mask, rows
+
+
 @dataclass
 class SafetyMetrics:
     """Outcome of evaluating every constraint on one step's pre-state."""

@@ -193,6 +193,7 @@ struct nig_handle {
     size_t hst_bytes = 0;
     float *mirror = nullptr; uint32_t ld_mirror = 0;    // StepArgs::mirror of the next step launch (nig_step_host*), else NULL
     float *act_soa = nullptr; size_t act_soa_floats = 0;   // nig_rollout with a row-major action ring on a kernel form that reads rows: the [A][ld] copy (owned, lazy)
+    LimitTable *lim_dev = nullptr; int n_limits = 0;       // nig_set_limits: the device copy of the added constraints (owned, lazy) and their number
 };
 
 // the handle's views of its workspace (nig_layout): per-lane counter words, lifetime violation counts, episode returns, tally rows
@@ -216,6 +217,10 @@ static int fail(int code, const char *msg) { snprintf(g_err, sizeof g_err, "%s",
 static int fail(int code, const char *fmt, const char *detail) { snprintf(g_err, sizeof g_err, fmt, detail); return code; }
 // "<fn>: <what>": the refusal of a check that several entry points share (formatted on refusal only)
 static int refuse(const char *fn, const char *what, int code = NIG_ERR_INVALID) { snprintf(g_err, sizeof g_err, "%s: %s", fn, what); return code; }
+
+// While limits are installed (nig_set_limits) every entry point that steps the env but the _limited ones refuses, on the host,
+// before anything is launched or written: their kernels do not know the added constraints.
+static int refuse_limited(const nig_handle *h, const char *fn);
 
 #define HIP_TRY(expr)                                                        \
     do {                                                                     \
@@ -308,6 +313,14 @@ static int ring_check(nig_handle *h, hipStream_t st, const char *who)
 static int enabled_constraints(const nig_handle *h)
 {
     return __builtin_popcount(h->cmask & ((1u << SPECS[h->env].n_constraints) - 1u));
+}
+
+static int refuse_limited(const nig_handle *h, const char *fn)
+{
+    if (h && h->n_limits > 0)
+        return refuse(fn, "limits are installed (nig_set_limits): this entry point does not know them -- use nig_step_limited / nig_step64_limited / "
+                          "nig_rollout_policy_limited / nig_rollout_mlp_limited, or remove them with nig_set_limits(h, 0, ...)", NIG_ERR_UNSUPPORTED);
+    return NIG_OK;
 }
 
 static void dispatch_step(const nig_handle *h, const StepArgs &a, bool parity, hipStream_t st)
@@ -435,6 +448,7 @@ static int disturb_args(const nig_handle *h, const char *fn, float *seen_out, in
 static PolicyArgs &shared_args(PolicyArgs &q) { return q; }
 static PolicyArgs &shared_args(PolicyDistArgs &q) { return q.p; }
 static MlpArgs &shared_args(MlpArgs &q) { return q; }
+static PolicyArgs &shared_args(PolicyLimArgs &q) { return q.p; }
 static MlpArgs &shared_args(MlpSearchArgs &q) { return q.sh.m; }
 template <class Args> static MlpArgs &shared_args(Args &q) { return q.m; }      // MlpShieldArgs, MlpEnsArgs, MlpDistArgs, MlpGateArgs, MlpProjectArgs
 static unsigned closed_loop_grid(const nig_handle *h, const PolicyArgs &) { return grid_for(h->B); }
@@ -509,6 +523,9 @@ extern "C" {
 // Still 0.8.0, for the same reason: nig_set_mlp_constraint / nig_rollout_mlp_projected ("nig-project-v1": ConstrainedIQLAgent's
 // get_safe_action -- a gradient projection of the actor's action towards the constraint predictor's feasible set).  Additive: no
 // existing kernel or entry point changed, no draw added.
+// Still 0.8.0, for the same reason: nig_set_limits / nig_get_limit_count / nig_step_limited / nig_step64_limited /
+// nig_rollout_policy_limited / nig_rollout_mlp_limited ("nig-limits-v1": box constraints added by the user, on the device).  Additive:
+// no existing kernel changed, no draw added; while limits are installed the other stepping entry points return NIG_ERR_UNSUPPORTED.
 const char *nig_version(void) { return "nig 0.8.0 (gfx950; generator nig-philox-v3)"; }
 const char *nig_last_error(void) { return g_err; }
 
@@ -683,6 +700,7 @@ int nig_destroy(nig_handle *h)
     if (h->pid_mem) (void)hipFree(h->pid_mem);
     if (h->act32) (void)hipFree(h->act32);
     if (h->act_soa) (void)hipFree(h->act_soa);
+    if (h->lim_dev) (void)hipFree(h->lim_dev);
     if (h->hst_dev) (void)hipFree(h->hst_dev);
     if (h->hst_pinned) (void)hipHostFree(h->hst_pinned);
     if (h->owns_ws && h->ws) (void)hipFree(h->ws);
@@ -778,6 +796,7 @@ int nig_step(nig_handle *h, const float *actions, int64_t ld_act, const double *
              int64_t ld_noise, float *reward_out, double *reward64_out, uint32_t *flags_out, float *final_obs,
              int64_t ld_obs, void *stream)
 {
+    NIG_TRY(refuse_limited(h, "nig_step"));
     NIG_TRY(check_step(h, "nig_step", actions, ld_act, step_noise, reset_noise, ld_noise, final_obs, ld_obs));
     StepArgs a = next_step_args(h, ld_act, step_noise, reset_noise, ld_noise, reward_out, reward64_out, flags_out, final_obs, ld_obs);
     a.actions = actions;
@@ -791,6 +810,7 @@ int nig_step64(nig_handle *h, const double *actions, int64_t ld_act, const doubl
                int64_t ld_obs, void *stream)
 {
     // every argument is checked before anything is launched: a refused call enqueues nothing (the narrowing copy below included)
+    NIG_TRY(refuse_limited(h, "nig_step64"));
     NIG_TRY(check_step(h, "nig_step64", actions, ld_act, step_noise, reset_noise, ld_noise, final_obs, ld_obs));
     const EnvLaunch *L = launch_of(h->env);
     if (!L->step64) {                             // this env's own arithmetic takes the action as float32
@@ -805,6 +825,106 @@ int nig_step64(nig_handle *h, const double *actions, int64_t ld_act, const doubl
     StepArgs a = next_step_args(h, ld_act, step_noise, reset_noise, ld_noise, reward_out, reward64_out, flags_out, final_obs, ld_obs);
     a.actions64 = actions;
     L->step64(a, step_noise || reset_noise, grid_for(h->B), (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return NIG_OK;
+}
+
+
+// ---- box constraints added by the user ("nig-limits-v1", csrc/nig_limits.hpp) -------------------------------------------------
+int nig_set_limits(nig_handle *h, int32_t n, const nig_limit *limits, void *stream)
+{
+    const char *const fn = "nig_set_limits";
+    if (!h) return refuse(fn, "NULL handle");
+    const nig_env_spec &sp = SPECS[h->env];
+    if (!launch_of(h->env)->step_limited)
+        return refuse(fn, "the Advanced envs override step() wholesale: no added constraints", NIG_ERR_UNSUPPORTED);
+    if (n < 0 || n > NIG_MAX_LIMITS) return refuse(fn, "n outside 0 .. NIG_MAX_LIMITS");
+    if (n == 0) { h->n_limits = 0; return NIG_OK; }
+    if (!limits) return refuse(fn, "limits is NULL");
+    const int rows = sp.state_dim + sp.action_dim;
+    static_assert(NIG_MAX_STATE_DIM + NIG_MAX_ACTION_DIM <= NIG_LIMIT_ROWS, "a bound for every state and action row");
+    for (int c = 0; c < n; ++c) {
+        const nig_limit &l = limits[c];
+        if (l.mask == 0) return refuse(fn, "a constraint lists no row (empty mask)");
+        if ((l.mask >> rows) != 0) return refuse(fn, "a mask bit >= S + A");
+        for (int r = 0; r < rows; ++r)
+            if (((l.mask >> r) & 1u) && !(l.lo[r] <= l.hi[r])) return refuse(fn, "lo > hi (or a NaN bound) on a listed row");
+        if (l.penalty != l.penalty) return refuse(fn, "a NaN penalty");
+    }
+    if ((int64_t)(sp.n_constraints + n) * h->max_steps > 65535)
+        return refuse(fn, "(built-in constraints + n) * max_episode_steps > 65535: the counter word keeps an episode's violations in 16 bits");
+    LimitTable T;
+    memset(&T, 0, sizeof T);
+    for (int c = 0; c < n; ++c) {
+        T.c[c] = limits[c];
+        T.c[c].critical = limits[c].critical != 0; T.c[c].reserved = 0;
+        for (int r = 0; r < NIG_LIMIT_ROWS; ++r)      // rows that are not listed are never read: a defined value all the same
+            if (r >= rows || !((limits[c].mask >> r) & 1u)) { T.c[c].lo[r] = 0.0f; T.c[c].hi[r] = 0.0f; }
+    }
+    T.n = n;
+    if (!h->lim_dev) HIP_TRY(hipMalloc((void **)&h->lim_dev, sizeof(LimitTable)));
+    HIP_TRY(hipMemcpyAsync(h->lim_dev, &T, sizeof T, hipMemcpyHostToDevice, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));        // (the source is this frame's)
+    h->n_limits = n;
+    return NIG_OK;
+}
+
+int nig_get_limit_count(const nig_handle *h) { return h ? h->n_limits : -1; }
+
+// the limited entry points' own prerequisite (a handle of an env that takes no limits never has any installed) ...
+static int check_limits(const nig_handle *h, const char *fn)
+{
+    return h->n_limits <= 0 ? refuse(fn, "no limits installed (nig_set_limits)") : NIG_OK;
+}
+// ... and the kernel's view of the limits.  n_en counts the added constraints as well: SafetyMetrics.total_constraints of every
+// step (base.py:115)
+static void limit_args(const nig_handle *h, uint32_t *xflags_out, StepArgs &s, LimitArgs &l)
+{
+    s.n_en += h->n_limits;
+    s.mirror = nullptr;
+    l.table = h->lim_dev; l.xflags = xflags_out;
+}
+
+int nig_step_limited(nig_handle *h, const float *actions, int64_t ld_act, const double *step_noise, const double *reset_noise,
+                     int64_t ld_noise, float *reward_out, double *reward64_out, uint32_t *flags_out, uint32_t *xflags_out,
+                     float *final_obs, int64_t ld_obs, void *stream)
+{
+    const char *const fn = "nig_step_limited";
+    NIG_TRY(check_step(h, fn, actions, ld_act, step_noise, reset_noise, ld_noise, final_obs, ld_obs));
+    NIG_TRY(check_limits(h, fn));
+    StepLimArgs q;
+    memset(&q, 0, sizeof q);
+    q.p = next_step_args(h, ld_act, step_noise, reset_noise, ld_noise, reward_out, reward64_out, flags_out, final_obs, ld_obs);
+    q.p.actions = actions;
+    limit_args(h, xflags_out, q.p, q.l);
+    launch_of(h->env)->step_limited(q, step_noise || reset_noise, grid_for(h->B), (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return NIG_OK;
+}
+
+int nig_step64_limited(nig_handle *h, const double *actions, int64_t ld_act, const double *step_noise, const double *reset_noise,
+                       int64_t ld_noise, float *reward_out, double *reward64_out, uint32_t *flags_out, uint32_t *xflags_out,
+                       float *final_obs, int64_t ld_obs, void *stream)
+{
+    const char *const fn = "nig_step64_limited";
+    NIG_TRY(check_step(h, fn, actions, ld_act, step_noise, reset_noise, ld_noise, final_obs, ld_obs));
+    NIG_TRY(check_limits(h, fn));
+    const EnvLaunch *L = launch_of(h->env);
+    if (!L->step64_limited) {                     // this env's own arithmetic takes the action as float32 (as nig_step64)
+        const int A = SPECS[h->env].action_dim;
+        if (!h->act32) HIP_TRY(hipMalloc((void **)&h->act32, (size_t)A * h->lay.ld * sizeof(float)));
+        hipLaunchKernelGGL(narrow_rows_kernel, dim3(grid_for(h->B)), dim3(BLOCK), 0, (hipStream_t)stream, actions, ld_act,
+                           h->act32, h->lay.ld, A, h->B);
+        HIP_TRY(hipGetLastError());
+        return nig_step_limited(h, h->act32, h->lay.ld, step_noise, reset_noise, ld_noise, reward_out, reward64_out, flags_out,
+                                xflags_out, final_obs, ld_obs, stream);
+    }
+    StepLimArgs q;
+    memset(&q, 0, sizeof q);
+    q.p = next_step_args(h, ld_act, step_noise, reset_noise, ld_noise, reward_out, reward64_out, flags_out, final_obs, ld_obs);
+    q.p.actions64 = actions;
+    limit_args(h, xflags_out, q.p, q.l);
+    L->step64_limited(q, step_noise || reset_noise, grid_for(h->B), (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return NIG_OK;
 }
@@ -839,6 +959,7 @@ static RolloutArgs rollout_args(const nig_handle *h, const RolloutSpec &c, int64
 static int rollout_impl(nig_handle *h, RolloutSpec c, void *stream)
 {
     const char *const fn = "nig_rollout";
+    NIG_TRY(refuse_limited(h, fn));
     // 1. validate
     if (!h || c.n_steps <= 0 || (!c.sampled && (!c.action_ring || c.ring_len <= 0))) return refuse(fn, "bad argument");
     const nig_env_spec &sp = SPECS[h->env];
@@ -978,6 +1099,7 @@ int nig_rollout_policy(nig_handle *h, int32_t n_steps, float *reward_out, uint32
                        int64_t act_step_stride, void *stream)
 {
     if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_policy: bad argument");
+    NIG_TRY(refuse_limited(h, "nig_rollout_policy"));
     if (!h->has_policy) return fail(NIG_ERR_INVALID, "nig_rollout_policy: no policy installed (nig_set_policy)");
     NIG_TRY(closed_loop<PolicyArgs>(h, "nig_rollout_policy", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](PolicyArgs &q) {
         policy_fields(h, q);
@@ -1030,10 +1152,42 @@ int nig_rollout_mlp(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t 
                     void *stream)
 {
     if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp: bad argument");
+    NIG_TRY(refuse_limited(h, "nig_rollout_mlp"));
     if (!h->mlp_stream || !launch_of(h->env)->mlp) return fail(NIG_ERR_INVALID, "nig_rollout_mlp: no actor installed (nig_set_mlp_policy)");
     return closed_loop<MlpArgs>(h, "nig_rollout_mlp", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpArgs &q) {
         q.wstream = h->mlp_stream;
         return launch_of(h->env)->mlp;
+    });
+}
+
+// the closed loops under the added constraints: the twins' prerequisites and checks, then the limits beside their arguments
+int nig_rollout_policy_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                               float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
+                               int64_t act_step_stride, uint32_t *xflags_out, void *stream)
+{
+    const char *const fn = "nig_rollout_policy_limited";
+    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    if (!h->has_policy) return refuse(fn, "no policy installed (nig_set_policy)");
+    NIG_TRY(check_limits(h, fn));
+    return closed_loop<PolicyLimArgs>(h, fn, n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](PolicyLimArgs &q) {
+        policy_fields(h, q.p);
+        limit_args(h, xflags_out, q.p.s, q.l);
+        return launch_of(h->env)->policy_limited;
+    });
+}
+
+int nig_rollout_mlp_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                            float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
+                            uint32_t *xflags_out, void *stream)
+{
+    const char *const fn = "nig_rollout_mlp_limited";
+    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    if (!h->mlp_stream || !launch_of(h->env)->mlp) return refuse(fn, "no actor installed (nig_set_mlp_policy)");
+    NIG_TRY(check_limits(h, fn));
+    return closed_loop<MlpLimArgs>(h, fn, n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpLimArgs &q) {
+        q.m.wstream = h->mlp_stream;
+        limit_args(h, xflags_out, q.m.s, q.l);
+        return launch_of(h->env)->mlp_limited;
     });
 }
 
@@ -1054,6 +1208,7 @@ int nig_rollout_mlp_safe(nig_handle *h, int32_t n_steps, float *reward_out, uint
                          float *prob_out, void *stream)
 {
     if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_safe: bad argument");
+    NIG_TRY(refuse_limited(h, "nig_rollout_mlp_safe"));
     if (!launch_of(h->env)->mlp_shield) return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_mlp_safe: env shape has no MFMA actor");
     if (!h->mlp_stream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_safe: no actor installed (nig_set_mlp_policy)");
     if (!h->mlp_cstream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_safe: no safety critic installed (nig_set_mlp_safety)");
@@ -1068,6 +1223,7 @@ int nig_rollout_mlp_search(nig_handle *h, int32_t n_steps, int32_t n_candidates,
                            float *prob_out, float *risk_out, int32_t *choice_out, void *stream)
 {
     if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_search: bad argument");
+    NIG_TRY(refuse_limited(h, "nig_rollout_mlp_search"));
     if (!launch_of(h->env)->mlp_search) return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_mlp_search: env shape has no MFMA actor");
     if (n_candidates < 1 || n_candidates > NIG_MAX_CANDIDATES) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_search: n_candidates outside 1 .. NIG_MAX_CANDIDATES");
     if (!h->mlp_stream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_search: no actor installed (nig_set_mlp_policy)");
@@ -1122,6 +1278,7 @@ int nig_rollout_mlp_ensemble(nig_handle *h, int32_t n_steps, float *reward_out, 
                              float *unc_out, float *member_act_out, void *stream)
 {
     if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_ensemble: bad argument (handle, n_steps)");
+    NIG_TRY(refuse_limited(h, "nig_rollout_mlp_ensemble"));
     if (!launch_of(h->env)->mlp_ensemble) return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_mlp_ensemble: env shape has no MFMA actor");
     if (h->ens_members < 1 || !h->ens_stream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_ensemble: no ensemble installed (nig_set_mlp_ensemble)");
     // member_act_out shares act_out's pitches: the same checks apply to it when act_out is absent
@@ -1174,6 +1331,7 @@ int nig_rollout_mlp_gated(nig_handle *h, int32_t n_steps, float *reward_out, uin
 {
     const char *const fn = "nig_rollout_mlp_gated";
     if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_gated: bad argument");
+    NIG_TRY(refuse_limited(h, "nig_rollout_mlp_gated"));
     if (!launch_of(h->env)->mlp_gated) return refuse(fn, "env shape has no MFMA actor", NIG_ERR_UNSUPPORTED);
     if (!h->mlp_stream) return refuse(fn, "no actor installed (nig_set_mlp_policy)");
     if (h->gate_members < 1 || !h->gate_stream) return refuse(fn, "no safety ensemble installed (nig_set_mlp_safety_ensemble)");
@@ -1234,6 +1392,7 @@ int nig_rollout_mlp_projected(nig_handle *h, int32_t n_steps, int32_t max_iters,
 {
     const char *const fn = "nig_rollout_mlp_projected";
     if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_projected: bad argument");
+    NIG_TRY(refuse_limited(h, "nig_rollout_mlp_projected"));
     if (!launch_of(h->env)->mlp_projected) return refuse(fn, "env shape has no MFMA actor", NIG_ERR_UNSUPPORTED);
     if (!h->mlp_stream) return refuse(fn, "no actor installed (nig_set_mlp_policy)");
     if (h->proj_outputs < 1 || !h->proj_cstream || !h->proj_bstream) return refuse(fn, "no constraint predictor installed (nig_set_mlp_constraint)");
@@ -1271,6 +1430,7 @@ int nig_rollout_policy_disturbed(nig_handle *h, int32_t n_steps, float *reward_o
                                  int64_t act_step_stride, float *seen_out, int64_t seen_step_stride, void *stream)
 {
     if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_policy_disturbed: bad argument");
+    NIG_TRY(refuse_limited(h, "nig_rollout_policy_disturbed"));
     if (!h->has_policy) return fail(NIG_ERR_INVALID, "nig_rollout_policy_disturbed: no policy installed (nig_set_policy)");
     DisturbArgs d;
     NIG_TRY(disturb_args(h, "nig_rollout_policy_disturbed", seen_out, seen_step_stride, d));
@@ -1286,6 +1446,7 @@ int nig_rollout_mlp_disturbed(nig_handle *h, int32_t n_steps, float *reward_out,
                               int64_t act_step_stride, float *seen_out, int64_t seen_step_stride, void *stream)
 {
     if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_disturbed: bad argument");
+    NIG_TRY(refuse_limited(h, "nig_rollout_mlp_disturbed"));
     if (!launch_of(h->env)->mlp_disturbed) return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_mlp_disturbed: env shape has no MFMA actor");
     if (!h->mlp_stream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_disturbed: no actor installed (nig_set_mlp_policy)");
     DisturbArgs d;
@@ -1374,6 +1535,7 @@ static int step_host_impl(nig_handle *h, const void *actions, bool act64, const 
                           double *reward64_out, uint32_t *flags_out, void *stream)
 {
     if (!h || !actions || !state_out || !reward64_out || !flags_out) return fail(NIG_ERR_INVALID, "nig_step_host: NULL argument");
+    NIG_TRY(refuse_limited(h, "nig_step_host"));
     const nig_env_spec &sp = SPECS[h->env];
     const HostStage L = host_stage_layout(h);
     NIG_TRY(host_stage_ensure(h, L));
@@ -1420,6 +1582,7 @@ int nig_plan_create(nig_handle *h, int32_t n_steps, const float *action_ring, in
     *out = nullptr;
     if (!h || !action_ring || n_steps <= 0 || ring_len <= 0 || ld_act < h->B || ld_act > NIG_MAX_PITCH)
         return fail(NIG_ERR_INVALID, "nig_plan_create: bad argument");
+    NIG_TRY(refuse_limited(h, "nig_plan_create"));
     if (slot_stride < (int64_t)SPECS[h->env].action_dim * ld_act)
         return fail(NIG_ERR_INVALID, "nig_plan_create: slot_stride smaller than one [A][ld_act] slot");
     if (out_stride != 0 && out_stride < h->B) return fail(NIG_ERR_INVALID, "nig_plan_create: out_stride < batch");
@@ -1457,6 +1620,7 @@ int nig_plan_create(nig_handle *h, int32_t n_steps, const float *action_ring, in
 int nig_plan_launch(nig_plan *p, void *stream)
 {
     if (!p) return fail(NIG_ERR_INVALID, "nig_plan_launch: NULL plan");
+    NIG_TRY(refuse_limited(p->h, "nig_plan_launch"));
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(set_u32_kernel, dim3(1), dim3(1), 0, st, p->h->t_dev, p->h->t);
     HIP_TRY(hipGraphLaunch(p->exec, st));
@@ -1522,6 +1686,7 @@ int nig_rollout_mixed_obs(nig_handle *const *handles, const int64_t *lane_offset
     for (int k = 0; k < n_handles; ++k) {
         const nig_handle *h = handles[k];
         if (!h) return fail(NIG_ERR_INVALID, "nig_rollout_mixed: NULL handle");
+        NIG_TRY(refuse_limited(h, fn));
         if (h->device != handles[0]->device) return fail(NIG_ERR_INVALID, "nig_rollout_mixed: handles on different devices");
         if (lane_offsets[k] < 0 || lane_offsets[k] + h->B > ld_act || (out_stride != 0 && lane_offsets[k] + h->B > out_stride))
             return fail(NIG_ERR_INVALID, "nig_rollout_mixed: a segment does not fit the row pitch");
@@ -1641,6 +1806,7 @@ int nig_mixed_fill_actions(nig_mixed *m, uint32_t t, float *actions, void *strea
 int nig_mixed_step(nig_mixed *m, const float *actions, float *reward_out, uint32_t *flags_out, void *stream)
 {
     if (!m || !actions) return fail(NIG_ERR_INVALID, "nig_mixed_step: NULL argument");
+    for (int k = 0; k < m->n; ++k) NIG_TRY(refuse_limited(m->seg[k], "nig_mixed_step"));      // (before any segment steps)
     for (int k = 0; k < m->n; ++k) {              // one step kernel per segment (each its own env type), same stream
         const int64_t o = m->off[k];
         NIG_TRY(nig_step(m->seg[k], actions + o, m->ld, nullptr, nullptr, 0, reward_out ? reward_out + o : nullptr, nullptr,
@@ -1833,6 +1999,7 @@ int nig_collect_episodes(nig_handle *h, int32_t n_steps, const float *reward, co
     const char *fn = "nig_collect_episodes";
     EpisodeLogArgs a;
     NIG_TRY(episode_log_args(h, fn, log, capacity, ld, a));
+    NIG_TRY(refuse_limited(h, fn));               // (the records are decoded from the main flag word alone)
     if (n_steps < 1) return refuse(fn, "n_steps < 1");
     if (!reward || !flags) return refuse(fn, "reward and flags rows are both required");
     if (n_steps > 1 ? (out_stride < h->B || out_stride > NIG_MAX_PITCH) : (out_stride != 0 && (out_stride < h->B || out_stride > NIG_MAX_PITCH)))

@@ -1,7 +1,7 @@
 // nig_launch.hpp -- the host side of libnig.so's kernels: the list of environments and the per-environment launch table.  An
 // env_<key>.hip instantiates the env's kernels by defining its table (NIG_DEFINE_ENV_LAUNCH); nig_api.hip reaches them through the
 // table's function pointers only.  The launchers of the kernel families with translation units of their own (sampled_, ensemble_,
-// disturbed_, search_, gated_, projected_<key>.hip) are DECLARED here and defined in nig_launch_families.hpp, which those units alone include.  Which
+// disturbed_, search_, gated_, projected_, limited_<key>.hip) are DECLARED here and defined in nig_launch_families.hpp, which those units alone include.  Which
 // kernel form a rollout launch takes is decided in nig_launch_plan.hpp; the functions here run its plans.
 #pragma once
 #include "nig_kernels.hpp"
@@ -54,6 +54,12 @@ struct EnvLaunch {
     void (*mlp_gated)(const MlpGateArgs &, unsigned grid, hipStream_t);
     // projected_<key>.hip: nig_rollout_mlp_projected; nullptr as `mlp`
     void (*mlp_projected)(const MlpProjectArgs &, unsigned grid, hipStream_t);
+    // limited_<key>.hip: nig_step_limited, nig_step64_limited (nullptr as `step64`), nig_rollout_policy_limited, nig_rollout_mlp_limited
+    // (nullptr as `mlp`); all nullptr for an env that overrides step() wholesale (the Advanced pair)
+    void (*step_limited)(const StepLimArgs &, bool parity, unsigned grid, hipStream_t);
+    void (*step64_limited)(const StepLimArgs &, bool parity, unsigned grid, hipStream_t);
+    void (*policy_limited)(const PolicyLimArgs &, unsigned grid, hipStream_t);
+    void (*mlp_limited)(const MlpLimArgs &, unsigned grid, hipStream_t);
 };
 
 template <class Env>
@@ -71,6 +77,7 @@ template <class Env> constexpr auto mlp_kernel(const MlpDistArgs &) { return rol
 template <class Env> constexpr auto mlp_kernel(const MlpSearchArgs &) { return rollout_mlp_search_kernel<Env>; }
 template <class Env> constexpr auto mlp_kernel(const MlpGateArgs &) { return rollout_mlp_gated_kernel<Env>; }
 template <class Env> constexpr auto mlp_kernel(const MlpProjectArgs &) { return rollout_mlp_projected_kernel<Env>; }
+template <class Env> constexpr auto mlp_kernel(const MlpLimArgs &) { return rollout_mlp_limited_kernel<Env>; }
 
 template <class Env, class Args>
 static void launch_mlp(const Args &q, unsigned grid, hipStream_t st)
@@ -240,6 +247,10 @@ template <class Env> void launch_mlp_disturbed_env(const MlpDistArgs &q, unsigne
 template <class Env> void launch_mlp_search_env(const MlpSearchArgs &q, unsigned grid, hipStream_t st);
 template <class Env> void launch_mlp_gated_env(const MlpGateArgs &q, unsigned grid, hipStream_t st);
 template <class Env> void launch_mlp_projected_env(const MlpProjectArgs &q, unsigned grid, hipStream_t st);
+template <class Env> void launch_step_limited_env(const StepLimArgs &q, bool parity, unsigned grid, hipStream_t st);
+template <class Env> void launch_step64_limited_env(const StepLimArgs &q, bool parity, unsigned grid, hipStream_t st);
+template <class Env> void launch_policy_limited_env(const PolicyLimArgs &q, unsigned grid, hipStream_t st);
+template <class Env> void launch_mlp_limited_env(const MlpLimArgs &q, unsigned grid, hipStream_t st);
 
 template <class Env>
 static void launch_policy(const PolicyArgs &q, unsigned /*grid*/, hipStream_t st)
@@ -288,6 +299,12 @@ static const EnvLaunch *env_launch_table()
         t.mlp_search = mlp_slot<Env>(launch_mlp_search_env<Env>);
         t.mlp_gated = mlp_slot<Env>(launch_mlp_gated_env<Env>);
         t.mlp_projected = mlp_slot<Env>(launch_mlp_projected_env<Env>);
+        if constexpr (!Env::CUSTOM_STEP) {
+            t.step_limited = launch_step_limited_env<Env>;
+            t.step64_limited = Env::HAS_ACT64 ? launch_step64_limited_env<Env> : nullptr;
+            t.policy_limited = launch_policy_limited_env<Env>;
+            t.mlp_limited = mlp_slot<Env>(launch_mlp_limited_env<Env>);
+        }
         return t;
     }();
     return &T;

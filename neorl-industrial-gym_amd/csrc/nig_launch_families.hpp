@@ -1,7 +1,8 @@
 // nig_launch_families.hpp -- the definitions of the family launchers nig_launch.hpp declares: the kernels of nig_rollout_sampled,
-// nig_rollout_mlp_ensemble, nig_rollout_policy_disturbed / nig_rollout_mlp_disturbed, nig_rollout_mlp_search, nig_rollout_mlp_gated and
-// nig_rollout_mlp_projected.
-// Included by the family translation units alone (sampled_, ensemble_, disturbed_, search_, gated_, projected_<key>.hip).  A template that is defined but not
+// nig_rollout_mlp_ensemble, nig_rollout_policy_disturbed / nig_rollout_mlp_disturbed, nig_rollout_mlp_search, nig_rollout_mlp_gated,
+// nig_rollout_mlp_projected and the _limited entry points (nig_step_limited, nig_step64_limited, nig_rollout_policy_limited,
+// nig_rollout_mlp_limited).
+// Included by the family translation units alone (sampled_, ensemble_, disturbed_, search_, gated_, projected_, limited_<key>.hip).  A template that is defined but not
 // instantiated emits nothing: each unit explicitly instantiates the launcher of its own family for its own env, and with it that
 // family's kernels and no other's.
 #pragma once
@@ -52,6 +53,38 @@ void launch_mlp_gated_env(const MlpGateArgs &q, unsigned grid, hipStream_t st) {
 template <class Env>
 void launch_mlp_projected_env(const MlpProjectArgs &q, unsigned grid, hipStream_t st) { launch_mlp<Env>(q, grid, st); }
 
+// nig_step_limited / nig_step64_limited: one plain kernel form each (injected or generated draws)
+template <class Env>
+void launch_step_limited_env(const StepLimArgs &q, bool parity, unsigned grid, hipStream_t st)
+{
+    if (parity) hipLaunchKernelGGL((step_limited_kernel<Env, true>), dim3(grid), dim3(BLOCK), 0, st, q);
+    else hipLaunchKernelGGL((step_limited_kernel<Env, false>), dim3(grid), dim3(BLOCK), 0, st, q);
+}
+template <class Env>
+void launch_step64_limited_env(const StepLimArgs &q, bool parity, unsigned grid, hipStream_t st)
+{
+    if constexpr (Env::HAS_ACT64) {
+        if (parity) hipLaunchKernelGGL((step_limited_kernel<Env, true, true>), dim3(grid), dim3(BLOCK), 0, st, q);
+        else hipLaunchKernelGGL((step_limited_kernel<Env, false, true>), dim3(grid), dim3(BLOCK), 0, st, q);
+    }
+}
+
+// nig_rollout_policy_limited: the one-wave form only, as the disturbed twin (plan_policy_disturbed: whole blocks and a ragged last one)
+template <class Env>
+void launch_policy_limited_env(const PolicyLimArgs &q, unsigned /*grid*/, hipStream_t st)
+{
+    const LaunchPlan plan = plan_policy_disturbed(q.p.s.B);
+    PolicyLimArgs r = q;
+    for (const Segment &s : plan) {
+        r.p.block0 = s.block0;
+        hipLaunchKernelGGL((rollout_policy_limited_kernel<Env>), dim3(s.grid), dim3(BLOCK), 0, st, r);
+    }
+}
+
+// nig_rollout_mlp_limited
+template <class Env>
+void launch_mlp_limited_env(const MlpLimArgs &q, unsigned grid, hipStream_t st) { launch_mlp<Env>(q, grid, st); }
+
 }  // namespace nig
 
 // the one line of a family translation unit: the explicit instantiation of its env's launcher(s)
@@ -68,3 +101,8 @@ void launch_mlp_projected_env(const MlpProjectArgs &q, unsigned grid, hipStream_
     template void nig::launch_mlp_gated_env<nig::EnvType>(const nig::MlpGateArgs &, unsigned, hipStream_t);
 #define NIG_DEFINE_ENV_PROJECTED(EnvType) \
     template void nig::launch_mlp_projected_env<nig::EnvType>(const nig::MlpProjectArgs &, unsigned, hipStream_t);
+#define NIG_DEFINE_ENV_LIMITED(EnvType) \
+    template void nig::launch_step_limited_env<nig::EnvType>(const nig::StepLimArgs &, bool, unsigned, hipStream_t); \
+    template void nig::launch_step64_limited_env<nig::EnvType>(const nig::StepLimArgs &, bool, unsigned, hipStream_t); \
+    template void nig::launch_policy_limited_env<nig::EnvType>(const nig::PolicyLimArgs &, unsigned, hipStream_t); \
+    template void nig::launch_mlp_limited_env<nig::EnvType>(const nig::MlpLimArgs &, unsigned, hipStream_t);

@@ -1,10 +1,11 @@
 // nig_mlp.hpp -- the fused MLP actor on MFMA with its safety-critic shield and its ensemble (device code only): MlpArgs,
-// MlpShieldArgs, MlpEnsArgs, MlpDistArgs, MlpSearchArgs, MlpGateArgs, MlpProjectArgs, rollout_mlp_body and its seven kernels.
+// MlpShieldArgs, MlpEnsArgs, MlpDistArgs, MlpSearchArgs, MlpGateArgs, MlpProjectArgs, MlpLimArgs, rollout_mlp_body and its eight kernels.
 #pragma once
 #include <type_traits>
 #include "nig_step.hpp"
 #include "nig_disturb.hpp"
-#include "nig_mlp_stream.hpp"         // the operand stream's constants and layer-1 shape (shared with the host's builder)
+#include "nig_limits.hpp"
+#include "nig_mlp_stream.hpp"        // the operand stream's constants and layer-1 shape (shared with the host's builder)
 
 namespace nig {
 
@@ -205,14 +206,16 @@ struct MlpProjectArgs {
     uint32_t ld_c; uint64_t c_step_stride;
 };
 
-template <class Env, bool SHIELD, int ENS = ENS_NONE, bool DIST = false, bool SEARCH = false, bool GATE = false, bool PROJECT = false>
+template <class Env, bool SHIELD, int ENS = ENS_NONE, bool DIST = false, bool SEARCH = false, bool GATE = false, bool PROJECT = false, bool LIMITS = false>
 __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const MlpArgs &q, const float *cstream, float *prob_out, float threshold,
                                                                        [[maybe_unused]] const MlpEnsArgs *eq = nullptr,
                                                                        [[maybe_unused]] const DisturbArgs *dq = nullptr,
                                                                        [[maybe_unused]] const MlpSearchArgs *sq = nullptr,
                                                                        [[maybe_unused]] const MlpGateArgs *gq = nullptr,
-                                                                       [[maybe_unused]] const MlpProjectArgs *jq = nullptr)
+                                                                       [[maybe_unused]] const MlpProjectArgs *jq = nullptr,
+                                                                       [[maybe_unused]] const LimitArgs *lq = nullptr)
 {
+    static_assert(!LIMITS || (!SHIELD && ENS == ENS_NONE && !DIST), "the added constraints have the plain actor's form only");
     static_assert(!PROJECT || (SHIELD && !SEARCH && !GATE), "the projection is a form of the shield; it excludes the search and the gate");
     static_assert(!(SHIELD && ENS != ENS_NONE), "the ensemble has no shield");
     static_assert(!SEARCH || SHIELD, "the search is a form of the shield");
@@ -714,7 +717,7 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
         // ---------------- IndustrialEnv.step (both lane halves, identical results) ----------------
         const uint32_t orow = (uint32_t)it * q.out_stride;
         uint32_t lo = li;                                          // the lane's index in this step's output addresses
-        if constexpr (SEARCH || GATE || PROJECT) asm volatile("" : "+v"(lo)); // (formed here, step by step: no address is kept in registers across the passes)
+        if constexpr (SEARCH || GATE || PROJECT || LIMITS) asm volatile("" : "+v"(lo)); // (formed here, step by step: no address is kept in registers across the passes; LIMITS: the per-lane xflags address, hoisted out of the step loop, was one more spilled register pair at the 256-register cap)
         const bool frozen = (ctr & NIG_CTR_DONE) != 0;
         if (writer && !frozen) {
             if (q.obs_out) {
@@ -755,12 +758,17 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
         if constexpr (KS > 0) Env::draw_step(key, nz); else nz[0] = 0;
         const int step_pre = (int)(ctr & NIG_CTR_STEP_MASK);
         StepResult<Env, reward_of<Env, act_t>> res;
-        if constexpr (ACT64) step_core<Env>(s, a64, nz, step_pre, p.max_steps, p.dt32, p.dt, p.cmask, n, res);
+        if constexpr (LIMITS) {                    // the added constraints beside the built-ins (nig_limits.hpp): res counts both kinds
+            const uint32_t xf = step_core_limited<Env>((limit_table_ptr)lq->table, s, a, nz, step_pre, p.max_steps, p.dt32, p.dt, p.cmask, n, res);
+            if (writer && lq->xflags) (lq->xflags + orow)[lo] = frozen ? 0u : xf;
+        }
+        else if constexpr (ACT64) step_core<Env>(s, a64, nz, step_pre, p.max_steps, p.dt32, p.dt, p.cmask, n, res);
         else step_core<Env>(s, a, nz, step_pre, p.max_steps, p.dt32, p.dt, p.cmask, n, res);
         const int step = step_pre + 1;
         const uint32_t viol_ep = episode_violations(ctr, res.nviol);
         const bool done = (res.terminated || res.truncated) && !frozen;
         uint32_t fl = pack_flags<Env>(res, step) | did_reset_flag(done && autoreset);
+        if constexpr (LIMITS) fl = limited_flag_counts<Env>(fl, res.viol_bits, res.shutdown);
         if constexpr (SHIELD) fl |= shield ? NIG_FLAG_SHIELDED : 0u;
         if constexpr (ENS != ENS_NONE) fl |= uncertain ? NIG_FLAG_UNCERTAIN : 0u;
         if constexpr (GATE) fl |= g_uncertain ? NIG_FLAG_UNCERTAIN : 0u;
@@ -843,6 +851,19 @@ template <class Env>
 __global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_disturbed_kernel(const MlpDistArgs q)
 {
     rollout_mlp_body<Env, false, ENS_NONE, true>(q.m, nullptr, nullptr, 0.0f, nullptr, &q.d);
+}
+
+struct MlpLimArgs {
+    MlpArgs m;
+    LimitArgs l;
+};
+
+// The plain actor under the user's added box constraints (include/nig.h "nig-limits-v1"): step_core_limited at the body's one step
+// site, a second word per step.  Instantiated in the env's limited_*.hip translation unit only (launch_mlp_limited_env).
+template <class Env>
+__global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_limited_kernel(const MlpLimArgs q)
+{
+    rollout_mlp_body<Env, false, ENS_NONE, false, false, false, false, true>(q.m, nullptr, nullptr, 0.0f, nullptr, nullptr, nullptr, nullptr, nullptr, &q.l);
 }
 
 }  // namespace nig

@@ -1,6 +1,7 @@
 // nig_rollout_policy_body.inc -- the body of the one-wave closed-loop kernels (nig_rollout_policy.hpp: rollout_policy_kernel,
-// rollout_policy_disturbed_kernel).  Included inside a __global__ function with `const PolicyArgs &q` (the kernel's own by-value
-// argument for rollout_policy_kernel), `const DisturbArgs *dq`, Env and DIST in scope.
+// rollout_policy_disturbed_kernel, rollout_policy_limited_kernel).  Included inside a __global__ function with `const PolicyArgs &q`
+// (the kernel's own by-value argument for rollout_policy_kernel), `const DisturbArgs *dq`, `const LimitArgs *lq`, Env, DIST and
+// LIM in scope.
     constexpr int S = Env::S, A = Env::A, KS = Env::KS, KR = Env::KR;
     constexpr int KSN = KS > 0 ? KS : 1;
     // The policy struct is staged in LDS: read from global memory inside the loop, every field was a
@@ -63,6 +64,9 @@
             if (in_range) {
                 if (p.flags) (p.flags + base + orow)[tid] = frozen_flag_word(ctr);
                 if (p.reward) (p.reward + base + orow)[tid] = 0.0f;
+                if constexpr (LIM) {
+                    if (lq->xflags) (lq->xflags + base + orow)[tid] = 0u;
+                }
             }
         } else {
         const RngKey key = make_key(gi, t_base + (uint32_t)it + 1u, p.seed_lo, p.seed_hi, s_probit);
@@ -120,11 +124,17 @@
         if constexpr (KS > 0) Env::draw_step(key, nz); else nz[0] = 0;
         const int step_pre = (int)(ctr & NIG_CTR_STEP_MASK);
         StepResult<Env> res;
-        step_core<Env>(s, a, nz, step_pre, p.max_steps, p.dt32, p.dt, p.cmask, n, res);
+        if constexpr (LIM) {                       // the added constraints beside the built-ins (nig_limits.hpp): res counts both kinds
+            const uint32_t xf = step_core_limited<Env>((limit_table_ptr)lq->table, s, a, nz, step_pre, p.max_steps, p.dt32, p.dt, p.cmask, n, res);
+            if (lq->xflags) stream_store(lq->xflags + base + orow + tid, xf);
+        } else {
+            step_core<Env>(s, a, nz, step_pre, p.max_steps, p.dt32, p.dt, p.cmask, n, res);
+        }
         const int step = step_pre + 1;
         const uint32_t viol_ep = episode_violations(ctr, res.nviol);
         const bool done = res.terminated || res.truncated;
         uint32_t fl = pack_flags<Env>(res, step) | did_reset_flag(done && autoreset);
+        if constexpr (LIM) fl = limited_flag_counts<Env>(fl, res.viol_bits, res.shutdown);
         ctr = counter_word(step, viol_ep);
         if (tally) ret = add_reward<Env>(ret, res.reward);
         if (p.reward) stream_store(p.reward + base + orow + tid, (float)res.reward);

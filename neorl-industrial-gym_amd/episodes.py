@@ -214,6 +214,7 @@ def evaluate_episodes(agent: Any, env_or_id, n_episodes: int = 100, episodes_per
     own = None
     if isinstance(env_or_id, BatchedIndustrialEnv):
         env = env_or_id
+        env._refuse_limits("evaluate_episodes (episode records are decoded from the main flag word alone)")
     else:
         b = int(batch or min(n, 65536))
         env = own = BatchedIndustrialEnv(env_or_id, b, device=device, seed=seed, autoreset=True)

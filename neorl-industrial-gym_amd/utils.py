@@ -143,7 +143,19 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
     shield, ensemble and disturbance are installed on the handle), or None -- the agent stays on the host and takes the
     per-step loop; `agent` may come back upgraded (a reference EnsembleAgent as an EnsemblePolicy); `disturbed` names the
     fused route of a disturbance.Disturbed ("fused-policy" / "fused-mlp": the caller removes the disturbance afterwards).
-    plain = no recorded draws are injected (with them every agent takes the host loop)."""
+    plain = no recorded draws are injected (with them every agent takes the host loop).
+    On an env with added safety constraints (add_safety_constraint) a plain DevicePolicy goes to rollout_policy_limited and a
+    plain fusable MLPPolicy to rollout_mlp_limited; every other agent takes the host loop, whose env.step knows the constraints."""
+    if getattr(env, "has_limits", False):
+        if plain and hasattr(agent, "to_struct"):
+            env.set_policy(agent)
+            return agent, env.rollout_policy_limited, None
+        shielded = getattr(agent, "safety_weights", None) is not None and hasattr(agent, "threshold")
+        if (plain and not hasattr(agent, "install") and getattr(agent, "fusable", False) and not shielded
+                and env.state_dim % 2 == 0 and env.action_dim <= 16):
+            env.set_mlp_policy(agent.weights)
+            return agent, env.rollout_mlp_limited, None
+        return agent, None, None
     device_policy = hasattr(agent, "to_struct") and plain
     if plain and all(hasattr(agent, k) for k in ("agents", "weights", "ensemble_method")) and not hasattr(agent, "install"):
         # the reference's EnsembleAgent: its K actors fused into the env kernel where members and env allow it (EnsemblePolicy);
