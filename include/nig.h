@@ -583,6 +583,18 @@ int nig_rollout_mlp_safe(nig_handle *h, int32_t n_steps, float *reward_out, uint
                          int64_t ld_act, int64_t act_step_stride, float *prob_out, void *stream);
 
 /*
+ * nig_rollout_mlp_safe under the installed limits ("nig-limits-v1", nig_set_limits): every argument as the parent's, plus xflags_out
+ * uint32 [n_steps][>= B] (row k at xflags_out + k * out_stride; may be NULL; a frozen lane's word is 0), nig_rollout_mlp_limited's
+ * layout.  The added constraints are checked on the action the env receives (the halved one where the shield acts); NIG_FLAG_SHIELDED
+ * is set as in the parent.  NIG_ERR_INVALID without installed limits, then every refusal of the parent; a refused call launches and writes nothing.  The kernel is the
+ * parent's body with the step law of nig_step_limited applied to the action the env receives, so a rollout equals nig_step_limited fed
+ * with the rollout's own actions (act_out holds them).
+ */
+int nig_rollout_mlp_safe_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out,
+                                 int64_t out_stride, float *obs_out, int64_t obs_step_stride, float *act_out,
+                                 int64_t ld_act, int64_t act_step_stride, float *prob_out, uint32_t *xflags_out, void *stream);
+
+/*
  * Safe-action search of the reference's safety-critical agents (agents/safety_critical.py:173-208,
  * RiskAwareCQLAgent.get_safe_action), fused into the shield's kernel: where the critic finds the actor's
  * action too risky, it scores n_candidates uniform actions and the env receives the least risky one.
@@ -618,6 +630,17 @@ int nig_rollout_mlp_search(nig_handle *h, int32_t n_steps, int32_t n_candidates,
                            uint32_t *flags_out, int64_t out_stride, float *obs_out, int64_t obs_step_stride,
                            float *act_out, int64_t ld_act, int64_t act_step_stride, float *prob_out,
                            float *risk_out, int32_t *choice_out, void *stream);
+
+/*
+ * nig_rollout_mlp_search under the installed limits: the parent's arguments plus xflags_out (nig_rollout_mlp_safe_limited's).  The
+ * added constraints are checked on the chosen candidate where the search acts.  NIG_ERR_INVALID without installed limits, then every refusal of the parent; a refused call launches and writes nothing.  The kernel is the
+ * parent's body with the step law of nig_step_limited applied to the action the env receives, so a rollout equals nig_step_limited fed
+ * with the rollout's own actions.
+ */
+int nig_rollout_mlp_search_limited(nig_handle *h, int32_t n_steps, int32_t n_candidates, float *reward_out,
+                                   uint32_t *flags_out, int64_t out_stride, float *obs_out, int64_t obs_step_stride,
+                                   float *act_out, int64_t ld_act, int64_t act_step_stride, float *prob_out,
+                                   float *risk_out, int32_t *choice_out, uint32_t *xflags_out, void *stream);
 
 /*
  * Ensemble of MLP actors (agents/ensemble.py EnsembleAgent: predict, predict_with_uncertainty,
@@ -674,6 +697,19 @@ int nig_rollout_mlp_ensemble(nig_handle *h, int32_t n_steps, float *reward_out, 
                              float *member_act_out, void *stream);
 
 /*
+ * nig_rollout_mlp_ensemble under the installed limits: the parent's arguments plus xflags_out (nig_rollout_mlp_safe_limited's).  With
+ * NIG_ENSEMBLE_AVERAGE on an env that steps on the float64 action (nig_step64's rule) the added constraints are checked on that
+ * float64 action against the float32 bounds widened to double: the law of nig_step64_limited.  NIG_FLAG_UNCERTAIN is set as in the
+ * parent.  NIG_ERR_INVALID without installed limits, then every refusal of the parent; a refused call launches and writes nothing.  The kernel is the
+ * parent's body with the step law of nig_step_limited applied to the action the env receives, so a rollout equals nig_step_limited fed
+ * with the rollout's own actions (nig_step64_limited and the float64 action where the env steps on one).
+ */
+int nig_rollout_mlp_ensemble_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out,
+                                     int64_t out_stride, float *obs_out, int64_t obs_step_stride, float *act_out,
+                                     int64_t ld_act, int64_t act_step_stride, float *unc_out,
+                                     float *member_act_out, uint32_t *xflags_out, void *stream);
+
+/*
  * Safety-ensemble gate of the reference's SafeEnsembleAgent.get_safe_action (agents/safety_critical.py:391-532),
  * fused into the shield's kernel: K safety predictors with one head row per constraint score the actor's
  * action; the env receives it only if every constraint's violation probability and every spread is small,
@@ -725,6 +761,17 @@ int nig_rollout_mlp_gated(nig_handle *h, int32_t n_steps, float *reward_out, uin
                           int64_t out_stride, float *obs_out, int64_t obs_step_stride, float *act_out,
                           int64_t ld_act, int64_t act_step_stride, float *prob_out, float *unc_out,
                           float *logit_out, int64_t ld_c, int64_t c_step_stride, void *stream);
+
+/*
+ * nig_rollout_mlp_gated under the installed limits: the parent's arguments plus xflags_out (nig_rollout_mlp_safe_limited's).  The
+ * added constraints are checked on the zero action where the gate rejects.  NIG_ERR_INVALID without installed limits, then every refusal of the parent; a refused call launches and writes nothing.  The kernel is the
+ * parent's body with the step law of nig_step_limited applied to the action the env receives, so a rollout equals nig_step_limited fed
+ * with the rollout's own actions.
+ */
+int nig_rollout_mlp_gated_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out,
+                                  int64_t out_stride, float *obs_out, int64_t obs_step_stride, float *act_out,
+                                  int64_t ld_act, int64_t act_step_stride, float *prob_out, float *unc_out,
+                                  float *logit_out, int64_t ld_c, int64_t c_step_stride, uint32_t *xflags_out, void *stream);
 
 /*
  * Constraint projection of the reference's ConstrainedIQLAgent.get_safe_action (agents/safety_critical.py:240-370),
@@ -783,6 +830,18 @@ int nig_rollout_mlp_projected(nig_handle *h, int32_t n_steps, int32_t max_iters,
                               int64_t c_step_stride, void *stream);
 
 /*
+ * nig_rollout_mlp_projected under the installed limits: the parent's arguments plus xflags_out (nig_rollout_mlp_safe_limited's).  The
+ * added constraints are checked on the projected action.  NIG_ERR_INVALID without installed limits, then every refusal of the parent; a refused call launches and writes nothing.  The kernel is the
+ * parent's body with the step law of nig_step_limited applied to the action the env receives, so a rollout equals nig_step_limited fed
+ * with the rollout's own actions.
+ */
+int nig_rollout_mlp_projected_limited(nig_handle *h, int32_t n_steps, int32_t max_iters, float step, float *reward_out,
+                                      uint32_t *flags_out, int64_t out_stride, float *obs_out, int64_t obs_step_stride,
+                                      float *act_out, int64_t ld_act, int64_t act_step_stride, float *prob_out,
+                                      float *viol_out, int32_t *iters_out, float *grad_out, int64_t ld_c,
+                                      int64_t c_step_stride, uint32_t *xflags_out, void *stream);
+
+/*
  * Sensor / actuator noise inside the closed loop ("nig-disturb-v1"): the policy sees a noisy observation, the plant
  * receives a noisy action.  Stands in for the observation_noise / action_noise runs of the reference's
  * RobustnessBenchmark (benchmarks/industrial_benchmarks.py:455-573) and for predict(obs, deterministic=False) of
@@ -835,6 +894,22 @@ int nig_rollout_policy_disturbed(nig_handle *h, int32_t n_steps, float *reward_o
 int nig_rollout_mlp_disturbed(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
                               float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
                               int64_t act_step_stride, float *seen_out, int64_t seen_step_stride, void *stream);
+
+/*
+ * nig_rollout_policy_disturbed / nig_rollout_mlp_disturbed under the installed limits: the parents' arguments plus xflags_out
+ * (nig_rollout_mlp_safe_limited's).  The added constraints are checked on the true state and on the disturbed, clipped action the
+ * plant receives (act_out's rows).  The policy twin has the one-wave kernel form only.  NIG_ERR_INVALID without installed limits, then every refusal of the parent; a refused call launches and writes nothing.  The kernel is the
+ * parent's body with the step law of nig_step_limited applied to the action the env receives, so a rollout equals nig_step_limited fed
+ * with the rollout's own actions.
+ */
+int nig_rollout_policy_disturbed_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                                         float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
+                                         int64_t act_step_stride, float *seen_out, int64_t seen_step_stride, uint32_t *xflags_out,
+                                         void *stream);
+int nig_rollout_mlp_disturbed_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                                      float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
+                                      int64_t act_step_stride, float *seen_out, int64_t seen_step_stride, uint32_t *xflags_out,
+                                      void *stream);
 
 /*
  * Host-buffer forms for SMALL batches -- the single-env drop-in classes (env.reset() / env.step()

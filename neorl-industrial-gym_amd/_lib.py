@@ -151,6 +151,14 @@ PROTOTYPES = {
     "nig_set_disturbance": (ci, [vp, P(DisturbanceStruct), vp]),
     "nig_rollout_policy_disturbed": (ci, CLOSED_LOOP + [vp, i64, vp]),
     "nig_rollout_mlp_disturbed": (ci, CLOSED_LOOP + [vp, i64, vp]),
+    # the other closed-loop families under the added constraints: the parent's arguments, xflags_out, the stream
+    "nig_rollout_mlp_safe_limited": (ci, CLOSED_LOOP + [vp, vp, vp]),
+    "nig_rollout_mlp_search_limited": (ci, CLOSED_LOOP[:2] + [i32] + CLOSED_LOOP[2:] + [vp, vp, vp, vp, vp]),
+    "nig_rollout_mlp_gated_limited": (ci, CLOSED_LOOP + [vp, vp, vp, i64, i64, vp, vp]),
+    "nig_rollout_mlp_projected_limited": (ci, CLOSED_LOOP[:2] + [i32, f32] + CLOSED_LOOP[2:] + [vp, vp, vp, vp, i64, i64, vp, vp]),
+    "nig_rollout_mlp_ensemble_limited": (ci, CLOSED_LOOP + [vp, vp, vp, vp]),
+    "nig_rollout_policy_disturbed_limited": (ci, CLOSED_LOOP + [vp, i64, vp, vp]),
+    "nig_rollout_mlp_disturbed_limited": (ci, CLOSED_LOOP + [vp, i64, vp, vp]),
     "nig_reset_host": (ci, [vp, vp, vp, vp]),
     "nig_step_host": (ci, [vp, vp, vp, vp, vp, vp, vp]),
     "nig_step_host64": (ci, [vp, vp, vp, vp, vp, vp, vp]),

@@ -306,8 +306,8 @@ class BatchedIndustrialEnv:
 
     def add_safety_constraint(self, constraint):
         """env.add_safety_constraint (base.py:220-222) for a BoxConstraint: from the next step on it is checked, penalised and
-        counted on the device beside the built-ins (at most MAX_LIMITS added ones).  step(), rollout_policy_limited() and
-        rollout_mlp_limited() know the added constraints; every other stepping entry point refuses while any is installed."""
+        counted on the device beside the built-ins (at most MAX_LIMITS added ones).  step() and the rollout_*_limited() methods
+        know the added constraints; every other stepping entry point refuses while any is installed."""
         if not isinstance(constraint, BoxConstraint):
             raise TypeError("BatchedIndustrialEnv evaluates added constraints on the device and takes BoxConstraint only (declarative "
                             "bounds on state / action rows); an arbitrary check_fn callable runs on the single env: make(env_id)"
@@ -561,6 +561,13 @@ class BatchedIndustrialEnv:
         self._closed_loop(self._L.nig_rollout_mlp_safe, n_steps, reward_out, flags_out, obs_out, act_out,
                           rows=[("prob_out", prob_out, torch.float32)])
 
+    def rollout_mlp_safe_limited(self, n_steps: int, reward_out=None, flags_out=None, obs_out=None, act_out=None, prob_out=None,
+                                 xflags_out=None):
+        """rollout_mlp_safe() under the added safety constraints (add_safety_constraint; "nig-limits-v1"), checked on the action
+        the env received; xflags_out as rollout_policy_limited()'s."""
+        self._closed_loop(self._L.nig_rollout_mlp_safe_limited, n_steps, reward_out, flags_out, obs_out, act_out,
+                          rows=[("prob_out", prob_out, torch.float32), ("xflags_out", xflags_out, torch.int32)])
+
     def rollout_mlp_search(self, n_steps: int, n_candidates: int, reward_out=None, flags_out=None, obs_out=None, act_out=None,
                            prob_out=None, risk_out=None, choice_out=None):
         """rollout_mlp_safe() with the safety-critical agents' get_safe_action in place of the halving ("nig-search-v1",
@@ -572,6 +579,14 @@ class BatchedIndustrialEnv:
         a candidate was taken."""
         self._closed_loop(self._L.nig_rollout_mlp_search, n_steps, reward_out, flags_out, obs_out, act_out, head=(int(n_candidates),),
                           rows=[("prob_out", prob_out, torch.float32), ("risk_out", risk_out, torch.float32), ("choice_out", choice_out, torch.int32)])
+
+    def rollout_mlp_search_limited(self, n_steps: int, n_candidates: int, reward_out=None, flags_out=None, obs_out=None, act_out=None,
+                                   prob_out=None, risk_out=None, choice_out=None, xflags_out=None):
+        """rollout_mlp_search() under the added safety constraints, checked on the action the env received; xflags_out as
+        rollout_policy_limited()'s."""
+        self._closed_loop(self._L.nig_rollout_mlp_search_limited, n_steps, reward_out, flags_out, obs_out, act_out, head=(int(n_candidates),),
+                          rows=[("prob_out", prob_out, torch.float32), ("risk_out", risk_out, torch.float32), ("choice_out", choice_out, torch.int32),
+                                ("xflags_out", xflags_out, torch.int32)])
 
     def set_mlp_safety_ensemble(self, members, temperature: float = 1.0, threshold: float = 0.1, max_uncertainty: float = 0.2):
         """Install the safety ensemble of SafeEnsembleAgent (agents/safety_critical.py) for rollout_mlp_gated(): `members` = a
@@ -595,6 +610,16 @@ class BatchedIndustrialEnv:
         [n_steps, C, >=B] p and sd per constraint; logit_out float32 [n_steps, K, C, >=B] every member's logits (the three
         share their pitches); flags carry FLAG_SHIELDED where the action was replaced and FLAG_UNCERTAIN where a spread is not
         below the limit."""
+        self._gated(self._L.nig_rollout_mlp_gated, (), n_steps, reward_out, flags_out, obs_out, act_out, prob_out, unc_out, logit_out)
+
+    def rollout_mlp_gated_limited(self, n_steps: int, reward_out=None, flags_out=None, obs_out=None, act_out=None, prob_out=None,
+                                  unc_out=None, logit_out=None, xflags_out=None):
+        """rollout_mlp_gated() under the added safety constraints, checked on the action the env received; xflags_out as
+        rollout_policy_limited()'s."""
+        self._gated(self._L.nig_rollout_mlp_gated_limited, [("xflags_out", xflags_out, torch.int32)], n_steps, reward_out, flags_out,
+                    obs_out, act_out, prob_out, unc_out, logit_out)
+
+    def _gated(self, fn, last_rows, n_steps, reward_out, flags_out, obs_out, act_out, prob_out, unc_out, logit_out):
         K, Cn = getattr(self, "_gate_shape", (0, 0))
         ptrs, pitches = [], set()
         for name, t, lead in (("prob_out", prob_out, ()), ("unc_out", unc_out, ()), ("logit_out", logit_out, (K,))):
@@ -608,7 +633,7 @@ class BatchedIndustrialEnv:
             pitches.add((t.stride(-2), t.stride(-3)))
         assert len(pitches) <= 1, "prob_out, unc_out and logit_out share their pitches"
         ld_c, c_step = pitches.pop() if pitches else (0, 0)
-        self._closed_loop(self._L.nig_rollout_mlp_gated, n_steps, reward_out, flags_out, obs_out, act_out, tail=(*ptrs, ld_c, c_step))
+        self._closed_loop(fn, n_steps, reward_out, flags_out, obs_out, act_out, tail=(*ptrs, ld_c, c_step), last_rows=last_rows)
 
     def set_mlp_constraint(self, predictor, threshold: float = 0.1, tolerance: float = 0.01):
         """Install the constraint predictor of ConstrainedIQLAgent (agents/safety_critical.py) for rollout_mlp_projected():
@@ -632,6 +657,20 @@ class BatchedIndustrialEnv:
         the actor's action / of the action the env received (they share their pitches); iters_out int32 [n_steps, >=B] the
         gradient steps taken, -1 where the actor's action was kept; grad_out float32 [n_steps, A, >=B] (act_out's pitches) the
         first gradient, written where iters >= 1; flags carry FLAG_SHIELDED on projected lanes."""
+        self._projected(self._L.nig_rollout_mlp_projected, None, n_steps, max_iters, step, reward_out, flags_out, obs_out, act_out,
+                        prob_out, viol_out, iters_out, grad_out)
+
+    def rollout_mlp_projected_limited(self, n_steps: int, max_iters: int = 10, step: float = 0.1, reward_out=None, flags_out=None,
+                                      obs_out=None, act_out=None, prob_out=None, viol_out=None, iters_out=None, grad_out=None,
+                                      xflags_out=None):
+        """rollout_mlp_projected() under the added safety constraints, checked on the action the env received; xflags_out as
+        rollout_policy_limited()'s."""
+        self._projected(self._L.nig_rollout_mlp_projected_limited, (xflags_out,), n_steps, max_iters, step, reward_out, flags_out,
+                        obs_out, act_out, prob_out, viol_out, iters_out, grad_out)
+
+    def _projected(self, fn, xflags, n_steps, max_iters, step, reward_out, flags_out, obs_out, act_out, prob_out, viol_out, iters_out,
+                   grad_out):
+        """xflags: None for the parent, (xflags_out,) for the _limited twin (a row of iters_out's stride behind the parent's arguments)."""
         Cn = getattr(self, "_constraint_outputs", 0)
         ptrs, pitches = [], set()
         for name, t in (("prob_out", prob_out), ("viol_out", viol_out)):
@@ -647,7 +686,12 @@ class BatchedIndustrialEnv:
         rp, fp, os_, op, so, ap, lda, sa = self._closed_loop_outputs(n_steps, reward_out, flags_out, obs_out, act_out)
         ip, is_ = _rows(iters_out, torch.int32, n_steps)
         strides = ({is_} if ip is not None else set()) | ({os_} if (rp is not None or fp is not None) else set())
-        assert len(strides) <= 1, "iters_out shares the reward/flags row stride"
+        last = ()
+        if xflags is not None:
+            xp, xs = _rows(xflags[0], torch.int32, n_steps)
+            strides |= {xs} if xp is not None else set()
+            last = (xp,)
+        assert len(strides) <= 1, "iters_out (and xflags_out) share the reward/flags row stride"
         gp = None
         if grad_out is not None:
             assert grad_out.dtype == torch.float32 and grad_out.dim() == 3 and grad_out.stride(2) == 1, "grad_out"
@@ -655,8 +699,8 @@ class BatchedIndustrialEnv:
             assert ap is None or (grad_out.stride(1), grad_out.stride(0)) == (lda, sa), "grad_out shares act_out's pitches"
             gp, lda, sa = C.c_void_p(grad_out.data_ptr()), grad_out.stride(1), grad_out.stride(0)
         with torch.cuda.device(self._dev_index):
-            _lib.check(self._L.nig_rollout_mlp_projected(self._h, int(n_steps), int(max_iters), float(step), rp, fp, strides.pop() if strides else 0,
-                                                         op, so, ap, lda, sa, *ptrs, ip, gp, ld_c, c_step, self._stream()))
+            _lib.check(fn(self._h, int(n_steps), int(max_iters), float(step), rp, fp, strides.pop() if strides else 0,
+                          op, so, ap, lda, sa, *ptrs, ip, gp, ld_c, c_step, *last, self._stream()))
 
     def set_mlp_ensemble(self, members, weights=None, weight_sum=None, method: str = "mean", uncertainty_threshold: float = 0.2):
         """Install an ensemble of actors (agents/ensemble.py EnsembleAgent) for rollout_mlp_ensemble(): `members` = a list of
@@ -684,25 +728,37 @@ class BatchedIndustrialEnv:
         to float32 for "mean" / "weighted"); unc_out float32 [n_steps, >=B] the members' disagreement (same row stride as
         reward_out / flags_out); member_act_out float32 [n_steps, K, A, >=B] every member's action (same pitches as act_out);
         flags carry FLAG_UNCERTAIN where the uncertainty exceeds the installed threshold."""
+        self._ensemble(self._L.nig_rollout_mlp_ensemble, (), n_steps, reward_out, flags_out, obs_out, act_out, unc_out, member_act_out)
+
+    def rollout_mlp_ensemble_limited(self, n_steps: int, reward_out=None, flags_out=None, obs_out=None, act_out=None, unc_out=None,
+                                     member_act_out=None, xflags_out=None):
+        """rollout_mlp_ensemble() under the added safety constraints, checked on the action the env received (the float64 average
+        where the env steps on it); xflags_out as rollout_policy_limited()'s."""
+        self._ensemble(self._L.nig_rollout_mlp_ensemble_limited, [("xflags_out", xflags_out, torch.int32)], n_steps, reward_out,
+                       flags_out, obs_out, act_out, unc_out, member_act_out)
+
+    def _ensemble(self, fn, last_rows, n_steps, reward_out, flags_out, obs_out, act_out, unc_out, member_act_out):
         mp, pitches = None, None
         if member_act_out is not None:
             K, m = getattr(self, "_ensemble_members", 0), member_act_out
             assert m.dtype == torch.float32 and m.dim() == 4 and m.stride(3) == 1 and m.stride(0) == K * m.stride(1)
             assert m.shape[0] >= n_steps and m.shape[1] == K and m.shape[2] == self.action_dim and m.shape[3] >= self.batch
             mp, pitches = C.c_void_p(m.data_ptr()), (m.stride(2), m.stride(1))
-        self._closed_loop(self._L.nig_rollout_mlp_ensemble, n_steps, reward_out, flags_out, obs_out, act_out,
-                          rows=[("unc_out", unc_out, torch.float32)], tail=(mp,), member_pitches=pitches)
+        self._closed_loop(fn, n_steps, reward_out, flags_out, obs_out, act_out,
+                          rows=[("unc_out", unc_out, torch.float32)], tail=(mp,), member_pitches=pitches, last_rows=last_rows)
 
-    def _closed_loop(self, fn, n_steps, reward_out, flags_out, obs_out, act_out, head=(), rows=(), tail=(), member_pitches=None):
+    def _closed_loop(self, fn, n_steps, reward_out, flags_out, obs_out, act_out, head=(), rows=(), tail=(), member_pitches=None, last_rows=()):
         """One closed-loop call of the C ABI: fn(handle, n_steps, *head, <the eight output arguments the closed loops share: reward
         ptr, flags ptr, out_stride, obs ptr, obs_step_stride, act ptr, ld_act, act_step_stride>, <a pointer per entry of `rows`>,
         *tail, stream), the four optional output tensors validated.  rows: (name, tensor or None, dtype) of the variant's extra
         per-step rows [n_steps, >=B], which share the row stride of reward_out / flags_out.  member_pitches: (ld_act,
-        act_step_stride) of the ensemble's member_act_out, which shares act_out's pitches and states them where act_out is absent."""
+        act_step_stride) of the ensemble's member_act_out, which shares act_out's pitches and states them where act_out is absent.
+        last_rows: as `rows`, for rows the ABI takes behind `tail` (a _limited twin's xflags_out behind its parent's arguments)."""
         rp, fp, os_, op, so, ap, lda, sa = self._closed_loop_outputs(n_steps, reward_out, flags_out, obs_out, act_out)
         extra = [_rows(t, dtype, n_steps) for _, t, dtype in rows]
-        strides = {st for ptr, st in extra if ptr is not None} | ({os_} if (rp is not None or fp is not None) else set())
-        names = [name for name, _, _ in rows]
+        last = [_rows(t, dtype, n_steps) for _, t, dtype in last_rows]
+        strides = {st for ptr, st in extra + last if ptr is not None} | ({os_} if (rp is not None or fp is not None) else set())
+        names = [name for name, _, _ in (*rows, *last_rows)]
         assert len(strides) <= 1, (f"{', '.join(names[:-1])} and {names[-1]} share" if len(names) > 1 else f"{names[0]} shares") \
             + " the reward/flags row stride"
         if member_pitches is not None:
@@ -710,7 +766,7 @@ class BatchedIndustrialEnv:
             lda, sa = member_pitches
         with torch.cuda.device(self._dev_index):
             _lib.check(fn(self._h, int(n_steps), *head, rp, fp, strides.pop() if strides else 0, op, so, ap, lda, sa,
-                          *[ptr for ptr, _ in extra], *tail, self._stream()))
+                          *[ptr for ptr, _ in extra], *tail, *[ptr for ptr, _ in last], self._stream()))
 
     def _closed_loop_outputs(self, n_steps, reward_out, flags_out, obs_out, act_out):
         """The output arguments the closed-loop rollouts share, from the optional tensors, validated:
@@ -779,6 +835,19 @@ class BatchedIndustrialEnv:
         """rollout_mlp() under the installed disturbance; outputs as rollout_policy_disturbed()."""
         self._closed_loop(self._L.nig_rollout_mlp_disturbed, n_steps, reward_out, flags_out, obs_out, act_out,
                           tail=self._seen_rows(n_steps, seen_out))
+
+    def rollout_policy_disturbed_limited(self, n_steps: int, reward_out=None, flags_out=None, obs_out=None, act_out=None, seen_out=None,
+                                         xflags_out=None):
+        """rollout_policy_disturbed() under the added safety constraints, checked on the true state and the action the env received;
+        xflags_out as rollout_policy_limited()'s."""
+        self._closed_loop(self._L.nig_rollout_policy_disturbed_limited, n_steps, reward_out, flags_out, obs_out, act_out,
+                          tail=self._seen_rows(n_steps, seen_out), last_rows=[("xflags_out", xflags_out, torch.int32)])
+
+    def rollout_mlp_disturbed_limited(self, n_steps: int, reward_out=None, flags_out=None, obs_out=None, act_out=None, seen_out=None,
+                                      xflags_out=None):
+        """rollout_mlp_disturbed() under the added safety constraints; outputs as rollout_policy_disturbed_limited()."""
+        self._closed_loop(self._L.nig_rollout_mlp_disturbed_limited, n_steps, reward_out, flags_out, obs_out, act_out,
+                          tail=self._seen_rows(n_steps, seen_out), last_rows=[("xflags_out", xflags_out, torch.int32)])
 
     def get_dataset(self, quality: str = "mixed", scale: int = 1, chunk: int = 100):
         """Batched env.get_dataset(quality): every lane is one episode of the reference's

@@ -1,0 +1,3 @@
+// PowerGrid's kernels of nig_rollout_policy_disturbed_limited / nig_rollout_mlp_disturbed_limited (the family under the user's added box constraints) -- a translation unit of their own (launcher: nig_launch_families.hpp)
+#include "nig_launch_families.hpp"
+NIG_DEFINE_ENV_DISTURBED_LIMITED(PowerGrid)

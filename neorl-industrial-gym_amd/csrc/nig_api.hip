@@ -451,6 +451,8 @@ static MlpArgs &shared_args(MlpArgs &q) { return q; }
 static PolicyArgs &shared_args(PolicyLimArgs &q) { return q.p; }
 static MlpArgs &shared_args(MlpSearchArgs &q) { return q.sh.m; }
 template <class Args> static MlpArgs &shared_args(Args &q) { return q.m; }      // MlpShieldArgs, MlpEnsArgs, MlpDistArgs, MlpGateArgs, MlpProjectArgs
+static PolicyArgs &shared_args(PolicyDistLimArgs &q) { return q.p; }
+template <class Parent> static MlpArgs &shared_args(MlpLimited<Parent> &q) { return shared_args(q.a); }      // a _limited twin: its parent's
 static unsigned closed_loop_grid(const nig_handle *h, const PolicyArgs &) { return grid_for(h->B); }
 static unsigned closed_loop_grid(const nig_handle *h, const MlpArgs &) { return (unsigned)((h->B + BLOCK / 2 - 1) / (BLOCK / 2)); }
 
@@ -1455,6 +1457,163 @@ int nig_rollout_mlp_disturbed(nig_handle *h, int32_t n_steps, float *reward_out,
         q.d = d;
         q.m.wstream = h->mlp_stream;
         return launch_of(h->env)->mlp_disturbed;
+    });
+}
+
+// ---- the other closed-loop families under the added constraints: the _limited twins --------------------------------------------
+// Each is its parent with the limits beside its arguments.  Order of refusals: bad argument, no limits installed (NIG_ERR_INVALID),
+// then every refusal of the parent in the parent's order, then closed_loop's argument contracts.  The Advanced pair never has
+// limits installed, so it refuses at the second step; an env without the MFMA actor refuses as the parent does.
+int nig_rollout_mlp_safe_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                                 float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
+                                 float *prob_out, uint32_t *xflags_out, void *stream)
+{
+    const char *const fn = "nig_rollout_mlp_safe_limited";
+    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    NIG_TRY(check_limits(h, fn));
+    if (!launch_of(h->env)->mlp_shield_limited) return refuse(fn, "env shape has no MFMA actor", NIG_ERR_UNSUPPORTED);
+    if (!h->mlp_stream) return refuse(fn, "no actor installed (nig_set_mlp_policy)");
+    if (!h->mlp_cstream) return refuse(fn, "no safety critic installed (nig_set_mlp_safety)");
+    return closed_loop<MlpLimited<MlpShieldArgs>>(h, fn, n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpLimited<MlpShieldArgs> &q) {
+        shield_fields(h, prob_out, q.a);
+        limit_args(h, xflags_out, q.a.m.s, q.l);
+        return launch_of(h->env)->mlp_shield_limited;
+    });
+}
+
+int nig_rollout_mlp_search_limited(nig_handle *h, int32_t n_steps, int32_t n_candidates, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                                   float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
+                                   float *prob_out, float *risk_out, int32_t *choice_out, uint32_t *xflags_out, void *stream)
+{
+    const char *const fn = "nig_rollout_mlp_search_limited";
+    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    NIG_TRY(check_limits(h, fn));
+    if (!launch_of(h->env)->mlp_search_limited) return refuse(fn, "env shape has no MFMA actor", NIG_ERR_UNSUPPORTED);
+    if (n_candidates < 1 || n_candidates > NIG_MAX_CANDIDATES) return refuse(fn, "n_candidates outside 1 .. NIG_MAX_CANDIDATES");
+    if (!h->mlp_stream) return refuse(fn, "no actor installed (nig_set_mlp_policy)");
+    if (!h->mlp_cstream) return refuse(fn, "no safety critic installed (nig_set_mlp_safety)");
+    return closed_loop<MlpLimited<MlpSearchArgs>>(h, fn, n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpLimited<MlpSearchArgs> &q) {
+        shield_fields(h, prob_out, q.a.sh);
+        q.a.n_candidates = n_candidates; q.a.risk_out = risk_out; q.a.choice_out = choice_out;
+        limit_args(h, xflags_out, q.a.sh.m.s, q.l);
+        return launch_of(h->env)->mlp_search_limited;
+    });
+}
+
+int nig_rollout_mlp_gated_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                                  float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
+                                  float *prob_out, float *unc_out, float *logit_out, int64_t ld_c, int64_t c_step_stride,
+                                  uint32_t *xflags_out, void *stream)
+{
+    const char *const fn = "nig_rollout_mlp_gated_limited";
+    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    NIG_TRY(check_limits(h, fn));
+    if (!launch_of(h->env)->mlp_gated_limited) return refuse(fn, "env shape has no MFMA actor", NIG_ERR_UNSUPPORTED);
+    if (!h->mlp_stream) return refuse(fn, "no actor installed (nig_set_mlp_policy)");
+    if (h->gate_members < 1 || !h->gate_stream) return refuse(fn, "no safety ensemble installed (nig_set_mlp_safety_ensemble)");
+    if (prob_out || unc_out || logit_out) {
+        if (ld_c < h->B || ld_c > NIG_MAX_PITCH) return refuse(fn, "ld_c outside [batch, 2^26]");
+        if (c_step_stride < (int64_t)h->gate_outputs * ld_c) return refuse(fn, "c_step_stride smaller than one [n_outputs][ld_c] block");
+    }
+    return closed_loop<MlpLimited<MlpGateArgs>>(h, fn, n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpLimited<MlpGateArgs> &q) {
+        q.a.m.wstream = h->mlp_stream;
+        q.a.cstreams = h->gate_stream; q.a.n_members = h->gate_members; q.a.n_outputs = h->gate_outputs; q.a.kf = (float)h->gate_members;
+        q.a.temperature = h->gate_T; q.a.threshold = h->gate_thr; q.a.umax = h->gate_umax;
+        q.a.prob_out = prob_out; q.a.unc_out = unc_out; q.a.logit_out = logit_out;
+        q.a.ld_c = (uint32_t)ld_c; q.a.c_step_stride = (uint64_t)c_step_stride;
+        limit_args(h, xflags_out, q.a.m.s, q.l);
+        return launch_of(h->env)->mlp_gated_limited;
+    });
+}
+
+int nig_rollout_mlp_projected_limited(nig_handle *h, int32_t n_steps, int32_t max_iters, float step, float *reward_out, uint32_t *flags_out,
+                                      int64_t out_stride, float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
+                                      int64_t act_step_stride, float *prob_out, float *viol_out, int32_t *iters_out, float *grad_out,
+                                      int64_t ld_c, int64_t c_step_stride, uint32_t *xflags_out, void *stream)
+{
+    const char *const fn = "nig_rollout_mlp_projected_limited";
+    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    NIG_TRY(check_limits(h, fn));
+    if (!launch_of(h->env)->mlp_projected_limited) return refuse(fn, "env shape has no MFMA actor", NIG_ERR_UNSUPPORTED);
+    if (!h->mlp_stream) return refuse(fn, "no actor installed (nig_set_mlp_policy)");
+    if (h->proj_outputs < 1 || !h->proj_cstream || !h->proj_bstream) return refuse(fn, "no constraint predictor installed (nig_set_mlp_constraint)");
+    if (max_iters < 1 || max_iters > NIG_MAX_PROJECT_ITERS) return refuse(fn, "max_iters outside 1 .. NIG_MAX_PROJECT_ITERS");
+    if (!std::isfinite(step)) return refuse(fn, "step must be finite");
+    if (prob_out || viol_out) {
+        if (ld_c < h->B || ld_c > NIG_MAX_PITCH) return refuse(fn, "ld_c outside [batch, 2^26]");
+        if (c_step_stride < (int64_t)h->proj_outputs * ld_c) return refuse(fn, "c_step_stride smaller than one [n_outputs][ld_c] block");
+    }
+    if (grad_out && (ld_act < h->B || ld_act > NIG_MAX_PITCH || act_step_stride < (int64_t)SPECS[h->env].action_dim * ld_act))
+        return refuse(fn, "bad action trajectory pitch (grad_out takes act_out's)");
+    return closed_loop<MlpLimited<MlpProjectArgs>>(h, fn, n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpLimited<MlpProjectArgs> &q) {
+        q.a.m.wstream = h->mlp_stream;
+        q.a.cstream = h->proj_cstream; q.a.bstream = h->proj_bstream; q.a.n_outputs = h->proj_outputs; q.a.max_iters = max_iters;
+        q.a.threshold = h->proj_thr; q.a.tolerance = h->proj_tol; q.a.step = step;
+        q.a.prob_out = prob_out; q.a.viol_out = viol_out; q.a.iters_out = iters_out; q.a.grad_out = grad_out;
+        q.a.ld_c = (uint32_t)ld_c; q.a.c_step_stride = (uint64_t)c_step_stride;
+        limit_args(h, xflags_out, q.a.m.s, q.l);
+        return launch_of(h->env)->mlp_projected_limited;
+    });
+}
+
+int nig_rollout_mlp_ensemble_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                                     float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
+                                     float *unc_out, float *member_act_out, uint32_t *xflags_out, void *stream)
+{
+    const char *const fn = "nig_rollout_mlp_ensemble_limited";
+    if (!h || n_steps <= 0) return refuse(fn, "bad argument (handle, n_steps)");
+    NIG_TRY(check_limits(h, fn));
+    if (!launch_of(h->env)->mlp_ensemble_limited) return refuse(fn, "env shape has no MFMA actor", NIG_ERR_UNSUPPORTED);
+    if (h->ens_members < 1 || !h->ens_stream) return refuse(fn, "no ensemble installed (nig_set_mlp_ensemble)");
+    // member_act_out shares act_out's pitches: the same checks apply to it when act_out is absent
+    return closed_loop<MlpLimited<MlpEnsArgs>>(h, fn, n_steps,
+                                               {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out ? act_out : member_act_out, ld_act, act_step_stride},
+                                               stream, [&](MlpLimited<MlpEnsArgs> &q) {
+        q.a.m.act_out = act_out;
+        q.a.m.wstream = h->ens_stream;
+        q.a.n_members = h->ens_members; q.a.w = h->ens_w; q.a.wsum = h->ens_wsum; q.a.kf = (float)h->ens_members; q.a.threshold = h->ens_threshold;
+        q.a.unc_out = unc_out; q.a.member_out = member_act_out;
+        limit_args(h, xflags_out, q.a.m.s, q.l);
+        return [h](const MlpLimited<MlpEnsArgs> &e, unsigned grid, hipStream_t st) {
+            launch_of(h->env)->mlp_ensemble_limited(h->ens_method == NIG_ENSEMBLE_AVERAGE ? ENS_AVERAGE : ENS_VOTING, e, grid, st);
+        };
+    });
+}
+
+int nig_rollout_policy_disturbed_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                                         float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
+                                         int64_t act_step_stride, float *seen_out, int64_t seen_step_stride, uint32_t *xflags_out, void *stream)
+{
+    const char *const fn = "nig_rollout_policy_disturbed_limited";
+    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    NIG_TRY(check_limits(h, fn));
+    if (!h->has_policy) return refuse(fn, "no policy installed (nig_set_policy)");
+    DisturbArgs d;
+    NIG_TRY(disturb_args(h, fn, seen_out, seen_step_stride, d));
+    return closed_loop<PolicyDistLimArgs>(h, fn, n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](PolicyDistLimArgs &q) {
+        q.d = d;
+        policy_fields(h, q.p);
+        limit_args(h, xflags_out, q.p.s, q.l);
+        return launch_of(h->env)->policy_disturbed_limited;
+    });
+}
+
+int nig_rollout_mlp_disturbed_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                                      float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
+                                      int64_t act_step_stride, float *seen_out, int64_t seen_step_stride, uint32_t *xflags_out, void *stream)
+{
+    const char *const fn = "nig_rollout_mlp_disturbed_limited";
+    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    NIG_TRY(check_limits(h, fn));
+    if (!launch_of(h->env)->mlp_disturbed_limited) return refuse(fn, "env shape has no MFMA actor", NIG_ERR_UNSUPPORTED);
+    if (!h->mlp_stream) return refuse(fn, "no actor installed (nig_set_mlp_policy)");
+    DisturbArgs d;
+    NIG_TRY(disturb_args(h, fn, seen_out, seen_step_stride, d));
+    return closed_loop<MlpLimited<MlpDistArgs>>(h, fn, n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpLimited<MlpDistArgs> &q) {
+        q.a.d = d;
+        q.a.m.wstream = h->mlp_stream;
+        limit_args(h, xflags_out, q.a.m.s, q.l);
+        return launch_of(h->env)->mlp_disturbed_limited;
     });
 }
 

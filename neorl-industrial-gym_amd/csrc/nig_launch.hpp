@@ -1,7 +1,7 @@
 // nig_launch.hpp -- the host side of libnig.so's kernels: the list of environments and the per-environment launch table.  An
 // env_<key>.hip instantiates the env's kernels by defining its table (NIG_DEFINE_ENV_LAUNCH); nig_api.hip reaches them through the
 // table's function pointers only.  The launchers of the kernel families with translation units of their own (sampled_, ensemble_,
-// disturbed_, search_, gated_, projected_, limited_<key>.hip) are DECLARED here and defined in nig_launch_families.hpp, which those units alone include.  Which
+// disturbed_, search_, gated_, projected_, limited_, limited_<family>_<key>.hip) are DECLARED here and defined in nig_launch_families.hpp, which those units alone include.  Which
 // kernel form a rollout launch takes is decided in nig_launch_plan.hpp; the functions here run its plans.
 #pragma once
 #include "nig_kernels.hpp"
@@ -60,6 +60,16 @@ struct EnvLaunch {
     void (*step64_limited)(const StepLimArgs &, bool parity, unsigned grid, hipStream_t);
     void (*policy_limited)(const PolicyLimArgs &, unsigned grid, hipStream_t);
     void (*mlp_limited)(const MlpLimArgs &, unsigned grid, hipStream_t);
+    // limited_<family>_<key>.hip: the other closed-loop families under the added constraints (nig_rollout_mlp_safe_limited, _search_limited,
+    // _gated_limited, _projected_limited, _ensemble_limited, _disturbed_limited: nullptr as `mlp`; nig_rollout_policy_disturbed_limited);
+    // all nullptr for the Advanced pair
+    void (*mlp_shield_limited)(const MlpLimited<MlpShieldArgs> &, unsigned grid, hipStream_t);
+    void (*mlp_search_limited)(const MlpLimited<MlpSearchArgs> &, unsigned grid, hipStream_t);
+    void (*mlp_gated_limited)(const MlpLimited<MlpGateArgs> &, unsigned grid, hipStream_t);
+    void (*mlp_projected_limited)(const MlpLimited<MlpProjectArgs> &, unsigned grid, hipStream_t);
+    void (*mlp_ensemble_limited)(int ens, const MlpLimited<MlpEnsArgs> &, unsigned grid, hipStream_t);
+    void (*mlp_disturbed_limited)(const MlpLimited<MlpDistArgs> &, unsigned grid, hipStream_t);
+    void (*policy_disturbed_limited)(const PolicyDistLimArgs &, unsigned grid, hipStream_t);
 };
 
 template <class Env>
@@ -78,6 +88,11 @@ template <class Env> constexpr auto mlp_kernel(const MlpSearchArgs &) { return r
 template <class Env> constexpr auto mlp_kernel(const MlpGateArgs &) { return rollout_mlp_gated_kernel<Env>; }
 template <class Env> constexpr auto mlp_kernel(const MlpProjectArgs &) { return rollout_mlp_projected_kernel<Env>; }
 template <class Env> constexpr auto mlp_kernel(const MlpLimArgs &) { return rollout_mlp_limited_kernel<Env>; }
+template <class Env> constexpr auto mlp_kernel(const MlpLimited<MlpShieldArgs> &) { return rollout_mlp_shield_limited_kernel<Env>; }
+template <class Env> constexpr auto mlp_kernel(const MlpLimited<MlpSearchArgs> &) { return rollout_mlp_search_limited_kernel<Env>; }
+template <class Env> constexpr auto mlp_kernel(const MlpLimited<MlpGateArgs> &) { return rollout_mlp_gated_limited_kernel<Env>; }
+template <class Env> constexpr auto mlp_kernel(const MlpLimited<MlpProjectArgs> &) { return rollout_mlp_projected_limited_kernel<Env>; }
+template <class Env> constexpr auto mlp_kernel(const MlpLimited<MlpDistArgs> &) { return rollout_mlp_disturbed_limited_kernel<Env>; }
 
 template <class Env, class Args>
 static void launch_mlp(const Args &q, unsigned grid, hipStream_t st)
@@ -251,6 +266,13 @@ template <class Env> void launch_step_limited_env(const StepLimArgs &q, bool par
 template <class Env> void launch_step64_limited_env(const StepLimArgs &q, bool parity, unsigned grid, hipStream_t st);
 template <class Env> void launch_policy_limited_env(const PolicyLimArgs &q, unsigned grid, hipStream_t st);
 template <class Env> void launch_mlp_limited_env(const MlpLimArgs &q, unsigned grid, hipStream_t st);
+template <class Env> void launch_mlp_shield_limited_env(const MlpLimited<MlpShieldArgs> &q, unsigned grid, hipStream_t st);
+template <class Env> void launch_mlp_search_limited_env(const MlpLimited<MlpSearchArgs> &q, unsigned grid, hipStream_t st);
+template <class Env> void launch_mlp_gated_limited_env(const MlpLimited<MlpGateArgs> &q, unsigned grid, hipStream_t st);
+template <class Env> void launch_mlp_projected_limited_env(const MlpLimited<MlpProjectArgs> &q, unsigned grid, hipStream_t st);
+template <class Env> void launch_mlp_ensemble_limited_env(int ens, const MlpLimited<MlpEnsArgs> &q, unsigned grid, hipStream_t st);
+template <class Env> void launch_mlp_disturbed_limited_env(const MlpLimited<MlpDistArgs> &q, unsigned grid, hipStream_t st);
+template <class Env> void launch_policy_disturbed_limited_env(const PolicyDistLimArgs &q, unsigned grid, hipStream_t st);
 
 template <class Env>
 static void launch_policy(const PolicyArgs &q, unsigned /*grid*/, hipStream_t st)
@@ -304,6 +326,13 @@ static const EnvLaunch *env_launch_table()
             t.step64_limited = Env::HAS_ACT64 ? launch_step64_limited_env<Env> : nullptr;
             t.policy_limited = launch_policy_limited_env<Env>;
             t.mlp_limited = mlp_slot<Env>(launch_mlp_limited_env<Env>);
+            t.mlp_shield_limited = mlp_slot<Env>(launch_mlp_shield_limited_env<Env>);
+            t.mlp_search_limited = mlp_slot<Env>(launch_mlp_search_limited_env<Env>);
+            t.mlp_gated_limited = mlp_slot<Env>(launch_mlp_gated_limited_env<Env>);
+            t.mlp_projected_limited = mlp_slot<Env>(launch_mlp_projected_limited_env<Env>);
+            t.mlp_ensemble_limited = mlp_slot<Env>(launch_mlp_ensemble_limited_env<Env>);
+            t.mlp_disturbed_limited = mlp_slot<Env>(launch_mlp_disturbed_limited_env<Env>);
+            t.policy_disturbed_limited = launch_policy_disturbed_limited_env<Env>;
         }
         return t;
     }();

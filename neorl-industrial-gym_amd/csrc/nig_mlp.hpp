@@ -1,5 +1,6 @@
 // nig_mlp.hpp -- the fused MLP actor on MFMA with its safety-critic shield and its ensemble (device code only): MlpArgs,
-// MlpShieldArgs, MlpEnsArgs, MlpDistArgs, MlpSearchArgs, MlpGateArgs, MlpProjectArgs, MlpLimArgs, rollout_mlp_body and its eight kernels.
+// MlpShieldArgs, MlpEnsArgs, MlpDistArgs, MlpSearchArgs, MlpGateArgs, MlpProjectArgs, MlpLimArgs, MlpLimited<>, rollout_mlp_body and its
+// eight kernels with their _limited twins.
 #pragma once
 #include <type_traits>
 #include "nig_step.hpp"
@@ -215,7 +216,7 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
                                                                        [[maybe_unused]] const MlpProjectArgs *jq = nullptr,
                                                                        [[maybe_unused]] const LimitArgs *lq = nullptr)
 {
-    static_assert(!LIMITS || (!SHIELD && ENS == ENS_NONE && !DIST), "the added constraints have the plain actor's form only");
+    // LIMITS combines with every other form (the _limited twins at the end of this header): the added constraints live at the one step site
     static_assert(!PROJECT || (SHIELD && !SEARCH && !GATE), "the projection is a form of the shield; it excludes the search and the gate");
     static_assert(!(SHIELD && ENS != ENS_NONE), "the ensemble has no shield");
     static_assert(!SEARCH || SHIELD, "the search is a form of the shield");
@@ -759,7 +760,10 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
         const int step_pre = (int)(ctr & NIG_CTR_STEP_MASK);
         StepResult<Env, reward_of<Env, act_t>> res;
         if constexpr (LIMITS) {                    // the added constraints beside the built-ins (nig_limits.hpp): res counts both kinds
-            const uint32_t xf = step_core_limited<Env>((limit_table_ptr)lq->table, s, a, nz, step_pre, p.max_steps, p.dt32, p.dt, p.cmask, n, res);
+            // (the action the env receives: halved, chosen, zeroed, projected, disturbed; the ensemble's float64 one where the env steps on it)
+            uint32_t xf;
+            if constexpr (ACT64) xf = step_core_limited<Env>((limit_table_ptr)lq->table, s, a64, nz, step_pre, p.max_steps, p.dt32, p.dt, p.cmask, n, res);
+            else xf = step_core_limited<Env>((limit_table_ptr)lq->table, s, a, nz, step_pre, p.max_steps, p.dt32, p.dt, p.cmask, n, res);
             if (writer && lq->xflags) (lq->xflags + orow)[lo] = frozen ? 0u : xf;
         }
         else if constexpr (ACT64) step_core<Env>(s, a64, nz, step_pre, p.max_steps, p.dt32, p.dt, p.cmask, n, res);
@@ -864,6 +868,52 @@ template <class Env>
 __global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_limited_kernel(const MlpLimArgs q)
 {
     rollout_mlp_body<Env, false, ENS_NONE, false, false, false, false, true>(q.m, nullptr, nullptr, 0.0f, nullptr, nullptr, nullptr, nullptr, nullptr, &q.l);
+}
+
+// The other families under the added constraints: a parent's argument block with the limits behind it, and the parent's body with
+// LIMITS on -- step_core_limited on the action the env receives, limited_flag_counts behind pack_flags (SHIELDED / UNCERTAIN are
+// OR-ed in after it), the xflags row.  Each is instantiated in the env's limited_<family>_*.hip translation unit only.
+template <class Parent>
+struct MlpLimited {
+    Parent a;
+    LimitArgs l;
+};
+
+template <class Env>
+__global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_shield_limited_kernel(const MlpLimited<MlpShieldArgs> q)
+{
+    rollout_mlp_body<Env, true, ENS_NONE, false, false, false, false, true>(q.a.m, q.a.cstream, q.a.prob_out, q.a.threshold, nullptr, nullptr, nullptr, nullptr, nullptr, &q.l);
+}
+
+template <class Env>
+__global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_search_limited_kernel(const MlpLimited<MlpSearchArgs> q)
+{
+    rollout_mlp_body<Env, true, ENS_NONE, false, true, false, false, true>(q.a.sh.m, q.a.sh.cstream, q.a.sh.prob_out, q.a.sh.threshold, nullptr, nullptr, &q.a, nullptr, nullptr, &q.l);
+}
+
+template <class Env>
+__global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_gated_limited_kernel(const MlpLimited<MlpGateArgs> q)
+{
+    rollout_mlp_body<Env, true, ENS_NONE, false, false, true, false, true>(q.a.m, q.a.cstreams, nullptr, q.a.threshold, nullptr, nullptr, nullptr, &q.a, nullptr, &q.l);
+}
+
+template <class Env>
+__global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_projected_limited_kernel(const MlpLimited<MlpProjectArgs> q)
+{
+    rollout_mlp_body<Env, true, ENS_NONE, false, false, false, true, true>(q.a.m, q.a.cstream, nullptr, q.a.threshold, nullptr, nullptr, nullptr, nullptr, &q.a, &q.l);
+}
+
+// (ENS_AVERAGE on an HAS_ACT64 env: step_core_limited on the float64 action, as step_limited_kernel<Env, *, true>)
+template <class Env, int ENS>
+__global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_ensemble_limited_kernel(const MlpLimited<MlpEnsArgs> q)
+{
+    rollout_mlp_body<Env, false, ENS, false, false, false, false, true>(q.a.m, nullptr, nullptr, 0.0f, &q.a, nullptr, nullptr, nullptr, nullptr, &q.l);
+}
+
+template <class Env>
+__global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_disturbed_limited_kernel(const MlpLimited<MlpDistArgs> q)
+{
+    rollout_mlp_body<Env, false, ENS_NONE, true, false, false, false, true>(q.a.m, nullptr, nullptr, 0.0f, nullptr, &q.a.d, nullptr, nullptr, nullptr, &q.l);
 }
 
 }  // namespace nig

@@ -1,5 +1,6 @@
 // nig_rollout_policy.hpp -- the closed-loop fused rollout, one wave per 64 lanes (device code only): rollout_policy_kernel,
-// under sensor / actuator noise rollout_policy_disturbed_kernel, and under added box constraints rollout_policy_limited_kernel.
+// under sensor / actuator noise rollout_policy_disturbed_kernel, under added box constraints rollout_policy_limited_kernel, and
+// under both rollout_policy_disturbed_limited_kernel.
 // Its three-wave form is nig_split_policy.hpp.
 #pragma once
 #include "nig_policy.hpp"
@@ -8,7 +9,7 @@
 
 namespace nig {
 
-// The body is written once (nig_rollout_policy_body.inc) and compiled into three kernels by textual inclusion, as the three-wave
+// The body is written once (nig_rollout_policy_body.inc) and compiled into four kernels by textual inclusion, as the three-wave
 // kernels are (nig_split.hpp says why: through a __device__ function taking the arguments by reference hipcc generates different
 // code for the existing kernel, which is required not to change: profiles/isa_diff.py).
 template <class Env>
@@ -52,6 +53,24 @@ __global__ void __launch_bounds__(BLOCK) rollout_policy_limited_kernel(const Pol
     const PolicyArgs &q = ql.p;
     [[maybe_unused]] constexpr const DisturbArgs *dq = nullptr;
     const LimitArgs *const lq = &ql.l;
+#include "nig_rollout_policy_body.inc"
+}
+
+struct PolicyDistLimArgs {
+    PolicyArgs p;
+    DisturbArgs d;
+    LimitArgs l;
+};
+
+// DIST and LIM together: the disturbed and clipped action is the one step_core_limited checks.
+// Instantiated in the env's limited_disturbed_*.hip translation unit only (launch_policy_disturbed_limited_env).
+template <class Env>
+__global__ void __launch_bounds__(BLOCK) rollout_policy_disturbed_limited_kernel(const PolicyDistLimArgs qx)
+{
+    constexpr bool DIST = true, LIM = true;
+    const PolicyArgs &q = qx.p;
+    const DisturbArgs *const dq = &qx.d;
+    const LimitArgs *const lq = &qx.l;
 #include "nig_rollout_policy_body.inc"
 }
 

@@ -160,13 +160,15 @@ def evaluate_robustness(agent, environment, n_episodes: int = 100, noise_levels=
                         disturbance_types=("observation_noise", "action_noise", "dynamics_noise"), hold: str = "episode",
                         batch: Optional[int] = None, seed: int = 0x5EED, device="cuda:0") -> Dict[str, Any]:
     """RobustnessBenchmark.evaluate_agent on batched lanes.  `environment`: an env id, or a BatchedIndustrialEnv whose
-    construction arguments (id, batch, device, seed, max_episode_steps, dt) are reused.  Every (type, level) cell plays
+    construction arguments (id, batch, device, seed, max_episode_steps, dt) are reused and whose added safety constraints
+    (add_safety_constraint) are installed on every cell's handle.  Every (type, level) cell plays
     n_episodes // len(noise_levels) episodes on a FRESH handle with the same seed -- tallies start at zero and the cells share
     their random numbers, as upstream's fixed episode keys do.  The level multiplies a unit sigma on every dimension;
     "dynamics_noise" runs undisturbed, as upstream.  safety_violations = the sum of the per-step violation counts
     (evaluate_with_safety's figure), violation_rate = the share of episodes with at least one violation (upstream reads a
     field that does not exist for both).  `path`: "fused-mlp", "fused-policy" or "host" -- how the disturbed cells ran."""
     from .batched import BatchedIndustrialEnv
+    from .core import BoxConstraint
     from .utils import _disturbed_route, _evaluate_batched
     if not getattr(agent, "is_trained", False):
         raise RuntimeError("Agent must be trained before evaluation")
@@ -175,7 +177,9 @@ def evaluate_robustness(agent, environment, n_episodes: int = 100, noise_levels=
             raise ValueError(f"unknown disturbance type {kind!r}")
     noise_levels, disturbance_types = list(noise_levels), list(disturbance_types)
     kw: Dict[str, Any] = {}
+    added = []                                     # the BoxConstraints added to `environment`: every cell's fresh handle takes them too
     if isinstance(environment, BatchedIndustrialEnv):
+        added = [c for c in environment.safety_constraints if isinstance(c, BoxConstraint)]
         env_id, device, seed = environment.env_id, environment.device, environment.seed
         batch = batch or environment.batch
         kw = dict(max_episode_steps=environment.max_episode_steps, dt=environment.dt, env_index0=environment.env_index0)
@@ -197,6 +201,8 @@ def evaluate_robustness(agent, environment, n_episodes: int = 100, noise_levels=
                 cell_agent = Disturbed(agent, Disturbance(action_noise=level, hold=hold), seed=seed)
             env = BatchedIndustrialEnv(env_id, batch, device=device, seed=seed, tally=True, autoreset=False, **kw)
             try:
+                for c in added:
+                    env.add_safety_constraint(c)
                 if cell_agent is not agent and path is None:
                     path = _disturbed_route(cell_agent, env)[0]
                 with_violation = [0]

@@ -144,18 +144,12 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
     per-step loop; `agent` may come back upgraded (a reference EnsembleAgent as an EnsemblePolicy); `disturbed` names the
     fused route of a disturbance.Disturbed ("fused-policy" / "fused-mlp": the caller removes the disturbance afterwards).
     plain = no recorded draws are injected (with them every agent takes the host loop).
-    On an env with added safety constraints (add_safety_constraint) a plain DevicePolicy goes to rollout_policy_limited and a
-    plain fusable MLPPolicy to rollout_mlp_limited; every other agent takes the host loop, whose env.step knows the constraints."""
-    if getattr(env, "has_limits", False):
-        if plain and hasattr(agent, "to_struct"):
-            env.set_policy(agent)
-            return agent, env.rollout_policy_limited, None
-        shielded = getattr(agent, "safety_weights", None) is not None and hasattr(agent, "threshold")
-        if (plain and not hasattr(agent, "install") and getattr(agent, "fusable", False) and not shielded
-                and env.state_dim % 2 == 0 and env.action_dim <= 16):
-            env.set_mlp_policy(agent.weights)
-            return agent, env.rollout_mlp_limited, None
-        return agent, None, None
+    On an env with added safety constraints (add_safety_constraint) every route is the same and ends at the `_limited` method of
+    its family (rollout_policy_limited, rollout_mlp_limited, rollout_mlp_safe_limited, ..., rollout_mlp_disturbed_limited), whose
+    kernels check the constraints on the action the env receives; an MFMA family on an env without the MFMA actor takes the host
+    loop there, whose env.step knows the constraints.  Only agents that take the host loop without added constraints take it with them."""
+    limited = bool(getattr(env, "has_limits", False))
+    mfma_env = env.state_dim % 2 == 0 and env.action_dim <= 16
     device_policy = hasattr(agent, "to_struct") and plain
     if plain and all(hasattr(agent, k) for k in ("agents", "weights", "ensemble_method")) and not hasattr(agent, "install"):
         # the reference's EnsembleAgent: its K actors fused into the env kernel where members and env allow it (EnsemblePolicy);
@@ -170,7 +164,7 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
     ensemble = plain and hasattr(agent, "install") and getattr(agent, "fusable", False) and env.state_dim % 2 == 0 and env.action_dim <= 16
     gated = ensemble and hasattr(agent, "max_uncertainty")        # SafetyEnsemblePolicy: its install() puts actor and members on the handle
     projecting = ensemble and hasattr(agent, "max_iters")         # ConstraintProjectionPolicy: install() puts actor and predictor on the handle
-    fused_mlp = not hasattr(agent, "install") and getattr(agent, "fusable", False) and plain
+    fused_mlp = not hasattr(agent, "install") and getattr(agent, "fusable", False) and plain and (mfma_env or not limited)
     shielded = fused_mlp and getattr(agent, "safety_weights", None) is not None and hasattr(agent, "threshold")
     searching = shielded and hasattr(agent, "n_candidates")       # MLPPolicy.searching(): get_safe_action instead of the halving
     disturbed = None           # a disturbance.Disturbed whose inner agent runs in the env kernel: "fused-policy" / "fused-mlp"
@@ -196,13 +190,13 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
         device_policy = True
     rollout = None
     if device_policy:
-        rollout = (env.rollout_policy_disturbed if disturbed == "fused-policy" else env.rollout_mlp_disturbed if disturbed
-                   else env.rollout_mlp_gated if gated
-                   else (lambda n, *a, **k: env.rollout_mlp_projected(n, agent.max_iters, agent.step, *a, **k)) if projecting
-                   else env.rollout_mlp_ensemble if ensemble
-                   else (lambda n, *a, **k: env.rollout_mlp_search(n, agent.n_candidates, *a, **k)) if searching
-                   else env.rollout_mlp_safe if shielded else env.rollout_mlp if fused_mlp
-                   else env.rollout_policy)
+        name = ("rollout_policy_disturbed" if disturbed == "fused-policy" else "rollout_mlp_disturbed" if disturbed
+                else "rollout_mlp_gated" if gated else "rollout_mlp_projected" if projecting else "rollout_mlp_ensemble" if ensemble
+                else "rollout_mlp_search" if searching else "rollout_mlp_safe" if shielded else "rollout_mlp" if fused_mlp
+                else "rollout_policy")
+        method = getattr(env, name + "_limited" if limited else name)
+        rollout = ((lambda n, *a, **k: method(n, agent.max_iters, agent.step, *a, **k)) if projecting
+                   else (lambda n, *a, **k: method(n, agent.n_candidates, *a, **k)) if searching else method)
     return agent, rollout, disturbed
 
 

@@ -14,7 +14,19 @@ The constraints are boxes over one state row and one action row each, with bound
 critical: the episodes keep the parents' lengths).  No outputs are written by any series (the rollouts' own default), so the
 figures are the kernels' compute cost.
 
-usage: python profiles/bench_limits.py [--out-dir DIR]   ->  DIR/ab.jsonl (one line per series), DIR/ab.txt (the table)"""
+usage: python profiles/bench_limits.py [--out-dir DIR]   ->  DIR/ab.jsonl (one line per series), DIR/ab.txt (the table)
+
+--families: the _limited twins of the other closed-loop families instead, each against its OWN parent family in the same session
+(DIR/ab_families.jsonl, DIR/ab_families.txt), the plain pair mlp / mlp_limited beside them:
+  safe, search (3 candidates), gated (2 members of 2 rows), projected (3 iterations), ensemble ("voting", 3 members),
+  disturbed (sigma 0.1 on observation and action, hold "step"), policy_disturbed (the "MPC" law; one-wave form in both)
+  and <family>_limited_1 / _limited_4.  Thresholds of 0.5 / an uncertainty limit of 0.2 on random critics: some lanes of nearly
+  every block take the correction, so the block-voted passes of the search and the projection run in parent and twin alike (the
+  boxes are not critical: the twin plays the parent's trajectory).
+Expectation, written before the first measurement: the added constraints are checked once per STEP, whatever the number of network
+passes of the step, so a twin's absolute overhead per step should equal the plain form's (mlp_limited - mlp) of the same session,
+and its relative overhead should be smaller than the plain form's 1.01 - 1.05 x.  A twin whose absolute overhead is more than twice
+the plain form's is a finding to explain from its listing."""
 import argparse
 import json
 import os
@@ -35,6 +47,7 @@ ap.add_argument("--policy-launches", type=int, default=200)
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--repeats", type=int, default=3)
 ap.add_argument("--envs", default="ChemicalReactor-v0,PowerGrid-v0")
+ap.add_argument("--families", action="store_true", help="time the _limited twins of the other families against their parents")
 ap.add_argument("--out-dir", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "limits"))
 args = ap.parse_args()
 B, T, N = args.batch, args.steps, args.launches
@@ -67,6 +80,92 @@ def timed(env, name, series, launch, repeat, N=N):
     rows.append(row)
     print(json.dumps(row), flush=True)
 
+
+def critic(S, A, seed, n_out=1):
+    rng, D = np.random.default_rng(seed), S + A
+    return [(rng.normal(0, 0.02 / np.sqrt(D), (D, 256)).astype(np.float32), np.zeros(256, np.float32)),
+            (rng.normal(0, 1 / 16, (256, 256)).astype(np.float32), np.zeros(256, np.float32)),
+            (rng.normal(0, 1 / 16, (256, n_out)).astype(np.float32), np.zeros(n_out, np.float32))]
+
+
+def run_families():
+    """Every family's parent and its _limited twin with one and four boxes, alternating through the repeats."""
+    FAMILIES = ("mlp", "safe", "search", "gated", "projected", "ensemble", "disturbed", "policy_disturbed")
+    for name in args.envs.split(","):
+        env = ni.make_batched(name, B, autoreset=True, tally=True)
+        S, A = env.state_dim, env.action_dim
+        env.set_mlp_policy(actor(S, A, 10))
+        env.set_policy(ni.mpc_agent(S, A))
+        env.set_mlp_safety(critic(S, A, 11), 0.5)
+        env.set_mlp_safety_ensemble([critic(S, A, 12, 2), critic(S, A, 13, 2)], 1.0, 0.5, 0.2)
+        env.set_mlp_constraint(critic(S, A, 14, 2), 0.5, 0.0)
+        env.set_mlp_ensemble([actor(S, A, 10 + k) for k in range(3)], None, None, "voting", 0.2)
+        env.set_disturbance(ni.Disturbance(obs_noise=0.1, action_noise=0.1, hold="step"))
+        env.reset()
+        state = env.get_state().cpu().numpy()
+        boxes = []
+        for c in range(4):      # the boxes of the plain series
+            lo, hi = np.quantile(state[:, c].astype(np.float64), [0.02, 0.98])
+            boxes.append(ni.BoxConstraint(f"box_{c}", {("state", c): (lo, max(hi, lo)), ("action", c % A): (-0.9, 0.9)}, -1.0))
+        call = {
+            "mlp": lambda sfx: getattr(env, "rollout_mlp" + sfx)(T),
+            "safe": lambda sfx: getattr(env, "rollout_mlp_safe" + sfx)(T),
+            "search": lambda sfx: getattr(env, "rollout_mlp_search" + sfx)(T, 3),
+            "gated": lambda sfx: getattr(env, "rollout_mlp_gated" + sfx)(T),
+            "projected": lambda sfx: getattr(env, "rollout_mlp_projected" + sfx)(T, 3, 0.1),
+            "ensemble": lambda sfx: getattr(env, "rollout_mlp_ensemble" + sfx)(T),
+            "disturbed": lambda sfx: getattr(env, "rollout_mlp_disturbed" + sfx)(T),
+            "policy_disturbed": lambda sfx: getattr(env, "rollout_policy_disturbed" + sfx)(T),
+        }
+
+        def install(n):
+            for b in list(env.safety_constraints):
+                if isinstance(b, ni.BoxConstraint):
+                    env.remove_safety_constraint(b.name)
+            for b in boxes[:n]:
+                env.add_safety_constraint(b)
+
+        for rep in range(args.repeats):
+            for fam in FAMILIES:
+                NL = args.policy_launches if fam == "policy_disturbed" else N
+                install(0)
+                timed(env, name, fam, lambda: call[fam](""), rep, NL)
+                for n in (1, 4):
+                    install(n)
+                    timed(env, name, f"{fam}_limited_{n}", lambda: call[fam]("_limited"), rep, NL)
+        env.close()
+    with open(os.path.join(args.out_dir, "ab_families.jsonl"), "w") as f:
+        for r in rows:
+            f.write(json.dumps(r) + "\n")
+    lines = [f"batch {B}, {T} steps per launch, {N} timed launches ({args.policy_launches} for policy_disturbed) after {args.warmup}, {args.repeats} alternating "
+             "repeats; microseconds per step, median of the launches, per repeat; overhead = twin - its own parent (medians of the repeats)",
+             f"{torch.cuda.get_device_name(0)}; {ni._lib.lib().nig_version().decode()}", ""]
+    for name in args.envs.split(","):
+        med = {}
+        for r in rows:
+            if r["env"] == name:
+                med.setdefault(r["series"], []).append(r["us_per_step_median"])
+        lines.append(name)
+        plain = {n: np.median(med[f"mlp_limited_{n}"]) - np.median(med["mlp"]) for n in (1, 4)}
+        for fam in FAMILIES:
+            for series in (fam, f"{fam}_limited_1", f"{fam}_limited_4"):
+                x = med[series]
+                txt = f"  {series:28s} {', '.join(f'{v:8.2f}' for v in x)} us   spread {100 * (max(x) - min(x)) / min(x):5.2f} %"
+                if series != fam:
+                    n = int(series[-1])
+                    over = np.median(x) - np.median(med[fam])
+                    txt += f"   / {fam}: {np.median(x) / np.median(med[fam]):.3f}   overhead {over:+7.2f} us"
+                    if fam not in ("mlp", "policy_disturbed"):
+                        txt += f" = {over / plain[n]:5.2f} x the plain form's {plain[n]:+.2f} us" if plain[n] > 0 else f" (the plain form's: {plain[n]:+.2f} us)"
+                lines.append(txt)
+        lines.append("")
+    open(os.path.join(args.out_dir, "ab_families.txt"), "w").write("\n".join(lines))
+    print("\n".join(lines))
+
+
+if args.families:
+    run_families()
+    sys.exit(0)
 
 SERIES = (("mlp", None), ("mlp_limited_1", "mlp"), ("mlp_limited_4", "mlp"), ("policy", None), ("policy_onewave", "policy"),
           ("policy_limited_1", "policy_onewave"), ("policy_limited_4", "policy_onewave"))
