@@ -544,6 +544,44 @@ int nig_rollout_mlp(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t 
                     float *act_out, int64_t ld_act, int64_t act_step_stride, void *stream);
 
 /*
+ * The same actor on the bf16 matrix unit (v_mfma_f32_32x32x16_bf16: a sixteenth of the float32 form's matrix cycles), for
+ * throughput-only sweeps: an opt-in family with its own arithmetic, outside the 1e-5 parity bar of nig_rollout_mlp, which it
+ * leaves untouched.  The law "nig-mlp-bf16-v1", for one lane and one step on state s[0..S) and the network (S -> 256 -> 256 -> A)
+ * of nig_set_mlp_policy:
+ *   rounding  bf(x): float32 -> bfloat16, round to nearest even; a NaN stays a NaN.
+ *   weights   W1, W2, W3 are rounded once on the host with bf; the biases b1, b2, b3 stay float32.
+ *   input     the observation enters as two bf16 parts (16 significant bits): hi_k = bf(s_k), lo_k = bf(s_k - hi_k) (the
+ *             subtraction is exact in float32), lo_k = 0 where hi_k is not finite; layer 1 reads
+ *             x = [hi_0 .. hi_{S-1}, lo_0 .. lo_{S-1}] against W1's rows used twice (zero-padded to a multiple of 16).
+ *   layers    z1_u = b1_u + sum_k W1[k][u] x_k, h1_u = bf(max(z1_u, 0));  z2_u = b2_u + sum_k W2[k][u] h1_k, h2_u = bf(max(z2_u, 0));
+ *             z3_j = b3_j + sum_k W3[k][j] h2_k, a_j = det_tanhf(z3_j) (the float32 actor's tanh).
+ *   sums      products of two bf16 values are exact; every sum is accumulated in float32 starting from the bias, in the kernel's
+ *             own k order.  That order, and the matrix unit's internal order within an instruction, are NOT part of the law: it
+ *             fixes the result only up to float32 accumulation error.
+ *   determinism  the same inputs give the same bits on the same device; the kernel uses no atomics.
+ *   the step  the env then steps on that float32 action exactly as in nig_rollout_mlp: clip, constraints, dynamics, reward,
+ *             bookkeeping, auto-reset, tally and generator streams are shared code.
+ * Non-finite observations are outside the law, as they are for the float32 loop.
+ *
+ * nig_set_mlp_policy_bf16: nig_set_mlp_policy's arguments (float32 host arrays); rounds them, builds the bf16 operand image and
+ * keeps it on the handle beside the float32 actor's: installing one does not disturb the other.
+ * nig_rollout_mlp_bf16: nig_rollout_mlp's arguments and checks, then the debug output hid_out (may be NULL): the lane's h1 and h2
+ * as bf16 words, unit u in natural index -- step k, layer L (0: h1, 1: h2), unit u at
+ * hid_out + k*hid_step_stride + (L*256 + u)*ld_hid + lane (ld_hid >= B, hid_step_stride >= 512*ld_hid, in uint16 elements;
+ * frozen lanes leave their words untouched).  Refusals, before anything is launched or written: limits installed
+ * (NIG_ERR_UNSUPPORTED, as every entry point without a _limited twin of its own), an env shape without the MFMA actor
+ * (NIG_ERR_UNSUPPORTED), no bf16 actor installed (NIG_ERR_INVALID).
+ * nig_bf16_from_f32: bf of n host floats (host only, no device needed): the builder's rounding.
+ */
+int nig_set_mlp_policy_bf16(nig_handle *h, int32_t hidden, const float *W1, const float *b1, const float *W2,
+                            const float *b2, const float *W3, const float *b3, void *stream);
+int nig_rollout_mlp_bf16(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out,
+                         int64_t out_stride, float *obs_out, int64_t obs_step_stride,
+                         float *act_out, int64_t ld_act, int64_t act_step_stride,
+                         uint16_t *hid_out, int64_t ld_hid, int64_t hid_step_stride, void *stream);
+int nig_bf16_from_f32(const float *x, uint16_t *out, int64_t n);
+
+/*
  * nig_rollout_policy / nig_rollout_mlp under the installed limits ("nig-limits-v1", nig_set_limits): every argument and
  * refusal as the twin's, plus xflags_out uint32 [n_steps][>= B] (row k at xflags_out + k * out_stride; may be NULL; a frozen
  * lane's word is 0).  NIG_ERR_INVALID without installed limits.  With limits that no state can violate (infinite bounds)

@@ -18,8 +18,8 @@ _lib.lib()   # fail loudly here if libnig.so is missing
 from .batched import BatchedIndustrialEnv, MixedBatchedEnv, StepInfo  # noqa: E402
 from .envs import (AdvancedChemicalReactorEnv, AdvancedPowerGridEnv, ChemicalReactorEnv, HVACControlEnv,  # noqa: E402
                    IndustrialEnv, PowerGridEnv, RobotAssemblyEnv, SteelAnnealingEnv, SupplyChainEnv, WaterTreatmentEnv)
-from .policies import (ConstraintProjectionPolicy, DevicePolicy, EnsemblePolicy, MLPPolicy, SafetyEnsemblePolicy, behaviour_policy, constant_agent, mpc_agent,  # noqa: E402
-                       pid_agent, random_agent)
+from .policies import (Bf16MLPPolicy, ConstraintProjectionPolicy, DevicePolicy, EnsemblePolicy, MLPPolicy, SafetyEnsemblePolicy, behaviour_policy, bf16_round,  # noqa: E402
+                       bf16_split, constant_agent, mlp_bf16_reference, mpc_agent, pid_agent, random_agent)
 from .utils import evaluate_with_safety, make, make_batched, uniform_action_statistics  # noqa: E402
 from .disturbance import Disturbance, Disturbed, evaluate_robustness, robustness_scores  # noqa: E402
 from .episodes import EpisodeLog, episodes_from_rows, evaluate_episodes  # noqa: E402
@@ -40,7 +40,7 @@ def tune(split_blocks=None, wide_min_blocks=None):
             "wide_min_blocks": int(L.nig_tune_get(_lib.TUNE_WIDE_MIN_BLOCKS))}
 
 
-__version__ = "0.8.0"        # 0.8.0: rollout_sampled, then EnsemblePolicy / rollout_mlp_ensemble, evaluate_robustness, EpisodeLog / evaluate_episodes, SafetyEnsemblePolicy / rollout_mlp_gated, ConstraintProjectionPolicy / rollout_mlp_projected (all additive; the number is pinned by tests/test_rollout_sampled_host.py); generator "nig-philox-v3" since round 4 (v2 + PowerGrid's reset load factors from spare low bytes; libnig: nig_version())
+__version__ = "0.8.0"        # 0.8.0: rollout_sampled, then EnsemblePolicy / rollout_mlp_ensemble, evaluate_robustness, EpisodeLog / evaluate_episodes, SafetyEnsemblePolicy / rollout_mlp_gated, ConstraintProjectionPolicy / rollout_mlp_projected, Bf16MLPPolicy / rollout_mlp_bf16 (all additive; the number is pinned by tests/test_rollout_sampled_host.py); generator "nig-philox-v3" since round 4 (v2 + PowerGrid's reset load factors from spare low bytes; libnig: nig_version())
 GENERATOR = "nig-philox-v3"
 __all__ = [
     "__version__", "BoxConstraint", "DatasetQuality", "SafetyConstraint", "SafetyMetrics", "IndustrialEnv",
@@ -48,5 +48,5 @@ __all__ = [
     "HVACControlEnv", "WaterTreatmentEnv", "SteelAnnealingEnv", "SupplyChainEnv", "BatchedIndustrialEnv", "MixedBatchedEnv", "StepInfo",
     "make", "make_batched", "evaluate_with_safety", "uniform_action_statistics", "tune", "DevicePolicy", "MLPPolicy", "EnsemblePolicy", "SafetyEnsemblePolicy", "ConstraintProjectionPolicy", "behaviour_policy", "constant_agent",
     "mpc_agent", "pid_agent", "random_agent", "Disturbance", "Disturbed", "evaluate_robustness", "robustness_scores",
-    "EpisodeLog", "episodes_from_rows", "evaluate_episodes",
+    "EpisodeLog", "episodes_from_rows", "evaluate_episodes", "Bf16MLPPolicy", "bf16_round", "bf16_split", "mlp_bf16_reference",
 ]

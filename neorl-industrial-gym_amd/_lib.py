@@ -139,6 +139,9 @@ PROTOTYPES = {
     "nig_rollout_policy": (ci, CLOSED_LOOP + [vp]),
     "nig_set_mlp_policy": (ci, [vp, i32, vp, vp, vp, vp, vp, vp, vp]),
     "nig_rollout_mlp": (ci, CLOSED_LOOP + [vp]),
+    "nig_set_mlp_policy_bf16": (ci, [vp, i32, vp, vp, vp, vp, vp, vp, vp]),
+    "nig_rollout_mlp_bf16": (ci, CLOSED_LOOP + [vp, i64, i64, vp]),
+    "nig_bf16_from_f32": (ci, [vp, vp, i64]),
     "nig_set_mlp_safety": (ci, [vp, i32, vp, vp, vp, vp, vp, vp, f32, vp]),
     "nig_rollout_mlp_safe": (ci, CLOSED_LOOP + [vp, vp]),
     "nig_rollout_mlp_search": (ci, CLOSED_LOOP[:2] + [i32] + CLOSED_LOOP[2:] + [vp, vp, vp, vp]),

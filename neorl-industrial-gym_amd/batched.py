@@ -544,6 +544,24 @@ class BatchedIndustrialEnv:
         (same outputs as rollout_policy)."""
         self._closed_loop(self._L.nig_rollout_mlp, n_steps, reward_out, flags_out, obs_out, act_out)
 
+    def set_mlp_policy_bf16(self, weights):
+        """Install the same actor for rollout_mlp_bf16(): set_mlp_policy()'s weights, rounded to bfloat16 by the library
+        ("nig-mlp-bf16-v1"; the biases stay float32).  Kept beside the float32 actor: neither install disturbs the other."""
+        W = _mlp_weights(weights, self._actor_shapes())
+        with torch.cuda.device(self._dev_index):
+            _lib.check(self._L.nig_set_mlp_policy_bf16(self._h, 256, *[w.ctypes.data_as(C.c_void_p) for w in W], self._stream()))
+
+    def rollout_mlp_bf16(self, n_steps: int, reward_out=None, flags_out=None, obs_out=None, act_out=None, hid_out=None):
+        """rollout_mlp() with the actor on the bf16 matrix unit, for throughput-only sweeps (its own arithmetic, "nig-mlp-bf16-v1":
+        outside rollout_mlp()'s parity bar).  hid_out (debug; int16 or uint16 [n_steps, 512, >=B]): the lane's h1 (rows 0-255)
+        and h2 (rows 256-511) as bf16 words."""
+        hp, ldh, sh = None, 0, 0
+        if hid_out is not None:
+            assert hid_out.dtype in (torch.int16, getattr(torch, "uint16", torch.int16)) and hid_out.dim() == 3 and hid_out.stride(2) == 1
+            assert hid_out.shape[0] >= n_steps and hid_out.shape[1] == 512 and hid_out.shape[2] >= self.batch
+            hp, ldh, sh = C.c_void_p(hid_out.data_ptr()), hid_out.stride(1), hid_out.stride(0)
+        self._closed_loop(self._L.nig_rollout_mlp_bf16, n_steps, reward_out, flags_out, obs_out, act_out, tail=(hp, ldh, sh))
+
     def set_mlp_safety(self, weights, threshold: float):
         """Install the reference agents' safety critic ((S+A)->256->256->1, ReLU, sigmoid) for rollout_mlp_safe():
         weights = [(C1 [S+A,256], c1), (C2 [256,256], c2), (C3 [256,1], c3)], host arrays, [in, out].  The action

@@ -177,6 +177,7 @@ struct nig_handle {
     bool has_policy = false;
     float *mlp_stream = nullptr;     // device copy of the MFMA operand stream of the MLP actor (owned)
     float *mlp_cstream = nullptr;    // device copy of the MFMA operand stream of the safety critic (owned)
+    float *mlp_bf16_stream = nullptr;   // device copy of the bf16 operand image of the MLP actor (owned; nig_set_mlp_policy_bf16), BF16_STREAM_BYTES bytes
     float mlp_threshold = 0.0f;      // shield threshold of nig_rollout_mlp_safe
     // nig_set_mlp_ensemble (owned): the members' operand streams back to back, MLP_STREAM_FLOATS floats each; their active weights
     // nig_set_mlp_safety_ensemble: the gate's member streams (owned), MLP_CSTREAM_FLOATS apart, and its law's parameters
@@ -693,6 +694,7 @@ int nig_destroy(nig_handle *h)
 {
     if (!h) return NIG_OK;
     if (h->mlp_stream) (void)hipFree(h->mlp_stream);
+    if (h->mlp_bf16_stream) (void)hipFree(h->mlp_bf16_stream);
     if (h->mlp_cstream) (void)hipFree(h->mlp_cstream);
     if (h->ens_stream) (void)hipFree(h->ens_stream);
     if (h->ens_w) (void)hipFree(h->ens_w);
@@ -1159,6 +1161,48 @@ int nig_rollout_mlp(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t 
     return closed_loop<MlpArgs>(h, "nig_rollout_mlp", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpArgs &q) {
         q.wstream = h->mlp_stream;
         return launch_of(h->env)->mlp;
+    });
+}
+
+// ---- the actor on the bf16 matrix unit ("nig-mlp-bf16-v1", include/nig.h) ----
+int nig_bf16_from_f32(const float *x, uint16_t *out, int64_t n)
+{
+    if (n < 0 || (n > 0 && (!x || !out))) return fail(NIG_ERR_INVALID, "nig_bf16_from_f32: bad argument");
+    for (int64_t i = 0; i < n; ++i) out[i] = bf16_from_f32(x[i]);
+    return NIG_OK;
+}
+
+int nig_set_mlp_policy_bf16(nig_handle *h, int32_t hidden, const float *W1, const float *b1, const float *W2, const float *b2,
+                            const float *W3, const float *b3, void *stream)
+{
+    const char *fn = "nig_set_mlp_policy_bf16";
+    if (!h || !W1 || !b1 || !W2 || !b2 || !W3 || !b3) return refuse(fn, "NULL argument");
+    if (hidden != MLP_H) return refuse(fn, "hidden must be 256 (agents/networks.py default)", NIG_ERR_UNSUPPORTED);
+    if (!launch_of(h->env)->mlp_bf16) return refuse(fn, "env shape not supported (even state dim, at most 16 actions)", NIG_ERR_UNSUPPORTED);
+    static_assert(BF16_STREAM_BYTES % sizeof(float) == 0);
+    float *host = (float *)calloc(BF16_STREAM_BYTES / sizeof(float), sizeof(float));
+    if (!host) return refuse(fn, "out of host memory");
+    if (!put_network_bf16(SPECS[h->env].state_dim, SPECS[h->env].action_dim, W1, b1, W2, b2, W3, b3, (unsigned char *)host, BF16_STREAM_BYTES)) {
+        free(host);
+        return refuse(fn, "the operand image does not fit its chunk plan");
+    }
+    return upload_stream(fn, &h->mlp_bf16_stream, host, BF16_STREAM_BYTES / sizeof(float), stream);
+}
+
+int nig_rollout_mlp_bf16(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                         float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
+                         uint16_t *hid_out, int64_t ld_hid, int64_t hid_step_stride, void *stream)
+{
+    const char *fn = "nig_rollout_mlp_bf16";
+    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    NIG_TRY(refuse_limited(h, fn));
+    if (!launch_of(h->env)->mlp_bf16) return refuse(fn, "env shape not supported (even state dim, at most 16 actions)", NIG_ERR_UNSUPPORTED);
+    if (!h->mlp_bf16_stream) return refuse(fn, "no bf16 actor installed (nig_set_mlp_policy_bf16)");
+    if (hid_out && (ld_hid < h->B || ld_hid > NIG_MAX_PITCH || hid_step_stride < 2 * (int64_t)MLP_H * ld_hid)) return refuse(fn, "bad hidden-activation pitch");
+    return closed_loop<MlpBf16Args>(h, fn, n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpBf16Args &q) {
+        q.m.wstream = h->mlp_bf16_stream;
+        q.hid_out = hid_out; q.ld_hid = (uint32_t)ld_hid; q.hid_step_stride = (uint64_t)hid_step_stride;
+        return launch_of(h->env)->mlp_bf16;
     });
 }
 

@@ -1,7 +1,7 @@
 // nig_launch.hpp -- the host side of libnig.so's kernels: the list of environments and the per-environment launch table.  An
 // env_<key>.hip instantiates the env's kernels by defining its table (NIG_DEFINE_ENV_LAUNCH); nig_api.hip reaches them through the
 // table's function pointers only.  The launchers of the kernel families with translation units of their own (sampled_, ensemble_,
-// disturbed_, search_, gated_, projected_, limited_, limited_<family>_<key>.hip) are DECLARED here and defined in nig_launch_families.hpp, which those units alone include.  Which
+// disturbed_, search_, gated_, projected_, bf16_, limited_, limited_<family>_<key>.hip) are DECLARED here and defined in nig_launch_families.hpp, which those units alone include.  Which
 // kernel form a rollout launch takes is decided in nig_launch_plan.hpp; the functions here run its plans.
 #pragma once
 #include "nig_kernels.hpp"
@@ -70,6 +70,8 @@ struct EnvLaunch {
     void (*mlp_ensemble_limited)(int ens, const MlpLimited<MlpEnsArgs> &, unsigned grid, hipStream_t);
     void (*mlp_disturbed_limited)(const MlpLimited<MlpDistArgs> &, unsigned grid, hipStream_t);
     void (*policy_disturbed_limited)(const PolicyDistLimArgs &, unsigned grid, hipStream_t);
+    // bf16_<key>.hip: nig_rollout_mlp_bf16; nullptr as `mlp`
+    void (*mlp_bf16)(const MlpBf16Args &, unsigned grid, hipStream_t);
 };
 
 template <class Env>
@@ -273,6 +275,7 @@ template <class Env> void launch_mlp_projected_limited_env(const MlpLimited<MlpP
 template <class Env> void launch_mlp_ensemble_limited_env(int ens, const MlpLimited<MlpEnsArgs> &q, unsigned grid, hipStream_t st);
 template <class Env> void launch_mlp_disturbed_limited_env(const MlpLimited<MlpDistArgs> &q, unsigned grid, hipStream_t st);
 template <class Env> void launch_policy_disturbed_limited_env(const PolicyDistLimArgs &q, unsigned grid, hipStream_t st);
+template <class Env> void launch_mlp_bf16_env(const MlpBf16Args &q, unsigned grid, hipStream_t st);
 
 template <class Env>
 static void launch_policy(const PolicyArgs &q, unsigned /*grid*/, hipStream_t st)
@@ -321,6 +324,7 @@ static const EnvLaunch *env_launch_table()
         t.mlp_search = mlp_slot<Env>(launch_mlp_search_env<Env>);
         t.mlp_gated = mlp_slot<Env>(launch_mlp_gated_env<Env>);
         t.mlp_projected = mlp_slot<Env>(launch_mlp_projected_env<Env>);
+        t.mlp_bf16 = mlp_slot<Env>(launch_mlp_bf16_env<Env>);
         if constexpr (!Env::CUSTOM_STEP) {
             t.step_limited = launch_step_limited_env<Env>;
             t.step64_limited = Env::HAS_ACT64 ? launch_step64_limited_env<Env> : nullptr;

@@ -1,8 +1,8 @@
 // nig_launch_families.hpp -- the definitions of the family launchers nig_launch.hpp declares: the kernels of nig_rollout_sampled,
 // nig_rollout_mlp_ensemble, nig_rollout_policy_disturbed / nig_rollout_mlp_disturbed, nig_rollout_mlp_search, nig_rollout_mlp_gated,
-// nig_rollout_mlp_projected and the _limited entry points (nig_step_limited, nig_step64_limited, nig_rollout_policy_limited,
+// nig_rollout_mlp_projected, nig_rollout_mlp_bf16 and the _limited entry points (nig_step_limited, nig_step64_limited, nig_rollout_policy_limited,
 // nig_rollout_mlp_limited) with the other families' _limited twins.
-// Included by the family translation units alone (sampled_, ensemble_, disturbed_, search_, gated_, projected_, limited_, limited_<family>_<key>.hip).  A template that is defined but not
+// Included by the family translation units alone (sampled_, ensemble_, disturbed_, search_, gated_, projected_, bf16_, limited_, limited_<family>_<key>.hip).  A template that is defined but not
 // instantiated emits nothing: each unit explicitly instantiates the launcher of its own family for its own env, and with it that
 // family's kernels and no other's.
 #pragma once
@@ -52,6 +52,13 @@ void launch_mlp_gated_env(const MlpGateArgs &q, unsigned grid, hipStream_t st) {
 
 template <class Env>
 void launch_mlp_projected_env(const MlpProjectArgs &q, unsigned grid, hipStream_t st) { launch_mlp<Env>(q, grid, st); }
+
+// nig_rollout_mlp_bf16: the actor on the bf16 matrix unit (nig_mlp_bf16.hpp)
+template <class Env>
+void launch_mlp_bf16_env(const MlpBf16Args &q, unsigned grid, hipStream_t st)
+{
+    if constexpr (has_mlp_actor<Env>) hipLaunchKernelGGL((rollout_mlp_bf16_kernel<Env>), dim3(grid), dim3(BLOCK), 0, st, q);
+}
 
 // nig_step_limited / nig_step64_limited: one plain kernel form each (injected or generated draws)
 template <class Env>
@@ -131,6 +138,8 @@ void launch_policy_disturbed_limited_env(const PolicyDistLimArgs &q, unsigned /*
     template void nig::launch_mlp_gated_env<nig::EnvType>(const nig::MlpGateArgs &, unsigned, hipStream_t);
 #define NIG_DEFINE_ENV_PROJECTED(EnvType) \
     template void nig::launch_mlp_projected_env<nig::EnvType>(const nig::MlpProjectArgs &, unsigned, hipStream_t);
+#define NIG_DEFINE_ENV_BF16(EnvType) \
+    template void nig::launch_mlp_bf16_env<nig::EnvType>(const nig::MlpBf16Args &, unsigned, hipStream_t);
 #define NIG_DEFINE_ENV_LIMITED(EnvType) \
     template void nig::launch_step_limited_env<nig::EnvType>(const nig::StepLimArgs &, bool, unsigned, hipStream_t); \
     template void nig::launch_step64_limited_env<nig::EnvType>(const nig::StepLimArgs &, bool, unsigned, hipStream_t); \

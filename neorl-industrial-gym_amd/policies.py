@@ -270,6 +270,88 @@ def pad_safety_member(weights, hidden: int = 256):
     return [(P1, p1), (P2, p2), (P3, c3.copy())]
 
 
+def bf16_round(x):
+    """bf(x) of "nig-mlp-bf16-v1" (include/nig.h): float32 -> bfloat16, round to nearest even, returned as float32 (the low 16
+    bits of every word are zero; `.view(np.uint32) >> 16` are the bf16 words).  A NaN stays a (quiet) NaN.  NumPy only."""
+    u = np.ascontiguousarray(np.asarray(x, dtype=f32)).view(np.uint32)
+    nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    r = (u.astype(np.uint64) + 0x7FFF + ((u >> np.uint32(16)) & np.uint32(1))).astype(np.uint32) & np.uint32(0xFFFF0000)
+    r = np.where(nan, (u & np.uint32(0xFFFF0000)) | np.uint32(0x00400000), r).astype(np.uint32)
+    return r.view(f32).reshape(np.shape(x))
+
+
+def bf16_split(x):
+    """The law's input split: (hi, lo) float32 with hi = bf(x), lo = bf(x - hi) (the subtraction is exact in float32), lo = 0
+    where hi is not finite."""
+    x = np.asarray(x, dtype=f32)
+    hi = bf16_round(x)
+    with np.errstate(invalid="ignore", over="ignore"):
+        lo = bf16_round((x - hi).astype(f32))
+    return hi, np.where(np.isfinite(hi), lo, f32(0)).astype(f32)
+
+
+def mlp_bf16_reference(weights, obs, h1=None, h2=None):
+    """ "nig-mlp-bf16-v1" with float64 sums, for obs [n, S] float32 and weights [(W1, b1), (W2, b2), (W3, b3)]: a dict of
+    z1, h1, z2, h2, z3 (pre-activations float64; h1, h2 float32 holding bf16 values), action = tanh(z3) (float64), and abs1, abs2,
+    abs3 = sum |term| including |bias| of every pre-activation (what an accumulation-error radius scales with).  h1 / h2 given:
+    the layers behind them are computed from these activations instead (a device's own intermediates)."""
+    f64 = np.float64
+    (W1, b1), (W2, b2), (W3, b3) = [(bf16_round(W).astype(f64), np.asarray(b, dtype=f32).astype(f64).reshape(-1)) for W, b in weights]
+    hi, lo = bf16_split(np.asarray(obs, dtype=f32).reshape(-1, W1.shape[0]))
+    x = np.concatenate([hi, lo], axis=1).astype(f64)
+    W1x = np.concatenate([W1, W1], axis=0)
+    out = {}
+
+    def layer(k, x, W, b):
+        out[f"z{k}"] = x @ W + b
+        out[f"abs{k}"] = np.abs(x) @ np.abs(W) + np.abs(b)
+        return out[f"z{k}"]
+
+    z1 = layer(1, x, W1x, b1)
+    out["h1"] = bf16_round(np.maximum(z1, 0).astype(f32)) if h1 is None else np.asarray(h1, dtype=f32)
+    z2 = layer(2, out["h1"].astype(f64), W2, b2)
+    out["h2"] = bf16_round(np.maximum(z2, 0).astype(f32)) if h2 is None else np.asarray(h2, dtype=f32)
+    z3 = layer(3, out["h2"].astype(f64), W3, b3)
+    out["action"] = np.tanh(z3)
+    return out
+
+
+class Bf16MLPPolicy:
+    """MLPPolicy.bf16(): the same actor under "nig-mlp-bf16-v1" (include/nig.h) -- weights and activations rounded to bfloat16,
+    the observation split into two bf16 parts, float32 sums -- for throughput-only sweeps: evaluate_with_safety and
+    evaluate_episodes play it with rollout_mlp_bf16 (the actor on the bf16 matrix unit) where the env has the MFMA actor and no
+    added constraints, and with this class's torch emulation of the law on the host loop elsewhere.  The emulation agrees with
+    the kernel up to accumulation order."""
+    is_trained = True
+    precision = "bf16"
+
+    def __init__(self, parent):
+        import torch
+        self.device, self.weights, self.fusable = parent.device, parent.weights, parent.fusable
+        self.state_dim, self.action_dim = parent.state_dim, parent.action_dim
+        bf = lambda W: W.to(torch.bfloat16).to(torch.float32)
+        self.layers = [(bf(W), b) for W, b in parent.layers]
+        self.layers[0] = (torch.cat([self.layers[0][0], self.layers[0][0]], dim=0).contiguous(), self.layers[0][1])
+
+    def predict_device(self, obs):
+        import torch
+        bf = lambda v: v.to(torch.bfloat16).to(torch.float32)
+        hi = bf(obs)
+        lo = torch.where(torch.isfinite(hi), bf(obs - hi), torch.zeros_like(hi))
+        x = torch.cat([hi, lo], dim=1)
+        for i, (W, b) in enumerate(self.layers):
+            x = torch.addmm(b, x, W)
+            x = bf(torch.relu(x)) if i + 1 < len(self.layers) else torch.tanh(x)
+        return x
+
+    def predict(self, observations, deterministic: bool = True):
+        import torch
+        o = torch.as_tensor(np.asarray(observations, dtype=f32), device=self.device)
+        single = o.dim() == 1
+        out = self.predict_device(o.reshape(-1, self.state_dim)).cpu().numpy()
+        return out[0] if single else out
+
+
 class MLPPolicy:
     """The deterministic actor of the reference's agents -- (S -> 256 -> 256 -> A) ReLU MLP with a
     tanh head (agents/networks.py:47-70,125-144; cql.py:339-343) -- kept on the GPU.
@@ -347,6 +429,10 @@ class MLPPolicy:
         single = o.dim() == 1
         out = self.predict_device(o.reshape(-1, self.state_dim)).cpu().numpy()
         return out[0] if single else out
+
+    def bf16(self):
+        """This actor under "nig-mlp-bf16-v1" (Bf16MLPPolicy): the bf16 matrix unit's kernel family, for throughput-only sweeps."""
+        return Bf16MLPPolicy(self)
 
     def exploring(self, sigma: float = 0.1):
         """The reference agents' predict(obs, deterministic=False), clip(actor + sigma N(0,1), -1, 1) (agents/cql.py:345-350),

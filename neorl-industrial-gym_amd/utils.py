@@ -139,7 +139,7 @@ def _disturbed_route(agent, env):
 def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
     """Where `agent` runs on `env`, and its installation there -- the routing _evaluate_batched and episodes.evaluate_episodes
     share.  Returns (agent, rollout, disturbed): `rollout` is the env method that plays n closed-loop steps with the agent in the
-    env kernel (rollout_policy, rollout_mlp, rollout_mlp_safe, rollout_mlp_search, rollout_mlp_gated, rollout_mlp_projected, rollout_mlp_ensemble or a _disturbed twin; policy, weights,
+    env kernel (rollout_policy, rollout_mlp, rollout_mlp_bf16, rollout_mlp_safe, rollout_mlp_search, rollout_mlp_gated, rollout_mlp_projected, rollout_mlp_ensemble or a _disturbed twin; policy, weights,
     shield, ensemble and disturbance are installed on the handle), or None -- the agent stays on the host and takes the
     per-step loop; `agent` may come back upgraded (a reference EnsembleAgent as an EnsemblePolicy); `disturbed` names the
     fused route of a disturbance.Disturbed ("fused-policy" / "fused-mlp": the caller removes the disturbance afterwards).
@@ -164,7 +164,12 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
     ensemble = plain and hasattr(agent, "install") and getattr(agent, "fusable", False) and env.state_dim % 2 == 0 and env.action_dim <= 16
     gated = ensemble and hasattr(agent, "max_uncertainty")        # SafetyEnsemblePolicy: its install() puts actor and members on the handle
     projecting = ensemble and hasattr(agent, "max_iters")         # ConstraintProjectionPolicy: install() puts actor and predictor on the handle
-    fused_mlp = not hasattr(agent, "install") and getattr(agent, "fusable", False) and plain and (mfma_env or not limited)
+    # Bf16MLPPolicy (MLPPolicy.bf16()): ahead of the fused_mlp test, which its `fusable` would send to the float32 kernel.  The bf16
+    # family has no _limited twin: with added constraints, as on an env without the MFMA actor, the agent takes the host loop
+    # through its predict_device.
+    bf16 = getattr(agent, "precision", None) == "bf16" and not hasattr(agent, "install")
+    fused_bf16 = bf16 and getattr(agent, "fusable", False) and plain and mfma_env and not limited
+    fused_mlp = not bf16 and not hasattr(agent, "install") and getattr(agent, "fusable", False) and plain and (mfma_env or not limited)
     shielded = fused_mlp and getattr(agent, "safety_weights", None) is not None and hasattr(agent, "threshold")
     searching = shielded and hasattr(agent, "n_candidates")       # MLPPolicy.searching(): get_safe_action instead of the halving
     disturbed = None           # a disturbance.Disturbed whose inner agent runs in the env kernel: "fused-policy" / "fused-mlp"
@@ -174,13 +179,16 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
             disturbed = route
             (env.set_policy if route == "fused-policy" else lambda a: env.set_mlp_policy(a.weights))(inner)
             env.set_disturbance(agent.disturbance)
-        device_policy = ensemble = gated = projecting = fused_mlp = shielded = searching = False
+        device_policy = ensemble = gated = projecting = fused_mlp = fused_bf16 = shielded = searching = False
     if disturbed:
         device_policy = True
     elif device_policy:
         env.set_policy(agent)
     elif ensemble:
         agent.install(env)
+        device_policy = True
+    elif fused_bf16:
+        env.set_mlp_policy_bf16(agent.weights)
         device_policy = True
     elif fused_mlp:
         env.set_mlp_policy(agent.weights)
@@ -192,6 +200,7 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
     if device_policy:
         name = ("rollout_policy_disturbed" if disturbed == "fused-policy" else "rollout_mlp_disturbed" if disturbed
                 else "rollout_mlp_gated" if gated else "rollout_mlp_projected" if projecting else "rollout_mlp_ensemble" if ensemble
+                else "rollout_mlp_bf16" if fused_bf16
                 else "rollout_mlp_search" if searching else "rollout_mlp_safe" if shielded else "rollout_mlp" if fused_mlp
                 else "rollout_policy")
         method = getattr(env, name + "_limited" if limited else name)
