@@ -1,12 +1,12 @@
 """The closed-loop test matrix, stated once: which envs every closed-loop kernel family is compiled for, what kernel shape
 each env brings, distinct start states for the two envs whose reset gives every lane the same state, and the network in NumPy
 float64.  A plain helper module (no fixtures, no collection hooks): the family modules (test_gpu_ensemble.py,
-test_gpu_safe_action_search.py, test_gpu_safety_gate.py, test_gpu_disturbance.py, test_gpu_safety_shield.py and the MFMA-actor
-test of test_gpu_parity.py) take their env lists from here, and test_closed_loop_matrix.py holds the lists to the library's
-own registry and to what each entry point accepts.
+test_gpu_safe_action_search.py, test_gpu_safety_gate.py, test_gpu_disturbance.py, test_gpu_safety_shield.py, test_gpu_projection.py,
+test_gpu_mlp_bf16.py and the MFMA-actor test of test_gpu_parity.py) take their env lists from here, and test_closed_loop_matrix.py
+holds the lists to the library's own registry and to what each entry point accepts.
 
-The MFMA families (rollout_mlp, _safe, _ensemble, _disturbed, _search, _gated) exist for the envs with an even state dim and at
-most 16 actions; rollout_policy_disturbed exists for all nine."""
+The MFMA families (rollout_mlp, _safe, _ensemble, _disturbed, _search, _gated, _projected and the bf16 actor's rollout_mlp_bf16) exist
+for the envs with an even state dim and at most 16 actions; rollout_policy_disturbed exists for all nine."""
 import numpy as np
 
 # (key, env id): head instruction and rows in use; critic layer-1 input width S + A, its chunks of four 4-wide k-tiles, parity

@@ -29,6 +29,8 @@ KINDS = {
     "i32": (torch.int32, torch.int32, 0x5A5A5A5B),                   # fixed odd patterns
     "i64": (torch.int64, torch.int64, 0x5A5A5A5B5A5A5A5B),
     "u8": (torch.uint8, torch.uint8, 0xA5),
+    # bf16 words of a ReLU output (hid_out of nig_rollout_mlp_bf16): 0xFA5B has its sign bit set and h >= +0, so no stored word is it
+    "bf16": (torch.int16, torch.int16, 0xFA5B - 0x10000),
 }
 
 

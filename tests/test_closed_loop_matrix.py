@@ -1,6 +1,8 @@
 """The guard of tests/closed_loop_matrix.py: the env lists are the library's own registry filtered by the documented condition
 (not gpu), every anchor test of every family module is parametrised over the whole list at both matrix shapes (not gpu), and
-each closed-loop entry point runs on exactly the envs of its list and refuses the others on the host (gpu)."""
+each closed-loop entry point runs on exactly the envs of its list and refuses the others on the host (gpu).  The families with a
+module of their own are held here too: the bf16 MFMA actor (rollout_mlp_bf16, tests/test_gpu_mlp_bf16.py) and the fused
+constraint projection (rollout_mlp_projected, tests/test_gpu_projection.py)."""
 import importlib
 import re
 
@@ -10,7 +12,7 @@ import pytest
 import closed_loop_matrix as M
 
 ENTRIES = ("rollout_mlp", "rollout_mlp_safe", "rollout_mlp_ensemble", "rollout_mlp_disturbed", "rollout_mlp_search",
-           "rollout_mlp_gated", "rollout_policy_disturbed")
+           "rollout_mlp_gated", "rollout_policy_disturbed", "rollout_mlp_bf16", "rollout_mlp_projected")
 UNSUPPORTED = 4            # NIG_ERR_UNSUPPORTED
 
 
@@ -52,6 +54,11 @@ ANCHORS = [
     ("test_gpu_disturbance", "test_the_draws_matrix", POLICY),
     ("test_gpu_disturbance", "test_the_action_matrix", POLICY),
     ("test_gpu_disturbance", "test_the_plant_received_it_matrix", POLICY),
+    ("test_gpu_mlp_bf16", "test_layout_bit_for_bit_on_integer_data", MFMA),
+    ("test_gpu_mlp_bf16", "test_each_layer_from_the_devices_own_previous_layer", MFMA),
+    ("test_gpu_mlp_bf16", "test_the_step_took_that_action", MFMA),
+    ("test_gpu_mlp_bf16", "test_frozen_lanes_store_nothing_and_live_lanes_follow_the_law", MFMA),
+    ("test_gpu_projection", "test_the_law_bit_for_bit", MFMA),
 ]
 
 
@@ -122,7 +129,7 @@ def test_each_entry_point_runs_on_exactly_its_envs(key, name, entry):
     import neorl_industrial_gym_amd as ni
     assert torch.cuda.is_available(), "GPU tests need a HIP device"
     supported = entry == "rollout_policy_disturbed" or key in {k for k, _ in M.MFMA_ENVS}
-    B, FILL, FLAGFILL = M.B_SMALL, -7.0, 0x5A5A5A5B
+    B, FILL, FLAGFILL, HIDFILL = M.B_SMALL, -7.0, 0x5A5A5A5B, 0x7A7B
     env = ni.make_batched(name, B, seed=0x5EED, max_episode_steps=M.MAXS_NEW)
     S, A, ld, dev = env.state_dim, env.action_dim, env.ld, env.device
     env.reset()
@@ -130,8 +137,12 @@ def test_each_entry_point_runs_on_exactly_its_envs(key, name, entry):
     installs = []
     if entry == "rollout_policy_disturbed":
         installs.append(lambda: env.set_policy(ni.mpc_agent(S, A)))
+    elif entry == "rollout_mlp_bf16":
+        installs.append(lambda: env.set_mlp_policy_bf16(ws))
     else:
         installs.append(lambda: env.set_mlp_policy(ws))
+    if entry == "rollout_mlp_projected":
+        installs.append(lambda: env.set_mlp_constraint(M.random_critic(S, A, 10, n_out=3), 0.5, 0.01))
     if entry in ("rollout_mlp_safe", "rollout_mlp_search"):
         installs.append(lambda: env.set_mlp_safety(M.random_critic(S, A, 6), 0.5))
     if entry == "rollout_mlp_ensemble":
@@ -146,6 +157,7 @@ def test_each_entry_point_runs_on_exactly_its_envs(key, name, entry):
     act = torch.full((1, A, ld), FILL, dtype=torch.float32, device=dev)
     rows = {n: torch.full((1, ld), FILL, dtype=torch.float32, device=dev) for n in ("pr", "rk", "un")}
     ch = torch.full((1, ld), FLAGFILL, dtype=torch.int32, device=dev)
+    hid = torch.full((1, 512, ld), HIDFILL, dtype=torch.int16, device=dev)
     t0 = env.counter
     launch = {"rollout_mlp": lambda: env.rollout_mlp(1, rw, fl, None, act),
               "rollout_mlp_safe": lambda: env.rollout_mlp_safe(1, rw, fl, None, act, rows["pr"]),
@@ -153,7 +165,9 @@ def test_each_entry_point_runs_on_exactly_its_envs(key, name, entry):
               "rollout_mlp_disturbed": lambda: env.rollout_mlp_disturbed(1, rw, fl, None, act, None),
               "rollout_mlp_search": lambda: env.rollout_mlp_search(1, 3, rw, fl, None, act, rows["pr"], rows["rk"], ch),
               "rollout_mlp_gated": lambda: env.rollout_mlp_gated(1, rw, fl, None, act),
-              "rollout_policy_disturbed": lambda: env.rollout_policy_disturbed(1, rw, fl, None, act, None)}[entry]
+              "rollout_policy_disturbed": lambda: env.rollout_policy_disturbed(1, rw, fl, None, act, None),
+              "rollout_mlp_bf16": lambda: env.rollout_mlp_bf16(1, rw, fl, None, act, hid),
+              "rollout_mlp_projected": lambda: env.rollout_mlp_projected(1, 3, 0.1, rw, fl, None, act, None, None, ch, None)}[entry]
     rc = _code(launch)
     torch.cuda.synchronize()
     used = {"rollout_mlp_safe": ("pr",), "rollout_mlp_search": ("pr", "rk"), "rollout_mlp_ensemble": ("un",)}.get(entry, ())
@@ -165,8 +179,10 @@ def test_each_entry_point_runs_on_exactly_its_envs(key, name, entry):
         assert bool(torch.isfinite(a).all()) and bool((a != FILL).all())
         for n in used:
             assert bool((rows[n][0, :B] != FILL).all()), n
-        if entry == "rollout_mlp_search":
+        if entry in ("rollout_mlp_search", "rollout_mlp_projected"):
             assert bool((ch[0, :B] != FLAGFILL).all())
+        if entry == "rollout_mlp_bf16":
+            assert bool((hid[0, :, :B] != HIDFILL).all()) and bool((hid[0, :, B:] == HIDFILL).all())
         # pad columns keep their words
         assert bool((fl[0, B:] == FLAGFILL).all()) and bool((rw[0, B:] == FILL).all()) and bool((act[0, :, B:] == FILL).all())
     else:
@@ -177,6 +193,10 @@ def test_each_entry_point_runs_on_exactly_its_envs(key, name, entry):
         assert env.counter == t0
         assert bool((fl == FLAGFILL).all()) and bool((rw == FILL).all()) and bool((act == FILL).all()) and bool((ch == FLAGFILL).all())
         assert all(bool((r == FILL).all()) for r in rows.values())
+    if entry != "rollout_mlp_bf16" or not supported:
+        assert bool((hid == HIDFILL).all()), "hid_out"
+    if entry not in ("rollout_mlp_search", "rollout_mlp_projected") or not supported:
+        assert bool((ch == FLAGFILL).all()), "choice / iters row"
     for n in rows:
         if n not in used or not supported:
             assert bool((rows[n] == FILL).all()), n

@@ -156,3 +156,69 @@ def test_explicit_masks_and_partly_written_buffers():
     w.tensors["u8"][w["workspace"].off - 1] = 0
     assert _strs(w.check({"workspace": dict(n_outer=1, complete=False)})) == \
         [f"workspace: 1 word(s), red zone before the buffer (first at element {w['workspace'].off - 1})"]
+
+
+def _hid_arena(H=6, ldh=B + 3, gap=5):
+    """hid_out's shape in small: T steps of H unit rows at pitch ldh with a gap behind each step, 16-bit words, element-aligned;
+    a second 16-bit buffer behind it, so that the red zone between two buffers of the kind is looked at too."""
+    a = Arena("cpu")
+    a.add("hid_out", "bf16", Layout(T, H * ldh + gap, H, ldh, B))
+    a.add("hid_next", "bf16", Layout(1, 8, 1, 8, 8), extra_outer=0)
+    a.build()
+    return a
+
+
+def test_the_16_bit_kind_shows_every_finding_class():
+    """pad column, stride gap, row beyond n_steps, frozen lane, red zone, unwritten -- each applied by hand to a buffer of 16-bit
+    words and named by the checker, one word at a time."""
+    H, ldh, gap = 6, B + 3, 5
+    step = H * ldh + gap
+    torch_dtype, int_dtype, canary = KINDS["bf16"]
+    assert torch_dtype == int_dtype == torch.int16 and canary < 0, "16-bit words; sign bit set: no bf16 word of a ReLU output"
+    assert (canary & 0xFFFF) == 0xFA5B
+    live = torch.ones(T, B, dtype=torch.bool)
+    live[1:, 7] = False                                          # lane 7 frozen from step 1 on
+    live[:, B - 1] = False                                       # the last lane held from the start
+
+    def correct():
+        a = _hid_arena(H, ldh, gap)
+        a["hid_out"].rows().fill_(0x3F80)                        # bf16 1.0
+        a["hid_out"].rows()[1:, :, 7] = canary
+        a["hid_out"].rows()[:, :, B - 1] = canary
+        a["hid_next"].rows().fill_(0)                            # bf16 +0: a written word that is not the canary
+        return a
+
+    def written(steps=T, lv=live):
+        return {"hid_out": dict(n_outer=steps, live=None if lv is None else lv[:steps]), "hid_next": dict(n_outer=1)}
+
+    a = correct()
+    assert a["hid_out"].ptr % 256 == 2 and a["hid_out"].ints.element_size() == 2       # element-aligned only
+    t = a.tensors["bf16"]
+    assert (a["hid_next"].off - a["hid_out"].off - a["hid_out"].size) * 2 >= REDZONE_BYTES and a["hid_out"].off * 2 >= REDZONE_BYTES
+    assert a.check(written()) == []
+    cases = [("pad column", 2 * step + 3 * ldh + B),             # step 2, unit row 3, the first pad column
+             ("stride gap", 1 * step + H * ldh),                 # behind step 1's last unit row
+             ("row beyond n_steps", T * step + 4),               # the step behind the last (memory the buffer owns)
+             ("frozen lane", 2 * step + 5 * ldh + 7),            # lane 7 in step 2
+             ("frozen lane", 0 * step + 0 * ldh + B - 1)]        # the held lane in step 0
+    for region, elem in cases:
+        a = correct()
+        a["hid_out"].ints[elem] = 0x4000
+        assert _strs(a.check(written())) == [f"hid_out: 1 word(s), {region} (first at element {elem})"], region
+    for side, off in (("before", -1), ("after", a["hid_out"].size)):
+        a = correct()
+        p = a["hid_out"].off + off
+        a.tensors["bf16"][p] = 0
+        assert _strs(a.check(written())) == [f"hid_out: 1 word(s), red zone {side} the buffer (first at element {p})"]
+    a = correct()
+    a["hid_out"].rows()[3, 2, 11] = canary                       # a live lane's word silently not written
+    assert _strs(a.check(written())) == [f"hid_out: 1 word(s), unwritten (first at element {3 * step + 2 * ldh + 11})"]
+    a = correct()
+    f = a.check(written(steps=T - 1))                            # asked for T - 1 steps, wrote T
+    assert {(x.buffer, x.region) for x in f} == {("hid_out", "row beyond n_steps")}
+    a = correct()
+    assert {(x.buffer, x.region) for x in a.check(written(lv=None))} == {("hid_out", "unwritten")}   # without the live mask
+    a = correct()
+    a["hid_out"].ints[0] = 0
+    f = a.check({"hid_out": None, "hid_next": dict(n_outer=1)})  # a NULL hid_out's arena: everything is stray
+    assert {(x.buffer, x.region) for x in f} == {("hid_out", "row beyond n_steps")}

@@ -42,6 +42,8 @@ def _play(ni, env, source, n, rew, fl):
         env.rollout_sampled(n, rew, fl)
     elif source == "mlp":
         env.rollout_mlp(n, rew, fl)
+    elif source == "mlp_bf16":
+        env.rollout_mlp_bf16(n, rew, fl)
     else:
         env.rollout_policy(n, rew, fl)
 
@@ -54,6 +56,8 @@ def _make(ni, key, B, source, autoreset, tally=False, seed=0xE915):
         env.set_policy(ni.pid_agent(env.state_dim, env.action_dim))
     elif source == "mlp":
         env.set_mlp_policy(_actor(env.state_dim, env.action_dim, 11))
+    elif source == "mlp_bf16":
+        env.set_mlp_policy_bf16(_actor(env.state_dim, env.action_dim, 11))
     env.reset()
     return env
 
@@ -86,7 +90,7 @@ CASES = [
     # (env, source of the rows, auto-reset, batch, extra log pitch)
     ("cr", "ring", True, 100, 0), ("cr", "ring", False, 100, 37), ("pg", "sampled", True, 257, 0), ("ra", "sampled", True, 100, 37),
     ("ra", "mpc", True, 257, 37), ("pg", "mpc", False, 100, 0), ("cr", "pid", True, 100, 0), ("cr", "mlp", True, 257, 0),
-    ("cr", "mlp", False, 100, 37), ("hvac", "mpc", True, 100, 37),
+    ("cr", "mlp", False, 100, 37), ("hvac", "mpc", True, 100, 37), ("cr", "mlp_bf16", True, 257, 0), ("pg", "mlp_bf16", False, 100, 37),
 ]
 
 
@@ -293,14 +297,32 @@ KEYS13 = ["return_mean", "return_std", "return_min", "return_max", "length_mean"
           "successful_episodes", "success_rate"]
 
 
-@pytest.mark.parametrize("key,agent", [("cr", "mpc"), ("hvac", "mpc"), ("cr", "host"), ("pg", "mpc")])
+def _counted(env, calls, name):
+    inner = getattr(env, name)
+
+    def call(*a, **k):
+        calls[name] += 1
+        return inner(*a, **k)
+
+    setattr(env, name, call)
+
+
+@pytest.mark.parametrize("key,agent", [("cr", "mpc"), ("hvac", "mpc"), ("cr", "host"), ("pg", "mpc"), ("cr", "bf16"), ("pg", "bf16")])
 def test_evaluate_episodes_rounds_mode_equals_evaluate_with_safety(ni, key, agent):
     B, n = 100, 250                                                   # three rounds, the last one half full
     out = []
     for fn in (ni.evaluate_with_safety, lambda a, e, n_episodes: ni.evaluate_episodes(a, e, n_episodes, chunk=5)):
         env = ni.make_batched(NAME[key], B, seed=0xE915, autoreset=False, tally=True, max_episode_steps=MAX_STEPS)
-        ag = ni.mpc_agent(env.state_dim, env.action_dim) if agent == "mpc" else HostAgent(env.action_dim)
+        calls = {"rollout_mlp_bf16": 0, "rollout_mlp": 0}
+        if agent == "bf16":                                               # the bf16 actor: both evaluations reach its own kernel
+            ag = ni.MLPPolicy(_actor(env.state_dim, env.action_dim, 11)).bf16()
+            _counted(env, calls, "rollout_mlp_bf16")
+            _counted(env, calls, "rollout_mlp")
+        else:
+            ag = ni.mpc_agent(env.state_dim, env.action_dim) if agent == "mpc" else HostAgent(env.action_dim)
         out.append(fn(ag, env, n_episodes=n))
+        if agent == "bf16":
+            assert calls["rollout_mlp_bf16"] >= 1 and calls["rollout_mlp"] == 0, calls
         env.close()
     ref, got = out
     assert got["mode"] == "rounds" and got["n_episodes"] == n and got["returns"].shape == (n,)

@@ -524,21 +524,25 @@ def _critic(S, A, seed):
 
 def run_closed_loop(ni, key, B, mode, subset, entry="policy", which="affine", chunks=(6, 4), autoreset=True, max_steps=7,
                     hold=None, overwrite=False, threshold=0.5):
-    """nig_rollout_policy / _mlp / _mlp_safe: `subset` of "o" (obs_out), "a" (act_out), "r" (reward_out), "f" (flags_out),
-    "p" (prob_out).  Frozen lanes (no auto-reset; `hold` = done before the first launch) leave their obs / act / prob rows
-    untouched and get NIG_FLAG_INACTIVE | step and reward 0.0f.  Returns (observables, findings, rig's policy)."""
+    """nig_rollout_policy / _mlp / _mlp_safe / _mlp_bf16: `subset` of "o" (obs_out), "a" (act_out), "r" (reward_out), "f" (flags_out),
+    "p" (prob_out), "h" (hid_out: 512 rows of 16-bit words per step at a pitch of its own).  Frozen lanes (no auto-reset; `hold` =
+    done before the first launch) leave their obs / act / prob / hid rows untouched and get NIG_FLAG_INACTIVE | step and reward
+    0.0f.  Returns (observables, findings, rig's policy)."""
     r = Rig(ni, key, B, autoreset=autoreset, max_steps=max_steps)
     S, A, ld, L, FL = r.S, r.A, r.ld, r.L, ni._lib
     pol = None
     if entry == "policy":
         pol = _policy(ni, key, which, S, A)
         r.env.set_policy(pol)
+    elif entry == "mlp_bf16":
+        r.env.set_mlp_policy_bf16(_actor(S, A, 11))
     else:
         r.env.set_mlp_policy(_actor(S, A, 11))
         if entry == "mlp_safe":
             r.env.set_mlp_safety(_critic(S, A, 12), threshold)
     a = Arena("cuda")
-    os_, lda = pitch(mode, B, ld, 1), pitch(mode, B, ld, 2)
+    os_, lda, ldh = pitch(mode, B, ld, 1), pitch(mode, B, ld, 2), pitch(mode, B, ld, 3)
+    assert set(subset) <= set("oarfph") and ("h" not in subset or entry == "mlp_bf16") and ("p" not in subset or entry == "mlp_safe")
     bufs = []
     for c, T in enumerate(chunks):
         n = 1 if overwrite else T
@@ -547,14 +551,15 @@ def run_closed_loop(ni, key, B, mode, subset, entry="policy", which="affine", ch
         pr = a.add(f"prob_out{c}", "f32", Layout(n, os_, 1, os_, B)) if "p" in subset else None
         obs = a.add(f"obs_out{c}", "f32", Layout(T, ceil4(B * S) + gap(mode, 1, mult4=True), 1, B * S, B * S, lane_width=S), align=16) if "o" in subset else None
         act = a.add(f"act_out{c}", "f32", Layout(T, A * lda + gap(mode, 2), A, lda, B)) if "a" in subset else None
-        bufs.append((T, n, rew, fl, pr, obs, act))
+        hid = a.add(f"hid_out{c}", "bf16", Layout(T, 512 * ldh + gap(mode, 3), 512, ldh, B)) if "h" in subset else None
+        bufs.append((T, n, rew, fl, pr, obs, act, hid))
     a.build()
     r.reset()
     if hold is not None:
         r.hold(hold)
     obsv, written = {}, {}
     p = lambda b: None if b is None else C.c_void_p(b.ptr)
-    for c, (T, n, rew, fl, pr, obs, act) in enumerate(bufs):
+    for c, (T, n, rew, fl, pr, obs, act, hid) in enumerate(bufs):
         # who is live in step k of this launch: not done on entry of the step (a handle without auto-reset never revives a lane)
         args = [r.h, T, p(rew), p(fl), 0 if overwrite else os_, p(obs), obs.layout.outer_stride if obs else 0, p(act), lda if act else 0,
                 act.layout.outer_stride if act else 0]
@@ -563,6 +568,8 @@ def run_closed_loop(ni, key, B, mode, subset, entry="policy", which="affine", ch
             rc = L.nig_rollout_policy(*args, r.st())
         elif entry == "mlp":
             rc = L.nig_rollout_mlp(*args, r.st())
+        elif entry == "mlp_bf16":
+            rc = L.nig_rollout_mlp_bf16(*args, p(hid), ldh if hid else 0, hid.layout.outer_stride if hid else 0, r.st())
         else:
             rc = L.nig_rollout_mlp_safe(*args, p(pr), r.st())
         assert rc == 0, L.nig_last_error()
@@ -577,9 +584,9 @@ def run_closed_loop(ni, key, B, mode, subset, entry="policy", which="affine", ch
             assert torch.equal(live[0], ~done0) and torch.equal(live[1:], live[:-1] & ~ended[:-1])
             if rew is not None:
                 assert bool((rew.rows(T)[:, 0][~live] == 0).all())
-        for b in (rew, fl, pr, obs, act):
+        for b in (rew, fl, pr, obs, act, hid):
             if b is not None:
-                per_lane = b in (obs, act, pr)
+                per_lane = b in (obs, act, pr, hid)
                 written[b.name] = dict(n_outer=n if b in (rew, fl, pr) else T, live=live if per_lane and live is not None else None)
                 obsv[b.name] = b.rows(written[b.name]["n_outer"]).cpu()
         if live is not None:
@@ -721,6 +728,32 @@ def test_mlp_rollout_awkward_pitches_against_the_oracle(ni, knobs, oracle, key):
     clean(f, key + " safe, overwrite")
     for k in ("reward_out0", "flags_out0", "prob_out0", "reward_out1", "flags_out1", "prob_out1"):
         assert torch.equal(last[k][0], s[k][-1]), k
+
+
+BF16_CASES = [("oarfh", True), ("h", True), ("a", True), ("rf", True), ("", True), ("oarfh", False), ("fh", False)]
+
+
+@pytest.mark.parametrize("subset,autoreset", BF16_CASES, ids=[f"{s or 'none'}-{'autoreset' if a else 'frozen'}" for s, a in BF16_CASES])
+@pytest.mark.parametrize("B", [1, 33, 129, 700])
+@pytest.mark.parametrize("key", ["cr", "hvac", "supply"])
+def test_mlp_bf16_footprint_and_pitch_invariance(ni, knobs, key, B, autoreset, subset):
+    """The MFMA actor on the bf16 matrix unit (a kernel body of its own; 32 lanes per wave on both lane halves, 128 per block):
+    ChemicalReactor (S 12: the 16-byte observation store, 3 head rows), HVACControl (S 18: scalar observation stores) and
+    SupplyChain (S 28, A 10: head rows 8 and 9 from the second register group); hid_out at a pitch of its own, from both lane
+    halves; every output alone, none at all, and frozen lanes told from the flag rows.  Pitch == B at one lane and at one lane
+    past a block."""
+    ref = None
+    for mode in MODES if B in (1, 129) else ("dense", "odd", "wide"):
+        o, f, _ = run_closed_loop(ni, key, B, mode, subset, entry="mlp_bf16", autoreset=autoreset, max_steps=4 if not autoreset else 7)
+        clean(f, f"{key} {B} mlp_bf16 {subset} {mode}")
+        ref = ref or o
+        same(ref, o, f"{key} {B} mlp_bf16 {subset} dense vs {mode}")
+    assert int(ref["tally"][ni._lib.T_EPISODES].view(torch.float64).sum()) > 0
+    if subset == "":                                        # the outputs do not change the trajectory
+        full, f, _ = run_closed_loop(ni, key, B, "dense", "oarfh", entry="mlp_bf16", autoreset=autoreset, max_steps=7)
+        clean(f, f"{key} {B} mlp_bf16 oarfh dense")
+        for k in ("state", "ctr", "tally", "life_viol", "ep_return", "reduce_tally", "counter"):
+            assert torch.equal(ref[k], full[k]), (key, B, k)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -91,6 +91,14 @@ def test_the_reference_is_integer_arithmetic_on_the_integer_case(key, name):
         assert ties >= 1 and lo >= 1
         assert _words(ref["h1"][0, :1])[0] == 0x3F80 and _words(ref["h1"][1, :1])[0] == 0x3F82, "the crafted ties, down and up"
         assert int((ref["h2"] > 0).sum()) >= B and np.max(np.abs(ref["z3"])) < 64
+        # the head bias of both sets: nonzero somewhere in every pair of rows, pairwise distinct, integers in [-8, 8] of W3's
+        # quantum; and z3 stays of order 1, so that a bias row moved to another row shows in the action (tanh is not saturated)
+        for (wsx, q3), z3x in (((K.set_a(key, S, A, B)[0], 2.0 ** -10), z3), ((ws, 2.0 ** -4), ref["z3"])):
+            b3 = wsx[2][1].astype(np.float64) / q3
+            assert len(set(b3.tolist())) == A and np.array_equal(b3, np.round(b3)) and np.max(np.abs(b3)) <= 8 and np.count_nonzero(b3) >= A - 1
+            assert np.median(np.abs(z3x)) < 4
+            if B == M.B_BIG:
+                assert np.all((np.abs(z3x) < 4).mean(axis=0) > 0.5), "every head row is unsaturated on most lanes"
     # h1 / h2 given: the layers behind them start from the given activations
     ref2 = mlp_bf16_reference(ws, st, h1=np.zeros_like(ref["h1"]))
     assert np.array_equal(ref2["z1"], ref["z1"]) and np.array_equal(ref2["z2"], np.broadcast_to(ws[1][1].astype(np.float64), ref["z2"].shape))
