@@ -107,6 +107,25 @@ def test_every_anchor_test_covers_its_whole_list(module, test, which):
         assert have == want, (module, test, B, "missing", sorted(want - have), "unknown", sorted(have - want))
 
 
+def test_the_lifecycle_module_covers_every_entry_points_list():
+    """tests/test_gpu_handle_lifecycle.py::test_held_lanes_on_an_autoreset_handle anchors every family at once: it is parametrised
+    over (case, key) cells, not over `key` alone, so it is held here and not in ANCHORS.  For every entry point of ENTRIES the
+    cells of the cases that launch it name exactly the envs of its list, at B = 700 and at B = 5.  (The whole table against the
+    exported symbols: tests/test_handle_lifecycle_host.py.)"""
+    import handle_lifecycle as H
+    fn = importlib.import_module("test_gpu_handle_lifecycle").test_held_lanes_on_an_autoreset_handle
+    marks = {m.args[0]: list(m.args[1]) for m in fn.pytestmark if m.name == "parametrize"}
+    assert set(marks["B"]) == {M.B_BIG, M.B_SMALL}
+    cells = [tuple(c) for c in marks["case,key"]]
+    for entry in ENTRIES:
+        cases = [c for c, v in H.CASES.items() if v[0] == "nig_" + entry]
+        assert cases, entry
+        want = {k for k, _ in (M.POLICY_ENVS_ALL if entry == "rollout_policy_disturbed" else M.MFMA_ENVS)}
+        for case in cases:
+            have = [k for c, k in cells if c == case]
+            assert len(have) == len(set(have)) and set(have) == want, (entry, case, sorted(set(have) ^ want))
+
+
 # ---- gpu: every entry point on every env ------------------------------------------------------------------------------------
 def _code(call):
     """0, or the status code of the NigError the call raised."""
