@@ -122,8 +122,6 @@ PROTOTYPES = {
     "nig_get_limit_count": (ci, [vp]),
     "nig_step_limited": (ci, [vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp]),
     "nig_step64_limited": (ci, [vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp]),
-    "nig_rollout_policy_limited": (ci, CLOSED_LOOP + [vp, vp]),
-    "nig_rollout_mlp_limited": (ci, CLOSED_LOOP + [vp, vp]),
     "nig_reset": (ci, [vp, vp, vp, i64, vp]),
     "nig_step": (ci, [vp, vp, i64, vp, vp, i64, vp, vp, vp, vp, i64, vp]),
     "nig_fill_actions": (ci, [vp, u32, vp, i64, vp]),
@@ -154,14 +152,6 @@ PROTOTYPES = {
     "nig_set_disturbance": (ci, [vp, P(DisturbanceStruct), vp]),
     "nig_rollout_policy_disturbed": (ci, CLOSED_LOOP + [vp, i64, vp]),
     "nig_rollout_mlp_disturbed": (ci, CLOSED_LOOP + [vp, i64, vp]),
-    # the other closed-loop families under the added constraints: the parent's arguments, xflags_out, the stream
-    "nig_rollout_mlp_safe_limited": (ci, CLOSED_LOOP + [vp, vp, vp]),
-    "nig_rollout_mlp_search_limited": (ci, CLOSED_LOOP[:2] + [i32] + CLOSED_LOOP[2:] + [vp, vp, vp, vp, vp]),
-    "nig_rollout_mlp_gated_limited": (ci, CLOSED_LOOP + [vp, vp, vp, i64, i64, vp, vp]),
-    "nig_rollout_mlp_projected_limited": (ci, CLOSED_LOOP[:2] + [i32, f32] + CLOSED_LOOP[2:] + [vp, vp, vp, vp, i64, i64, vp, vp]),
-    "nig_rollout_mlp_ensemble_limited": (ci, CLOSED_LOOP + [vp, vp, vp, vp]),
-    "nig_rollout_policy_disturbed_limited": (ci, CLOSED_LOOP + [vp, i64, vp, vp]),
-    "nig_rollout_mlp_disturbed_limited": (ci, CLOSED_LOOP + [vp, i64, vp, vp]),
     "nig_reset_host": (ci, [vp, vp, vp, vp]),
     "nig_step_host": (ci, [vp, vp, vp, vp, vp, vp, vp]),
     "nig_step_host64": (ci, [vp, vp, vp, vp, vp, vp, vp]),
@@ -187,6 +177,11 @@ PROTOTYPES = {
     "nig_collect_episodes": (ci, [vp, i32, vp, vp, i64, vp, i64, i64, vp]),
     "nig_reduce_episodes": (ci, [vp, vp, i64, i64, i64, vp, vp]),
 }
+# a closed loop's twin under the added constraints: the parent's arguments, xflags_out, the stream
+for _parent in ("nig_rollout_policy", "nig_rollout_mlp", "nig_rollout_mlp_safe", "nig_rollout_mlp_search", "nig_rollout_mlp_gated",
+                "nig_rollout_mlp_projected", "nig_rollout_mlp_ensemble", "nig_rollout_policy_disturbed", "nig_rollout_mlp_disturbed"):
+    _restype, _argtypes = PROTOTYPES[_parent]
+    PROTOTYPES[_parent + "_limited"] = (_restype, _argtypes[:-1] + [vp, _argtypes[-1]])
 SYMBOLS = list(PROTOTYPES)
 
 

@@ -584,7 +584,7 @@ class BatchedIndustrialEnv:
         """rollout_mlp_safe() under the added safety constraints (add_safety_constraint; "nig-limits-v1"), checked on the action
         the env received; xflags_out as rollout_policy_limited()'s."""
         self._closed_loop(self._L.nig_rollout_mlp_safe_limited, n_steps, reward_out, flags_out, obs_out, act_out,
-                          rows=[("prob_out", prob_out, torch.float32), ("xflags_out", xflags_out, torch.int32)])
+                          rows=[("prob_out", prob_out, torch.float32)], xflags=(xflags_out,))
 
     def rollout_mlp_search(self, n_steps: int, n_candidates: int, reward_out=None, flags_out=None, obs_out=None, act_out=None,
                            prob_out=None, risk_out=None, choice_out=None):
@@ -603,8 +603,8 @@ class BatchedIndustrialEnv:
         """rollout_mlp_search() under the added safety constraints, checked on the action the env received; xflags_out as
         rollout_policy_limited()'s."""
         self._closed_loop(self._L.nig_rollout_mlp_search_limited, n_steps, reward_out, flags_out, obs_out, act_out, head=(int(n_candidates),),
-                          rows=[("prob_out", prob_out, torch.float32), ("risk_out", risk_out, torch.float32), ("choice_out", choice_out, torch.int32),
-                                ("xflags_out", xflags_out, torch.int32)])
+                          rows=[("prob_out", prob_out, torch.float32), ("risk_out", risk_out, torch.float32), ("choice_out", choice_out, torch.int32)],
+                          xflags=(xflags_out,))
 
     def set_mlp_safety_ensemble(self, members, temperature: float = 1.0, threshold: float = 0.1, max_uncertainty: float = 0.2):
         """Install the safety ensemble of SafeEnsembleAgent (agents/safety_critical.py) for rollout_mlp_gated(): `members` = a
@@ -634,10 +634,10 @@ class BatchedIndustrialEnv:
                                   unc_out=None, logit_out=None, xflags_out=None):
         """rollout_mlp_gated() under the added safety constraints, checked on the action the env received; xflags_out as
         rollout_policy_limited()'s."""
-        self._gated(self._L.nig_rollout_mlp_gated_limited, [("xflags_out", xflags_out, torch.int32)], n_steps, reward_out, flags_out,
-                    obs_out, act_out, prob_out, unc_out, logit_out)
+        self._gated(self._L.nig_rollout_mlp_gated_limited, (xflags_out,), n_steps, reward_out, flags_out, obs_out, act_out, prob_out, unc_out,
+                    logit_out)
 
-    def _gated(self, fn, last_rows, n_steps, reward_out, flags_out, obs_out, act_out, prob_out, unc_out, logit_out):
+    def _gated(self, fn, xflags, n_steps, reward_out, flags_out, obs_out, act_out, prob_out, unc_out, logit_out):
         K, Cn = getattr(self, "_gate_shape", (0, 0))
         ptrs, pitches = [], set()
         for name, t, lead in (("prob_out", prob_out, ()), ("unc_out", unc_out, ()), ("logit_out", logit_out, (K,))):
@@ -651,7 +651,7 @@ class BatchedIndustrialEnv:
             pitches.add((t.stride(-2), t.stride(-3)))
         assert len(pitches) <= 1, "prob_out, unc_out and logit_out share their pitches"
         ld_c, c_step = pitches.pop() if pitches else (0, 0)
-        self._closed_loop(fn, n_steps, reward_out, flags_out, obs_out, act_out, tail=(*ptrs, ld_c, c_step), last_rows=last_rows)
+        self._closed_loop(fn, n_steps, reward_out, flags_out, obs_out, act_out, tail=(*ptrs, ld_c, c_step), xflags=xflags)
 
     def set_mlp_constraint(self, predictor, threshold: float = 0.1, tolerance: float = 0.01):
         """Install the constraint predictor of ConstrainedIQLAgent (agents/safety_critical.py) for rollout_mlp_projected():
@@ -675,7 +675,7 @@ class BatchedIndustrialEnv:
         the actor's action / of the action the env received (they share their pitches); iters_out int32 [n_steps, >=B] the
         gradient steps taken, -1 where the actor's action was kept; grad_out float32 [n_steps, A, >=B] (act_out's pitches) the
         first gradient, written where iters >= 1; flags carry FLAG_SHIELDED on projected lanes."""
-        self._projected(self._L.nig_rollout_mlp_projected, None, n_steps, max_iters, step, reward_out, flags_out, obs_out, act_out,
+        self._projected(self._L.nig_rollout_mlp_projected, (), n_steps, max_iters, step, reward_out, flags_out, obs_out, act_out,
                         prob_out, viol_out, iters_out, grad_out)
 
     def rollout_mlp_projected_limited(self, n_steps: int, max_iters: int = 10, step: float = 0.1, reward_out=None, flags_out=None,
@@ -688,7 +688,6 @@ class BatchedIndustrialEnv:
 
     def _projected(self, fn, xflags, n_steps, max_iters, step, reward_out, flags_out, obs_out, act_out, prob_out, viol_out, iters_out,
                    grad_out):
-        """xflags: None for the parent, (xflags_out,) for the _limited twin (a row of iters_out's stride behind the parent's arguments)."""
         Cn = getattr(self, "_constraint_outputs", 0)
         ptrs, pitches = [], set()
         for name, t in (("prob_out", prob_out), ("viol_out", viol_out)):
@@ -701,24 +700,14 @@ class BatchedIndustrialEnv:
             pitches.add((t.stride(1), t.stride(0)))
         assert len(pitches) <= 1, "prob_out and viol_out share their pitches"
         ld_c, c_step = pitches.pop() if pitches else (0, 0)
-        rp, fp, os_, op, so, ap, lda, sa = self._closed_loop_outputs(n_steps, reward_out, flags_out, obs_out, act_out)
-        ip, is_ = _rows(iters_out, torch.int32, n_steps)
-        strides = ({is_} if ip is not None else set()) | ({os_} if (rp is not None or fp is not None) else set())
-        last = ()
-        if xflags is not None:
-            xp, xs = _rows(xflags[0], torch.int32, n_steps)
-            strides |= {xs} if xp is not None else set()
-            last = (xp,)
-        assert len(strides) <= 1, "iters_out (and xflags_out) share the reward/flags row stride"
-        gp = None
+        gp, grad_pitches = None, None
         if grad_out is not None:
             assert grad_out.dtype == torch.float32 and grad_out.dim() == 3 and grad_out.stride(2) == 1, "grad_out"
             assert grad_out.shape[0] >= n_steps and grad_out.shape[1] == self.action_dim and grad_out.shape[2] >= self.batch, "grad_out"
-            assert ap is None or (grad_out.stride(1), grad_out.stride(0)) == (lda, sa), "grad_out shares act_out's pitches"
-            gp, lda, sa = C.c_void_p(grad_out.data_ptr()), grad_out.stride(1), grad_out.stride(0)
-        with torch.cuda.device(self._dev_index):
-            _lib.check(fn(self._h, int(n_steps), int(max_iters), float(step), rp, fp, strides.pop() if strides else 0,
-                          op, so, ap, lda, sa, *ptrs, ip, gp, ld_c, c_step, *last, self._stream()))
+            gp, grad_pitches = C.c_void_p(grad_out.data_ptr()), (grad_out.stride(1), grad_out.stride(0))
+        self._closed_loop(fn, n_steps, reward_out, flags_out, obs_out, act_out, head=(int(max_iters), float(step)), front=ptrs,
+                          rows=[("iters_out", iters_out, torch.int32)], tail=(gp, ld_c, c_step), act_pitches=("grad_out", grad_pitches),
+                          xflags=xflags, sharing="iters_out (and xflags_out) share")
 
     def set_mlp_ensemble(self, members, weights=None, weight_sum=None, method: str = "mean", uncertainty_threshold: float = 0.2):
         """Install an ensemble of actors (agents/ensemble.py EnsembleAgent) for rollout_mlp_ensemble(): `members` = a list of
@@ -752,10 +741,10 @@ class BatchedIndustrialEnv:
                                      member_act_out=None, xflags_out=None):
         """rollout_mlp_ensemble() under the added safety constraints, checked on the action the env received (the float64 average
         where the env steps on it); xflags_out as rollout_policy_limited()'s."""
-        self._ensemble(self._L.nig_rollout_mlp_ensemble_limited, [("xflags_out", xflags_out, torch.int32)], n_steps, reward_out,
-                       flags_out, obs_out, act_out, unc_out, member_act_out)
+        self._ensemble(self._L.nig_rollout_mlp_ensemble_limited, (xflags_out,), n_steps, reward_out, flags_out, obs_out, act_out, unc_out,
+                       member_act_out)
 
-    def _ensemble(self, fn, last_rows, n_steps, reward_out, flags_out, obs_out, act_out, unc_out, member_act_out):
+    def _ensemble(self, fn, xflags, n_steps, reward_out, flags_out, obs_out, act_out, unc_out, member_act_out):
         mp, pitches = None, None
         if member_act_out is not None:
             K, m = getattr(self, "_ensemble_members", 0), member_act_out
@@ -763,28 +752,33 @@ class BatchedIndustrialEnv:
             assert m.shape[0] >= n_steps and m.shape[1] == K and m.shape[2] == self.action_dim and m.shape[3] >= self.batch
             mp, pitches = C.c_void_p(m.data_ptr()), (m.stride(2), m.stride(1))
         self._closed_loop(fn, n_steps, reward_out, flags_out, obs_out, act_out,
-                          rows=[("unc_out", unc_out, torch.float32)], tail=(mp,), member_pitches=pitches, last_rows=last_rows)
+                          rows=[("unc_out", unc_out, torch.float32)], tail=(mp,), act_pitches=("member_act_out", pitches), xflags=xflags)
 
-    def _closed_loop(self, fn, n_steps, reward_out, flags_out, obs_out, act_out, head=(), rows=(), tail=(), member_pitches=None, last_rows=()):
+    def _closed_loop(self, fn, n_steps, reward_out, flags_out, obs_out, act_out, head=(), front=(), rows=(), tail=(), act_pitches=(None, None),
+                     xflags=(), sharing=None):
         """One closed-loop call of the C ABI: fn(handle, n_steps, *head, <the eight output arguments the closed loops share: reward
-        ptr, flags ptr, out_stride, obs ptr, obs_step_stride, act ptr, ld_act, act_step_stride>, <a pointer per entry of `rows`>,
-        *tail, stream), the four optional output tensors validated.  rows: (name, tensor or None, dtype) of the variant's extra
-        per-step rows [n_steps, >=B], which share the row stride of reward_out / flags_out.  member_pitches: (ld_act,
-        act_step_stride) of the ensemble's member_act_out, which shares act_out's pitches and states them where act_out is absent.
-        last_rows: as `rows`, for rows the ABI takes behind `tail` (a _limited twin's xflags_out behind its parent's arguments)."""
+        ptr, flags ptr, out_stride, obs ptr, obs_step_stride, act ptr, ld_act, act_step_stride>, *front, <a pointer per entry of
+        `rows`>, *tail, <a _limited twin's xflags_out>, stream), the four optional output tensors validated.  rows: (name, tensor or
+        None, dtype) of the variant's extra per-step rows [n_steps, >=B], which share the row stride of reward_out / flags_out.
+        xflags: () for a parent, (xflags_out,) for a _limited twin -- such a row, the last argument before the stream.  act_pitches:
+        (name, (ld_act, act_step_stride) or None) of an output that shares act_out's pitches and states them where act_out is
+        absent (the ensemble's member_act_out, the projection's grad_out).  sharing: the subject of the row-stride message where
+        it is not made of the rows' names."""
         rp, fp, os_, op, so, ap, lda, sa = self._closed_loop_outputs(n_steps, reward_out, flags_out, obs_out, act_out)
+        rows = [*rows, *(("xflags_out", t, torch.int32) for t in xflags)]
         extra = [_rows(t, dtype, n_steps) for _, t, dtype in rows]
-        last = [_rows(t, dtype, n_steps) for _, t, dtype in last_rows]
-        strides = {st for ptr, st in extra + last if ptr is not None} | ({os_} if (rp is not None or fp is not None) else set())
-        names = [name for name, _, _ in (*rows, *last_rows)]
-        assert len(strides) <= 1, (f"{', '.join(names[:-1])} and {names[-1]} share" if len(names) > 1 else f"{names[0]} shares") \
+        strides = {st for ptr, st in extra if ptr is not None} | ({os_} if (rp is not None or fp is not None) else set())
+        names = [name for name, _, _ in rows]
+        assert len(strides) <= 1, (sharing or (f"{', '.join(names[:-1])} and {names[-1]} share" if len(names) > 1 else f"{names[0]} shares")) \
             + " the reward/flags row stride"
-        if member_pitches is not None:
-            assert ap is None or member_pitches == (lda, sa), "member_act_out shares act_out's pitches"
-            lda, sa = member_pitches
+        name, pitches = act_pitches
+        if pitches is not None:
+            assert ap is None or pitches == (lda, sa), f"{name} shares act_out's pitches"
+            lda, sa = pitches
+        ptrs = [ptr for ptr, _ in extra]
         with torch.cuda.device(self._dev_index):
-            _lib.check(fn(self._h, int(n_steps), *head, rp, fp, strides.pop() if strides else 0, op, so, ap, lda, sa,
-                          *[ptr for ptr, _ in extra], *tail, *[ptr for ptr, _ in last], self._stream()))
+            _lib.check(fn(self._h, int(n_steps), *head, rp, fp, strides.pop() if strides else 0, op, so, ap, lda, sa, *front,
+                          *ptrs[:len(ptrs) - len(xflags)], *tail, *ptrs[len(ptrs) - len(xflags):], self._stream()))
 
     def _closed_loop_outputs(self, n_steps, reward_out, flags_out, obs_out, act_out):
         """The output arguments the closed-loop rollouts share, from the optional tensors, validated:
@@ -816,13 +810,11 @@ class BatchedIndustrialEnv:
         """rollout_policy() under the added safety constraints (add_safety_constraint; "nig-limits-v1"): xflags_out int32
         [n_steps, >=B] (the row stride of reward_out / flags_out) is the added constraints' word of every step -- bit c: added
         constraint c violated, bits 4-6 how many, bits 8-10 how many critical ones."""
-        self._closed_loop(self._L.nig_rollout_policy_limited, n_steps, reward_out, flags_out, obs_out, act_out,
-                          rows=[("xflags_out", xflags_out, torch.int32)])
+        self._closed_loop(self._L.nig_rollout_policy_limited, n_steps, reward_out, flags_out, obs_out, act_out, xflags=(xflags_out,))
 
     def rollout_mlp_limited(self, n_steps: int, reward_out=None, flags_out=None, obs_out=None, act_out=None, xflags_out=None):
         """rollout_mlp() under the added safety constraints; outputs as rollout_policy_limited()."""
-        self._closed_loop(self._L.nig_rollout_mlp_limited, n_steps, reward_out, flags_out, obs_out, act_out,
-                          rows=[("xflags_out", xflags_out, torch.int32)])
+        self._closed_loop(self._L.nig_rollout_mlp_limited, n_steps, reward_out, flags_out, obs_out, act_out, xflags=(xflags_out,))
 
     # ------------------------------------------------------------------
     def set_disturbance(self, disturbance):
@@ -859,13 +851,13 @@ class BatchedIndustrialEnv:
         """rollout_policy_disturbed() under the added safety constraints, checked on the true state and the action the env received;
         xflags_out as rollout_policy_limited()'s."""
         self._closed_loop(self._L.nig_rollout_policy_disturbed_limited, n_steps, reward_out, flags_out, obs_out, act_out,
-                          tail=self._seen_rows(n_steps, seen_out), last_rows=[("xflags_out", xflags_out, torch.int32)])
+                          tail=self._seen_rows(n_steps, seen_out), xflags=(xflags_out,))
 
     def rollout_mlp_disturbed_limited(self, n_steps: int, reward_out=None, flags_out=None, obs_out=None, act_out=None, seen_out=None,
                                       xflags_out=None):
         """rollout_mlp_disturbed() under the added safety constraints; outputs as rollout_policy_disturbed_limited()."""
         self._closed_loop(self._L.nig_rollout_mlp_disturbed_limited, n_steps, reward_out, flags_out, obs_out, act_out,
-                          tail=self._seen_rows(n_steps, seen_out), last_rows=[("xflags_out", xflags_out, torch.int32)])
+                          tail=self._seen_rows(n_steps, seen_out), xflags=(xflags_out,))
 
     def get_dataset(self, quality: str = "mixed", scale: int = 1, chunk: int = 100):
         """Batched env.get_dataset(quality): every lane is one episode of the reference's

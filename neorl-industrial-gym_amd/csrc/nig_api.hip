@@ -323,6 +323,19 @@ static int refuse_limited(const nig_handle *h, const char *fn)
                           "nig_rollout_policy_limited / nig_rollout_mlp_limited, or remove them with nig_set_limits(h, 0, ...)", NIG_ERR_UNSUPPORTED);
     return NIG_OK;
 }
+// the _limited entry points' own prerequisite (a handle of an env that takes no limits never has any installed) ...
+static int check_limits(const nig_handle *h, const char *fn)
+{
+    return h->n_limits <= 0 ? refuse(fn, "no limits installed (nig_set_limits)") : NIG_OK;
+}
+// ... and the kernel's view of the limits.  n_en counts the added constraints as well: SafetyMetrics.total_constraints of every
+// step (base.py:115)
+static void limit_args(const nig_handle *h, uint32_t *xflags_out, StepArgs &s, LimitArgs &l)
+{
+    s.n_en += h->n_limits;
+    s.mirror = nullptr;
+    l.table = h->lim_dev; l.xflags = xflags_out;
+}
 
 static void dispatch_step(const nig_handle *h, const StepArgs &a, bool parity, hipStream_t st)
 {
@@ -386,7 +399,10 @@ struct ClosedLoopOut {
     float *reward; uint32_t *flags; int64_t out_stride;
     float *obs; int64_t obs_step_stride;
     float *act; int64_t ld_act, act_step_stride;
+    uint32_t *xflags;           // a _limited twin's xflags_out (a parent leaves it out: NULL)
 };
+// what every closed-loop entry point passes on, in the struct's order (a twin: {CLOSED_LOOP_OUT, xflags_out})
+#define CLOSED_LOOP_OUT reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride
 // A row-major [n_steps][B][S] trajectory (obs_out, seen_out): 16-byte aligned, rows of step k at k * step_stride >= S * batch floats,
 // a multiple of 4 (there is no "overwrite" form)
 static int check_state_rows(const nig_handle *h, const char *fn, const float *rows, int64_t step_stride, const char *refusal)
@@ -443,33 +459,80 @@ static int disturb_args(const nig_handle *h, const char *fn, float *seen_out, in
     return NIG_OK;
 }
 
-// ---- the closed loop: what nig_rollout_policy / _mlp / _mlp_safe / _mlp_search / _mlp_gated / _mlp_projected / _mlp_ensemble / _policy_disturbed / _mlp_disturbed
-// do after their own prerequisites.  A variant's argument block holds the shared fields as PolicyArgs or MlpArgs, which also says
-// what grid its kernels take: a thread per env for the policy kernels, 32 envs per wave (128 per block) for the MFMA kernels.
+// ---- the closed loop: what nig_rollout_policy / _mlp / _mlp_bf16 / _mlp_safe / _mlp_search / _mlp_gated / _mlp_projected / _mlp_ensemble /
+// _policy_disturbed / _mlp_disturbed and their _limited twins do after their own prerequisites.  A variant's argument block holds the
+// shared fields as PolicyArgs or MlpArgs, which also says what grid its kernels take: a thread per env for the policy kernels, 32 envs
+// per wave (128 per block) for the MFMA kernels.
 static PolicyArgs &shared_args(PolicyArgs &q) { return q; }
 static PolicyArgs &shared_args(PolicyDistArgs &q) { return q.p; }
 static MlpArgs &shared_args(MlpArgs &q) { return q; }
 static PolicyArgs &shared_args(PolicyLimArgs &q) { return q.p; }
 static MlpArgs &shared_args(MlpSearchArgs &q) { return q.sh.m; }
-template <class Args> static MlpArgs &shared_args(Args &q) { return q.m; }      // MlpShieldArgs, MlpEnsArgs, MlpDistArgs, MlpGateArgs, MlpProjectArgs
+template <class Args> static MlpArgs &shared_args(Args &q) { return q.m; }      // MlpShieldArgs, MlpEnsArgs, MlpDistArgs, MlpGateArgs, MlpProjectArgs, MlpBf16Args, MlpLimArgs
 static PolicyArgs &shared_args(PolicyDistLimArgs &q) { return q.p; }
 template <class Parent> static MlpArgs &shared_args(MlpLimited<Parent> &q) { return shared_args(q.a); }      // a _limited twin: its parent's
 static unsigned closed_loop_grid(const nig_handle *h, const PolicyArgs &) { return grid_for(h->B); }
 static unsigned closed_loop_grid(const nig_handle *h, const MlpArgs &) { return (unsigned)((h->B + BLOCK / 2 - 1) / (BLOCK / 2)); }
 
-// The zeroed block, the argument checks and the shared fields; `variant(q)` fills the variant's own fields and returns the launcher
-// (an EnvLaunch entry, or a callable of its shape); then the launch, its error and the launch counter.  No synchronisation.
-template <class Args, class Variant>
-static int closed_loop(nig_handle *h, const char *fn, int32_t n_steps, const ClosedLoopOut &o, void *stream, Variant &&variant)
+// A family is stated once, as a function template on LIM: false is the parent entry point, true its _limited twin.  The twin's
+// argument block is the parent's beside a LimitArgs `l`; these say which type that is, where the parent's own fields lie in it, and
+// which of the family's two EnvLaunch slots a call takes.
+template <class Parent> struct limited_twin { using type = MlpLimited<Parent>; };
+template <> struct limited_twin<PolicyArgs> { using type = PolicyLimArgs; };
+template <> struct limited_twin<PolicyDistArgs> { using type = PolicyDistLimArgs; };
+template <> struct limited_twin<MlpArgs> { using type = MlpLimArgs; };
+template <class Args> static Args &parent_args(Args &q) { return q; }           // a parent; PolicyDistLimArgs, which restates its parent's members
+static PolicyArgs &parent_args(PolicyLimArgs &q) { return q.p; }
+static MlpArgs &parent_args(MlpLimArgs &q) { return q.m; }
+template <class Parent> static Parent &parent_args(MlpLimited<Parent> &q) { return q.a; }
+template <bool LIM, class P, class T>
+static auto slot_of(P parent, T twin)
 {
-    Args q;
+    if constexpr (LIM) return twin;
+    else return parent;
+}
+
+// The zeroed block (the parent's, or with LIM its twin's), the argument checks and the shared fields; `fill` writes the family's
+// own fields into the parent's part of the block, a twin gets the limits beside them (o.xflags: its xflags_out); then the launch
+// through `launch` (an EnvLaunch entry, or a callable of its shape), its error and the launch counter.  No synchronisation.
+template <bool LIM, class Parent, class Launch, class Fill>
+static int closed_loop(nig_handle *h, const char *fn, int32_t n_steps, const ClosedLoopOut &o, void *stream, Launch launch, Fill &&fill)
+{
+    std::conditional_t<LIM, typename limited_twin<Parent>::type, Parent> q;
     memset(&q, 0, sizeof q);
     auto &shared = shared_args(q);
     NIG_TRY(closed_loop_args(h, fn, n_steps, o, shared));
-    const auto launch = variant(q);
+    fill(parent_args(q));
+    if constexpr (LIM) limit_args(h, o.xflags, shared.s, q.l);
     launch(q, closed_loop_grid(h, shared), (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     h->t += (uint32_t)n_steps;
+    return NIG_OK;
+}
+
+// The refusals several families share.  A parent refuses installed limits and a twin needs them: the later families ask at one
+// place, right after the bad-argument check (the early pairs -- the step pair, nig_rollout_policy, nig_rollout_mlp -- ask the parent's
+// question before their prerequisites and the twin's after them).
+template <bool LIM>
+static int limits_gate(const nig_handle *h, const char *fn) { return LIM ? check_limits(h, fn) : refuse_limited(h, fn); }
+static int need_mfma_actor(const nig_handle *h, const char *fn)
+{
+    return launch_of(h->env)->mlp ? NIG_OK : refuse(fn, "env shape has no MFMA actor", NIG_ERR_UNSUPPORTED);
+}
+static int need_actor(const nig_handle *h, const char *fn)       // (an env without the MFMA actor never has one: nig_set_mlp_policy refuses)
+{
+    return h->mlp_stream ? NIG_OK : refuse(fn, "no actor installed (nig_set_mlp_policy)");
+}
+static int need_policy(const nig_handle *h, const char *fn) { return h->has_policy ? NIG_OK : refuse(fn, "no policy installed (nig_set_policy)"); }
+static int need_critic(const nig_handle *h, const char *fn)
+{
+    return h->mlp_cstream ? NIG_OK : refuse(fn, "no safety critic installed (nig_set_mlp_safety)");
+}
+// the per-constraint rows of the gate and the projection: [n_outputs][ld_c] blocks, c_step_stride apart
+static int check_constraint_rows(const nig_handle *h, const char *fn, int n_outputs, int64_t ld_c, int64_t c_step_stride)
+{
+    if (ld_c < h->B || ld_c > NIG_MAX_PITCH) return refuse(fn, "ld_c outside [batch, 2^26]");
+    if (c_step_stride < (int64_t)n_outputs * ld_c) return refuse(fn, "c_step_stride smaller than one [n_outputs][ld_c] block");
     return NIG_OK;
 }
 
@@ -483,6 +546,165 @@ static void shield_fields(const nig_handle *h, float *prob_out, MlpShieldArgs &q
 {
     q.m.wstream = h->mlp_stream;
     q.cstream = h->mlp_cstream; q.prob_out = prob_out; q.threshold = h->mlp_threshold;
+}
+
+// ---- the families with a twin, in the order of their entry points below ---------------------------------------------------
+// Order of refusals: bad argument; the question about limits (code 4 from a parent, "no limits installed", NIG_ERR_INVALID, from a
+// twin); the family's own refusals; closed_loop's argument contracts.  The Advanced pair never has limits installed, so its twins
+// refuse at the second step.  The entry points pass their own name, and a twin its xflags_out in the ClosedLoopOut.
+template <bool LIM>
+static int rollout_policy(nig_handle *h, const char *fn, int32_t n_steps, const ClosedLoopOut &o, void *stream)
+{
+    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    if (!LIM) NIG_TRY(refuse_limited(h, fn));
+    NIG_TRY(need_policy(h, fn));
+    if (LIM) NIG_TRY(check_limits(h, fn));
+    const EnvLaunch *L = launch_of(h->env);
+    NIG_TRY((closed_loop<LIM, PolicyArgs>(h, fn, n_steps, o, stream, slot_of<LIM>(L->policy, L->policy_limited),
+                                          [&](PolicyArgs &q) { policy_fields(h, q); })));
+    return LIM ? NIG_OK : ring_check(h, (hipStream_t)stream, fn);      // (the one closed loop with cooperating-wave forms)
+}
+
+template <bool LIM>
+static int rollout_mlp(nig_handle *h, const char *fn, int32_t n_steps, const ClosedLoopOut &o, void *stream)
+{
+    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    if (!LIM) NIG_TRY(refuse_limited(h, fn));
+    NIG_TRY(need_actor(h, fn));
+    if (LIM) NIG_TRY(check_limits(h, fn));
+    const EnvLaunch *L = launch_of(h->env);
+    return closed_loop<LIM, MlpArgs>(h, fn, n_steps, o, stream, slot_of<LIM>(L->mlp, L->mlp_limited),
+                                     [&](MlpArgs &q) { q.wstream = h->mlp_stream; });
+}
+
+template <bool LIM>
+static int rollout_mlp_safe(nig_handle *h, const char *fn, int32_t n_steps, const ClosedLoopOut &o, float *prob_out, void *stream)
+{
+    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    NIG_TRY(limits_gate<LIM>(h, fn));
+    NIG_TRY(need_mfma_actor(h, fn));
+    NIG_TRY(need_actor(h, fn));
+    NIG_TRY(need_critic(h, fn));
+    const EnvLaunch *L = launch_of(h->env);
+    return closed_loop<LIM, MlpShieldArgs>(h, fn, n_steps, o, stream, slot_of<LIM>(L->mlp_shield, L->mlp_shield_limited),
+                                           [&](MlpShieldArgs &q) { shield_fields(h, prob_out, q); });
+}
+
+template <bool LIM>
+static int rollout_mlp_search(nig_handle *h, const char *fn, int32_t n_steps, int32_t n_candidates, const ClosedLoopOut &o, float *prob_out,
+                              float *risk_out, int32_t *choice_out, void *stream)
+{
+    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    NIG_TRY(limits_gate<LIM>(h, fn));
+    NIG_TRY(need_mfma_actor(h, fn));
+    if (n_candidates < 1 || n_candidates > NIG_MAX_CANDIDATES) return refuse(fn, "n_candidates outside 1 .. NIG_MAX_CANDIDATES");
+    NIG_TRY(need_actor(h, fn));
+    NIG_TRY(need_critic(h, fn));
+    const EnvLaunch *L = launch_of(h->env);
+    return closed_loop<LIM, MlpSearchArgs>(h, fn, n_steps, o, stream, slot_of<LIM>(L->mlp_search, L->mlp_search_limited), [&](MlpSearchArgs &q) {
+        shield_fields(h, prob_out, q.sh);
+        q.n_candidates = n_candidates; q.risk_out = risk_out; q.choice_out = choice_out;
+    });
+}
+
+template <bool LIM>
+static int rollout_mlp_ensemble(nig_handle *h, const char *fn, int32_t n_steps, ClosedLoopOut o, float *unc_out, float *member_act_out, void *stream)
+{
+    if (!h || n_steps <= 0) return refuse(fn, "bad argument (handle, n_steps)");
+    NIG_TRY(limits_gate<LIM>(h, fn));
+    NIG_TRY(need_mfma_actor(h, fn));
+    if (h->ens_members < 1 || !h->ens_stream) return refuse(fn, "no ensemble installed (nig_set_mlp_ensemble)");
+    float *const act_out = o.act;
+    if (!o.act) o.act = member_act_out;           // member_act_out shares act_out's pitches: the same checks apply to it when act_out is absent
+    const int ens = h->ens_method == NIG_ENSEMBLE_AVERAGE ? ENS_AVERAGE : ENS_VOTING;      // one kernel per combination rule
+    const auto launch = [&](const auto &e, unsigned grid, hipStream_t st) {
+        const EnvLaunch *L = launch_of(h->env);
+        slot_of<LIM>(L->mlp_ensemble, L->mlp_ensemble_limited)(ens, e, grid, st);
+    };
+    return closed_loop<LIM, MlpEnsArgs>(h, fn, n_steps, o, stream, launch, [&](MlpEnsArgs &q) {
+        q.m.act_out = act_out;
+        q.m.wstream = h->ens_stream;
+        q.n_members = h->ens_members; q.w = h->ens_w; q.wsum = h->ens_wsum; q.kf = (float)h->ens_members; q.threshold = h->ens_threshold;
+        q.unc_out = unc_out; q.member_out = member_act_out;
+    });
+}
+
+template <bool LIM>
+static int rollout_mlp_gated(nig_handle *h, const char *fn, int32_t n_steps, const ClosedLoopOut &o, float *prob_out, float *unc_out,
+                             float *logit_out, int64_t ld_c, int64_t c_step_stride, void *stream)
+{
+    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    NIG_TRY(limits_gate<LIM>(h, fn));
+    NIG_TRY(need_mfma_actor(h, fn));
+    NIG_TRY(need_actor(h, fn));
+    if (h->gate_members < 1 || !h->gate_stream) return refuse(fn, "no safety ensemble installed (nig_set_mlp_safety_ensemble)");
+    if (prob_out || unc_out || logit_out) NIG_TRY(check_constraint_rows(h, fn, h->gate_outputs, ld_c, c_step_stride));
+    const EnvLaunch *L = launch_of(h->env);
+    return closed_loop<LIM, MlpGateArgs>(h, fn, n_steps, o, stream, slot_of<LIM>(L->mlp_gated, L->mlp_gated_limited), [&](MlpGateArgs &q) {
+        q.m.wstream = h->mlp_stream;
+        q.cstreams = h->gate_stream; q.n_members = h->gate_members; q.n_outputs = h->gate_outputs; q.kf = (float)h->gate_members;
+        q.temperature = h->gate_T; q.threshold = h->gate_thr; q.umax = h->gate_umax;
+        q.prob_out = prob_out; q.unc_out = unc_out; q.logit_out = logit_out;
+        q.ld_c = (uint32_t)ld_c; q.c_step_stride = (uint64_t)c_step_stride;
+    });
+}
+
+template <bool LIM>
+static int rollout_mlp_projected(nig_handle *h, const char *fn, int32_t n_steps, int32_t max_iters, float step, const ClosedLoopOut &o,
+                                 float *prob_out, float *viol_out, int32_t *iters_out, float *grad_out, int64_t ld_c, int64_t c_step_stride,
+                                 void *stream)
+{
+    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    NIG_TRY(limits_gate<LIM>(h, fn));
+    NIG_TRY(need_mfma_actor(h, fn));
+    NIG_TRY(need_actor(h, fn));
+    if (h->proj_outputs < 1 || !h->proj_cstream || !h->proj_bstream) return refuse(fn, "no constraint predictor installed (nig_set_mlp_constraint)");
+    if (max_iters < 1 || max_iters > NIG_MAX_PROJECT_ITERS) return refuse(fn, "max_iters outside 1 .. NIG_MAX_PROJECT_ITERS");
+    if (!std::isfinite(step)) return refuse(fn, "step must be finite");
+    if (prob_out || viol_out) NIG_TRY(check_constraint_rows(h, fn, h->proj_outputs, ld_c, c_step_stride));
+    if (grad_out && (o.ld_act < h->B || o.ld_act > NIG_MAX_PITCH || o.act_step_stride < (int64_t)SPECS[h->env].action_dim * o.ld_act))
+        return refuse(fn, "bad action trajectory pitch (grad_out takes act_out's)");
+    const EnvLaunch *L = launch_of(h->env);
+    return closed_loop<LIM, MlpProjectArgs>(h, fn, n_steps, o, stream, slot_of<LIM>(L->mlp_projected, L->mlp_projected_limited), [&](MlpProjectArgs &q) {
+        q.m.wstream = h->mlp_stream;
+        q.cstream = h->proj_cstream; q.bstream = h->proj_bstream; q.n_outputs = h->proj_outputs; q.max_iters = max_iters;
+        q.threshold = h->proj_thr; q.tolerance = h->proj_tol; q.step = step;
+        q.prob_out = prob_out; q.viol_out = viol_out; q.iters_out = iters_out; q.grad_out = grad_out;
+        q.ld_c = (uint32_t)ld_c; q.c_step_stride = (uint64_t)c_step_stride;
+    });
+}
+
+template <bool LIM>
+static int rollout_policy_disturbed(nig_handle *h, const char *fn, int32_t n_steps, const ClosedLoopOut &o, float *seen_out,
+                                    int64_t seen_step_stride, void *stream)
+{
+    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    NIG_TRY(limits_gate<LIM>(h, fn));
+    NIG_TRY(need_policy(h, fn));
+    DisturbArgs d;
+    NIG_TRY(disturb_args(h, fn, seen_out, seen_step_stride, d));
+    const EnvLaunch *L = launch_of(h->env);
+    return closed_loop<LIM, PolicyDistArgs>(h, fn, n_steps, o, stream, slot_of<LIM>(L->policy_disturbed, L->policy_disturbed_limited), [&](auto &q) {
+        q.d = d;
+        policy_fields(h, q.p);
+    });
+}
+
+template <bool LIM>
+static int rollout_mlp_disturbed(nig_handle *h, const char *fn, int32_t n_steps, const ClosedLoopOut &o, float *seen_out,
+                                 int64_t seen_step_stride, void *stream)
+{
+    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    NIG_TRY(limits_gate<LIM>(h, fn));
+    NIG_TRY(need_mfma_actor(h, fn));
+    NIG_TRY(need_actor(h, fn));
+    DisturbArgs d;
+    NIG_TRY(disturb_args(h, fn, seen_out, seen_step_stride, d));
+    const EnvLaunch *L = launch_of(h->env);
+    return closed_loop<LIM, MlpDistArgs>(h, fn, n_steps, o, stream, slot_of<LIM>(L->mlp_disturbed, L->mlp_disturbed_limited), [&](MlpDistArgs &q) {
+        q.d = d;
+        q.m.wstream = h->mlp_stream;
+    });
 }
 
 extern "C" {
@@ -796,41 +1018,72 @@ static StepArgs next_step_args(nig_handle *h, int64_t ld_act, const double *step
     return a;
 }
 
+// nig_step / nig_step64 (act64: float64 action rows) and, with lim, their _limited twins (xflags_out: the twins').  The parent asks
+// whether limits are installed before anything else (a NULL handle has none), the twin after its argument checks.  Every argument
+// is checked before anything is launched: a refused call enqueues nothing, the narrowing copy included.
+static int step_impl(nig_handle *h, const char *fn, bool lim, bool act64, const void *actions, int64_t ld_act, const double *step_noise,
+                     const double *reset_noise, int64_t ld_noise, float *reward_out, double *reward64_out, uint32_t *flags_out,
+                     uint32_t *xflags_out, float *final_obs, int64_t ld_obs, void *stream)
+{
+    if (!lim) NIG_TRY(refuse_limited(h, fn));
+    NIG_TRY(check_step(h, fn, actions, ld_act, step_noise, reset_noise, ld_noise, final_obs, ld_obs));
+    if (lim) NIG_TRY(check_limits(h, fn));
+    const EnvLaunch *L = launch_of(h->env);
+    const unsigned grid = grid_for(h->B);
+    if (act64 && !L->step64) {                    // this env's own arithmetic takes the action as float32: narrow the rows, step on them
+        const int A = SPECS[h->env].action_dim;
+        if (!h->act32) HIP_TRY(hipMalloc((void **)&h->act32, (size_t)A * h->lay.ld * sizeof(float)));
+        hipLaunchKernelGGL(narrow_rows_kernel, dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, (const double *)actions, ld_act,
+                           h->act32, h->lay.ld, A, h->B);
+        HIP_TRY(hipGetLastError());
+        actions = h->act32; ld_act = h->lay.ld; act64 = false;
+    }
+    StepLimArgs q;
+    memset(&q, 0, sizeof q);
+    q.p = next_step_args(h, ld_act, step_noise, reset_noise, ld_noise, reward_out, reward64_out, flags_out, final_obs, ld_obs);
+    if (act64) q.p.actions64 = (const double *)actions;
+    else q.p.actions = (const float *)actions;
+    const bool parity = step_noise || reset_noise;
+    if (lim) {
+        limit_args(h, xflags_out, q.p, q.l);
+        (act64 ? L->step64_limited : L->step_limited)(q, parity, grid, (hipStream_t)stream);
+    } else {
+        (act64 ? L->step64 : L->step)(q.p, parity, grid, (hipStream_t)stream);
+    }
+    HIP_TRY(hipGetLastError());
+    return NIG_OK;
+}
+
 int nig_step(nig_handle *h, const float *actions, int64_t ld_act, const double *step_noise, const double *reset_noise,
              int64_t ld_noise, float *reward_out, double *reward64_out, uint32_t *flags_out, float *final_obs,
              int64_t ld_obs, void *stream)
 {
-    NIG_TRY(refuse_limited(h, "nig_step"));
-    NIG_TRY(check_step(h, "nig_step", actions, ld_act, step_noise, reset_noise, ld_noise, final_obs, ld_obs));
-    StepArgs a = next_step_args(h, ld_act, step_noise, reset_noise, ld_noise, reward_out, reward64_out, flags_out, final_obs, ld_obs);
-    a.actions = actions;
-    dispatch_step(h, a, step_noise || reset_noise, (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    return NIG_OK;
+    return step_impl(h, "nig_step", false, false, actions, ld_act, step_noise, reset_noise, ld_noise, reward_out, reward64_out, flags_out,
+                     nullptr, final_obs, ld_obs, stream);
 }
 
 int nig_step64(nig_handle *h, const double *actions, int64_t ld_act, const double *step_noise, const double *reset_noise,
                int64_t ld_noise, float *reward_out, double *reward64_out, uint32_t *flags_out, float *final_obs,
                int64_t ld_obs, void *stream)
 {
-    // every argument is checked before anything is launched: a refused call enqueues nothing (the narrowing copy below included)
-    NIG_TRY(refuse_limited(h, "nig_step64"));
-    NIG_TRY(check_step(h, "nig_step64", actions, ld_act, step_noise, reset_noise, ld_noise, final_obs, ld_obs));
-    const EnvLaunch *L = launch_of(h->env);
-    if (!L->step64) {                             // this env's own arithmetic takes the action as float32
-        const int A = SPECS[h->env].action_dim;
-        if (!h->act32) HIP_TRY(hipMalloc((void **)&h->act32, (size_t)A * h->lay.ld * sizeof(float)));
-        hipLaunchKernelGGL(narrow_rows_kernel, dim3(grid_for(h->B)), dim3(BLOCK), 0, (hipStream_t)stream, actions, ld_act,
-                           h->act32, h->lay.ld, A, h->B);
-        HIP_TRY(hipGetLastError());
-        return nig_step(h, h->act32, h->lay.ld, step_noise, reset_noise, ld_noise, reward_out, reward64_out, flags_out,
-                        final_obs, ld_obs, stream);
-    }
-    StepArgs a = next_step_args(h, ld_act, step_noise, reset_noise, ld_noise, reward_out, reward64_out, flags_out, final_obs, ld_obs);
-    a.actions64 = actions;
-    L->step64(a, step_noise || reset_noise, grid_for(h->B), (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    return NIG_OK;
+    return step_impl(h, "nig_step64", false, true, actions, ld_act, step_noise, reset_noise, ld_noise, reward_out, reward64_out, flags_out,
+                     nullptr, final_obs, ld_obs, stream);
+}
+
+int nig_step_limited(nig_handle *h, const float *actions, int64_t ld_act, const double *step_noise, const double *reset_noise,
+                     int64_t ld_noise, float *reward_out, double *reward64_out, uint32_t *flags_out, uint32_t *xflags_out,
+                     float *final_obs, int64_t ld_obs, void *stream)
+{
+    return step_impl(h, "nig_step_limited", true, false, actions, ld_act, step_noise, reset_noise, ld_noise, reward_out, reward64_out,
+                     flags_out, xflags_out, final_obs, ld_obs, stream);
+}
+
+int nig_step64_limited(nig_handle *h, const double *actions, int64_t ld_act, const double *step_noise, const double *reset_noise,
+                       int64_t ld_noise, float *reward_out, double *reward64_out, uint32_t *flags_out, uint32_t *xflags_out,
+                       float *final_obs, int64_t ld_obs, void *stream)
+{
+    return step_impl(h, "nig_step64_limited", true, true, actions, ld_act, step_noise, reset_noise, ld_noise, reward_out, reward64_out,
+                     flags_out, xflags_out, final_obs, ld_obs, stream);
 }
 
 
@@ -874,64 +1127,6 @@ int nig_set_limits(nig_handle *h, int32_t n, const nig_limit *limits, void *stre
 }
 
 int nig_get_limit_count(const nig_handle *h) { return h ? h->n_limits : -1; }
-
-// the limited entry points' own prerequisite (a handle of an env that takes no limits never has any installed) ...
-static int check_limits(const nig_handle *h, const char *fn)
-{
-    return h->n_limits <= 0 ? refuse(fn, "no limits installed (nig_set_limits)") : NIG_OK;
-}
-// ... and the kernel's view of the limits.  n_en counts the added constraints as well: SafetyMetrics.total_constraints of every
-// step (base.py:115)
-static void limit_args(const nig_handle *h, uint32_t *xflags_out, StepArgs &s, LimitArgs &l)
-{
-    s.n_en += h->n_limits;
-    s.mirror = nullptr;
-    l.table = h->lim_dev; l.xflags = xflags_out;
-}
-
-int nig_step_limited(nig_handle *h, const float *actions, int64_t ld_act, const double *step_noise, const double *reset_noise,
-                     int64_t ld_noise, float *reward_out, double *reward64_out, uint32_t *flags_out, uint32_t *xflags_out,
-                     float *final_obs, int64_t ld_obs, void *stream)
-{
-    const char *const fn = "nig_step_limited";
-    NIG_TRY(check_step(h, fn, actions, ld_act, step_noise, reset_noise, ld_noise, final_obs, ld_obs));
-    NIG_TRY(check_limits(h, fn));
-    StepLimArgs q;
-    memset(&q, 0, sizeof q);
-    q.p = next_step_args(h, ld_act, step_noise, reset_noise, ld_noise, reward_out, reward64_out, flags_out, final_obs, ld_obs);
-    q.p.actions = actions;
-    limit_args(h, xflags_out, q.p, q.l);
-    launch_of(h->env)->step_limited(q, step_noise || reset_noise, grid_for(h->B), (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    return NIG_OK;
-}
-
-int nig_step64_limited(nig_handle *h, const double *actions, int64_t ld_act, const double *step_noise, const double *reset_noise,
-                       int64_t ld_noise, float *reward_out, double *reward64_out, uint32_t *flags_out, uint32_t *xflags_out,
-                       float *final_obs, int64_t ld_obs, void *stream)
-{
-    const char *const fn = "nig_step64_limited";
-    NIG_TRY(check_step(h, fn, actions, ld_act, step_noise, reset_noise, ld_noise, final_obs, ld_obs));
-    NIG_TRY(check_limits(h, fn));
-    const EnvLaunch *L = launch_of(h->env);
-    if (!L->step64_limited) {                     // this env's own arithmetic takes the action as float32 (as nig_step64)
-        const int A = SPECS[h->env].action_dim;
-        if (!h->act32) HIP_TRY(hipMalloc((void **)&h->act32, (size_t)A * h->lay.ld * sizeof(float)));
-        hipLaunchKernelGGL(narrow_rows_kernel, dim3(grid_for(h->B)), dim3(BLOCK), 0, (hipStream_t)stream, actions, ld_act,
-                           h->act32, h->lay.ld, A, h->B);
-        HIP_TRY(hipGetLastError());
-        return nig_step_limited(h, h->act32, h->lay.ld, step_noise, reset_noise, ld_noise, reward_out, reward64_out, flags_out,
-                                xflags_out, final_obs, ld_obs, stream);
-    }
-    StepLimArgs q;
-    memset(&q, 0, sizeof q);
-    q.p = next_step_args(h, ld_act, step_noise, reset_noise, ld_noise, reward_out, reward64_out, flags_out, final_obs, ld_obs);
-    q.p.actions64 = actions;
-    limit_args(h, xflags_out, q.p, q.l);
-    L->step64_limited(q, step_noise || reset_noise, grid_for(h->B), (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    return NIG_OK;
-}
 
 // ---- fused rollout ---------------------------------------------------------------------------------------------------------
 // What nig_rollout / nig_rollout_sampled / nig_rollout_noise (and nig_rollout_mixed_obs, per segment) ask for
@@ -1102,14 +1297,14 @@ int nig_rollout_policy(nig_handle *h, int32_t n_steps, float *reward_out, uint32
                        float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
                        int64_t act_step_stride, void *stream)
 {
-    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_policy: bad argument");
-    NIG_TRY(refuse_limited(h, "nig_rollout_policy"));
-    if (!h->has_policy) return fail(NIG_ERR_INVALID, "nig_rollout_policy: no policy installed (nig_set_policy)");
-    NIG_TRY(closed_loop<PolicyArgs>(h, "nig_rollout_policy", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](PolicyArgs &q) {
-        policy_fields(h, q);
-        return launch_of(h->env)->policy;
-    }));
-    return ring_check(h, (hipStream_t)stream, "nig_rollout_policy");      // (the one closed loop with cooperating-wave forms)
+    return rollout_policy<false>(h, "nig_rollout_policy", n_steps, {CLOSED_LOOP_OUT}, stream);
+}
+
+int nig_rollout_policy_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                               float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
+                               int64_t act_step_stride, uint32_t *xflags_out, void *stream)
+{
+    return rollout_policy<true>(h, "nig_rollout_policy_limited", n_steps, {CLOSED_LOOP_OUT, xflags_out}, stream);
 }
 
 // nig_set_mlp_policy / _safety / _ensemble: `count` operand-stream images of `floats` floats, back to back, network k (in_dim -> 256 ->
@@ -1155,13 +1350,14 @@ int nig_rollout_mlp(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t 
                     float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
                     void *stream)
 {
-    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp: bad argument");
-    NIG_TRY(refuse_limited(h, "nig_rollout_mlp"));
-    if (!h->mlp_stream || !launch_of(h->env)->mlp) return fail(NIG_ERR_INVALID, "nig_rollout_mlp: no actor installed (nig_set_mlp_policy)");
-    return closed_loop<MlpArgs>(h, "nig_rollout_mlp", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpArgs &q) {
-        q.wstream = h->mlp_stream;
-        return launch_of(h->env)->mlp;
-    });
+    return rollout_mlp<false>(h, "nig_rollout_mlp", n_steps, {CLOSED_LOOP_OUT}, stream);
+}
+
+int nig_rollout_mlp_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                            float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
+                            uint32_t *xflags_out, void *stream)
+{
+    return rollout_mlp<true>(h, "nig_rollout_mlp_limited", n_steps, {CLOSED_LOOP_OUT, xflags_out}, stream);
 }
 
 // ---- the actor on the bf16 matrix unit ("nig-mlp-bf16-v1", include/nig.h) ----
@@ -1199,41 +1395,9 @@ int nig_rollout_mlp_bf16(nig_handle *h, int32_t n_steps, float *reward_out, uint
     if (!launch_of(h->env)->mlp_bf16) return refuse(fn, "env shape not supported (even state dim, at most 16 actions)", NIG_ERR_UNSUPPORTED);
     if (!h->mlp_bf16_stream) return refuse(fn, "no bf16 actor installed (nig_set_mlp_policy_bf16)");
     if (hid_out && (ld_hid < h->B || ld_hid > NIG_MAX_PITCH || hid_step_stride < 2 * (int64_t)MLP_H * ld_hid)) return refuse(fn, "bad hidden-activation pitch");
-    return closed_loop<MlpBf16Args>(h, fn, n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpBf16Args &q) {
+    return closed_loop<false, MlpBf16Args>(h, fn, n_steps, {CLOSED_LOOP_OUT}, stream, launch_of(h->env)->mlp_bf16, [&](MlpBf16Args &q) {
         q.m.wstream = h->mlp_bf16_stream;
         q.hid_out = hid_out; q.ld_hid = (uint32_t)ld_hid; q.hid_step_stride = (uint64_t)hid_step_stride;
-        return launch_of(h->env)->mlp_bf16;
-    });
-}
-
-// the closed loops under the added constraints: the twins' prerequisites and checks, then the limits beside their arguments
-int nig_rollout_policy_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
-                               float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
-                               int64_t act_step_stride, uint32_t *xflags_out, void *stream)
-{
-    const char *const fn = "nig_rollout_policy_limited";
-    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
-    if (!h->has_policy) return refuse(fn, "no policy installed (nig_set_policy)");
-    NIG_TRY(check_limits(h, fn));
-    return closed_loop<PolicyLimArgs>(h, fn, n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](PolicyLimArgs &q) {
-        policy_fields(h, q.p);
-        limit_args(h, xflags_out, q.p.s, q.l);
-        return launch_of(h->env)->policy_limited;
-    });
-}
-
-int nig_rollout_mlp_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
-                            float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
-                            uint32_t *xflags_out, void *stream)
-{
-    const char *const fn = "nig_rollout_mlp_limited";
-    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
-    if (!h->mlp_stream || !launch_of(h->env)->mlp) return refuse(fn, "no actor installed (nig_set_mlp_policy)");
-    NIG_TRY(check_limits(h, fn));
-    return closed_loop<MlpLimArgs>(h, fn, n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpLimArgs &q) {
-        q.m.wstream = h->mlp_stream;
-        limit_args(h, xflags_out, q.m.s, q.l);
-        return launch_of(h->env)->mlp_limited;
     });
 }
 
@@ -1253,32 +1417,28 @@ int nig_rollout_mlp_safe(nig_handle *h, int32_t n_steps, float *reward_out, uint
                          float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
                          float *prob_out, void *stream)
 {
-    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_safe: bad argument");
-    NIG_TRY(refuse_limited(h, "nig_rollout_mlp_safe"));
-    if (!launch_of(h->env)->mlp_shield) return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_mlp_safe: env shape has no MFMA actor");
-    if (!h->mlp_stream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_safe: no actor installed (nig_set_mlp_policy)");
-    if (!h->mlp_cstream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_safe: no safety critic installed (nig_set_mlp_safety)");
-    return closed_loop<MlpShieldArgs>(h, "nig_rollout_mlp_safe", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpShieldArgs &q) {
-        shield_fields(h, prob_out, q);
-        return launch_of(h->env)->mlp_shield;
-    });
+    return rollout_mlp_safe<false>(h, "nig_rollout_mlp_safe", n_steps, {CLOSED_LOOP_OUT}, prob_out, stream);
+}
+
+int nig_rollout_mlp_safe_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                                 float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
+                                 float *prob_out, uint32_t *xflags_out, void *stream)
+{
+    return rollout_mlp_safe<true>(h, "nig_rollout_mlp_safe_limited", n_steps, {CLOSED_LOOP_OUT, xflags_out}, prob_out, stream);
 }
 
 int nig_rollout_mlp_search(nig_handle *h, int32_t n_steps, int32_t n_candidates, float *reward_out, uint32_t *flags_out, int64_t out_stride,
                            float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
                            float *prob_out, float *risk_out, int32_t *choice_out, void *stream)
 {
-    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_search: bad argument");
-    NIG_TRY(refuse_limited(h, "nig_rollout_mlp_search"));
-    if (!launch_of(h->env)->mlp_search) return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_mlp_search: env shape has no MFMA actor");
-    if (n_candidates < 1 || n_candidates > NIG_MAX_CANDIDATES) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_search: n_candidates outside 1 .. NIG_MAX_CANDIDATES");
-    if (!h->mlp_stream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_search: no actor installed (nig_set_mlp_policy)");
-    if (!h->mlp_cstream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_search: no safety critic installed (nig_set_mlp_safety)");
-    return closed_loop<MlpSearchArgs>(h, "nig_rollout_mlp_search", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpSearchArgs &q) {
-        shield_fields(h, prob_out, q.sh);
-        q.n_candidates = n_candidates; q.risk_out = risk_out; q.choice_out = choice_out;
-        return launch_of(h->env)->mlp_search;
-    });
+    return rollout_mlp_search<false>(h, "nig_rollout_mlp_search", n_steps, n_candidates, {CLOSED_LOOP_OUT}, prob_out, risk_out, choice_out, stream);
+}
+
+int nig_rollout_mlp_search_limited(nig_handle *h, int32_t n_steps, int32_t n_candidates, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                                   float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
+                                   float *prob_out, float *risk_out, int32_t *choice_out, uint32_t *xflags_out, void *stream)
+{
+    return rollout_mlp_search<true>(h, "nig_rollout_mlp_search_limited", n_steps, n_candidates, {CLOSED_LOOP_OUT, xflags_out}, prob_out, risk_out, choice_out, stream);
 }
 
 int nig_set_mlp_ensemble(nig_handle *h, int32_t n_members, int32_t hidden, const float *const *W1, const float *const *b1,
@@ -1323,22 +1483,14 @@ int nig_rollout_mlp_ensemble(nig_handle *h, int32_t n_steps, float *reward_out, 
                              float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
                              float *unc_out, float *member_act_out, void *stream)
 {
-    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_ensemble: bad argument (handle, n_steps)");
-    NIG_TRY(refuse_limited(h, "nig_rollout_mlp_ensemble"));
-    if (!launch_of(h->env)->mlp_ensemble) return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_mlp_ensemble: env shape has no MFMA actor");
-    if (h->ens_members < 1 || !h->ens_stream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_ensemble: no ensemble installed (nig_set_mlp_ensemble)");
-    // member_act_out shares act_out's pitches: the same checks apply to it when act_out is absent
-    return closed_loop<MlpEnsArgs>(h, "nig_rollout_mlp_ensemble", n_steps,
-                                   {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out ? act_out : member_act_out, ld_act, act_step_stride},
-                                   stream, [&](MlpEnsArgs &q) {
-        q.m.act_out = act_out;
-        q.m.wstream = h->ens_stream;
-        q.n_members = h->ens_members; q.w = h->ens_w; q.wsum = h->ens_wsum; q.kf = (float)h->ens_members; q.threshold = h->ens_threshold;
-        q.unc_out = unc_out; q.member_out = member_act_out;
-        return [h](const MlpEnsArgs &e, unsigned grid, hipStream_t st) {
-            launch_of(h->env)->mlp_ensemble(h->ens_method == NIG_ENSEMBLE_AVERAGE ? ENS_AVERAGE : ENS_VOTING, e, grid, st);
-        };
-    });
+    return rollout_mlp_ensemble<false>(h, "nig_rollout_mlp_ensemble", n_steps, {CLOSED_LOOP_OUT}, unc_out, member_act_out, stream);
+}
+
+int nig_rollout_mlp_ensemble_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                                     float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
+                                     float *unc_out, float *member_act_out, uint32_t *xflags_out, void *stream)
+{
+    return rollout_mlp_ensemble<true>(h, "nig_rollout_mlp_ensemble_limited", n_steps, {CLOSED_LOOP_OUT, xflags_out}, unc_out, member_act_out, stream);
 }
 
 // ---- the safety-ensemble gate ("nig-gate-v1") ------------------------------------------------
@@ -1375,24 +1527,15 @@ int nig_rollout_mlp_gated(nig_handle *h, int32_t n_steps, float *reward_out, uin
                           float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
                           float *prob_out, float *unc_out, float *logit_out, int64_t ld_c, int64_t c_step_stride, void *stream)
 {
-    const char *const fn = "nig_rollout_mlp_gated";
-    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_gated: bad argument");
-    NIG_TRY(refuse_limited(h, "nig_rollout_mlp_gated"));
-    if (!launch_of(h->env)->mlp_gated) return refuse(fn, "env shape has no MFMA actor", NIG_ERR_UNSUPPORTED);
-    if (!h->mlp_stream) return refuse(fn, "no actor installed (nig_set_mlp_policy)");
-    if (h->gate_members < 1 || !h->gate_stream) return refuse(fn, "no safety ensemble installed (nig_set_mlp_safety_ensemble)");
-    if (prob_out || unc_out || logit_out) {
-        if (ld_c < h->B || ld_c > NIG_MAX_PITCH) return refuse(fn, "ld_c outside [batch, 2^26]");
-        if (c_step_stride < (int64_t)h->gate_outputs * ld_c) return refuse(fn, "c_step_stride smaller than one [n_outputs][ld_c] block");
-    }
-    return closed_loop<MlpGateArgs>(h, fn, n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpGateArgs &q) {
-        q.m.wstream = h->mlp_stream;
-        q.cstreams = h->gate_stream; q.n_members = h->gate_members; q.n_outputs = h->gate_outputs; q.kf = (float)h->gate_members;
-        q.temperature = h->gate_T; q.threshold = h->gate_thr; q.umax = h->gate_umax;
-        q.prob_out = prob_out; q.unc_out = unc_out; q.logit_out = logit_out;
-        q.ld_c = (uint32_t)ld_c; q.c_step_stride = (uint64_t)c_step_stride;
-        return launch_of(h->env)->mlp_gated;
-    });
+    return rollout_mlp_gated<false>(h, "nig_rollout_mlp_gated", n_steps, {CLOSED_LOOP_OUT}, prob_out, unc_out, logit_out, ld_c, c_step_stride, stream);
+}
+
+int nig_rollout_mlp_gated_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                                  float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
+                                  float *prob_out, float *unc_out, float *logit_out, int64_t ld_c, int64_t c_step_stride,
+                                  uint32_t *xflags_out, void *stream)
+{
+    return rollout_mlp_gated<true>(h, "nig_rollout_mlp_gated_limited", n_steps, {CLOSED_LOOP_OUT, xflags_out}, prob_out, unc_out, logit_out, ld_c, c_step_stride, stream);
 }
 
 // ---- the constraint projection ("nig-project-v1") ------------------------------------------
@@ -1436,28 +1579,15 @@ int nig_rollout_mlp_projected(nig_handle *h, int32_t n_steps, int32_t max_iters,
                               int64_t act_step_stride, float *prob_out, float *viol_out, int32_t *iters_out, float *grad_out,
                               int64_t ld_c, int64_t c_step_stride, void *stream)
 {
-    const char *const fn = "nig_rollout_mlp_projected";
-    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_projected: bad argument");
-    NIG_TRY(refuse_limited(h, "nig_rollout_mlp_projected"));
-    if (!launch_of(h->env)->mlp_projected) return refuse(fn, "env shape has no MFMA actor", NIG_ERR_UNSUPPORTED);
-    if (!h->mlp_stream) return refuse(fn, "no actor installed (nig_set_mlp_policy)");
-    if (h->proj_outputs < 1 || !h->proj_cstream || !h->proj_bstream) return refuse(fn, "no constraint predictor installed (nig_set_mlp_constraint)");
-    if (max_iters < 1 || max_iters > NIG_MAX_PROJECT_ITERS) return refuse(fn, "max_iters outside 1 .. NIG_MAX_PROJECT_ITERS");
-    if (!std::isfinite(step)) return refuse(fn, "step must be finite");
-    if (prob_out || viol_out) {
-        if (ld_c < h->B || ld_c > NIG_MAX_PITCH) return refuse(fn, "ld_c outside [batch, 2^26]");
-        if (c_step_stride < (int64_t)h->proj_outputs * ld_c) return refuse(fn, "c_step_stride smaller than one [n_outputs][ld_c] block");
-    }
-    if (grad_out && (ld_act < h->B || ld_act > NIG_MAX_PITCH || act_step_stride < (int64_t)SPECS[h->env].action_dim * ld_act))
-        return refuse(fn, "bad action trajectory pitch (grad_out takes act_out's)");
-    return closed_loop<MlpProjectArgs>(h, fn, n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpProjectArgs &q) {
-        q.m.wstream = h->mlp_stream;
-        q.cstream = h->proj_cstream; q.bstream = h->proj_bstream; q.n_outputs = h->proj_outputs; q.max_iters = max_iters;
-        q.threshold = h->proj_thr; q.tolerance = h->proj_tol; q.step = step;
-        q.prob_out = prob_out; q.viol_out = viol_out; q.iters_out = iters_out; q.grad_out = grad_out;
-        q.ld_c = (uint32_t)ld_c; q.c_step_stride = (uint64_t)c_step_stride;
-        return launch_of(h->env)->mlp_projected;
-    });
+    return rollout_mlp_projected<false>(h, "nig_rollout_mlp_projected", n_steps, max_iters, step, {CLOSED_LOOP_OUT}, prob_out, viol_out, iters_out, grad_out, ld_c, c_step_stride, stream);
+}
+
+int nig_rollout_mlp_projected_limited(nig_handle *h, int32_t n_steps, int32_t max_iters, float step, float *reward_out, uint32_t *flags_out,
+                                      int64_t out_stride, float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
+                                      int64_t act_step_stride, float *prob_out, float *viol_out, int32_t *iters_out, float *grad_out,
+                                      int64_t ld_c, int64_t c_step_stride, uint32_t *xflags_out, void *stream)
+{
+    return rollout_mlp_projected<true>(h, "nig_rollout_mlp_projected_limited", n_steps, max_iters, step, {CLOSED_LOOP_OUT, xflags_out}, prob_out, viol_out, iters_out, grad_out, ld_c, c_step_stride, stream);
 }
 
 // ---- sensor / actuator noise in the closed loop ("nig-disturb-v1") --------------------------
@@ -1475,190 +1605,28 @@ int nig_rollout_policy_disturbed(nig_handle *h, int32_t n_steps, float *reward_o
                                  float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
                                  int64_t act_step_stride, float *seen_out, int64_t seen_step_stride, void *stream)
 {
-    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_policy_disturbed: bad argument");
-    NIG_TRY(refuse_limited(h, "nig_rollout_policy_disturbed"));
-    if (!h->has_policy) return fail(NIG_ERR_INVALID, "nig_rollout_policy_disturbed: no policy installed (nig_set_policy)");
-    DisturbArgs d;
-    NIG_TRY(disturb_args(h, "nig_rollout_policy_disturbed", seen_out, seen_step_stride, d));
-    return closed_loop<PolicyDistArgs>(h, "nig_rollout_policy_disturbed", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](PolicyDistArgs &q) {
-        q.d = d;
-        policy_fields(h, q.p);
-        return launch_of(h->env)->policy_disturbed;
-    });
-}
-
-int nig_rollout_mlp_disturbed(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
-                              float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
-                              int64_t act_step_stride, float *seen_out, int64_t seen_step_stride, void *stream)
-{
-    if (!h || n_steps <= 0) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_disturbed: bad argument");
-    NIG_TRY(refuse_limited(h, "nig_rollout_mlp_disturbed"));
-    if (!launch_of(h->env)->mlp_disturbed) return fail(NIG_ERR_UNSUPPORTED, "nig_rollout_mlp_disturbed: env shape has no MFMA actor");
-    if (!h->mlp_stream) return fail(NIG_ERR_INVALID, "nig_rollout_mlp_disturbed: no actor installed (nig_set_mlp_policy)");
-    DisturbArgs d;
-    NIG_TRY(disturb_args(h, "nig_rollout_mlp_disturbed", seen_out, seen_step_stride, d));
-    return closed_loop<MlpDistArgs>(h, "nig_rollout_mlp_disturbed", n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpDistArgs &q) {
-        q.d = d;
-        q.m.wstream = h->mlp_stream;
-        return launch_of(h->env)->mlp_disturbed;
-    });
-}
-
-// ---- the other closed-loop families under the added constraints: the _limited twins --------------------------------------------
-// Each is its parent with the limits beside its arguments.  Order of refusals: bad argument, no limits installed (NIG_ERR_INVALID),
-// then every refusal of the parent in the parent's order, then closed_loop's argument contracts.  The Advanced pair never has
-// limits installed, so it refuses at the second step; an env without the MFMA actor refuses as the parent does.
-int nig_rollout_mlp_safe_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
-                                 float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
-                                 float *prob_out, uint32_t *xflags_out, void *stream)
-{
-    const char *const fn = "nig_rollout_mlp_safe_limited";
-    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
-    NIG_TRY(check_limits(h, fn));
-    if (!launch_of(h->env)->mlp_shield_limited) return refuse(fn, "env shape has no MFMA actor", NIG_ERR_UNSUPPORTED);
-    if (!h->mlp_stream) return refuse(fn, "no actor installed (nig_set_mlp_policy)");
-    if (!h->mlp_cstream) return refuse(fn, "no safety critic installed (nig_set_mlp_safety)");
-    return closed_loop<MlpLimited<MlpShieldArgs>>(h, fn, n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpLimited<MlpShieldArgs> &q) {
-        shield_fields(h, prob_out, q.a);
-        limit_args(h, xflags_out, q.a.m.s, q.l);
-        return launch_of(h->env)->mlp_shield_limited;
-    });
-}
-
-int nig_rollout_mlp_search_limited(nig_handle *h, int32_t n_steps, int32_t n_candidates, float *reward_out, uint32_t *flags_out, int64_t out_stride,
-                                   float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
-                                   float *prob_out, float *risk_out, int32_t *choice_out, uint32_t *xflags_out, void *stream)
-{
-    const char *const fn = "nig_rollout_mlp_search_limited";
-    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
-    NIG_TRY(check_limits(h, fn));
-    if (!launch_of(h->env)->mlp_search_limited) return refuse(fn, "env shape has no MFMA actor", NIG_ERR_UNSUPPORTED);
-    if (n_candidates < 1 || n_candidates > NIG_MAX_CANDIDATES) return refuse(fn, "n_candidates outside 1 .. NIG_MAX_CANDIDATES");
-    if (!h->mlp_stream) return refuse(fn, "no actor installed (nig_set_mlp_policy)");
-    if (!h->mlp_cstream) return refuse(fn, "no safety critic installed (nig_set_mlp_safety)");
-    return closed_loop<MlpLimited<MlpSearchArgs>>(h, fn, n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpLimited<MlpSearchArgs> &q) {
-        shield_fields(h, prob_out, q.a.sh);
-        q.a.n_candidates = n_candidates; q.a.risk_out = risk_out; q.a.choice_out = choice_out;
-        limit_args(h, xflags_out, q.a.sh.m.s, q.l);
-        return launch_of(h->env)->mlp_search_limited;
-    });
-}
-
-int nig_rollout_mlp_gated_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
-                                  float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
-                                  float *prob_out, float *unc_out, float *logit_out, int64_t ld_c, int64_t c_step_stride,
-                                  uint32_t *xflags_out, void *stream)
-{
-    const char *const fn = "nig_rollout_mlp_gated_limited";
-    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
-    NIG_TRY(check_limits(h, fn));
-    if (!launch_of(h->env)->mlp_gated_limited) return refuse(fn, "env shape has no MFMA actor", NIG_ERR_UNSUPPORTED);
-    if (!h->mlp_stream) return refuse(fn, "no actor installed (nig_set_mlp_policy)");
-    if (h->gate_members < 1 || !h->gate_stream) return refuse(fn, "no safety ensemble installed (nig_set_mlp_safety_ensemble)");
-    if (prob_out || unc_out || logit_out) {
-        if (ld_c < h->B || ld_c > NIG_MAX_PITCH) return refuse(fn, "ld_c outside [batch, 2^26]");
-        if (c_step_stride < (int64_t)h->gate_outputs * ld_c) return refuse(fn, "c_step_stride smaller than one [n_outputs][ld_c] block");
-    }
-    return closed_loop<MlpLimited<MlpGateArgs>>(h, fn, n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpLimited<MlpGateArgs> &q) {
-        q.a.m.wstream = h->mlp_stream;
-        q.a.cstreams = h->gate_stream; q.a.n_members = h->gate_members; q.a.n_outputs = h->gate_outputs; q.a.kf = (float)h->gate_members;
-        q.a.temperature = h->gate_T; q.a.threshold = h->gate_thr; q.a.umax = h->gate_umax;
-        q.a.prob_out = prob_out; q.a.unc_out = unc_out; q.a.logit_out = logit_out;
-        q.a.ld_c = (uint32_t)ld_c; q.a.c_step_stride = (uint64_t)c_step_stride;
-        limit_args(h, xflags_out, q.a.m.s, q.l);
-        return launch_of(h->env)->mlp_gated_limited;
-    });
-}
-
-int nig_rollout_mlp_projected_limited(nig_handle *h, int32_t n_steps, int32_t max_iters, float step, float *reward_out, uint32_t *flags_out,
-                                      int64_t out_stride, float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
-                                      int64_t act_step_stride, float *prob_out, float *viol_out, int32_t *iters_out, float *grad_out,
-                                      int64_t ld_c, int64_t c_step_stride, uint32_t *xflags_out, void *stream)
-{
-    const char *const fn = "nig_rollout_mlp_projected_limited";
-    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
-    NIG_TRY(check_limits(h, fn));
-    if (!launch_of(h->env)->mlp_projected_limited) return refuse(fn, "env shape has no MFMA actor", NIG_ERR_UNSUPPORTED);
-    if (!h->mlp_stream) return refuse(fn, "no actor installed (nig_set_mlp_policy)");
-    if (h->proj_outputs < 1 || !h->proj_cstream || !h->proj_bstream) return refuse(fn, "no constraint predictor installed (nig_set_mlp_constraint)");
-    if (max_iters < 1 || max_iters > NIG_MAX_PROJECT_ITERS) return refuse(fn, "max_iters outside 1 .. NIG_MAX_PROJECT_ITERS");
-    if (!std::isfinite(step)) return refuse(fn, "step must be finite");
-    if (prob_out || viol_out) {
-        if (ld_c < h->B || ld_c > NIG_MAX_PITCH) return refuse(fn, "ld_c outside [batch, 2^26]");
-        if (c_step_stride < (int64_t)h->proj_outputs * ld_c) return refuse(fn, "c_step_stride smaller than one [n_outputs][ld_c] block");
-    }
-    if (grad_out && (ld_act < h->B || ld_act > NIG_MAX_PITCH || act_step_stride < (int64_t)SPECS[h->env].action_dim * ld_act))
-        return refuse(fn, "bad action trajectory pitch (grad_out takes act_out's)");
-    return closed_loop<MlpLimited<MlpProjectArgs>>(h, fn, n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpLimited<MlpProjectArgs> &q) {
-        q.a.m.wstream = h->mlp_stream;
-        q.a.cstream = h->proj_cstream; q.a.bstream = h->proj_bstream; q.a.n_outputs = h->proj_outputs; q.a.max_iters = max_iters;
-        q.a.threshold = h->proj_thr; q.a.tolerance = h->proj_tol; q.a.step = step;
-        q.a.prob_out = prob_out; q.a.viol_out = viol_out; q.a.iters_out = iters_out; q.a.grad_out = grad_out;
-        q.a.ld_c = (uint32_t)ld_c; q.a.c_step_stride = (uint64_t)c_step_stride;
-        limit_args(h, xflags_out, q.a.m.s, q.l);
-        return launch_of(h->env)->mlp_projected_limited;
-    });
-}
-
-int nig_rollout_mlp_ensemble_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
-                                     float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,
-                                     float *unc_out, float *member_act_out, uint32_t *xflags_out, void *stream)
-{
-    const char *const fn = "nig_rollout_mlp_ensemble_limited";
-    if (!h || n_steps <= 0) return refuse(fn, "bad argument (handle, n_steps)");
-    NIG_TRY(check_limits(h, fn));
-    if (!launch_of(h->env)->mlp_ensemble_limited) return refuse(fn, "env shape has no MFMA actor", NIG_ERR_UNSUPPORTED);
-    if (h->ens_members < 1 || !h->ens_stream) return refuse(fn, "no ensemble installed (nig_set_mlp_ensemble)");
-    // member_act_out shares act_out's pitches: the same checks apply to it when act_out is absent
-    return closed_loop<MlpLimited<MlpEnsArgs>>(h, fn, n_steps,
-                                               {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out ? act_out : member_act_out, ld_act, act_step_stride},
-                                               stream, [&](MlpLimited<MlpEnsArgs> &q) {
-        q.a.m.act_out = act_out;
-        q.a.m.wstream = h->ens_stream;
-        q.a.n_members = h->ens_members; q.a.w = h->ens_w; q.a.wsum = h->ens_wsum; q.a.kf = (float)h->ens_members; q.a.threshold = h->ens_threshold;
-        q.a.unc_out = unc_out; q.a.member_out = member_act_out;
-        limit_args(h, xflags_out, q.a.m.s, q.l);
-        return [h](const MlpLimited<MlpEnsArgs> &e, unsigned grid, hipStream_t st) {
-            launch_of(h->env)->mlp_ensemble_limited(h->ens_method == NIG_ENSEMBLE_AVERAGE ? ENS_AVERAGE : ENS_VOTING, e, grid, st);
-        };
-    });
+    return rollout_policy_disturbed<false>(h, "nig_rollout_policy_disturbed", n_steps, {CLOSED_LOOP_OUT}, seen_out, seen_step_stride, stream);
 }
 
 int nig_rollout_policy_disturbed_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
                                          float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
                                          int64_t act_step_stride, float *seen_out, int64_t seen_step_stride, uint32_t *xflags_out, void *stream)
 {
-    const char *const fn = "nig_rollout_policy_disturbed_limited";
-    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
-    NIG_TRY(check_limits(h, fn));
-    if (!h->has_policy) return refuse(fn, "no policy installed (nig_set_policy)");
-    DisturbArgs d;
-    NIG_TRY(disturb_args(h, fn, seen_out, seen_step_stride, d));
-    return closed_loop<PolicyDistLimArgs>(h, fn, n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](PolicyDistLimArgs &q) {
-        q.d = d;
-        policy_fields(h, q.p);
-        limit_args(h, xflags_out, q.p.s, q.l);
-        return launch_of(h->env)->policy_disturbed_limited;
-    });
+    return rollout_policy_disturbed<true>(h, "nig_rollout_policy_disturbed_limited", n_steps, {CLOSED_LOOP_OUT, xflags_out}, seen_out, seen_step_stride, stream);
+}
+
+int nig_rollout_mlp_disturbed(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
+                              float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
+                              int64_t act_step_stride, float *seen_out, int64_t seen_step_stride, void *stream)
+{
+    return rollout_mlp_disturbed<false>(h, "nig_rollout_mlp_disturbed", n_steps, {CLOSED_LOOP_OUT}, seen_out, seen_step_stride, stream);
 }
 
 int nig_rollout_mlp_disturbed_limited(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
                                       float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act,
                                       int64_t act_step_stride, float *seen_out, int64_t seen_step_stride, uint32_t *xflags_out, void *stream)
 {
-    const char *const fn = "nig_rollout_mlp_disturbed_limited";
-    if (!h || n_steps <= 0) return refuse(fn, "bad argument");
-    NIG_TRY(check_limits(h, fn));
-    if (!launch_of(h->env)->mlp_disturbed_limited) return refuse(fn, "env shape has no MFMA actor", NIG_ERR_UNSUPPORTED);
-    if (!h->mlp_stream) return refuse(fn, "no actor installed (nig_set_mlp_policy)");
-    DisturbArgs d;
-    NIG_TRY(disturb_args(h, fn, seen_out, seen_step_stride, d));
-    return closed_loop<MlpLimited<MlpDistArgs>>(h, fn, n_steps, {reward_out, flags_out, out_stride, obs_out, obs_step_stride, act_out, ld_act, act_step_stride}, stream, [&](MlpLimited<MlpDistArgs> &q) {
-        q.a.d = d;
-        q.a.m.wstream = h->mlp_stream;
-        limit_args(h, xflags_out, q.a.m.s, q.l);
-        return launch_of(h->env)->mlp_disturbed_limited;
-    });
+    return rollout_mlp_disturbed<true>(h, "nig_rollout_mlp_disturbed_limited", n_steps, {CLOSED_LOOP_OUT, xflags_out}, seen_out, seen_step_stride, stream);
 }
 
 // ---- host-buffer entry points (small batches) -------------------------------------------------

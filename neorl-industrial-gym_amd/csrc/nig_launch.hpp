@@ -1,8 +1,10 @@
 // nig_launch.hpp -- the host side of libnig.so's kernels: the list of environments and the per-environment launch table.  An
 // env_<key>.hip instantiates the env's kernels by defining its table (NIG_DEFINE_ENV_LAUNCH); nig_api.hip reaches them through the
 // table's function pointers only.  The launchers of the kernel families with translation units of their own (sampled_, ensemble_,
-// disturbed_, search_, gated_, projected_, bf16_, limited_, limited_<family>_<key>.hip) are DECLARED here and defined in nig_launch_families.hpp, which those units alone include.  Which
-// kernel form a rollout launch takes is decided in nig_launch_plan.hpp; the functions here run its plans.
+// disturbed_, search_, gated_, projected_, bf16_, limited_, limited_<family>_<key>.hip) are DECLARED here and defined in
+// nig_launch_families.hpp, which those units alone include: one function template per kind of family, keyed by the argument-block
+// type, so that a family and its _limited twin are two instantiations of one launcher and two neighbouring slots of the table.
+// Which kernel form a rollout launch takes is decided in nig_launch_plan.hpp; the functions here run its plans.
 #pragma once
 #include "nig_kernels.hpp"
 #include "nig_launch_plan.hpp"
@@ -43,34 +45,34 @@ struct EnvLaunch {
     void (*mlp_shield)(const MlpShieldArgs &, unsigned grid, hipStream_t);   // the same with the safety-critic shield; nullptr as `mlp`
     // sampled_<key>.hip (nig_launch_families.hpp): nig_rollout_sampled
     void (*rollout_sampled)(int out_mode, const RolloutArgs &, uint32_t t0, unsigned grid, hipStream_t);
-    // ensemble_<key>.hip: nig_rollout_mlp_ensemble; nullptr as `mlp`
-    void (*mlp_ensemble)(int ens, const MlpEnsArgs &, unsigned grid, hipStream_t);
-    // disturbed_<key>.hip: nig_rollout_policy_disturbed, nig_rollout_mlp_disturbed (nullptr as `mlp`)
-    void (*policy_disturbed)(const PolicyDistArgs &, unsigned grid, hipStream_t);
-    void (*mlp_disturbed)(const MlpDistArgs &, unsigned grid, hipStream_t);
-    // search_<key>.hip: nig_rollout_mlp_search; nullptr as `mlp`
-    void (*mlp_search)(const MlpSearchArgs &, unsigned grid, hipStream_t);
-    // gated_<key>.hip: nig_rollout_mlp_gated; nullptr as `mlp`
-    void (*mlp_gated)(const MlpGateArgs &, unsigned grid, hipStream_t);
-    // projected_<key>.hip: nig_rollout_mlp_projected; nullptr as `mlp`
-    void (*mlp_projected)(const MlpProjectArgs &, unsigned grid, hipStream_t);
-    // limited_<key>.hip: nig_step_limited, nig_step64_limited (nullptr as `step64`), nig_rollout_policy_limited, nig_rollout_mlp_limited
-    // (nullptr as `mlp`); all nullptr for an env that overrides step() wholesale (the Advanced pair)
+    // The families in units of their own, each beside its twin under the added constraints (nig_<entry point>_limited; the twins
+    // of the env's own kernels come first).  An mlp_ slot is nullptr as `mlp`, step64_limited as `step64`; every _limited slot is
+    // nullptr for an env that overrides step() wholesale (the Advanced pair).
+    // limited_<key>.hip
     void (*step_limited)(const StepLimArgs &, bool parity, unsigned grid, hipStream_t);
     void (*step64_limited)(const StepLimArgs &, bool parity, unsigned grid, hipStream_t);
     void (*policy_limited)(const PolicyLimArgs &, unsigned grid, hipStream_t);
     void (*mlp_limited)(const MlpLimArgs &, unsigned grid, hipStream_t);
-    // limited_<family>_<key>.hip: the other closed-loop families under the added constraints (nig_rollout_mlp_safe_limited, _search_limited,
-    // _gated_limited, _projected_limited, _ensemble_limited, _disturbed_limited: nullptr as `mlp`; nig_rollout_policy_disturbed_limited);
-    // all nullptr for the Advanced pair
+    // limited_shield_<key>.hip
     void (*mlp_shield_limited)(const MlpLimited<MlpShieldArgs> &, unsigned grid, hipStream_t);
-    void (*mlp_search_limited)(const MlpLimited<MlpSearchArgs> &, unsigned grid, hipStream_t);
-    void (*mlp_gated_limited)(const MlpLimited<MlpGateArgs> &, unsigned grid, hipStream_t);
-    void (*mlp_projected_limited)(const MlpLimited<MlpProjectArgs> &, unsigned grid, hipStream_t);
+    // ensemble_<key>.hip, limited_ensemble_<key>.hip: nig_rollout_mlp_ensemble
+    void (*mlp_ensemble)(int ens, const MlpEnsArgs &, unsigned grid, hipStream_t);
     void (*mlp_ensemble_limited)(int ens, const MlpLimited<MlpEnsArgs> &, unsigned grid, hipStream_t);
-    void (*mlp_disturbed_limited)(const MlpLimited<MlpDistArgs> &, unsigned grid, hipStream_t);
+    // disturbed_<key>.hip, limited_disturbed_<key>.hip: nig_rollout_policy_disturbed, nig_rollout_mlp_disturbed
+    void (*policy_disturbed)(const PolicyDistArgs &, unsigned grid, hipStream_t);
     void (*policy_disturbed_limited)(const PolicyDistLimArgs &, unsigned grid, hipStream_t);
-    // bf16_<key>.hip: nig_rollout_mlp_bf16; nullptr as `mlp`
+    void (*mlp_disturbed)(const MlpDistArgs &, unsigned grid, hipStream_t);
+    void (*mlp_disturbed_limited)(const MlpLimited<MlpDistArgs> &, unsigned grid, hipStream_t);
+    // search_<key>.hip, limited_search_<key>.hip: nig_rollout_mlp_search
+    void (*mlp_search)(const MlpSearchArgs &, unsigned grid, hipStream_t);
+    void (*mlp_search_limited)(const MlpLimited<MlpSearchArgs> &, unsigned grid, hipStream_t);
+    // gated_<key>.hip, limited_gated_<key>.hip: nig_rollout_mlp_gated
+    void (*mlp_gated)(const MlpGateArgs &, unsigned grid, hipStream_t);
+    void (*mlp_gated_limited)(const MlpLimited<MlpGateArgs> &, unsigned grid, hipStream_t);
+    // projected_<key>.hip, limited_projected_<key>.hip: nig_rollout_mlp_projected
+    void (*mlp_projected)(const MlpProjectArgs &, unsigned grid, hipStream_t);
+    void (*mlp_projected_limited)(const MlpLimited<MlpProjectArgs> &, unsigned grid, hipStream_t);
+    // bf16_<key>.hip: nig_rollout_mlp_bf16
     void (*mlp_bf16)(const MlpBf16Args &, unsigned grid, hipStream_t);
 };
 
@@ -95,6 +97,7 @@ template <class Env> constexpr auto mlp_kernel(const MlpLimited<MlpSearchArgs> &
 template <class Env> constexpr auto mlp_kernel(const MlpLimited<MlpGateArgs> &) { return rollout_mlp_gated_limited_kernel<Env>; }
 template <class Env> constexpr auto mlp_kernel(const MlpLimited<MlpProjectArgs> &) { return rollout_mlp_projected_limited_kernel<Env>; }
 template <class Env> constexpr auto mlp_kernel(const MlpLimited<MlpDistArgs> &) { return rollout_mlp_disturbed_limited_kernel<Env>; }
+template <class Env> constexpr auto mlp_kernel(const MlpBf16Args &) { return rollout_mlp_bf16_kernel<Env>; }
 
 template <class Env, class Args>
 static void launch_mlp(const Args &q, unsigned grid, hipStream_t st)
@@ -256,26 +259,13 @@ static void launch_rollout_env(int out_mode, const RolloutArgs &q, uint32_t t0, 
 // unit that includes this header alone -- env_*.hip, nig_api.hip, nig_mixed.hip -- can name them (the table below does) but cannot
 // instantiate them, so the env_*.hip units hold exactly the instantiations they held before a family existed: their code objects do
 // not move by an instruction (profiles/isa_diff.py), each kernel symbol of the library lives in one code object, and the families
-// compile beside them in parallel.
+// compile beside them in parallel.  A family and its _limited twin are one launcher on two argument-block types: the type names
+// the kernel.
 template <class Env> void launch_rollout_sampled_env(int out_mode, const RolloutArgs &q, uint32_t t0, unsigned grid, hipStream_t st);
-template <class Env> void launch_mlp_ensemble_env(int ens, const MlpEnsArgs &q, unsigned grid, hipStream_t st);
-template <class Env> void launch_policy_disturbed_env(const PolicyDistArgs &q, unsigned grid, hipStream_t st);
-template <class Env> void launch_mlp_disturbed_env(const MlpDistArgs &q, unsigned grid, hipStream_t st);
-template <class Env> void launch_mlp_search_env(const MlpSearchArgs &q, unsigned grid, hipStream_t st);
-template <class Env> void launch_mlp_gated_env(const MlpGateArgs &q, unsigned grid, hipStream_t st);
-template <class Env> void launch_mlp_projected_env(const MlpProjectArgs &q, unsigned grid, hipStream_t st);
-template <class Env> void launch_step_limited_env(const StepLimArgs &q, bool parity, unsigned grid, hipStream_t st);
-template <class Env> void launch_step64_limited_env(const StepLimArgs &q, bool parity, unsigned grid, hipStream_t st);
-template <class Env> void launch_policy_limited_env(const PolicyLimArgs &q, unsigned grid, hipStream_t st);
-template <class Env> void launch_mlp_limited_env(const MlpLimArgs &q, unsigned grid, hipStream_t st);
-template <class Env> void launch_mlp_shield_limited_env(const MlpLimited<MlpShieldArgs> &q, unsigned grid, hipStream_t st);
-template <class Env> void launch_mlp_search_limited_env(const MlpLimited<MlpSearchArgs> &q, unsigned grid, hipStream_t st);
-template <class Env> void launch_mlp_gated_limited_env(const MlpLimited<MlpGateArgs> &q, unsigned grid, hipStream_t st);
-template <class Env> void launch_mlp_projected_limited_env(const MlpLimited<MlpProjectArgs> &q, unsigned grid, hipStream_t st);
-template <class Env> void launch_mlp_ensemble_limited_env(int ens, const MlpLimited<MlpEnsArgs> &q, unsigned grid, hipStream_t st);
-template <class Env> void launch_mlp_disturbed_limited_env(const MlpLimited<MlpDistArgs> &q, unsigned grid, hipStream_t st);
-template <class Env> void launch_policy_disturbed_limited_env(const PolicyDistLimArgs &q, unsigned grid, hipStream_t st);
-template <class Env> void launch_mlp_bf16_env(const MlpBf16Args &q, unsigned grid, hipStream_t st);
+template <class Env, class Args> void launch_mlp_family(const Args &q, unsigned grid, hipStream_t st);         // the MFMA families: mlp_kernel
+template <class Env, class Args> void launch_policy_family(const Args &q, unsigned grid, hipStream_t st);      // the planned policy loops
+template <class Env, class Args> void launch_ensemble_family(int ens, const Args &q, unsigned grid, hipStream_t st);
+template <class Env, bool ACT64> void launch_step_limited(const StepLimArgs &q, bool parity, unsigned grid, hipStream_t st);
 
 template <class Env>
 static void launch_policy(const PolicyArgs &q, unsigned /*grid*/, hipStream_t st)
@@ -318,25 +308,25 @@ static const EnvLaunch *env_launch_table()
         t.mlp = mlp_slot<Env>(launch_mlp<Env, MlpArgs>);
         t.mlp_shield = mlp_slot<Env>(launch_mlp<Env, MlpShieldArgs>);
         t.rollout_sampled = launch_rollout_sampled_env<Env>;
-        t.mlp_ensemble = mlp_slot<Env>(launch_mlp_ensemble_env<Env>);
-        t.policy_disturbed = launch_policy_disturbed_env<Env>;
-        t.mlp_disturbed = mlp_slot<Env>(launch_mlp_disturbed_env<Env>);
-        t.mlp_search = mlp_slot<Env>(launch_mlp_search_env<Env>);
-        t.mlp_gated = mlp_slot<Env>(launch_mlp_gated_env<Env>);
-        t.mlp_projected = mlp_slot<Env>(launch_mlp_projected_env<Env>);
-        t.mlp_bf16 = mlp_slot<Env>(launch_mlp_bf16_env<Env>);
-        if constexpr (!Env::CUSTOM_STEP) {
-            t.step_limited = launch_step_limited_env<Env>;
-            t.step64_limited = Env::HAS_ACT64 ? launch_step64_limited_env<Env> : nullptr;
-            t.policy_limited = launch_policy_limited_env<Env>;
-            t.mlp_limited = mlp_slot<Env>(launch_mlp_limited_env<Env>);
-            t.mlp_shield_limited = mlp_slot<Env>(launch_mlp_shield_limited_env<Env>);
-            t.mlp_search_limited = mlp_slot<Env>(launch_mlp_search_limited_env<Env>);
-            t.mlp_gated_limited = mlp_slot<Env>(launch_mlp_gated_limited_env<Env>);
-            t.mlp_projected_limited = mlp_slot<Env>(launch_mlp_projected_limited_env<Env>);
-            t.mlp_ensemble_limited = mlp_slot<Env>(launch_mlp_ensemble_limited_env<Env>);
-            t.mlp_disturbed_limited = mlp_slot<Env>(launch_mlp_disturbed_limited_env<Env>);
-            t.policy_disturbed_limited = launch_policy_disturbed_limited_env<Env>;
+        t.mlp_ensemble = mlp_slot<Env>(launch_ensemble_family<Env, MlpEnsArgs>);
+        t.policy_disturbed = launch_policy_family<Env, PolicyDistArgs>;
+        t.mlp_disturbed = mlp_slot<Env>(launch_mlp_family<Env, MlpDistArgs>);
+        t.mlp_search = mlp_slot<Env>(launch_mlp_family<Env, MlpSearchArgs>);
+        t.mlp_gated = mlp_slot<Env>(launch_mlp_family<Env, MlpGateArgs>);
+        t.mlp_projected = mlp_slot<Env>(launch_mlp_family<Env, MlpProjectArgs>);
+        t.mlp_bf16 = mlp_slot<Env>(launch_mlp_family<Env, MlpBf16Args>);
+        if constexpr (!Env::CUSTOM_STEP) {            // the twins: the same lines on the twin's argument block
+            t.step_limited = launch_step_limited<Env, false>;
+            t.step64_limited = Env::HAS_ACT64 ? launch_step_limited<Env, true> : nullptr;
+            t.policy_limited = launch_policy_family<Env, PolicyLimArgs>;
+            t.mlp_limited = mlp_slot<Env>(launch_mlp_family<Env, MlpLimArgs>);
+            t.mlp_shield_limited = mlp_slot<Env>(launch_mlp_family<Env, MlpLimited<MlpShieldArgs>>);
+            t.mlp_ensemble_limited = mlp_slot<Env>(launch_ensemble_family<Env, MlpLimited<MlpEnsArgs>>);
+            t.policy_disturbed_limited = launch_policy_family<Env, PolicyDistLimArgs>;
+            t.mlp_disturbed_limited = mlp_slot<Env>(launch_mlp_family<Env, MlpLimited<MlpDistArgs>>);
+            t.mlp_search_limited = mlp_slot<Env>(launch_mlp_family<Env, MlpLimited<MlpSearchArgs>>);
+            t.mlp_gated_limited = mlp_slot<Env>(launch_mlp_family<Env, MlpLimited<MlpGateArgs>>);
+            t.mlp_projected_limited = mlp_slot<Env>(launch_mlp_family<Env, MlpLimited<MlpProjectArgs>>);
         }
         return t;
     }();

@@ -822,35 +822,35 @@ __global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_shield_kernel(const MlpS
     rollout_mlp_body<Env, true>(q.m, q.cstream, q.prob_out, q.threshold);
 }
 
-// Instantiated in the env's search_*.hip translation unit only (launch_mlp_search_env).
+// Instantiated in the env's search_*.hip translation unit only (launch_mlp_family).
 template <class Env>
 __global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_search_kernel(const MlpSearchArgs q)
 {
     rollout_mlp_body<Env, true, ENS_NONE, false, true>(q.sh.m, q.sh.cstream, q.sh.prob_out, q.sh.threshold, nullptr, nullptr, &q);
 }
 
-// Instantiated in the env's gated_*.hip translation unit only (launch_mlp_gated_env).
+// Instantiated in the env's gated_*.hip translation unit only (launch_mlp_family).
 template <class Env>
 __global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_gated_kernel(const MlpGateArgs q)
 {
     rollout_mlp_body<Env, true, ENS_NONE, false, false, true>(q.m, q.cstreams, nullptr, q.threshold, nullptr, nullptr, nullptr, &q);
 }
 
-// Instantiated in the env's projected_*.hip translation unit only (launch_mlp_projected_env).
+// Instantiated in the env's projected_*.hip translation unit only (launch_mlp_family).
 template <class Env>
 __global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_projected_kernel(const MlpProjectArgs q)
 {
     rollout_mlp_body<Env, true, ENS_NONE, false, false, false, true>(q.m, q.cstream, nullptr, q.threshold, nullptr, nullptr, nullptr, nullptr, &q);
 }
 
-// ENS = ENS_AVERAGE / ENS_VOTING.  Instantiated in the env's ensemble_*.hip translation unit only (launch_mlp_ensemble_env).
+// ENS = ENS_AVERAGE / ENS_VOTING.  Instantiated in the env's ensemble_*.hip translation unit only (launch_ensemble_family).
 template <class Env, int ENS>
 __global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_ensemble_kernel(const MlpEnsArgs q)
 {
     rollout_mlp_body<Env, false, ENS>(q.m, nullptr, nullptr, 0.0f, &q);
 }
 
-// Instantiated in the env's disturbed_*.hip translation unit only (launch_mlp_disturbed_env).
+// Instantiated in the env's disturbed_*.hip translation unit only (launch_mlp_family).
 template <class Env>
 __global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_disturbed_kernel(const MlpDistArgs q)
 {
@@ -863,7 +863,7 @@ struct MlpLimArgs {
 };
 
 // The plain actor under the user's added box constraints (include/nig.h "nig-limits-v1"): step_core_limited at the body's one step
-// site, a second word per step.  Instantiated in the env's limited_*.hip translation unit only (launch_mlp_limited_env).
+// site, a second word per step.  Instantiated in the env's limited_*.hip translation unit only (launch_mlp_family).
 template <class Env>
 __global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_limited_kernel(const MlpLimArgs q)
 {

@@ -27,7 +27,7 @@ struct PolicyDistArgs {
 };
 
 // DIST: the policy acts on a disturbed observation and the plant receives a disturbed action (include/nig.h "nig-disturb-v1").
-// Instantiated in the env's disturbed_*.hip translation unit only (launch_policy_disturbed_env).
+// Instantiated in the env's disturbed_*.hip translation unit only (launch_policy_family on PolicyDistArgs).
 template <class Env>
 __global__ void __launch_bounds__(BLOCK) rollout_policy_disturbed_kernel(const PolicyDistArgs qd)
 {
@@ -45,7 +45,7 @@ struct PolicyLimArgs {
 
 // LIM: the step law is step_core_limited -- the user's added box constraints beside the built-ins (include/nig.h "nig-limits-v1")
 // -- and a second word per step, xflags, says which of them fired.  The one-wave form only, like the disturbed twin.
-// Instantiated in the env's limited_*.hip translation unit only (launch_policy_limited_env).
+// Instantiated in the env's limited_*.hip translation unit only (launch_policy_family on PolicyLimArgs).
 template <class Env>
 __global__ void __launch_bounds__(BLOCK) rollout_policy_limited_kernel(const PolicyLimArgs ql)
 {
@@ -63,7 +63,7 @@ struct PolicyDistLimArgs {
 };
 
 // DIST and LIM together: the disturbed and clipped action is the one step_core_limited checks.
-// Instantiated in the env's limited_disturbed_*.hip translation unit only (launch_policy_disturbed_limited_env).
+// Instantiated in the env's limited_disturbed_*.hip translation unit only (launch_policy_family on PolicyDistLimArgs).
 template <class Env>
 __global__ void __launch_bounds__(BLOCK) rollout_policy_disturbed_limited_kernel(const PolicyDistLimArgs qx)
 {

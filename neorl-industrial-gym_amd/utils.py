@@ -149,7 +149,7 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
     kernels check the constraints on the action the env receives; an MFMA family on an env without the MFMA actor takes the host
     loop there, whose env.step knows the constraints.  Only agents that take the host loop without added constraints take it with them."""
     limited = bool(getattr(env, "has_limits", False))
-    mfma_env = env.state_dim % 2 == 0 and env.action_dim <= 16
+    mfma_env = env.state_dim % 2 == 0 and env.action_dim <= 16        # the env shapes with the MFMA actor (has_mlp_actor)
     device_policy = hasattr(agent, "to_struct") and plain
     if plain and all(hasattr(agent, k) for k in ("agents", "weights", "ensemble_method")) and not hasattr(agent, "install"):
         # the reference's EnsembleAgent: its K actors fused into the env kernel where members and env allow it (EnsemblePolicy);
@@ -157,11 +157,11 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
         from .policies import EnsemblePolicy
         try:
             upgraded = EnsemblePolicy.from_agent(agent, device=env.device)
-            if upgraded.fusable and env.state_dim % 2 == 0 and env.action_dim <= 16:
+            if upgraded.fusable and mfma_env:
                 agent = upgraded
         except Exception:
             pass
-    ensemble = plain and hasattr(agent, "install") and getattr(agent, "fusable", False) and env.state_dim % 2 == 0 and env.action_dim <= 16
+    ensemble = plain and hasattr(agent, "install") and getattr(agent, "fusable", False) and mfma_env
     gated = ensemble and hasattr(agent, "max_uncertainty")        # SafetyEnsemblePolicy: its install() puts actor and members on the handle
     projecting = ensemble and hasattr(agent, "max_iters")         # ConstraintProjectionPolicy: install() puts actor and predictor on the handle
     # Bf16MLPPolicy (MLPPolicy.bf16()): ahead of the fused_mlp test, which its `fusable` would send to the float32 kernel.  The bf16
