@@ -681,6 +681,72 @@ int nig_rollout_mlp_search_limited(nig_handle *h, int32_t n_steps, int32_t n_can
                                    float *risk_out, int32_t *choice_out, uint32_t *xflags_out, void *stream);
 
 /*
+ * Distributional safety critic of the reference's RiskAwareCQLAgent (agents/safety_critical.py:92-110, 151-171,
+ * DistributionalSafetyCritic / compute_safety_violation_probability): an (S + A) -> 256 -> 256 -> N ReLU MLP whose
+ * softmax is a distribution over N atoms; the violation probability is its mass on the atoms that count as
+ * a violation (the reference: N = 51, linspace(-1, 1, 51) < 0: atoms 0 .. 24).
+ * The law, "nig-categorical-v1".  One lane, one (s, a); N = atoms, 2 <= N <= 64; below_mask a uint64 with bit j
+ * set where atom j counts as a violation:
+ *     z_j  = logit j of the network ([s, a]) -> 256 -> 256 -> N, j = 0 .. N-1.  Layers 1 and 2 are the shield
+ *            critic's, bit for bit.  Head column j has the summation order of the shield's one-row head (each
+ *            lane half's fma chain over the hidden rows it holds, the bias as one more k-step of B = 1 / 0,
+ *            then the one joining add): z_j is bit for bit the logit of the one-output critic (C3[:, j], c3[j]).
+ *     m    = max_j z_j                  a NaN z_j takes no part (fmaxf); rows j >= N take no part in anything
+ *     e_j  = det_expf(z_j - m)
+ *     Row j = 16 P + 4 q + i (P, q, i in 0 .. 3) belongs to group q.  With the terms of rows j >= N (and, for V,
+ *     of rows outside below_mask) replaced by +0, float32:
+ *         t_q = the left-to-right sum, from +0, of e_j over the group's 16 rows in ascending j
+ *               (4q, 4q+1, 4q+2, 4q+3, 16+4q, ..., 48+4q+3)
+ *         T   = (t_0 + t_1) + (t_2 + t_3)
+ *         v_q, V likewise over the rows of below_mask
+ *     p    = V / T                      IEEE division; T >= 1 whenever it is a number: the max term is det_expf(0) = 1
+ * (The groups are the lanes that hold the head rows after four 16-row passes of v_mfma_f32_16x16x1: lane
+ * 16 q + c holds rows 16 P + 4 q + i of env column c, so each sum runs where its terms lie and two butterfly
+ * steps join the four lanes.)
+ * Non-finite logits.  A NaN z_j gives e_j = NaN and p = NaN.  z_j = -inf is an atom of no mass: det_expf's
+ * stated domain gives exactly +0 below -104 (tests/test_detmath.py "expf.exact"; the code returns +0 for every
+ * x < -103, -inf included).  z_j = +inf gives m = +inf, e_j = det_expf(inf - inf) = NaN and p = NaN; so does
+ * every z_j = -inf (m = -inf).  A head bias c3[j] = -inf does NOT give z_j = -inf: the bias k-step multiplies
+ * it by B = 0 on the second lane half, so z_j = NaN (the one-row head's arithmetic, which the oracle restates).
+ * In the closed loops a lane whose p is not below the threshold (!(p < threshold)) counts as risky: a NaN p shields.
+ *
+ * nig_set_mlp_safety_categorical installs the critic: C1 .. c2 as nig_set_mlp_safety, C3 [hidden][atoms], c3 [atoms],
+ * row-major [in][out]; hidden must be 256.  The handle has ONE critic slot with a kind: this call and nig_set_mlp_safety
+ * replace each other (threshold included); installing an actor keeps the critic; the gate's and the projection's
+ * networks are separate and untouched.  NIG_ERR_INVALID: a NULL argument, atoms outside 2 .. 64, a mask bit >= atoms;
+ * NIG_ERR_UNSUPPORTED: another hidden width, an env shape without the MFMA actor.  A refused call changes nothing.
+ * A HIP failure while the weights are copied leaves the slot empty (kind none).
+ * nig_get_mlp_safety_kind: which critic the slot holds (NIG_SAFETY_*); -1 for a NULL handle.
+ * nig_get_mlp_safety_atoms: the installed categorical critic's atoms, 0 without one; -1 for a NULL handle.
+ *
+ * With the categorical critic installed, nig_rollout_mlp_safe, nig_rollout_mlp_search and their _limited twins run their
+ * own laws with p, p0 and p_c from "nig-categorical-v1" in place of the sigmoid; prototypes, arguments, refusals, outputs,
+ * NIG_FLAG_SHIELDED, frozen lanes and tallies are unchanged, the raw action stays nig_rollout_mlp's and the candidates
+ * "nig-search-v1"'s draws.  With the sigmoid critic installed nothing changes.
+ */
+#define NIG_SAFETY_NONE        0
+#define NIG_SAFETY_SIGMOID     1
+#define NIG_SAFETY_CATEGORICAL 2
+#define NIG_MAX_ATOMS 64
+int nig_set_mlp_safety_categorical(nig_handle *h, int32_t hidden, int32_t atoms, const float *C1, const float *c1,
+                                   const float *C2, const float *c2, const float *C3, const float *c3,
+                                   uint64_t below_mask, float threshold, void *stream);
+int nig_get_mlp_safety_kind(const nig_handle *h);
+int nig_get_mlp_safety_atoms(const nig_handle *h);
+
+/*
+ * compute_safety_violation_probability over a batch: p of "nig-categorical-v1" (and, optionally, the logits) of n
+ * caller-supplied (state, action) columns.  obs float [S][ld_obs], act float [A][ld_act] (device; the action is used as
+ * given: the reference does not clip), prob_out float [n], logit_out float [atoms][ld_logit] or NULL (ld_logit is then
+ * ignored).  A kernel of its own: it reads nothing of the handle's env state and writes none of it -- no counter, tally,
+ * generator position or state matrix changes.  n >= 1 need not be a multiple of anything; words of the outputs past column
+ * n - 1 keep their values.  NIG_ERR_INVALID (nothing launched or written): a NULL handle, obs, act or prob_out, no
+ * categorical critic installed, n < 1, or a pitch below n or above 2^26.
+ */
+int nig_mlp_violation_prob(nig_handle *h, int64_t n, const float *obs, int64_t ld_obs, const float *act, int64_t ld_act,
+                           float *prob_out, float *logit_out, int64_t ld_logit, void *stream);
+
+/*
  * Ensemble of MLP actors (agents/ensemble.py EnsembleAgent: predict, predict_with_uncertainty,
  * get_high_uncertainty_mask) fused with IndustrialEnv.step: n_members actors of nig_set_mlp_policy's
  * shape and layouts are evaluated per step by the same f32-MFMA scheme, one after the other through

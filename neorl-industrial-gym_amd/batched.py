@@ -64,6 +64,14 @@ def _mlp_weights(weights, shapes):
     return W
 
 
+def categorical_below_mask(atoms: int, v_min: float = -1.0, v_max: float = 1.0, safety_threshold: float = 0.0) -> int:
+    """The atoms of a distributional critic that count as a violation, as "nig-categorical-v1"'s mask: bit j where
+    np.linspace(v_min, v_max, atoms, dtype=float32)[j] < safety_threshold (agents/safety_critical.py:163-168; the reference's
+    51 atoms on [-1, 1] against 0: bits 0 .. 24, atom 25 is exactly 0.0)."""
+    below = np.linspace(v_min, v_max, int(atoms), dtype=np.float32) < np.float32(safety_threshold)
+    return sum(1 << j for j in range(int(atoms)) if below[j])
+
+
 class StepInfo:
     """Lazy view of the per-lane flag words of one step (the batched `info`).
 
@@ -571,6 +579,67 @@ class BatchedIndustrialEnv:
         with torch.cuda.device(self._dev_index):
             _lib.check(self._L.nig_set_mlp_safety(self._h, Hd, *[w.ctypes.data_as(C.c_void_p) for w in W],
                                                   float(threshold), self._stream()))
+
+    def set_mlp_safety_categorical(self, weights, threshold: float, below_mask=None, v_min: float = -1.0, v_max: float = 1.0,
+                                   safety_threshold: float = 0.0):
+        """Install the distributional safety critic of RiskAwareCQLAgent ((S+A)->256->256->atoms, ReLU, softmax;
+        agents/safety_critical.py DistributionalSafetyCritic) in the handle's ONE critic slot, in place of set_mlp_safety()'s:
+        weights = [(C1 [S+A,256], c1), (C2 [256,256], c2), (C3 [256,atoms], c3 [atoms])], 2 <= atoms <= 64.  p is the softmax
+        mass on the atoms of `below_mask` (an int, bit j = atom j; default: the atoms of linspace(v_min, v_max, atoms) below
+        safety_threshold -- bits 0 .. 24 for the reference's 51 atoms), the law "nig-categorical-v1" (include/nig.h).
+        rollout_mlp_safe() / rollout_mlp_search() and their _limited twins then act on this p (risky unless p < threshold);
+        violation_prob() evaluates it on any batch."""
+        D, Hd = self.state_dim + self.action_dim, 256
+        atoms = int(np.shape(weights[2][0])[-1])
+        W = _mlp_weights(weights, [(D, Hd), (Hd,), (Hd, Hd), (Hd,), (Hd, atoms), (atoms,)])
+        if below_mask is None:
+            below_mask = categorical_below_mask(atoms, v_min, v_max, safety_threshold)
+        with torch.cuda.device(self._dev_index):
+            _lib.check(self._L.nig_set_mlp_safety_categorical(self._h, Hd, atoms, *[w.ctypes.data_as(C.c_void_p) for w in W],
+                                                              int(below_mask), float(threshold), self._stream()))
+
+    @property
+    def mlp_safety_kind(self) -> int:
+        """What the critic slot holds: 0 none, 1 the sigmoid critic (set_mlp_safety), 2 the categorical one."""
+        return int(self._L.nig_get_mlp_safety_kind(self._h))
+
+    def violation_prob(self, obs, act, prob_out=None, logits_out=None, layout: str = "rows"):
+        """compute_safety_violation_probability of the installed categorical critic over a batch, on the device: p of
+        "nig-categorical-v1" for n (state, action) pairs; the action is used as given.  layout "rows": obs [n, S], act [n, A]
+        (transposed on the device first); "soa": obs [S, >=n], act [A, >=n] with unit column stride, read in place, n = the
+        pitch-free width obs.shape[1].  prob_out float32 [>=n], logits_out float32 [atoms, >=n] (optional; words past column
+        n - 1 keep their values).  A kernel of its own: no env state is read or written.  Returns p [n]."""
+        obs, act = (torch.as_tensor(x, dtype=torch.float32, device=self.device) for x in (obs, act))
+        if layout == "rows":
+            obs, act = obs.reshape(-1, self.state_dim).t().contiguous(), act.reshape(-1, self.action_dim).t().contiguous()
+        elif layout != "soa":
+            raise ValueError(f"layout is 'rows' or 'soa', not {layout!r}")
+        if obs.dim() != 2 or act.dim() != 2 or obs.shape[0] != self.state_dim or act.shape[0] != self.action_dim:
+            raise ValueError(f"obs / act must be [{self.state_dim}, n] / [{self.action_dim}, n] (layout 'soa'), got {tuple(obs.shape)} / {tuple(act.shape)}")
+        n = int(obs.shape[1])
+        if n < 1 or act.shape[1] < n or (n > 1 and (obs.stride(1) != 1 or act.stride(1) != 1)):     # (one column has no column stride)
+            raise ValueError("obs / act need n >= 1 columns of unit stride, act at least as many as obs")
+        atoms = int(self._L.nig_get_mlp_safety_atoms(self._h))          # (the handle's own: the critic may have been installed through the C ABI)
+        if prob_out is None:
+            prob_out = torch.empty(n, dtype=torch.float32, device=self.device)
+
+        def on_device(t, what):
+            if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device.type != obs.device.type
+                    or t.device.index != obs.device.index):
+                raise ValueError(f"{what} must be a float32 tensor on {self.device}")
+        on_device(prob_out, "prob_out")
+        if prob_out.dim() != 1 or prob_out.shape[0] < n or (prob_out.shape[0] > 1 and prob_out.stride(0) != 1):
+            raise ValueError(f"prob_out must be a contiguous vector of at least {n} words")
+        zp, ldz = None, 0
+        if logits_out is not None:
+            on_device(logits_out, "logits_out")
+            if logits_out.dim() != 2 or logits_out.shape[0] < atoms or logits_out.shape[1] < n or (logits_out.shape[1] > 1 and logits_out.stride(1) != 1):
+                raise ValueError(f"logits_out must be [>= {atoms} atoms, >= {n}] with unit column stride, got {tuple(logits_out.shape)}")
+            zp, ldz = C.c_void_p(logits_out.data_ptr()), max(int(logits_out.stride(0)), n)
+        with torch.cuda.device(self._dev_index):
+            _lib.check(self._L.nig_mlp_violation_prob(self._h, n, _ptr(obs), obs.stride(0), _ptr(act), act.stride(0), _ptr(prob_out),
+                                                      zp, ldz, self._stream()))
+        return prob_out[:n]
 
     def rollout_mlp_safe(self, n_steps: int, reward_out=None, flags_out=None, obs_out=None, act_out=None, prob_out=None):
         """rollout_mlp() with the safety-critic shield (predict_with_safety on the device): act_out holds the action the

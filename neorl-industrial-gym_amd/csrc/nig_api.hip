@@ -179,6 +179,9 @@ struct nig_handle {
     float *mlp_cstream = nullptr;    // device copy of the MFMA operand stream of the safety critic (owned)
     float *mlp_bf16_stream = nullptr;   // device copy of the bf16 operand image of the MLP actor (owned; nig_set_mlp_policy_bf16), BF16_STREAM_BYTES bytes
     float mlp_threshold = 0.0f;      // shield threshold of nig_rollout_mlp_safe
+    // the ONE critic slot's kind (NIG_SAFETY_*): mlp_cstream holds the sigmoid critic's image (nig_set_mlp_safety) or the categorical
+    // critic's (nig_set_mlp_safety_categorical), whose head rows 16 .. 63 lie in mlp_ctail (owned, MLP_TAIL_FLOATS floats)
+    int mlp_ckind = NIG_SAFETY_NONE; float *mlp_ctail = nullptr; int cat_atoms = 0; uint64_t cat_mask = 0;
     // nig_set_mlp_ensemble (owned): the members' operand streams back to back, MLP_STREAM_FLOATS floats each; their active weights
     // nig_set_mlp_safety_ensemble: the gate's member streams (owned), MLP_CSTREAM_FLOATS apart, and its law's parameters
     float *gate_stream = nullptr; int gate_members = 0, gate_cap = 0, gate_outputs = 0; float gate_T = 1.0f, gate_thr = 0.0f, gate_umax = 0.0f;
@@ -468,6 +471,8 @@ static PolicyArgs &shared_args(PolicyDistArgs &q) { return q.p; }
 static MlpArgs &shared_args(MlpArgs &q) { return q; }
 static PolicyArgs &shared_args(PolicyLimArgs &q) { return q.p; }
 static MlpArgs &shared_args(MlpSearchArgs &q) { return q.sh.m; }
+static MlpArgs &shared_args(MlpCatShieldArgs &q) { return q.sh.m; }
+static MlpArgs &shared_args(MlpCatSearchArgs &q) { return q.sr.sh.m; }
 template <class Args> static MlpArgs &shared_args(Args &q) { return q.m; }      // MlpShieldArgs, MlpEnsArgs, MlpDistArgs, MlpGateArgs, MlpProjectArgs, MlpBf16Args, MlpLimArgs
 static PolicyArgs &shared_args(PolicyDistLimArgs &q) { return q.p; }
 template <class Parent> static MlpArgs &shared_args(MlpLimited<Parent> &q) { return shared_args(q.a); }      // a _limited twin: its parent's
@@ -526,7 +531,7 @@ static int need_actor(const nig_handle *h, const char *fn)       // (an env with
 static int need_policy(const nig_handle *h, const char *fn) { return h->has_policy ? NIG_OK : refuse(fn, "no policy installed (nig_set_policy)"); }
 static int need_critic(const nig_handle *h, const char *fn)
 {
-    return h->mlp_cstream ? NIG_OK : refuse(fn, "no safety critic installed (nig_set_mlp_safety)");
+    return h->mlp_cstream && h->mlp_ckind != NIG_SAFETY_NONE ? NIG_OK : refuse(fn, "no safety critic installed (nig_set_mlp_safety)");
 }
 // the per-constraint rows of the gate and the projection: [n_outputs][ld_c] blocks, c_step_stride apart
 static int check_constraint_rows(const nig_handle *h, const char *fn, int n_outputs, int64_t ld_c, int64_t c_step_stride)
@@ -546,6 +551,12 @@ static void shield_fields(const nig_handle *h, float *prob_out, MlpShieldArgs &q
 {
     q.m.wstream = h->mlp_stream;
     q.cstream = h->mlp_cstream; q.prob_out = prob_out; q.threshold = h->mlp_threshold;
+}
+// the categorical critic's part of an argument block ("nig-categorical-v1"); the launchers below choose the kernel by the slot's kind
+static bool categorical(const nig_handle *h) { return h->mlp_ckind == NIG_SAFETY_CATEGORICAL; }
+static void categorical_fields(const nig_handle *h, MlpCatArgs &c)
+{
+    c.tail = h->mlp_ctail; c.below_mask = h->cat_mask; c.atoms = h->cat_atoms;
 }
 
 // ---- the families with a twin, in the order of their entry points below ---------------------------------------------------
@@ -586,6 +597,9 @@ static int rollout_mlp_safe(nig_handle *h, const char *fn, int32_t n_steps, cons
     NIG_TRY(need_actor(h, fn));
     NIG_TRY(need_critic(h, fn));
     const EnvLaunch *L = launch_of(h->env);
+    if (categorical(h))
+        return closed_loop<LIM, MlpCatShieldArgs>(h, fn, n_steps, o, stream, slot_of<LIM>(L->mlp_cat_shield, L->mlp_cat_shield_limited),
+                                                  [&](MlpCatShieldArgs &q) { shield_fields(h, prob_out, q.sh); categorical_fields(h, q.c); });
     return closed_loop<LIM, MlpShieldArgs>(h, fn, n_steps, o, stream, slot_of<LIM>(L->mlp_shield, L->mlp_shield_limited),
                                            [&](MlpShieldArgs &q) { shield_fields(h, prob_out, q); });
 }
@@ -601,6 +615,11 @@ static int rollout_mlp_search(nig_handle *h, const char *fn, int32_t n_steps, in
     NIG_TRY(need_actor(h, fn));
     NIG_TRY(need_critic(h, fn));
     const EnvLaunch *L = launch_of(h->env);
+    if (categorical(h))
+        return closed_loop<LIM, MlpCatSearchArgs>(h, fn, n_steps, o, stream, slot_of<LIM>(L->mlp_cat_search, L->mlp_cat_search_limited), [&](MlpCatSearchArgs &q) {
+            shield_fields(h, prob_out, q.sr.sh); categorical_fields(h, q.c);
+            q.sr.n_candidates = n_candidates; q.sr.risk_out = risk_out; q.sr.choice_out = choice_out;
+        });
     return closed_loop<LIM, MlpSearchArgs>(h, fn, n_steps, o, stream, slot_of<LIM>(L->mlp_search, L->mlp_search_limited), [&](MlpSearchArgs &q) {
         shield_fields(h, prob_out, q.sh);
         q.n_candidates = n_candidates; q.risk_out = risk_out; q.choice_out = choice_out;
@@ -748,6 +767,9 @@ extern "C" {
 // Still 0.8.0, for the same reason: nig_set_mlp_constraint / nig_rollout_mlp_projected ("nig-project-v1": ConstrainedIQLAgent's
 // get_safe_action -- a gradient projection of the actor's action towards the constraint predictor's feasible set).  Additive: no
 // existing kernel or entry point changed, no draw added.
+// Still 0.8.0, for the same reason: nig_set_mlp_safety_categorical / nig_get_mlp_safety_kind / nig_mlp_violation_prob
+// ("nig-categorical-v1": RiskAwareCQLAgent's distributional critic -- a softmax head of up to 64 atoms in the shield's and the search's
+// critic slot, and its violation probability over a caller's batch).  Additive: no existing kernel changed, no draw added.
 // Still 0.8.0, for the same reason: nig_set_limits / nig_get_limit_count / nig_step_limited / nig_step64_limited /
 // nig_rollout_policy_limited / nig_rollout_mlp_limited ("nig-limits-v1": box constraints added by the user, on the device).  Additive:
 // no existing kernel changed, no draw added; while limits are installed the other stepping entry points return NIG_ERR_UNSUPPORTED.
@@ -918,6 +940,7 @@ int nig_destroy(nig_handle *h)
     if (h->mlp_stream) (void)hipFree(h->mlp_stream);
     if (h->mlp_bf16_stream) (void)hipFree(h->mlp_bf16_stream);
     if (h->mlp_cstream) (void)hipFree(h->mlp_cstream);
+    if (h->mlp_ctail) (void)hipFree(h->mlp_ctail);
     if (h->ens_stream) (void)hipFree(h->ens_stream);
     if (h->ens_w) (void)hipFree(h->ens_w);
     if (h->gate_stream) (void)hipFree(h->gate_stream);
@@ -1410,6 +1433,59 @@ int nig_set_mlp_safety(nig_handle *h, int32_t hidden, const float *C1, const flo
     NIG_TRY(build_network_images(h, "nig_set_mlp_safety", hidden, S + A, 1, MLP_CSTREAM_FLOATS, 1, &C1, &c1, &C2, &c2, &C3, &c3, &host));
     NIG_TRY(upload_stream("nig_set_mlp_safety", &h->mlp_cstream, host, MLP_CSTREAM_FLOATS, stream));
     h->mlp_threshold = threshold;
+    h->mlp_ckind = NIG_SAFETY_SIGMOID;
+    return NIG_OK;
+}
+
+// ---- the distributional safety critic ("nig-categorical-v1") ------------------------------------
+int nig_set_mlp_safety_categorical(nig_handle *h, int32_t hidden, int32_t atoms, const float *C1, const float *c1, const float *C2,
+                                   const float *c2, const float *C3, const float *c3, uint64_t below_mask, float threshold, void *stream)
+{
+    const char *const fn = "nig_set_mlp_safety_categorical";
+    // (the law's own bounds first: they need no handle)
+    if (atoms < 2 || atoms > NIG_MAX_ATOMS) return refuse(fn, "atoms outside 2 .. NIG_MAX_ATOMS");
+    if (atoms < 64 && (below_mask >> atoms) != 0) return refuse(fn, "below_mask has a bit at or above atoms");
+    if (!h || !C1 || !c1 || !C2 || !c2 || !C3 || !c3) return refuse(fn, "NULL argument");
+    if (hidden != MLP_H) return refuse(fn, "hidden must be 256 (agents/networks.py default)", NIG_ERR_UNSUPPORTED);
+    if (!launch_of(h->env)->mlp_cat_eval) return refuse(fn, "env shape not supported (even state dim, at most 16 actions)", NIG_ERR_UNSUPPORTED);
+    const int S = SPECS[h->env].state_dim, A = SPECS[h->env].action_dim;
+    float *host = (float *)calloc(MLP_CSTREAM_FLOATS, sizeof(float)), *tail = (float *)calloc(MLP_TAIL_FLOATS, sizeof(float));
+    if (!host || !tail || !put_network_wide(S + A, atoms, C1, c1, C2, c2, C3, c3, host, MLP_CSTREAM_FLOATS, tail)) {
+        free(host); free(tail);
+        return refuse(fn, "out of host memory, or the operand stream does not fit its image");
+    }
+    // Both uploads overwrite device arrays the installed critic may be using, so a HIP failure in either leaves no critic at all: a
+    // slot of kind none refuses every rollout and evaluation, where a half-replaced critic would compute with mixed weights.
+    const int rc_tail = upload_stream(fn, &h->mlp_ctail, tail, MLP_TAIL_FLOATS, stream);
+    const int rc = rc_tail ? (free(host), rc_tail) : upload_stream(fn, &h->mlp_cstream, host, MLP_CSTREAM_FLOATS, stream);
+    if (rc) { h->mlp_ckind = NIG_SAFETY_NONE; return rc; }
+    h->mlp_threshold = threshold;
+    h->cat_atoms = atoms; h->cat_mask = below_mask;
+    h->mlp_ckind = NIG_SAFETY_CATEGORICAL;
+    return NIG_OK;
+}
+
+int nig_get_mlp_safety_kind(const nig_handle *h) { return h ? h->mlp_ckind : -1; }
+int nig_get_mlp_safety_atoms(const nig_handle *h) { return h ? (h->mlp_ckind == NIG_SAFETY_CATEGORICAL ? h->cat_atoms : 0) : -1; }
+
+int nig_mlp_violation_prob(nig_handle *h, int64_t n, const float *obs, int64_t ld_obs, const float *act, int64_t ld_act,
+                           float *prob_out, float *logit_out, int64_t ld_logit, void *stream)
+{
+    const char *const fn = "nig_mlp_violation_prob";
+    if (!h || !obs || !act || !prob_out) return refuse(fn, "NULL argument");
+    if (!categorical(h) || !h->mlp_cstream || !h->mlp_ctail) return refuse(fn, "no categorical critic installed (nig_set_mlp_safety_categorical)");
+    if (n < 1) return refuse(fn, "n < 1");
+    if (ld_obs < n || ld_obs > NIG_MAX_PITCH || ld_act < n || ld_act > NIG_MAX_PITCH) return refuse(fn, "ld_obs / ld_act outside [n, 2^26]");
+    if (logit_out && (ld_logit < n || ld_logit > NIG_MAX_PITCH)) return refuse(fn, "ld_logit outside [n, 2^26]");
+    MlpCatEvalArgs q;
+    memset(&q, 0, sizeof q);
+    // the body's view of a batch: its "state rows" are the caller's observations, read and never written (CAT_EVAL)
+    q.sh.m.s.state = const_cast<float *>(obs); q.sh.m.s.ld_state = (uint32_t)ld_obs; q.sh.m.s.B = (uint32_t)n;
+    q.sh.cstream = h->mlp_cstream; q.sh.prob_out = prob_out;
+    categorical_fields(h, q.c);
+    q.c.act = act; q.c.ld_act = (uint32_t)ld_act; q.c.logit_out = logit_out; q.c.ld_logit = (uint32_t)ld_logit;
+    launch_of(h->env)->mlp_cat_eval(q, (unsigned)((n + BLOCK / 2 - 1) / (BLOCK / 2)), (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
     return NIG_OK;
 }
 

@@ -1,7 +1,7 @@
 // nig_launch.hpp -- the host side of libnig.so's kernels: the list of environments and the per-environment launch table.  An
 // env_<key>.hip instantiates the env's kernels by defining its table (NIG_DEFINE_ENV_LAUNCH); nig_api.hip reaches them through the
 // table's function pointers only.  The launchers of the kernel families with translation units of their own (sampled_, ensemble_,
-// disturbed_, search_, gated_, projected_, bf16_, limited_, limited_<family>_<key>.hip) are DECLARED here and defined in
+// disturbed_, search_, gated_, projected_, bf16_, categorical_, limited_, limited_<family>_<key>.hip) are DECLARED here and defined in
 // nig_launch_families.hpp, which those units alone include: one function template per kind of family, keyed by the argument-block
 // type, so that a family and its _limited twin are two instantiations of one launcher and two neighbouring slots of the table.
 // Which kernel form a rollout launch takes is decided in nig_launch_plan.hpp; the functions here run its plans.
@@ -74,6 +74,13 @@ struct EnvLaunch {
     void (*mlp_projected_limited)(const MlpLimited<MlpProjectArgs> &, unsigned grid, hipStream_t);
     // bf16_<key>.hip: nig_rollout_mlp_bf16
     void (*mlp_bf16)(const MlpBf16Args &, unsigned grid, hipStream_t);
+    // categorical_<key>.hip, limited_categorical_<key>.hip ("nig-categorical-v1"): what nig_rollout_mlp_safe / _search and their
+    // twins launch when the handle's critic is the distributional one, and nig_mlp_violation_prob's kernel
+    void (*mlp_cat_shield)(const MlpCatShieldArgs &, unsigned grid, hipStream_t);
+    void (*mlp_cat_shield_limited)(const MlpLimited<MlpCatShieldArgs> &, unsigned grid, hipStream_t);
+    void (*mlp_cat_search)(const MlpCatSearchArgs &, unsigned grid, hipStream_t);
+    void (*mlp_cat_search_limited)(const MlpLimited<MlpCatSearchArgs> &, unsigned grid, hipStream_t);
+    void (*mlp_cat_eval)(const MlpCatEvalArgs &, unsigned grid, hipStream_t);
 };
 
 template <class Env>
@@ -98,6 +105,11 @@ template <class Env> constexpr auto mlp_kernel(const MlpLimited<MlpGateArgs> &) 
 template <class Env> constexpr auto mlp_kernel(const MlpLimited<MlpProjectArgs> &) { return rollout_mlp_projected_limited_kernel<Env>; }
 template <class Env> constexpr auto mlp_kernel(const MlpLimited<MlpDistArgs> &) { return rollout_mlp_disturbed_limited_kernel<Env>; }
 template <class Env> constexpr auto mlp_kernel(const MlpBf16Args &) { return rollout_mlp_bf16_kernel<Env>; }
+template <class Env> constexpr auto mlp_kernel(const MlpCatShieldArgs &) { return rollout_mlp_cat_shield_kernel<Env>; }
+template <class Env> constexpr auto mlp_kernel(const MlpCatSearchArgs &) { return rollout_mlp_cat_search_kernel<Env>; }
+template <class Env> constexpr auto mlp_kernel(const MlpLimited<MlpCatShieldArgs> &) { return rollout_mlp_cat_shield_limited_kernel<Env>; }
+template <class Env> constexpr auto mlp_kernel(const MlpLimited<MlpCatSearchArgs> &) { return rollout_mlp_cat_search_limited_kernel<Env>; }
+template <class Env> constexpr auto mlp_kernel(const MlpCatEvalArgs &) { return mlp_violation_prob_kernel<Env>; }
 
 template <class Env, class Args>
 static void launch_mlp(const Args &q, unsigned grid, hipStream_t st)
@@ -315,6 +327,9 @@ static const EnvLaunch *env_launch_table()
         t.mlp_gated = mlp_slot<Env>(launch_mlp_family<Env, MlpGateArgs>);
         t.mlp_projected = mlp_slot<Env>(launch_mlp_family<Env, MlpProjectArgs>);
         t.mlp_bf16 = mlp_slot<Env>(launch_mlp_family<Env, MlpBf16Args>);
+        t.mlp_cat_shield = mlp_slot<Env>(launch_mlp_family<Env, MlpCatShieldArgs>);
+        t.mlp_cat_search = mlp_slot<Env>(launch_mlp_family<Env, MlpCatSearchArgs>);
+        t.mlp_cat_eval = mlp_slot<Env>(launch_mlp_family<Env, MlpCatEvalArgs>);
         if constexpr (!Env::CUSTOM_STEP) {            // the twins: the same lines on the twin's argument block
             t.step_limited = launch_step_limited<Env, false>;
             t.step64_limited = Env::HAS_ACT64 ? launch_step_limited<Env, true> : nullptr;
@@ -327,6 +342,8 @@ static const EnvLaunch *env_launch_table()
             t.mlp_search_limited = mlp_slot<Env>(launch_mlp_family<Env, MlpLimited<MlpSearchArgs>>);
             t.mlp_gated_limited = mlp_slot<Env>(launch_mlp_family<Env, MlpLimited<MlpGateArgs>>);
             t.mlp_projected_limited = mlp_slot<Env>(launch_mlp_family<Env, MlpLimited<MlpProjectArgs>>);
+            t.mlp_cat_shield_limited = mlp_slot<Env>(launch_mlp_family<Env, MlpLimited<MlpCatShieldArgs>>);
+            t.mlp_cat_search_limited = mlp_slot<Env>(launch_mlp_family<Env, MlpLimited<MlpCatSearchArgs>>);
         }
         return t;
     }();

@@ -1,6 +1,7 @@
 // nig_mlp.hpp -- the fused MLP actor on MFMA with its safety-critic shield and its ensemble (device code only): MlpArgs,
-// MlpShieldArgs, MlpEnsArgs, MlpDistArgs, MlpSearchArgs, MlpGateArgs, MlpProjectArgs, MlpLimArgs, MlpLimited<>, rollout_mlp_body and its
-// eight kernels with their _limited twins.
+// MlpShieldArgs, MlpEnsArgs, MlpDistArgs, MlpSearchArgs, MlpGateArgs, MlpProjectArgs, MlpCatArgs, MlpLimArgs, MlpLimited<>,
+// rollout_mlp_body and its eight kernels with their _limited twins, the distributional critic's kernels (the shield and the search on a
+// 64-row softmax head, and the stand-alone evaluator).
 #pragma once
 #include <type_traits>
 #include "nig_step.hpp"
@@ -207,14 +208,99 @@ struct MlpProjectArgs {
     uint32_t ld_c; uint64_t c_step_stride;
 };
 
-template <class Env, bool SHIELD, int ENS = ENS_NONE, bool DIST = false, bool SEARCH = false, bool GATE = false, bool PROJECT = false, bool LIMITS = false>
+// Distributional safety critic (agents/safety_critical.py RiskAwareCQLAgent.compute_safety_violation_probability; include/nig.h
+// "nig-categorical-v1"): CAT is the shield's (and the search's) form with a head of up to 64 rows and a softmax across them in
+// place of the sigmoid.  Layers 1 and 2 are the critic pass as it stands.  The head is four 16-row passes of v_mfma_f32_16x16x1
+// per hidden register, their four accumulators (MlpCatHead) held across the eight layer-2 tiles: every column keeps the one-row
+// head's two fma chains and joining add.  Pass 0's operands are the chunk's 16 head records (put_network's 16-row head), so the
+// chunk slot, the double buffer and two blocks per CU stay as they are; the operands of passes 1 .. 3 come from the image's tail
+// in global memory (put_network_wide: 16 bytes per lane and hidden register, 129 KiB a network, L2-resident and shared by every
+// block), through a ring of MLP_CAT_RING entries whose first loads are issued ahead of the tile's 129 layer-2 MFMAs.  No chunk
+// barrier is added and the fill chain is the shield's.
+// After the last tile lane 16 q + c holds, for the two env columns 16 beta + c, the 16 logits of rows 16 P + 4 q + i (P: pass,
+// i: register) -- the softmax runs where they lie (categorical_prob): the lane's own 16 rows in row order, then the four lanes
+// of a column by two butterfly steps (xor 16, xor 32), which is the law's fixed order ((q0 + q1) + (q2 + q3)).
+constexpr int CAT_NONE = 0, CAT_LOOP = 1, CAT_EVAL = 2;   // no categorical critic; in the closed loop; the stand-alone evaluator (nig_mlp_violation_prob)
+constexpr int MLP_CAT_RING = 4;
+// Experiment builds only (profiles/mkvariant.sh, profiles/categorical/parts.txt; never libnig.so): -DNIG_CAT_PARTS=1 replaces the tail's
+// global loads by zero operands (the MFMAs stay), 2 replaces the softmax by a plain sum of the 64 accumulator registers, 3 both -- what each part costs.
+#ifndef NIG_CAT_PARTS
+#define NIG_CAT_PARTS 0
+#endif
+struct MlpCatHead { f32x16 p[MLP_WIDE_PASSES]; };
+struct MlpCatArgs {
+    const float *tail;          // put_network_wide's tail: rows 16 .. 63 of the head
+    uint64_t below_mask;        // bit j: atom j counts as a violation
+    int atoms;                  // N, 2 .. 64
+    // the evaluator alone (the closed loops leave them zero):
+    const float *act;           // [A][ld_act] the actions as given
+    float *logit_out;           // [atoms][ld_logit], may be NULL
+    uint32_t ld_act, ld_logit;
+};
+struct MlpCatShieldArgs { MlpShieldArgs sh; MlpCatArgs c; };
+struct MlpCatSearchArgs { MlpSearchArgs sr; MlpCatArgs c; };
+struct MlpCatEvalArgs { MlpShieldArgs sh; MlpCatArgs c; };     // sh.m.s.state / ld_state / B: the observations [S][ld_obs] and n; sh.prob_out: [n]
+
+// p of "nig-categorical-v1" from the four head accumulators, for the env of this lane (both lane halves).  Whole wave, EXEC all
+// ones.  STORE: the logits leave from the lanes that hold them (env column lane0 + 16 beta + c, where it is below n).
+template <bool STORE>
+__device__ __forceinline__ float categorical_prob(const MlpCatHead &h, const MlpCatArgs &cq, unsigned lane, [[maybe_unused]] uint32_t lane0, [[maybe_unused]] uint32_t n)
+{
+    const int q4 = 4 * (int)(lane >> 4);
+    if constexpr ((NIG_CAT_PARTS & 2) != 0) {                // (every accumulator register stays live, so no head MFMA is removed with the softmax)
+        float sum = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 64; ++k) sum = sum + h.p[k >> 4][k & 15];
+        return sum;
+    }
+    float pb[2];
+#pragma unroll
+    for (int beta = 0; beta < 2; ++beta) {
+        float z[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) z[k] = h.p[k >> 2][4 * beta + (k & 3)] + h.p[k >> 2][8 + 4 * beta + (k & 3)];    // the two chains' joining add
+        float m = -__builtin_inff();
+#pragma unroll
+        for (int k = 0; k < 16; ++k) m = (16 * (k >> 2) + q4 + (k & 3)) < cq.atoms ? fmaxf(m, z[k]) : m;
+        m = fmaxf(m, __shfl_xor(m, 16));
+        m = fmaxf(m, __shfl_xor(m, 32));
+        float t = 0.0f, v = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const int j = 16 * (k >> 2) + q4 + (k & 3);
+            const float ej = det_expf(z[k] - m);
+            t = t + (j < cq.atoms ? ej : 0.0f);
+            v = v + ((j < cq.atoms && ((cq.below_mask >> j) & 1ull)) ? ej : 0.0f);
+        }
+        t = t + __shfl_xor(t, 16);
+        v = v + __shfl_xor(v, 16);
+        t = t + __shfl_xor(t, 32);
+        v = v + __shfl_xor(v, 32);
+        pb[beta] = v / t;
+        if constexpr (STORE) {
+            const uint32_t col = lane0 + 16u * (uint32_t)beta + (lane & 15u);
+            if (cq.logit_out && col < n) {
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    const int j = 16 * (k >> 2) + q4 + (k & 3);
+                    if (j < cq.atoms) (cq.logit_out + (size_t)j * cq.ld_logit)[col] = z[k];
+                }
+            }
+        }
+    }
+    // (after the two butterfly steps every lane 16 q + c holds p of both columns c and 16 + c: the lane's own env is one of them)
+    return ((lane >> 4) & 1u) ? pb[1] : pb[0];
+}
+
+template <class Env, bool SHIELD, int ENS = ENS_NONE, bool DIST = false, bool SEARCH = false, bool GATE = false, bool PROJECT = false, bool LIMITS = false, int CAT = CAT_NONE>
 __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const MlpArgs &q, const float *cstream, float *prob_out, float threshold,
                                                                        [[maybe_unused]] const MlpEnsArgs *eq = nullptr,
                                                                        [[maybe_unused]] const DisturbArgs *dq = nullptr,
                                                                        [[maybe_unused]] const MlpSearchArgs *sq = nullptr,
                                                                        [[maybe_unused]] const MlpGateArgs *gq = nullptr,
                                                                        [[maybe_unused]] const MlpProjectArgs *jq = nullptr,
-                                                                       [[maybe_unused]] const LimitArgs *lq = nullptr)
+                                                                       [[maybe_unused]] const LimitArgs *lq = nullptr,
+                                                                       [[maybe_unused]] const MlpCatArgs *cq = nullptr)
 {
     // LIMITS combines with every other form (the _limited twins at the end of this header): the added constraints live at the one step site
     static_assert(!PROJECT || (SHIELD && !SEARCH && !GATE), "the projection is a form of the shield; it excludes the search and the gate");
@@ -222,6 +308,8 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
     static_assert(!SEARCH || SHIELD, "the search is a form of the shield");
     static_assert(!GATE || (SHIELD && !SEARCH), "the gate is a form of the shield; it has no searching twin");
     static_assert(!DIST || (!SHIELD && ENS == ENS_NONE), "the shield and the ensemble have no disturbed form");
+    static_assert(CAT == CAT_NONE || (SHIELD && !GATE && !PROJECT), "the categorical critic is a form of the shield and of the search");
+    static_assert(CAT != CAT_EVAL || (!SEARCH && !LIMITS), "the evaluator steps no env");
     // the env steps on the ensemble's float64 action where its NumPy arithmetic follows the action's type (nig_step64's rule)
     constexpr bool ACT64 = ENS == ENS_AVERAGE && Env::HAS_ACT64;
     using act_t = std::conditional_t<ACT64, double, float>;
@@ -253,7 +341,9 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
     const bool autoreset = (p.hflags & NIG_F_AUTORESET) != 0;
     const bool tally = p.tally != nullptr;
 
-    uint32_t ctr = in_range ? p.ctr[li] : (uint32_t)NIG_CTR_DONE;
+    uint32_t ctr;
+    if constexpr (CAT == CAT_EVAL) ctr = in_range ? 0u : (uint32_t)NIG_CTR_DONE;      // (the evaluator has no handle state: p.state is the caller's obs)
+    else ctr = in_range ? p.ctr[li] : (uint32_t)NIG_CTR_DONE;
     float s[S], a[A], n[S];
     typename Env::fast_noise_t nz[KSN];
 #pragma unroll
@@ -339,6 +429,17 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
         float ring[RING];
 #pragma unroll
         for (int j = 0; j < RING; ++j) ring[j] = wb[j * 64];
+        // the 64-row head: this tile's entries of the tail (rows 16 .. 63), from global memory ahead of the layer-2 MFMAs
+        constexpr bool WIDE = std::is_same_v<decltype(out), MlpCatHead>;
+        [[maybe_unused]] f32x4 gring[MLP_CAT_RING];
+        [[maybe_unused]] const f32x4 *gt = nullptr;
+        if constexpr (WIDE) {
+            gt = (const f32x4 *)cq->tail + (size_t)(tiles - 1) * (16 * 64) + lane;
+#pragma unroll
+            for (int j = 0; j < MLP_CAT_RING; ++j) {
+                if constexpr ((NIG_CAT_PARTS & 1) != 0) gring[j] = f32x4{0, 0, 0, 0}; else gring[j] = gt[j * 64];
+            }
+        }
 #pragma unroll
         for (int i = 0; i < MLP_PER; ++i) {
             const float aop = ring[i % RING];
@@ -351,6 +452,16 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aop, half ? 0.0f : 1.0f, acc, 0, 0, 0);      // + bias
             } else if constexpr (std::is_same_v<decltype(out), f32x4>) {      // own value x the weights of the lane's block
                 out = __builtin_amdgcn_mfma_f32_4x4x1f32(aop, hidden(acc, i - MLP_MT * 16 - 1), out, 0, 0, 0);
+            } else if constexpr (WIDE) {                    // four 16-row passes on the one hidden value
+                const int t = i - MLP_MT * 16 - 1;
+                const float hv = hidden(acc, t);
+                const f32x4 g = gring[t % MLP_CAT_RING];
+                if constexpr ((NIG_CAT_PARTS & 1) == 0)
+                    if (t + MLP_CAT_RING < 16 + 1) gring[t % MLP_CAT_RING] = gt[(t + MLP_CAT_RING) * 64];   // (+1: the bias entry behind the last tile)
+                out.p[0] = __builtin_amdgcn_mfma_f32_16x16x1f32(aop, hv, out.p[0], 0, 0, 0);
+                out.p[1] = __builtin_amdgcn_mfma_f32_16x16x1f32(g[0], hv, out.p[1], 0, 0, 0);
+                out.p[2] = __builtin_amdgcn_mfma_f32_16x16x1f32(g[1], hv, out.p[2], 0, 0, 0);
+                out.p[3] = __builtin_amdgcn_mfma_f32_16x16x1f32(g[2], hv, out.p[3], 0, 0, 0);
             } else {
                 out = __builtin_amdgcn_mfma_f32_16x16x1f32(aop, hidden(acc, i - MLP_MT * 16 - 1), out, 0, 0, 0);
             }
@@ -367,12 +478,62 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
         }
         if (tiles == MLP_MT) {                              // record 145 of the last chunk: + the head's bias
             if constexpr (std::is_same_v<decltype(out), f32x4>) out = __builtin_amdgcn_mfma_f32_4x4x1f32(ring[MLP_PER % RING], half ? 0.0f : 1.0f, out, 0, 0, 0);
+            else if constexpr (WIDE) {
+                const f32x4 g = gring[16 % MLP_CAT_RING];
+                const float one = half ? 0.0f : 1.0f;
+                out.p[0] = __builtin_amdgcn_mfma_f32_16x16x1f32(ring[MLP_PER % RING], one, out.p[0], 0, 0, 0);
+                out.p[1] = __builtin_amdgcn_mfma_f32_16x16x1f32(g[0], one, out.p[1], 0, 0, 0);
+                out.p[2] = __builtin_amdgcn_mfma_f32_16x16x1f32(g[1], one, out.p[2], 0, 0, 0);
+                out.p[3] = __builtin_amdgcn_mfma_f32_16x16x1f32(g[2], one, out.p[3], 0, 0, 0);
+            }
             else out = __builtin_amdgcn_mfma_f32_16x16x1f32(ring[MLP_PER % RING], half ? 0.0f : 1.0f, out, 0, 0, 0);
         }
         return out;
     };
-    fill(0, 0, L1.pieces);
+    if constexpr (CAT == CAT_EVAL) cfill(0, 0, C1.pieces);   // the evaluator has no actor: the critic's layer 1
+    else fill(0, 0, L1.pieces);
     int gbuf = 0;                                            // buffer that holds (or receives) the chunk consumed next
+    // The categorical critic's pass on x = [s, a, 0] -> p of "nig-categorical-v1": the shield's critic pass with the 64-row head,
+    // stated once for the closed loops and the evaluator.  `next_fill` issues what follows the last chunk (the caller's business,
+    // as in the shield); store_: the logits leave too.  (The closure exists in the categorical kernels alone: one that captures
+    // gbuf in every kernel reorders two scalar moves in all of them -- profiles/categorical/isa_diff.txt.)
+    [[maybe_unused]] auto cat_pass = [&]() __attribute__((always_inline)) { if constexpr (CAT == CAT_NONE) return 0; else
+    return [&](const auto &x, auto &&next_fill, auto store_) __attribute__((always_inline)) {
+        f32x16 g1[MLP_MT];
+        if constexpr (C1.chunks == 1) {
+            __syncthreads();                                // the critic's layer 1 is in s_w[gbuf]
+            cfill(1, gbuf ^ 1, MLP_PIECES);
+            layer1_chunk(mlp_int<MLP_MT>{}, mlp_int<C1.records>{}, x, g1, gbuf, mlp_int<ACT_RELU>{}, nullptr);
+            gbuf ^= 1;
+        } else {
+#pragma unroll
+            for (int c1 = 0; c1 < C1.chunks; ++c1) {
+                __syncthreads();                            // critic layer-1 chunk c1 is in s_w[gbuf]
+                if (c1 + 1 < C1.chunks) cfill(c1 + 1, gbuf ^ 1, C1.pieces);
+                else cfill(C1.chunks, gbuf ^ 1, MLP_PIECES);
+                layer1_chunk(mlp_int<C1.tiles>{}, mlp_int<C1.records>{}, x, g1 + c1 * C1.tiles, gbuf, mlp_int<ACT_RELU>{}, nullptr);
+                gbuf ^= 1;
+            }
+        }
+        MlpCatHead zc = {};
+        for (int m2 = 0; m2 < MLP_MT; ++m2) {
+            __syncthreads();                                // critic chunk C1.chunks + m2 is in s_w[gbuf]
+            if (m2 + 1 < MLP_MT) cfill(C1.chunks + 1 + m2, gbuf ^ 1, MLP_PIECES);
+            else next_fill();
+            zc = layer2_chunk(g1, zc, m2 + 1, gbuf, mlp_int<ACT_RELU>{}, nullptr);
+            gbuf ^= 1;
+        }
+        return categorical_prob<decltype(store_)::value != 0>(zc, *cq, lane, lane0, p.B);
+    }; }();
+    if constexpr (CAT == CAT_EVAL) {
+        // ---------------- nig_mlp_violation_prob: one pass on the caller's (state, action) columns, no env ----------------
+#pragma unroll
+        for (int j = 0; j < A; ++j) a[j] = in_range ? (cq->act + (size_t)j * cq->ld_act)[li] : 0.0f;
+        auto x = [&](int k) __attribute__((always_inline)) { return k < S ? s[k] : (k < S + A ? a[k - S] : 0.0f); };
+        const float pv = cat_pass(x, [] {}, mlp_int<1>{});
+        if (writer && prob_out) prob_out[li] = pv;
+        return;
+    }
     const int n_members = ENS != ENS_NONE ? eq->n_members : 1;
     [[maybe_unused]] bool d_obs = false, d_act = false;
     if constexpr (DIST) disturb_switches<S, A>(*dq, d_obs, d_act);
@@ -598,6 +759,19 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
                 if constexpr (SEARCH) return k < S ? s[k] : (k < S + A ? (s_cand < 0 ? a[k - S] : s_u[k - S]) : 0.0f);
                 else return k < S ? s[k] : (k < S + A ? a[k - S] : 0.0f);
             };
+            if constexpr (CAT != CAT_NONE) {                       // the distributional critic: the same pass, p from the softmax of its 64-row head
+                prob = cat_pass(x, [&]() __attribute__((always_inline)) {
+                    if constexpr (SEARCH) {                        // (the search's fill chain, below)
+                        if (s_cand >= 0) {
+                            if (s_cand + 1 < s_passes) cfill(0, gbuf ^ 1, C1.pieces);
+                            else if (it + 1 < q.n_steps) fill(0, gbuf ^ 1, L1.pieces);
+                        }
+                    }
+                    else if (it + 1 < q.n_steps) fill(0, gbuf ^ 1, L1.pieces);
+                }, mlp_int<0>{});
+            } else {
+            // (The sigmoid critic's pass.  cat_pass above restates its layer-1 and layer-2 loops on purpose -- moving these lines into a
+            // routine both share changes the existing kernels' instructions -- so the two must change together.)
             f32x16 g1[MLP_MT];
             // (one chunk: the actor's lines; two: a loop.  Only so do all eight shield kernels keep the parent's registers and
             // scratch -- with a one-trip loop, or with the two chunks spelled out, some spill more: profiles/mlp_network/isa_diff.txt)
@@ -659,6 +833,7 @@ __device__ __attribute__((always_inline)) inline void rollout_mlp_body(const Mlp
                 }
             }
             else prob = det_sigmoidf(z4[0] + __shfl_xor(z4[0], 32));
+            }
             if constexpr (SEARCH) {
                 if (s_cand < 0) {
                     s_best = prob;
@@ -914,6 +1089,39 @@ template <class Env>
 __global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_disturbed_limited_kernel(const MlpLimited<MlpDistArgs> q)
 {
     rollout_mlp_body<Env, false, ENS_NONE, true, false, false, false, true>(q.a.m, nullptr, nullptr, 0.0f, nullptr, &q.a.d, nullptr, nullptr, nullptr, &q.l);
+}
+
+// The distributional critic's kernels ("nig-categorical-v1").  Instantiated in the env's categorical_*.hip /
+// limited_categorical_*.hip translation units only (launch_mlp_family).
+template <class Env>
+__global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_cat_shield_kernel(const MlpCatShieldArgs q)
+{
+    rollout_mlp_body<Env, true, ENS_NONE, false, false, false, false, false, CAT_LOOP>(q.sh.m, q.sh.cstream, q.sh.prob_out, q.sh.threshold, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &q.c);
+}
+
+template <class Env>
+__global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_cat_search_kernel(const MlpCatSearchArgs q)
+{
+    rollout_mlp_body<Env, true, ENS_NONE, false, true, false, false, false, CAT_LOOP>(q.sr.sh.m, q.sr.sh.cstream, q.sr.sh.prob_out, q.sr.sh.threshold, nullptr, nullptr, &q.sr, nullptr, nullptr, nullptr, &q.c);
+}
+
+template <class Env>
+__global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_cat_shield_limited_kernel(const MlpLimited<MlpCatShieldArgs> q)
+{
+    rollout_mlp_body<Env, true, ENS_NONE, false, false, false, false, true, CAT_LOOP>(q.a.sh.m, q.a.sh.cstream, q.a.sh.prob_out, q.a.sh.threshold, nullptr, nullptr, nullptr, nullptr, nullptr, &q.l, &q.a.c);
+}
+
+template <class Env>
+__global__ void __launch_bounds__(BLOCK, 2) rollout_mlp_cat_search_limited_kernel(const MlpLimited<MlpCatSearchArgs> q)
+{
+    rollout_mlp_body<Env, true, ENS_NONE, false, true, false, false, true, CAT_LOOP>(q.a.sr.sh.m, q.a.sr.sh.cstream, q.a.sr.sh.prob_out, q.a.sr.sh.threshold, nullptr, nullptr, &q.a.sr, nullptr, nullptr, &q.l, &q.a.c);
+}
+
+// nig_mlp_violation_prob: the pass alone, on the caller's columns
+template <class Env>
+__global__ void __launch_bounds__(BLOCK, 2) mlp_violation_prob_kernel(const MlpCatEvalArgs q)
+{
+    rollout_mlp_body<Env, true, ENS_NONE, false, false, false, false, false, CAT_EVAL>(q.sh.m, q.sh.cstream, q.sh.prob_out, q.sh.threshold, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &q.c);
 }
 
 }  // namespace nig

@@ -88,4 +88,37 @@ inline bool put_network(int IN, int OUT, const float *W1, const float *b1, const
     return true;
 }
 
+// ---- a head of up to 64 rows ("nig-categorical-v1", include/nig.h): four 16-row passes of the v_mfma_f32_16x16x1 head ----
+// Pass 0 (rows 0 .. 15) is the 16-row head of put_network, in the chunks, so the image keeps the 148-record slot and every
+// existing image its bytes.  Passes 1 .. 3 (rows 16 .. 63) do not travel through LDS: they lie in a TAIL of their own that the
+// lanes read from global memory, one 16-byte entry per lane and hidden register.  Entry e = 16 m2 + t of lane l holds the words
+// (pass 1, pass 2, pass 3, 0) = W3[32 m2 + mfma_row(t, l >> 5)][16 P + (l & 15)], zero for rows >= OUT; entry MLP_H / 2 holds the
+// head's bias b3[16 P + (l & 15)] in the same words (B = 1 on lane half 0, 0 on half 1, as the chunk's bias record).
+constexpr int MLP_WIDE_ROWS = 64, MLP_WIDE_PASSES = MLP_WIDE_ROWS / 16;
+constexpr int MLP_TAIL_ENTRIES = MLP_MT * 16 + 1;                      // 129 entries of 64 lanes x 4 floats
+constexpr int MLP_TAIL_FLOATS = MLP_TAIL_ENTRIES * 64 * 4;             // 129 KiB
+
+// The image of the network IN -> 256 -> 256 -> OUT, 2 <= OUT <= 64 (W3 [256][OUT], row-major): put_network's image of the network
+// whose head is columns 0 .. 15 of W3 (zero-padded to 16: the 16 x 16 x 1 layout whatever OUT is) into host[floats], and the tail
+// of columns 16 .. 63 into the zeroed tail[MLP_TAIL_FLOATS].
+inline bool put_network_wide(int IN, int OUT, const float *W1, const float *b1, const float *W2, const float *b2, const float *W3,
+                             const float *b3, float *host, size_t floats, float *tail)
+{
+    if (OUT < 2 || OUT > MLP_WIDE_ROWS) return false;
+    float W16[MLP_H * 16], b16[16];                         // (16 KiB of stack on the host's set-up path)
+    for (int k = 0; k < MLP_H; ++k)
+        for (int i = 0; i < 16; ++i) W16[k * 16 + i] = i < OUT ? W3[(size_t)k * OUT + i] : 0.0f;
+    for (int i = 0; i < 16; ++i) b16[i] = i < OUT ? b3[i] : 0.0f;
+    if (!put_network(IN, 16, W1, b1, W2, b2, W16, b16, host, floats)) return false;
+    for (int e = 0; e < MLP_TAIL_ENTRIES; ++e)
+        for (int l = 0; l < 64; ++l)
+            for (int P = 1; P < MLP_WIDE_PASSES; ++P) {
+                const int row = 16 * P + (l & 15);
+                float v = 0.0f;
+                if (row < OUT) v = e < MLP_MT * 16 ? W3[(size_t)(32 * (e / 16) + mfma_row(e % 16, l >> 5)) * OUT + row] : b3[row];
+                tail[((size_t)e * 64 + l) * 4 + (P - 1)] = v;
+            }
+    return true;
+}
+
 }  // namespace nig

@@ -232,6 +232,14 @@ def search_candidates(seed: int, env_index: int, t: int, n_candidates: int, acti
     return ((w >> np.uint32(8)).astype(f32) * f32(2.0 ** -23) - f32(1.0)).astype(f32)
 
 
+def categorical_mass(logits, below):
+    """The softmax mass of logits [n, N] on the atoms of the bool mask `below` [N], in torch: exp(z - max z) summed over the
+    mask / over all atoms -- "nig-categorical-v1"'s formula (include/nig.h) without its summation order or its det_expf."""
+    import torch
+    e = torch.exp(logits - logits.max(dim=1, keepdim=True).values)
+    return (e * below.to(e.dtype)).sum(dim=1) / e.sum(dim=1)
+
+
 def pad_critic(weights, hidden: int = 256):
     """A critic [(C1 [D,h], c1 [h]), (C2 [h,h], c2 [h]), (C3 [h,1], c3 [1])] with h <= hidden (the reference's RiskEstimator:
     128) as the `hidden`-wide network set_mlp_safety() takes: C1's columns, C2's rows and columns, C3's rows and the biases
@@ -364,10 +372,17 @@ class MLPPolicy:
     `safety_weights` (optional) = the agents' SafetyCritic, [(C1 [S+A,H], c1), (C2 [H,H], c2), (C3 [H,1], c3)]
     (networks.py:147-169), with `constraint_threshold` (base.py: 0.1): predict_with_safety() follows
     cql.py:354-394, and shielded() is the policy that acts with it (fused into the env kernel by
-    evaluate_with_safety when both nets have the reference shape)."""
+    evaluate_with_safety when both nets have the reference shape).
+
+    safety_kind="categorical": `safety_weights` is the DistributionalSafetyCritic of RiskAwareCQLAgent instead
+    (agents/safety_critical.py:92-110), [(C1 [S+A,H], c1), (C2 [H,H], c2), (C3 [H,N], c3 [N])] with 2 <= N <= 64 atoms, and p is
+    its softmax mass on the atoms of `below_mask` (an int, bit j = atom j; default: linspace(-1, 1, N) < 0, the reference's
+    compute_safety_violation_probability) -- the law "nig-categorical-v1" (include/nig.h).  Every method that scores with p
+    (predict_with_safety, get_safe_action, shielded(), searching()) then scores with that p."""
     is_trained = True
 
-    def __init__(self, weights, device="cuda:0", safety_weights=None, constraint_threshold: float = 0.1):
+    def __init__(self, weights, device="cuda:0", safety_weights=None, constraint_threshold: float = 0.1, safety_kind: str = "sigmoid",
+                 below_mask=None):
         import torch
         self.device = torch.device(device)
         self.layers = [(torch.as_tensor(np.asarray(W), dtype=torch.float32, device=self.device).contiguous(),
@@ -382,28 +397,56 @@ class MLPPolicy:
         self.constraint_threshold = float(constraint_threshold)
         self.safety_weights = None
         self.safety_layers = None
+        if safety_kind not in ("sigmoid", "categorical"):
+            raise ValueError(f"safety_kind is 'sigmoid' or 'categorical', not {safety_kind!r}")
+        self.safety_kind, self.below_mask = safety_kind, None
         if safety_weights is not None:
             self.safety_weights = [(np.asarray(W, dtype=f32).reshape(np.shape(W)[0], -1), np.asarray(b, dtype=f32).reshape(-1))
                                    for W, b in safety_weights]
-            if self.safety_weights[0][0].shape[0] != self.state_dim + self.action_dim or self.safety_weights[-1][0].shape[1] != 1:
+            n_out = self.safety_weights[-1][0].shape[1]
+            if safety_kind == "categorical":
+                from .batched import categorical_below_mask
+                if self.safety_weights[0][0].shape[0] != self.state_dim + self.action_dim or not 2 <= n_out <= _lib.MAX_ATOMS:
+                    raise ValueError(f"distributional safety critic must map S+A={self.state_dim + self.action_dim} inputs to 2 .. "
+                                     f"{_lib.MAX_ATOMS} atoms, got {[w.shape for w, _ in self.safety_weights]}")
+                self.below_mask = categorical_below_mask(n_out) if below_mask is None else int(below_mask)
+                if self.below_mask >> n_out:
+                    raise ValueError(f"below_mask {self.below_mask:#x} has a bit at or above the {n_out} atoms")
+                self._below = torch.as_tensor([(self.below_mask >> j) & 1 for j in range(n_out)], dtype=torch.bool, device=self.device)
+            elif self.safety_weights[0][0].shape[0] != self.state_dim + self.action_dim or n_out != 1:
                 raise ValueError(f"safety critic must map S+A={self.state_dim + self.action_dim} inputs to 1 output, got "
                                  f"{[w.shape for w, _ in self.safety_weights]}")
             self.safety_layers = [(torch.as_tensor(W, device=self.device).contiguous(), torch.as_tensor(b, device=self.device).contiguous())
                                   for W, b in self.safety_weights]
 
     @classmethod
-    def from_agent(cls, agent, device="cuda:0", critic: str = "safety"):
+    def from_agent(cls, agent, device="cuda:0", critic: str = "safety", below_mask=None):
         """The actor (and, when the agent has one, the safety critic with the agent's constraint_threshold) of a
         reference agent: agent.state["actor"].params / agent.state["safety"].params, Flax trees
         {"params": {"MLP_0": {"Dense_0|1|2": {"kernel", "bias"}}}} (any nested mapping of array-likes).  LayerNorm
         networks are refused (ValueError); Dropout has no parameters and is inert at training=False.
         critic="risk": the critic is the RiskEstimator of the safety-critical agents (agents/safety_critical.py:113-149),
         agent.risk_state.params = {"params": {"layers_0", "layers_1", "risk_head"}} (modules built in setup), with
-        agent.uncertainty_threshold as the threshold -- what get_safe_action / searching() score with."""
-        if critic not in ("safety", "risk"):
-            raise ValueError(f"critic is 'safety' or 'risk', not {critic!r}")
+        agent.uncertainty_threshold as the threshold -- what get_safe_action / searching() score with.
+        critic="distributional": the critic is the same agents' DistributionalSafetyCritic (safety_critical.py:92-110),
+        agent.safety_state.params = {"params": {"layers_0", "layers_1", "value_head"}} with agent.distributional_atoms atoms
+        (checked against the head), scored by compute_safety_violation_probability's softmax mass ("nig-categorical-v1";
+        below_mask: the atoms that count, default the reference's linspace(-1, 1, atoms) < 0), agent.uncertainty_threshold
+        as the threshold."""
+        if critic not in ("safety", "risk", "distributional"):
+            raise ValueError(f"critic is 'safety', 'risk' or 'distributional', not {critic!r}")
         state = agent.state
         actor = _dense_layers(state["actor"].params, "actor")
+        if critic == "distributional":
+            ss = getattr(agent, "safety_state", None)
+            if ss is None or getattr(ss, "params", None) is None:
+                raise ValueError("critic='distributional' needs agent.safety_state.params (a RiskAwareCQLAgent's DistributionalSafetyCritic)")
+            layers = _named_layers(ss.params, ("layers_0", "layers_1", "value_head"), "distributional safety critic")
+            atoms = getattr(agent, "distributional_atoms", None)
+            if atoms is not None and int(atoms) != np.shape(layers[-1][0])[-1]:
+                raise ValueError(f"agent.distributional_atoms = {atoms}, but the value head has {np.shape(layers[-1][0])[-1]} columns")
+            return cls(actor, device=device, safety_weights=layers, constraint_threshold=getattr(agent, "uncertainty_threshold", 0.1),
+                       safety_kind="categorical", below_mask=below_mask)
         if critic == "risk":
             rs = getattr(agent, "risk_state", None)
             if rs is None or getattr(rs, "params", None) is None:
@@ -444,7 +487,9 @@ class MLPPolicy:
         return safety_threshold or self.constraint_threshold           # cql.py:384 (0.0 / None fall back)
 
     def safety_probs_device(self, obs, actions):
-        """p = sigmoid(critic([obs, actions])), [n] (networks.py:147-169)."""
+        """p = sigmoid(critic([obs, actions])), [n] (networks.py:147-169); with the categorical critic the softmax mass on the
+        atoms of below_mask (safety_critical.py:151-171): "nig-categorical-v1"'s formula in torch's arithmetic -- max-shifted
+        exponentials, V / T -- not its bits."""
         import torch
         if self.safety_layers is None:
             raise RuntimeError("Safety critic must be trained")
@@ -453,7 +498,32 @@ class MLPPolicy:
             x = torch.addmm(b, x, W)
             if i + 1 < len(self.safety_layers):
                 x = torch.relu(x)
+        if self.safety_kind == "categorical":
+            return categorical_mass(x, self._below)
         return torch.sigmoid(x[:, 0])
+
+    def compute_safety_violation_probability(self, state, action, env=None):
+        """RiskAwareCQLAgent.compute_safety_violation_probability over a batch (the categorical critic; with the sigmoid critic,
+        its p).  With `env` a BatchedIndustrialEnv whose shape has the MFMA actor and a critic of the reference's width, the
+        critic is installed there and evaluated by the device kernel (env.violation_prob, "nig-categorical-v1" bit for bit);
+        otherwise by the torch form.  state [n, S] / [S], action [n, A] / [A]; returns a NumPy array [n] (a float for one pair)."""
+        import torch
+        if self.safety_layers is None:
+            raise RuntimeError("Safety critic must be trained")
+        o = torch.as_tensor(np.asarray(state, dtype=f32), device=self.device)
+        single = o.dim() == 1
+        o = o.reshape(-1, self.state_dim)
+        a = torch.as_tensor(np.asarray(action, dtype=f32), device=self.device).reshape(-1, self.action_dim)
+        sw = self.safety_weights
+        on_device = (env is not None and self.safety_kind == "categorical" and env.state_dim % 2 == 0 and env.action_dim <= 16
+                     and len(sw) == 3 and sw[0][0].shape[1] == 256 and sw[1][0].shape == (256, 256))
+        if on_device:
+            env.set_mlp_safety_categorical(sw, self.constraint_threshold, self.below_mask)
+            p = env.violation_prob(o, a)
+        else:
+            p = self.safety_probs_device(o, a)
+        p = p.cpu().numpy()
+        return float(p[0]) if single else p
 
     def predict_with_safety_device(self, obs, safety_threshold=None):
         """predict_with_safety on device tensors: (actions [n, A], probs [n])."""
@@ -549,8 +619,13 @@ class SearchShieldPolicy:
         self.weights = base.weights
         sw = base.safety_weights
         h = sw[0][0].shape[1]
-        self.fusable = base.fusable and len(sw) == 3 and h <= 256 and sw[1][0].shape == (h, h)
-        self.safety_weights = pad_critic(sw) if self.fusable else sw        # what set_mlp_safety takes
+        self.safety_kind, self.below_mask = base.safety_kind, base.below_mask
+        if self.safety_kind == "categorical":      # the reference's DistributionalSafetyCritic is 256 wide: no padding
+            self.fusable = base.fusable and len(sw) == 3 and h == 256 and sw[1][0].shape == (h, h)
+            self.safety_weights = sw                                        # what set_mlp_safety_categorical takes
+        else:
+            self.fusable = base.fusable and len(sw) == 3 and h <= 256 and sw[1][0].shape == (h, h)
+            self.safety_weights = pad_critic(sw) if self.fusable else sw    # what set_mlp_safety takes
 
     def predict_device(self, obs):
         return self.base.get_safe_action_device(obs, None, self.n_candidates, self.threshold)[0]
@@ -570,6 +645,7 @@ class ShieldedMLPPolicy:
         self.threshold = float(threshold)
         self.state_dim, self.action_dim = base.state_dim, base.action_dim
         self.weights, self.safety_weights = base.weights, base.safety_weights
+        self.safety_kind, self.below_mask = base.safety_kind, base.below_mask
         sw = base.safety_weights
         self.fusable = base.fusable and len(sw) == 3 and sw[0][0].shape[1] == 256 and sw[1][0].shape == (256, 256)
 

@@ -194,7 +194,10 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
         env.set_mlp_policy(agent.weights)
         if shielded:        # MLPPolicy.shielded() / searching(): actor + safety critic + shield in the same kernel
             from .policies import pad_critic
-            env.set_mlp_safety(pad_critic(agent.safety_weights), agent.threshold)
+            if getattr(agent, "safety_kind", "sigmoid") == "categorical":      # the distributional critic ("nig-categorical-v1"): the same
+                env.set_mlp_safety_categorical(agent.safety_weights, agent.threshold, agent.below_mask)   # rollouts, p from its softmax
+            else:
+                env.set_mlp_safety(pad_critic(agent.safety_weights), agent.threshold)
         device_policy = True
     rollout = None
     if device_policy:
