@@ -582,6 +582,51 @@ int nig_rollout_mlp_bf16(nig_handle *h, int32_t n_steps, float *reward_out, uint
 int nig_bf16_from_f32(const float *x, uint16_t *out, int64_t n);
 
 /*
+ * The float32 MFMA actor for the other hidden shapes of the reference's agents (hidden_dims of CQLAgent, IQLAgent, TD3BCAgent; the
+ * tuner sweeps (128,128) (256,256) (512,256) (256,256,256) (512,512)): two or three ReLU hidden layers of 1 .. 512 units and the
+ * tanh head.  The kernel family "nig-mlp-shape-v1", reached through nig_rollout_mlp, which runs whichever actor the handle holds.
+ *
+ * Shape classes.  A network is zero-padded (zero weight rows and columns, zero biases) to the class that holds it with the fewest
+ * 32x32x2 MFMAs per step; padding changes no value (a padded unit is relu(0), and fma(w, 0, c) == c), only the sign of a zero:
+ *   "128x128"      two hidden layers, both <= 128                        4, 4 tiles of 32 units
+ *   reference      two hidden layers, both <= 256, not in "128x128"      nig_set_mlp_policy's image and kernel, padded to 256 x 256
+ *   "512x256"      two hidden layers, H1 <= 512, H2 <= 256               16, 8 tiles
+ *   "512x512"      two hidden layers, both <= 512                        16, 16 tiles
+ *   "256x256x256"  three hidden layers, all <= 256                       8, 8, 8 tiles
+ * More than three hidden layers, a width above 512 and LayerNorm are outside every class.
+ *
+ * The law, for one lane and one step on state s[0..S) and the PADDED network (the arithmetic of the padded network is the law):
+ *   layer 1   z_u = the float32 fma chain over k = 0 .. S-1 in natural order, from 0: c = fma(W1[k][u], s_k, c), two inputs per MFMA
+ *             k-step applied as fma(a1, b1, fma(a0, b0, c)); then the bias, c = fma(b1_u, 1, c) (and fma(0, 0, c));
+ *             h_u = fmaxf(z_u, 0).
+ *   layer n   (every later hidden layer) the same chain over the units of the layer below in the order of the accumulator
+ *             registers that hold them: for tile kt = 0, 1, .. and register t = 0 .. 15 the pair (k0, k1) =
+ *             (32 kt + rho_0(t), 32 kt + rho_1(t)), rho_h(t) = (t & 3) + 8 (t >> 2) + 4 h, applied as
+ *             c = fma(W[k1][u], h_k1, fma(W[k0][u], h_k0, c)); the bias comes last; h_u = fmaxf(z_u, 0).
+ *   head      row j is two chains, one per lane half h, each over the units 32 kt + rho_h(t) of the last hidden layer in (kt, t) order
+ *             from 0, c_h = fma(W_head[k][j], h_k, c_h); the bias rides behind half 0's chain (c_0 = fma(b_j, 1, c_0), c_1 =
+ *             fma(b_j, 0, c_1)); z_j = c_0 + c_1; a_j = det_tanhf(z_j), the project's tanh.
+ *   the step  the env then steps on that action exactly as in nig_rollout_mlp: shared code.
+ * For (256, 256) this text is what nig_rollout_mlp computes with nig_set_mlp_policy's actor (the oracle's mlp_actor).
+ *
+ * nig_set_mlp_policy_dims: n_hidden in 2 .. 3 hidden widths `hidden`, and n_hidden + 1 layers W[i] ([in][out] row-major, unpadded)
+ * and b[i] as host pointers.  The library pads, builds the image, uploads it and records the class on the handle.  The handle has ONE
+ * actor slot with a kind: nig_set_mlp_policy, and a _dims call whose class is the reference, fill it with nig_set_mlp_policy's image
+ * (bit for bit the image of the padded arrays); every other class fills it with the shaped image; either call replaces the other's
+ * actor.  The critic, ensemble, bf16 and limits slots are untouched.  NIG_ERR_UNSUPPORTED on an env without the MFMA actor;
+ * NIG_ERR_INVALID for n_hidden outside 2 .. 3, a width outside 1 .. 512, a shape no class holds, a NULL pointer.
+ * nig_rollout_mlp dispatches on the slot's kind: prototype, checks, outputs, frozen lanes, tallies and counter are the same.  While
+ * a SHAPED actor is installed every other entry point that reads the actor slot (nig_rollout_mlp_safe, _search, _gated, _projected,
+ * _disturbed and every _limited twin, nig_rollout_mlp_limited included) returns NIG_ERR_UNSUPPORTED with nothing launched or
+ * written and the handle unchanged: those families on other shapes are later work.
+ * nig_get_mlp_policy_dims: n_hidden of the installed actor and its (unpadded) widths in hidden[0 .. n_hidden) (an actor of
+ * nig_set_mlp_policy reports 2 and 256, 256); 0 without one; -1 for NULL.
+ */
+int nig_set_mlp_policy_dims(nig_handle *h, int32_t n_hidden, const int32_t *hidden, const float *const *W,
+                            const float *const *b, void *stream);
+int nig_get_mlp_policy_dims(const nig_handle *h, int32_t *hidden /* [3] */);
+
+/*
  * nig_rollout_policy / nig_rollout_mlp under the installed limits ("nig-limits-v1", nig_set_limits): every argument and
  * refusal as the twin's, plus xflags_out uint32 [n_steps][>= B] (row k at xflags_out + k * out_stride; may be NULL; a frozen
  * lane's word is 0).  NIG_ERR_INVALID without installed limits.  With limits that no state can violate (infinite bounds)

@@ -547,6 +547,31 @@ class BatchedIndustrialEnv:
         with torch.cuda.device(self._dev_index):
             _lib.check(self._L.nig_set_mlp_policy(self._h, Hd, *[w.ctypes.data_as(C.c_void_p) for w in W], self._stream()))
 
+    def set_mlp_policy_dims(self, weights):
+        """Install an actor of any hidden shape a shape class holds ("nig-mlp-shape-v1", include/nig.h: two or three ReLU hidden
+        layers of 1 .. 512 units, tanh head) for rollout_mlp(): weights = [(W1 [S,h1], b1), .., (W_head [h_last,A], b_head)], host
+        arrays, [in, out], unpadded -- the library pads to the class.  Fills the ONE actor slot set_mlp_policy() fills: either
+        call replaces the other's actor.  While a class other than the reference's is installed, every other closed loop that
+        reads the actor (safe, search, gated, projected, disturbed, the _limited twins) refuses with code 4."""
+        ws = [(np.ascontiguousarray(W, dtype=np.float32), np.ascontiguousarray(np.asarray(b, dtype=np.float32).reshape(-1))) for W, b in weights]
+        n_hidden = len(ws) - 1
+        ins = [self.state_dim] + [W.shape[1] for W, _ in ws[:-1]]
+        outs = [W.shape[1] for W, _ in ws[:-1]] + [self.action_dim]
+        if n_hidden < 1 or any(W.shape != (i, o) or b.shape != (o,) for (W, b), i, o in zip(ws, ins, outs)):
+            raise ValueError(f"actor layers must chain {self.state_dim} -> .. -> {self.action_dim}, got {[W.shape for W, _ in ws]}")
+        hidden = (C.c_int32 * max(n_hidden, 1))(*outs[:-1])
+        Wp = (C.c_void_p * len(ws))(*[W.ctypes.data for W, _ in ws])
+        bp = (C.c_void_p * len(ws))(*[b.ctypes.data for _, b in ws])
+        with torch.cuda.device(self._dev_index):
+            _lib.check(self._L.nig_set_mlp_policy_dims(self._h, n_hidden, hidden, Wp, bp, self._stream()))
+
+    @property
+    def mlp_policy_dims(self):
+        """The hidden widths of the installed actor (set_mlp_policy: (256, 256)), () without one."""
+        hidden = (C.c_int32 * 3)()
+        n = self._L.nig_get_mlp_policy_dims(self._h, hidden)
+        return tuple(int(hidden[i]) for i in range(max(n, 0)))
+
     def rollout_mlp(self, n_steps: int, reward_out=None, flags_out=None, obs_out=None, act_out=None):
         """Closed loop with the installed MLP actor evaluated by f32 MFMA inside the env kernel
         (same outputs as rollout_policy)."""

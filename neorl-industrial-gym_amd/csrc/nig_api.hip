@@ -178,6 +178,10 @@ struct nig_handle {
     float *mlp_stream = nullptr;     // device copy of the MFMA operand stream of the MLP actor (owned)
     float *mlp_cstream = nullptr;    // device copy of the MFMA operand stream of the safety critic (owned)
     float *mlp_bf16_stream = nullptr;   // device copy of the bf16 operand image of the MLP actor (owned; nig_set_mlp_policy_bf16), BF16_STREAM_BYTES bytes
+    // the ONE actor slot's kind (SHAPE_KIND_*, nig_mlp_shape_stream.hpp): mlp_stream holds the reference image (nig_set_mlp_policy, or a
+    // nig_set_mlp_policy_dims call of the reference class), mlp_shape_stream the shaped image of any other class (owned, allocated once
+    // for the env's largest class); actor_dims: the installed actor's unpadded hidden widths
+    int actor_kind = SHAPE_KIND_NONE, actor_nh = 0; int32_t actor_dims[3] = {0, 0, 0}; float *mlp_shape_stream = nullptr;
     float mlp_threshold = 0.0f;      // shield threshold of nig_rollout_mlp_safe
     // the ONE critic slot's kind (NIG_SAFETY_*): mlp_cstream holds the sigmoid critic's image (nig_set_mlp_safety) or the categorical
     // critic's (nig_set_mlp_safety_categorical), whose head rows 16 .. 63 lie in mlp_ctail (owned, MLP_TAIL_FLOATS floats)
@@ -524,9 +528,16 @@ static int need_mfma_actor(const nig_handle *h, const char *fn)
 {
     return launch_of(h->env)->mlp ? NIG_OK : refuse(fn, "env shape has no MFMA actor", NIG_ERR_UNSUPPORTED);
 }
+static bool shaped_actor(const nig_handle *h) { return h->actor_kind > SHAPE_KIND_REFERENCE; }
+// the families that run the 256 x 256 actor only ask this right after their bad-argument check ("nig-mlp-shape-v1")
+static int refuse_shaped(const nig_handle *h, const char *fn)
+{
+    return shaped_actor(h) ? refuse(fn, "a shaped actor is installed (nig_set_mlp_policy_dims): this entry point runs the 256 x 256 actor only", NIG_ERR_UNSUPPORTED) : NIG_OK;
+}
 static int need_actor(const nig_handle *h, const char *fn)       // (an env without the MFMA actor never has one: nig_set_mlp_policy refuses)
 {
-    return h->mlp_stream ? NIG_OK : refuse(fn, "no actor installed (nig_set_mlp_policy)");
+    NIG_TRY(refuse_shaped(h, fn));
+    return h->actor_kind == SHAPE_KIND_REFERENCE ? NIG_OK : refuse(fn, "no actor installed (nig_set_mlp_policy)");
 }
 static int need_policy(const nig_handle *h, const char *fn) { return h->has_policy ? NIG_OK : refuse(fn, "no policy installed (nig_set_policy)"); }
 static int need_critic(const nig_handle *h, const char *fn)
@@ -576,11 +587,29 @@ static int rollout_policy(nig_handle *h, const char *fn, int32_t n_steps, const 
     return LIM ? NIG_OK : ring_check(h, (hipStream_t)stream, fn);      // (the one closed loop with cooperating-wave forms)
 }
 
+// nig_rollout_mlp with a shaped actor in the slot: the class's kernel on the shaped image ("nig-mlp-shape-v1")
+static int rollout_mlp_shaped(nig_handle *h, const char *fn, int32_t n_steps, const ClosedLoopOut &o, void *stream)
+{
+    const EnvLaunch *L = launch_of(h->env);
+    auto run = [&](auto launch, auto shape) {
+        using Args = MlpShapeArgs<decltype(shape)>;
+        return closed_loop<false, Args>(h, fn, n_steps, o, stream, launch, [&](Args &q) { q.m.wstream = h->mlp_shape_stream; });
+    };
+    switch (h->actor_kind) {
+    case SHAPE_KIND_128: return run(L->mlp_shape128, Shape128{});
+    case SHAPE_KIND_512x256: return run(L->mlp_shape512x256, Shape512x256{});
+    case SHAPE_KIND_512: return run(L->mlp_shape512, Shape512{});
+    case SHAPE_KIND_3: return run(L->mlp_shape3, Shape3{});
+    default: return refuse(fn, "no actor installed (nig_set_mlp_policy)");
+    }
+}
+
 template <bool LIM>
 static int rollout_mlp(nig_handle *h, const char *fn, int32_t n_steps, const ClosedLoopOut &o, void *stream)
 {
     if (!h || n_steps <= 0) return refuse(fn, "bad argument");
     if (!LIM) NIG_TRY(refuse_limited(h, fn));
+    if (!LIM && shaped_actor(h)) return rollout_mlp_shaped(h, fn, n_steps, o, stream);
     NIG_TRY(need_actor(h, fn));
     if (LIM) NIG_TRY(check_limits(h, fn));
     const EnvLaunch *L = launch_of(h->env);
@@ -592,6 +621,7 @@ template <bool LIM>
 static int rollout_mlp_safe(nig_handle *h, const char *fn, int32_t n_steps, const ClosedLoopOut &o, float *prob_out, void *stream)
 {
     if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    NIG_TRY(refuse_shaped(h, fn));
     NIG_TRY(limits_gate<LIM>(h, fn));
     NIG_TRY(need_mfma_actor(h, fn));
     NIG_TRY(need_actor(h, fn));
@@ -609,6 +639,7 @@ static int rollout_mlp_search(nig_handle *h, const char *fn, int32_t n_steps, in
                               float *risk_out, int32_t *choice_out, void *stream)
 {
     if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    NIG_TRY(refuse_shaped(h, fn));
     NIG_TRY(limits_gate<LIM>(h, fn));
     NIG_TRY(need_mfma_actor(h, fn));
     if (n_candidates < 1 || n_candidates > NIG_MAX_CANDIDATES) return refuse(fn, "n_candidates outside 1 .. NIG_MAX_CANDIDATES");
@@ -653,6 +684,7 @@ static int rollout_mlp_gated(nig_handle *h, const char *fn, int32_t n_steps, con
                              float *logit_out, int64_t ld_c, int64_t c_step_stride, void *stream)
 {
     if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    NIG_TRY(refuse_shaped(h, fn));
     NIG_TRY(limits_gate<LIM>(h, fn));
     NIG_TRY(need_mfma_actor(h, fn));
     NIG_TRY(need_actor(h, fn));
@@ -674,6 +706,7 @@ static int rollout_mlp_projected(nig_handle *h, const char *fn, int32_t n_steps,
                                  void *stream)
 {
     if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    NIG_TRY(refuse_shaped(h, fn));
     NIG_TRY(limits_gate<LIM>(h, fn));
     NIG_TRY(need_mfma_actor(h, fn));
     NIG_TRY(need_actor(h, fn));
@@ -714,6 +747,7 @@ static int rollout_mlp_disturbed(nig_handle *h, const char *fn, int32_t n_steps,
                                  int64_t seen_step_stride, void *stream)
 {
     if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    NIG_TRY(refuse_shaped(h, fn));
     NIG_TRY(limits_gate<LIM>(h, fn));
     NIG_TRY(need_mfma_actor(h, fn));
     NIG_TRY(need_actor(h, fn));
@@ -938,6 +972,7 @@ int nig_destroy(nig_handle *h)
 {
     if (!h) return NIG_OK;
     if (h->mlp_stream) (void)hipFree(h->mlp_stream);
+    if (h->mlp_shape_stream) (void)hipFree(h->mlp_shape_stream);
     if (h->mlp_bf16_stream) (void)hipFree(h->mlp_bf16_stream);
     if (h->mlp_cstream) (void)hipFree(h->mlp_cstream);
     if (h->mlp_ctail) (void)hipFree(h->mlp_ctail);
@@ -1366,7 +1401,68 @@ int nig_set_mlp_policy(nig_handle *h, int32_t hidden, const float *W1, const flo
     const int S = SPECS[h->env].state_dim, A = SPECS[h->env].action_dim;
     float *host = nullptr;
     NIG_TRY(build_network_images(h, "nig_set_mlp_policy", hidden, S, A, MLP_STREAM_FLOATS, 1, &W1, &b1, &W2, &b2, &W3, &b3, &host));
-    return upload_stream("nig_set_mlp_policy", &h->mlp_stream, host, MLP_STREAM_FLOATS, stream);
+    NIG_TRY(upload_stream("nig_set_mlp_policy", &h->mlp_stream, host, MLP_STREAM_FLOATS, stream));
+    h->actor_kind = SHAPE_KIND_REFERENCE; h->actor_nh = 2; h->actor_dims[0] = h->actor_dims[1] = MLP_H; h->actor_dims[2] = 0;
+    return NIG_OK;
+}
+
+// ---- the actor of the other hidden shapes ("nig-mlp-shape-v1", include/nig.h) ----
+int nig_set_mlp_policy_dims(nig_handle *h, int32_t n_hidden, const int32_t *hidden, const float *const *W, const float *const *b, void *stream)
+{
+    const char *fn = "nig_set_mlp_policy_dims";
+    if (!h || !hidden || !W || !b) return refuse(fn, "NULL argument");
+    if (n_hidden < 2 || n_hidden > 3) return refuse(fn, "n_hidden outside 2 .. 3");
+    int dims[3] = {0, 0, 0};
+    for (int l = 0; l < n_hidden; ++l) {
+        if (hidden[l] < 1 || hidden[l] > SHAPE_MAX_WIDTH) return refuse(fn, "a hidden width outside 1 .. 512");
+        dims[l] = hidden[l];
+    }
+    for (int l = 0; l <= n_hidden; ++l)
+        if (!W[l] || !b[l]) return refuse(fn, "NULL layer");
+    if (!launch_of(h->env)->mlp) return refuse(fn, "env shape not supported (even state dim, at most 16 actions)", NIG_ERR_UNSUPPORTED);
+    const int S = SPECS[h->env].state_dim, A = SPECS[h->env].action_dim;
+    const int kind = shape_class_of(n_hidden, dims, S);
+    if (kind == SHAPE_KIND_NONE) return refuse(fn, "no shape class holds these hidden widths");
+    auto installed = [&]() {
+        h->actor_kind = kind; h->actor_nh = n_hidden;
+        for (int l = 0; l < 3; ++l) h->actor_dims[l] = dims[l];
+        return NIG_OK;
+    };
+    if (kind == SHAPE_KIND_REFERENCE) {                     // padded to 256 x 256 on the host: the existing image and kernel
+        float *pad = (float *)calloc(reference_pad_floats(S, A), sizeof(float));
+        float *host = (float *)calloc(MLP_STREAM_FLOATS, sizeof(float));
+        const bool ok = pad && host && put_reference_padded(S, A, dims, W, b, pad, host, MLP_STREAM_FLOATS);
+        free(pad);
+        if (!ok) { free(host); return refuse(fn, "out of host memory, or the operand stream does not fit its image"); }
+        NIG_TRY(upload_stream(fn, &h->mlp_stream, host, MLP_STREAM_FLOATS, stream));
+        return installed();
+    }
+    size_t cap = 0;                                         // the env's largest shaped image: the slot is allocated once
+    for (int k = SHAPE_KIND_128; k <= SHAPE_KIND_3; ++k) {
+        const size_t f = shape_plan(SHAPE_CLASSES[k], S).floats();
+        cap = f > cap ? f : cap;
+    }
+    const size_t floats = shape_plan(SHAPE_CLASSES[kind], S).floats();
+    float *host = (float *)calloc(floats, sizeof(float));
+    if (!host) return refuse(fn, "out of host memory");
+    if (!put_shape_network(SHAPE_CLASSES[kind], S, A, n_hidden, dims, W, b, host, floats)) {
+        free(host);
+        return refuse(fn, "the operand image does not fit its chunk plan");
+    }
+    if (!h->mlp_shape_stream) {
+        const hipError_t e = hipMalloc((void **)&h->mlp_shape_stream, cap * sizeof(float));
+        if (e != hipSuccess) { h->mlp_shape_stream = nullptr; free(host); return refuse(fn, hipGetErrorString(e), NIG_ERR_HIP); }
+    }
+    NIG_TRY(upload_stream(fn, &h->mlp_shape_stream, host, floats, stream));
+    return installed();
+}
+
+int nig_get_mlp_policy_dims(const nig_handle *h, int32_t *hidden)
+{
+    if (!h) return -1;
+    if (hidden)
+        for (int l = 0; l < 3; ++l) hidden[l] = l < h->actor_nh ? h->actor_dims[l] : 0;
+    return h->actor_kind == SHAPE_KIND_NONE ? 0 : h->actor_nh;
 }
 
 int nig_rollout_mlp(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,

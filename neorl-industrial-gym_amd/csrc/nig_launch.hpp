@@ -1,7 +1,7 @@
 // nig_launch.hpp -- the host side of libnig.so's kernels: the list of environments and the per-environment launch table.  An
 // env_<key>.hip instantiates the env's kernels by defining its table (NIG_DEFINE_ENV_LAUNCH); nig_api.hip reaches them through the
 // table's function pointers only.  The launchers of the kernel families with translation units of their own (sampled_, ensemble_,
-// disturbed_, search_, gated_, projected_, bf16_, categorical_, limited_, limited_<family>_<key>.hip) are DECLARED here and defined in
+// disturbed_, search_, gated_, projected_, bf16_, categorical_, shape*_, limited_, limited_<family>_<key>.hip) are DECLARED here and defined in
 // nig_launch_families.hpp, which those units alone include: one function template per kind of family, keyed by the argument-block
 // type, so that a family and its _limited twin are two instantiations of one launcher and two neighbouring slots of the table.
 // Which kernel form a rollout launch takes is decided in nig_launch_plan.hpp; the functions here run its plans.
@@ -81,6 +81,12 @@ struct EnvLaunch {
     void (*mlp_cat_search)(const MlpCatSearchArgs &, unsigned grid, hipStream_t);
     void (*mlp_cat_search_limited)(const MlpLimited<MlpCatSearchArgs> &, unsigned grid, hipStream_t);
     void (*mlp_cat_eval)(const MlpCatEvalArgs &, unsigned grid, hipStream_t);
+    // shape128_<key>.hip, shape512x256_<key>.hip, shape512_<key>.hip, shape3_<key>.hip ("nig-mlp-shape-v1"): what nig_rollout_mlp
+    // launches when the handle's actor slot holds a shaped actor of that class
+    void (*mlp_shape128)(const MlpShapeArgs<Shape128> &, unsigned grid, hipStream_t);
+    void (*mlp_shape512x256)(const MlpShapeArgs<Shape512x256> &, unsigned grid, hipStream_t);
+    void (*mlp_shape512)(const MlpShapeArgs<Shape512> &, unsigned grid, hipStream_t);
+    void (*mlp_shape3)(const MlpShapeArgs<Shape3> &, unsigned grid, hipStream_t);
 };
 
 template <class Env>
@@ -110,6 +116,7 @@ template <class Env> constexpr auto mlp_kernel(const MlpCatSearchArgs &) { retur
 template <class Env> constexpr auto mlp_kernel(const MlpLimited<MlpCatShieldArgs> &) { return rollout_mlp_cat_shield_limited_kernel<Env>; }
 template <class Env> constexpr auto mlp_kernel(const MlpLimited<MlpCatSearchArgs> &) { return rollout_mlp_cat_search_limited_kernel<Env>; }
 template <class Env> constexpr auto mlp_kernel(const MlpCatEvalArgs &) { return mlp_violation_prob_kernel<Env>; }
+template <class Env, class Shape> constexpr auto mlp_kernel(const MlpShapeArgs<Shape> &) { return rollout_mlp_shape_kernel<Env, Shape>; }
 
 template <class Env, class Args>
 static void launch_mlp(const Args &q, unsigned grid, hipStream_t st)
@@ -330,6 +337,12 @@ static const EnvLaunch *env_launch_table()
         t.mlp_cat_shield = mlp_slot<Env>(launch_mlp_family<Env, MlpCatShieldArgs>);
         t.mlp_cat_search = mlp_slot<Env>(launch_mlp_family<Env, MlpCatSearchArgs>);
         t.mlp_cat_eval = mlp_slot<Env>(launch_mlp_family<Env, MlpCatEvalArgs>);
+        if constexpr (has_mlp_actor<Env>) {           // (the shape units exist for the envs with the actor alone)
+            t.mlp_shape128 = launch_mlp_family<Env, MlpShapeArgs<Shape128>>;
+            t.mlp_shape512x256 = launch_mlp_family<Env, MlpShapeArgs<Shape512x256>>;
+            t.mlp_shape512 = launch_mlp_family<Env, MlpShapeArgs<Shape512>>;
+            t.mlp_shape3 = launch_mlp_family<Env, MlpShapeArgs<Shape3>>;
+        }
         if constexpr (!Env::CUSTOM_STEP) {            // the twins: the same lines on the twin's argument block
             t.step_limited = launch_step_limited<Env, false>;
             t.step64_limited = Env::HAS_ACT64 ? launch_step_limited<Env, true> : nullptr;

@@ -84,6 +84,7 @@ void launch_step_limited(const StepLimArgs &q, bool parity, unsigned grid, hipSt
 #define NIG_DEFINE_ENV_PROJECTED(EnvType) NIG_FAMILY(launch_mlp_family, EnvType, MlpProjectArgs)
 #define NIG_DEFINE_ENV_PROJECTED_LIMITED(EnvType) NIG_FAMILY(launch_mlp_family, EnvType, MlpLimited<MlpProjectArgs>)
 #define NIG_DEFINE_ENV_BF16(EnvType) NIG_FAMILY(launch_mlp_family, EnvType, MlpBf16Args)
+#define NIG_DEFINE_ENV_SHAPE(EnvType, Shape) NIG_FAMILY(launch_mlp_family, EnvType, MlpShapeArgs<Shape>)
 #define NIG_DEFINE_ENV_CATEGORICAL(EnvType) \
     NIG_FAMILY(launch_mlp_family, EnvType, MlpCatShieldArgs) NIG_FAMILY(launch_mlp_family, EnvType, MlpCatSearchArgs) \
     NIG_FAMILY(launch_mlp_family, EnvType, MlpCatEvalArgs)

@@ -259,6 +259,44 @@ def pad_critic(weights, hidden: int = 256):
     return [(P1, p1), (P2, p2), (P3, c3.copy())]
 
 
+# The shape classes of the float32 MFMA actor ("nig-mlp-shape-v1", include/nig.h), cheapest first among those of equal depth:
+# name -> the widths a network is zero-padded to.  "reference" is the 256 x 256 kernel of set_mlp_policy.
+ACTOR_SHAPE_CLASSES = (("128x128", (128, 128)), ("reference", (256, 256)), ("512x256", (512, 256)), ("512x512", (512, 512)),
+                       ("256x256x256", (256, 256, 256)))
+
+
+def actor_shape_class(hidden_dims):
+    """The name of the cheapest shape class (fewest MFMAs per step) that holds an actor with these hidden widths -- "128x128",
+    "reference", "512x256", "512x512", "256x256x256" -- or None where no class does: one or more than three hidden layers, a
+    width outside 1 .. 512.  The library's own choice (nig_set_mlp_policy_dims) is the same function."""
+    dims = tuple(int(d) for d in hidden_dims)
+    for name, cls in ACTOR_SHAPE_CLASSES:
+        if len(cls) == len(dims) and all(1 <= d <= c for d, c in zip(dims, cls)):
+            return name
+    return None
+
+
+def pad_actor(weights, dims):
+    """An actor [(W1 [S,h1], b1), .., (W_head [h_last,A], b_head)] zero-padded to the hidden widths `dims` (one per hidden layer,
+    each at least the network's own): the columns and biases of a hidden layer and the rows of the layer above it.  The added
+    units are exactly relu(0) = 0 and every added term is fma(w, 0, c) == c, so the padded network computes the same numbers (the
+    sign of a zero aside).  Float32 copies come back; anything that does not fit is refused."""
+    dims = tuple(int(d) for d in dims)
+    ws = [(np.asarray(W, dtype=f32), np.asarray(b, dtype=f32).reshape(-1)) for W, b in weights]
+    own = tuple(W.shape[1] for W, _ in ws[:-1])
+    if len(ws) != len(dims) + 1 or any(o > d for o, d in zip(own, dims)) or any(W.shape[1] != b.shape[0] for W, b in ws) \
+            or any(ws[i + 1][0].shape[0] != own[i] for i in range(len(own))):
+        raise ValueError(f"cannot pad an actor of shapes {[np.shape(W) for W, _ in weights]} to hidden widths {dims}")
+    out, rows = [], ws[0][0].shape[0]
+    for i, (W, b) in enumerate(ws):
+        cols = dims[i] if i < len(dims) else W.shape[1]
+        P, q = np.zeros((rows, cols), dtype=f32), np.zeros(cols, dtype=f32)
+        P[:W.shape[0], :W.shape[1]], q[:b.shape[0]] = W, b
+        out.append((P, q))
+        rows = cols
+    return out
+
+
 def pad_safety_member(weights, hidden: int = 256):
     """pad_critic for a head of 1 .. 4 columns: a safety-ensemble member [(C1 [D,h], c1 [h]), (C2 [h,h], c2 [h]), (C3 [h,C], c3 [C])]
     with h <= hidden (the reference's SafetyEnsembleMember: 128) as the `hidden`-wide network set_mlp_safety_ensemble() takes.
@@ -394,6 +432,11 @@ class MLPPolicy:
         # the fused MFMA kernel covers the reference actor shape; anything else goes through torch GEMMs
         self.fusable = (len(self.weights) == 3 and self.weights[0][0].shape[1] == 256
                         and self.weights[1][0].shape == (256, 256))
+        # every hidden shape: the widths, and the shape class of the MFMA actor that holds them ("nig-mlp-shape-v1"; None: the host path)
+        self.hidden_dims = tuple(int(W.shape[1]) for W, _ in self.weights[:-1])
+        self.shape_class = actor_shape_class(self.hidden_dims)
+        # the widths are a shaped class's own, no padding needed: what evaluate_with_safety sends to the shaped kernel by itself
+        self.shape_class_exact = self.shape_class not in (None, "reference") and dict(ACTOR_SHAPE_CLASSES)[self.shape_class] == self.hidden_dims
         self.constraint_threshold = float(constraint_threshold)
         self.safety_weights = None
         self.safety_layers = None

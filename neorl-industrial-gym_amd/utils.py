@@ -170,6 +170,23 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
     bf16 = getattr(agent, "precision", None) == "bf16" and not hasattr(agent, "install")
     fused_bf16 = bf16 and getattr(agent, "fusable", False) and plain and mfma_env and not limited
     fused_mlp = not bf16 and not hasattr(agent, "install") and getattr(agent, "fusable", False) and plain and (mfma_env or not limited)
+    # The other hidden shapes ("nig-mlp-shape-v1"): a plain MLPPolicy -- unshielded, undisturbed, float32 -- whose hidden widths ARE a
+    # shaped class's (128x128, 512x256, 512x512, 256x256x256: with (256, 256) the five hidden_dims the reference's tuner builds) goes to
+    # set_mlp_policy_dims + rollout_mlp, and so does a reference agent MLPPolicy.from_agent can read into such a policy.  A network that
+    # only fits a class after zero-padding -- (64, 64), (200, 200), (400, 300) -- keeps the host loop here, as it always has
+    # (tests/test_limits_families_host.py holds that); it runs fused where the caller installs it with env.set_mlp_policy_dims.
+    # The family has no _limited twin: with added constraints the agent takes the host loop, as bf16 does.
+    fused_shape = False
+    if plain and mfma_env and not limited and not bf16:
+        from .policies import MLPPolicy
+        cand = agent
+        if (not hasattr(agent, "fusable") and hasattr(agent, "state") and not any(hasattr(agent, k) for k in ("agents", "install", "to_struct", "disturbance"))):
+            try:
+                cand = MLPPolicy.from_agent(agent, device=env.device)
+            except Exception:
+                cand = agent
+        if type(cand) is MLPPolicy and not cand.fusable and cand.shape_class_exact:
+            agent, fused_shape = cand, True
     shielded = fused_mlp and getattr(agent, "safety_weights", None) is not None and hasattr(agent, "threshold")
     searching = shielded and hasattr(agent, "n_candidates")       # MLPPolicy.searching(): get_safe_action instead of the halving
     disturbed = None           # a disturbance.Disturbed whose inner agent runs in the env kernel: "fused-policy" / "fused-mlp"
@@ -179,7 +196,7 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
             disturbed = route
             (env.set_policy if route == "fused-policy" else lambda a: env.set_mlp_policy(a.weights))(inner)
             env.set_disturbance(agent.disturbance)
-        device_policy = ensemble = gated = projecting = fused_mlp = fused_bf16 = shielded = searching = False
+        device_policy = ensemble = gated = projecting = fused_mlp = fused_bf16 = fused_shape = shielded = searching = False
     if disturbed:
         device_policy = True
     elif device_policy:
@@ -189,6 +206,9 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
         device_policy = True
     elif fused_bf16:
         env.set_mlp_policy_bf16(agent.weights)
+        device_policy = True
+    elif fused_shape:
+        env.set_mlp_policy_dims(agent.weights)
         device_policy = True
     elif fused_mlp:
         env.set_mlp_policy(agent.weights)
@@ -204,7 +224,7 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
         name = ("rollout_policy_disturbed" if disturbed == "fused-policy" else "rollout_mlp_disturbed" if disturbed
                 else "rollout_mlp_gated" if gated else "rollout_mlp_projected" if projecting else "rollout_mlp_ensemble" if ensemble
                 else "rollout_mlp_bf16" if fused_bf16
-                else "rollout_mlp_search" if searching else "rollout_mlp_safe" if shielded else "rollout_mlp" if fused_mlp
+                else "rollout_mlp_search" if searching else "rollout_mlp_safe" if shielded else "rollout_mlp" if fused_mlp or fused_shape
                 else "rollout_policy")
         method = getattr(env, name + "_limited" if limited else name)
         rollout = ((lambda n, *a, **k: method(n, agent.max_iters, agent.step, *a, **k)) if projecting
