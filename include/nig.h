@@ -593,7 +593,8 @@ int nig_bf16_from_f32(const float *x, uint16_t *out, int64_t n);
  *   "512x256"      two hidden layers, H1 <= 512, H2 <= 256               16, 8 tiles
  *   "512x512"      two hidden layers, both <= 512                        16, 16 tiles
  *   "256x256x256"  three hidden layers, all <= 256                       8, 8, 8 tiles
- * More than three hidden layers, a width above 512 and LayerNorm are outside every class.
+ * More than three hidden layers and a width above 512 are outside every class; a LayerNorm actor of hidden widths (256, 256) has a
+ * kernel family of its own ("nig-mlp-ln-v1", nig_set_mlp_policy_ln below), any other LayerNorm network stays on the host.
  *
  * The law, for one lane and one step on state s[0..S) and the PADDED network (the arithmetic of the padded network is the law):
  *   layer 1   z_u = the float32 fma chain over k = 0 .. S-1 in natural order, from 0: c = fma(W1[k][u], s_k, c), two inputs per MFMA
@@ -625,6 +626,29 @@ int nig_bf16_from_f32(const float *x, uint16_t *out, int64_t n);
 int nig_set_mlp_policy_dims(nig_handle *h, int32_t n_hidden, const int32_t *hidden, const float *const *W,
                             const float *const *b, void *stream);
 int nig_get_mlp_policy_dims(const nig_handle *h, int32_t *hidden /* [3] */);
+
+/*
+ * The float32 MFMA actor with LayerNorm: the reference's MLP with use_layer_norm=True (agents/networks.py: Dense -> LayerNorm ->
+ * ReLU per hidden layer, tanh head), S -> 256 -> 256 -> A with hidden widths exactly (256, 256).  The kernel family "nig-mlp-ln-v1",
+ * reached through nig_rollout_mlp.  The law is stated once, in csrc/nig_mlp_ln.hpp's opening comment (tests/mlp_ln_ref.c restates
+ * it): the Dense pre-activations are the 256 x 256 law's fma chains; mean and a TWO-PASS variance are float32 sums in one stated
+ * order per lane half, joined by one add; 1 / sigma is det_rsqrtf(var + eps) (IEEE sqrt and division); y = fma(z - mean, rs *
+ * gamma, beta); the head and det_tanhf are nig_rollout_mlp's.  Non-finite inputs are outside the law.
+ *
+ * nig_set_mlp_policy_ln: nig_set_mlp_policy's arrays plus g1 / be1 and g2 / be2 [256], the scale and bias of the two LayerNorms,
+ * and eps (flax's default: 1e-6), all host pointers.  Fills the ONE actor slot with a kind of its own: nig_set_mlp_policy and
+ * nig_set_mlp_policy_dims replace the LayerNorm actor and it replaces theirs; the critic, ensemble, bf16 and limits slots are
+ * untouched.  nig_get_mlp_policy_dims reports 2 and 256, 256.  Refusals, before anything is written: NIG_ERR_INVALID for a NULL
+ * pointer and for an eps that is not finite and positive; NIG_ERR_UNSUPPORTED for hidden != 256 and for an env shape without the
+ * MFMA actor.  While a LayerNorm actor is installed nig_rollout_mlp runs it, and every other entry point that reads the actor slot
+ * (nig_rollout_mlp_safe, _search, _gated, _projected, _disturbed and every _limited twin, nig_rollout_mlp_limited included)
+ * returns NIG_ERR_UNSUPPORTED with nothing launched or written: the shaped actor's rule.
+ * nig_get_mlp_policy_norm: 1 while the actor slot holds a LayerNorm actor, 0 otherwise; -1 for NULL.
+ */
+int nig_set_mlp_policy_ln(nig_handle *h, int32_t hidden, const float *W1, const float *b1, const float *g1, const float *be1,
+                          const float *W2, const float *b2, const float *g2, const float *be2, const float *W3, const float *b3,
+                          float eps, void *stream);
+int nig_get_mlp_policy_norm(const nig_handle *h);
 
 /*
  * nig_rollout_policy / nig_rollout_mlp under the installed limits ("nig-limits-v1", nig_set_limits): every argument and

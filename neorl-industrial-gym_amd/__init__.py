@@ -18,7 +18,7 @@ _lib.lib()   # fail loudly here if libnig.so is missing
 from .batched import BatchedIndustrialEnv, MixedBatchedEnv, StepInfo, categorical_below_mask  # noqa: E402
 from .envs import (AdvancedChemicalReactorEnv, AdvancedPowerGridEnv, ChemicalReactorEnv, HVACControlEnv,  # noqa: E402
                    IndustrialEnv, PowerGridEnv, RobotAssemblyEnv, SteelAnnealingEnv, SupplyChainEnv, WaterTreatmentEnv)
-from .policies import (Bf16MLPPolicy, categorical_mass, ConstraintProjectionPolicy, DevicePolicy, EnsemblePolicy, MLPPolicy, SafetyEnsemblePolicy, behaviour_policy, bf16_round,  # noqa: E402
+from .policies import (Bf16MLPPolicy, categorical_mass, ConstraintProjectionPolicy, DevicePolicy, EnsemblePolicy, LayerNormMLPPolicy, MLPPolicy, SafetyEnsemblePolicy, behaviour_policy, bf16_round,  # noqa: E402
                        bf16_split, constant_agent, mlp_bf16_reference, mpc_agent, pid_agent, random_agent)
 from .utils import evaluate_with_safety, make, make_batched, uniform_action_statistics  # noqa: E402
 from .disturbance import Disturbance, Disturbed, evaluate_robustness, robustness_scores  # noqa: E402
@@ -49,5 +49,5 @@ __all__ = [
     "make", "make_batched", "evaluate_with_safety", "uniform_action_statistics", "tune", "DevicePolicy", "MLPPolicy", "EnsemblePolicy", "SafetyEnsemblePolicy", "ConstraintProjectionPolicy", "behaviour_policy", "constant_agent",
     "mpc_agent", "pid_agent", "random_agent", "Disturbance", "Disturbed", "evaluate_robustness", "robustness_scores",
     "EpisodeLog", "episodes_from_rows", "evaluate_episodes", "Bf16MLPPolicy", "bf16_round", "bf16_split", "mlp_bf16_reference",
-    "categorical_below_mask", "categorical_mass",
+    "categorical_below_mask", "categorical_mass", "LayerNormMLPPolicy",
 ]

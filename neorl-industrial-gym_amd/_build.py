@@ -159,9 +159,16 @@ def build_variant(name, verbose=False):
 # own, never part of libnig.so, compiled with HIPCC_FLAGS -- the library's bits are a property of these flags.
 PROBE_SRC = os.path.join(os.path.dirname(_HERE), "tests", "detmath_probe.hip")
 PROBE = os.path.join(_HERE, "libnig_detmath_probe.so")
+# det_rsqrtf's probe (tests/rsqrt_probe.hip, tests/test_gpu_rsqrt.py): the same kind of library, in a file of its own
+RSQRT_PROBE_SRC = os.path.join(os.path.dirname(_HERE), "tests", "rsqrt_probe.hip")
+RSQRT_PROBE = os.path.join(_HERE, "libnig_rsqrt_probe.so")
 
 
-def build_probe(verbose=False):
+def build_rsqrt_probe(verbose=False):
+    return build_probe(verbose, RSQRT_PROBE_SRC, RSQRT_PROBE)
+
+
+def build_probe(verbose=False, PROBE_SRC=PROBE_SRC, PROBE=PROBE):
     stamp = PROBE + ".srchash"
     want = _digest([PROBE_SRC] + headers(), " ".join(HIPCC_FLAGS))
     if os.path.exists(PROBE) and os.path.exists(stamp) and open(stamp).read().strip() == want:

@@ -141,6 +141,8 @@ PROTOTYPES = {
     "nig_rollout_mlp": (ci, CLOSED_LOOP + [vp]),
     "nig_set_mlp_policy_dims": (ci, [vp, i32, vp, vp, vp, vp]),
     "nig_get_mlp_policy_dims": (ci, [vp, vp]),
+    "nig_set_mlp_policy_ln": (ci, [vp, i32] + [vp] * 10 + [f32, vp]),
+    "nig_get_mlp_policy_norm": (ci, [vp]),
     "nig_set_mlp_policy_bf16": (ci, [vp, i32, vp, vp, vp, vp, vp, vp, vp]),
     "nig_rollout_mlp_bf16": (ci, CLOSED_LOOP + [vp, i64, i64, vp]),
     "nig_bf16_from_f32": (ci, [vp, vp, i64]),

@@ -572,6 +572,24 @@ class BatchedIndustrialEnv:
         n = self._L.nig_get_mlp_policy_dims(self._h, hidden)
         return tuple(int(hidden[i]) for i in range(max(n, 0)))
 
+    def set_mlp_policy_ln(self, policy):
+        """Install a LayerNorm actor (policies.LayerNormMLPPolicy: S->256->LayerNorm->ReLU->256->LayerNorm->ReLU->A, tanh; the law
+        "nig-mlp-ln-v1", csrc/nig_mlp_ln.hpp) for rollout_mlp().  Fills the ONE actor slot set_mlp_policy() and set_mlp_policy_dims()
+        fill: each call replaces the others' actor.  While it is installed, every other closed loop that reads the actor (safe,
+        search, gated, projected, disturbed, the _limited twins) refuses with code 4."""
+        W = _mlp_weights(policy.weights, self._actor_shapes())
+        G = [np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1)) for pair in policy.norms for x in pair]
+        assert len(G) == 4 and all(g.shape == (256,) for g in G), [g.shape for g in G]
+        P = lambda a: a.ctypes.data_as(C.c_void_p)
+        with torch.cuda.device(self._dev_index):
+            _lib.check(self._L.nig_set_mlp_policy_ln(self._h, 256, P(W[0]), P(W[1]), P(G[0]), P(G[1]), P(W[2]), P(W[3]), P(G[2]), P(G[3]),
+                                                     P(W[4]), P(W[5]), float(policy.eps), self._stream()))
+
+    @property
+    def mlp_policy_norm(self):
+        """True while the actor slot holds a LayerNorm actor (set_mlp_policy_ln)."""
+        return self._L.nig_get_mlp_policy_norm(self._h) == 1
+
     def rollout_mlp(self, n_steps: int, reward_out=None, flags_out=None, obs_out=None, act_out=None):
         """Closed loop with the installed MLP actor evaluated by f32 MFMA inside the env kernel
         (same outputs as rollout_policy)."""

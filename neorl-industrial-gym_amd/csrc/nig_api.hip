@@ -182,6 +182,8 @@ struct nig_handle {
     // nig_set_mlp_policy_dims call of the reference class), mlp_shape_stream the shaped image of any other class (owned, allocated once
     // for the env's largest class); actor_dims: the installed actor's unpadded hidden widths
     int actor_kind = SHAPE_KIND_NONE, actor_nh = 0; int32_t actor_dims[3] = {0, 0, 0}; float *mlp_shape_stream = nullptr;
+    // ACTOR_KIND_LN ("nig-mlp-ln-v1", nig_set_mlp_policy_ln): the LayerNorm actor's image (owned) and its eps
+    float *mlp_ln_stream = nullptr; float ln_eps = 0.0f;
     float mlp_threshold = 0.0f;      // shield threshold of nig_rollout_mlp_safe
     // the ONE critic slot's kind (NIG_SAFETY_*): mlp_cstream holds the sigmoid critic's image (nig_set_mlp_safety) or the categorical
     // critic's (nig_set_mlp_safety_categorical), whose head rows 16 .. 63 lie in mlp_ctail (owned, MLP_TAIL_FLOATS floats)
@@ -528,10 +530,14 @@ static int need_mfma_actor(const nig_handle *h, const char *fn)
 {
     return launch_of(h->env)->mlp ? NIG_OK : refuse(fn, "env shape has no MFMA actor", NIG_ERR_UNSUPPORTED);
 }
+// a kind of the actor slot beside the shape classes: the LayerNorm actor.  It follows the shaped actor's rule everywhere.
+constexpr int ACTOR_KIND_LN = SHAPE_KIND_3 + 1;
 static bool shaped_actor(const nig_handle *h) { return h->actor_kind > SHAPE_KIND_REFERENCE; }
 // the families that run the 256 x 256 actor only ask this right after their bad-argument check ("nig-mlp-shape-v1")
 static int refuse_shaped(const nig_handle *h, const char *fn)
 {
+    if (h->actor_kind == ACTOR_KIND_LN)
+        return refuse(fn, "a LayerNorm actor is installed (nig_set_mlp_policy_ln): this entry point runs the plain 256 x 256 actor only", NIG_ERR_UNSUPPORTED);
     return shaped_actor(h) ? refuse(fn, "a shaped actor is installed (nig_set_mlp_policy_dims): this entry point runs the 256 x 256 actor only", NIG_ERR_UNSUPPORTED) : NIG_OK;
 }
 static int need_actor(const nig_handle *h, const char *fn)       // (an env without the MFMA actor never has one: nig_set_mlp_policy refuses)
@@ -587,7 +593,8 @@ static int rollout_policy(nig_handle *h, const char *fn, int32_t n_steps, const 
     return LIM ? NIG_OK : ring_check(h, (hipStream_t)stream, fn);      // (the one closed loop with cooperating-wave forms)
 }
 
-// nig_rollout_mlp with a shaped actor in the slot: the class's kernel on the shaped image ("nig-mlp-shape-v1")
+// nig_rollout_mlp with a shaped actor in the slot: the class's kernel on the shaped image ("nig-mlp-shape-v1"), or the LayerNorm
+// actor's on its own ("nig-mlp-ln-v1")
 static int rollout_mlp_shaped(nig_handle *h, const char *fn, int32_t n_steps, const ClosedLoopOut &o, void *stream)
 {
     const EnvLaunch *L = launch_of(h->env);
@@ -596,6 +603,8 @@ static int rollout_mlp_shaped(nig_handle *h, const char *fn, int32_t n_steps, co
         return closed_loop<false, Args>(h, fn, n_steps, o, stream, launch, [&](Args &q) { q.m.wstream = h->mlp_shape_stream; });
     };
     switch (h->actor_kind) {
+    case ACTOR_KIND_LN:
+        return closed_loop<false, MlpLnArgs>(h, fn, n_steps, o, stream, L->mlp_ln, [&](MlpLnArgs &q) { q.m.wstream = h->mlp_ln_stream; q.eps = h->ln_eps; });
     case SHAPE_KIND_128: return run(L->mlp_shape128, Shape128{});
     case SHAPE_KIND_512x256: return run(L->mlp_shape512x256, Shape512x256{});
     case SHAPE_KIND_512: return run(L->mlp_shape512, Shape512{});
@@ -973,6 +982,7 @@ int nig_destroy(nig_handle *h)
     if (!h) return NIG_OK;
     if (h->mlp_stream) (void)hipFree(h->mlp_stream);
     if (h->mlp_shape_stream) (void)hipFree(h->mlp_shape_stream);
+    if (h->mlp_ln_stream) (void)hipFree(h->mlp_ln_stream);
     if (h->mlp_bf16_stream) (void)hipFree(h->mlp_bf16_stream);
     if (h->mlp_cstream) (void)hipFree(h->mlp_cstream);
     if (h->mlp_ctail) (void)hipFree(h->mlp_ctail);
@@ -1464,6 +1474,32 @@ int nig_get_mlp_policy_dims(const nig_handle *h, int32_t *hidden)
         for (int l = 0; l < 3; ++l) hidden[l] = l < h->actor_nh ? h->actor_dims[l] : 0;
     return h->actor_kind == SHAPE_KIND_NONE ? 0 : h->actor_nh;
 }
+
+// ---- the LayerNorm actor ("nig-mlp-ln-v1", csrc/nig_mlp_ln.hpp) ----
+int nig_set_mlp_policy_ln(nig_handle *h, int32_t hidden, const float *W1, const float *b1, const float *g1, const float *be1,
+                          const float *W2, const float *b2, const float *g2, const float *be2, const float *W3, const float *b3,
+                          float eps, void *stream)
+{
+    const char *fn = "nig_set_mlp_policy_ln";
+    if (!h || !W1 || !b1 || !g1 || !be1 || !W2 || !b2 || !g2 || !be2 || !W3 || !b3) return refuse(fn, "NULL argument");
+    if (!(eps > 0.0f) || !(eps < __builtin_inff())) return refuse(fn, "eps must be finite and positive");
+    if (hidden != MLP_H) return refuse(fn, "hidden must be 256: the LayerNorm actor has hidden widths (256, 256)", NIG_ERR_UNSUPPORTED);
+    if (!launch_of(h->env)->mlp_ln) return refuse(fn, "env shape not supported (even state dim, at most 16 actions)", NIG_ERR_UNSUPPORTED);
+    const int S = SPECS[h->env].state_dim, A = SPECS[h->env].action_dim;
+    const size_t floats = ln_plan(S).floats();
+    float *host = (float *)calloc(floats, sizeof(float));
+    if (!host) return refuse(fn, "out of host memory");
+    if (!put_ln_network(S, A, W1, b1, g1, be1, W2, b2, g2, be2, W3, b3, host, floats)) {
+        free(host);
+        return refuse(fn, "the operand image does not fit its chunk plan");
+    }
+    NIG_TRY(upload_stream(fn, &h->mlp_ln_stream, host, floats, stream));
+    h->actor_kind = ACTOR_KIND_LN; h->actor_nh = 2; h->actor_dims[0] = h->actor_dims[1] = MLP_H; h->actor_dims[2] = 0;
+    h->ln_eps = eps;
+    return NIG_OK;
+}
+
+int nig_get_mlp_policy_norm(const nig_handle *h) { return !h ? -1 : h->actor_kind == ACTOR_KIND_LN ? 1 : 0; }
 
 int nig_rollout_mlp(nig_handle *h, int32_t n_steps, float *reward_out, uint32_t *flags_out, int64_t out_stride,
                     float *obs_out, int64_t obs_step_stride, float *act_out, int64_t ld_act, int64_t act_step_stride,

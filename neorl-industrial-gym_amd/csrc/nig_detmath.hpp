@@ -189,7 +189,17 @@ __device__ __forceinline__ float det_sigmoidf(float x)
     return 1.0f / (1.0f + det_expf(-x));
 }
 
-// float32 sine: Cody-Waite by pi/2 (3 constants), degree-7/8 kernels.  Stated domain |x| <= 1e4, absolute error
+// 1 / sqrt(x) for a positive normal float: the correctly rounded square root, then the correctly rounded division of 1 by it (plain
+// `/` and __builtin_sqrtf, which hipcc expands to the IEEE sequences; v_rsq_f32, good to about 1 ulp and not specified bit for bit,
+// is not used).  Two roundings: <= 1.5 ulp of the exact value's binade over every positive normal float (measured: 1.4904, just above a power of
+// four; tests/rsqrt_check.c); the
+// result is a normal float on that whole domain.  LayerNorm's 1 / sigma ("nig-mlp-ln-v1", nig_mlp_ln.hpp), twice per step.
+__device__ __forceinline__ float det_rsqrtf(float x)
+{
+    return 1.0f / __builtin_sqrtf(x);
+}
+
+// float32 sine: Cody-Waite by pi/2 (3 constants), degree-7/8 kernels. Stated domain |x| <= 1e4, absolute error
 // <= 8e-8 there (tests/detmath_check.c).  Beyond it the reduction loses accuracy (from |x| ~ 3e7 on the result leaves
 // [-1, 1]) but stays one defined function of x: the quadrant is read from the low mantissa bits of fk + 1.5 * 2^23
 // (fk mod 4 for |fk| < 2^22, the same as the former (int)fk & 3 there), not from a float -> int conversion, which

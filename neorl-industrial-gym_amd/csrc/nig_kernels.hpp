@@ -31,4 +31,5 @@
 #include "nig_mlp.hpp"               // the MFMA actor, its shield and its ensemble
 #include "nig_mlp_bf16.hpp"          // the MFMA actor on the bf16 matrix unit ("nig-mlp-bf16-v1")
 #include "nig_mlp_shape.hpp"         // the MFMA actor of the other hidden shapes ("nig-mlp-shape-v1")
+#include "nig_mlp_ln.hpp"            // the MFMA actor with LayerNorm ("nig-mlp-ln-v1")
 #include "nig_episodes.hpp"          // per-episode records from reward / flag rows (env-independent)

@@ -646,6 +646,85 @@ class MLPPolicy:
         return SearchShieldPolicy(self, n_candidates, self._search_threshold(safety_threshold))
 
 
+class LayerNormMLPPolicy:
+    """The deterministic actor of a reference agent built with use_layer_norm=True (agents/networks.py MLP.__call__: Dense ->
+    LayerNorm -> ReLU per hidden layer, tanh head), hidden widths exactly (256, 256), kept on the GPU.
+
+    `weights` = [(W1 [S,256], b1), (W2 [256,256], b2), (W3 [256,A], b3)] (Flax Dense kernels are [in, out]); `norms` =
+    [(scale1 [256], bias1 [256]), (scale2, bias2)], the two LayerNorms; `eps` flax's epsilon (1e-6).  On an env with the MFMA actor,
+    without added constraints and without recorded draws, evaluate_with_safety / evaluate_episodes install it with
+    env.set_mlp_policy_ln and play it inside the env kernel (rollout_mlp, the law "nig-mlp-ln-v1": csrc/nig_mlp_ln.hpp).
+    `predict` / `predict_device` are the torch host form of the same formula -- two-pass variance, 1 / sqrt(var + eps) -- in torch's
+    arithmetic, not the law's bits: the route on WaterTreatment and under added constraints."""
+    is_trained = True
+    normalization = "layer_norm"
+
+    def __init__(self, weights, norms, eps: float = 1e-6, device="cuda:0"):
+        import torch
+        self.device = torch.device(device)
+        self.weights = [(np.asarray(W, dtype=f32), np.asarray(b, dtype=f32).reshape(-1)) for W, b in weights]
+        self.norms = [(np.asarray(g, dtype=f32).reshape(-1), np.asarray(b, dtype=f32).reshape(-1)) for g, b in norms]
+        if len(self.weights) != 3 or len(self.norms) != 2:
+            raise ValueError(f"a LayerNorm actor has three Dense layers and two LayerNorms, got {len(self.weights)} and {len(self.norms)}")
+        self.weights[2] = (self.weights[2][0].reshape(self.weights[1][0].shape[-1], -1), self.weights[2][1])
+        (W1, b1), (W2, b2), (W3, b3) = self.weights
+        self.hidden_dims = (int(W1.shape[1]), int(W2.shape[1]))
+        if self.hidden_dims != (256, 256):
+            raise ValueError(f"a LayerNorm actor has hidden widths (256, 256), got {self.hidden_dims}")
+        if W2.shape != (256, 256) or W3.shape[0] != 256 or b1.shape != (256,) or b2.shape != (256,) or b3.shape != (W3.shape[1],) \
+                or any(g.shape != (256,) or b.shape != (256,) for g, b in self.norms):
+            raise ValueError(f"LayerNorm actor layers do not chain: {[W.shape for W, _ in self.weights]}, norms {[g.shape for g, _ in self.norms]}")
+        self.eps = float(eps)
+        if not (np.isfinite(self.eps) and self.eps > 0):
+            raise ValueError(f"eps must be finite and positive, got {eps}")
+        self.state_dim, self.action_dim = int(W1.shape[0]), int(W3.shape[1])
+        T = lambda a: torch.as_tensor(a, dtype=torch.float32, device=self.device).contiguous()
+        self.layers = [(T(W), T(b)) for W, b in self.weights]
+        self.norm_layers = [(T(g), T(b)) for g, b in self.norms]
+        self.fusable = True          # the shape "nig-mlp-ln-v1" covers: the constructor refuses every other
+
+    @classmethod
+    def from_agent(cls, agent, device="cuda:0", eps: float = 1e-6):
+        """The actor of a reference agent trained with use_layer_norm=True: agent.state["actor"].params, a Flax tree
+        {"params": {"MLP_0": {"Dense_0|1|2": {"kernel", "bias"}, "LayerNorm_0|1": {"scale", "bias"}}}} (any nested mapping of
+        array-likes).  Both hidden layers must carry a LayerNorm with scale and bias; anything else is refused (ValueError)."""
+        t = agent.state["actor"].params
+        while hasattr(t, "items") and not any(str(k).startswith("Dense_") for k in t.keys()):
+            subs = [v for v in t.values() if hasattr(v, "items")]
+            if len(subs) != 1:
+                raise ValueError(f"actor: cannot find the Dense layers of the parameter tree (keys {list(t.keys())})")
+            t = subs[0]
+        if not hasattr(t, "items"):
+            raise ValueError("actor: cannot find the Dense layers of the parameter tree")
+        dense = sorted((k for k in t.keys() if str(k).startswith("Dense_")), key=lambda k: int(str(k)[6:]))
+        norm = sorted((k for k in t.keys() if str(k).startswith("LayerNorm_")), key=lambda k: int(str(k)[10:]))
+        if [str(k) for k in dense] != ["Dense_0", "Dense_1", "Dense_2"] or [str(k) for k in norm] != ["LayerNorm_0", "LayerNorm_1"]:
+            raise ValueError(f"actor: a LayerNorm actor is Dense_0..2 with LayerNorm_0 and LayerNorm_1, got {[str(k) for k in dense + norm]}")
+        for k in norm:
+            if not (hasattr(t[k], "keys") and "scale" in t[k].keys() and "bias" in t[k].keys()):
+                raise ValueError(f"actor: {k} needs both scale and bias (use_scale / use_bias)")
+        return cls([(np.asarray(t[k]["kernel"], dtype=f32), np.asarray(t[k]["bias"], dtype=f32)) for k in dense],
+                   [(np.asarray(t[k]["scale"], dtype=f32), np.asarray(t[k]["bias"], dtype=f32)) for k in norm], eps=eps, device=device)
+
+    def predict_device(self, obs):
+        import torch
+        x = obs
+        for (W, b), (g, be) in zip(self.layers[:2], self.norm_layers):
+            z = torch.addmm(b, x, W)
+            d = z - z.mean(dim=1, keepdim=True)
+            rs = torch.rsqrt((d * d).mean(dim=1, keepdim=True) + self.eps)
+            x = torch.relu(d * (rs * g) + be)
+        W, b = self.layers[2]
+        return torch.tanh(torch.addmm(b, x, W))
+
+    def predict(self, observations, deterministic: bool = True):
+        import torch
+        o = torch.as_tensor(np.asarray(observations, dtype=f32), device=self.device)
+        single = o.dim() == 1
+        out = self.predict_device(o.reshape(-1, self.state_dim)).cpu().numpy()
+        return out[0] if single else out
+
+
 class SearchShieldPolicy:
     """MLPPolicy.searching(): predict / predict_device give get_safe_action's actions.  When the actor has the reference shape
     and the critic three layers of hidden width <= 256 (padded to 256 by pad_critic: the reference's RiskEstimator is 128 wide),

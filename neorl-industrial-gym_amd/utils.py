@@ -169,7 +169,12 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
     # through its predict_device.
     bf16 = getattr(agent, "precision", None) == "bf16" and not hasattr(agent, "install")
     fused_bf16 = bf16 and getattr(agent, "fusable", False) and plain and mfma_env and not limited
-    fused_mlp = not bf16 and not hasattr(agent, "install") and getattr(agent, "fusable", False) and plain and (mfma_env or not limited)
+    # LayerNormMLPPolicy ("nig-mlp-ln-v1"): ahead of the fused_mlp test as well.  Only the explicit policy goes to the device -- a raw
+    # reference agent with LayerNorm keeps the host loop, as it always has -- and the family has no _limited twin: with added
+    # constraints, as on an env without the MFMA actor, it takes the host loop through its predict_device.
+    layer_norm = getattr(agent, "normalization", None) == "layer_norm" and not hasattr(agent, "install")
+    fused_ln = layer_norm and getattr(agent, "fusable", False) and plain and mfma_env and not limited
+    fused_mlp = not bf16 and not layer_norm and not hasattr(agent, "install") and getattr(agent, "fusable", False) and plain and (mfma_env or not limited)
     # The other hidden shapes ("nig-mlp-shape-v1"): a plain MLPPolicy -- unshielded, undisturbed, float32 -- whose hidden widths ARE a
     # shaped class's (128x128, 512x256, 512x512, 256x256x256: with (256, 256) the five hidden_dims the reference's tuner builds) goes to
     # set_mlp_policy_dims + rollout_mlp, and so does a reference agent MLPPolicy.from_agent can read into such a policy.  A network that
@@ -177,7 +182,7 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
     # (tests/test_limits_families_host.py holds that); it runs fused where the caller installs it with env.set_mlp_policy_dims.
     # The family has no _limited twin: with added constraints the agent takes the host loop, as bf16 does.
     fused_shape = False
-    if plain and mfma_env and not limited and not bf16:
+    if plain and mfma_env and not limited and not bf16 and not layer_norm:
         from .policies import MLPPolicy
         cand = agent
         if (not hasattr(agent, "fusable") and hasattr(agent, "state") and not any(hasattr(agent, k) for k in ("agents", "install", "to_struct", "disturbance"))):
@@ -196,7 +201,7 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
             disturbed = route
             (env.set_policy if route == "fused-policy" else lambda a: env.set_mlp_policy(a.weights))(inner)
             env.set_disturbance(agent.disturbance)
-        device_policy = ensemble = gated = projecting = fused_mlp = fused_bf16 = fused_shape = shielded = searching = False
+        device_policy = ensemble = gated = projecting = fused_mlp = fused_bf16 = fused_ln = fused_shape = shielded = searching = False
     if disturbed:
         device_policy = True
     elif device_policy:
@@ -206,6 +211,9 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
         device_policy = True
     elif fused_bf16:
         env.set_mlp_policy_bf16(agent.weights)
+        device_policy = True
+    elif fused_ln:
+        env.set_mlp_policy_ln(agent)
         device_policy = True
     elif fused_shape:
         env.set_mlp_policy_dims(agent.weights)
@@ -224,7 +232,7 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
         name = ("rollout_policy_disturbed" if disturbed == "fused-policy" else "rollout_mlp_disturbed" if disturbed
                 else "rollout_mlp_gated" if gated else "rollout_mlp_projected" if projecting else "rollout_mlp_ensemble" if ensemble
                 else "rollout_mlp_bf16" if fused_bf16
-                else "rollout_mlp_search" if searching else "rollout_mlp_safe" if shielded else "rollout_mlp" if fused_mlp or fused_shape
+                else "rollout_mlp_search" if searching else "rollout_mlp_safe" if shielded else "rollout_mlp" if fused_mlp or fused_shape or fused_ln
                 else "rollout_policy")
         method = getattr(env, name + "_limited" if limited else name)
         rollout = ((lambda n, *a, **k: method(n, agent.max_iters, agent.step, *a, **k)) if projecting
