@@ -594,7 +594,8 @@ int nig_bf16_from_f32(const float *x, uint16_t *out, int64_t n);
  *   "512x512"      two hidden layers, both <= 512                        16, 16 tiles
  *   "256x256x256"  three hidden layers, all <= 256                       8, 8, 8 tiles
  * More than three hidden layers and a width above 512 are outside every class; a LayerNorm actor of hidden widths (256, 256) has a
- * kernel family of its own ("nig-mlp-ln-v1", nig_set_mlp_policy_ln below), any other LayerNorm network stays on the host.
+ * kernel family of its own ("nig-mlp-ln-v1", nig_set_mlp_policy_ln below) and so has its shield beside a LayerNorm critic
+ * ("nig-mlp-ln-shield-v1", nig_set_mlp_safety_ln), any other LayerNorm network stays on the host.
  *
  * The law, for one lane and one step on state s[0..S) and the PADDED network (the arithmetic of the padded network is the law):
  *   layer 1   z_u = the float32 fma chain over k = 0 .. S-1 in natural order, from 0: c = fma(W1[k][u], s_k, c), two inputs per MFMA
@@ -640,9 +641,10 @@ int nig_get_mlp_policy_dims(const nig_handle *h, int32_t *hidden /* [3] */);
  * nig_set_mlp_policy_dims replace the LayerNorm actor and it replaces theirs; the critic, ensemble, bf16 and limits slots are
  * untouched.  nig_get_mlp_policy_dims reports 2 and 256, 256.  Refusals, before anything is written: NIG_ERR_INVALID for a NULL
  * pointer and for an eps that is not finite and positive; NIG_ERR_UNSUPPORTED for hidden != 256 and for an env shape without the
- * MFMA actor.  While a LayerNorm actor is installed nig_rollout_mlp runs it, and every other entry point that reads the actor slot
- * (nig_rollout_mlp_safe, _search, _gated, _projected, _disturbed and every _limited twin, nig_rollout_mlp_limited included)
- * returns NIG_ERR_UNSUPPORTED with nothing launched or written: the shaped actor's rule.
+ * MFMA actor.  While a LayerNorm actor is installed nig_rollout_mlp runs it, nig_rollout_mlp_safe runs it beside a LayerNorm critic
+ * ("nig-mlp-ln-shield-v1", nig_set_mlp_safety_ln below), and every other entry point that reads the actor slot (nig_rollout_mlp_safe
+ * beside any other critic, _search, _gated, _projected, _disturbed and every _limited twin, nig_rollout_mlp_limited and
+ * nig_rollout_mlp_safe_limited included) returns NIG_ERR_UNSUPPORTED with nothing launched or written: the shaped actor's rule.
  * nig_get_mlp_policy_norm: 1 while the actor slot holds a LayerNorm actor, 0 otherwise; -1 for NULL.
  */
 int nig_set_mlp_policy_ln(nig_handle *h, int32_t hidden, const float *W1, const float *b1, const float *g1, const float *be1,
@@ -802,6 +804,43 @@ int nig_set_mlp_safety_categorical(nig_handle *h, int32_t hidden, int32_t atoms,
                                    uint64_t below_mask, float threshold, void *stream);
 int nig_get_mlp_safety_kind(const nig_handle *h);
 int nig_get_mlp_safety_atoms(const nig_handle *h);
+
+/*
+ * The safety critic with LayerNorm and the fused shield of a LayerNorm agent: agents/networks.py SafetyCritic built with
+ * use_layer_norm=True, (S + A) -> 256 -> LayerNorm -> ReLU -> 256 -> LayerNorm -> ReLU -> 1, played by agents/cql.py
+ * predict_with_safety beside a LayerNorm actor.  The law "nig-mlp-ln-shield-v1" (stated in csrc/nig_mlp_ln_shield.hpp, restated
+ * here).  For one live lane and one step on state s:
+ *   a     = actor(s): "nig-mlp-ln-v1" bit for bit, the action nig_rollout_mlp computes with the same LayerNorm actor.
+ *   x     = [s_0 .. s_{S-1}, a_0 .. a_{A-1}, 0 ..], zero-padded to the critic's layer-1 width (S + A rounded up to even).
+ *   pre   = the head pre-activation of the critic under "nig-mlp-ln-v1" with IN = S + A, OUT = 1 and the critic's own eps: layer 1
+ *           the fma chain in natural k order on x, the mean, two-pass variance, det_rsqrtf and fma(d, rs * gamma, beta) of that
+ *           law on both layers, the head the one-row case of the four-row head (each lane half's fma chain over the hidden rows
+ *           it holds, the bias as one more k-step of B = 1 / 0, then the one joining add).
+ *   p     = det_sigmoidf(pre);  shield = !(p < threshold).
+ *   The env receives a_j * 0.5f where shield and a_j otherwise, and steps on it exactly as nig_step does.
+ * Outputs are nig_rollout_mlp_safe's: prob_out gets p, act_out the action the env received, NIG_FLAG_SHIELDED is set on shielded
+ * live lanes; a frozen lane writes the INACTIVE flag word and a zero reward and leaves its obs / act / prob words untouched.
+ * Non-finite inputs are outside the law.
+ *
+ * nig_set_mlp_safety_ln installs the critic: nig_set_mlp_safety's arrays plus g1 / be1 and g2 / be2 [256], the scale and bias of
+ * the two LayerNorms, eps (flax's default: 1e-6) and the threshold, all host pointers.  It fills the ONE critic slot with the kind
+ * NIG_SAFETY_SIGMOID_LN: nig_set_mlp_safety, nig_set_mlp_safety_categorical and this call replace each other (threshold included);
+ * installing any actor keeps the critic.  Refusals, with nothing changed: NIG_ERR_INVALID for a NULL pointer and for an eps that
+ * is not finite and positive (the threshold is taken as nig_set_mlp_safety takes it); NIG_ERR_UNSUPPORTED for hidden != 256 and
+ * for an env shape without the MFMA actor.  A HIP failure while the weights are copied leaves the slot empty (kind none).
+ *
+ * nig_rollout_mlp_safe keeps its prototype and dispatches on both slots: a LayerNorm actor AND a LayerNorm critic run this law; a
+ * LayerNorm actor beside any other critic is refused as before (NIG_ERR_UNSUPPORTED), and without a critic NIG_ERR_INVALID; a
+ * plain, shaped or bf16 actor beside the LayerNorm critic is NIG_ERR_UNSUPPORTED ("... LayerNorm critic ...").  While the
+ * LayerNorm critic is installed every other reader of the critic slot refuses the same way, with nothing launched or written:
+ * nig_rollout_mlp_search, nig_mlp_violation_prob and every _limited twin, nig_rollout_mlp_safe_limited included.
+ * Out of scope: the _limited, search, categorical, gate, projection and disturbed forms on LayerNorm networks, and LayerNorm
+ * networks of other shapes -- they stay on the host.
+ */
+#define NIG_SAFETY_SIGMOID_LN  3
+int nig_set_mlp_safety_ln(nig_handle *h, int32_t hidden, const float *C1, const float *c1, const float *g1, const float *be1,
+                          const float *C2, const float *c2, const float *g2, const float *be2, const float *C3, const float *c3,
+                          float eps, float threshold, void *stream);
 
 /*
  * compute_safety_violation_probability over a batch: p of "nig-categorical-v1" (and, optionally, the logits) of n

@@ -641,9 +641,35 @@ class BatchedIndustrialEnv:
             _lib.check(self._L.nig_set_mlp_safety_categorical(self._h, Hd, atoms, *[w.ctypes.data_as(C.c_void_p) for w in W],
                                                               int(below_mask), float(threshold), self._stream()))
 
+    def set_mlp_safety_ln(self, critic, threshold: float, eps=None):
+        """Install a LayerNorm safety critic ((S+A)->256->LayerNorm->ReLU->256->LayerNorm->ReLU->1, sigmoid: agents/networks.py
+        SafetyCritic with use_layer_norm=True) in the handle's ONE critic slot, in place of set_mlp_safety()'s and
+        set_mlp_safety_categorical()'s.  `critic`: a policies.LayerNormMLPPolicy with a safety critic (its safety_weights,
+        safety_norms and safety_eps), or a pair (weights, norms) laid out as the actor's of set_mlp_policy_ln(); eps: flax's epsilon
+        (default: the policy's, 1e-6 for a pair).  Beside a LayerNorm actor rollout_mlp_safe() then runs the law
+        "nig-mlp-ln-shield-v1" (csrc/nig_mlp_ln_shield.hpp): the action is halved unless p < threshold.  While it is installed,
+        every other reader of the critic slot (search, violation_prob, the _limited twins) refuses with code 4."""
+        if hasattr(critic, "safety_weights"):
+            if critic.safety_weights is None:
+                raise RuntimeError("Safety critic must be trained")
+            weights, norms = critic.safety_weights, critic.safety_norms
+            eps = critic.safety_eps if eps is None else eps
+        else:
+            weights, norms = critic
+        eps = 1e-6 if eps is None else eps
+        D, Hd = self.state_dim + self.action_dim, 256
+        W = _mlp_weights(weights, [(D, Hd), (Hd,), (Hd, Hd), (Hd,), (Hd, 1), (1,)])
+        G = [np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1)) for pair in norms for x in pair]
+        assert len(G) == 4 and all(g.shape == (256,) for g in G), [g.shape for g in G]
+        P = lambda a: a.ctypes.data_as(C.c_void_p)
+        with torch.cuda.device(self._dev_index):
+            _lib.check(self._L.nig_set_mlp_safety_ln(self._h, Hd, P(W[0]), P(W[1]), P(G[0]), P(G[1]), P(W[2]), P(W[3]), P(G[2]), P(G[3]),
+                                                     P(W[4]), P(W[5]), float(eps), float(threshold), self._stream()))
+
     @property
     def mlp_safety_kind(self) -> int:
-        """What the critic slot holds: 0 none, 1 the sigmoid critic (set_mlp_safety), 2 the categorical one."""
+        """What the critic slot holds: 0 none, 1 the sigmoid critic (set_mlp_safety), 2 the categorical one, 3 the LayerNorm
+        critic (set_mlp_safety_ln)."""
         return int(self._L.nig_get_mlp_safety_kind(self._h))
 
     def violation_prob(self, obs, act, prob_out=None, logits_out=None, layout: str = "rows"):

@@ -188,6 +188,8 @@ struct nig_handle {
     // the ONE critic slot's kind (NIG_SAFETY_*): mlp_cstream holds the sigmoid critic's image (nig_set_mlp_safety) or the categorical
     // critic's (nig_set_mlp_safety_categorical), whose head rows 16 .. 63 lie in mlp_ctail (owned, MLP_TAIL_FLOATS floats)
     int mlp_ckind = NIG_SAFETY_NONE; float *mlp_ctail = nullptr; int cat_atoms = 0; uint64_t cat_mask = 0;
+    // NIG_SAFETY_SIGMOID_LN ("nig-mlp-ln-shield-v1", nig_set_mlp_safety_ln): the LayerNorm critic's image (owned) and its eps
+    float *mlp_cln_stream = nullptr; float cln_eps = 0.0f;
     // nig_set_mlp_ensemble (owned): the members' operand streams back to back, MLP_STREAM_FLOATS floats each; their active weights
     // nig_set_mlp_safety_ensemble: the gate's member streams (owned), MLP_CSTREAM_FLOATS apart, and its law's parameters
     float *gate_stream = nullptr; int gate_members = 0, gate_cap = 0, gate_outputs = 0; float gate_T = 1.0f, gate_thr = 0.0f, gate_umax = 0.0f;
@@ -479,6 +481,7 @@ static PolicyArgs &shared_args(PolicyLimArgs &q) { return q.p; }
 static MlpArgs &shared_args(MlpSearchArgs &q) { return q.sh.m; }
 static MlpArgs &shared_args(MlpCatShieldArgs &q) { return q.sh.m; }
 static MlpArgs &shared_args(MlpCatSearchArgs &q) { return q.sr.sh.m; }
+static MlpArgs &shared_args(MlpLnShieldArgs &q) { return q.a.m; }
 template <class Args> static MlpArgs &shared_args(Args &q) { return q.m; }      // MlpShieldArgs, MlpEnsArgs, MlpDistArgs, MlpGateArgs, MlpProjectArgs, MlpBf16Args, MlpLimArgs
 static PolicyArgs &shared_args(PolicyDistLimArgs &q) { return q.p; }
 template <class Parent> static MlpArgs &shared_args(MlpLimited<Parent> &q) { return shared_args(q.a); }      // a _limited twin: its parent's
@@ -546,9 +549,16 @@ static int need_actor(const nig_handle *h, const char *fn)       // (an env with
     return h->actor_kind == SHAPE_KIND_REFERENCE ? NIG_OK : refuse(fn, "no actor installed (nig_set_mlp_policy)");
 }
 static int need_policy(const nig_handle *h, const char *fn) { return h->has_policy ? NIG_OK : refuse(fn, "no policy installed (nig_set_policy)"); }
+static bool ln_critic(const nig_handle *h) { return h->mlp_ckind == NIG_SAFETY_SIGMOID_LN; }
 static int need_critic(const nig_handle *h, const char *fn)
 {
-    return h->mlp_cstream && h->mlp_ckind != NIG_SAFETY_NONE ? NIG_OK : refuse(fn, "no safety critic installed (nig_set_mlp_safety)");
+    const float *image = ln_critic(h) ? h->mlp_cln_stream : h->mlp_cstream;
+    return image && h->mlp_ckind != NIG_SAFETY_NONE ? NIG_OK : refuse(fn, "no safety critic installed (nig_set_mlp_safety)");
+}
+// the readers of the critic slot that run the plain critics only ask this right after refuse_shaped ("nig-mlp-ln-shield-v1")
+static int refuse_ln_critic(const nig_handle *h, const char *fn)
+{
+    return ln_critic(h) ? refuse(fn, "a LayerNorm critic is installed (nig_set_mlp_safety_ln): this entry point runs it beside a LayerNorm actor in nig_rollout_mlp_safe only", NIG_ERR_UNSUPPORTED) : NIG_OK;
 }
 // the per-constraint rows of the gate and the projection: [n_outputs][ld_c] blocks, c_step_stride apart
 static int check_constraint_rows(const nig_handle *h, const char *fn, int n_outputs, int64_t ld_c, int64_t c_step_stride)
@@ -626,11 +636,27 @@ static int rollout_mlp(nig_handle *h, const char *fn, int32_t n_steps, const Clo
                                      [&](MlpArgs &q) { q.wstream = h->mlp_stream; });
 }
 
+// nig_rollout_mlp_safe with a LayerNorm actor and a LayerNorm critic (or none) in the slots: "nig-mlp-ln-shield-v1"
+static int rollout_mlp_safe_ln(nig_handle *h, const char *fn, int32_t n_steps, const ClosedLoopOut &o, float *prob_out, void *stream)
+{
+    NIG_TRY(refuse_limited(h, fn));
+    NIG_TRY(need_mfma_actor(h, fn));
+    NIG_TRY(need_critic(h, fn));
+    return closed_loop<false, MlpLnShieldArgs>(h, fn, n_steps, o, stream, launch_of(h->env)->mlp_ln_shield, [&](MlpLnShieldArgs &q) {
+        q.a.m.wstream = h->mlp_ln_stream; q.a.eps = h->ln_eps;
+        q.cstream = h->mlp_cln_stream; q.ceps = h->cln_eps; q.prob_out = prob_out; q.threshold = h->mlp_threshold;
+    });
+}
+
 template <bool LIM>
 static int rollout_mlp_safe(nig_handle *h, const char *fn, int32_t n_steps, const ClosedLoopOut &o, float *prob_out, void *stream)
 {
     if (!h || n_steps <= 0) return refuse(fn, "bad argument");
+    // (a LayerNorm actor beside any other critic keeps the shaped actor's refusal, below)
+    if (!LIM && h->actor_kind == ACTOR_KIND_LN && (ln_critic(h) || h->mlp_ckind == NIG_SAFETY_NONE))
+        return rollout_mlp_safe_ln(h, fn, n_steps, o, prob_out, stream);
     NIG_TRY(refuse_shaped(h, fn));
+    NIG_TRY(refuse_ln_critic(h, fn));
     NIG_TRY(limits_gate<LIM>(h, fn));
     NIG_TRY(need_mfma_actor(h, fn));
     NIG_TRY(need_actor(h, fn));
@@ -649,6 +675,7 @@ static int rollout_mlp_search(nig_handle *h, const char *fn, int32_t n_steps, in
 {
     if (!h || n_steps <= 0) return refuse(fn, "bad argument");
     NIG_TRY(refuse_shaped(h, fn));
+    NIG_TRY(refuse_ln_critic(h, fn));
     NIG_TRY(limits_gate<LIM>(h, fn));
     NIG_TRY(need_mfma_actor(h, fn));
     if (n_candidates < 1 || n_candidates > NIG_MAX_CANDIDATES) return refuse(fn, "n_candidates outside 1 .. NIG_MAX_CANDIDATES");
@@ -983,6 +1010,7 @@ int nig_destroy(nig_handle *h)
     if (h->mlp_stream) (void)hipFree(h->mlp_stream);
     if (h->mlp_shape_stream) (void)hipFree(h->mlp_shape_stream);
     if (h->mlp_ln_stream) (void)hipFree(h->mlp_ln_stream);
+    if (h->mlp_cln_stream) (void)hipFree(h->mlp_cln_stream);
     if (h->mlp_bf16_stream) (void)hipFree(h->mlp_bf16_stream);
     if (h->mlp_cstream) (void)hipFree(h->mlp_cstream);
     if (h->mlp_ctail) (void)hipFree(h->mlp_ctail);
@@ -1597,6 +1625,34 @@ int nig_set_mlp_safety_categorical(nig_handle *h, int32_t hidden, int32_t atoms,
     return NIG_OK;
 }
 
+// ---- the LayerNorm safety critic ("nig-mlp-ln-shield-v1", csrc/nig_mlp_ln_shield.hpp) ----
+int nig_set_mlp_safety_ln(nig_handle *h, int32_t hidden, const float *C1, const float *c1, const float *g1, const float *be1,
+                          const float *C2, const float *c2, const float *g2, const float *be2, const float *C3, const float *c3,
+                          float eps, float threshold, void *stream)
+{
+    const char *fn = "nig_set_mlp_safety_ln";
+    if (!h || !C1 || !c1 || !g1 || !be1 || !C2 || !c2 || !g2 || !be2 || !C3 || !c3) return refuse(fn, "NULL argument");
+    if (!(eps > 0.0f) || !(eps < __builtin_inff())) return refuse(fn, "eps must be finite and positive");
+    if (hidden != MLP_H) return refuse(fn, "hidden must be 256: the LayerNorm critic has hidden widths (256, 256)", NIG_ERR_UNSUPPORTED);
+    if (!launch_of(h->env)->mlp_ln_shield) return refuse(fn, "env shape not supported (even state dim, at most 16 actions)", NIG_ERR_UNSUPPORTED);
+    const int S = SPECS[h->env].state_dim, A = SPECS[h->env].action_dim;
+    // (the slot's device image has room for either layer-1 form: it is allocated once and reused)
+    const size_t floats = LN_STREAM_MAX_FLOATS;
+    float *host = (float *)calloc(floats, sizeof(float));
+    if (!host) return refuse(fn, "out of host memory");
+    if (!put_ln_network(S + A, 1, C1, c1, g1, be1, C2, c2, g2, be2, C3, c3, host, floats)) {
+        free(host);
+        return refuse(fn, "the operand image does not fit its chunk plan");
+    }
+    // (the upload overwrites the image an installed LayerNorm critic may be using: after a HIP failure the slot holds no critic)
+    const int rc = upload_stream(fn, &h->mlp_cln_stream, host, floats, stream);
+    if (rc) { if (ln_critic(h)) h->mlp_ckind = NIG_SAFETY_NONE; return rc; }
+    h->mlp_threshold = threshold;
+    h->cln_eps = eps;
+    h->mlp_ckind = NIG_SAFETY_SIGMOID_LN;
+    return NIG_OK;
+}
+
 int nig_get_mlp_safety_kind(const nig_handle *h) { return h ? h->mlp_ckind : -1; }
 int nig_get_mlp_safety_atoms(const nig_handle *h) { return h ? (h->mlp_ckind == NIG_SAFETY_CATEGORICAL ? h->cat_atoms : 0) : -1; }
 
@@ -1605,6 +1661,7 @@ int nig_mlp_violation_prob(nig_handle *h, int64_t n, const float *obs, int64_t l
 {
     const char *const fn = "nig_mlp_violation_prob";
     if (!h || !obs || !act || !prob_out) return refuse(fn, "NULL argument");
+    NIG_TRY(refuse_ln_critic(h, fn));
     if (!categorical(h) || !h->mlp_cstream || !h->mlp_ctail) return refuse(fn, "no categorical critic installed (nig_set_mlp_safety_categorical)");
     if (n < 1) return refuse(fn, "n < 1");
     if (ld_obs < n || ld_obs > NIG_MAX_PITCH || ld_act < n || ld_act > NIG_MAX_PITCH) return refuse(fn, "ld_obs / ld_act outside [n, 2^26]");

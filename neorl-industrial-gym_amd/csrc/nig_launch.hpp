@@ -1,7 +1,7 @@
 // nig_launch.hpp -- the host side of libnig.so's kernels: the list of environments and the per-environment launch table.  An
 // env_<key>.hip instantiates the env's kernels by defining its table (NIG_DEFINE_ENV_LAUNCH); nig_api.hip reaches them through the
 // table's function pointers only.  The launchers of the kernel families with translation units of their own (sampled_, ensemble_,
-// disturbed_, search_, gated_, projected_, bf16_, categorical_, shape*_, ln_, limited_, limited_<family>_<key>.hip) are DECLARED here and defined in
+// disturbed_, search_, gated_, projected_, bf16_, categorical_, shape*_, ln_, ln_shield_, limited_, limited_<family>_<key>.hip) are DECLARED here and defined in
 // nig_launch_families.hpp, which those units alone include: one function template per kind of family, keyed by the argument-block
 // type, so that a family and its _limited twin are two instantiations of one launcher and two neighbouring slots of the table.
 // Which kernel form a rollout launch takes is decided in nig_launch_plan.hpp; the functions here run its plans.
@@ -89,6 +89,8 @@ struct EnvLaunch {
     void (*mlp_shape3)(const MlpShapeArgs<Shape3> &, unsigned grid, hipStream_t);
     // ln_<key>.hip ("nig-mlp-ln-v1"): what nig_rollout_mlp launches when the slot holds a LayerNorm actor
     void (*mlp_ln)(const MlpLnArgs &, unsigned grid, hipStream_t);
+    // ln_shield_<key>.hip ("nig-mlp-ln-shield-v1"): what nig_rollout_mlp_safe launches when both slots hold LayerNorm networks
+    void (*mlp_ln_shield)(const MlpLnShieldArgs &, unsigned grid, hipStream_t);
 };
 
 template <class Env>
@@ -120,6 +122,7 @@ template <class Env> constexpr auto mlp_kernel(const MlpLimited<MlpCatSearchArgs
 template <class Env> constexpr auto mlp_kernel(const MlpCatEvalArgs &) { return mlp_violation_prob_kernel<Env>; }
 template <class Env, class Shape> constexpr auto mlp_kernel(const MlpShapeArgs<Shape> &) { return rollout_mlp_shape_kernel<Env, Shape>; }
 template <class Env> constexpr auto mlp_kernel(const MlpLnArgs &) { return rollout_mlp_ln_kernel<Env>; }
+template <class Env> constexpr auto mlp_kernel(const MlpLnShieldArgs &) { return rollout_mlp_ln_shield_kernel<Env>; }
 
 template <class Env, class Args>
 static void launch_mlp(const Args &q, unsigned grid, hipStream_t st)
@@ -341,6 +344,7 @@ static const EnvLaunch *env_launch_table()
         t.mlp_cat_search = mlp_slot<Env>(launch_mlp_family<Env, MlpCatSearchArgs>);
         t.mlp_cat_eval = mlp_slot<Env>(launch_mlp_family<Env, MlpCatEvalArgs>);
         t.mlp_ln = mlp_slot<Env>(launch_mlp_family<Env, MlpLnArgs>);
+        t.mlp_ln_shield = mlp_slot<Env>(launch_mlp_family<Env, MlpLnShieldArgs>);
         if constexpr (has_mlp_actor<Env>) {           // (the shape units exist for the envs with the actor alone)
             t.mlp_shape128 = launch_mlp_family<Env, MlpShapeArgs<Shape128>>;
             t.mlp_shape512x256 = launch_mlp_family<Env, MlpShapeArgs<Shape512x256>>;

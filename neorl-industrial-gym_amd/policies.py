@@ -655,11 +655,18 @@ class LayerNormMLPPolicy:
     without added constraints and without recorded draws, evaluate_with_safety / evaluate_episodes install it with
     env.set_mlp_policy_ln and play it inside the env kernel (rollout_mlp, the law "nig-mlp-ln-v1": csrc/nig_mlp_ln.hpp).
     `predict` / `predict_device` are the torch host form of the same formula -- two-pass variance, 1 / sqrt(var + eps) -- in torch's
-    arithmetic, not the law's bits: the route on WaterTreatment and under added constraints."""
+    arithmetic, not the law's bits: the route on WaterTreatment and under added constraints.
+
+    With `safety_weights` = [(C1 [S+A,256], c1), (C2 [256,256], c2), (C3 [256,1], c3)] and `safety_norms` (the critic's two
+    LayerNorms; `safety_eps`: its epsilon, default `eps`) the policy also carries the agent's LayerNorm safety critic
+    (agents/networks.py SafetyCritic with use_layer_norm=True) and `constraint_threshold` (base.py: 0.1): predict_with_safety()
+    follows agents/cql.py:354-394, and shielded() is the policy evaluate_with_safety / evaluate_episodes play inside the env kernel
+    (set_mlp_policy_ln + set_mlp_safety_ln + rollout_mlp_safe, the law "nig-mlp-ln-shield-v1": csrc/nig_mlp_ln_shield.hpp)."""
     is_trained = True
     normalization = "layer_norm"
 
-    def __init__(self, weights, norms, eps: float = 1e-6, device="cuda:0"):
+    def __init__(self, weights, norms, eps: float = 1e-6, device="cuda:0", safety_weights=None, safety_norms=None, safety_eps=None,
+                 constraint_threshold: float = 0.1):
         import torch
         self.device = torch.device(device)
         self.weights = [(np.asarray(W, dtype=f32), np.asarray(b, dtype=f32).reshape(-1)) for W, b in weights]
@@ -682,40 +689,111 @@ class LayerNormMLPPolicy:
         self.layers = [(T(W), T(b)) for W, b in self.weights]
         self.norm_layers = [(T(g), T(b)) for g, b in self.norms]
         self.fusable = True          # the shape "nig-mlp-ln-v1" covers: the constructor refuses every other
+        self.constraint_threshold = float(constraint_threshold)
+        self.safety_weights = self.safety_norms = self.safety_layers = self.safety_norm_layers = None
+        self.safety_eps = self.eps if safety_eps is None else float(safety_eps)
+        if (safety_weights is None) != (safety_norms is None):
+            raise ValueError("a LayerNorm safety critic needs both safety_weights and safety_norms")
+        if safety_weights is not None:
+            sw = [(np.asarray(W, dtype=f32), np.asarray(b, dtype=f32).reshape(-1)) for W, b in safety_weights]
+            sn = [(np.asarray(g, dtype=f32).reshape(-1), np.asarray(b, dtype=f32).reshape(-1)) for g, b in safety_norms]
+            if len(sw) != 3 or len(sn) != 2:
+                raise ValueError(f"a LayerNorm safety critic has three Dense layers and two LayerNorms, got {len(sw)} and {len(sn)}")
+            sw[2] = (sw[2][0].reshape(sw[1][0].shape[-1], -1), sw[2][1])
+            (C1, c1), (C2, c2), (C3, c3) = sw
+            D = self.state_dim + self.action_dim
+            if C1.shape != (D, 256) or C2.shape != (256, 256) or C3.shape != (256, 1) or c1.shape != (256,) or c2.shape != (256,) \
+                    or c3.shape != (1,) or any(g.shape != (256,) or b.shape != (256,) for g, b in sn):
+                raise ValueError(f"a LayerNorm safety critic is ({D}, 256), (256, 256), (256, 1) with two LayerNorms of 256, got "
+                                 f"{[W.shape for W, _ in sw]}, norms {[g.shape for g, _ in sn]}")
+            if not (np.isfinite(self.safety_eps) and self.safety_eps > 0):
+                raise ValueError(f"safety_eps must be finite and positive, got {safety_eps}")
+            self.safety_weights, self.safety_norms = sw, sn
+            self.safety_layers = [(T(W), T(b)) for W, b in sw]
+            self.safety_norm_layers = [(T(g), T(b)) for g, b in sn]
 
     @classmethod
     def from_agent(cls, agent, device="cuda:0", eps: float = 1e-6):
         """The actor of a reference agent trained with use_layer_norm=True: agent.state["actor"].params, a Flax tree
         {"params": {"MLP_0": {"Dense_0|1|2": {"kernel", "bias"}, "LayerNorm_0|1": {"scale", "bias"}}}} (any nested mapping of
-        array-likes).  Both hidden layers must carry a LayerNorm with scale and bias; anything else is refused (ValueError)."""
-        t = agent.state["actor"].params
-        while hasattr(t, "items") and not any(str(k).startswith("Dense_") for k in t.keys()):
-            subs = [v for v in t.values() if hasattr(v, "items")]
-            if len(subs) != 1:
-                raise ValueError(f"actor: cannot find the Dense layers of the parameter tree (keys {list(t.keys())})")
-            t = subs[0]
-        if not hasattr(t, "items"):
-            raise ValueError("actor: cannot find the Dense layers of the parameter tree")
-        dense = sorted((k for k in t.keys() if str(k).startswith("Dense_")), key=lambda k: int(str(k)[6:]))
-        norm = sorted((k for k in t.keys() if str(k).startswith("LayerNorm_")), key=lambda k: int(str(k)[10:]))
-        if [str(k) for k in dense] != ["Dense_0", "Dense_1", "Dense_2"] or [str(k) for k in norm] != ["LayerNorm_0", "LayerNorm_1"]:
-            raise ValueError(f"actor: a LayerNorm actor is Dense_0..2 with LayerNorm_0 and LayerNorm_1, got {[str(k) for k in dense + norm]}")
-        for k in norm:
-            if not (hasattr(t[k], "keys") and "scale" in t[k].keys() and "bias" in t[k].keys()):
-                raise ValueError(f"actor: {k} needs both scale and bias (use_scale / use_bias)")
-        return cls([(np.asarray(t[k]["kernel"], dtype=f32), np.asarray(t[k]["bias"], dtype=f32)) for k in dense],
-                   [(np.asarray(t[k]["scale"], dtype=f32), np.asarray(t[k]["bias"], dtype=f32)) for k in norm], eps=eps, device=device)
+        array-likes).  Both hidden layers must carry a LayerNorm with scale and bias; anything else is refused (ValueError).
+        When agent.state has a "safety" entry that is not None, its params -- the same Dense_0..2 / LayerNorm_0..1 tree -- become the
+        policy's safety critic, with agent.constraint_threshold; a safety tree without LayerNorm is a ValueError."""
+        def read(t, what):
+            while hasattr(t, "items") and not any(str(k).startswith("Dense_") for k in t.keys()):
+                subs = [v for v in t.values() if hasattr(v, "items")]
+                if len(subs) != 1:
+                    raise ValueError(f"{what}: cannot find the Dense layers of the parameter tree (keys {list(t.keys())})")
+                t = subs[0]
+            if not hasattr(t, "items"):
+                raise ValueError(f"{what}: cannot find the Dense layers of the parameter tree")
+            dense = sorted((k for k in t.keys() if str(k).startswith("Dense_")), key=lambda k: int(str(k)[6:]))
+            norm = sorted((k for k in t.keys() if str(k).startswith("LayerNorm_")), key=lambda k: int(str(k)[10:]))
+            if [str(k) for k in dense] != ["Dense_0", "Dense_1", "Dense_2"] or [str(k) for k in norm] != ["LayerNorm_0", "LayerNorm_1"]:
+                raise ValueError(f"{what}: a LayerNorm network is Dense_0..2 with LayerNorm_0 and LayerNorm_1, got {[str(k) for k in dense + norm]}")
+            for k in norm:
+                if not (hasattr(t[k], "keys") and "scale" in t[k].keys() and "bias" in t[k].keys()):
+                    raise ValueError(f"{what}: {k} needs both scale and bias (use_scale / use_bias)")
+            return ([(np.asarray(t[k]["kernel"], dtype=f32), np.asarray(t[k]["bias"], dtype=f32)) for k in dense],
+                    [(np.asarray(t[k]["scale"], dtype=f32), np.asarray(t[k]["bias"], dtype=f32)) for k in norm])
+        weights, norms = read(agent.state["actor"].params, "actor")
+        safety = agent.state["safety"] if "safety" in agent.state else None
+        if safety is None:
+            return cls(weights, norms, eps=eps, device=device)
+        sw, sn = read(safety.params, "safety")
+        return cls(weights, norms, eps=eps, device=device, safety_weights=sw, safety_norms=sn,
+                   constraint_threshold=getattr(agent, "constraint_threshold", 0.1))
+
+    @staticmethod
+    def _hidden(x, layers, norm_layers, eps):
+        import torch
+        for (W, b), (g, be) in zip(layers[:2], norm_layers):
+            z = torch.addmm(b, x, W)
+            d = z - z.mean(dim=1, keepdim=True)
+            rs = torch.rsqrt((d * d).mean(dim=1, keepdim=True) + eps)
+            x = torch.relu(d * (rs * g) + be)
+        W, b = layers[2]
+        return torch.addmm(b, x, W)
 
     def predict_device(self, obs):
         import torch
-        x = obs
-        for (W, b), (g, be) in zip(self.layers[:2], self.norm_layers):
-            z = torch.addmm(b, x, W)
-            d = z - z.mean(dim=1, keepdim=True)
-            rs = torch.rsqrt((d * d).mean(dim=1, keepdim=True) + self.eps)
-            x = torch.relu(d * (rs * g) + be)
-        W, b = self.layers[2]
-        return torch.tanh(torch.addmm(b, x, W))
+        return torch.tanh(self._hidden(obs, self.layers, self.norm_layers, self.eps))
+
+    def _threshold(self, safety_threshold):
+        return safety_threshold or self.constraint_threshold           # cql.py:384 (0.0 / None fall back)
+
+    def safety_probs_device(self, obs, actions):
+        """p = sigmoid(critic([obs, actions])), [n]: the LayerNorm critic in torch's arithmetic ("nig-mlp-ln-shield-v1"'s formula,
+        not its bits)."""
+        import torch
+        if self.safety_layers is None:
+            raise RuntimeError("Safety critic must be trained")
+        return torch.sigmoid(self._hidden(torch.cat([obs, actions], dim=1), self.safety_layers, self.safety_norm_layers, self.safety_eps)[:, 0])
+
+    def predict_with_safety_device(self, obs, safety_threshold=None):
+        """predict_with_safety on device tensors: (actions [n, A], probs [n])."""
+        import torch
+        a = self.predict_device(obs)
+        p = self.safety_probs_device(obs, a)
+        return torch.where((p < self._threshold(safety_threshold))[:, None], a, a * 0.5), p
+
+    def predict_with_safety(self, observations, safety_threshold=None):
+        """cql.py:354-394: actions of the deterministic actor, halved where the safety critic's p is not below
+        `safety_threshold or constraint_threshold`; returns (actions, safety_probs) as NumPy arrays."""
+        import torch
+        if self.safety_layers is None:
+            raise RuntimeError("Safety critic must be trained")
+        o = torch.as_tensor(np.asarray(observations, dtype=f32), device=self.device)
+        single = o.dim() == 1
+        a, p = self.predict_with_safety_device(o.reshape(-1, self.state_dim), safety_threshold)
+        a, p = a.cpu().numpy(), p.cpu().numpy()
+        return (a[0], p[0]) if single else (a, p)
+
+    def shielded(self, safety_threshold=None):
+        """The policy that acts with predict_with_safety's actions (for evaluate_with_safety / evaluate_episodes)."""
+        if self.safety_layers is None:
+            raise RuntimeError("Safety critic must be trained")
+        return ShieldedLayerNormPolicy(self, self._threshold(safety_threshold))
 
     def predict(self, observations, deterministic: bool = True):
         import torch
@@ -723,6 +801,26 @@ class LayerNormMLPPolicy:
         single = o.dim() == 1
         out = self.predict_device(o.reshape(-1, self.state_dim)).cpu().numpy()
         return out[0] if single else out
+
+
+class ShieldedLayerNormPolicy:
+    """LayerNormMLPPolicy.shielded(): predict / predict_device give predict_with_safety's actions.  On an env with the MFMA actor,
+    without added constraints and without recorded draws, evaluate_with_safety / evaluate_episodes run it fused into the env kernel
+    (set_mlp_policy_ln + set_mlp_safety_ln + rollout_mlp_safe, "nig-mlp-ln-shield-v1"); otherwise through torch GEMMs."""
+    is_trained = True
+    normalization = "layer_norm"
+
+    def __init__(self, base: LayerNormMLPPolicy, threshold: float):
+        self.base = base
+        self.threshold = float(threshold)
+        self.state_dim, self.action_dim = base.state_dim, base.action_dim
+        self.fusable = bool(base.fusable) and base.safety_weights is not None
+
+    def predict_device(self, obs):
+        return self.base.predict_with_safety_device(obs, self.threshold)[0]
+
+    def predict(self, observations, deterministic: bool = True):
+        return self.base.predict_with_safety(observations, self.threshold)[0]
 
 
 class SearchShieldPolicy:

@@ -174,6 +174,8 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
     # constraints, as on an env without the MFMA actor, it takes the host loop through its predict_device.
     layer_norm = getattr(agent, "normalization", None) == "layer_norm" and not hasattr(agent, "install")
     fused_ln = layer_norm and getattr(agent, "fusable", False) and plain and mfma_env and not limited
+    # LayerNormMLPPolicy.shielded() ("nig-mlp-ln-shield-v1"): the same conditions, actor and critic both installed
+    ln_shielded = fused_ln and hasattr(agent, "base") and hasattr(agent, "threshold")
     fused_mlp = not bf16 and not layer_norm and not hasattr(agent, "install") and getattr(agent, "fusable", False) and plain and (mfma_env or not limited)
     # The other hidden shapes ("nig-mlp-shape-v1"): a plain MLPPolicy -- unshielded, undisturbed, float32 -- whose hidden widths ARE a
     # shaped class's (128x128, 512x256, 512x512, 256x256x256: with (256, 256) the five hidden_dims the reference's tuner builds) goes to
@@ -201,7 +203,7 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
             disturbed = route
             (env.set_policy if route == "fused-policy" else lambda a: env.set_mlp_policy(a.weights))(inner)
             env.set_disturbance(agent.disturbance)
-        device_policy = ensemble = gated = projecting = fused_mlp = fused_bf16 = fused_ln = fused_shape = shielded = searching = False
+        device_policy = ensemble = gated = projecting = fused_mlp = fused_bf16 = fused_ln = ln_shielded = fused_shape = shielded = searching = False
     if disturbed:
         device_policy = True
     elif device_policy:
@@ -213,7 +215,9 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
         env.set_mlp_policy_bf16(agent.weights)
         device_policy = True
     elif fused_ln:
-        env.set_mlp_policy_ln(agent)
+        env.set_mlp_policy_ln(agent.base if ln_shielded else agent)
+        if ln_shielded:
+            env.set_mlp_safety_ln(agent.base, agent.threshold)
         device_policy = True
     elif fused_shape:
         env.set_mlp_policy_dims(agent.weights)
@@ -232,7 +236,7 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
         name = ("rollout_policy_disturbed" if disturbed == "fused-policy" else "rollout_mlp_disturbed" if disturbed
                 else "rollout_mlp_gated" if gated else "rollout_mlp_projected" if projecting else "rollout_mlp_ensemble" if ensemble
                 else "rollout_mlp_bf16" if fused_bf16
-                else "rollout_mlp_search" if searching else "rollout_mlp_safe" if shielded else "rollout_mlp" if fused_mlp or fused_shape or fused_ln
+                else "rollout_mlp_search" if searching else "rollout_mlp_safe" if shielded or ln_shielded else "rollout_mlp" if fused_mlp or fused_shape or fused_ln
                 else "rollout_policy")
         method = getattr(env, name + "_limited" if limited else name)
         rollout = ((lambda n, *a, **k: method(n, agent.max_iters, agent.step, *a, **k)) if projecting
