@@ -843,6 +843,49 @@ int nig_set_mlp_safety_ln(nig_handle *h, int32_t hidden, const float *C1, const 
                           float eps, float threshold, void *stream);
 
 /*
+ * The safety critic of the other hidden shapes and the fused shield of a shaped agent: the reference builds every agent's
+ * SafetyCritic with the actor's own hidden_dims, and agents/cql.py predict_with_safety plays the pair.  The law
+ * "nig-mlp-shape-shield-v1" (stated in csrc/nig_mlp_shape_shield.hpp, restated here).  For one live lane and one step on state s:
+ *   a     = actor(s): "nig-mlp-shape-v1" bit for bit, the action nig_rollout_mlp computes with the same shaped actor of class K.
+ *   x     = [s_0 .. s_{S-1}, a_0 .. a_{A-1}, 0 ..], zero-padded to the critic's layer-1 width (S + A rounded up to even).
+ *   pre   = the head pre-activation of the critic under "nig-mlp-shape-v1" with IN = S + A, OUT = 1, its hidden widths zero-padded
+ *           to the actor's class K: layer 1 the fma chain in natural k order on x, the hidden layers that law's chains, the head
+ *           the one-row case of the 4 x 4 x 1 head on every env (each lane half's fma chain over the hidden rows it holds, the
+ *           bias as one more k-step of B = 1 / 0 behind the last tile, then the one joining add).
+ *   p     = det_sigmoidf(pre);  shield = !(p < threshold).
+ *   The env receives a_j * 0.5f where shield and a_j otherwise, and steps on it exactly as nig_step does.
+ * Outputs are nig_rollout_mlp_safe's: prob_out gets p of the unshielded action, act_out the action the env received,
+ * NIG_FLAG_SHIELDED is set on shielded live lanes; a frozen lane writes the INACTIVE flag word and a zero reward and leaves its
+ * obs / act / prob words untouched; tallies and the launch counter behave as in nig_rollout_mlp_safe.  Non-finite inputs are
+ * outside the law.
+ *
+ * nig_set_mlp_safety_dims installs the critic: n_hidden in 2 .. 3, the unpadded widths hidden[l] in 1 .. 512, and n_hidden + 1
+ * layers C[l] [in][out] row-major with biases c[l] -- the first has S + A rows, the last one column -- all host pointers; the
+ * threshold is taken as nig_set_mlp_safety takes it.  The class is the cheapest that holds the widths at S + A (rounded up to
+ * even) inputs.  A shaped class fills the ONE critic slot with the kind NIG_SAFETY_SIGMOID_SHAPED; the reference class is padded
+ * to 256 x 256 on the host and fills it exactly as nig_set_mlp_safety does on the padded arrays (kind NIG_SAFETY_SIGMOID, the
+ * same image bit for bit).  The four critic installs replace each other (threshold included); installing any actor keeps the
+ * critic.  Refusals, with nothing changed: NIG_ERR_INVALID for a NULL pointer, n_hidden outside 2 .. 3, a width outside 1 .. 512
+ * and widths no class holds; NIG_ERR_UNSUPPORTED for an env shape without the MFMA actor.  A HIP failure while the weights are
+ * copied leaves the slot empty (kind none).
+ * nig_get_mlp_safety_dims mirrors nig_get_mlp_policy_dims: the installed critic's n_hidden, its unpadded widths into hidden[3]
+ * (may be NULL); 0 without a critic; 2 and 256, 256 for the plain, categorical and LayerNorm critics; -1 for a NULL handle.
+ *
+ * nig_rollout_mlp_safe keeps its prototype and dispatches on both slots: a shaped actor of class K AND a shaped critic of the same
+ * class K run this law.  A shaped actor beside a plain, categorical, LayerNorm or absent critic is refused as before
+ * (NIG_ERR_UNSUPPORTED, "... shaped actor ..."); a shaped critic beside a reference, LayerNorm or absent actor, or a shaped actor
+ * of another class, is NIG_ERR_UNSUPPORTED ("... shaped critic ...").  While the shaped critic is installed every other reader of
+ * the critic slot refuses the same way, with nothing launched or written: nig_rollout_mlp_search, nig_mlp_violation_prob and every
+ * _limited twin, nig_rollout_mlp_safe_limited included.
+ * Out of scope: the _limited, search, categorical, gate, projection, ensemble, disturbed and bf16 forms on shaped networks, an
+ * actor and a critic of different classes, and a shaped critic beside the reference actor -- they stay on the host.
+ */
+#define NIG_SAFETY_SIGMOID_SHAPED 4
+int nig_set_mlp_safety_dims(nig_handle *h, int32_t n_hidden, const int32_t *hidden, const float *const *C, const float *const *c,
+                            float threshold, void *stream);
+int nig_get_mlp_safety_dims(const nig_handle *h, int32_t *hidden /*[3]*/);
+
+/*
  * compute_safety_violation_probability over a batch: p of "nig-categorical-v1" (and, optionally, the logits) of n
  * caller-supplied (state, action) columns.  obs float [S][ld_obs], act float [A][ld_act] (device; the action is used as
  * given: the reference does not clip), prob_out float [n], logit_out float [atoms][ld_logit] or NULL (ld_logit is then

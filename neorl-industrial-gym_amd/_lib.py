@@ -25,7 +25,7 @@ FLAG_UNCERTAIN = 0x8000         # nig_rollout_mlp_ensemble: uncertainty > thresh
 MAX_ENSEMBLE = 8
 MAX_PROJECT_ITERS = 16          # nig_rollout_mlp_projected: max_iters 1 .. NIG_MAX_PROJECT_ITERS
 MAX_ATOMS = 64                  # nig_set_mlp_safety_categorical: atoms 2 .. NIG_MAX_ATOMS ("nig-categorical-v1")
-SAFETY_NONE, SAFETY_SIGMOID, SAFETY_CATEGORICAL, SAFETY_SIGMOID_LN = 0, 1, 2, 3       # nig_get_mlp_safety_kind
+SAFETY_NONE, SAFETY_SIGMOID, SAFETY_CATEGORICAL, SAFETY_SIGMOID_LN, SAFETY_SIGMOID_SHAPED = 0, 1, 2, 3, 4       # nig_get_mlp_safety_kind
 MAX_CANDIDATES = 128            # nig_rollout_mlp_search: n_candidates 1 .. NIG_MAX_CANDIDATES
 ENSEMBLE_AVERAGE, ENSEMBLE_VOTING = 0, 1
 CTR_STEP_MASK, CTR_DONE, CTR_VIOL_SHIFT = 0x7FFF, 0x8000, 16
@@ -149,6 +149,8 @@ PROTOTYPES = {
     "nig_set_mlp_safety": (ci, [vp, i32, vp, vp, vp, vp, vp, vp, f32, vp]),
     "nig_set_mlp_safety_categorical": (ci, [vp, i32, i32, vp, vp, vp, vp, vp, vp, u64, f32, vp]),
     "nig_get_mlp_safety_kind": (ci, [vp]),
+    "nig_set_mlp_safety_dims": (ci, [vp, i32, vp, vp, vp, f32, vp]),
+    "nig_get_mlp_safety_dims": (ci, [vp, vp]),
     "nig_set_mlp_safety_ln": (ci, [vp, i32] + [vp] * 10 + [f32, f32, vp]),
     "nig_get_mlp_safety_atoms": (ci, [vp]),
     "nig_mlp_violation_prob": (ci, [vp, i64, vp, i64, vp, i64, vp, vp, i64, vp]),

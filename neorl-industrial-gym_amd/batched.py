@@ -666,10 +666,38 @@ class BatchedIndustrialEnv:
             _lib.check(self._L.nig_set_mlp_safety_ln(self._h, Hd, P(W[0]), P(W[1]), P(G[0]), P(G[1]), P(W[2]), P(W[3]), P(G[2]), P(G[3]),
                                                      P(W[4]), P(W[5]), float(eps), float(threshold), self._stream()))
 
+    def set_mlp_safety_dims(self, weights, threshold: float):
+        """Install a sigmoid safety critic of any hidden shape a shape class holds ("nig-mlp-shape-shield-v1", include/nig.h: two or
+        three ReLU hidden layers of 1 .. 512 units, one output) in the handle's ONE critic slot, in place of the other three critic
+        installs: weights = [(C1 [S+A,h1], c1), .., (C_head [h_last,1], c_head)], host arrays, [in, out], unpadded -- the library
+        pads to the class.  Beside a shaped actor of the same class (set_mlp_policy_dims) rollout_mlp_safe() then runs the fused
+        shield: the action is halved unless p < threshold.  Widths of the reference class fill the slot as set_mlp_safety() does on
+        the zero-padded arrays.  While a shaped critic is installed, every other reader of the critic slot (search, violation_prob,
+        the _limited twins) refuses with code 4."""
+        ws = [(np.ascontiguousarray(W, dtype=np.float32), np.ascontiguousarray(np.asarray(b, dtype=np.float32).reshape(-1))) for W, b in weights]
+        n_hidden = len(ws) - 1
+        D = self.state_dim + self.action_dim
+        ins = [D] + [W.shape[1] for W, _ in ws[:-1]]
+        outs = [W.shape[1] for W, _ in ws[:-1]] + [1]
+        if n_hidden < 1 or any(W.shape != (i, o) or b.shape != (o,) for (W, b), i, o in zip(ws, ins, outs)):
+            raise ValueError(f"critic layers must chain {D} -> .. -> 1, got {[W.shape for W, _ in ws]}")
+        hidden = (C.c_int32 * max(n_hidden, 1))(*outs[:-1])
+        Wp = (C.c_void_p * len(ws))(*[W.ctypes.data for W, _ in ws])
+        bp = (C.c_void_p * len(ws))(*[b.ctypes.data for _, b in ws])
+        with torch.cuda.device(self._dev_index):
+            _lib.check(self._L.nig_set_mlp_safety_dims(self._h, n_hidden, hidden, Wp, bp, float(threshold), self._stream()))
+
+    @property
+    def mlp_safety_dims(self):
+        """The hidden widths of the installed critic (set_mlp_safety, _categorical, _ln: (256, 256)), () without one."""
+        hidden = (C.c_int32 * 3)()
+        n = self._L.nig_get_mlp_safety_dims(self._h, hidden)
+        return tuple(int(hidden[i]) for i in range(max(n, 0)))
+
     @property
     def mlp_safety_kind(self) -> int:
         """What the critic slot holds: 0 none, 1 the sigmoid critic (set_mlp_safety), 2 the categorical one, 3 the LayerNorm
-        critic (set_mlp_safety_ln)."""
+        critic (set_mlp_safety_ln), 4 a shaped sigmoid critic (set_mlp_safety_dims)."""
         return int(self._L.nig_get_mlp_safety_kind(self._h))
 
     def violation_prob(self, obs, act, prob_out=None, logits_out=None, layout: str = "rows"):

@@ -190,6 +190,9 @@ struct nig_handle {
     int mlp_ckind = NIG_SAFETY_NONE; float *mlp_ctail = nullptr; int cat_atoms = 0; uint64_t cat_mask = 0;
     // NIG_SAFETY_SIGMOID_LN ("nig-mlp-ln-shield-v1", nig_set_mlp_safety_ln): the LayerNorm critic's image (owned) and its eps
     float *mlp_cln_stream = nullptr; float cln_eps = 0.0f;
+    // NIG_SAFETY_SIGMOID_SHAPED ("nig-mlp-shape-shield-v1", nig_set_mlp_safety_dims): the shaped critic's image (owned, allocated once
+    // for the env's largest class) and its class (SHAPE_KIND_128 .. SHAPE_KIND_3); critic_dims: the installed critic's unpadded hidden widths
+    float *mlp_cshape_stream = nullptr; int critic_class = SHAPE_KIND_NONE, critic_nh = 0; int32_t critic_dims[3] = {0, 0, 0};
     // nig_set_mlp_ensemble (owned): the members' operand streams back to back, MLP_STREAM_FLOATS floats each; their active weights
     // nig_set_mlp_safety_ensemble: the gate's member streams (owned), MLP_CSTREAM_FLOATS apart, and its law's parameters
     float *gate_stream = nullptr; int gate_members = 0, gate_cap = 0, gate_outputs = 0; float gate_T = 1.0f, gate_thr = 0.0f, gate_umax = 0.0f;
@@ -482,6 +485,7 @@ static MlpArgs &shared_args(MlpSearchArgs &q) { return q.sh.m; }
 static MlpArgs &shared_args(MlpCatShieldArgs &q) { return q.sh.m; }
 static MlpArgs &shared_args(MlpCatSearchArgs &q) { return q.sr.sh.m; }
 static MlpArgs &shared_args(MlpLnShieldArgs &q) { return q.a.m; }
+template <class Shape> static MlpArgs &shared_args(MlpShapeShieldArgs<Shape> &q) { return q.a.m; }
 template <class Args> static MlpArgs &shared_args(Args &q) { return q.m; }      // MlpShieldArgs, MlpEnsArgs, MlpDistArgs, MlpGateArgs, MlpProjectArgs, MlpBf16Args, MlpLimArgs
 static PolicyArgs &shared_args(PolicyDistLimArgs &q) { return q.p; }
 template <class Parent> static MlpArgs &shared_args(MlpLimited<Parent> &q) { return shared_args(q.a); }      // a _limited twin: its parent's
@@ -550,15 +554,21 @@ static int need_actor(const nig_handle *h, const char *fn)       // (an env with
 }
 static int need_policy(const nig_handle *h, const char *fn) { return h->has_policy ? NIG_OK : refuse(fn, "no policy installed (nig_set_policy)"); }
 static bool ln_critic(const nig_handle *h) { return h->mlp_ckind == NIG_SAFETY_SIGMOID_LN; }
+static bool shaped_critic(const nig_handle *h) { return h->mlp_ckind == NIG_SAFETY_SIGMOID_SHAPED; }
 static int need_critic(const nig_handle *h, const char *fn)
 {
-    const float *image = ln_critic(h) ? h->mlp_cln_stream : h->mlp_cstream;
+    const float *image = ln_critic(h) ? h->mlp_cln_stream : shaped_critic(h) ? h->mlp_cshape_stream : h->mlp_cstream;
     return image && h->mlp_ckind != NIG_SAFETY_NONE ? NIG_OK : refuse(fn, "no safety critic installed (nig_set_mlp_safety)");
 }
 // the readers of the critic slot that run the plain critics only ask this right after refuse_shaped ("nig-mlp-ln-shield-v1")
 static int refuse_ln_critic(const nig_handle *h, const char *fn)
 {
     return ln_critic(h) ? refuse(fn, "a LayerNorm critic is installed (nig_set_mlp_safety_ln): this entry point runs it beside a LayerNorm actor in nig_rollout_mlp_safe only", NIG_ERR_UNSUPPORTED) : NIG_OK;
+}
+// and this right after refuse_ln_critic ("nig-mlp-shape-shield-v1"): the same rule for the shaped critic
+static int refuse_shaped_critic(const nig_handle *h, const char *fn)
+{
+    return shaped_critic(h) ? refuse(fn, "a shaped critic is installed (nig_set_mlp_safety_dims): this entry point runs it beside a shaped actor of the same class in nig_rollout_mlp_safe only", NIG_ERR_UNSUPPORTED) : NIG_OK;
 }
 // the per-constraint rows of the gate and the projection: [n_outputs][ld_c] blocks, c_step_stride apart
 static int check_constraint_rows(const nig_handle *h, const char *fn, int n_outputs, int64_t ld_c, int64_t c_step_stride)
@@ -648,6 +658,29 @@ static int rollout_mlp_safe_ln(nig_handle *h, const char *fn, int32_t n_steps, c
     });
 }
 
+// nig_rollout_mlp_safe with a shaped actor and a shaped critic of the same class in the slots: "nig-mlp-shape-shield-v1"
+static int rollout_mlp_safe_shaped(nig_handle *h, const char *fn, int32_t n_steps, const ClosedLoopOut &o, float *prob_out, void *stream)
+{
+    NIG_TRY(refuse_limited(h, fn));
+    NIG_TRY(need_mfma_actor(h, fn));
+    NIG_TRY(need_critic(h, fn));
+    const EnvLaunch *L = launch_of(h->env);
+    auto run = [&](auto launch, auto shape) {
+        using Args = MlpShapeShieldArgs<decltype(shape)>;
+        return closed_loop<false, Args>(h, fn, n_steps, o, stream, launch, [&](Args &q) {
+            q.a.m.wstream = h->mlp_shape_stream;
+            q.cstream = h->mlp_cshape_stream; q.prob_out = prob_out; q.threshold = h->mlp_threshold;
+        });
+    };
+    switch (h->actor_kind) {
+    case SHAPE_KIND_128: return run(L->mlp_shape128_shield, Shape128{});
+    case SHAPE_KIND_512x256: return run(L->mlp_shape512x256_shield, Shape512x256{});
+    case SHAPE_KIND_512: return run(L->mlp_shape512_shield, Shape512{});
+    case SHAPE_KIND_3: return run(L->mlp_shape3_shield, Shape3{});
+    default: return refuse(fn, "no actor installed (nig_set_mlp_policy)");
+    }
+}
+
 template <bool LIM>
 static int rollout_mlp_safe(nig_handle *h, const char *fn, int32_t n_steps, const ClosedLoopOut &o, float *prob_out, void *stream)
 {
@@ -655,6 +688,11 @@ static int rollout_mlp_safe(nig_handle *h, const char *fn, int32_t n_steps, cons
     // (a LayerNorm actor beside any other critic keeps the shaped actor's refusal, below)
     if (!LIM && h->actor_kind == ACTOR_KIND_LN && (ln_critic(h) || h->mlp_ckind == NIG_SAFETY_NONE))
         return rollout_mlp_safe_ln(h, fn, n_steps, o, prob_out, stream);
+    // (a shaped critic beside any actor but a shaped one of its own class is refused by name; a shaped actor beside any other critic
+    // keeps its refusal, below)
+    if (!LIM && shaped_critic(h) && h->actor_kind == h->critic_class)
+        return rollout_mlp_safe_shaped(h, fn, n_steps, o, prob_out, stream);
+    NIG_TRY(refuse_shaped_critic(h, fn));
     NIG_TRY(refuse_shaped(h, fn));
     NIG_TRY(refuse_ln_critic(h, fn));
     NIG_TRY(limits_gate<LIM>(h, fn));
@@ -676,6 +714,7 @@ static int rollout_mlp_search(nig_handle *h, const char *fn, int32_t n_steps, in
     if (!h || n_steps <= 0) return refuse(fn, "bad argument");
     NIG_TRY(refuse_shaped(h, fn));
     NIG_TRY(refuse_ln_critic(h, fn));
+    NIG_TRY(refuse_shaped_critic(h, fn));
     NIG_TRY(limits_gate<LIM>(h, fn));
     NIG_TRY(need_mfma_actor(h, fn));
     if (n_candidates < 1 || n_candidates > NIG_MAX_CANDIDATES) return refuse(fn, "n_candidates outside 1 .. NIG_MAX_CANDIDATES");
@@ -1009,6 +1048,7 @@ int nig_destroy(nig_handle *h)
     if (!h) return NIG_OK;
     if (h->mlp_stream) (void)hipFree(h->mlp_stream);
     if (h->mlp_shape_stream) (void)hipFree(h->mlp_shape_stream);
+    if (h->mlp_cshape_stream) (void)hipFree(h->mlp_cshape_stream);
     if (h->mlp_ln_stream) (void)hipFree(h->mlp_ln_stream);
     if (h->mlp_cln_stream) (void)hipFree(h->mlp_cln_stream);
     if (h->mlp_bf16_stream) (void)hipFree(h->mlp_bf16_stream);
@@ -1584,6 +1624,12 @@ int nig_rollout_mlp_bf16(nig_handle *h, int32_t n_steps, float *reward_out, uint
     });
 }
 
+// what nig_get_mlp_safety_dims reports for the critics of hidden widths (256, 256): the plain, the categorical and the LayerNorm one
+static void critic_dims_256(nig_handle *h)
+{
+    h->critic_class = SHAPE_KIND_REFERENCE; h->critic_nh = 2; h->critic_dims[0] = h->critic_dims[1] = MLP_H; h->critic_dims[2] = 0;
+}
+
 int nig_set_mlp_safety(nig_handle *h, int32_t hidden, const float *C1, const float *c1, const float *C2, const float *c2,
                        const float *C3, const float *c3, float threshold, void *stream)
 {
@@ -1594,6 +1640,7 @@ int nig_set_mlp_safety(nig_handle *h, int32_t hidden, const float *C1, const flo
     NIG_TRY(upload_stream("nig_set_mlp_safety", &h->mlp_cstream, host, MLP_CSTREAM_FLOATS, stream));
     h->mlp_threshold = threshold;
     h->mlp_ckind = NIG_SAFETY_SIGMOID;
+    critic_dims_256(h);
     return NIG_OK;
 }
 
@@ -1622,6 +1669,7 @@ int nig_set_mlp_safety_categorical(nig_handle *h, int32_t hidden, int32_t atoms,
     h->mlp_threshold = threshold;
     h->cat_atoms = atoms; h->cat_mask = below_mask;
     h->mlp_ckind = NIG_SAFETY_CATEGORICAL;
+    critic_dims_256(h);
     return NIG_OK;
 }
 
@@ -1650,7 +1698,73 @@ int nig_set_mlp_safety_ln(nig_handle *h, int32_t hidden, const float *C1, const 
     h->mlp_threshold = threshold;
     h->cln_eps = eps;
     h->mlp_ckind = NIG_SAFETY_SIGMOID_LN;
+    critic_dims_256(h);
     return NIG_OK;
+}
+
+// ---- the safety critic of the other hidden shapes ("nig-mlp-shape-shield-v1", csrc/nig_mlp_shape_shield.hpp) ----
+int nig_set_mlp_safety_dims(nig_handle *h, int32_t n_hidden, const int32_t *hidden, const float *const *C, const float *const *c,
+                            float threshold, void *stream)
+{
+    const char *fn = "nig_set_mlp_safety_dims";
+    if (!h || !hidden || !C || !c) return refuse(fn, "NULL argument");
+    if (n_hidden < 2 || n_hidden > 3) return refuse(fn, "n_hidden outside 2 .. 3");
+    int dims[3] = {0, 0, 0};
+    for (int l = 0; l < n_hidden; ++l) {
+        if (hidden[l] < 1 || hidden[l] > SHAPE_MAX_WIDTH) return refuse(fn, "a hidden width outside 1 .. 512");
+        dims[l] = hidden[l];
+    }
+    for (int l = 0; l <= n_hidden; ++l)
+        if (!C[l] || !c[l]) return refuse(fn, "NULL layer");
+    if (!launch_of(h->env)->mlp) return refuse(fn, "env shape not supported (even state dim, at most 16 actions)", NIG_ERR_UNSUPPORTED);
+    const int IN = SPECS[h->env].state_dim + SPECS[h->env].action_dim;
+    const int kind = shape_class_of(n_hidden, dims, (IN + 1) & ~1);
+    if (kind == SHAPE_KIND_NONE) return refuse(fn, "no shape class holds these hidden widths");
+    auto installed = [&](int ckind) {
+        h->mlp_threshold = threshold;
+        h->mlp_ckind = ckind;
+        h->critic_class = kind; h->critic_nh = n_hidden;
+        for (int l = 0; l < 3; ++l) h->critic_dims[l] = dims[l];
+        return NIG_OK;
+    };
+    if (kind == SHAPE_KIND_REFERENCE) {                     // padded to 256 x 256 on the host: nig_set_mlp_safety's image and kernels
+        float *pad = (float *)calloc(reference_pad_floats(IN, 1), sizeof(float));
+        float *host = (float *)calloc(MLP_CSTREAM_FLOATS, sizeof(float));
+        const bool ok = pad && host && put_reference_padded(IN, 1, dims, C, c, pad, host, MLP_CSTREAM_FLOATS);
+        free(pad);
+        if (!ok) { free(host); return refuse(fn, "out of host memory, or the operand stream does not fit its image"); }
+        NIG_TRY(upload_stream(fn, &h->mlp_cstream, host, MLP_CSTREAM_FLOATS, stream));
+        return installed(NIG_SAFETY_SIGMOID);
+    }
+    size_t cap = 0;                                         // the env's largest shaped image: the slot is allocated once
+    for (int k = SHAPE_KIND_128; k <= SHAPE_KIND_3; ++k) {
+        const size_t f = shape_plan(SHAPE_CLASSES[k], IN).floats();
+        cap = f > cap ? f : cap;
+    }
+    const size_t floats = shape_plan(SHAPE_CLASSES[kind], IN).floats();
+    float *host = (float *)calloc(floats, sizeof(float));
+    if (!host) return refuse(fn, "out of host memory");
+    if (!put_shape_network(SHAPE_CLASSES[kind], IN, 1, n_hidden, dims, C, c, host, floats)) {
+        free(host);
+        return refuse(fn, "the operand image does not fit its chunk plan");
+    }
+    if (!h->mlp_cshape_stream) {
+        const hipError_t e = hipMalloc((void **)&h->mlp_cshape_stream, cap * sizeof(float));
+        if (e != hipSuccess) { h->mlp_cshape_stream = nullptr; free(host); return refuse(fn, hipGetErrorString(e), NIG_ERR_HIP); }
+    }
+    // (the upload overwrites the image an installed shaped critic may be using: after a HIP failure the slot holds no critic)
+    const int rc = upload_stream(fn, &h->mlp_cshape_stream, host, floats, stream);
+    if (rc) { if (shaped_critic(h)) h->mlp_ckind = NIG_SAFETY_NONE; return rc; }
+    return installed(NIG_SAFETY_SIGMOID_SHAPED);
+}
+
+int nig_get_mlp_safety_dims(const nig_handle *h, int32_t *hidden)
+{
+    if (!h) return -1;
+    const int nh = h->mlp_ckind == NIG_SAFETY_NONE ? 0 : h->critic_nh;
+    if (hidden)
+        for (int l = 0; l < 3; ++l) hidden[l] = l < nh ? h->critic_dims[l] : 0;
+    return nh;
 }
 
 int nig_get_mlp_safety_kind(const nig_handle *h) { return h ? h->mlp_ckind : -1; }
@@ -1662,6 +1776,7 @@ int nig_mlp_violation_prob(nig_handle *h, int64_t n, const float *obs, int64_t l
     const char *const fn = "nig_mlp_violation_prob";
     if (!h || !obs || !act || !prob_out) return refuse(fn, "NULL argument");
     NIG_TRY(refuse_ln_critic(h, fn));
+    NIG_TRY(refuse_shaped_critic(h, fn));
     if (!categorical(h) || !h->mlp_cstream || !h->mlp_ctail) return refuse(fn, "no categorical critic installed (nig_set_mlp_safety_categorical)");
     if (n < 1) return refuse(fn, "n < 1");
     if (ld_obs < n || ld_obs > NIG_MAX_PITCH || ld_act < n || ld_act > NIG_MAX_PITCH) return refuse(fn, "ld_obs / ld_act outside [n, 2^26]");

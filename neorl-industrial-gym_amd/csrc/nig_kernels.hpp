@@ -31,6 +31,7 @@
 #include "nig_mlp.hpp"               // the MFMA actor, its shield and its ensemble
 #include "nig_mlp_bf16.hpp"          // the MFMA actor on the bf16 matrix unit ("nig-mlp-bf16-v1")
 #include "nig_mlp_shape.hpp"         // the MFMA actor of the other hidden shapes ("nig-mlp-shape-v1")
+#include "nig_mlp_shape_shield.hpp"  // the shaped actor with its shaped safety-critic shield ("nig-mlp-shape-shield-v1")
 #include "nig_mlp_ln.hpp"            // the MFMA actor with LayerNorm ("nig-mlp-ln-v1")
 #include "nig_mlp_ln_shield.hpp"     // the LayerNorm actor with its LayerNorm safety-critic shield ("nig-mlp-ln-shield-v1")
 #include "nig_episodes.hpp"          // per-episode records from reward / flag rows (env-independent)

@@ -87,6 +87,12 @@ struct EnvLaunch {
     void (*mlp_shape512x256)(const MlpShapeArgs<Shape512x256> &, unsigned grid, hipStream_t);
     void (*mlp_shape512)(const MlpShapeArgs<Shape512> &, unsigned grid, hipStream_t);
     void (*mlp_shape3)(const MlpShapeArgs<Shape3> &, unsigned grid, hipStream_t);
+    // shape128_shield_<key>.hip .. shape3_shield_<key>.hip ("nig-mlp-shape-shield-v1"): what nig_rollout_mlp_safe launches when the
+    // actor slot and the critic slot hold shaped networks of the same class
+    void (*mlp_shape128_shield)(const MlpShapeShieldArgs<Shape128> &, unsigned grid, hipStream_t);
+    void (*mlp_shape512x256_shield)(const MlpShapeShieldArgs<Shape512x256> &, unsigned grid, hipStream_t);
+    void (*mlp_shape512_shield)(const MlpShapeShieldArgs<Shape512> &, unsigned grid, hipStream_t);
+    void (*mlp_shape3_shield)(const MlpShapeShieldArgs<Shape3> &, unsigned grid, hipStream_t);
     // ln_<key>.hip ("nig-mlp-ln-v1"): what nig_rollout_mlp launches when the slot holds a LayerNorm actor
     void (*mlp_ln)(const MlpLnArgs &, unsigned grid, hipStream_t);
     // ln_shield_<key>.hip ("nig-mlp-ln-shield-v1"): what nig_rollout_mlp_safe launches when both slots hold LayerNorm networks
@@ -121,6 +127,7 @@ template <class Env> constexpr auto mlp_kernel(const MlpLimited<MlpCatShieldArgs
 template <class Env> constexpr auto mlp_kernel(const MlpLimited<MlpCatSearchArgs> &) { return rollout_mlp_cat_search_limited_kernel<Env>; }
 template <class Env> constexpr auto mlp_kernel(const MlpCatEvalArgs &) { return mlp_violation_prob_kernel<Env>; }
 template <class Env, class Shape> constexpr auto mlp_kernel(const MlpShapeArgs<Shape> &) { return rollout_mlp_shape_kernel<Env, Shape>; }
+template <class Env, class Shape> constexpr auto mlp_kernel(const MlpShapeShieldArgs<Shape> &) { return rollout_mlp_shape_shield_kernel<Env, Shape>; }
 template <class Env> constexpr auto mlp_kernel(const MlpLnArgs &) { return rollout_mlp_ln_kernel<Env>; }
 template <class Env> constexpr auto mlp_kernel(const MlpLnShieldArgs &) { return rollout_mlp_ln_shield_kernel<Env>; }
 
@@ -350,6 +357,10 @@ static const EnvLaunch *env_launch_table()
             t.mlp_shape512x256 = launch_mlp_family<Env, MlpShapeArgs<Shape512x256>>;
             t.mlp_shape512 = launch_mlp_family<Env, MlpShapeArgs<Shape512>>;
             t.mlp_shape3 = launch_mlp_family<Env, MlpShapeArgs<Shape3>>;
+            t.mlp_shape128_shield = launch_mlp_family<Env, MlpShapeShieldArgs<Shape128>>;
+            t.mlp_shape512x256_shield = launch_mlp_family<Env, MlpShapeShieldArgs<Shape512x256>>;
+            t.mlp_shape512_shield = launch_mlp_family<Env, MlpShapeShieldArgs<Shape512>>;
+            t.mlp_shape3_shield = launch_mlp_family<Env, MlpShapeShieldArgs<Shape3>>;
         }
         if constexpr (!Env::CUSTOM_STEP) {            // the twins: the same lines on the twin's argument block
             t.step_limited = launch_step_limited<Env, false>;

@@ -1,8 +1,8 @@
 // nig_launch_families.hpp -- the definitions of the family launchers nig_launch.hpp declares: the kernels of nig_rollout_sampled,
 // nig_rollout_mlp_ensemble, nig_rollout_policy_disturbed / nig_rollout_mlp_disturbed, nig_rollout_mlp_search, nig_rollout_mlp_gated,
-// nig_rollout_mlp_projected, nig_rollout_mlp_bf16, the shaped and the LayerNorm actor of nig_rollout_mlp, the LayerNorm shield of nig_rollout_mlp_safe, and of every _limited entry point.  A launcher is stated once per kind of family,
+// nig_rollout_mlp_projected, nig_rollout_mlp_bf16, the shaped and the LayerNorm actor of nig_rollout_mlp, the LayerNorm and the shaped shield of nig_rollout_mlp_safe, and of every _limited entry point.  A launcher is stated once per kind of family,
 // on the argument-block type: a family's parent and its _limited twin are two instantiations of it.
-// Included by the family translation units alone (sampled_, ensemble_, disturbed_, search_, gated_, projected_, bf16_, categorical_, shape*_, ln_, ln_shield_, limited_,
+// Included by the family translation units alone (sampled_, ensemble_, disturbed_, search_, gated_, projected_, bf16_, categorical_, shape*_, shape*_shield_, ln_, ln_shield_, limited_,
 // limited_<family>_<key>.hip).  A template that is defined but not instantiated emits nothing: each unit explicitly instantiates the
 // launcher of its own family for its own env (the macros at the end), and with it that family's kernels and no other's.
 #pragma once
@@ -85,6 +85,7 @@ void launch_step_limited(const StepLimArgs &q, bool parity, unsigned grid, hipSt
 #define NIG_DEFINE_ENV_PROJECTED_LIMITED(EnvType) NIG_FAMILY(launch_mlp_family, EnvType, MlpLimited<MlpProjectArgs>)
 #define NIG_DEFINE_ENV_BF16(EnvType) NIG_FAMILY(launch_mlp_family, EnvType, MlpBf16Args)
 #define NIG_DEFINE_ENV_SHAPE(EnvType, Shape) NIG_FAMILY(launch_mlp_family, EnvType, MlpShapeArgs<Shape>)
+#define NIG_DEFINE_ENV_SHAPE_SHIELD(EnvType, Shape) NIG_FAMILY(launch_mlp_family, EnvType, MlpShapeShieldArgs<Shape>)
 #define NIG_DEFINE_ENV_LN(EnvType) NIG_FAMILY(launch_mlp_family, EnvType, MlpLnArgs)
 #define NIG_DEFINE_ENV_LN_SHIELD(EnvType) NIG_FAMILY(launch_mlp_family, EnvType, MlpLnShieldArgs)
 #define NIG_DEFINE_ENV_CATEGORICAL(EnvType) \

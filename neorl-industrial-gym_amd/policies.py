@@ -461,6 +461,11 @@ class MLPPolicy:
                                  f"{[w.shape for w, _ in self.safety_weights]}")
             self.safety_layers = [(torch.as_tensor(W, device=self.device).contiguous(), torch.as_tensor(b, device=self.device).contiguous())
                                   for W, b in self.safety_weights]
+        # the shaped shield ("nig-mlp-shape-shield-v1"): the actor's widths are a shaped class's own and the sigmoid critic has the
+        # same hidden widths, as the reference builds it (SafetyCritic(hidden_dims=self.hidden_dims)) -- what evaluate_with_safety
+        # sends to set_mlp_policy_dims + set_mlp_safety_dims + rollout_mlp_safe by itself
+        self.shape_shield_exact = bool(self.shape_class_exact and self.safety_weights is not None and safety_kind == "sigmoid"
+                                       and tuple(int(W.shape[1]) for W, _ in self.safety_weights[:-1]) == self.hidden_dims)
 
     @classmethod
     def from_agent(cls, agent, device="cuda:0", critic: str = "safety", below_mask=None):
@@ -857,7 +862,8 @@ class SearchShieldPolicy:
 class ShieldedMLPPolicy:
     """MLPPolicy.shielded(): predict / predict_device give predict_with_safety's actions.  When actor and critic
     have the reference shape (hidden 256), evaluate_with_safety runs it fused into the env kernel
-    (BatchedIndustrialEnv.rollout_mlp_safe); otherwise through torch GEMMs."""
+    (BatchedIndustrialEnv.rollout_mlp_safe), and so it does when both have the widths of one shaped class (`shape_shield_exact`:
+    set_mlp_policy_dims + set_mlp_safety_dims, "nig-mlp-shape-shield-v1"); otherwise through torch GEMMs."""
     is_trained = True
 
     def __init__(self, base: MLPPolicy, threshold: float):
@@ -868,6 +874,8 @@ class ShieldedMLPPolicy:
         self.safety_kind, self.below_mask = base.safety_kind, base.below_mask
         sw = base.safety_weights
         self.fusable = base.fusable and len(sw) == 3 and sw[0][0].shape[1] == 256 and sw[1][0].shape == (256, 256)
+        # actor and critic of the same shaped class, unpadded: the fused shaped shield ("nig-mlp-shape-shield-v1")
+        self.shape_shield_exact = type(base) is MLPPolicy and bool(getattr(base, "shape_shield_exact", False))
 
     def predict_device(self, obs):
         return self.base.predict_with_safety_device(obs, self.threshold)[0]

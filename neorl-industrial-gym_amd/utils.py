@@ -136,6 +136,13 @@ def _disturbed_route(agent, env):
     return "host", None
 
 
+# The shape classes whose shielded form _install_agent sends to the fused shaped shield: those whose new kernel is below the host
+# route in every round on both timed envs of profiles/shape_shield/ab.txt (written by profiles/bench_shape_shield.py) -- all four, by
+# 5.9 x / 4.6 x (128x128) down to 1.49 x / 1.46 x (512x512) on ChemicalReactor / PowerGrid ("The shaped shield").
+# A class that a later measurement does not admit is taken out here and keeps the host loop; its C entry point still runs.
+SHAPE_SHIELD_ROUTED = ("128x128", "512x256", "512x512", "256x256x256")
+
+
 def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
     """Where `agent` runs on `env`, and its installation there -- the routing _evaluate_batched and episodes.evaluate_episodes
     share.  Returns (agent, rollout, disturbed): `rollout` is the env method that plays n closed-loop steps with the agent in the
@@ -194,6 +201,16 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
                 cand = agent
         if type(cand) is MLPPolicy and not cand.fusable and cand.shape_class_exact:
             agent, fused_shape = cand, True
+    # The shaped shield ("nig-mlp-shape-shield-v1"): MLPPolicy.shielded() whose actor AND sigmoid critic have the widths of one shaped
+    # class (`shape_shield_exact`: the reference builds the SafetyCritic with the actor's hidden_dims) goes to set_mlp_policy_dims +
+    # set_mlp_safety_dims + rollout_mlp_safe, for the classes of SHAPE_SHIELD_ROUTED.  A critic of other widths than the actor's, a
+    # pair that needs padding, a categorical critic and a raw reference agent keep the routes they had; the family has no _limited
+    # twin: with added constraints the agent takes the host loop.
+    shape_shielded = False
+    if plain and mfma_env and not limited:
+        from .policies import ShieldedMLPPolicy
+        shape_shielded = (type(agent) is ShieldedMLPPolicy and bool(getattr(agent, "shape_shield_exact", False))
+                          and agent.base.shape_class in SHAPE_SHIELD_ROUTED)
     shielded = fused_mlp and getattr(agent, "safety_weights", None) is not None and hasattr(agent, "threshold")
     searching = shielded and hasattr(agent, "n_candidates")       # MLPPolicy.searching(): get_safe_action instead of the halving
     disturbed = None           # a disturbance.Disturbed whose inner agent runs in the env kernel: "fused-policy" / "fused-mlp"
@@ -203,7 +220,7 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
             disturbed = route
             (env.set_policy if route == "fused-policy" else lambda a: env.set_mlp_policy(a.weights))(inner)
             env.set_disturbance(agent.disturbance)
-        device_policy = ensemble = gated = projecting = fused_mlp = fused_bf16 = fused_ln = ln_shielded = fused_shape = shielded = searching = False
+        device_policy = ensemble = gated = projecting = fused_mlp = fused_bf16 = fused_ln = ln_shielded = fused_shape = shape_shielded = shielded = searching = False
     if disturbed:
         device_policy = True
     elif device_policy:
@@ -222,6 +239,10 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
     elif fused_shape:
         env.set_mlp_policy_dims(agent.weights)
         device_policy = True
+    elif shape_shielded:
+        env.set_mlp_policy_dims(agent.weights)
+        env.set_mlp_safety_dims(agent.safety_weights, agent.threshold)
+        device_policy = True
     elif fused_mlp:
         env.set_mlp_policy(agent.weights)
         if shielded:        # MLPPolicy.shielded() / searching(): actor + safety critic + shield in the same kernel
@@ -236,7 +257,7 @@ def _install_agent(agent, env: BatchedIndustrialEnv, plain: bool = True):
         name = ("rollout_policy_disturbed" if disturbed == "fused-policy" else "rollout_mlp_disturbed" if disturbed
                 else "rollout_mlp_gated" if gated else "rollout_mlp_projected" if projecting else "rollout_mlp_ensemble" if ensemble
                 else "rollout_mlp_bf16" if fused_bf16
-                else "rollout_mlp_search" if searching else "rollout_mlp_safe" if shielded or ln_shielded else "rollout_mlp" if fused_mlp or fused_shape or fused_ln
+                else "rollout_mlp_search" if searching else "rollout_mlp_safe" if shielded or ln_shielded or shape_shielded else "rollout_mlp" if fused_mlp or fused_shape or fused_ln
                 else "rollout_policy")
         method = getattr(env, name + "_limited" if limited else name)
         rollout = ((lambda n, *a, **k: method(n, agent.max_iters, agent.step, *a, **k)) if projecting
